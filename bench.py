@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- convex-MPC QP solves/sec on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config C | --workload standing --horizon H] [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--config C | --workload standing --horizon H] [--batch B] [--dump-outputs DIR]
 
 One "step" = one pass of the whole hot path (state -> linearisation -> condensed
 QP -> exact QP solve -> first-step GRF) over one batch of synthetic robot states
@@ -333,6 +333,21 @@ def cpu_baseline_sparse(b, spec, budget_s=8.0, all_cores=True, gpu_grf=None, n_p
         return {"value": None, "error": repr(e)}
 
 
+def dump_outputs(dirname, arrays, limit=64 << 20):
+    """--dump-outputs: every array as dirname/<name>.npy, float32 kept, any other dtype as float64.  Over `limit` bytes in all,
+    the same fraction of every array's rows is written instead, chosen by a fixed seed, with its row indices as <name>_rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: v.astype(np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes + 8 * len(v) for v in arrays.values())
+    room = limit - 2 * 1024 * len(arrays)          # (the .npy headers)
+    for name, v in arrays.items():
+        if total > room:
+            rows = np.sort(np.random.default_rng(0).choice(len(v), int(len(v) * room / total), replace=False))
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+            v = v[rows]
+        np.save(os.path.join(dirname, name + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -384,6 +399,11 @@ def main():
                          "with QMPC_ST_MAXITER -- counters by cap give the cost of ONE iteration as a slope")
     ap.add_argument("--no-hint", action="store_true",
                     help="do not tell the solver the workload's max stance foot-steps (launch every size class)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed regions, write what the last timed step returned (rank 0: grf, status, iters; with "
+                         "--caller-side the body-frame forces grf_body; with --gather the gathered rows) as DIR/<name>.npy, "
+                         "float32 / float64, at most 64 MB in all (beyond that a fixed seeded sample of rows, indices in "
+                         "DIR/<name>_rows.npy); the inputs are the same on every run with the same arguments")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -537,6 +557,14 @@ def main():
     for _ in range(R - 1):
         el, e0, e1 = timed_region()
         regions.append((el, e0.elapsed_time(e1)))   # HIP events on the launch stream
+    # what the last timed step returned, taken before the extra regions below reuse the output buffers
+    last_outputs = None
+    if args.dump_outputs and rank == 0:
+        last_outputs = {"grf": o["grf"].cpu().numpy(), "status": o["status"].cpu().numpy(), "iters": o["iters"].cpu().numpy()}
+        if args.caller_side:
+            last_outputs["grf_body"] = f_ff.cpu().numpy()
+        if gathered is not None:
+            last_outputs["grf_gathered"] = gathered.cpu().numpy()
     local_el = [r[0] for r in regions]
     per_rank = None
     ev_mat = None
@@ -992,6 +1020,8 @@ def main():
                                                                      "robots_over_1e-4", "max_err_over_reference_spread",
                                                                      "worst_checked_within_1.5x_reference_spread", "spread_checked_on",
                                                                      "spread_unchecked", "all_over_1e-4_checked")}
+        if last_outputs is not None:
+            dump_outputs(args.dump_outputs, last_outputs)
         print(json.dumps(res))
     if dist is not None:
         dist.barrier()
