@@ -210,7 +210,7 @@ int qmpc_set_order_hint(qmpc_handle h, int mode);
 
 /* Everything else the library exports lives in two companion headers, so that this one is the surface a caller needs:
  *   include/qmpc_expert.h -- scheduling / memory knobs whose DEFAULT is the measured optimum (qmpc_set_split, qmpc_set_dense,
- *                            qmpc_set_chunks, qmpc_reserve, qmpc_set_block_start) and the warm start across MPC cycles, which is
+ *                            qmpc_set_chunks, qmpc_reserve) and the warm start across MPC cycles, which is
  *                            correct but measured slower than the cold solve (qmpc_set_warm_start, _min_iters);
  *   include/qmpc_debug.h  -- test and profiling hooks (qmpc_set_debug_*, qmpc_debug_*): used by tests/ and tools/ only.
  * Same shared library, same ABI version. */

@@ -33,15 +33,6 @@ extern "C" {
  * qmpc_create).  The JCQP alternate and warm-started solves always take the one-kernel path. */
 int qmpc_set_split(qmpc_handle h, int mode);
 
-/* Block start of the decoupled path's engine -- EXPERIMENTAL, default off.  The rows of the friction pyramids / force
- * limits that are violated at the unconstrained minimiser are, almost without exception, active at the solution; with
- * on != 0 the engine adds such candidate sets (one row per stance foot-step and round, up to four rounds) as forced
- * additions made by all threads of the workgroup with the records in LDS, removes the rows whose multiplier came out
- * negative and hands a valid Goldfarb-Idnani state to the normal iteration.  Same unique minimiser (tested), but as
- * measured on MI355X not faster than the iteration it replaces: ~3.1 k cycles per forced change against
- * ~4.9 k per iteration, and 20 % more changes.  `iters` counts every forced change like an iteration. */
-int qmpc_set_block_start(qmpc_handle h, int on);
-
 /* The 64-row size class has a second instantiation sized for FIVE workgroups per CU (96 VGPRs, a 16-event pool in LDS
  * instead of 28): a launch of several rounds of workgroups is bound by instruction issue, and a fifth wave per SIMD fills
  * the slots the other four leave (trot: +3.5 % at 2048 robots, +8 % at 4096, +14 % from 8192 on); a single round (1024 robots)

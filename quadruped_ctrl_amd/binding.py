@@ -13,7 +13,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libqmpc.so")
 
 QMPC_OK = 0
-ABI_VERSION = 21              # qmpc_abi_version() this binding was written against
+ABI_VERSION = 22              # qmpc_abi_version() this binding was written against
 ST_MAXITER, ST_NOT_PD, ST_INFEASIBLE, ST_WS_FULL, ST_FALLBACK = 1, 2, 4, 8, 16
 ST_COMPACTED, ST_SPILLED = 64, 128
 ST_NONFINITE = 32
@@ -25,7 +25,7 @@ EXPORTS = ["qmpc_abi_version", "qmpc_last_error", "qmpc_create", "qmpc_destroy",
            "qmpc_forces_to_body", "qmpc_solve_commands", "qmpc_set_min_stance",
            "qmpc_set_debug_aux", "qmpc_set_debug_overflow_slices", "qmpc_solve_sharded", "qmpc_set_leg_geometry",
            "qmpc_leg_kinematics", "qmpc_leg_torques", "qmpc_swing_trajectory", "qmpc_set_warm_start", "qmpc_settings_jcqp", "qmpc_kf_init", "qmpc_kf_step", "qmpc_set_model",
-           "qmpc_max_horizon", "qmpc_set_debug_pool_busy", "qmpc_set_split", "qmpc_reserve", "qmpc_set_debug_engine_events", "qmpc_set_chunks", "qmpc_set_block_start", "qmpc_debug_read_item", "qmpc_debug_read_counts", "qmpc_set_dense", "qmpc_set_size_order", "qmpc_debug_keys", "qmpc_set_order_hint", "qmpc_set_debug_balance",
+           "qmpc_max_horizon", "qmpc_set_debug_pool_busy", "qmpc_set_split", "qmpc_reserve", "qmpc_set_debug_engine_events", "qmpc_set_chunks", "qmpc_debug_read_item", "qmpc_debug_read_counts", "qmpc_set_dense", "qmpc_set_size_order", "qmpc_debug_keys", "qmpc_set_order_hint", "qmpc_set_debug_balance",
            "qmpc_set_warm_start_min_iters", "qmpc_set_debug_overflow_spin"]
 
 KF_FIELDS = ("xhat", "P", "r_body", "a_world", "omega_body", "contact_phase", "leg_p", "leg_v", "position", "v_world", "v_body")
@@ -131,7 +131,6 @@ def load_library():
         lib.qmpc_debug_keys.argtypes = [C.c_void_p, C.c_int, C.POINTER(Inputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.qmpc_set_order_hint.argtypes = [C.c_void_p, C.c_int]
         lib.qmpc_set_debug_balance.argtypes = [C.c_void_p, C.c_int]
-        lib.qmpc_set_block_start.argtypes = [C.c_void_p, C.c_int]
         lib.qmpc_set_warm_start.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         lib.qmpc_set_warm_start_min_iters.argtypes = [C.c_void_p, C.c_int]
         lib.qmpc_set_model.argtypes = [C.c_void_p, C.c_int]
@@ -509,9 +508,6 @@ class BatchedConvexMPC:
         size (default), 2 / True always."""
         mode = 2 if mode is True else (0 if mode is False else int(mode))
         self._check(self.lib.qmpc_set_split(self.h, mode), "qmpc_set_split")
-
-    def set_block_start(self, on):
-        self._check(self.lib.qmpc_set_block_start(self.h, int(bool(on))), "qmpc_set_block_start")
 
     def set_dense(self, mode):
         """0 / 1 / 2: the 64-row class's five-workgroups-per-CU instantiation never / automatic (handles of 2048+ robots; see

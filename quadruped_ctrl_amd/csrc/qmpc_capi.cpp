@@ -110,30 +110,6 @@ static hipError_t fill_ints(int* p, int n, int v, hipStream_t stream) {
   return hipGetLastError();
 }
 
-// Order hint: robots sorted by the iteration count of the handle's previous call, longest first (counting sort, one
-// workgroup; the order inside a bin is whatever the atomics make it -- a robot's result does not depend on its place)
-#define QMPC_HINT_BINS 64
-__global__ __launch_bounds__(1024) void qmpc_order_kernel(const int* __restrict__ it, int* __restrict__ order, int n) {
-  __shared__ int hist[QMPC_HINT_BINS];
-  if (threadIdx.x < QMPC_HINT_BINS) hist[threadIdx.x] = 0;
-  __syncthreads();
-  auto bin = [](int v) { return QMPC_HINT_BINS - 1 - (v < 0 ? 0 : (v > QMPC_HINT_BINS - 1 ? QMPC_HINT_BINS - 1 : v)); };
-  for (int i = threadIdx.x; i < n; i += blockDim.x) atomicAdd(&hist[bin(it[i])], 1);
-  __syncthreads();
-  if (threadIdx.x < QMPC_HINT_BINS) {  // exclusive prefix over the 64 bins: one wave, six shuffle steps
-    const int cnt = hist[threadIdx.x];
-    int acc = cnt;
-#pragma unroll
-    for (int d = 1; d < QMPC_HINT_BINS; d <<= 1) {
-      const int up = __shfl_up(acc, d);
-      if ((int)threadIdx.x >= d) acc += up;
-    }
-    hist[threadIdx.x] = acc - cnt;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < n; i += blockDim.x) order[atomicAdd(&hist[bin(it[i])], 1)] = i;
-}
-
 struct qmpc_ctx {
   int device = 0;
   int max_batch = 0, max_horizon = 0;
@@ -158,7 +134,6 @@ struct qmpc_ctx {
   double* d_wk_ovf[3] = {nullptr, nullptr, nullptr};  // engine kernels' overflow event pools (one slice per resident workgroup)  // [QMPC_ORDER_BUCKETS][max_batch] item indices, hardest robots first
   int wk_cap[3] = {0, 0, 0};    // work items per class: a bounded pool, min(max_batch, QMPC_ITEMS_*) -- ensure_pools
   int* d_fb_lists = nullptr;   // [3][max_batch] robots the engine kernels hand back (128-row, 192-row, large problems)
-  bool block = false;          // qmpc_set_block_start (experimental, off: measured no faster); QMPC_BLOCK=1 in the environment switches it on at creation
   int dense = 1;               // qmpc_set_dense: the 64-row class at five workgroups per CU -- 0 never, 1 automatic (by the handle's size), 2 whenever the chain is that class alone
   int chunks = 0;              // qmpc_set_chunks (test hook): run the item classes in at least this many chunks (0 / 1: as few as the pools allow)
   int dbg_engine_events = 0;   // test hook: events the engine may hold per robot (0 = the compiled capacity)
@@ -167,7 +142,6 @@ struct qmpc_ctx {
   // resident workgroups takes them in the order of the previous call's iteration counts (same batch size), longest first
   int order_hint = 1;
   int* d_hint_iters = nullptr;  // [max_batch] iteration counts the one-kernel classes left in the previous call
-  int* d_order = nullptr;       // [max_batch] the permutation of this call
   // size order (qmpc_set_size_order, default on): no hint usable (first call, another batch size, hint off) -> the first class of a
   // chain, launched over several rounds, takes the robots that fit it largest first by their contact tables; the permutation is
   // built inside the launch (qmpc_kernels.hip: size_order_build)
@@ -176,12 +150,11 @@ struct qmpc_ctx {
   unsigned so_call = 0;
   unsigned long long* d_prio_cu = nullptr;  // [2048] one-round launches without a hint: one word per CU (qmpc_device.h: prio_cu)
   unsigned prio_call = 0;
-  int so_first_pct = 0, so_first_pct_hint = 50;  // the unsorted head beyond the first round, % of a round: keys from the records / from the hint
-  int so_min_div = 8;     // at least a round / so_min_div robots to order (measured 2 / 4 / 8 on batches of 1.1 ... 2.5 rounds: no loss anywhere, +4 ... +13 % at 1.4 rounds)
-  int so_tail_rounds = 5;
-  int hint_prepass = 0;  // 1: the order hint's permutation by a sort kernel in front of the call (as until round 6)
+  static constexpr int so_first_pct = 0, so_first_pct_hint = 50;  // the unsorted head beyond the first round, % of a round: keys from the records / from the hint
+  static constexpr int so_min_div = 8;  // at least a round / so_min_div robots to order (measured 2 / 4 / 8 on batches of 1.1 ... 2.5 rounds: no loss anywhere, +4 ... +13 % at 1.4 rounds)
+  static constexpr int so_tail_rounds = 5;  // a launch of many rounds orders its last five only (solve_impl)
   int hint_batch = 0;           // batch size of the call that wrote d_hint_iters (0: none yet)
-  int hint_hard = 5;            // single-round launches: iterations in the previous call from which a robot may keep the highest issue priority (0 = off)
+  static constexpr int hint_hard = 5;  // single-round launches: iterations in the previous call from which a robot may keep the highest issue priority (0 = off)
   int* d_hint_max = nullptr;    // [3] largest iteration count of the last calls (slots rotated by hint_call: read / fold / clear)
   unsigned hint_call = 0;
   int* d_cu_slots = nullptr;
@@ -279,7 +252,7 @@ int ensure_pools(qmpc_ctx* c);
 
 extern "C" {
 
-int qmpc_abi_version(void) { return 21; }  // 21: qmpc_set_size_order (expert), qmpc_debug_keys (debug) added; no signature changed
+int qmpc_abi_version(void) { return 22; }  // 22: the engine's block-start setter (expert) removed; no signature changed
 int qmpc_max_horizon(void) { return QMPC_MAX_HORIZON; }
 
 const char* qmpc_last_error(qmpc_handle h) { return h ? h->err.c_str() : "null handle"; }
@@ -301,30 +274,20 @@ int qmpc_create(int device_id, int max_batch, int max_horizon, qmpc_handle* out)
   if (e == hipSuccess) e = hipMalloc(&c->d_counts, sizeof(int) * 3 * QMPC_COUNTERS);
   if (e == hipSuccess) e = hipMemset(c->d_counts, 0, sizeof(int) * 3 * QMPC_COUNTERS);
   if (e == hipSuccess) e = hipMalloc(&c->d_fb_lists, sizeof(int) * 3 * (size_t)max_batch);
-  if (e == hipSuccess) e = hipMalloc(&c->d_hint_iters, sizeof(int) * (2 * (size_t)max_batch + 4 + 2048));
-  if (e == hipSuccess) e = hipMemset(c->d_hint_iters, 0, sizeof(int) * (2 * (size_t)max_batch + 4 + 2048));
-  if (e == hipSuccess) c->d_order = c->d_hint_iters + max_batch;
+  // [max_batch] hint iterations, [4] d_hint_max, [2048] d_cu_slots
+  if (e == hipSuccess) e = hipMalloc(&c->d_hint_iters, sizeof(int) * ((size_t)max_batch + 4 + 2048));
+  if (e == hipSuccess) e = hipMemset(c->d_hint_iters, 0, sizeof(int) * ((size_t)max_batch + 4 + 2048));
+  if (e == hipSuccess) {
+    c->d_hint_max = c->d_hint_iters + max_batch;
+    c->d_cu_slots = c->d_hint_max + 4;  // [2048] the 96-row class's per-CU placement words (zero whenever no kernel runs)
+  }
   if (e == hipSuccess) e = hipMalloc(&c->d_prio_cu, sizeof(unsigned long long) * 2048);
   if (e == hipSuccess) e = hipMemset(c->d_prio_cu, 0, sizeof(unsigned long long) * 2048);
   if (e == hipSuccess) e = hipMalloc(&c->d_so_order, sizeof(unsigned long long) * 2 * (size_t)max_batch);  // near copy, far copy
   if (e == hipSuccess) e = hipMemset(c->d_so_order, 0, sizeof(unsigned long long) * 2 * (size_t)max_batch);  // (call numbers start at 1)
-  if (e == hipSuccess) c->d_hint_max = c->d_hint_iters + 2 * (size_t)max_batch;
-  if (e == hipSuccess) c->d_cu_slots = c->d_hint_max + 4;  // [2048] the 96-row class's per-CU placement words (zero whenever no kernel runs)
   {
     const char* ns = std::getenv("QMPC_NO_SPLIT");
     c->split = (ns && ns[0] == '1') ? 0 : 1;
-    const char* sm = std::getenv("QMPC_SO_MIN_DIV");
-    if (sm && std::atoi(sm) > 0) c->so_min_div = std::atoi(sm);
-    const char* st = std::getenv("QMPC_SO_TAIL_ROUNDS");
-    if (st && std::atoi(st) > 0) c->so_tail_rounds = std::atoi(st);
-    const char* sf = std::getenv("QMPC_SO_FIRST_PCT");  // (measurement knob: the unsorted head of a size-ordered launch, % of a round beyond the first)
-    if (sf) c->so_first_pct = c->so_first_pct_hint = std::atoi(sf);
-    const char* hp = std::getenv("QMPC_HINT_PREPASS");
-    if (hp) c->hint_prepass = std::atoi(hp);
-    const char* hh = std::getenv("QMPC_HINT_HARD");
-    if (hh) c->hint_hard = std::atoi(hh);
-    const char* nb = std::getenv("QMPC_BLOCK");
-    c->block = nb && nb[0] == '1';
   }
   if (e == hipSuccess) {
     // a robot whose on-chip event pool fills up continues here.  The slices are RECYCLED within a call (one flag per slice,
@@ -342,12 +305,8 @@ int qmpc_create(int device_id, int max_batch, int max_horizon, qmpc_handle* out)
   if (e == hipSuccess) e = qmpc_prepare();
   if (e == hipSuccess) {
     // the runtime loads a translation unit's code object at the first launch of one of its kernels (2 MiB of device
-    // memory): this file's small kernels (fill, order hint) are first launched HERE, not inside some later solve call
+    // memory): this file's small kernel (fill) is first launched HERE, not inside some later solve call
     e = fill_ints(c->d_hint_max, 4, 0, nullptr);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(qmpc_order_kernel, dim3(1), dim3(1024), 0, nullptr, (const int*)c->d_hint_iters, c->d_order, 1);
-      e = hipGetLastError();
-    }
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
   }
   if (e != hipSuccess) {
@@ -549,12 +508,6 @@ int qmpc_set_split(qmpc_handle c, int on) {
   if (on < 0 || on > 2) return QMPC_ERR_ARG;
   c->split = on;
   return ensure_pools(c);
-}
-
-int qmpc_set_block_start(qmpc_handle c, int on) {
-  if (!c) return QMPC_ERR_ARG;
-  c->block = on != 0;
-  return QMPC_OK;
 }
 
 int qmpc_set_dense(qmpc_handle c, int mode) {
@@ -933,7 +886,6 @@ int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command
     A.wk_cap = c->wk_cap[sk];
     A.wk_base = 0;
     A.wk_kev = c->dbg_engine_events > 0 ? c->dbg_engine_events : (1 << 20);
-    A.wk_block = (sk < 2 && c->block) ? 1 : 0;
     A.fb_list = c->d_fb_lists + (size_t)sk * c->max_batch;
     A.fb_count = cnt + QMPC_CNT_FB + sk;
     A.list = list;
@@ -1051,20 +1003,12 @@ int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command
     // A launch of ONE round (the order cannot matter) uses the counts differently: the robots the previous call found hard
     // keep the highest issue priority through their sweep (qmpc_device.h: hint_hard) -- batch 1024, trot: 2.42e7 -> 2.75e7 QP/s.
     // (Only there: in a launch of many rounds it costs 3 %, measured at 16384 robots.)
-    P.order = nullptr;
     P.hint_hard = 0;
     bool use_hint_keys = false;
     if (!listed && c->order_hint && !capturing && !P.admm_mode) {
       if (batch > qmpc_resident_blocks(kcls)) {
-        if (c->hint_batch == batch) {
-          if (c->hint_prepass) {  // (until round 6, kept for comparison: QMPC_HINT_PREPASS=1)
-            hipLaunchKernelGGL(qmpc_order_kernel, dim3(1), dim3(1024), 0, stream, (const int*)c->d_hint_iters, c->d_order, batch);
-            HIP_TRY(c, hipGetLastError());
-            P.order = c->d_order;
-          } else {
-            use_hint_keys = true;  // the permutation is built inside the launch (below), keys = the previous call's counts
-          }
-        }
+        // the permutation is built inside the launch (below), keys = the previous call's counts
+        if (c->hint_batch == batch) use_hint_keys = true;
       } else if (2 * batch > qmpc_resident_blocks(kcls)) {  // (workgroups share CUs: below that priority has nobody to act on)
         // the largest count of the previous one-round call / of this one / cleared for the next: three slots in rotation
         const unsigned hc = c->hint_call++;
@@ -1080,7 +1024,7 @@ int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command
     // (measured: no loss on configs[4], where a third of the first round is handed on)
     P.so_order = nullptr;
     const bool by_size = c->size_order && !cmd && P.gait && ((uintptr_t)P.gait & 7u) == 0;
-    if (!listed && !capturing && !P.admm_mode && !P.order && (use_hint_keys || by_size)) {
+    if (!listed && !capturing && !P.admm_mode && (use_hint_keys || by_size)) {
       const int res = qmpc_resident_blocks(kcls);
       if (res > 0 && batch > res) {
         // (the unsorted head beyond the first round: none by size -- measured 0 / 15 / 30 / 50 % of a round: 0 is best or equal
@@ -1127,7 +1071,6 @@ int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command
     HIP_TRY(c, qmpc_launch(kcls, &P, grid, stream));
     P.prio_cu = nullptr;
     P.so_order = nullptr;
-    P.order = nullptr;
     P.hint_hard = 0;
     P.hint_max_z = nullptr;
     P.hint_max_w = nullptr;  // (the later classes of a chain are queues of several rounds)

@@ -141,7 +141,6 @@ struct QmpcParams {
   double* wk_ovf;  // engine kernel: overflow event pool, one slice of QMPC_ENGINE_OVF_EVENTS records per workgroup of the grid
   int rid0;     // sweep kernel: first robot (or list entry) of this launch's chunk
   int list_hi;  // ... and one past its last list entry (list-consuming launches)
-  int wk_block;  // 1: the engine starts from a block-factorised candidate set (block_start, qmpc_engine.hip)
   int wk_kev;  // events the engine may hold per robot (test hook; the compiled capacity when larger)
   int* fb_list;
   int* fb_count;
@@ -189,11 +188,9 @@ struct QmpcParams {
   double* dbg_g;
   double* dbg_aux;     // [batch][8]: cos/sin(yaw), roll, pitch, yaw as the kernel evaluated them (float transcendentals)
   long long* dbg_clk;  // [batch][16] shader-clock stamps per phase
-  // order hint (qmpc_set_order_hint; both nullptr = off): the first class of the chain takes robot order[blockIdx.x]
-  // instead of blockIdx.x -- the robots that iterated longest in the handle's previous call first, so that a launch of
-  // several rounds of workgroups does not end with a hard robot that started last -- and every one-kernel solve
-  // leaves its iteration count in hint_iters[robot] for the next call's order
-  const int32_t* order;
+  // order hint (qmpc_set_order_hint; nullptr = off): every one-kernel solve leaves its iteration count in hint_iters[robot]
+  // for the next call's order -- the robots that iterated longest first (so_hint), so that a launch of several rounds of
+  // workgroups does not end with a hard robot that started last
   int32_t* hint_iters;
   // ... and in a launch of ONE round of workgroups (the order cannot matter: everybody starts at once) a robot the previous
   // call found hard keeps the highest issue priority through its sweep instead of yielding as it advances: of the workgroups

@@ -21,7 +21,6 @@
 //     fixed order of the final sum: results do not depend on timing).
 // A robot that needs more events than registers + LDS hold (NH * MAXL + MAXE), or whose projected inverse loses
 // definiteness numerically, is handed back to the monolithic kernel of its class through a list (QMPC_ST_FALLBACK).
-// block_start (experimental, off by default): forced additions of candidate sets by all threads before the iteration.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -50,8 +49,6 @@ struct ECfg {
   static constexpr int BIAS = (RE == 2) ? 5 : 7;  // events the engine wave is dealt fewer than a holder (measured)
   static constexpr int EV = NP + KS;
   static_assert(MAXE >= MAXL && MAXE <= 64, "engine-held events");
-  // block start: records it may leave -- what the holders' registers take afterwards (its LDS is the engine wave's pool)
-  static constexpr int MAXB = (NH * MAXL < MAXE ? NH * MAXL : MAXE) & ~1;
   static_assert(NSL <= QMPC_WK_SLOTS_MAX, "stance slots of a work item");
   static_assert(5 * NSL <= 1024, "constraint id in ten bits of the selection key");
 };
@@ -89,17 +86,6 @@ struct ESmem {
   double D[C::NP];                       // diag(H^-1)
   float fb[12];
   signed char gsign[C::MAXG];            // overflow events in global memory: +1 add, -1 drop
-  // block start (see block_start): working set and multipliers by slot, the signs of the records in the event pool
-  struct Blk {
-    int ne, nadd, nc, fail, dl, pad0, pad1, pad2;
-    int cand[C::NSL];          // this round's candidates (constraint ids)
-    int wcid[C::KS];           // working-set slot -> constraint id (-1 = free)
-    int sign[C::MAXE];         // record e: +1 add event, -1 drop event
-    unsigned bmask[C::NSL];    // stance slot -> rows in the working set
-    double lam[C::KS];         // multipliers by slot
-    alignas(16) double Y[C::MAXE];
-    alignas(16) double Ys[C::MAXE];
-  } bk;
 };
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() carries a workgroup-scope fence over ALL address
@@ -138,331 +124,6 @@ __device__ __forceinline__ void dispatch_blocks(int q1, int q2, F&& f) {
       else if constexpr (QA + 1 < RE) f(std::integral_constant<int, QA>{}, std::integral_constant<int, QA + 1>{});
     }
   });
-}
-
-// f(integral_constant<V>) for the run-time value v in [LO, HI): a binary tree of wave-uniform branches (log2 levels)
-template <int LO, int HI>
-struct Pick {
-  template <class F>
-  static __device__ __forceinline__ void run(int v, F&& f) {
-    if constexpr (HI - LO == 1) {
-      f(std::integral_constant<int, LO>{});
-    } else {
-      constexpr int MID = (LO + HI) / 2;
-      if (v < MID) Pick<LO, MID>::run(v, f);
-      else Pick<MID, HI>::run(v, f);
-    }
-  }
-};
-
-// ---------------------------------------------------------------------------------------------------- block start
-// The dual active set adds ONE constraint per iteration, and a robot braking to a stand ends with 30+ rows at a bound:
-// a serial chain of 30+ iterations of ~5 k cycles, each with a selection, a ratio test and two barrier rounds with the
-// holders.  Most of those rows are known early: the rows violated at the unconstrained minimiser x_u are, almost
-// without exception, active at the solution (precision 0.96 - 1.00).  So the iteration starts from a BLOCK
-// of forced changes made by ALL threads of the workgroup:
-//   round r = 1 .. QMPC_BLK_ROUNDS: the most violated row of every stance foot-step at the current x (not in W yet),
-//   each added as in a full Goldfarb-Idnani step but WITHOUT search and ratio test:
-//       y_e = z~_e^T c,  z = H^-1 c - sum y z~,  r = sum y g~,  delta = c^T z,  t = -(c^T x - rhs) / delta,
-//       x += t z,  lambda_W -= t r,  lambda_p = t,  new record (z, -r, 1) / sqrt(delta);
-//   x is then the minimiser on W as equalities; afterwards the rows whose multiplier came out negative leave, most
-//   negative first (drop records with the repair step: x -= (lambda_l / gamma) N*_l, lambda -= (lambda_l / gamma) S^-1[:, l]).
-// Data layout of the phase: thread t owns ENTRY t of every record (t < NP: variable t of z~; t >= NP: slot t - NP of g~)
-// in REGISTERS (`col`, statically indexed), and a TRANSPOSED copy of the records sits in LDS (`Rt[t][e]`: entry t of all
-// records contiguous) -- so y for all records is two contiguous broadcast vectors (16-byte loads), and the accumulation
-// over the records is one fma per record on the thread's own registers: no pass over record-major data in LDS (measured
-// before: ~95 cycles per record and forced change, latency-bound).  Two LDS-only barriers per forced change.
-// What comes out is a genuine Goldfarb-Idnani state (x optimal on W, multipliers >= 0, the projected inverse as rank-1
-// records): the holders take the records into their registers and the normal iteration finishes the job -- same unique
-// minimiser (tools/block_proto.py: braking at horizon 10, 34 iterations -> 4 rounds, ~5 removals, ~4 iterations).
-#ifndef QMPC_BLK_ROUNDS
-#define QMPC_BLK_ROUNDS 4
-#endif
-template <class C>
-__device__ __forceinline__ void block_start(const int tid, ESmem<C>& S, const GlobalF64* const Hi, const GlobalF64* const xu,
-                                            const int n, const int nst, const int max_changes) {
-  constexpr int SQ = C::SQ, NP = C::NP, LD = C::NP, NT = C::NT, EV = C::EV, KS = C::KS, NH = C::NH;
-  constexpr int MAXB = C::MAXB;
-  constexpr int NCMAX = 12;  // candidates added per round
-  static_assert(EV <= NT, "one thread per record entry");
-  const QmpcParams& P = S.par;
-  const int lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  auto& B = S.bk;
-  double(*const Rt)[MAXB] = reinterpret_cast<double(*)[MAXB]>(&S.epool[0][0]);  // Rt[entry][record]
-  static_assert(sizeof(double) * EV * MAXB <= sizeof(S.epool), "transposed records fit the engine wave's pool");
-  double* const T = S.stage;  // the vector being built (z | r)
-  const double mi = P.mu_inv;
-  const bool isvar = tid < NP, isslot = tid >= NP && tid < EV, isent = tid < EV;
-  const int w = tid - NP;  // slot of a slot thread
-  if (tid == 0) {
-    B.ne = 0;
-    B.nadd = 0;
-    B.fail = 0;
-  }
-  for (int k = tid; k < KS; k += NT) {
-    B.wcid[k] = -1;
-    B.lam[k] = 0.0;
-  }
-  if (isent) {
-#pragma unroll
-    for (int e = 0; e < MAXB; e += 2) st2(&Rt[tid][e], 0.0, 0.0);
-  }
-  double col[MAXB];  // this thread's entry of every record
-#pragma unroll
-  for (int e = 0; e < MAXB; ++e) col[e] = 0.0;
-  __syncthreads();
-  // the new record's entry goes into register [ne] (a run-time index: one case per register, kept apart by a dummy
-  // instruction -- see the holders' ingest) and into the transposed copy
-  auto put_entry = [&](int ne, double v) __attribute__((always_inline)) {
-    Pick<0, MAXB>::run(ne, [&](auto ec) __attribute__((always_inline)) {
-      constexpr int e = decltype(ec)::value;
-      col[e] = v;
-      asm volatile("; record register %0" ::"n"(e));
-    });
-    Rt[tid][ne] = v;
-  };
-  bool stop = false;
-  for (int round = 0; round < QMPC_BLK_ROUNDS && !stop; ++round) {
-    if (wv == 0) {
-      // ---- this round's candidates: the most violated row of every stance foot-step at the current x, not in W
-      const double inv_fr = P.inv_fr_norm, tol = P.tol;
-#pragma unroll
-      for (int s = 0; s < SQ; ++s) B.bmask[lane + 64 * s] = 0u;
-      __builtin_amdgcn_wave_barrier();
-      for (int k = lane; k < KS; k += 64) {
-        const int id = B.wcid[k];
-        if (id >= 0) atomicOr(&B.bmask[id / 5], 1u << (id % 5));
-      }
-      __builtin_amdgcn_wave_barrier();
-      int nc = 0;
-#pragma unroll
-      for (int s = 0; s < SQ; ++s) {
-        const int sl = lane + 64 * s;
-        const int sc = sl < nst ? sl : 0;
-        const double x0 = S.xl[3 * sc], x1 = S.xl[3 * sc + 1], x2 = S.xl[3 * sc + 2];
-        const unsigned am = B.bmask[sc];
-        const double fmx = (double)S.fmaxk[sc];
-        int tmin = -1;
-        if (sl < nst) {
-          const double fx = mi * x0, fy = mi * x1;
-          double vmin = 0.0;
-          const double sv[5] = {(fx + x2) * inv_fr, (x2 - fx) * inv_fr, (fy + x2) * inv_fr, (x2 - fy) * inv_fr, fmx - x2};
-#pragma unroll
-          for (int ty = 0; ty < 5; ++ty) {
-            const bool cand = !((am >> ty) & 1u) && sv[ty] < vmin;
-            vmin = cand ? sv[ty] : vmin;
-            tmin = cand ? ty : tmin;
-          }
-          if (!(vmin < -tol)) tmin = -1;
-        }
-        const unsigned long long vm = __ballot(tmin >= 0);
-        if (tmin >= 0) B.cand[nc + __popcll(vm & ((1ull << lane) - 1ull))] = 5 * sl + tmin;
-        nc += __popcll(vm);
-      }
-      if (lane == 0) B.nc = nc;
-    }
-    __syncthreads();
-    int nc = B.nc;
-    if (nc == 0) break;  // uniform: nothing violated (optimal) -- or nothing new to add
-    nc = nc < NCMAX ? nc : NCMAX;  // (the rest of a longer list is picked up by the next round)
-    // ---- H^-1 c for EVERY candidate of the round first: all loads in flight together, one L2 / HBM round trip per round
-    // (the inverse was written by another kernel: every column is a first touch, ~2 k cycles each if waited for singly)
-    double zc[NCMAX];
-    Upto<0, NCMAX>::run(nc, [&](auto cic) __attribute__((always_inline)) {
-      constexpr int ci = decltype(cic)::value;
-      const int id = B.cand[ci];
-      const int slot = id / 5, ty = id - 5 * slot, j0 = 3 * slot;
-      const int j1 = (ty < 4) ? j0 + (ty >> 1) : j0 + 2, j2 = j0 + 2;
-      const double a1 = (ty < 4) ? ((ty & 1) ? -mi : mi) : -1.0, a2 = (ty < 4) ? 1.0 : 0.0;
-      // (lower block triangle: above the column's diagonal block by symmetry from the row, below it from the column)
-      const bool up1 = (tid >> 6) <= (j1 >> 6), up2 = (tid >> 6) <= (j2 >> 6);
-      zc[ci] = (isvar && tid < n) ? __builtin_fma(a2, up2 ? Hi[(size_t)j2 * LD + tid] : Hi[(size_t)tid * LD + j2],
-                                                  a1 * (up1 ? Hi[(size_t)j1 * LD + tid] : Hi[(size_t)tid * LD + j1]))
-                                  : 0.0;
-    });
-#pragma unroll 1
-    for (int ci = 0; ci < nc && !stop; ++ci) {
-      const int ne = B.ne, q = B.nadd;
-      if (ne >= MAXB || q >= KS || ne >= max_changes) {  // uniform: no room / iteration limit -- the normal iteration goes on
-        stop = true;
-        break;
-      }
-#ifdef QMPC_BLK_STAMP
-      long long* const bclk = (P.dbg_clk && tid == 0 && ne == QMPC_BLK_STAMP) ? P.dbg_clk + (size_t)S.rid * 16 : nullptr;
-      if (bclk) bclk[0] = clock64();
-#endif
-      // ---- forced addition of row id into slot q
-      const int id = B.cand[ci];
-      const int slot = id / 5, ty = id - 5 * slot, j0 = 3 * slot;
-      const int j1 = (ty < 4) ? j0 + (ty >> 1) : j0 + 2, j2 = j0 + 2;
-      const double a1 = (ty < 4) ? ((ty & 1) ? -mi : mi) : -1.0, a2 = (ty < 4) ? 1.0 : 0.0;
-      const double rhs = (ty == 4) ? -(double)S.fmaxk[slot] : 0.0;
-      const double sp = __builtin_fma(a2, S.xl[j2], a1 * S.xl[j1]) - rhs;  // (x is stable until step 2)
-      // (every record is an ADD record while the rounds last -- removals come after them)
-      double zc_ci = 0.0;
-      StaticFor<0, NCMAX>::run([&](auto cc) __attribute__((always_inline)) {
-        if (decltype(cc)::value == ci) zc_ci = zc[decltype(cc)::value];
-      });
-      if (isent) {
-        const double sg = isvar ? -1.0 : 1.0;
-        double acc = isvar ? zc_ci : 0.0, acc2 = 0.0;
-        const double* const r1 = Rt[j1];
-        const double* const r2 = Rt[j2];
-        // eight records per group: their 16-byte broadcast loads in flight together, ONE wait (behind a wave-uniform
-        // branch per record the loads cannot be hoisted and every step waits its own LDS round trip: 1.8 k cycles at 20 records)
-        Upto<0, (MAXB + 7) / 8>::run((ne + 7) >> 3, [&](auto gc) __attribute__((always_inline)) {
-          constexpr int e0 = 8 * decltype(gc)::value;
-          constexpr int NPR = (MAXB - e0 >= 8) ? 4 : (MAXB - e0) / 2;
-          F64x2 p[NPR], qq[NPR];
-#pragma unroll
-          for (int u = 0; u < NPR; ++u) {
-            p[u] = ld2(r1 + e0 + 2 * u);  // (records past the last one are zero)
-            qq[u] = ld2(r2 + e0 + 2 * u);
-          }
-#pragma unroll
-          for (int u = 0; u < NPR; ++u) {
-            acc = __builtin_fma(sg * __builtin_fma(a2, qq[u].x, a1 * p[u].x), col[e0 + 2 * u], acc);
-            acc2 = __builtin_fma(sg * __builtin_fma(a2, qq[u].y, a1 * p[u].y), col[e0 + 2 * u + 1], acc2);
-          }
-        });
-        T[tid] = acc + acc2;
-      }
-#ifdef QMPC_BLK_STAMP
-      if (bclk) bclk[3] = clock64();
-#endif
-      lds_barrier();
-#ifdef QMPC_BLK_STAMP
-      if (bclk) bclk[4] = clock64();
-#endif
-      const double delta = __builtin_fma(a2, T[j2], a1 * T[j1]);
-      const double cn = __builtin_fma(a2 * a2, S.D[j2], a1 * a1 * S.D[j1]);
-      if (delta > 1e-11 * cn) {  // uniform (else: the row depends on the ones in W, e.g. the pyramid's apex: skipped)
-        const double tt = -sp * fast_rcp(delta);
-        double sq = __builtin_amdgcn_rsq(delta);
-        {
-          double e = __builtin_fma(-delta * sq, sq, 1.0);
-          sq = __builtin_fma(0.5 * sq, e, sq);
-          e = __builtin_fma(-delta * sq, sq, 1.0);
-          sq = __builtin_fma(0.5 * sq, e, sq);
-        }
-        if (isvar) {
-          const double z = T[tid];
-          put_entry(ne, z * sq);
-          if (tid < n) S.xl[tid] = __builtin_fma(tt, z, S.xl[tid]);
-        } else if (isslot) {
-          const double r = T[tid];
-          const bool active = B.wcid[w] >= 0;
-          put_entry(ne, (w == q) ? sq : (active ? -r * sq : 0.0));
-          if (active) B.lam[w] = __builtin_fma(-tt, r, B.lam[w]);
-          if (w == q) {
-            B.lam[w] = tt;
-            B.wcid[w] = id;
-          }
-        }
-        if (tid == 0) {
-          B.sign[ne] = 1;
-          B.ne = ne + 1;
-          B.nadd = q + 1;
-        }
-      }
-#ifdef QMPC_BLK_STAMP
-      if (bclk) bclk[5] = clock64();
-#endif
-      lds_barrier();
-#ifdef QMPC_BLK_STAMP
-      if (bclk) bclk[7] = clock64();
-#endif
-    }
-  }
-  // ---- rows whose multiplier came out negative leave, most negative first
-  while (true) {
-    if (wv == 0) {
-      double worst = 0.0;
-      for (int k = lane; k < KS; k += 64) {
-        const double v = (B.wcid[k] >= 0 && B.lam[k] < 0.0) ? -B.lam[k] : 0.0;
-        worst = v > worst ? v : worst;
-      }
-      const double wmax = wave_max_pos_f64(worst);
-      int l = -1;
-      if (wmax > 0.0) {
-        for (int k0 = 0; k0 < KS && l < 0; k0 += 64) {
-          const int k = k0 + lane;
-          const unsigned long long hit = __ballot(B.wcid[k] >= 0 && B.lam[k] < 0.0 && -B.lam[k] == wmax);
-          if (hit != 0ull) l = k0 + __ffsll((long long)hit) - 1;
-        }
-      }
-      if (lane == 0) B.dl = l;
-    }
-    lds_barrier();
-    const int l = B.dl, ne = B.ne;
-    if (l < 0 || ne >= MAXB || ne >= max_changes) break;  // uniform (rows still negative are dropped by the engine wave's own loop)
-    const double laml = B.lam[l];
-    if (isent) {
-      // u = N*_l = sum g~_e[l] z~_e (variable entries), sc = S^-1[:, l] = sum +-g~_e[l] g~_e (slot entries; - for drop records)
-      double acc = 0.0, acc2 = 0.0;
-      const double* const rl = Rt[NP + l];
-      Upto<0, (MAXB + 7) / 8>::run((ne + 7) >> 3, [&](auto gc) __attribute__((always_inline)) {
-        constexpr int e0 = 8 * decltype(gc)::value;
-        constexpr int NPR = (MAXB - e0 >= 8) ? 4 : (MAXB - e0) / 2;
-        F64x2 y[NPR];
-        int sgn[2 * NPR];
-#pragma unroll
-        for (int u = 0; u < NPR; ++u) {
-          y[u] = ld2(rl + e0 + 2 * u);
-          sgn[2 * u] = B.sign[e0 + 2 * u];
-          sgn[2 * u + 1] = B.sign[e0 + 2 * u + 1];
-        }
-#pragma unroll
-        for (int u = 0; u < NPR; ++u) {
-          const double s0 = (isslot && sgn[2 * u] < 0) ? -y[u].x : y[u].x, s1 = (isslot && sgn[2 * u + 1] < 0) ? -y[u].y : y[u].y;
-          acc = __builtin_fma(s0, col[e0 + 2 * u], acc);
-          acc2 = __builtin_fma(s1, col[e0 + 2 * u + 1], acc2);
-        }
-      });
-      T[tid] = acc + acc2;
-    }
-    lds_barrier();
-    const double gamma = T[NP + l];
-    if (!(gamma > 0.0)) {  // uniform: numerically lost S^-1[l][l] > 0 -- the robot is handed back
-      if (tid == 0) B.fail = 1;
-      break;
-    }
-    const double coef = laml * fast_rcp(gamma);
-    double sg = __builtin_amdgcn_rsq(gamma);
-    {
-      double e = __builtin_fma(-gamma * sg, sg, 1.0);
-      sg = __builtin_fma(0.5 * sg, e, sg);
-      e = __builtin_fma(-gamma * sg, sg, 1.0);
-      sg = __builtin_fma(0.5 * sg, e, sg);
-    }
-    if (isvar) {
-      const double u = T[tid];
-      put_entry(ne, u * sg);
-      if (tid < n) S.xl[tid] = __builtin_fma(-coef, u, S.xl[tid]);
-    } else if (isslot) {
-      const double sc = T[tid];
-      const bool active = B.wcid[w] >= 0 && w != l;
-      if (w == l) {
-        // slot l leaves: its column of every earlier g~ is cleared -- this thread's registers and its row of the copy
-#pragma unroll
-        for (int e = 0; e < MAXB; ++e) col[e] = 0.0;
-#pragma unroll
-        for (int e = 0; e < MAXB; e += 2) st2(&Rt[tid][e], 0.0, 0.0);
-        B.wcid[w] = -1;
-        B.lam[w] = 0.0;
-      } else {
-        put_entry(ne, active ? -sc * sg : 0.0);
-        if (active) B.lam[w] = __builtin_fma(-coef, sc, B.lam[w]);
-      }
-    }
-    if (tid == 0) {
-      B.sign[ne] = -1;
-      B.ne = ne + 1;
-    }
-    lds_barrier();
-  }
-  __syncthreads();
 }
 
 // +-1.0 in a scalar register pair, opaque to the optimiser (which would turn y * (c ? 1 : -1) back into a negation and a
@@ -552,28 +213,15 @@ __device__ __forceinline__ void engine_item(const int item, const int tid, ESmem
   const int h = P.horizon;
   long long* dbg_clk = P.dbg_clk ? P.dbg_clk + (size_t)rid * 16 : nullptr;
   if (dbg_clk && tid == 0) dbg_clk[12] = clock64();
-  // (the experimental block start needs one thread per record entry: the 128-row class's engine has them)
-  const bool blk = C::EV <= C::NT && P.wk_block != 0;
-  if constexpr (C::EV <= C::NT) {
-    if (blk) block_start<C>(tid, S, Hi, xu, n, nst, P.max_iter);
-  }
-  if (!blk && tid == 0) {
-    S.bk.ne = 0;
-    S.bk.fail = 0;
-  }
-  __syncthreads();
-  const int bkev = S.bk.ne;  // records the block start left in the engine wave's pool (record e = event e)
-  if (dbg_clk && tid == 0) dbg_clk[13] = clock64();
   // Events are dealt to whoever holds the fewest: the engine wave (owner 0, its LDS pool, MAXE records) or a holder
-  // (owners 1..NH, MAXL register slots each); the engine wave keeps the counts.  The block start's records all go to the
-  // holders (record e -> holder 1 + e mod NH, registers [e / NH]): its LDS is the engine wave's pool.
+  // (owners 1..NH, MAXL register slots each); the engine wave keeps the counts.
   if (wv == 0) {
     // =============================================================== the engine wave
     const double mi = P.mu_inv, inv_fr = P.inv_fr_norm, tol = P.tol;
     const int max_iter = __builtin_amdgcn_readfirstlane(P.max_iter);
     const int kev = __builtin_amdgcn_readfirstlane(P.wk_kev < C::KEV + C::MAXG ? P.wk_kev : C::KEV + C::MAXG);  // (test hook)
     auto uni = [](bool cnd) __attribute__((always_inline)) { return __builtin_amdgcn_ballot_w64(cnd) != 0ull; };
-    double xv[RE];  // (x_u, or the block start's minimiser on its working set)
+    double xv[RE];  // (x_u)
 #pragma unroll
     for (int q = 0; q < RE; ++q) xv[q] = (lane + 64 * q < n) ? S.xl[lane + 64 * q] : 0.0;
     double fmx[SQ];
@@ -600,33 +248,6 @@ __device__ __forceinline__ void engine_item(const int item, const int tid, ESmem
 #pragma unroll
     for (int o = 0; o <= NH; ++o) cnt[o] = 0;
     bool retry = false;
-    if (bkev > 0) {
-      // ---- state left by the block start: x (already in xl), the working set and its multipliers by slot, membership
-      // masks, and the engine wave's share of the records (event e belongs to owner e mod (NH + 1)), compacted to the
-      // front of its pool once the holders have taken theirs (barrier)
-#pragma unroll
-      for (int k = 0; k < KQ; ++k) {
-        wcid[k] = S.bk.wcid[lane + 64 * k];
-        lam[k] = S.bk.lam[lane + 64 * k];
-        const unsigned long long used = __ballot(wcid[k] >= 0);
-        if (used != 0ull) khw = 64 * k + 64 - __builtin_clzll(used);
-      }
-#pragma unroll
-      for (int s = 0; s < SQ; ++s) S.bk.bmask[lane + 64 * s] = 0u;
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int k = 0; k < KQ; ++k)
-        if (wcid[k] >= 0) atomicOr(&S.bk.bmask[wcid[k] / 5], 1u << (wcid[k] % 5));
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int s = 0; s < SQ; ++s) amask[s] = S.bk.bmask[lane + 64 * s];
-      nev = bkev;
-      iters = bkev;  // (every forced addition / removal of the block start is a working-set change like an iteration's)
-      if (S.bk.fail != 0) retry = true;
-#pragma unroll
-      for (int o = 1; o <= NH; ++o) cnt[o] = (bkev > o - 1) ? (bkev - (o - 1) + NH - 1) / NH : 0;
-      lds_barrier();  // the holders have taken the records (the phase's LDS is this wave's event pool from here on)
-    }
     int p_e = 0, psl = 0, pty = 0, pj1 = 0, pj2 = 0;
     double pa1 = 0.0, pa2 = 0.0, p_rhs = 0.0, lp = 0.0;
     auto rsqrt_full = [&](double d) __attribute__((always_inline)) {
@@ -800,10 +421,8 @@ __device__ __forceinline__ void engine_item(const int item, const int tid, ESmem
     };
     __builtin_amdgcn_s_setprio(2);  // the serial part of the workgroup
     // Remove working-set slot l: one drop event.  u = N*_l (variable lanes), sc = S^-1[:, l] (slot lanes) over ALL events (a
-    // round with the holders), gamma = S^-1[l][l].  With `repair` (after a block start: a row whose multiplier came out
-    // negative does not belong to the working set) the iterate also moves to the minimiser WITHOUT that row:
-    // x -= (lam_l / gamma) u, lam -= (lam_l / gamma) sc.  false: the projected inverse lost definiteness numerically.
-    auto drop_slot = [&](int l, bool repair) __attribute__((always_inline)) {
+    // round with the holders), gamma = S^-1[l][l].  false: the projected inverse lost definiteness numerically.
+    auto drop_slot = [&](int l) __attribute__((always_inline)) {
       double u[RE], sc[KQ];
 #pragma unroll
       for (int q = 0; q < RE; ++q) u[q] = 0.0;
@@ -821,16 +440,6 @@ __device__ __forceinline__ void engine_item(const int item, const int tid, ESmem
       if (uni(!(gamma > 0.0))) {
         retry = true;
         return false;
-      }
-      if (repair) {
-        const double coef = lane_elem<KQ>(lam, l) * fast_rcp(gamma);
-#pragma unroll
-        for (int q = 0; q < RE; ++q) {
-          xv[q] = __builtin_fma(-coef, u[q], xv[q]);
-          S.xl[lane + 64 * q] = xv[q];
-        }
-#pragma unroll
-        for (int k = 0; k < KQ; ++k) lam[k] = __builtin_fma(-coef, sc[k], lam[k]);
       }
       // the drop event (placed in the next round's window): N*_l / sqrt(gamma), -S^-1[:, l] / sqrt(gamma) on the slots in
       // use, zero in slot l
@@ -910,31 +519,7 @@ __device__ __forceinline__ void engine_item(const int item, const int tid, ESmem
       }
       return true;
     };
-    // ---- after a block start: rows whose multiplier came out negative leave, most negative first, one drop event
-    // each -- what remains is a Goldfarb-Idnani state (x optimal on W, multipliers >= 0)
-    while (bkev > 0 && !retry) {  // (normally nothing left to do: the block start removes them itself while it has room)
-      double worst = 0.0;
-#pragma unroll
-      for (int k = 0; k < KQ; ++k) {
-        const double v = (wcid[k] >= 0 && lam[k] < 0.0) ? -lam[k] : 0.0;
-        worst = v > worst ? v : worst;
-      }
-      const double wmax = wave_max_pos_f64(worst);
-      if (!(wmax > 0.0)) break;
-      if (iters >= max_iter) {
-        retry = true;
-        break;
-      }
-      int l = -1;
-#pragma unroll
-      for (int k = 0; k < KQ; ++k) {
-        const unsigned long long hit = __ballot(wcid[k] >= 0 && lam[k] < 0.0 && -lam[k] == wmax);
-        if (l < 0 && hit != 0ull) l = 64 * k + __ffsll((long long)hit) - 1;
-      }
-      if (!drop_slot(l, true)) break;
-      iters += 1;
-    }
-    bool have_p = !retry && select_next();
+    bool have_p = select_next();
     while (have_p) {
       iters = __builtin_amdgcn_readfirstlane(iters);
       khw = __builtin_amdgcn_readfirstlane(khw);
@@ -1081,7 +666,7 @@ __device__ __forceinline__ void engine_item(const int item, const int tid, ESmem
         have_p = select_next();
       } else {
         // ---- partial step: the multiplier of slot l reached zero -> drop it.  p stays (its columns are still in c1, c2)
-        if (!drop_slot(l, false)) break;
+        if (!drop_slot(l)) break;
       }
       __builtin_amdgcn_wave_barrier();
       if (dbg_clk && lane == 0 && iters == QMPC_EDBG_ITER + 1) dbg_clk[7] = clock64();
@@ -1156,22 +741,6 @@ __device__ __forceinline__ void engine_item(const int item, const int tid, ESmem
     int nloc = 0, hround = 0;
     const GlobalF64* const hgov = P.wk_ovf ? (const GlobalF64*)P.wk_ovf + (size_t)blockIdx.x * ((size_t)C::MAXG * EV) : nullptr;
     unsigned long long dropm = 0ull;  // local events that are drop events
-    if (bkev > 0) {
-      // the block start's records (transposed in LDS: Rt[entry][record]): record e goes to holder 1 + e mod NH,
-      // registers [e / NH]
-      const double(*const Rt)[C::MAXB] = reinterpret_cast<const double(*)[C::MAXB]>(&S.epool[0][0]);
-      nloc = (bkev > wv - 1) ? (bkev - (wv - 1) + NH - 1) / NH : 0;
-      Upto<0, MAXL>::run(nloc, [&](auto lic) __attribute__((always_inline)) {
-        constexpr int li = decltype(lic)::value;
-        const int e = li * NH + (wv - 1);
-#pragma unroll
-        for (int q = 0; q < RE; ++q) zt[li][q] = Rt[lane + 64 * q][e];
-#pragma unroll
-        for (int k = 0; k < KQ; ++k) gt[li][k] = Rt[NP + lane + 64 * k][e];
-        if (S.bk.sign[e] < 0) dropm |= (1ull << li);
-      });
-      lds_barrier();  // (the phase's LDS becomes the engine wave's event pool after this)
-    }
     while (true) {
       lds_barrier();  // (A)
       const bool hst = dbg_clk && wv == 1 && lane == 0 && hround == QMPC_EDBG_ITER;  // (rounds ~ iterations while nothing is dropped)

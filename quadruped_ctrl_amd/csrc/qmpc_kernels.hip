@@ -53,18 +53,6 @@
 #include "qmpc_wave.h"
 
 namespace {
-#ifndef QMPC_ENGINE_PRIO
-#define QMPC_ENGINE_PRIO 3
-#endif
-#ifndef QMPC_SWEEP_PRIO
-#define QMPC_SWEEP_PRIO 1
-#endif
-#ifndef QMPC_START_PRIO
-#define QMPC_START_PRIO 1
-#endif
-#ifndef QMPC_PROD_PRIO
-#define QMPC_PROD_PRIO 0  // 1: the wave that produces the next pivot pair runs at the highest issue priority while it does (measured, round 6)
-#endif
 
 // a[j] += c[lane j of this lane's row of 16] * u for j = 0..15: sixteen DP-ALU DPP
 // fmacs (row_newbcast), i.e. the 16 wave-uniform pivot-column values are held one
@@ -347,11 +335,6 @@ __device__ __forceinline__ int qmpc_score_level(const float score, const float p
   return levels - 1 - b;
 }
 
-// (one-round staging: the other robots of a staged CU step back one level from the assembly on -- 0: only in the sweep)
-#ifndef QMPC_STAGE_EARLY
-#define QMPC_STAGE_EARLY 1
-#endif
-
 // Size classes.  RB names the class: 1, 2, 3 = 64 / 128 / 192 padded rows (four column
 // groups of 16 RB columns, 256 RB threads); 4 = the 96-row class between 1 and 2 (four
 // groups of 24 columns, 384 threads, two workgroups per CU) that catches n_r <= 96 --
@@ -373,10 +356,7 @@ struct Cfg {
   // (HW_REG_HW_ID), and two of them exit at once: the workgroup keeps both waves on two SIMDs and one on the other two,
   // WHICH two decided per CU (a two-bit slot word per CU in global memory) so that the two residents complement each
   // other: (3,3,3,3).  balance_waves() below
-#ifndef QMPC_BALANCE4
-#define QMPC_BALANCE4 1
-#endif
-  static constexpr bool BALANCE = QMPC_BALANCE4 && (RB == 4);
+  static constexpr bool BALANCE = (RB == 4);
   static constexpr int NT_LAUNCH = BALANCE ? 512 : NT;
   static constexpr int RE = (NP + 63) / 64;  // 64-row blocks of an index-major engine vector
   // Schur-form engine (the fallback): working-set slots.  Every n_r <= 64 problem fits 64; in the largest
@@ -406,14 +386,8 @@ struct Cfg {
   static constexpr int NHELP = C1 ? 0 : 3;
   // event records with the lane's entries stored adjacently (16-byte loads): the classes whose robots hold many
   // events; the record size is the same (NP and KS are multiples of 64 there)
-#ifndef QMPC_PAIRED
-#define QMPC_PAIRED 1
-#endif
-  static constexpr bool PAIRED = QMPC_PAIRED && (RB == 2 || RB == 3);
-#ifndef QMPC_HELP_MIN_TRIPS
-#define QMPC_HELP_MIN_TRIPS 3
-#endif
-  static constexpr int HELP_MIN_TRIPS = QMPC_HELP_MIN_TRIPS;
+  static constexpr bool PAIRED = (RB == 2 || RB == 3);
+  static constexpr int HELP_MIN_TRIPS = 3;
   // horizons this class assembles: the reference's gaits use 10 .. 16 segments; its interface takes up to
   // K_MAX_GAIT_SEGMENTS = 36 (convexMPC_interface.h:3).  The long ones (h > 16) are assembled by the 192-row class only:
   // its 768 threads cover the 12 h <= 432 tracking-error entries one per thread, and it alone has the LDS for h x h tables
@@ -421,10 +395,7 @@ struct Cfg {
   static constexpr int MIN_WAVES = (RB == 1 || RB == 4) ? 4 : (RB == 6 ? 5 : (RB == 2 ? 2 : 3));  // per SIMD (launch bounds)
   // ... of the producer half of the decoupled path (qmpc_sweep_kernel): without the packed inverse its LDS is the
   // assembly / sweep storage only, so the 128-row class fits two workgroups per CU if it stays within 128 VGPRs
-#ifndef QMPC_SWEEP_WAVES2
-#define QMPC_SWEEP_WAVES2 4
-#endif
-  static constexpr int MIN_WAVES_A = (RB == 2) ? QMPC_SWEEP_WAVES2 : MIN_WAVES;
+  static constexpr int MIN_WAVES_A = (RB == 2) ? 4 : MIN_WAVES;
 };
 
 template <int RB>
@@ -576,9 +547,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     (void)none;
     QMPC_STOP(-1, none);
   }
-#if QMPC_SWEEP_PRIO && QMPC_START_PRIO
   __builtin_amdgcn_s_setprio(3);  // a workgroup that is just starting is behind everybody else on its CU
-#endif
   // order hint, single-round launches: a robot the previous call found hard (wave-uniform: two scalar loads)
   bool hard = false;
   int hfloor = 0;  // the priority the robot does not fall below while it sweeps
@@ -921,11 +890,9 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     (void)keep0;
     QMPC_STOP(0, keep0);
   }
-#if QMPC_SWEEP_PRIO && QMPC_START_PRIO
   // one-round launch with the order hint: everybody started at the highest priority (a tie); from here to the sweep the
   // robots the previous call did not find hard step back one level (the hint's two scalar loads have landed with the record)
   if (PK.hint_hard > 0 && !hard) __builtin_amdgcn_s_setprio(2);
-#endif
   const int nst = S.nst;
   const int n = 3 * nst;
   // command mode: what the thread that finalises a robot does besides the outputs --
@@ -1076,13 +1043,12 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
   }
   __syncthreads();  // ---- barrier 2
   QMPC_TICK(2);
-#if QMPC_STAGE_EARLY
   // (the robots of a staged CU that are not its hardest step back one level from the assembly on, like the hint's robots after
-  //  stage 0: configs[1] 2.73e7 -> 2.76e7; one level lower still throughout their sweep: no change -- tools/dbg/run_stage_variants.sh)
+  //  stage 0: configs[1] 2.73e7 -> 2.76e7, against stepping back only in the sweep; one level lower still throughout their
+  //  sweep: no change)
   if constexpr (PRIO && !CMD && !ADMM && !BIG && !PHA) {
     if (PK.prio_cu && __builtin_amdgcn_readfirstlane(S.prio_rank) == 1) __builtin_amdgcn_s_setprio(2);
   }
-#endif
   {
     const double keep1[2] = {alpha, x_drag};
     (void)keep1;
@@ -1758,7 +1724,6 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
 #define QMPC_PIN __builtin_amdgcn_sched_barrier(0)
 #pragma unroll 1
     for (int kb = 0; kb < 4; ++kb) {
-#if QMPC_SWEEP_PRIO
       // Issue priority falls as the sweep advances.  Among equal priorities the SIMD
       // favours its OLDEST wave, so of the four workgroups of a CU the first one
       // dispatched used to sweep at full speed (24k cycles) and the last one at half
@@ -1768,7 +1733,6 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       else if (kb <= 1 || hfloor >= 2) __builtin_amdgcn_s_setprio(2);
       else if (kb == 2) __builtin_amdgcn_s_setprio(1);
       else __builtin_amdgcn_s_setprio(0);
-#endif
       StaticFor<0, CW / 2>::run([&](auto pc) __attribute__((always_inline)) {
         constexpr int r0 = 2 * decltype(pc)::value;
         constexpr int rn0 = (r0 + 2 < CW) ? r0 + 2 : 0, rn1 = rn0 + 1;
@@ -1784,9 +1748,6 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
           if (k0 + 2 < n && c == kbn) {
             // this wave owns the next pivot pair: its two columns first, then the
             // pivot-block inverse interleaved with the other twelve columns
-#if QMPC_PROD_PRIO
-            __builtin_amdgcn_s_setprio(3);  // (experiment: the producing wave's stream paces the pair)
-#endif
             fmac4_rowbcast<G0>(a, cv0, nu0);
             fmac4_rowbcast<G0>(a, cv1, nu1);
             QMPC_PIN;
@@ -1817,12 +1778,6 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
             prod_store(m + 1);
             QMPC_PIN;
             fmac4_rowbcast<G3>(a, cv1, nu1);
-#if QMPC_PROD_PRIO
-            if (hard || (kb == 0 && !staged)) __builtin_amdgcn_s_setprio(3);
-            else if (kb <= 1 || hfloor >= 2) __builtin_amdgcn_s_setprio(2);
-            else if (kb == 2) __builtin_amdgcn_s_setprio(1);
-            else __builtin_amdgcn_s_setprio(0);
-#endif
           } else if (c * CW < n) {
             // (a column group that lies entirely in the identity padding never changes:
             //  its pivot-column entries are zero)
@@ -1881,13 +1836,11 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     __syncthreads();
 #pragma unroll 1
     for (int kb = 0; kb < 4; ++kb) {
-#if QMPC_SWEEP_PRIO
       // see the class-1 loop: a wave that is ahead yields issue slots to the ones behind it
       if (hard || (kb == 0 && !staged)) __builtin_amdgcn_s_setprio(3);
       else if (kb <= 1 || hfloor >= 2) __builtin_amdgcn_s_setprio(2);
       else if (kb == 2) __builtin_amdgcn_s_setprio(1);
       else __builtin_amdgcn_s_setprio(0);
-#endif
       StaticFor<0, CW / 2>::run([&](auto pc) __attribute__((always_inline)) {
         constexpr int r0 = 2 * decltype(pc)::value;
         constexpr int rn0 = (r0 + 2 < CW) ? r0 + 2 : 0, rn1 = rn0 + 1;
@@ -2190,7 +2143,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       };
       double resid = __builtin_inf();
       double* const rv = Sb.D;  // rhs, broadcast through LDS
-      __builtin_amdgcn_s_setprio(QMPC_ENGINE_PRIO);
+      __builtin_amdgcn_s_setprio(3);
       for (int it = 1; it <= max_it; ++it) {
         // rhs = sigma x - q + A^T (R z - y)                                       (solveLinearSystem :315-323)
         const double w0 = rinf * z[0] - y[0], w1 = rinf * z[1] - y[1], w2 = rinf * z[2] - y[2],
@@ -2296,12 +2249,9 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     constexpr int NHELP = C::NHELP;
     // (LDS pool: the last NHELP records' worth of it holds the helper waves' partial sums)
     constexpr int KEV_L = ((C::NPOOL - (C::GLOBAL_EVENTS ? 0 : NHELP * EV)) / EV) & ~3, KEV_G = C::KEV_GLOBAL;
-#ifndef QMPC_TR_G
-#define QMPC_TR_G 4
-#endif
     // events per trip on a global pool.  (8 -- twice the loads in flight per wait -- measured: no faster, the
     // accumulation pays ~22 cycles per load instruction whatever the trip length, and it costs 20 VGPRs)
-    constexpr int TR_G = QMPC_TR_G;
+    constexpr int TR_G = 4;
     // this lane's entries of an index-major vector stored NP long: lanes past row NP (class 4:
     // 96 rows in two 64-lane blocks) read entry 0 -- harmless, those rows are never used -- and
     // do not write
@@ -2879,7 +2829,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
         need_p0 = need_p;
         return retry;
       };
-      __builtin_amdgcn_s_setprio(QMPC_ENGINE_PRIO);  // the serial part of the workgroup: win issue arbitration
+      __builtin_amdgcn_s_setprio(3);  // the serial part of the workgroup: win issue arbitration
       if constexpr (C::GLOBAL_EVENTS) {
         // (this workgroup's slice of the class's pool, taken in the kernel prologue)
         GlobalF64* const gpool = (GlobalF64*)P.evpool + (size_t)S.evslot * ((size_t)KEV_G * EV);
@@ -3049,7 +2999,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     const double inv_fr = P.inv_fr_norm;
     const double tol = P.tol;
     const int max_iter = P.max_iter;
-    __builtin_amdgcn_s_setprio(QMPC_ENGINE_PRIO);  // the serial part of the workgroup: win issue arbitration
+    __builtin_amdgcn_s_setprio(3);  // the serial part of the workgroup: win issue arbitration
     auto Hinv = [&](int r, int cidx) __attribute__((always_inline)) {
       const int hi = r > cidx ? r : cidx, lo = r > cidx ? cidx : r;
       return Sb.Hp[hi * (hi + 1) / 2 + lo];
@@ -3732,10 +3682,6 @@ __device__ __forceinline__ int size_order_take(const QmpcParams& P) {
   return (int)blockIdx.x;
 }
 
-#ifndef QMPC_LISTED_VARIANT
-#define QMPC_LISTED_VARIANT 2
-#endif
-
 // LISTED = false: the first class launched: robot = blockIdx.x; clears the NEXT call's list counters and queue
 // heads.  LISTED = true: every later class, launched with at most one workgroup per resident slot; it consumes
 // the list the previous classes filled as a queue: entry blockIdx.x first, then whatever entry the head counter
@@ -3754,8 +3700,7 @@ __global__ __launch_bounds__(Cfg<RB>::NT_LAUNCH, Cfg<RB>::MIN_WAVES) void qmpc_s
       for (int k = tid0; k < QMPC_COUNTERS; k += Cfg<RB>::NT) P.clear_counts[k] = 0;  // 3 counters + 3 heads
     if (blockIdx.x == 0 && tid0 == 0 && P.hint_max_z) *P.hint_max_z = 0;
     pool_acquire<RB>(S, P);
-    // (order hint: the previous call's hardest robots first; results do not depend on the order)
-    int rid = P.order ? __builtin_amdgcn_readfirstlane(P.order[blockIdx.x]) : (int)blockIdx.x;
+    int rid = (int)blockIdx.x;
     // (size order / order hint: the first workgroups build the permutation, a segment each, before they solve their own robots;
     //  the workgroups of the later rounds read it)
     if (P.so_order) {
@@ -3780,11 +3725,8 @@ __global__ __launch_bounds__(Cfg<RB>::NT_LAUNCH, Cfg<RB>::MIN_WAVES) void qmpc_s
       // opaque thread id per robot: nothing derived from it is loop-invariant, so the compiler cannot hoist
       // per-thread values out of the loop (and spill them across the whole solve)
       int tid1 = tid0;
-#if QMPC_LISTED_VARIANT >= 1
       asm volatile("" : "+v"(tid1));
       __builtin_assume(tid1 >= 0 && tid1 < Cfg<RB>::NT);
-#endif
-#if QMPC_LISTED_VARIANT >= 2
       // ... and an opaque kernel-argument pointer: the ~30 scalar loads of stage 0 stay inside the loop instead
       // of being hoisted into SGPRs that then spill (the parameter block is the only explicit kernel argument,
       // so it sits at offset 0 of the kernarg segment)
@@ -3793,9 +3735,6 @@ __global__ __launch_bounds__(Cfg<RB>::NT_LAUNCH, Cfg<RB>::MIN_WAVES) void qmpc_s
       asm volatile("" : "+s"(pk));
       const QmpcParams& PK = *(const QmpcParams*)pk;
       solve_robot<RB, CMD, WARM>(rid, tid1, S, PK);
-#else
-      solve_robot<RB, CMD, WARM>(rid, tid1, S, P);
-#endif
       __syncthreads();  // every wave is done with this robot's LDS state
       if (tid0 == 0) S.qnext = (int)gridDim.x + atomicAdd(P.qhead, 1);
       __syncthreads();

@@ -50,6 +50,39 @@ def timed(m, B, inp, out, steps, repeats=9):
     return float(np.median(ts))
 
 
+def run(b, so, steps, hints=True):
+    """One handle with qmpc_set_size_order(so): milliseconds per call and the outputs (soln, iters, status, grf)."""
+    B = int(b["batch"])
+    m = handle(b, B, False, stance=hints)
+    m.set_size_order(so)
+    d = m.upload(b)
+    o = m.alloc_outputs(B, full=True, iters=True)
+    inp, out = m.make_args(d, o)
+    ms = timed(m, B, inp, out, steps)
+    r = (o["soln"].cpu().numpy().copy(), o["iters"].cpu().numpy().copy(), o["status"].cpu().numpy().copy(), o["grf"].cpu().numpy().copy())
+    m.close()
+    return ms, r
+
+
+def ab(name, b, steps, hints=True):
+    """Size order off / on, alternated twice: rates, gain and bit-identity."""
+    B = int(b["batch"])
+    res = {"workload": name, "batch": B, "stance_hints": hints}
+    ms = {}
+    outs = {}
+    for so in (0, 1, 0, 1):
+        t, r = run(b, so, steps, hints)
+        ms.setdefault(so, []).append(t)
+        outs[so] = r
+    res["ms_off"], res["ms_on"] = ms[0], ms[1]
+    res["qps_off"] = B / min(ms[0]) * 1e3
+    res["qps_on"] = B / min(ms[1]) * 1e3
+    res["gain"] = min(ms[0]) / min(ms[1]) - 1.0
+    res["bit_identical"] = bool(all((outs[0][k] == outs[1][k]).all() for k in range(4)))
+    res["failed"] = int(((outs[1][2] & 47) != 0).sum())
+    return res
+
+
 def static(name, b, steps):
     B = int(b["batch"])
     res = {"workload": name, "batch": B}

@@ -8,7 +8,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 from quadruped_ctrl_amd import workloads as W
 from tools.size_order_study import permute, interleave
-from tools.size_order_ab import run
+from tools.order_hint import run
 
 
 def feats(b):

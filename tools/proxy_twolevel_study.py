@@ -6,7 +6,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 from quadruped_ctrl_amd import workloads as W
 from tools.size_order_study import permute, interleave
-from tools.size_order_ab import run
+from tools.order_hint import run
 from tools.proxy_order_study import feats
 out = []
 for name, b, steps, maxfit in (("cfg2", W.make_config(2), 40, 21), ("cfg2_8192", W.make_config(2, batch=8192), 20, 21), ("cfg4", W.make_config(4, batch=8192), 20, 21)):

@@ -7,7 +7,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 from quadruped_ctrl_amd import workloads as W
 from tools.size_order_study import permute
-from tools.size_order_ab import run
+from tools.order_hint import run
 from tools.proxy_order_study import feats
 out = []
 for name, b, steps in (("cfg3_4096", W.make_config(3, batch=4096), 10), ("cfg1_8192", W.make_config(1, batch=8192), 20), ("cfg1_4096", W.make_config(1, batch=4096), 30),

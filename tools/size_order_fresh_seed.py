@@ -6,7 +6,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
 from quadruped_ctrl_amd import workloads as W
-from tools.size_order_ab import ab, run
+from tools.order_hint import ab, run
 from tools.proxy2_study import score2
 out = []
 for seed in (777, 4242):

@@ -7,7 +7,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 from quadruped_ctrl_amd import workloads as W
 from tools.size_order_study import permute, interleave
-from tools.size_order_ab import run
+from tools.order_hint import run
 
 out = []
 for name, b, steps in (("cfg2_8192", W.make_config(2, batch=8192), 20), ("cfg4", W.make_config(4, batch=8192), 20), ("cfg2", W.make_config(2), 40)):
