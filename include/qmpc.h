@@ -213,6 +213,7 @@ int qmpc_set_order_hint(qmpc_handle h, int mode);
  *                            qmpc_set_chunks, qmpc_reserve) and the warm start across MPC cycles, which is
  *                            correct but measured slower than the cold solve (qmpc_set_warm_start, _min_iters);
  *   include/qmpc_debug.h  -- test and profiling hooks (qmpc_set_debug_*, qmpc_debug_*): used by tests/ and tools/ only.
+ * The batched locomotion controller built on this ABI (GaitCtrller's whole control tick) is declared in include/qmpc_ctrl.h.
  * Same shared library, same ABI version. */
 
 /* Solve `batch` independent MPC problems.  All pointers are DEVICE pointers

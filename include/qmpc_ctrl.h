@@ -1,0 +1,100 @@
+/*
+ * qmpc_ctrl.h -- batched locomotion controller on top of the C ABI of qmpc.h (same library, same ABI version).
+ *
+ * GaitCtrller::TorqueCalculator (src/GaitCtrller.cpp:95-145) for `batch` robots in lockstep: the orientation
+ * estimator (src/Controllers/OrientationEstimator.cpp:46-110), the Kalman filter, the safety checks
+ * (GaitCtrller.cpp:108-123, src/Controllers/SafetyChecker.cpp), ConvexMPCLocomotion::run
+ * (src/MPC_Ctrl/ConvexMPCLocomotion.cpp:116-496) with the MPC every 13 ticks, and LegController::updateCommand.
+ * Every piece of controller state lives on the device (allocated by qmpc_ctrl_init for the handle's max_batch
+ * robots); a tick only enqueues kernels on `stream`, so a run of ticks can be captured into a graph.
+ *
+ * Scope: robot mode 0 only -- the reference's fixed gaits at horizonLength 14 (ConvexMPCLocomotion.cpp:25-41,
+ * :149-171).  Robot mode 1 (the `aio` gait, :172-233) changes the horizon per robot (10 .. 32) and so splits a
+ * batch across several qmpc_setup horizons; it is not provided, and neither is a single-robot drop-in of the six
+ * GaitCtrller.h:63-99 symbols (the reference's walking_simulation.py starts in mode 1).
+ *
+ * Layouts (one row per robot, DEVICE pointers, the reference's own orders):
+ *   imu[B][10]    double: accelerometer x y z, quaternion x y z w, gyro x y z (GaitCtrller.cpp:34-45,
+ *                 OrientationEstimator.cpp:49-58)
+ *   motor[B][24]  double: q[3*leg + joint], then qd[3*leg + joint] (GaitCtrller.cpp:47-56)
+ *   effort[B][12] double: tau[3*leg + joint]; zeros for a robot whose safety flag has latched (:130-144)
+ *   vel[B][3]     double: x, y, yaw-rate command (SetRobotVel, :75-93: |v| < 0.03 reads 0)
+ *   gait[B]       int32: gait number 0 .. 11 (:149-171; 1 bounding, 2 pronking, 4 standing, 5 trot running,
+ *                 7 galloping, 8 pacing, 10 walking, 11 walking2, anything else trotting), +20 = omni mode (:129-132)
+ *
+ * Lockstep: the handle counts ticks (T).  Every robot's iterationCounter is congruent to T modulo 13, so the
+ * MPC runs for the whole batch on the same ticks -- one qmpc_solve_commands launch.  qmpc_ctrl_reset deviates
+ * from a fresh init_controller on exactly this point: a reset robot restarts with iterationCounter = T mod 13
+ * (not 0), i.e. its gait clock starts part-way into the first MPC segment.  A graph captured from the tick
+ * calls must hold a multiple of 13 ticks: T counts qmpc_ctrl_tick calls, captured ones included, and graph replays
+ * do not advance it (qmpc_ctrl_view's `ticks` is T, not the number of ticks executed).
+ *
+ * Errors: a tick that returns QMPC_ERR_DEVICE may have advanced some of the controller state (T and the counters
+ * advance together once the locomotion kernel is enqueued, so the MPC schedule stays consistent); re-initialise the
+ * controller (qmpc_ctrl_init) before relying on its state again.
+ *
+ * Every call takes the batch given to qmpc_ctrl_init (QMPC_ERR_ARG otherwise); QMPC_ERR_STATE before
+ * qmpc_ctrl_init.
+ */
+#ifndef QMPC_CTRL_H
+#define QMPC_CTRL_H
+
+#include "qmpc.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* GaitCtrller(freq, PIDParam) + init_controller: qmpc_setup(h, float(1 / freq) * 13, 14, 0.4, 120)
+ * (ConvexMPCLocomotion.cpp:23-42, :629-630), device state for max_batch robots, and the initial state of
+ * robots 0 .. batch-1: firstRun, firstSwing, f_ff = 0, Kalman filter setup(), contact phase 0.5
+ * (GaitCtrller.cpp:21-24), orientation first visit, safety flag set, iteration counters 0, gait 0, velocity
+ * command 0.  pid[2], pid[3] are the joint PD gains of LegController::updateCommand (ctrlParam(2..3)).
+ * The handle's max_horizon must be at least 14.  Synchronises the device (allocation); resets T to 0. */
+int qmpc_ctrl_init(qmpc_handle h, int batch, double freq, const double pid[4], void* stream);
+
+/* Re-initialise the robots whose mask_dev[b] (uint8, device) is non-zero exactly as qmpc_ctrl_init does, except
+ * that their iteration counter restarts at T mod 13 (see Lockstep above).  The other robots are untouched. */
+int qmpc_ctrl_reset(qmpc_handle h, int batch, const uint8_t* mask_dev, void* stream);
+
+/* set_gait_type for every robot (gait_dev: int32 [B], device). */
+int qmpc_ctrl_set_gait(qmpc_handle h, int batch, const int32_t* gait_dev, void* stream);
+
+/* set_robot_vel for every robot (vel_dev: double [B][3], device), with its 0.03 dead band. */
+int qmpc_ctrl_set_vel(qmpc_handle h, int batch, const double* vel_dev, void* stream);
+
+/* pre_work (GaitCtrller.cpp:58-63): the estimators (orientation, Kalman filter) and the leg data. */
+int qmpc_ctrl_prework(qmpc_handle h, int batch, const double* imu, const double* motor, void* stream);
+
+/* torque_calculator (GaitCtrller.cpp:95-145): pre_work, the safety checks, one ConvexMPCLocomotion::run tick
+ * (the MPC when the incremented counter is a multiple of 13) and the leg commands -> effort[B][12]. */
+int qmpc_ctrl_tick(qmpc_handle h, int batch, const double* imu, const double* motor, double* effort, void* stream);
+
+/* Read-only device views of the controller state (valid until the handle is destroyed or re-initialised). */
+typedef struct {
+  const float* position;      /* [B][3]  state estimate (StateEstimate<float>) */
+  const float* v_world;       /* [B][3] */
+  const float* orientation;   /* [B][4]  w, x, y, z */
+  const float* rpy;           /* [B][3] */
+  const float* r_body;        /* [B][9]  row-major */
+  const float* omega_world;   /* [B][3] */
+  const float* leg_q;         /* [B][12] datas[leg].q after checkJointLimit's clamp */
+  const float* leg_p;         /* [B][12] datas[leg].p (hip frame) */
+  const float* leg_v;         /* [B][12] datas[leg].v */
+  const float* leg_J;         /* [B][4][9] datas[leg].J */
+  const float* contact_state; /* [B][4]  gait->getContactState() of the last tick */
+  const float* swing_state;   /* [B][4]  gait->getSwingState(); > 0: the foot swings */
+  const float* p_des;         /* [B][12] commands[leg].pDes (hip frame) */
+  const float* v_des;         /* [B][12] commands[leg].vDes */
+  const float* f_ff;          /* [B][12] body-frame forces of the last MPC solve, f_ff[3*leg + axis] */
+  const int32_t* safe;        /* [B]     GaitCtrller::_safetyCheck (1 = effort is passed on) */
+  const int32_t* counter;     /* [B]     iterationCounter */
+  int batch;                  /* robots initialised */
+  int ticks;                  /* T */
+} qmpc_ctrl_view;
+int qmpc_ctrl_view_get(qmpc_handle h, qmpc_ctrl_view* v);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* QMPC_CTRL_H */

@@ -71,6 +71,13 @@ int qmpc_set_debug_clock(qmpc_handle h, long long* clk_dev);
 int qmpc_debug_keys(qmpc_handle h, int batch, const qmpc_inputs* in, int32_t* nst_dev, float* score_dev, float* demand_dev,
                     void* stream);
 
+/* Test hook: copies one array of the locomotion controller's device state (qmpc_ctrl.h) for the initialised batch to `dst`
+ * (host or device memory, cap_bytes large enough), after the handle's stream has finished.  Names are the members of
+ * QmpcCtrlDev (quadruped_ctrl_amd/csrc/qmpc_glue.h), e.g. "p_foot", "sw_p", "counter"; every element is 4 bytes (float or
+ * int32), `*per_robot` (may be NULL) receives the elements per robot, also when cap_bytes is too small (QMPC_ERR_ARG, nothing copied).
+ * QMPC_ERR_ARG for an unknown name. */
+int qmpc_debug_ctrl_read(qmpc_handle h, const char* name, void* dst, long long cap_bytes, int* per_robot);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libqmpc.so")
 
 QMPC_OK = 0
-ABI_VERSION = 22              # qmpc_abi_version() this binding was written against
+ABI_VERSION = 23              # qmpc_abi_version() this binding was written against
 ST_MAXITER, ST_NOT_PD, ST_INFEASIBLE, ST_WS_FULL, ST_FALLBACK = 1, 2, 4, 8, 16
 ST_COMPACTED, ST_SPILLED = 64, 128
 ST_NONFINITE = 32
@@ -26,7 +26,16 @@ EXPORTS = ["qmpc_abi_version", "qmpc_last_error", "qmpc_create", "qmpc_destroy",
            "qmpc_set_debug_aux", "qmpc_set_debug_overflow_slices", "qmpc_solve_sharded", "qmpc_set_leg_geometry",
            "qmpc_leg_kinematics", "qmpc_leg_torques", "qmpc_swing_trajectory", "qmpc_set_warm_start", "qmpc_settings_jcqp", "qmpc_kf_init", "qmpc_kf_step", "qmpc_set_model",
            "qmpc_max_horizon", "qmpc_set_debug_pool_busy", "qmpc_set_split", "qmpc_reserve", "qmpc_set_debug_engine_events", "qmpc_set_chunks", "qmpc_debug_read_item", "qmpc_debug_read_counts", "qmpc_set_dense", "qmpc_set_size_order", "qmpc_debug_keys", "qmpc_set_order_hint", "qmpc_set_debug_balance",
-           "qmpc_set_warm_start_min_iters", "qmpc_set_debug_overflow_spin"]
+           "qmpc_set_warm_start_min_iters", "qmpc_set_debug_overflow_spin", "qmpc_debug_ctrl_read"]
+# the batched locomotion controller's own header (include/qmpc_ctrl.h), same library and ABI version
+CTRL_EXPORTS = ["qmpc_ctrl_init", "qmpc_ctrl_reset", "qmpc_ctrl_set_gait", "qmpc_ctrl_set_vel", "qmpc_ctrl_prework",
+                "qmpc_ctrl_tick", "qmpc_ctrl_view_get"]
+
+# qmpc_ctrl_view's float arrays (include/qmpc_ctrl.h) in declaration order, elements per robot
+CTRL_VIEW_FIELDS = ("position", "v_world", "orientation", "rpy", "r_body", "omega_world", "leg_q", "leg_p", "leg_v",
+                    "leg_J", "contact_state", "swing_state", "p_des", "v_des", "f_ff")
+CTRL_VIEW_WIDTH = dict(position=3, v_world=3, orientation=4, rpy=3, r_body=9, omega_world=3, leg_q=12, leg_p=12, leg_v=12,
+                       leg_J=36, contact_state=4, swing_state=4, p_des=12, v_des=12, f_ff=12, safe=1, counter=1)
 
 KF_FIELDS = ("xhat", "P", "r_body", "a_world", "omega_body", "contact_phase", "leg_p", "leg_v", "position", "v_world", "v_body")
 
@@ -66,6 +75,12 @@ class Record(C.Structure):
 class KfState(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("xhat", "P", "r_body", "a_world", "omega_body", "contact_phase", "leg_p", "leg_v",
                                           "position", "v_world", "v_body")]
+
+
+class CtrlView(C.Structure):
+    """qmpc_ctrl_view (include/qmpc_ctrl.h)."""
+    _fields_ = [(n, C.c_void_p) for n in CTRL_VIEW_FIELDS] + [("safe", C.c_void_p), ("counter", C.c_void_p),
+                                                                ("batch", C.c_int), ("ticks", C.c_int)]
 
 
 class LegCommand(C.Structure):
@@ -150,6 +165,14 @@ def load_library():
         lib.qmpc_pack.argtypes = [C.c_void_p, C.c_int, C.POINTER(Command), C.POINTER(Record), C.c_void_p]
         lib.qmpc_solve_commands.argtypes = [C.c_void_p, C.c_int, C.POINTER(Command), C.POINTER(Outputs), C.c_void_p,
                                             C.c_void_p]
+        lib.qmpc_debug_ctrl_read.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_longlong, C.POINTER(C.c_int)]
+        lib.qmpc_ctrl_init.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double), C.c_void_p]
+        lib.qmpc_ctrl_reset.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.qmpc_ctrl_set_gait.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.qmpc_ctrl_set_vel.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.qmpc_ctrl_prework.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.qmpc_ctrl_tick.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.qmpc_ctrl_view_get.argtypes = [C.c_void_p, C.POINTER(CtrlView)]
         lib.qmpc_forces_to_body.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = lib
     return _lib
@@ -587,3 +610,109 @@ class BatchedConvexMPC:
         self.lib.qmpc_set_debug_aux(self.h, None)
         self._dbg = None
         self._dbg_aux = None
+
+
+class BatchedController:
+    """GaitCtrller::TorqueCalculator for `batch` robots in lockstep on one GPU (include/qmpc_ctrl.h), robot mode 0.
+
+    The reference's single-robot calls map one to one: init_controller -> init(), set_gait_type -> set_gait(),
+    set_robot_vel -> set_vel(), pre_work -> prework(), torque_calculator -> tick(); reset() re-initialises chosen
+    robots (RL episode ends).  Arguments are torch tensors on the controller's device: imu [B,10] and motor [B,24]
+    float64 in the reference's layouts, gait [B] int32, vel [B,3] float64, mask [B] bool / uint8.  Every call only
+    enqueues work on the current stream (or `stream`); view() and read() synchronise.  Owns its BatchedConvexMPC
+    (`self.mpc`), whose handle holds the controller state."""
+
+    def __init__(self, device=0, max_batch=4096):
+        self.mpc = BatchedConvexMPC(device, max_batch=max_batch, max_horizon=16)
+        self.torch, self.lib, self.device = self.mpc.torch, self.mpc.lib, self.mpc.device
+        self.batch = None
+
+    def close(self):
+        self.mpc.close()
+
+    def _s(self, stream):
+        return self.mpc._stream_ptr(stream)
+
+    def _chk(self, t, shape, dtype, what):
+        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+            raise QmpcError(f"{what}: expected a contiguous {dtype} tensor of shape {tuple(shape)} on {self.device}")
+        return t.data_ptr()
+
+    def init(self, batch, freq=500.0, pid=(0.0, 0.0, 0.0, 0.0), stream=None):
+        """GaitCtrller(freq, PIDParam) for robots 0 .. batch-1; pid[2], pid[3] are the joint PD gains."""
+        pid_c = (C.c_double * 4)(*[float(x) for x in pid])
+        self.mpc._check(self.lib.qmpc_ctrl_init(self.mpc.h, int(batch), float(freq), pid_c, self._s(stream)), "qmpc_ctrl_init")
+        self.batch = int(batch)
+        self.mpc.horizon = 14
+
+    def reset(self, mask, stream=None):
+        """Re-initialise the robots where mask is set; their iteration counter restarts at T mod 13 (lockstep)."""
+        m = mask.to(self.torch.uint8).contiguous() if mask is not None else None
+        ptr = self._chk(m, (self.batch,), self.torch.uint8, "mask") if m is not None else None
+        self.mpc._check(self.lib.qmpc_ctrl_reset(self.mpc.h, self.batch or 0, ptr, self._s(stream)), "qmpc_ctrl_reset")
+        self._keep = m   # (alive until the next call: the launch reads it asynchronously)
+
+    def set_gait(self, gait, stream=None):
+        """set_gait_type: gait numbers 0 .. 11, +20 for omni mode."""
+        ptr = self._chk(gait, (self.batch,), self.torch.int32, "gait")
+        self.mpc._check(self.lib.qmpc_ctrl_set_gait(self.mpc.h, self.batch, ptr, self._s(stream)), "qmpc_ctrl_set_gait")
+
+    def set_vel(self, vel, stream=None):
+        """set_robot_vel: [B,3] float64 (x, y, yaw rate), dead band 0.03."""
+        ptr = self._chk(vel, (self.batch, 3), self.torch.float64, "vel")
+        self.mpc._check(self.lib.qmpc_ctrl_set_vel(self.mpc.h, self.batch, ptr, self._s(stream)), "qmpc_ctrl_set_vel")
+
+    def prework(self, imu, motor, stream=None):
+        """pre_work: the estimators and the leg data, no control."""
+        a = self._chk(imu, (self.batch, 10), self.torch.float64, "imu")
+        b = self._chk(motor, (self.batch, 24), self.torch.float64, "motor")
+        self.mpc._check(self.lib.qmpc_ctrl_prework(self.mpc.h, self.batch, a, b, self._s(stream)), "qmpc_ctrl_prework")
+
+    def tick(self, imu, motor, effort=None, stream=None):
+        """torque_calculator for every robot -> effort [B,12] float64 (zeros for a latched robot)."""
+        if self.batch is None:
+            raise QmpcError("qmpc_ctrl_tick before init()")
+        a = self._chk(imu, (self.batch, 10), self.torch.float64, "imu")
+        b = self._chk(motor, (self.batch, 24), self.torch.float64, "motor")
+        if effort is None:
+            effort = self.torch.empty((self.batch, 12), dtype=self.torch.float64, device=self.device)
+        e = self._chk(effort, (self.batch, 12), self.torch.float64, "effort")
+        self.mpc._check(self.lib.qmpc_ctrl_tick(self.mpc.h, self.batch, a, b, e, self._s(stream)), "qmpc_ctrl_tick")
+        return effort
+
+    def read(self, name):
+        """One array of the controller's device state (qmpc_debug_ctrl_read) -> numpy [B, n] (float32 or int32)."""
+        per = C.c_int(0)
+        self.lib.qmpc_debug_ctrl_read(self.mpc.h, name.encode(), np.zeros(1, np.float32).ctypes.data, 0, C.byref(per))
+        if per.value == 0:
+            raise QmpcError(f"qmpc_debug_ctrl_read: no controller array {name!r} (or no init())")
+        out = np.zeros((self.batch, per.value), np.float32)
+        self.mpc._check(self.lib.qmpc_debug_ctrl_read(self.mpc.h, name.encode(), out.ctypes.data, out.nbytes, C.byref(per)),
+                        f"qmpc_debug_ctrl_read({name})")
+        if name in ("counter", "first_run", "first_swing", "first_visit", "gait_num", "current_gait", "offsets", "durations",
+                    "iteration", "safe", "status"):
+            out = out.view(np.int32)
+        return out
+
+    def view(self):
+        """qmpc_ctrl_view_get as zero-copy torch device tensors ([B, n]; safe / counter int32) that ALIAS the controller's
+        state: no copy, no synchronisation; they show what the last enqueued work left once the stream has reached it,
+        and are valid until close() or the next init().  Read-only by contract.  Plus batch and ticks (T: the ticks
+        enqueued since init, captured ones included)."""
+        v = CtrlView()
+        self.mpc._check(self.lib.qmpc_ctrl_view_get(self.mpc.h, C.byref(v)), "qmpc_ctrl_view_get")
+        res = {}
+        for k, n in CTRL_VIEW_WIDTH.items():
+            typestr = "<i4" if k in ("safe", "counter") else "<f4"
+            res[k] = self.torch.as_tensor(_DeviceArray(getattr(v, k), (v.batch, n), typestr, self), device=self.device)
+        res["batch"], res["ticks"] = v.batch, v.ticks
+        return res
+
+
+class _DeviceArray:
+    """__cuda_array_interface__ over a device pointer of the controller; keeps its owner alive while a tensor uses it."""
+
+    def __init__(self, ptr, shape, typestr, owner):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False),
+                                         "version": 2}
+        self.owner = owner

@@ -11,12 +11,15 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/qmpc.h"
 #include "../../include/qmpc_debug.h"   // test / profiling hooks (same library)
 #include "../../include/qmpc_expert.h"  // tuning knobs whose default is the measured optimum, warm start
+#include "../../include/qmpc_ctrl.h"    // batched locomotion controller (same library)
 #include "qmpc_device.h"
+#include "qmpc_glue.h"
 
 // per-class entry points of qmpc_kernels.hip (one translation unit per size class)
 #define QMPC_DECLARE_CLASS(RB)                                                                  \
@@ -95,6 +98,14 @@ extern "C" hipError_t qmpc_launch_leg_cmd(const float geom[4], const qmpc_leg_co
                                           int batch, hipStream_t stream);
 extern "C" hipError_t qmpc_launch_kf(const qmpc_kf_state* st, const float hip[3], int batch, hipStream_t stream);
 extern "C" hipError_t qmpc_launch_kf_init(float* xhat, float* P, int batch, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_ctrl_init(const QmpcCtrlDev* S, const uint8_t* mask, int counter0, int batch,
+                                            hipStream_t stream);
+extern "C" hipError_t qmpc_launch_ctrl_set(const QmpcCtrlDev* S, const int32_t* gait, const double* vel, int batch,
+                                           hipStream_t stream);
+extern "C" hipError_t qmpc_launch_ctrl_est(const QmpcCtrlDev* S, const float geom[4], const double* imu,
+                                           const double* motor, int batch, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_ctrl_loco(const QmpcCtrlDev* S, int batch, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_ctrl_legcmd(const QmpcCtrlDev* S, double* effort, int batch, hipStream_t stream);
 extern "C" hipError_t qmpc_launch_swing(const float* p0, const float* pf, const float* height, const float* phase,
                                         const float* swing_time, float* p, float* v, float* a, int n_feet,
                                         hipStream_t stream);
@@ -196,6 +207,14 @@ struct qmpc_ctx {
   int tab_h = -1, tab_model = -1;
   int model = 0;         // QMPC_MODEL_*
   std::string err;
+  // batched locomotion controller (qmpc_ctrl.h): device state for max_batch robots, made by qmpc_ctrl_init
+  struct Ctrl {
+    QmpcCtrlDev d{};
+    void* buf = nullptr;
+    int batch = 0;       // robots initialised
+    long long ticks = 0; // T: qmpc_ctrl_tick calls since qmpc_ctrl_init
+  };
+  Ctrl* ctrl = nullptr;
 };
 
 namespace {
@@ -252,7 +271,7 @@ int ensure_pools(qmpc_ctx* c);
 
 extern "C" {
 
-int qmpc_abi_version(void) { return 22; }  // 22: the engine's block-start setter (expert) removed; no signature changed
+int qmpc_abi_version(void) { return 23; }  // 23: the batched locomotion controller (qmpc_ctrl.h) added; no signature changed
 int qmpc_max_horizon(void) { return QMPC_MAX_HORIZON; }
 
 const char* qmpc_last_error(qmpc_handle h) { return h ? h->err.c_str() : "null handle"; }
@@ -344,7 +363,9 @@ int qmpc_destroy(qmpc_handle h) {
     if (h->order_ev) hipEventDestroy(h->order_ev);
     if (h->host_ev) hipEventDestroy(h->host_ev);
     if (h->host_stream) hipStreamDestroy(h->host_stream);
+    if (h->ctrl && h->ctrl->buf) hipFree(h->ctrl->buf);
   }
+  delete h->ctrl;
   delete h;
   return QMPC_OK;
 }
@@ -1363,6 +1384,226 @@ int qmpc_solve_sharded(const qmpc_handle* handles, int n_handles, int batch, con
     if (rc != QMPC_OK && rc_all == QMPC_OK) rc_all = rc;
   }
   return rc_all;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
+// Batched locomotion controller (include/qmpc_ctrl.h).  The kernels are in qmpc_glue.hip.
+namespace {
+
+// Lay the controller's arrays out in one allocation (base == nullptr: only count), each array 256-byte aligned
+size_t ctrl_carve(QmpcCtrlDev& d, char* base, int M) {
+  size_t off = 0;
+  auto take = [&](auto*& p, int per_robot) {
+    using T = std::remove_reference_t<decltype(*p)>;
+    off = (off + 255) & ~(size_t)255;
+    p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += sizeof(T) * (size_t)per_robot * (size_t)M;
+  };
+  take(d.q, 12); take(d.qd, 12); take(d.leg_J, 36); take(d.leg_p, 12); take(d.leg_v, 12); take(d.kf_p, 12);
+  take(d.kf_v, 12); take(d.orientation, 4); take(d.rpy, 3); take(d.r_body, 9); take(d.omega_body, 3);
+  take(d.omega_world, 3); take(d.a_world, 3); take(d.ori_ini_inv, 4); take(d.xhat, 18); take(d.P, 324);
+  take(d.position, 3); take(d.v_world, 3); take(d.v_body, 3); take(d.contact_phase, 4); take(d.vel_cmd, 3);
+  take(d.vel_des, 3); take(d.yaw_des, 1); take(d.yaw_des_true, 1); take(d.rpy_int, 2); take(d.rpy_comp, 2);
+  take(d.stand_traj, 6); take(d.wpd, 2); take(d.xci, 1); take(d.p_foot, 12); take(d.r_cmd, 9); take(d.sw_p0, 12);
+  take(d.sw_pf, 12); take(d.sw_p, 12); take(d.sw_v, 12); take(d.swing_time, 4); take(d.swing_rem, 4);
+  take(d.contact_state, 4); take(d.swing_state, 4); take(d.p_des, 12); take(d.v_des, 12); take(d.f_ff, 12);
+  take(d.grf, 12); take(d.pf_rel, 8); take(d.counter, 1); take(d.first_run, 1); take(d.first_swing, 4); take(d.first_visit, 1);
+  take(d.gait_num, 1); take(d.current_gait, 1); take(d.offsets, 4); take(d.durations, 4); take(d.iteration, 1);
+  take(d.safe, 1); take(d.status, 1);
+  return off;
+}
+
+int ctrl_check(qmpc_ctx* c, int batch) {
+  if (!c) return QMPC_ERR_ARG;
+  if (!c->ctrl || !c->ctrl->batch) return QMPC_ERR_STATE;
+  if (batch != c->ctrl->batch) return QMPC_ERR_ARG;
+  return QMPC_OK;
+}
+
+// pre_work: orientation estimator + leg data, then the Kalman filter (previous tick's leg data and contact phase)
+int ctrl_prework(qmpc_ctx* c, const double* imu, const double* motor, hipStream_t stream) {
+  const QmpcCtrlDev& d = c->ctrl->d;
+  const int B = c->ctrl->batch;
+  HIP_TRY(c, qmpc_launch_ctrl_est(&d, c->leg_geom, imu, motor, B, stream));
+  qmpc_kf_state st{d.xhat, d.P, d.r_body, d.a_world, d.omega_body, d.contact_phase, d.kf_p, d.kf_v,
+                   d.position, d.v_world, d.v_body};
+  static const float hip[3] = {0.19f, 0.049f, 0.f};  // _abadLocation (MiniCheetah.h:25-26,105)
+  HIP_TRY(c, qmpc_launch_kf(&st, hip, B, stream));
+  return QMPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qmpc_ctrl_init(qmpc_handle c, int batch, double freq, const double pid[4], void* stream_) {
+  if (!c || !pid || batch <= 0 || batch > c->max_batch || !(freq > 0) || c->max_horizon < 14) return QMPC_ERR_ARG;
+  // ConvexMPCLocomotion(1.0 / freq, 13): float dt, dtMPC = dt * iterationsBetweenMPC (:23-42); setup_problem(dtMPC, 14,
+  // 0.4, 120) (:629-630)
+  const float dt = (float)(1.0 / freq);
+  const float dt_mpc = dt * 13;
+  if (const int rc = qmpc_setup(c, (double)dt_mpc, 14, 0.4, 120.0)) return rc;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!c->ctrl) c->ctrl = new qmpc_ctx::Ctrl();
+  qmpc_ctx::Ctrl* k = c->ctrl;
+  if (!k->buf) {
+    const size_t bytes = ctrl_carve(k->d, nullptr, c->max_batch);
+    HIP_TRY(c, hipMalloc(&k->buf, bytes));
+  }
+  ctrl_carve(k->d, static_cast<char*>(k->buf), c->max_batch);
+  k->d.dt = dt;
+  k->d.dt_mpc = dt_mpc;
+  k->d.kp_joint = (float)pid[2];  // Vec4<float> ctrlParam (GaitCtrller.cpp:14-16)
+  k->d.kd_joint = (float)pid[3];
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  HIP_TRY(c, qmpc_launch_ctrl_init(&k->d, nullptr, 0, batch, stream));
+  k->batch = batch;
+  k->ticks = 0;
+  return QMPC_OK;
+}
+
+int qmpc_ctrl_reset(qmpc_handle c, int batch, const uint8_t* mask_dev, void* stream_) {
+  if (const int rc = ctrl_check(c, batch)) return rc;
+  if (!mask_dev) return QMPC_ERR_ARG;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  HIP_TRY(c, qmpc_launch_ctrl_init(&c->ctrl->d, mask_dev, (int)(c->ctrl->ticks % 13), batch, stream));
+  return QMPC_OK;
+}
+
+int qmpc_ctrl_set_gait(qmpc_handle c, int batch, const int32_t* gait_dev, void* stream_) {
+  if (const int rc = ctrl_check(c, batch)) return rc;
+  if (!gait_dev) return QMPC_ERR_ARG;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  HIP_TRY(c, qmpc_launch_ctrl_set(&c->ctrl->d, gait_dev, nullptr, batch, stream));
+  return QMPC_OK;
+}
+
+int qmpc_ctrl_set_vel(qmpc_handle c, int batch, const double* vel_dev, void* stream_) {
+  if (const int rc = ctrl_check(c, batch)) return rc;
+  if (!vel_dev) return QMPC_ERR_ARG;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  HIP_TRY(c, qmpc_launch_ctrl_set(&c->ctrl->d, nullptr, vel_dev, batch, stream));
+  return QMPC_OK;
+}
+
+int qmpc_ctrl_prework(qmpc_handle c, int batch, const double* imu, const double* motor, void* stream_) {
+  if (const int rc = ctrl_check(c, batch)) return rc;
+  if (!imu || !motor) return QMPC_ERR_ARG;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  return ctrl_prework(c, imu, motor, stream);
+}
+
+int qmpc_ctrl_tick(qmpc_handle c, int batch, const double* imu, const double* motor, double* effort, void* stream_) {
+  if (const int rc = ctrl_check(c, batch)) return rc;
+  if (!imu || !motor || !effort) return QMPC_ERR_ARG;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  qmpc_ctx::Ctrl* k = c->ctrl;
+  const QmpcCtrlDev& d = k->d;
+  if (const int rc = ctrl_prework(c, imu, motor, stream)) return rc;
+  HIP_TRY(c, qmpc_launch_ctrl_loco(&d, batch, stream));
+  // the locomotion kernel advances every robot's counter: T follows it here, before the launches that can still fail,
+  // so that the host's MPC schedule and the device's `counter % 13` test never disagree
+  const bool mpc_tick = ++k->ticks % 13 == 0;  // every robot's incremented counter is a multiple of 13 (lockstep)
+  if (mpc_tick) {
+    qmpc_command cmd{};
+    cmd.position = d.position;
+    cmd.v_world = d.v_world;
+    cmd.omega_world = d.omega_world;
+    cmd.orientation = d.orientation;
+    cmd.rpy = d.rpy;
+    cmd.r_body = d.r_cmd;
+    cmd.p_foot = d.p_foot;
+    cmd.vel_des = d.vel_des;
+    cmd.yaw_des_true = d.yaw_des_true;
+    cmd.rpy_comp = d.rpy_comp;
+    cmd.stand_traj = d.stand_traj;
+    cmd.rp_des = nullptr;  // _roll_des = _pitch_des = 0 (:112-113)
+    cmd.gait_type = d.current_gait;
+    cmd.gait_offsets = d.offsets;
+    cmd.gait_durations = d.durations;
+    cmd.gait_iteration = d.iteration;
+    cmd.world_position_desired = d.wpd;
+    cmd.x_comp_integral = d.xci;
+    cmd.body_height = 0.25f;  // _SetupCommand (:79)
+    cmd.omni_mode = 0;        // per robot through r_cmd
+    qmpc_outputs out{d.grf, nullptr, d.status, nullptr};
+    if (const int rc = qmpc_solve_commands(c, batch, &cmd, &out, nullptr, stream)) return rc;
+  }
+  HIP_TRY(c, qmpc_launch_ctrl_legcmd(&d, effort, batch, stream));
+  return QMPC_OK;
+}
+
+int qmpc_debug_ctrl_read(qmpc_handle c, const char* name, void* dst, long long cap_bytes, int* per_robot) {
+  if (!c || !name || !dst) return QMPC_ERR_ARG;
+  if (!c->ctrl || !c->ctrl->batch) return QMPC_ERR_STATE;
+  const QmpcCtrlDev& d = c->ctrl->d;
+  struct Arr {
+    const char* n;
+    const void* p;
+    int per;
+  };
+#define QA(f, k) {#f, d.f, k}
+  const Arr tab[] = {QA(q, 12), QA(qd, 12), QA(leg_J, 36), QA(leg_p, 12), QA(leg_v, 12), QA(kf_p, 12), QA(kf_v, 12),
+                     QA(orientation, 4), QA(rpy, 3), QA(r_body, 9), QA(omega_body, 3), QA(omega_world, 3),
+                     QA(a_world, 3), QA(ori_ini_inv, 4), QA(xhat, 18), QA(P, 324), QA(position, 3), QA(v_world, 3),
+                     QA(v_body, 3), QA(contact_phase, 4), QA(vel_cmd, 3), QA(vel_des, 3), QA(yaw_des, 1),
+                     QA(yaw_des_true, 1), QA(rpy_int, 2), QA(rpy_comp, 2), QA(stand_traj, 6), QA(wpd, 2), QA(xci, 1),
+                     QA(p_foot, 12), QA(r_cmd, 9), QA(sw_p0, 12), QA(sw_pf, 12), QA(sw_p, 12), QA(sw_v, 12),
+                     QA(swing_time, 4), QA(swing_rem, 4), QA(contact_state, 4), QA(swing_state, 4), QA(p_des, 12),
+                     QA(v_des, 12), QA(f_ff, 12), QA(grf, 12), QA(pf_rel, 8), QA(counter, 1), QA(first_run, 1), QA(first_swing, 4),
+                     QA(first_visit, 1), QA(gait_num, 1), QA(current_gait, 1), QA(offsets, 4), QA(durations, 4),
+                     QA(iteration, 1), QA(safe, 1), QA(status, 1)};
+#undef QA
+  for (const Arr& a : tab) {
+    if (std::strcmp(a.n, name) != 0) continue;
+    const size_t bytes = (size_t)4 * a.per * (size_t)c->ctrl->batch;
+    if (per_robot) *per_robot = a.per;
+    if (cap_bytes < 0 || (size_t)cap_bytes < bytes) return QMPC_ERR_ARG;
+    DeviceGuard g(c->device);
+    if (c->has_last) HIP_TRY(c, hipStreamSynchronize(c->last_stream));
+    HIP_TRY(c, hipMemcpy(dst, a.p, bytes, hipMemcpyDefault));
+    return QMPC_OK;
+  }
+  return QMPC_ERR_ARG;
+}
+
+int qmpc_ctrl_view_get(qmpc_handle c, qmpc_ctrl_view* v) {
+  if (!c || !v) return QMPC_ERR_ARG;
+  if (!c->ctrl || !c->ctrl->batch) return QMPC_ERR_STATE;
+  const QmpcCtrlDev& d = c->ctrl->d;
+  v->position = d.position;
+  v->v_world = d.v_world;
+  v->orientation = d.orientation;
+  v->rpy = d.rpy;
+  v->r_body = d.r_body;
+  v->omega_world = d.omega_world;
+  v->leg_q = d.q;
+  v->leg_p = d.leg_p;
+  v->leg_v = d.leg_v;
+  v->leg_J = d.leg_J;
+  v->contact_state = d.contact_state;
+  v->swing_state = d.swing_state;
+  v->p_des = d.p_des;
+  v->v_des = d.v_des;
+  v->f_ff = d.f_ff;
+  v->safe = d.safe;
+  v->counter = d.counter;
+  v->batch = c->ctrl->batch;
+  v->ticks = (int)c->ctrl->ticks;
+  return QMPC_OK;
 }
 
 }  // extern "C"

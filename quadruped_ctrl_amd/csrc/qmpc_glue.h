@@ -106,4 +106,83 @@ __device__ __forceinline__ void qmpc_swing_axis(int axis, float p0, float pf, fl
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Batched locomotion controller (include/qmpc_ctrl.h): the device state of GaitCtrller / ConvexMPCLocomotion for
+// every robot, one row per robot in every array.  Views into two allocations made by qmpc_ctrl_init.
+struct QmpcCtrlDev {
+  // inputs of the tick, rounded to float like VectorNavData / LegData (GaitCtrller.cpp:34-56)
+  float *q, *qd;                          // [B][12] datas[leg].q (clamped by checkJointLimit), .qd
+  float *leg_J, *leg_p, *leg_v;           // [B][36], [B][12], [B][12] datas[leg].J, .p, .v of this tick
+  float *kf_p, *kf_v;                     // [B][12] the previous tick's .p, .v: what the Kalman filter reads
+  // StateEstimate
+  float *orientation, *rpy, *r_body, *omega_body, *omega_world, *a_world;  // [B][4] [B][3] [B][9] [B][3] x 3
+  float *ori_ini_inv;                     // [B][4] VectorNavOrientationEstimator::_ori_ini_inv
+  float *xhat, *P;                        // [B][18], [B][324] LinearKFPositionVelocityEstimator
+  float *position, *v_world, *v_body;     // [B][3]
+  float *contact_phase;                   // [B][4] StateEstimatorContainer contactPhase
+  // ConvexMPCLocomotion members
+  float *vel_cmd;                         // [B][3] _gamepadCommand after SetRobotVel's dead band
+  float *vel_des;                         // [B][3] _x_vel_des, _y_vel_des, _yaw_turn_rate
+  float *yaw_des, *yaw_des_true;          // [B]
+  float *rpy_int, *rpy_comp;              // [B][2]
+  float *stand_traj;                      // [B][6]
+  float *wpd;                             // [B][2] world_position_desired
+  float *xci;                             // [B]    x_comp_integral
+  float *p_foot;                          // [B][12] pFoot
+  float *r_cmd;                           // [B][9] rBody for the MPC command (identity in omni mode, see qmpc_ctrl_tick)
+  float *sw_p0, *sw_pf, *sw_p, *sw_v;     // [B][12] footSwingTrajectories[leg] _p0, _pf, _p, _v
+  float *swing_time, *swing_rem;          // [B][4] swingTimes, swingTimeRemaining
+  float *contact_state, *swing_state;     // [B][4]
+  float *p_des, *v_des;                   // [B][12] commands[leg].pDes, .vDes
+  float *f_ff, *grf;                      // [B][12] f_ff (body frame), grf (the solve's world-frame forces)
+  float *pf_rel;                          // [B][8]  pfx_rel, pfy_rel per leg after the clamp (:346-365), for tests
+  int *counter, *first_run, *first_swing; // [B], [B], [B][4]
+  int *first_visit;                       // [B] VectorNavOrientationEstimator::_b_first_visit
+  int *gait_num, *current_gait;           // [B] set_gait_type's number, current_gait (-1: none yet)
+  int *offsets, *durations, *iteration;   // [B][4], [B][4], [B] the selected gait (OffsetDurationGait)
+  int *safe;                              // [B] _safetyCheck
+  int *status;                            // [B] status of the last solve
+  float dt, dt_mpc;                       // ConvexMPCLocomotion::dt, dtMPC
+  float kp_joint, kd_joint;               // ctrlParam(2), ctrlParam(3)
+};
+
+// Mini Cheetah _abadLocation (MiniCheetah.h:25-26,105), Quadruped::getHipLocation (Quadruped.h:95-101)
+__device__ __forceinline__ void qmpc_hip_location(int leg, float* h) {
+  h[0] = (leg == 0 || leg == 1) ? 0.19f : -0.19f;
+  h[1] = (leg == 1 || leg == 3) ? 0.049f : -0.049f;
+  h[2] = 0.f;
+}
+
+// The reference's gaits at horizonLength 14 (ConvexMPCLocomotion.cpp:27-41) as picked by gait number in robot mode 0
+// (:149-172).  Vec4<int>(double) truncates: walking is offsets (0, 7, 3, 10), durations 10 (:37-38).
+__device__ __forceinline__ void qmpc_ctrl_gait(int gn, int* off, int* dur) {
+  int o0 = 0, o1 = 7, o2 = 7, o3 = 0, d = 7;  // trotting (0, 3, 6, 9 and everything unlisted)
+  if (gn == 1) { o0 = 7; o1 = 7; o2 = 0; o3 = 0; d = 6; }         // bounding
+  else if (gn == 2) { o1 = 0; o2 = 0; d = 6; }                    // pronking
+  else if (gn == 4) { o1 = 0; o2 = 0; d = 14; }                   // standing
+  else if (gn == 5) { d = 6; }                                    // trotRunning
+  else if (gn == 7) { o1 = 4; o2 = 7; o3 = 11; d = 7; }           // galloping
+  else if (gn == 8) { o0 = 7; o1 = 0; o2 = 7; o3 = 0; d = 7; }    // pacing
+  else if (gn == 10) { o1 = 7; o2 = 3; o3 = 10; d = 10; }         // walking
+  else if (gn == 11) { d = 10; }                                  // walking2
+  off[0] = o0; off[1] = o1; off[2] = o2; off[3] = o3;
+  dur[0] = dur[1] = dur[2] = dur[3] = d;
+}
+
+// OffsetDurationGait::getContactState / getSwingState (Gait.cpp:61-123) of one leg at _phase
+__device__ __forceinline__ void qmpc_ctrl_gait_state(float phase, int off, int dur, int n, float& contact, float& swing) {
+#pragma clang fp contract(off)
+  const float offF = (float)off / (float)n, durF = (float)dur / (float)n;  // setGaitParam (:36-37)
+  float pr = phase - offF;
+  if (pr < 0) pr = pr + 1.f;
+  contact = (pr > durF) ? 0.f : pr / durF;
+  float so = offF + durF;
+  if (so > 1) so = so - 1.f;
+  const float sd = 1.f - durF;
+  pr = phase - so;
+  if (pr < 0) pr = pr + 1.f;
+  if (pr > sd) swing = 0.f;
+  else swing = ((double)sd < 0.0000000001) ? 0.f : pr / sd;
+}
+
 #endif

@@ -486,3 +486,46 @@ def make_kf_stream(batch, steps, seed=5):
             "leg_v": (v_body + rng.normal(0, 0.02, (B, 4, 3))).reshape(B, 12).astype(f32),
             "true_position": pos, "true_velocity": vel})
     return out
+
+
+def make_tick_stream(batch, ticks, seed, dt=0.002, roll=None, joint=None):
+    """Seeded, smooth synthetic sensor stream for the batched controller (include/qmpc_ctrl.h), in the
+    reference's layouts (GaitCtrller.cpp:34-56, OrientationEstimator.cpp:49-58):
+
+        imu   [ticks, B, 10] float64: accelerometer (~ gravity), quaternion x y z w (small roll / pitch,
+              drifting yaw), gyro
+        motor [ticks, B, 24] float64: q[3*leg + joint] near the Mini Cheetah stance pose (0, -0.8, 1.6), then qd
+
+    roll = (robot, value, from_tick): from that tick on the robot's roll is `value` (orientation safety check).
+    joint = (robot, index, value, from_tick): from that tick on motor[:, robot, index] = value (joint limits)."""
+    rng = np.random.default_rng(seed)
+    t = np.arange(ticks)[:, None] * dt                       # [T, 1]
+    ph = rng.uniform(0, 2 * np.pi, (1, batch, 6))
+    amp_rp = rng.uniform(0.005, 0.03, (1, batch, 2))
+    yaw0 = rng.uniform(-np.pi, np.pi, (1, batch))
+    yaw_rate = rng.normal(0, 0.2, (1, batch))
+    r = amp_rp[..., 0] * np.sin(2 * np.pi * 1.5 * t + ph[..., 0])
+    p = amp_rp[..., 1] * np.sin(2 * np.pi * 1.1 * t + ph[..., 1])
+    y = yaw0 + yaw_rate * t
+    if roll is not None:
+        rb, val, t0 = roll
+        r[t0:, rb] = val
+    rpy = np.stack([r, p, y], -1)                             # [T, B, 3]
+    q_wxyz = _quat_from_rpy(rpy.reshape(-1, 3)).reshape(ticks, batch, 4)
+    imu = np.zeros((ticks, batch, 10))
+    imu[..., 0:3] = np.array([0, 0, 9.81]) + 0.05 * np.sin(2 * np.pi * 2.0 * t[..., None] + ph[..., 2:5])
+    imu[..., 3:6] = q_wxyz[..., 1:4]
+    imu[..., 6] = q_wxyz[..., 0]
+    imu[..., 7:10] = 0.05 * np.sin(2 * np.pi * 1.3 * t[..., None] + ph[..., 3:6])
+    imu[..., 9] += yaw_rate
+    pose = np.tile(np.array([0.0, -0.8, 1.6]), 4)
+    jph = rng.uniform(0, 2 * np.pi, (1, batch, 12))
+    jamp = rng.uniform(0.01, 0.05, (1, batch, 12))
+    w = 2 * np.pi * 2.0
+    motor = np.zeros((ticks, batch, 24))
+    motor[..., :12] = pose + jamp * np.sin(w * t[..., None] + jph)
+    motor[..., 12:] = jamp * w * np.cos(w * t[..., None] + jph)
+    if joint is not None:
+        jb, idx, val, t0 = joint
+        motor[t0:, jb, idx] = val
+    return imu, motor

@@ -1,0 +1,77 @@
+"""Robot-ticks/s of the batched locomotion controller (include/qmpc_ctrl.h) on one GPU.
+
+For each batch size: mixed reference gaits (every gait number 0 .. 11 and its omni variant), the calm synthetic
+stream of workloads.make_tick_stream, warm-up ticks, then HIP-event timing of non-MPC ticks and of MPC ticks
+separately (one tick per event pair, median over the measured ticks).  Prints one JSON line per batch size and, with
+--out, writes them as a JSON list.  The kernel split comes from a separate run under
+`rocprofv3 --kernel-trace --stats -- python tools/ctrl_bench.py --batches 4096 --cycles 4`.
+
+    python tools/ctrl_bench.py [--batches 1024,4096,16384] [--cycles 8] [--warmup 26] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def run(B, cycles, warmup):
+    import torch
+    from quadruped_ctrl_amd import workloads as W
+    from quadruped_ctrl_amd.binding import BatchedController
+    ctrl = BatchedController(0, max_batch=B)
+    ctrl.init(B, freq=500.0, pid=(0.0, 0.0, 3.0, 0.3))
+    g = (np.arange(B) % 12).astype(np.int32)
+    g = np.where(np.arange(B) % 24 >= 12, g + 20, g).astype(np.int32)
+    ctrl.set_gait(torch.from_numpy(g).cuda())
+    rng = np.random.default_rng(B)
+    vel = np.stack([rng.uniform(-0.5, 1.2, B), rng.uniform(-0.3, 0.3, B), rng.uniform(-0.5, 0.5, B)], 1)
+    ctrl.set_vel(torch.from_numpy(vel).cuda())
+    n = warmup + 13 * cycles
+    imu, motor = W.make_tick_stream(B, 26, seed=B)
+    imu, motor = torch.from_numpy(imu).cuda(), torch.from_numpy(motor).cuda()
+    eff = torch.empty((B, 12), dtype=torch.float64, device="cuda")
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+    for t in range(n):
+        ev[t][0].record()
+        ctrl.tick(imu[t % 26], motor[t % 26], eff)
+        ev[t][1].record()
+    torch.cuda.synchronize()
+    us = np.array([a.elapsed_time(b) * 1e3 for a, b in ev])
+    mpc = (np.arange(n) + 1) % 13 == 0
+    keep = np.arange(n) >= warmup
+    t_non, t_mpc = float(np.median(us[keep & ~mpc])), float(np.median(us[keep & mpc]))
+    per_cycle = 12 * t_non + t_mpc
+    v = ctrl.view()
+    res = {"batch": B, "ticks_timed": int(keep.sum()), "us_per_nonmpc_tick": round(t_non, 2),
+           "us_per_mpc_tick": round(t_mpc, 2), "us_per_13_tick_cycle": round(per_cycle, 1),
+           "robot_ticks_per_s": float(f"{13 * B / (per_cycle * 1e-6):.4g}"),
+           "all_finite": bool(torch.isfinite(eff).all().item()), "latched": int((v["safe"] == 0).sum())}
+    ctrl.close()
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="1024,4096,16384")
+    ap.add_argument("--cycles", type=int, default=8)
+    ap.add_argument("--warmup", type=int, default=26)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    out = []
+    for B in [int(x) for x in a.batches.split(",")]:
+        r = run(B, a.cycles, a.warmup)
+        print(json.dumps(r), flush=True)
+        out.append(r)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
