@@ -18,18 +18,9 @@ ST_MAXITER, ST_NOT_PD, ST_INFEASIBLE, ST_WS_FULL, ST_FALLBACK = 1, 2, 4, 8, 16
 ST_COMPACTED, ST_SPILLED = 64, 128
 ST_NONFINITE = 32
 ST_ERROR_MASK = 15 | 32
-EXPORTS = ["qmpc_abi_version", "qmpc_last_error", "qmpc_create", "qmpc_destroy",
-           "qmpc_setup", "qmpc_set_robot", "qmpc_settings", "qmpc_solve",
-           "qmpc_solve_host", "qmpc_set_debug", "qmpc_debug_ld",
-           "qmpc_set_debug_clock", "qmpc_set_max_stance", "qmpc_pack",
-           "qmpc_forces_to_body", "qmpc_solve_commands", "qmpc_set_min_stance",
-           "qmpc_set_debug_aux", "qmpc_set_debug_overflow_slices", "qmpc_solve_sharded", "qmpc_set_leg_geometry",
-           "qmpc_leg_kinematics", "qmpc_leg_torques", "qmpc_swing_trajectory", "qmpc_set_warm_start", "qmpc_settings_jcqp", "qmpc_kf_init", "qmpc_kf_step", "qmpc_set_model",
-           "qmpc_max_horizon", "qmpc_set_debug_pool_busy", "qmpc_set_split", "qmpc_reserve", "qmpc_set_debug_engine_events", "qmpc_set_chunks", "qmpc_debug_read_item", "qmpc_debug_read_counts", "qmpc_set_dense", "qmpc_set_size_order", "qmpc_debug_keys", "qmpc_set_order_hint", "qmpc_set_debug_balance",
-           "qmpc_set_warm_start_min_iters", "qmpc_set_debug_overflow_spin", "qmpc_debug_ctrl_read"]
-# the batched locomotion controller's own header (include/qmpc_ctrl.h), same library and ABI version
-CTRL_EXPORTS = ["qmpc_ctrl_init", "qmpc_ctrl_reset", "qmpc_ctrl_set_gait", "qmpc_ctrl_set_vel", "qmpc_ctrl_prework",
-                "qmpc_ctrl_tick", "qmpc_ctrl_view_get"]
+# the int32 arrays among the controller's device state (QMPC_CTRL_ARRAYS in csrc/qmpc_glue.h): what read() returns as int32
+CTRL_INT_ARRAYS = ("counter", "first_run", "first_swing", "first_visit", "gait_num", "current_gait", "offsets", "durations",
+                   "iteration", "safe", "status")
 
 # qmpc_ctrl_view's float arrays (include/qmpc_ctrl.h) in declaration order, elements per robot
 CTRL_VIEW_FIELDS = ("position", "v_world", "orientation", "rpy", "r_body", "omega_world", "leg_q", "leg_p", "leg_v",
@@ -48,14 +39,13 @@ CMD_F32 = ("position", "v_world", "omega_world", "orientation", "rpy", "r_body",
 CMD_I32 = ("gait_type", "gait_offsets", "gait_durations", "gait_iteration")
 CMD_STATE = ("world_position_desired", "x_comp_integral")
 REC_FIELDS = ("p", "v", "q", "w", "r", "yaw", "traj", "gait", "x_drag", "weights", "alpha")
+# qmpc_inputs arrays (include/qmpc.h), in declaration order
+INPUT_FIELDS = ("p", "v", "q", "w", "r", "yaw", "traj", "gait", "weights", "alpha", "x_drag")
 
 
 class Inputs(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in
-                ("p", "v", "q", "w", "r", "yaw", "traj", "gait", "weights",
-                 "alpha", "x_drag")] + [("weights_stride", C.c_int),
-                                        ("alpha_stride", C.c_int),
-                                        ("x_drag_stride", C.c_int)]
+    _fields_ = [(n, C.c_void_p) for n in INPUT_FIELDS] + [("weights_stride", C.c_int), ("alpha_stride", C.c_int),
+                                                          ("x_drag_stride", C.c_int)]
 
 
 class Outputs(C.Structure):
@@ -86,6 +76,100 @@ class CtrlView(C.Structure):
 class LegCommand(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in LEG_F32] + [("kp_joint", C.c_float), ("kd_joint", C.c_float)]
 
+
+def make_inputs(arrays, batch):
+    """Inputs over the record arrays in `arrays` (INPUT_FIELDS keys; contiguous numpy arrays or torch tensors).  weights,
+    alpha and x_drag are per robot when they hold `batch` rows, else one row shared by the batch (stride 0); with
+    batch == 1 both readings address the same row."""
+    ptr = lambda a: a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+    numel = lambda a: a.numel() if hasattr(a, "numel") else a.size
+    inp = Inputs(*(ptr(arrays[k]) for k in INPUT_FIELDS))
+    inp.weights_stride = 12 if numel(arrays["weights"]) == 12 * batch else 0
+    inp.alpha_stride = 1 if numel(arrays["alpha"]) == batch else 0
+    inp.x_drag_stride = 1 if numel(arrays["x_drag"]) == batch else 0
+    return inp
+
+
+def _host_record(b):
+    """The record arrays of a numpy batch dict (workloads layout), contiguous, in the kernels' dtypes."""
+    rec = {k: np.ascontiguousarray(b[k], np.float32) for k in INPUT_FIELDS if k != "gait"}
+    rec["gait"] = np.ascontiguousarray(b["gait"], np.uint8)
+    return rec
+
+
+def _host_outputs(batch, horizon, full):
+    """Host result arrays ({grf, status, iters[, soln]}) and the Outputs over them."""
+    res = {"grf": np.zeros((batch, 12), np.float32), "status": np.zeros(batch, np.int32),
+           "iters": np.zeros(batch, np.int32)}
+    if full:
+        res["soln"] = np.zeros((batch, 12 * horizon))
+    out = Outputs(res["grf"].ctypes.data, res["soln"].ctypes.data if full else None, res["status"].ctypes.data,
+                  res["iters"].ctypes.data)
+    return res, out
+
+
+# C signatures: name -> argtypes, or (argtypes, restype) where the result is not int
+_P, _I, _D = C.c_void_p, C.c_int, C.c_double
+# include/qmpc.h, qmpc_expert.h and qmpc_debug.h
+SIGNATURES = {
+    "qmpc_abi_version": [],
+    "qmpc_last_error": ([_P], C.c_char_p),
+    "qmpc_create": [_I, _I, _I, C.POINTER(_P)],
+    "qmpc_destroy": [_P],
+    "qmpc_setup": [_P, _D, _I, _D, _D],
+    "qmpc_set_robot": [_P, _D, C.POINTER(_D), _D],
+    "qmpc_settings": [_P, _I, _D],
+    "qmpc_solve": [_P, _I, C.POINTER(Inputs), C.POINTER(Outputs), _P],
+    "qmpc_solve_host": [_P, _I, C.POINTER(Inputs), C.POINTER(Outputs)],
+    "qmpc_set_debug": [_P, _P, _P],
+    "qmpc_debug_ld": [_P],
+    "qmpc_set_debug_clock": [_P, _P],
+    "qmpc_set_max_stance": [_P, _I],
+    "qmpc_pack": [_P, _I, C.POINTER(Command), C.POINTER(Record), _P],
+    "qmpc_forces_to_body": [_P, _I, _P, _P, _P, _P],
+    "qmpc_solve_commands": [_P, _I, C.POINTER(Command), C.POINTER(Outputs), _P, _P],
+    "qmpc_set_min_stance": [_P, _I],
+    "qmpc_set_debug_aux": [_P, _P],
+    "qmpc_set_debug_overflow_slices": [_P, _I],
+    "qmpc_solve_sharded": [C.POINTER(_P), _I, _I, C.POINTER(Inputs), C.POINTER(Outputs)],
+    "qmpc_set_leg_geometry": [_P] + [_D] * 4,
+    "qmpc_leg_kinematics": [_P, _I] + [_P] * 6,
+    "qmpc_leg_torques": [_P, _I, C.POINTER(LegCommand), _P, _P, _P],
+    "qmpc_swing_trajectory": [_P, _I] + [_P] * 9,
+    "qmpc_set_warm_start": [_P, _P, _I],
+    "qmpc_settings_jcqp": [_P, _I, _I] + [_D] * 4,
+    "qmpc_kf_init": [_P, _I, _P, _P, _P],
+    "qmpc_kf_step": [_P, _I, C.POINTER(KfState), _P],
+    "qmpc_set_model": [_P, _I],
+    "qmpc_max_horizon": [],
+    "qmpc_set_debug_pool_busy": [_P, _I],
+    "qmpc_set_split": [_P, _I],
+    "qmpc_reserve": [_P],
+    "qmpc_set_debug_engine_events": [_P, _I],
+    "qmpc_set_chunks": [_P, _I],
+    "qmpc_debug_read_item": [_P, _I, _I, _P, _P, _P],
+    "qmpc_debug_read_counts": [_P, _P],
+    "qmpc_set_dense": [_P, _I],
+    "qmpc_set_size_order": [_P, _I],
+    "qmpc_debug_keys": [_P, _I, C.POINTER(Inputs), _P, _P, _P, _P],
+    "qmpc_set_order_hint": [_P, _I],
+    "qmpc_set_debug_balance": [_P, _I],
+    "qmpc_set_warm_start_min_iters": [_P, _I],
+    "qmpc_set_debug_overflow_spin": [_P, _I],
+    "qmpc_debug_ctrl_read": [_P, C.c_char_p, _P, C.c_longlong, C.POINTER(_I)],
+}
+# the batched locomotion controller's own header (include/qmpc_ctrl.h), same library and ABI version
+CTRL_SIGNATURES = {
+    "qmpc_ctrl_init": [_P, _I, _D, C.POINTER(_D), _P],
+    "qmpc_ctrl_reset": [_P, _I, _P, _P],
+    "qmpc_ctrl_set_gait": [_P, _I, _P, _P],
+    "qmpc_ctrl_set_vel": [_P, _I, _P, _P],
+    "qmpc_ctrl_prework": [_P, _I, _P, _P, _P],
+    "qmpc_ctrl_tick": [_P, _I, _P, _P, _P, _P],
+    "qmpc_ctrl_view_get": [_P, C.POINTER(CtrlView)],
+}
+EXPORTS = list(SIGNATURES)
+CTRL_EXPORTS = list(CTRL_SIGNATURES)
 
 _lib = None
 
@@ -119,61 +203,9 @@ def load_library():
                 f"{LIB_PATH} not found: build the HIP extension first "
                 "(python -c 'import __graft_entry__ as g; g.build()')")
         lib = C.CDLL(LIB_PATH)
-        lib.qmpc_last_error.restype = C.c_char_p
-        lib.qmpc_last_error.argtypes = [C.c_void_p]
-        lib.qmpc_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
-        lib.qmpc_destroy.argtypes = [C.c_void_p]
-        lib.qmpc_setup.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_double, C.c_double]
-        lib.qmpc_set_robot.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_double), C.c_double]
-        lib.qmpc_settings.argtypes = [C.c_void_p, C.c_int, C.c_double]
-        lib.qmpc_solve.argtypes = [C.c_void_p, C.c_int, C.POINTER(Inputs),
-                                   C.POINTER(Outputs), C.c_void_p]
-        lib.qmpc_solve_host.argtypes = [C.c_void_p, C.c_int, C.POINTER(Inputs),
-                                        C.POINTER(Outputs)]
-        lib.qmpc_set_debug.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.qmpc_debug_ld.argtypes = [C.c_void_p]
-        lib.qmpc_set_debug_aux.argtypes = [C.c_void_p, C.c_void_p]
-        lib.qmpc_set_debug_overflow_slices.argtypes = [C.c_void_p, C.c_int]
-        lib.qmpc_set_debug_overflow_spin.argtypes = [C.c_void_p, C.c_int]
-        lib.qmpc_set_debug_pool_busy.argtypes = [C.c_void_p, C.c_int]
-        lib.qmpc_debug_read_item.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.qmpc_set_split.argtypes = [C.c_void_p, C.c_int]
-        lib.qmpc_reserve.argtypes = [C.c_void_p]
-        lib.qmpc_set_debug_engine_events.argtypes = [C.c_void_p, C.c_int]
-        lib.qmpc_set_chunks.argtypes = [C.c_void_p, C.c_int]
-        lib.qmpc_set_dense.argtypes = [C.c_void_p, C.c_int]
-        lib.qmpc_set_size_order.argtypes = [C.c_void_p, C.c_int]
-        lib.qmpc_debug_keys.argtypes = [C.c_void_p, C.c_int, C.POINTER(Inputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.qmpc_set_order_hint.argtypes = [C.c_void_p, C.c_int]
-        lib.qmpc_set_debug_balance.argtypes = [C.c_void_p, C.c_int]
-        lib.qmpc_set_warm_start.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        lib.qmpc_set_warm_start_min_iters.argtypes = [C.c_void_p, C.c_int]
-        lib.qmpc_set_model.argtypes = [C.c_void_p, C.c_int]
-        lib.qmpc_kf_init.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.qmpc_kf_step.argtypes = [C.c_void_p, C.c_int, C.POINTER(KfState), C.c_void_p]
-        lib.qmpc_settings_jcqp.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_double] * 4
-        lib.qmpc_set_leg_geometry.argtypes = [C.c_void_p] + [C.c_double] * 4
-        lib.qmpc_leg_kinematics.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
-        lib.qmpc_leg_torques.argtypes = [C.c_void_p, C.c_int, C.POINTER(LegCommand), C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.qmpc_swing_trajectory.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9
-        lib.qmpc_solve_sharded.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(Inputs),
-                                           C.POINTER(Outputs)]
-        lib.qmpc_set_debug_clock.argtypes = [C.c_void_p, C.c_void_p]
-        lib.qmpc_debug_read_counts.argtypes = [C.c_void_p, C.c_void_p]
-        lib.qmpc_set_max_stance.argtypes = [C.c_void_p, C.c_int]
-        lib.qmpc_set_min_stance.argtypes = [C.c_void_p, C.c_int]
-        lib.qmpc_pack.argtypes = [C.c_void_p, C.c_int, C.POINTER(Command), C.POINTER(Record), C.c_void_p]
-        lib.qmpc_solve_commands.argtypes = [C.c_void_p, C.c_int, C.POINTER(Command), C.POINTER(Outputs), C.c_void_p,
-                                            C.c_void_p]
-        lib.qmpc_debug_ctrl_read.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_longlong, C.POINTER(C.c_int)]
-        lib.qmpc_ctrl_init.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double), C.c_void_p]
-        lib.qmpc_ctrl_reset.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        lib.qmpc_ctrl_set_gait.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        lib.qmpc_ctrl_set_vel.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        lib.qmpc_ctrl_prework.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.qmpc_ctrl_tick.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.qmpc_ctrl_view_get.argtypes = [C.c_void_p, C.POINTER(CtrlView)]
-        lib.qmpc_forces_to_body.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        for name, sig in {**SIGNATURES, **CTRL_SIGNATURES}.items():
+            f = getattr(lib, name)
+            f.argtypes, f.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
         _lib = lib
     return _lib
 
@@ -270,11 +302,7 @@ class BatchedConvexMPC:
     # ---- device-resident path -------------------------------------------
     def upload(self, b):
         """numpy batch dict (workloads layout) -> dict of device tensors."""
-        t = self.torch
-        d = {}
-        for k in ("p", "v", "q", "w", "r", "yaw", "traj", "weights", "alpha", "x_drag"):
-            d[k] = t.from_numpy(np.ascontiguousarray(b[k], np.float32)).to(self.device)
-        d["gait"] = t.from_numpy(np.ascontiguousarray(b["gait"], np.uint8)).to(self.device)
+        d = {k: self.torch.from_numpy(a).to(self.device) for k, a in _host_record(b).items()}
         d["batch"] = int(b["batch"])
         return d
 
@@ -289,13 +317,7 @@ class BatchedConvexMPC:
 
     def make_args(self, d, o):
         """Pack ctypes argument structs once (for launch-only timing loops)."""
-        inp = Inputs()
-        for k in ("p", "v", "q", "w", "r", "yaw", "traj", "gait", "weights", "alpha", "x_drag"):
-            setattr(inp, k, d[k].data_ptr())
-        B = d["batch"]
-        inp.weights_stride = 12 if d["weights"].dim() == 2 else 0
-        inp.alpha_stride = 1 if d["alpha"].numel() == B else 0
-        inp.x_drag_stride = 1 if d["x_drag"].numel() == B else 0
+        inp = make_inputs(d, d["batch"])
         out = Outputs(o["grf"].data_ptr(),
                       o["soln"].data_ptr() if o["soln"] is not None else None,
                       o["status"].data_ptr(),
@@ -304,10 +326,7 @@ class BatchedConvexMPC:
 
     def solve_async(self, batch, inp, out, stream=None):
         """Enqueue one batched solve on `stream` (torch current stream by default)."""
-        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
-        rc = self.lib.qmpc_solve(self.h, batch, C.byref(inp), C.byref(out),
-                                 C.c_void_p(s.cuda_stream))
-        self._check(rc, "qmpc_solve")
+        self._check(self.lib.qmpc_solve(self.h, batch, C.byref(inp), C.byref(out), self._stream_ptr(stream)), "qmpc_solve")
 
     def solve(self, b, full=False):
         """Convenience: numpy batch dict in, numpy results out (device path)."""
@@ -347,61 +366,34 @@ class BatchedConvexMPC:
 
     def pack_async(self, dcmd, rec, stream=None):
         """Enqueue the record build (qmpc_pack) for the uploaded command."""
-        cs = Command()
-        for k in CMD_F32 + CMD_I32 + CMD_STATE:
-            setattr(cs, k, None if dcmd[k] is None else dcmd[k].data_ptr())
-        cs.body_height = dcmd["body_height"]
-        cs.omni_mode = dcmd["omni_mode"]
-        rs = Record()
-        for k in REC_FIELDS:
-            setattr(rs, k, rec[k].data_ptr())
-        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
-        self._check(self.lib.qmpc_pack(self.h, dcmd["batch"], C.byref(cs), C.byref(rs),
-                                       C.c_void_p(s.cuda_stream)), "qmpc_pack")
+        cs = self.make_command_args(dcmd)
+        rs = Record(*(rec[k].data_ptr() for k in REC_FIELDS))
+        self._check(self.lib.qmpc_pack(self.h, dcmd["batch"], C.byref(cs), C.byref(rs), self._stream_ptr(stream)),
+                    "qmpc_pack")
 
     def make_command_args(self, dcmd):
-        cs = Command()
-        for k in CMD_F32 + CMD_I32 + CMD_STATE:
-            setattr(cs, k, None if dcmd[k] is None else dcmd[k].data_ptr())
+        """Command struct over the uploaded command (upload_command)."""
+        cs = Command(*(None if dcmd[k] is None else dcmd[k].data_ptr() for k in CMD_F32 + CMD_I32 + CMD_STATE))
         cs.body_height = dcmd["body_height"]
         cs.omni_mode = dcmd["omni_mode"]
         return cs
 
     def solve_commands_async(self, batch, cs, out, f_ff=None, stream=None):
         """One fused launch: command -> (record in registers) -> solve -> grf (+ body-frame forces)."""
-        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
         self._check(self.lib.qmpc_solve_commands(self.h, batch, C.byref(cs), C.byref(out),
-                                                 None if f_ff is None else f_ff.data_ptr(),
-                                                 C.c_void_p(s.cuda_stream)), "qmpc_solve_commands")
+                                                 None if f_ff is None else f_ff.data_ptr(), self._stream_ptr(stream)),
+                    "qmpc_solve_commands")
 
     def forces_to_body_async(self, batch, r_body, grf, f_ff, stream=None):
-        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
         self._check(self.lib.qmpc_forces_to_body(self.h, batch, r_body.data_ptr(), grf.data_ptr(), f_ff.data_ptr(),
-                                                 C.c_void_p(s.cuda_stream)), "qmpc_forces_to_body")
+                                                 self._stream_ptr(stream)), "qmpc_forces_to_body")
 
     # ---- host-pointer path (what the single-robot shim uses) -------------
     def solve_host(self, b, full=False):
-        B, h = int(b["batch"]), self.horizon
-        keep = {k: np.ascontiguousarray(b[k], np.float32) for k in
-                ("p", "v", "q", "w", "r", "yaw", "traj", "weights", "alpha", "x_drag")}
-        keep["gait"] = np.ascontiguousarray(b["gait"], np.uint8)
-        inp = Inputs()
-        for k, a in keep.items():
-            setattr(inp, k, a.ctypes.data)
-        inp.weights_stride = 12 if keep["weights"].size == 12 * B else 0
-        inp.alpha_stride = 1 if keep["alpha"].size == B else 0
-        inp.x_drag_stride = 1 if keep["x_drag"].size == B else 0
-        grf = np.zeros((B, 12), np.float32)
-        st = np.zeros(B, np.int32)
-        it = np.zeros(B, np.int32)
-        soln = np.zeros((B, 12 * h)) if full else None
-        out = Outputs(grf.ctypes.data, soln.ctypes.data if full else None,
-                      st.ctypes.data, it.ctypes.data)
-        self._check(self.lib.qmpc_solve_host(self.h, B, C.byref(inp), C.byref(out)),
-                    "qmpc_solve_host")
-        res = {"grf": grf, "status": st, "iters": it}
-        if full:
-            res["soln"] = soln
+        B = int(b["batch"])
+        rec = _host_record(b)
+        res, out = _host_outputs(B, self.horizon, full)
+        self._check(self.lib.qmpc_solve_host(self.h, B, C.byref(make_inputs(rec, B)), C.byref(out)), "qmpc_solve_host")
         return res
 
     # ---- per-tick glue either side of the solve (SURVEY.md 8f-2) ---------------------------
@@ -473,29 +465,14 @@ class BatchedConvexMPC:
         production; several may share a device): contiguous shards of the host batch `b`, all
         devices busy at once, results collected into one set of host arrays."""
         first = solvers[0]
-        B, h = int(b["batch"]), first.horizon
-        keep = {k: np.ascontiguousarray(b[k], np.float32) for k in
-                ("p", "v", "q", "w", "r", "yaw", "traj", "weights", "alpha", "x_drag")}
-        keep["gait"] = np.ascontiguousarray(b["gait"], np.uint8)
-        inp = Inputs()
-        for k, a in keep.items():
-            setattr(inp, k, a.ctypes.data)
-        inp.weights_stride = 12 if keep["weights"].size == 12 * B else 0
-        inp.alpha_stride = 1 if keep["alpha"].size == B else 0
-        inp.x_drag_stride = 1 if keep["x_drag"].size == B else 0
-        grf = np.zeros((B, 12), np.float32)
-        st = np.zeros(B, np.int32)
-        it = np.zeros(B, np.int32)
-        soln = np.zeros((B, 12 * h)) if full else None
-        out = Outputs(grf.ctypes.data, soln.ctypes.data if full else None, st.ctypes.data, it.ctypes.data)
+        B = int(b["batch"])
+        rec = _host_record(b)
+        res, out = _host_outputs(B, first.horizon, full)
         hs = (C.c_void_p * len(solvers))(*[m.h for m in solvers])
-        rc = first.lib.qmpc_solve_sharded(hs, len(solvers), B, C.byref(inp), C.byref(out))
+        rc = first.lib.qmpc_solve_sharded(hs, len(solvers), B, C.byref(make_inputs(rec, B)), C.byref(out))
         if rc != QMPC_OK:
             raise QmpcError(f"qmpc_solve_sharded failed rc={rc}: " +
                             "; ".join(m.lib.qmpc_last_error(m.h).decode() for m in solvers))
-        res = {"grf": grf, "status": st, "iters": it}
-        if full:
-            res["soln"] = soln
         return res
 
     # ---- test hook ---------------------------------------------------------
@@ -547,9 +524,8 @@ class BatchedConvexMPC:
         nst = t.empty((B,), dtype=t.int32, device=self.device)
         score = t.empty((B,), dtype=t.float32, device=self.device)
         demand = t.empty((B,), dtype=t.float32, device=self.device)
-        s = t.cuda.current_stream(self.device)
         self._check(self.lib.qmpc_debug_keys(self.h, B, C.byref(inp), nst.data_ptr(), score.data_ptr(), demand.data_ptr(),
-                                             C.c_void_p(s.cuda_stream)), "qmpc_debug_keys")
+                                             self._stream_ptr(None)), "qmpc_debug_keys")
         t.cuda.synchronize(self.device)
         return nst.cpu().numpy(), score.cpu().numpy(), demand.cpu().numpy()
 
@@ -689,8 +665,7 @@ class BatchedController:
         out = np.zeros((self.batch, per.value), np.float32)
         self.mpc._check(self.lib.qmpc_debug_ctrl_read(self.mpc.h, name.encode(), out.ctypes.data, out.nbytes, C.byref(per)),
                         f"qmpc_debug_ctrl_read({name})")
-        if name in ("counter", "first_run", "first_swing", "first_visit", "gait_num", "current_gait", "offsets", "durations",
-                    "iteration", "safe", "status"):
+        if name in CTRL_INT_ARRAYS:
             out = out.view(np.int32)
         return out
 

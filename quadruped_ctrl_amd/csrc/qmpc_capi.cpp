@@ -177,7 +177,8 @@ struct qmpc_ctx {
   double* d_evpool = nullptr;  // largest size class: global event pool (allocated on first use)
   double* d_ovpool = nullptr;  // the other classes: overflow event pool, ov_nslice slices, recycled within a call (one flag per slice)
   int* d_ovflags = nullptr;    // [ov_nslice_alloc] 0 = free
-  int ov_nslice = 0;
+  int ov_nslice_alloc = 0;     // slices allocated: min(max_batch, 2048)
+  int ov_nslice = 0;           // slices in use (all of them unless qmpc_set_debug_overflow_slices says fewer)
   int ov_spin = 1 << 22;       // probes of a robot that finds every slice taken before it gives up (test hook: qmpc_set_debug_overflow_slices)
   bool device_error = false;   // a HIP call of this handle failed since the last successful solve (fail()): see solve_impl
   int* d_evflags = nullptr;
@@ -263,6 +264,47 @@ int order_after_previous(qmpc_ctx* c, hipStream_t stream) {
   return QMPC_OK;
 }
 
+// The solve record (qmpc_inputs), described once: f(array, bytes per robot at horizon h, per robot?) for each of its
+// arrays in declaration order.  weights / alpha / x_drag with stride 0 are one row shared by the batch.  `in` may be a
+// copy whose pointers f rebinds.
+template <class Record, class F>
+void for_each_record_array(Record& in, size_t h, F&& f) {
+  f(in.p, 4 * 3, true);
+  f(in.v, 4 * 3, true);
+  f(in.q, 4 * 4, true);
+  f(in.w, 4 * 3, true);
+  f(in.r, 4 * 12, true);
+  f(in.yaw, 4, true);
+  f(in.traj, 4 * 12 * h, true);
+  f(in.gait, 4 * h, true);
+  f(in.weights, 4 * 12, in.weights_stride != 0);
+  f(in.alpha, 4, in.alpha_stride != 0);
+  f(in.x_drag, 4, in.x_drag_stride != 0);
+}
+constexpr int kRecordArrays = 11;
+
+// every array of the record given (need_x_drag = false: x_drag may be missing)
+bool record_ok(const qmpc_inputs& in, bool need_x_drag = true) {
+  int missing = 0;
+  for_each_record_array(in, 0, [&](const void* p, size_t, bool) { missing += !p; });
+  return missing == (need_x_drag || in.x_drag ? 0 : 1);
+}
+
+// the kernels' view of the record
+void bind_record(QmpcParams& P, const qmpc_inputs& in) {
+  P.p = in.p; P.v = in.v; P.q = in.q; P.w = in.w; P.r = in.r; P.yaw = in.yaw;
+  P.traj = in.traj; P.gait = in.gait; P.weights = in.weights; P.alpha = in.alpha; P.x_drag = in.x_drag;
+  P.weights_stride = in.weights_stride;
+  P.alpha_stride = in.alpha_stride;
+  P.x_drag_stride = in.x_drag_stride;
+}
+
+// leading dimension of a work item of pool sk: 0 = 128-row class, 1 = 192-row class, 2 = large problems
+size_t item_ld(int sk) { return sk == 0 ? 128 : (sk == 1 ? 192 : QMPC_BIG_LD); }
+
+// Mini Cheetah _abadLocation (MiniCheetah.h:25-26,105): the Kalman filter's hip location
+const float kAbadLocation[3] = {0.19f, 0.049f, 0.f};
+
 }  // namespace
 
 namespace {
@@ -316,10 +358,10 @@ int qmpc_create(int device_id, int max_batch, int max_horizon, qmpc_handle* out)
     // (solve_impl) -- a flag left at 1 would otherwise be lost for the life of the handle
     // (2048 slices of 192 KiB: what a call of 8192 robots needs when the 64-row class runs five per CU ahead of larger
     //  classes -- see the launch loop of solve_impl)
-    c->ov_nslice = max_batch < 2048 ? max_batch : 2048;
-    e = hipMalloc(&c->d_ovpool, sizeof(double) * (size_t)c->ov_nslice * QMPC_OV_SLICE);
-    if (e == hipSuccess) e = hipMalloc(&c->d_ovflags, sizeof(int) * (size_t)c->ov_nslice);
-    if (e == hipSuccess) e = hipMemset(c->d_ovflags, 0, sizeof(int) * (size_t)c->ov_nslice);
+    c->ov_nslice_alloc = c->ov_nslice = max_batch < 2048 ? max_batch : 2048;
+    e = hipMalloc(&c->d_ovpool, sizeof(double) * (size_t)c->ov_nslice_alloc * QMPC_OV_SLICE);
+    if (e == hipSuccess) e = hipMalloc(&c->d_ovflags, sizeof(int) * (size_t)c->ov_nslice_alloc);
+    if (e == hipSuccess) e = hipMemset(c->d_ovflags, 0, sizeof(int) * (size_t)c->ov_nslice_alloc);
   }
   if (e == hipSuccess) e = qmpc_prepare();
   if (e == hipSuccess) {
@@ -518,9 +560,8 @@ int qmpc_set_debug_overflow_spin(qmpc_handle c, int probes) {
 
 int qmpc_set_debug_overflow_slices(qmpc_handle c, int n) {
   if (!c) return QMPC_ERR_ARG;
-  const int all = c->max_batch < 2048 ? c->max_batch : 2048;  // what qmpc_create allocated
-  if (n > all) return QMPC_ERR_ARG;  // more slices than allocated
-  c->ov_nslice = n < 0 ? all : n;
+  if (n > c->ov_nslice_alloc) return QMPC_ERR_ARG;  // more slices than allocated
+  c->ov_nslice = n < 0 ? c->ov_nslice_alloc : n;
   return QMPC_OK;
 }
 
@@ -549,16 +590,11 @@ int qmpc_debug_keys(qmpc_handle c, int batch, const qmpc_inputs* in, int32_t* ns
   if (!c->is_setup) return QMPC_ERR_STATE;
   if (batch < 0 || batch > c->max_batch) return QMPC_ERR_ARG;
   if (batch == 0) return QMPC_OK;
-  if (!in->p || !in->v || !in->q || !in->w || !in->r || !in->yaw || !in->traj || !in->gait || !in->weights || !in->alpha ||
-      ((uintptr_t)in->gait & 3u))
-    return QMPC_ERR_ARG;
+  if (!record_ok(*in, false) || ((uintptr_t)in->gait & 3u)) return QMPC_ERR_ARG;  // (the key pass reads no x_drag)
   DeviceGuard g(c->device);
   QmpcParams P;
   std::memset(&P, 0, sizeof(P));
-  P.p = in->p; P.v = in->v; P.q = in->q; P.w = in->w; P.r = in->r; P.yaw = in->yaw;
-  P.traj = in->traj; P.gait = in->gait; P.weights = in->weights; P.alpha = in->alpha;
-  P.weights_stride = in->weights_stride;
-  P.alpha_stride = in->alpha_stride;
+  bind_record(P, *in);
   P.batch = batch; P.horizon = c->horizon;
   P.dt = c->dt;
   P.mu_inv = (double)(1.f / (float)c->mu);
@@ -619,7 +655,7 @@ int qmpc_debug_ld(qmpc_handle) { return QMPC_DBG_LD; }
 int qmpc_debug_read_item(qmpc_handle c, int which, int item, double* hinv_host, double* xu_host, int* hdr4) {
   if (!c || which < 0 || which > 2 || c->wk_cap[which] <= 0 || item < 0 || item >= c->wk_cap[which]) return QMPC_ERR_ARG;
   DeviceGuard g(c->device);
-  const size_t ld = which == 0 ? 128 : (which == 1 ? 192 : QMPC_BIG_LD);
+  const size_t ld = item_ld(which);
   HIP_TRY(c, hipDeviceSynchronize());
   if (hinv_host) HIP_TRY(c, hipMemcpy(hinv_host, c->d_wk_hinv[which] + (size_t)item * ld * ld, sizeof(double) * ld * ld, hipMemcpyDeviceToHost));
   if (xu_host) HIP_TRY(c, hipMemcpy(xu_host, c->d_wk_xu[which] + (size_t)item * ld, sizeof(double) * ld, hipMemcpyDeviceToHost));
@@ -712,7 +748,7 @@ int ensure_items(qmpc_ctx* c, int sk) {
   if (c->wk_cap[sk] > 0) return QMPC_OK;  // (set last: a pool counts as present only when ALL its arrays are)
   static const int lim[3] = {QMPC_ITEMS_C2, QMPC_ITEMS_C3, QMPC_ITEMS_BIG};
   const int rb = sk == 0 ? 2 : (sk == 1 ? 3 : 5);
-  const size_t ld = sk == 0 ? 128 : (sk == 1 ? 192 : QMPC_BIG_LD);
+  const size_t ld = item_ld(sk);
   const size_t cap = (size_t)(c->max_batch < lim[sk] ? c->max_batch : lim[sk]);
   // (the engine grid never exceeds the resident workgroups: slice = blockIdx.x)
   size_t wgs = (size_t)qmpc_engine_resident(rb);
@@ -769,9 +805,7 @@ int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command
   if (batch == 0) return QMPC_OK;
   if (!out->grf || !out->status) return QMPC_ERR_ARG;
   if (in) {
-    if (!in->p || !in->v || !in->q || !in->w || !in->r || !in->yaw || !in->traj || !in->gait ||
-        !in->weights || !in->alpha || !in->x_drag)
-      return QMPC_ERR_ARG;
+    if (!record_ok(*in)) return QMPC_ERR_ARG;
     if ((in->weights_stride != 0 && in->weights_stride != 12) || (in->alpha_stride & ~1) ||
         (in->x_drag_stride & ~1))
       return QMPC_ERR_ARG;
@@ -787,19 +821,14 @@ int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command
     // the previous call (or set-up step) of this handle failed on the device: whatever its kernels left in the
     // recycled-slice flags and the per-CU placement words is void.  Re-armed with the fill kernel (no memset node: they
     // replay wrongly when captured, and this path must not differ from the normal one in kind)
-    if (c->d_ovflags && c->ov_nslice > 0) HIP_TRY(c, fill_ints(c->d_ovflags, c->max_batch < 2048 ? c->max_batch : 2048, 0, stream));
+    if (c->d_ovflags && c->ov_nslice > 0) HIP_TRY(c, fill_ints(c->d_ovflags, c->ov_nslice_alloc, 0, stream));
     c->device_error = false;
   }
 
   QmpcParams P;
   std::memset(&P, 0, sizeof(P));
   if (in) {
-    P.p = in->p; P.v = in->v; P.q = in->q; P.w = in->w; P.r = in->r; P.yaw = in->yaw;
-    P.traj = in->traj; P.gait = in->gait; P.weights = in->weights; P.alpha = in->alpha;
-    P.x_drag = in->x_drag;
-    P.weights_stride = in->weights_stride;
-    P.alpha_stride = in->alpha_stride;
-    P.x_drag_stride = in->x_drag_stride;
+    bind_record(P, *in);
   } else {
     P.c_position = cmd->position; P.c_v_world = cmd->v_world; P.c_omega_world = cmd->omega_world;
     P.c_orientation = cmd->orientation; P.c_rpy = cmd->rpy; P.c_r_body = cmd->r_body; P.c_p_foot = cmd->p_foot;
@@ -903,7 +932,7 @@ int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command
     A.wk_hdr = c->d_wk_hdr[sk];
     A.wk_order = c->d_wk_order[sk];
     A.wk_ovf = c->d_wk_ovf[sk];
-    A.wk_ld = sk == 0 ? 128 : (sk == 1 ? 192 : QMPC_BIG_LD);
+    A.wk_ld = (int)item_ld(sk);
     A.wk_cap = c->wk_cap[sk];
     A.wk_base = 0;
     A.wk_kev = c->dbg_engine_events > 0 ? c->dbg_engine_events : (1 << 20);
@@ -1167,9 +1196,7 @@ int host_enqueue(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_outpu
   if (!c || !in || !out) return QMPC_ERR_ARG;
   if (!c->is_setup) return QMPC_ERR_STATE;
   if (batch <= 0 || batch > c->max_batch) return QMPC_ERR_ARG;
-  if (!in->p || !in->v || !in->q || !in->w || !in->r || !in->yaw || !in->traj || !in->gait ||
-      !in->weights || !in->alpha || !in->x_drag || !out->grf || !out->status)
-    return QMPC_ERR_ARG;
+  if (!record_ok(*in) || !out->grf || !out->status) return QMPC_ERR_ARG;
   DeviceGuard g(c->device);
   const size_t B = (size_t)batch, h = (size_t)c->horizon;
   // ONE pinned host block holds the whole record and the results:  [ inputs | outputs ].
@@ -1184,12 +1211,14 @@ int host_enqueue(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_outpu
     off += (bytes + 63) & ~(size_t)63;
     return o;
   };
-  const size_t wN = in->weights_stride ? 12 * B : 12, aN = in->alpha_stride ? B : 1,
-               xN = in->x_drag_stride ? B : 1;
-  const size_t o_p = carve(4 * 3 * B), o_v = carve(4 * 3 * B), o_q = carve(4 * 4 * B),
-               o_w = carve(4 * 3 * B), o_r = carve(4 * 12 * B), o_yaw = carve(4 * B),
-               o_traj = carve(4 * 12 * h * B), o_gait = carve(4 * h * B), o_wt = carve(4 * wN),
-               o_al = carve(4 * aN), o_xd = carve(4 * xN);
+  struct Part {
+    size_t off, bytes;
+  } rec[kRecordArrays];
+  int n = 0;
+  for_each_record_array(*in, h, [&](const void*, size_t bytes, bool per_robot) {
+    const size_t all = per_robot ? bytes * B : bytes;
+    rec[n++] = Part{carve(all), all};
+  });
   const size_t in_bytes = (off + 255) & ~(size_t)255;
   off = in_bytes;
   const size_t o_grf = carve(4 * 12 * B), o_soln = carve(out->soln ? 8 * 12 * h * B : 0), o_st = carve(4 * B),
@@ -1213,30 +1242,19 @@ int host_enqueue(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_outpu
     c->stage_bytes = total;
   }
   char* hb = (char*)c->h_pin;
-  std::memcpy(hb + o_p, in->p, 4 * 3 * B);
-  std::memcpy(hb + o_v, in->v, 4 * 3 * B);
-  std::memcpy(hb + o_q, in->q, 4 * 4 * B);
-  std::memcpy(hb + o_w, in->w, 4 * 3 * B);
-  std::memcpy(hb + o_r, in->r, 4 * 12 * B);
-  std::memcpy(hb + o_yaw, in->yaw, 4 * B);
-  std::memcpy(hb + o_traj, in->traj, 4 * 12 * h * B);
-  std::memcpy(hb + o_gait, in->gait, 4 * h * B);
-  std::memcpy(hb + o_wt, in->weights, 4 * wN);
-  std::memcpy(hb + o_al, in->alpha, 4 * aN);
-  std::memcpy(hb + o_xd, in->x_drag, 4 * xN);
   hipStream_t s = c->host_stream;
   char* base = in_place ? hb : (char*)c->d_stage;
+  // gather the record into the pinned block; the solve reads it at `base`
+  qmpc_inputs din = *in;
+  n = 0;
+  for_each_record_array(din, h, [&](auto& p, size_t, bool) {
+    std::memcpy(hb + rec[n].off, p, rec[n].bytes);
+    p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + rec[n++].off);
+  });
   if (!in_place) {
     if (const int rc = order_after_previous(c, s)) return rc;  // the mirror may still be read by an earlier call
     HIP_TRY(c, hipMemcpyAsync(base, hb, in_bytes, hipMemcpyHostToDevice, s));
   }
-  qmpc_inputs din = *in;
-  din.p = (const float*)(base + o_p); din.v = (const float*)(base + o_v);
-  din.q = (const float*)(base + o_q); din.w = (const float*)(base + o_w);
-  din.r = (const float*)(base + o_r); din.yaw = (const float*)(base + o_yaw);
-  din.traj = (const float*)(base + o_traj); din.gait = (const uint8_t*)(base + o_gait);
-  din.weights = (const float*)(base + o_wt); din.alpha = (const float*)(base + o_al);
-  din.x_drag = (const float*)(base + o_xd);
   qmpc_outputs dout;
   dout.grf = (float*)(base + o_grf);
   dout.soln = out->soln ? (double*)(base + o_soln) : nullptr;
@@ -1331,8 +1349,7 @@ int qmpc_kf_step(qmpc_handle c, int batch, const qmpc_kf_state* st, void* stream
     return QMPC_ERR_ARG;
   if (batch == 0) return QMPC_OK;
   DeviceGuard g(c->device);
-  static const float hip[3] = {0.19f, 0.049f, 0.f};  // _abadLocation (MiniCheetah.h:25-26,105)
-  HIP_TRY(c, qmpc_launch_kf(st, hip, batch, (hipStream_t)stream));
+  HIP_TRY(c, qmpc_launch_kf(st, kAbadLocation, batch, (hipStream_t)stream));
   return QMPC_OK;
 }
 
@@ -1349,9 +1366,7 @@ int qmpc_solve_sharded(const qmpc_handle* handles, int n_handles, int batch, con
   for (int k = 0; k < n_handles; ++k)
     if (!handles[k]) return QMPC_ERR_ARG;
   if (batch == 0) return QMPC_OK;
-  if (!in->p || !in->v || !in->q || !in->w || !in->r || !in->yaw || !in->traj || !in->gait || !in->weights ||
-      !in->alpha || !in->x_drag || !out->grf || !out->status)
-    return QMPC_ERR_ARG;
+  if (!record_ok(*in) || !out->grf || !out->status) return QMPC_ERR_ARG;
   const int h = handles[0]->horizon;
   for (int k = 1; k < n_handles; ++k)
     if (handles[k]->horizon != h) return QMPC_ERR_STATE;  // every device must be set up for the same problem
@@ -1364,12 +1379,10 @@ int qmpc_solve_sharded(const qmpc_handle* handles, int n_handles, int batch, con
     if (lo >= hi) break;
     const size_t o = (size_t)lo;
     qmpc_inputs si = *in;
-    si.p = in->p + 3 * o; si.v = in->v + 3 * o; si.q = in->q + 4 * o; si.w = in->w + 3 * o;
-    si.r = in->r + 12 * o; si.yaw = in->yaw + o; si.traj = in->traj + (size_t)12 * h * o;
-    si.gait = in->gait + (size_t)4 * h * o;
-    si.weights = in->weights + (size_t)in->weights_stride * o;
-    si.alpha = in->alpha + (size_t)in->alpha_stride * o;
-    si.x_drag = in->x_drag + (size_t)in->x_drag_stride * o;
+    for_each_record_array(si, (size_t)h, [&](auto& p, size_t bytes, bool per_robot) {
+      p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(reinterpret_cast<const char*>(p) +
+                                                                  (per_robot ? bytes * o : 0));
+    });
     qmpc_outputs so;
     so.grf = out->grf + 12 * o;
     so.soln = out->soln ? out->soln + (size_t)12 * h * o : nullptr;
@@ -1395,23 +1408,12 @@ namespace {
 // Lay the controller's arrays out in one allocation (base == nullptr: only count), each array 256-byte aligned
 size_t ctrl_carve(QmpcCtrlDev& d, char* base, int M) {
   size_t off = 0;
-  auto take = [&](auto*& p, int per_robot) {
-    using T = std::remove_reference_t<decltype(*p)>;
-    off = (off + 255) & ~(size_t)255;
-    p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += sizeof(T) * (size_t)per_robot * (size_t)M;
-  };
-  take(d.q, 12); take(d.qd, 12); take(d.leg_J, 36); take(d.leg_p, 12); take(d.leg_v, 12); take(d.kf_p, 12);
-  take(d.kf_v, 12); take(d.orientation, 4); take(d.rpy, 3); take(d.r_body, 9); take(d.omega_body, 3);
-  take(d.omega_world, 3); take(d.a_world, 3); take(d.ori_ini_inv, 4); take(d.xhat, 18); take(d.P, 324);
-  take(d.position, 3); take(d.v_world, 3); take(d.v_body, 3); take(d.contact_phase, 4); take(d.vel_cmd, 3);
-  take(d.vel_des, 3); take(d.yaw_des, 1); take(d.yaw_des_true, 1); take(d.rpy_int, 2); take(d.rpy_comp, 2);
-  take(d.stand_traj, 6); take(d.wpd, 2); take(d.xci, 1); take(d.p_foot, 12); take(d.r_cmd, 9); take(d.sw_p0, 12);
-  take(d.sw_pf, 12); take(d.sw_p, 12); take(d.sw_v, 12); take(d.swing_time, 4); take(d.swing_rem, 4);
-  take(d.contact_state, 4); take(d.swing_state, 4); take(d.p_des, 12); take(d.v_des, 12); take(d.f_ff, 12);
-  take(d.grf, 12); take(d.pf_rel, 8); take(d.counter, 1); take(d.first_run, 1); take(d.first_swing, 4); take(d.first_visit, 1);
-  take(d.gait_num, 1); take(d.current_gait, 1); take(d.offsets, 4); take(d.durations, 4); take(d.iteration, 1);
-  take(d.safe, 1); take(d.status, 1);
+#define QMPC_CTRL_CARVE(T, name, per_robot)                     \
+  off = (off + 255) & ~(size_t)255;                            \
+  d.name = base ? reinterpret_cast<T*>(base + off) : nullptr;  \
+  off += sizeof(T) * (size_t)(per_robot) * (size_t)M;
+  QMPC_CTRL_ARRAYS(QMPC_CTRL_CARVE)
+#undef QMPC_CTRL_CARVE
   return off;
 }
 
@@ -1429,8 +1431,7 @@ int ctrl_prework(qmpc_ctx* c, const double* imu, const double* motor, hipStream_
   HIP_TRY(c, qmpc_launch_ctrl_est(&d, c->leg_geom, imu, motor, B, stream));
   qmpc_kf_state st{d.xhat, d.P, d.r_body, d.a_world, d.omega_body, d.contact_phase, d.kf_p, d.kf_v,
                    d.position, d.v_world, d.v_body};
-  static const float hip[3] = {0.19f, 0.049f, 0.f};  // _abadLocation (MiniCheetah.h:25-26,105)
-  HIP_TRY(c, qmpc_launch_kf(&st, hip, B, stream));
+  HIP_TRY(c, qmpc_launch_kf(&st, kAbadLocation, B, stream));
   return QMPC_OK;
 }
 
@@ -1555,18 +1556,9 @@ int qmpc_debug_ctrl_read(qmpc_handle c, const char* name, void* dst, long long c
     const void* p;
     int per;
   };
-#define QA(f, k) {#f, d.f, k}
-  const Arr tab[] = {QA(q, 12), QA(qd, 12), QA(leg_J, 36), QA(leg_p, 12), QA(leg_v, 12), QA(kf_p, 12), QA(kf_v, 12),
-                     QA(orientation, 4), QA(rpy, 3), QA(r_body, 9), QA(omega_body, 3), QA(omega_world, 3),
-                     QA(a_world, 3), QA(ori_ini_inv, 4), QA(xhat, 18), QA(P, 324), QA(position, 3), QA(v_world, 3),
-                     QA(v_body, 3), QA(contact_phase, 4), QA(vel_cmd, 3), QA(vel_des, 3), QA(yaw_des, 1),
-                     QA(yaw_des_true, 1), QA(rpy_int, 2), QA(rpy_comp, 2), QA(stand_traj, 6), QA(wpd, 2), QA(xci, 1),
-                     QA(p_foot, 12), QA(r_cmd, 9), QA(sw_p0, 12), QA(sw_pf, 12), QA(sw_p, 12), QA(sw_v, 12),
-                     QA(swing_time, 4), QA(swing_rem, 4), QA(contact_state, 4), QA(swing_state, 4), QA(p_des, 12),
-                     QA(v_des, 12), QA(f_ff, 12), QA(grf, 12), QA(pf_rel, 8), QA(counter, 1), QA(first_run, 1), QA(first_swing, 4),
-                     QA(first_visit, 1), QA(gait_num, 1), QA(current_gait, 1), QA(offsets, 4), QA(durations, 4),
-                     QA(iteration, 1), QA(safe, 1), QA(status, 1)};
-#undef QA
+#define QMPC_CTRL_ENTRY(T, name, per_robot) {#name, d.name, per_robot},
+  const Arr tab[] = {QMPC_CTRL_ARRAYS(QMPC_CTRL_ENTRY)};
+#undef QMPC_CTRL_ENTRY
   for (const Arr& a : tab) {
     if (std::strcmp(a.n, name) != 0) continue;
     const size_t bytes = (size_t)4 * a.per * (size_t)c->ctrl->batch;

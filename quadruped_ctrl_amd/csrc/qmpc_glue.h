@@ -109,39 +109,73 @@ __device__ __forceinline__ void qmpc_swing_axis(int axis, float p0, float pf, fl
 // ---------------------------------------------------------------------------------------------------
 // Batched locomotion controller (include/qmpc_ctrl.h): the device state of GaitCtrller / ConvexMPCLocomotion for
 // every robot, one row per robot in every array.  Views into two allocations made by qmpc_ctrl_init.
+// The arrays are listed once, as X(element type, name, elements per robot): QmpcCtrlDev's members (in this order -- the
+// struct is passed to kernels by value, so its layout is that of the kernel arguments), their carving out of the
+// allocation (qmpc_capi.cpp: ctrl_carve) and the names of qmpc_debug_ctrl_read are generated from the list.
+#define QMPC_CTRL_ARRAYS(X)                                                                                            \
+  /* inputs of the tick, rounded to float like VectorNavData / LegData (GaitCtrller.cpp:34-56) */                      \
+  X(float, q, 12)                 /* datas[leg].q (clamped by checkJointLimit) */                                      \
+  X(float, qd, 12)                /* .qd */                                                                            \
+  X(float, leg_J, 36)             /* datas[leg].J of this tick */                                                      \
+  X(float, leg_p, 12)             /* .p of this tick */                                                                \
+  X(float, leg_v, 12)             /* .v of this tick */                                                                \
+  X(float, kf_p, 12)              /* the previous tick's .p: what the Kalman filter reads */                           \
+  X(float, kf_v, 12)              /* the previous tick's .v */                                                         \
+  /* StateEstimate */                                                                                                  \
+  X(float, orientation, 4)                                                                                             \
+  X(float, rpy, 3)                                                                                                     \
+  X(float, r_body, 9)                                                                                                  \
+  X(float, omega_body, 3)                                                                                              \
+  X(float, omega_world, 3)                                                                                             \
+  X(float, a_world, 3)                                                                                                 \
+  X(float, ori_ini_inv, 4)        /* VectorNavOrientationEstimator::_ori_ini_inv */                                    \
+  X(float, xhat, 18)              /* LinearKFPositionVelocityEstimator */                                              \
+  X(float, P, 324)                                                                                                     \
+  X(float, position, 3)                                                                                                \
+  X(float, v_world, 3)                                                                                                 \
+  X(float, v_body, 3)                                                                                                  \
+  X(float, contact_phase, 4)      /* StateEstimatorContainer contactPhase */                                           \
+  /* ConvexMPCLocomotion members */                                                                                    \
+  X(float, vel_cmd, 3)            /* _gamepadCommand after SetRobotVel's dead band */                                  \
+  X(float, vel_des, 3)            /* _x_vel_des, _y_vel_des, _yaw_turn_rate */                                         \
+  X(float, yaw_des, 1)                                                                                                 \
+  X(float, yaw_des_true, 1)                                                                                            \
+  X(float, rpy_int, 2)                                                                                                 \
+  X(float, rpy_comp, 2)                                                                                                \
+  X(float, stand_traj, 6)                                                                                              \
+  X(float, wpd, 2)                /* world_position_desired */                                                         \
+  X(float, xci, 1)                /* x_comp_integral */                                                                \
+  X(float, p_foot, 12)            /* pFoot */                                                                          \
+  X(float, r_cmd, 9)              /* rBody for the MPC command (identity in omni mode, see qmpc_ctrl_tick) */          \
+  X(float, sw_p0, 12)             /* footSwingTrajectories[leg] _p0 */                                                 \
+  X(float, sw_pf, 12)             /* _pf */                                                                            \
+  X(float, sw_p, 12)              /* _p */                                                                             \
+  X(float, sw_v, 12)              /* _v */                                                                             \
+  X(float, swing_time, 4)         /* swingTimes */                                                                     \
+  X(float, swing_rem, 4)          /* swingTimeRemaining */                                                             \
+  X(float, contact_state, 4)                                                                                           \
+  X(float, swing_state, 4)                                                                                             \
+  X(float, p_des, 12)             /* commands[leg].pDes */                                                             \
+  X(float, v_des, 12)             /* commands[leg].vDes */                                                             \
+  X(float, f_ff, 12)              /* f_ff (body frame) */                                                              \
+  X(float, grf, 12)               /* grf (the solve's world-frame forces) */                                           \
+  X(float, pf_rel, 8)             /* pfx_rel, pfy_rel per leg after the clamp (:346-365), for tests */                 \
+  X(int, counter, 1)                                                                                                   \
+  X(int, first_run, 1)                                                                                                 \
+  X(int, first_swing, 4)                                                                                               \
+  X(int, first_visit, 1)          /* VectorNavOrientationEstimator::_b_first_visit */                                  \
+  X(int, gait_num, 1)             /* set_gait_type's number */                                                         \
+  X(int, current_gait, 1)         /* current_gait (-1: none yet) */                                                    \
+  X(int, offsets, 4)              /* the selected gait (OffsetDurationGait) */                                         \
+  X(int, durations, 4)                                                                                                 \
+  X(int, iteration, 1)                                                                                                 \
+  X(int, safe, 1)                 /* _safetyCheck */                                                                   \
+  X(int, status, 1)               /* status of the last solve */
+
 struct QmpcCtrlDev {
-  // inputs of the tick, rounded to float like VectorNavData / LegData (GaitCtrller.cpp:34-56)
-  float *q, *qd;                          // [B][12] datas[leg].q (clamped by checkJointLimit), .qd
-  float *leg_J, *leg_p, *leg_v;           // [B][36], [B][12], [B][12] datas[leg].J, .p, .v of this tick
-  float *kf_p, *kf_v;                     // [B][12] the previous tick's .p, .v: what the Kalman filter reads
-  // StateEstimate
-  float *orientation, *rpy, *r_body, *omega_body, *omega_world, *a_world;  // [B][4] [B][3] [B][9] [B][3] x 3
-  float *ori_ini_inv;                     // [B][4] VectorNavOrientationEstimator::_ori_ini_inv
-  float *xhat, *P;                        // [B][18], [B][324] LinearKFPositionVelocityEstimator
-  float *position, *v_world, *v_body;     // [B][3]
-  float *contact_phase;                   // [B][4] StateEstimatorContainer contactPhase
-  // ConvexMPCLocomotion members
-  float *vel_cmd;                         // [B][3] _gamepadCommand after SetRobotVel's dead band
-  float *vel_des;                         // [B][3] _x_vel_des, _y_vel_des, _yaw_turn_rate
-  float *yaw_des, *yaw_des_true;          // [B]
-  float *rpy_int, *rpy_comp;              // [B][2]
-  float *stand_traj;                      // [B][6]
-  float *wpd;                             // [B][2] world_position_desired
-  float *xci;                             // [B]    x_comp_integral
-  float *p_foot;                          // [B][12] pFoot
-  float *r_cmd;                           // [B][9] rBody for the MPC command (identity in omni mode, see qmpc_ctrl_tick)
-  float *sw_p0, *sw_pf, *sw_p, *sw_v;     // [B][12] footSwingTrajectories[leg] _p0, _pf, _p, _v
-  float *swing_time, *swing_rem;          // [B][4] swingTimes, swingTimeRemaining
-  float *contact_state, *swing_state;     // [B][4]
-  float *p_des, *v_des;                   // [B][12] commands[leg].pDes, .vDes
-  float *f_ff, *grf;                      // [B][12] f_ff (body frame), grf (the solve's world-frame forces)
-  float *pf_rel;                          // [B][8]  pfx_rel, pfy_rel per leg after the clamp (:346-365), for tests
-  int *counter, *first_run, *first_swing; // [B], [B], [B][4]
-  int *first_visit;                       // [B] VectorNavOrientationEstimator::_b_first_visit
-  int *gait_num, *current_gait;           // [B] set_gait_type's number, current_gait (-1: none yet)
-  int *offsets, *durations, *iteration;   // [B][4], [B][4], [B] the selected gait (OffsetDurationGait)
-  int *safe;                              // [B] _safetyCheck
-  int *status;                            // [B] status of the last solve
+#define QMPC_CTRL_MEMBER(T, name, per_robot) T* name;
+  QMPC_CTRL_ARRAYS(QMPC_CTRL_MEMBER)
+#undef QMPC_CTRL_MEMBER
   float dt, dt_mpc;                       // ConvexMPCLocomotion::dt, dtMPC
   float kp_joint, kd_joint;               // ctrlParam(2), ctrlParam(3)
 };

@@ -17,7 +17,6 @@ is destroyed: a handle owns a few hundred MB of event pools).  One handle serial
 (include/qmpc.h, "Streams"), so concurrent streams on one device are ordered, not raced.
 """
 from collections import OrderedDict
-import ctypes as C
 
 import torch
 
@@ -95,18 +94,10 @@ def solve(p: torch.Tensor, v: torch.Tensor, q: torch.Tensor, w: torch.Tensor, r:
     iters = torch.empty((B,), dtype=torch.int32, device=dev)
     if B == 0:
         return grf, soln, status, iters
-    inp = _b.Inputs()
-    for name, t in (("p", p), ("v", v), ("q", q), ("w", w), ("r", r), ("yaw", yaw), ("traj", traj), ("gait", gait),
-                    ("weights", weights.contiguous()), ("alpha", alpha.contiguous()), ("x_drag", x_drag.contiguous())):
-        setattr(inp, name, t.data_ptr())
-    # stride 0 = one row shared by the batch (with B == 1 both readings address the same row)
-    inp.weights_stride = 0 if weights.numel() == 12 else 12
-    inp.alpha_stride = 0 if alpha.numel() == 1 else 1
-    inp.x_drag_stride = 0 if x_drag.numel() == 1 else 1
+    rec = dict(p=p, v=v, q=q, w=w, r=r, yaw=yaw, traj=traj, gait=gait, weights=weights.contiguous(),
+               alpha=alpha.contiguous(), x_drag=x_drag.contiguous())
     out = _b.Outputs(grf.data_ptr(), soln.data_ptr() if full else None, status.data_ptr(), iters.data_ptr())
-    stream = torch.cuda.current_stream(dev)
-    rc = m.lib.qmpc_solve(m.h, B, C.byref(inp), C.byref(out), C.c_void_p(stream.cuda_stream))
-    m._check(rc, "qmpc_solve")
+    m.solve_async(B, _b.make_inputs(rec, B), out)   # (on torch's current stream)
     return grf, soln, status, iters
 
 

@@ -144,3 +144,16 @@ def test_controller_symbols_exported():
     # the argument checks need no device: a null handle is refused
     assert lib.qmpc_ctrl_tick(None, 1, None, None, None, None) == 1
     assert lib.qmpc_ctrl_view_get(None, None) == 1
+
+
+def test_binding_agrees_with_the_controller_array_list():
+    """QMPC_CTRL_ARRAYS (csrc/qmpc_glue.h) is the one list of the controller's device arrays; what the binding still has
+    to know about it (read()'s int32 arrays, view()'s widths and element types) matches it."""
+    src = open(os.path.join(ROOT, "quadruped_ctrl_amd", "csrc", "qmpc_glue.h")).read()
+    body = re.search(r"#define QMPC_CTRL_ARRAYS\(X\)((?:.*\\\n)*.*)", src).group(1)
+    arrays = {n: (t, int(w)) for t, n, w in re.findall(r"X\((\w+), (\w+), (\d+)\)", body)}
+    assert arrays and {t for t, _ in arrays.values()} <= {"float", "int"}   # (read() moves 4-byte elements)
+    assert {n for n, (t, _) in arrays.items() if t == "int"} == set(binding.CTRL_INT_ARRAYS)
+    for k, n in binding.CTRL_VIEW_WIDTH.items():
+        t, w = arrays[dict(leg_q="q").get(k, k)]
+        assert w == n and t == ("int" if k in ("safe", "counter") else "float"), k
