@@ -1,7 +1,7 @@
 /*
  * qmpc_ctrl.h -- batched locomotion controller on top of the C ABI of qmpc.h (same library, same ABI version).
  *
- * GaitCtrller::TorqueCalculator (src/GaitCtrller.cpp:95-145) for `batch` robots in lockstep: the orientation
+ * GaitCtrller::TorqueCalculator (src/GaitCtrller.cpp:95-145) for `batch` robots: the orientation
  * estimator (src/Controllers/OrientationEstimator.cpp:46-110), the Kalman filter, the safety checks
  * (GaitCtrller.cpp:108-123, src/Controllers/SafetyChecker.cpp), ConvexMPCLocomotion::run
  * (src/MPC_Ctrl/ConvexMPCLocomotion.cpp:116-496) with the MPC every 13 ticks, and LegController::updateCommand.
@@ -22,12 +22,26 @@
  *   gait[B]       int32: gait number 0 .. 11 (:149-171; 1 bounding, 2 pronking, 4 standing, 5 trot running,
  *                 7 galloping, 8 pacing, 10 walking, 11 walking2, anything else trotting), +20 = omni mode (:129-132)
  *
- * Lockstep: the handle counts ticks (T).  Every robot's iterationCounter is congruent to T modulo 13, so the
- * MPC runs for the whole batch on the same ticks -- one qmpc_solve_commands launch.  qmpc_ctrl_reset deviates
+ * MPC schedule (qmpc_ctrl_set_schedule), two modes:
+ *
+ * Lockstep (QMPC_CTRL_LOCKSTEP, the default): the handle counts ticks (T).  Every robot's iterationCounter is congruent
+ * to T modulo 13, so the MPC runs for the whole batch on the same ticks -- one solve launch over the batch, decided on
+ * the host from T.  qmpc_ctrl_reset deviates
  * from a fresh init_controller on exactly this point: a reset robot restarts with iterationCounter = T mod 13
  * (not 0), i.e. its gait clock starts part-way into the first MPC segment.  A graph captured from the tick
  * calls must hold a multiple of 13 ticks: T counts qmpc_ctrl_tick calls, captured ones included, and graph replays
  * do not advance it (qmpc_ctrl_view's `ticks` is T, not the number of ticks executed).
+ *
+ * Per-robot schedule (QMPC_CTRL_PER_ROBOT): each robot's own device-side counter decides.  Every tick enqueues the same
+ * kernels -- estimator, Kalman filter, locomotion, solve, leg commands; the locomotion kernel writes due[b] =
+ * (incremented counter % 13 == 0) and appends the due robots to a dense device-side list, and the solve's first launch
+ * takes its robots from that list (workgroups beyond the device-side count leave at once).  A robot that is not due is not
+ * scheduled: its command rows, world_position_desired / x_comp_integral bookkeeping of the MPC, grf, status and f_ff are
+ * not touched by the solve.  qmpc_ctrl_reset is init_controller exactly: iterationCounter = 0, so the robot's first
+ * solve comes 13 ticks after its reset, whatever T is -- the lockstep deviation does not apply.  T is still counted and
+ * reported, but nothing depends on it: a captured graph may hold any number of ticks, and replays continue every
+ * robot's schedule (the counters are device state).  To spread the solves of a fleet over the ticks, initialise,
+ * select this mode, and reset group g on tick g (g = 0 .. 12): every robot stays in a state the reference can reach.
  *
  * Errors: a tick that returns QMPC_ERR_DEVICE may have advanced some of the controller state (T and the counters
  * advance together once the locomotion kernel is enqueued, so the MPC schedule stays consistent); re-initialise the
@@ -53,8 +67,15 @@ extern "C" {
  * The handle's max_horizon must be at least 14.  Synchronises the device (allocation); resets T to 0. */
 int qmpc_ctrl_init(qmpc_handle h, int batch, double freq, const double pid[4], void* stream);
 
-/* Re-initialise the robots whose mask_dev[b] (uint8, device) is non-zero exactly as qmpc_ctrl_init does, except
- * that their iteration counter restarts at T mod 13 (see Lockstep above).  The other robots are untouched. */
+/* The MPC schedule (see above).  qmpc_ctrl_init always leaves the handle in lockstep; the mode can be changed only
+ * between qmpc_ctrl_init and the first qmpc_ctrl_tick or qmpc_ctrl_reset (QMPC_ERR_STATE afterwards, and before
+ * qmpc_ctrl_init); an unknown mode is QMPC_ERR_ARG.  Host state only: nothing is enqueued. */
+enum { QMPC_CTRL_LOCKSTEP = 0, QMPC_CTRL_PER_ROBOT = 1 };
+int qmpc_ctrl_set_schedule(qmpc_handle h, int mode);
+
+/* Re-initialise the robots whose mask_dev[b] (uint8, device) is non-zero exactly as qmpc_ctrl_init does -- in lockstep
+ * except that their iteration counter restarts at T mod 13 (see Lockstep above); with the per-robot schedule without
+ * exception (counter 0).  The other robots are untouched. */
 int qmpc_ctrl_reset(qmpc_handle h, int batch, const uint8_t* mask_dev, void* stream);
 
 /* set_gait_type for every robot (gait_dev: int32 [B], device). */
@@ -67,7 +88,8 @@ int qmpc_ctrl_set_vel(qmpc_handle h, int batch, const double* vel_dev, void* str
 int qmpc_ctrl_prework(qmpc_handle h, int batch, const double* imu, const double* motor, void* stream);
 
 /* torque_calculator (GaitCtrller.cpp:95-145): pre_work, the safety checks, one ConvexMPCLocomotion::run tick
- * (the MPC when the incremented counter is a multiple of 13) and the leg commands -> effort[B][12]. */
+ * (the MPC when the incremented counter is a multiple of 13: for the whole batch in lockstep, for the due robots with
+ * the per-robot schedule) and the leg commands -> effort[B][12]. */
 int qmpc_ctrl_tick(qmpc_handle h, int batch, const double* imu, const double* motor, double* effort, void* stream);
 
 /* Read-only device views of the controller state (valid until the handle is destroyed or re-initialised). */

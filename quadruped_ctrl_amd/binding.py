@@ -20,7 +20,8 @@ ST_NONFINITE = 32
 ST_ERROR_MASK = 15 | 32
 # the int32 arrays among the controller's device state (QMPC_CTRL_ARRAYS in csrc/qmpc_glue.h): what read() returns as int32
 CTRL_INT_ARRAYS = ("counter", "first_run", "first_swing", "first_visit", "gait_num", "current_gait", "offsets", "durations",
-                   "iteration", "safe", "status")
+                   "iteration", "safe", "status", "due", "due_list", "due_count")
+CTRL_SCHEDULES = dict(lockstep=0, per_robot=1)   # QMPC_CTRL_LOCKSTEP / QMPC_CTRL_PER_ROBOT (include/qmpc_ctrl.h)
 
 # qmpc_ctrl_view's float arrays (include/qmpc_ctrl.h) in declaration order, elements per robot
 CTRL_VIEW_FIELDS = ("position", "v_world", "orientation", "rpy", "r_body", "omega_world", "leg_q", "leg_p", "leg_v",
@@ -161,6 +162,7 @@ SIGNATURES = {
 # the batched locomotion controller's own header (include/qmpc_ctrl.h), same library and ABI version
 CTRL_SIGNATURES = {
     "qmpc_ctrl_init": [_P, _I, _D, C.POINTER(_D), _P],
+    "qmpc_ctrl_set_schedule": [_P, _I],
     "qmpc_ctrl_reset": [_P, _I, _P, _P],
     "qmpc_ctrl_set_gait": [_P, _I, _P, _P],
     "qmpc_ctrl_set_vel": [_P, _I, _P, _P],
@@ -589,7 +591,8 @@ class BatchedConvexMPC:
 
 
 class BatchedController:
-    """GaitCtrller::TorqueCalculator for `batch` robots in lockstep on one GPU (include/qmpc_ctrl.h), robot mode 0.
+    """GaitCtrller::TorqueCalculator for `batch` robots on one GPU (include/qmpc_ctrl.h), robot mode 0; the MPC in
+    lockstep by default, per robot after set_schedule("per_robot").
 
     The reference's single-robot calls map one to one: init_controller -> init(), set_gait_type -> set_gait(),
     set_robot_vel -> set_vel(), pre_work -> prework(), torque_calculator -> tick(); reset() re-initialises chosen
@@ -621,8 +624,16 @@ class BatchedController:
         self.batch = int(batch)
         self.mpc.horizon = 14
 
+    def set_schedule(self, mode):
+        """"lockstep" (the default after every init()) or "per_robot": each robot's own counter decides when it solves, and
+        reset() is init_controller exactly (counter 0).  Only between init() and the first tick() or reset()."""
+        if mode not in CTRL_SCHEDULES:
+            raise QmpcError(f"set_schedule: unknown mode {mode!r} (one of {sorted(CTRL_SCHEDULES)})")
+        self.mpc._check(self.lib.qmpc_ctrl_set_schedule(self.mpc.h, CTRL_SCHEDULES[mode]), "qmpc_ctrl_set_schedule")
+
     def reset(self, mask, stream=None):
-        """Re-initialise the robots where mask is set; their iteration counter restarts at T mod 13 (lockstep)."""
+        """Re-initialise the robots where mask is set; their iteration counter restarts at T mod 13 in lockstep, at 0
+        with the per-robot schedule."""
         m = mask.to(self.torch.uint8).contiguous() if mask is not None else None
         ptr = self._chk(m, (self.batch,), self.torch.uint8, "mask") if m is not None else None
         self.mpc._check(self.lib.qmpc_ctrl_reset(self.mpc.h, self.batch or 0, ptr, self._s(stream)), "qmpc_ctrl_reset")

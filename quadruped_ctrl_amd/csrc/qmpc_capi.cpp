@@ -104,7 +104,7 @@ extern "C" hipError_t qmpc_launch_ctrl_set(const QmpcCtrlDev* S, const int32_t* 
                                            hipStream_t stream);
 extern "C" hipError_t qmpc_launch_ctrl_est(const QmpcCtrlDev* S, const float geom[4], const double* imu,
                                            const double* motor, int batch, hipStream_t stream);
-extern "C" hipError_t qmpc_launch_ctrl_loco(const QmpcCtrlDev* S, int batch, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_ctrl_loco(const QmpcCtrlDev* S, int batch, int build_list, hipStream_t stream);
 extern "C" hipError_t qmpc_launch_ctrl_legcmd(const QmpcCtrlDev* S, double* effort, int batch, hipStream_t stream);
 extern "C" hipError_t qmpc_launch_swing(const float* p0, const float* pf, const float* height, const float* phase,
                                         const float* swing_time, float* p, float* v, float* a, int n_feet,
@@ -214,6 +214,8 @@ struct qmpc_ctx {
     void* buf = nullptr;
     int batch = 0;       // robots initialised
     long long ticks = 0; // T: qmpc_ctrl_tick calls since qmpc_ctrl_init
+    int schedule = QMPC_CTRL_LOCKSTEP;  // qmpc_ctrl_set_schedule
+    bool started = false;               // a tick or a reset has been enqueued since qmpc_ctrl_init: the schedule is fixed
   };
   Ctrl* ctrl = nullptr;
 };
@@ -796,10 +798,17 @@ int ensure_pools(qmpc_ctx* c) {
   return QMPC_OK;
 }
 
-// one solve: inputs either as the record (`in`) or as the controller command (`cmd`, record built in stage 0)
+// one solve: inputs either as the record (`in`) or as the controller command (`cmd`, record built in stage 0).
+// due_list / due_count (internal, device-resident, command mode only; nullptr: every robot of the batch): the dense list
+// of the robots this call solves and its length, both written on the device by work enqueued before the call (the
+// batched controller's per-robot schedule).  A robot that is not listed is not scheduled at all: the first class of
+// the chain maps its workgroups to robots through the list and those beyond the device-side count leave at once, as
+// the later classes do with theirs, so the robot runs no QP, reaches no later list, no engine and no overflow slice, and
+// none of its outputs or command rows is written.
 int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command* cmd, const qmpc_outputs* out,
-               float* f_ff, void* stream_) {
+               float* f_ff, void* stream_, const int* due_list = nullptr, int* due_count = nullptr) {
   if (!c || (!in && !cmd) || !out) return QMPC_ERR_ARG;
+  if ((due_list != nullptr) != (due_count != nullptr) || (due_list && !cmd)) return QMPC_ERR_ARG;
   if (!c->is_setup) return QMPC_ERR_STATE;
   if (batch < 0 || batch > c->max_batch) return QMPC_ERR_ARG;
   if (batch == 0) return QMPC_OK;
@@ -906,7 +915,8 @@ int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command
   }
   int* cnt;       // this call's counters
   int* cnt_next;  // the set this call's first kernel clears (the next call's)
-  if (capturing) {
+  if (capturing || due_list) {
+    // (a due-list call too: its first launch is a list consumer, and those do not clear the next call's set)
     // a call captured into a hipGraph is replayed with the SAME kernel arguments every time: it cannot take part in
     // the ping-pong (its set would be dirty from the previous replay).  Captured calls use a set of their own, cleared
     // by a small kernel node in front of the call's kernels; the eager calls' two sets are not touched
@@ -1005,10 +1015,15 @@ int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command
   // n_r = 3 * stance foot-steps.  The first class is launched over the whole batch; a robot that
   // does not fit appends itself to the list of the next one.
   for (int k = pl.k0; k < pl.k1; ++k) {
-    const bool listed = k > pl.k0;
+    const bool listed = k > pl.k0 || due_list;
     P.list = listed ? c->d_lists + (size_t)(k - 1) * c->max_batch : nullptr;
     P.count = listed ? cnt + (k - 1) : nullptr;
     P.qhead = listed ? cnt + 4 + (k - 1) : nullptr;
+    if (k == pl.k0 && due_list) {  // the first class takes the caller's list instead of the whole batch
+      P.list = due_list;
+      P.count = due_count;
+      P.qhead = cnt + QMPC_CNT_DUEQ;
+    }
     const bool more = k + 1 < pl.k1;
     P.next_list = more ? c->d_lists + (size_t)k * c->max_batch : nullptr;
     P.next_count = more ? cnt + k : nullptr;
@@ -1047,6 +1062,9 @@ int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command
     // batch <= 4 x the slices)
     if (kcls == 1 && pl.k1 - pl.k0 > 1 && !pl.long_h && c->dense == 1 && c->max_batch >= 2048) kcls = 6;
     if (kcls == 1 && pl.k1 - pl.k0 == 1 && !pl.long_h && (c->dense == 2 || (c->dense == 1 && c->max_batch >= 2048))) kcls = 6;
+    // (a due list in front of a 64-row class: qmpc_solve_due_kernel, one workgroup per list place -- the grid is the batch, and
+    //  the workgroups beyond the device-side count leave at once; in front of any other class: that class's list consumer)
+    if (k == pl.k0 && due_list && (kcls == 1 || kcls == 6)) grid = batch;
     // order hint: the first class of the chain, launched over more robots than it has resident workgroups (several rounds:
     // the launch ends with whichever hard robot started last), takes the robots in the order of their iteration counts in the
     // previous call -- the same robots one MPC cycle earlier -- longest first.  Results do not depend on the order.
@@ -1125,7 +1143,7 @@ int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command
     P.hint_max_z = nullptr;
     P.hint_max_w = nullptr;  // (the later classes of a chain are queues of several rounds)
   }
-  if (c->order_hint && !capturing && !P.admm_mode) c->hint_batch = batch;
+  if (c->order_hint && !capturing && !P.admm_mode && !due_list) c->hint_batch = batch;  // (a due list leaves counts for its robots only)
   if (pl.long_h) {
     // ---- the large problems (192 < n_r <= 432: all feet down beyond 16 segments, a trot beyond 32): H in global memory,
     // block sweep, the seven-block engine; what that engine cannot hold is REPORTED.  Normally the list is empty: launches
@@ -1463,6 +1481,8 @@ int qmpc_ctrl_init(qmpc_handle c, int batch, double freq, const double pid[4], v
   HIP_TRY(c, qmpc_launch_ctrl_init(&k->d, nullptr, 0, batch, stream));
   k->batch = batch;
   k->ticks = 0;
+  k->schedule = QMPC_CTRL_LOCKSTEP;
+  k->started = false;
   return QMPC_OK;
 }
 
@@ -1472,7 +1492,21 @@ int qmpc_ctrl_reset(qmpc_handle c, int batch, const uint8_t* mask_dev, void* str
   DeviceGuard g(c->device);
   hipStream_t stream = (hipStream_t)stream_;
   if (const int rc = order_after_previous(c, stream)) return rc;
-  HIP_TRY(c, qmpc_launch_ctrl_init(&c->ctrl->d, mask_dev, (int)(c->ctrl->ticks % 13), batch, stream));
+  // lockstep: the counter restarts at T mod 13 (the batch keeps solving on the same ticks); per-robot schedule: at 0, as
+  // init_controller leaves it
+  qmpc_ctx::Ctrl* k = c->ctrl;
+  k->started = true;
+  const int counter0 = k->schedule == QMPC_CTRL_PER_ROBOT ? 0 : (int)(k->ticks % 13);
+  HIP_TRY(c, qmpc_launch_ctrl_init(&k->d, mask_dev, counter0, batch, stream));
+  return QMPC_OK;
+}
+
+int qmpc_ctrl_set_schedule(qmpc_handle c, int mode) {
+  if (!c) return QMPC_ERR_ARG;
+  if (!c->ctrl || !c->ctrl->batch) return QMPC_ERR_STATE;
+  if (mode != QMPC_CTRL_LOCKSTEP && mode != QMPC_CTRL_PER_ROBOT) return QMPC_ERR_ARG;
+  if (c->ctrl->started) return QMPC_ERR_STATE;
+  c->ctrl->schedule = mode;
   return QMPC_OK;
 }
 
@@ -1513,11 +1547,16 @@ int qmpc_ctrl_tick(qmpc_handle c, int batch, const double* imu, const double* mo
   if (const int rc = order_after_previous(c, stream)) return rc;
   qmpc_ctx::Ctrl* k = c->ctrl;
   const QmpcCtrlDev& d = k->d;
+  const bool per_robot = k->schedule == QMPC_CTRL_PER_ROBOT;
+  k->started = true;
   if (const int rc = ctrl_prework(c, imu, motor, stream)) return rc;
-  HIP_TRY(c, qmpc_launch_ctrl_loco(&d, batch, stream));
+  HIP_TRY(c, qmpc_launch_ctrl_loco(&d, batch, per_robot ? 1 : 0, stream));
   // the locomotion kernel advances every robot's counter: T follows it here, before the launches that can still fail,
   // so that the host's MPC schedule and the device's `counter % 13` test never disagree
-  const bool mpc_tick = ++k->ticks % 13 == 0;  // every robot's incremented counter is a multiple of 13 (lockstep)
+  // lockstep: every robot's incremented counter is a multiple of 13 on the same ticks, known from T alone.
+  // per-robot schedule: nothing depends on T -- every tick enqueues the solve over the list of due robots the locomotion
+  // kernel has just built (d.due_list, d.due_count[0]); a tick on which nobody is due costs launches that find no entry
+  const bool mpc_tick = (++k->ticks % 13 == 0) || per_robot;
   if (mpc_tick) {
     qmpc_command cmd{};
     cmd.position = d.position;
@@ -1541,7 +1580,9 @@ int qmpc_ctrl_tick(qmpc_handle c, int batch, const double* imu, const double* mo
     cmd.body_height = 0.25f;  // _SetupCommand (:79)
     cmd.omni_mode = 0;        // per robot through r_cmd
     qmpc_outputs out{d.grf, nullptr, d.status, nullptr};
-    if (const int rc = qmpc_solve_commands(c, batch, &cmd, &out, nullptr, stream)) return rc;
+    if (const int rc = solve_impl(c, batch, nullptr, &cmd, &out, nullptr, stream, per_robot ? d.due_list : nullptr,
+                                  per_robot ? d.due_count : nullptr))
+      return rc;
   }
   HIP_TRY(c, qmpc_launch_ctrl_legcmd(&d, effort, batch, stream));
   return QMPC_OK;

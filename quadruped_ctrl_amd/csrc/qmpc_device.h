@@ -28,6 +28,7 @@
 //   [0..2] list lengths of classes 4, 2, 3   [3] list length of the large problems (horizons > 16, n_r > 192)
 //   [4..6] queue heads of the one-kernel list consumers   [7] overflow-pool slices handed out   [16] / [17] probes that
 //   found a slice taken / robots that timed out waiting for one (QMPC_CNT_OV_*)
+//   [18] queue head of a call's due list (QMPC_CNT_DUEQ: a first class other than the 64-row ones consumes it as a queue)
 //   [8 + sk] robots the engine kernel of item class sk hands back (sk = 0: 128-row class, 1: 192-row class, 2: large
 //   problems)   [12 + sk] queue heads of the launches that take them
 //   [QMPC_CNT_GRP(sk, g)], g = 0 / 1: one GROUP of counters per chunk in flight of item class sk.  The work items of a class
@@ -43,6 +44,7 @@
 #define QMPC_CNT_OV 7          // robots that took a slice of the overflow pool in this call
 #define QMPC_CNT_OV_PROBES 16  // ... compare-and-swap probes of theirs that found a slice taken (0 unless the pool is nearly full)
 #define QMPC_CNT_OV_TIMEOUT 17 // ... robots that gave up after ov_spin probes (-> Schur-form fallback, QMPC_ST_FALLBACK)
+#define QMPC_CNT_DUEQ 18       // queue head of the due list (solve_impl's due_list: the first class consumes it like a later class its list)
 #define QMPC_CNT_FB 8
 #define QMPC_CNT_FBQ 12
 #define QMPC_CNT_GRP(sk, g) (64 + QMPC_GRP_INTS * (2 * (sk) + (g)))
@@ -153,7 +155,8 @@ struct QmpcParams {
   // selective warm start (qmpc_set_warm_start_min_iters): only robots that needed at least this many iterations in the
   // handle's previous call (hint_iters) read their previous working set; everybody else starts cold.  <= 0: every robot
   int ws_min_iters;
-  // work lists: robots handed from one size class to the next
+  // work lists: robots handed from one size class to the next -- or, for the first class of a call, the caller's dense list of
+  // the robots to solve (the batched controller's due robots, device-resident; every other robot of the batch is not scheduled)
   const int* list;   // nullptr: robot = blockIdx.x
   int* count;        // entries in `list`
   int* qhead;        // queue head of `list`: entries past the grid size are handed out through it

@@ -170,7 +170,11 @@ __device__ __forceinline__ void qmpc_swing_axis(int axis, float p0, float pf, fl
   X(int, durations, 4)                                                                                                 \
   X(int, iteration, 1)                                                                                                 \
   X(int, safe, 1)                 /* _safetyCheck */                                                                   \
-  X(int, status, 1)               /* status of the last solve */
+  X(int, status, 1)               /* status of the last solve */                                                       \
+  /* the MPC schedule of the tick (qmpc_ctrl_set_schedule) */                                                          \
+  X(int, due, 1)                  /* 1: the incremented counter is a multiple of 13 (this tick solves for the robot) */\
+  X(int, due_list, 1)             /* per-robot schedule: the due robots of the tick, dense, [0 .. due_count[0]) */      \
+  X(int, due_count, 1)            /* ... their number, in element 0 (the rest of the row-per-robot array is unused) */
 
 struct QmpcCtrlDev {
 #define QMPC_CTRL_MEMBER(T, name, per_robot) T* name;

@@ -348,7 +348,9 @@ extern "C" hipError_t qmpc_launch_kf_init(float* xhat, float* P, int batch, hipS
 //                            updateData, GaitCtrller.cpp:58-63) and the contact phase of the previous tick
 //   qmpc_ctrl_loco_kernel    the safety checks and ConvexMPCLocomotion::run up to the MPC (one thread per robot):
 //                            writes the qmpc_command rows
-//   (qmpc_solve_commands     on ticks whose incremented counter is a multiple of 13, unchanged)
+//   (the solve               lockstep: qmpc_solve_commands on the ticks whose incremented counter is a multiple of 13,
+//                            decided on the host from T; per-robot schedule: every tick, over the list of due
+//                            robots the locomotion kernel left -- qmpc_capi.cpp: solve_impl's due list)
 //   qmpc_ctrl_legcmd_kernel  f_ff from the solve, the swing / stance gains, LegController::updateCommand, the latch
 // Decisions where the reference's C++ does not say what it computes at first sight (pinned by
 // tests/test_gpu_controller.py and tests/test_ctrl_cpu.py):
@@ -490,6 +492,7 @@ __global__ __launch_bounds__(256) void qmpc_ctrl_est_kernel(const QmpcCtrlDev S,
   if (t >= n) return;
   const int b = t >> 2, leg = t & 3;
   const size_t o3 = (size_t)t * 3;
+  if (t == 0) S.due_count[0] = 0;  // the tick's list of due robots starts empty (filled by the locomotion kernel)
   const double* m = motor + (size_t)b * 24;
   const float q0 = (float)m[3 * leg], q1 = (float)m[3 * leg + 1], q2 = (float)m[3 * leg + 2];
   const float d0 = (float)m[12 + 3 * leg], d1 = (float)m[12 + 3 * leg + 1], d2 = (float)m[12 + 3 * leg + 2];
@@ -514,7 +517,8 @@ __global__ __launch_bounds__(256) void qmpc_ctrl_est_kernel(const QmpcCtrlDev S,
 }
 
 // The safety checks and ConvexMPCLocomotion::run up to updateMPCIfNeeded, one thread per robot
-__global__ __launch_bounds__(256) void qmpc_ctrl_loco_kernel(const QmpcCtrlDev S, const int batch) {
+// build_list (per-robot schedule): the due robots also append themselves to S.due_list, one atomic per wave
+__global__ __launch_bounds__(256) void qmpc_ctrl_loco_kernel(const QmpcCtrlDev S, const int batch, const int build_list) {
 #pragma clang fp contract(off)
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= batch) return;
@@ -719,6 +723,21 @@ __global__ __launch_bounds__(256) void qmpc_ctrl_loco_kernel(const QmpcCtrlDev S
   // the MPC command's rBody: the identity for omni robots (v_des_world = v_des_robot); f_ff uses the true rBody
   float* rc9 = S.r_cmd + (size_t)b * 9;
   for (int k = 0; k < 9; ++k) rc9[k] = omni ? ((k % 4 == 0) ? 1.f : 0.f) : rB[k];
+  // the MPC schedule: updateMPCIfNeeded solves when the incremented counter is a multiple of 13 (:387)
+  const bool due = (cnt + 1) % ibm == 0;
+  S.due[b] = due ? 1 : 0;
+  if (build_list) {
+    // dense list of the due robots (what the solve's first launch consumes): the wave's due lanes take consecutive
+    // places behind one atomic add of its first due lane; at most `batch` entries (every robot appends at most once)
+    const unsigned long long m = __ballot(due);
+    if (m) {
+      const int lane = (int)__lane_id(), leader = __ffsll(m) - 1;
+      int base = 0;
+      if (lane == leader) base = atomicAdd(S.due_count, __popcll(m));
+      base = __shfl(base, leader);
+      if (due) S.due_list[base + __popcll(m & ((1ull << lane) - 1ull))] = b;
+    }
+  }
 }
 
 // f_ff (on MPC ticks), the gains of :378-382, LegController::updateCommand and the latch; one thread per (robot, leg)
@@ -839,6 +858,9 @@ __global__ __launch_bounds__(256) void qmpc_ctrl_init_kernel(const QmpcCtrlDev S
   S.iteration[b] = 0;
   S.safe[b] = 1;
   S.status[b] = 0;
+  S.due[b] = 0;
+  S.due_list[b] = 0;
+  S.due_count[b] = 0;  // (element 0 is the count of a tick, rebuilt by every tick; the rest is never used)
 }
 
 __global__ __launch_bounds__(256) void qmpc_ctrl_set_kernel(const QmpcCtrlDev S, const int32_t* __restrict__ gait,
@@ -875,8 +897,8 @@ extern "C" hipError_t qmpc_launch_ctrl_est(const QmpcCtrlDev* S, const float geo
   return hipGetLastError();
 }
 
-extern "C" hipError_t qmpc_launch_ctrl_loco(const QmpcCtrlDev* S, int batch, hipStream_t stream) {
-  hipLaunchKernelGGL(qmpc_ctrl_loco_kernel, dim3((batch + 255) / 256), dim3(256), 0, stream, *S, batch);
+extern "C" hipError_t qmpc_launch_ctrl_loco(const QmpcCtrlDev* S, int batch, int build_list, hipStream_t stream) {
+  hipLaunchKernelGGL(qmpc_ctrl_loco_kernel, dim3((batch + 255) / 256), dim3(256), 0, stream, *S, batch, build_list);
   return hipGetLastError();
 }
 

@@ -3746,6 +3746,23 @@ __global__ __launch_bounds__(Cfg<RB>::NT_LAUNCH, Cfg<RB>::MIN_WAVES) void qmpc_s
   }
 }
 
+// The first class of a call over a DUE LIST (qmpc_capi.cpp: solve_impl's due_list -- the batched controller's per-robot MPC
+// schedule; command mode, the 64-row classes): the grid is the batch, workgroup i takes robot list[i], and the workgroups beyond
+// the device-side count leave at once -- the live workgroups are the first *count of the grid, contiguous.  No queue loop (the
+// first class runs four / five workgroups per CU, so a no-op workgroup costs its dispatch only): the body is the first-class
+// kernel's, one robot per workgroup.  A kernel of its own, so that no existing instantiation gains an argument or a branch.
+template <int RB>
+__global__ __launch_bounds__(Cfg<RB>::NT_LAUNCH, Cfg<RB>::MIN_WAVES) void qmpc_solve_due_kernel(const QmpcParams P) {
+  static_assert(Cfg<RB>::C1 && !Cfg<RB>::BALANCE && !Cfg<RB>::GLOBAL_EVENTS, "the 64-row classes: no wave placement, no global event pool");
+  extern __shared__ __attribute__((aligned(16))) unsigned char qmpc_smem[];
+  Smem<RB>& S = *reinterpret_cast<Smem<RB>*>(qmpc_smem);
+  if ((int)blockIdx.x >= *P.count) return;  // uniform: not a due robot's workgroup
+  const int rid = P.list[blockIdx.x];        // (< batch: the list holds robot indices of this call)
+  const int tid0 = (int)threadIdx.x;
+  __builtin_assume(tid0 >= 0 && tid0 < Cfg<RB>::NT);
+  solve_robot<RB, true, false>(rid, tid0, S, P);
+}
+
 // JCQP alternate (update_solver_settings' use_jcqp = 1 / 2): same assembly and sweep, ADMM instead of the
 // active set; record mode only, same size-class chain
 template <int RB, bool LISTED = false>
@@ -3855,7 +3872,9 @@ hipError_t prepare_class() {
   if ((e = set_smem(qmpc_solve_kernel<RB, true, false, false>, n)) != hipSuccess) return e;
   if ((e = set_smem(qmpc_solve_kernel<RB, false, true, false>, n)) != hipSuccess) return e;
   if ((e = set_smem(qmpc_admm_kernel<RB, false>, n)) != hipSuccess) return e;
-  if constexpr (!Cfg<RB>::C1) {  // (class 1 is only ever launched first)
+  if constexpr (Cfg<RB>::C1) {  // (class 1 is only ever launched first: over a call's due list with a kernel of its own)
+    if ((e = set_smem(qmpc_solve_due_kernel<RB>, n)) != hipSuccess) return e;
+  } else {
     if ((e = set_smem(qmpc_solve_kernel<RB, false, false, true>, n)) != hipSuccess) return e;
     if ((e = set_smem(qmpc_solve_kernel<RB, true, false, true>, n)) != hipSuccess) return e;
     if ((e = set_smem(qmpc_solve_kernel<RB, false, true, true>, n)) != hipSuccess) return e;
@@ -3917,6 +3936,13 @@ template <int RB>
 void launch_one(bool cmd, const QmpcParams* P, int grid, hipStream_t stream) {
   if constexpr (!Cfg<RB>::C1) {
     if (P->list) return launch_variant<RB, true>(cmd, P, grid, stream);
+  } else {
+    // the first class over a due list (solve_impl: command mode only; grid = batch): qmpc_solve_due_kernel
+    if (P->list) {
+      const dim3 g(grid), bs(Cfg<RB>::NT_LAUNCH);
+      hipLaunchKernelGGL((qmpc_solve_due_kernel<RB>), g, bs, sizeof(Smem<RB>), stream, *P);
+      return;
+    }
   }
   launch_variant<RB, false>(cmd, P, grid, stream);
 }

@@ -1,0 +1,295 @@
+"""GPU suite (-m gpu) for the batched controller's per-robot MPC schedule (qmpc_ctrl_set_schedule, include/qmpc_ctrl.h).
+
+The robots of a batch are independent, so a robot under the per-robot schedule must behave as the same robot in a
+LOCKSTEP controller freshly initialised at the moment of its reset: a fresh lockstep controller has T = 0 and is the
+reference's init_controller exactly, and lockstep is what tests/test_gpu_controller.py pins against the restatement and
+the oracle.  Everything here is therefore compared bit for bit between two runs of the library:
+  * the effort of every tick,
+  * the arrays of test_gpu_controller's EXACT_F32 / EXACT_I32 lists, f_ff, wpd and xci after every tick.
+Streams are workloads.make_tick_stream, gaits and velocities the mixed ones of test_gpu_controller.py (every gait number
+and omni variant, switched into and out of standing at tick 20 of the stream), PID (0, 0, 3.0, 0.3).  A reset zeroes the
+robot's gait and velocity command, so both are applied again after every reset, in both runs.
+
+One deliberate difference from "every MPC array of a robot that is not due is bit-equal before and after the tick":
+world_position_desired is ALSO integrated by the locomotion step of every tick (ConvexMPCLocomotion.cpp:268-270,
+wpd += dt * v_des_world for a robot that is not standing), independent of the MPC.  For a robot that is not due the test
+therefore requires wpd after the tick to equal, bit for bit, what that step alone makes of the value before the tick
+(_loco_wpd: the float32 statement of tests/ctrl_model.py) -- i.e. that the solve's clamp (:534-545) did not touch it;
+f_ff, grf, status and xci must be bit-equal before and after.
+"""
+import numpy as np
+import pytest
+
+from quadruped_ctrl_amd import workloads as W
+
+from test_gpu_controller import EXACT_F32, EXACT_I32, PID, _gaits, _vel
+
+pytestmark = pytest.mark.gpu
+
+f32 = np.float32
+STATE = EXACT_F32 + EXACT_I32 + ("f_ff", "wpd", "xci")
+SWITCH_AT = 20   # tick of the stream at which the gaits switch
+
+
+def _ctrl(B, mode):
+    from quadruped_ctrl_amd.binding import BatchedController
+    c = BatchedController(0, max_batch=B)
+    c.init(B, 500.0, PID)
+    if mode != "lockstep":
+        c.set_schedule(mode)
+    return c
+
+
+def _apply(c, B, t_abs, vel):
+    import torch
+    c.set_gait(torch.from_numpy(_gaits(B, t_abs, SWITCH_AT)).to(c.device))
+    c.set_vel(torch.from_numpy(vel).to(c.device))
+
+
+def _run(c, B, imu, motor, vel, t0, ticks, resets=None, extra=(), before=None):
+    """Ticks t0 .. t0 + ticks - 1 of the stream (absolute indices) on controller c.  resets: {tick: mask}, applied before
+    that tick.  -> (effort [ticks, B, 12], per-tick dicts of STATE + extra).  before(t): called ahead of tick t."""
+    import torch
+    dev = c.device
+    eff, snaps = [], []
+    for t in range(t0, t0 + ticks):
+        if resets and t in resets:
+            c.reset(torch.from_numpy(resets[t]).to(dev))
+        if t in (t0, SWITCH_AT) or (resets and t in resets):
+            _apply(c, B, t, vel)
+        if before:
+            before(t)
+        e = c.tick(torch.from_numpy(imu[t]).to(dev), torch.from_numpy(motor[t]).to(dev)).cpu().numpy()
+        eff.append(e)
+        snaps.append({k: c.read(k) for k in STATE + tuple(extra)})
+    return np.array(eff), snaps
+
+
+def _same(a_eff, a_snaps, b_eff, b_snaps, rows, what, a_off=0, b_off=0, ticks=None):
+    """Rows `rows` of run a from tick a_off equal those of run b from tick b_off, bit for bit, on `ticks` ticks."""
+    n = ticks if ticks is not None else min(len(a_eff) - a_off, len(b_eff) - b_off)
+    for i in range(n):
+        ea, eb = a_eff[a_off + i][rows], b_eff[b_off + i][rows]
+        assert np.array_equal(ea, eb), (what, i, "effort", np.abs(ea - eb).max())
+        for k in STATE:
+            if k == "counter":
+                continue   # compared by the caller (runs that start at different ticks count differently)
+            xa, xb = a_snaps[a_off + i][k][rows], b_snaps[b_off + i][k][rows]
+            assert np.array_equal(xa, xb), (what, i, k)
+
+
+def test_per_robot_without_resets_equals_lockstep():
+    B, ticks = 257, 40
+    imu, motor = W.make_tick_stream(B, ticks, 51)
+    vel = _vel(B, 52)
+    out = {}
+    for mode in ("lockstep", "per_robot"):
+        c = _ctrl(B, mode)
+        out[mode] = _run(c, B, imu, motor, vel, 0, ticks, extra=("due", "grf", "status"))
+        assert c.view()["ticks"] == ticks
+        c.close()
+    rows = np.ones(B, bool)
+    _same(*out["lockstep"], *out["per_robot"], rows, "per_robot vs lockstep")
+    for mode in out:
+        for t, s in enumerate(out[mode][1]):
+            assert (s["counter"] == t + 1).all(), (mode, t)
+            want = 1 if (t + 1) % 13 == 0 else 0       # the 13th, 26th and 39th tick
+            assert (s["due"] == want).all(), (mode, t)
+    for a, b in zip(out["lockstep"][1], out["per_robot"][1]):
+        assert np.array_equal(a["grf"], b["grf"]) and np.array_equal(a["status"], b["status"])
+    assert np.abs(out["per_robot"][1][-1]["f_ff"]).max() > 1.0
+
+
+def test_exact_reset():
+    """Every third robot reset after 17 ticks (not a multiple of 13): over the next 40 ticks (three solves) it is the robot of
+    a fresh lockstep controller fed stream[17:]; the other robots are those of the run without resets."""
+    B, at, ticks = 257, 17, 40
+    n = at + ticks
+    imu, motor = W.make_tick_stream(B, n, 61)
+    vel = _vel(B, 62)
+    mask = np.arange(B) % 3 == 0
+    c = _ctrl(B, "per_robot")
+    r_eff, r_snaps = _run(c, B, imu, motor, vel, 0, n, resets={at: mask}, extra=("due",))
+    c.close()
+    c = _ctrl(B, "per_robot")
+    p_eff, p_snaps = _run(c, B, imu, motor, vel, 0, n)
+    c.close()
+    c = _ctrl(B, "lockstep")
+    f_eff, f_snaps = _run(c, B, imu, motor, vel, at, ticks)
+    c.close()
+    _same(r_eff, r_snaps, f_eff, f_snaps, mask, "reset robots vs fresh lockstep", a_off=at, ticks=ticks)
+    _same(r_eff, r_snaps, p_eff, p_snaps, ~mask, "other robots vs no reset")
+    for i in range(ticks):
+        s = r_snaps[at + i]
+        assert (s["counter"][mask, 0] == i + 1).all(), i                 # ticks since the reset
+        assert np.array_equal(s["counter"][mask], f_snaps[i]["counter"][mask])
+        assert (s["counter"][~mask, 0] == at + i + 1).all(), i
+        assert np.array_equal(s["counter"][~mask], p_snaps[at + i]["counter"][~mask])
+        assert (s["due"][mask, 0] == (1 if (i + 1) % 13 == 0 else 0)).all(), i    # first due 13 ticks after the reset
+        assert (s["due"][~mask, 0] == (1 if (at + i + 1) % 13 == 0 else 0)).all(), i
+    assert (r_snaps[-1]["safe"] == 1).all()
+
+
+def _loco_wpd(before, after, gait_num):
+    """world_position_desired after the locomotion step of a tick alone (ConvexMPCLocomotion.cpp:137-146, :268-270,
+    :280-283; float32, no fma) from its value before the tick and the tick's estimate / filtered command."""
+    dt = f32(1.0 / 500.0)
+    gn = np.where(gait_num >= 20, gait_num - 20, gait_num)
+    omni = gait_num >= 20
+    first = before["first_run"][:, 0] != 0
+    pos, rB, vd = after["position"], after["r_body"], after["vel_des"]
+    xv, yv = vd[:, 0], vd[:, 1]
+    vw0 = np.where(omni, xv, ((rB[:, 0] * xv) + (rB[:, 3] * yv)) + (rB[:, 6] * f32(0)))
+    vw1 = np.where(omni, yv, ((rB[:, 1] * xv) + (rB[:, 4] * yv)) + (rB[:, 7] * f32(0)))
+    w = before["wpd"].copy()
+    st = ((gn == 4) & (before["current_gait"][:, 0] != 4)) | first
+    w[st] = pos[st, :2]
+    ns = gn != 4
+    w[ns, 0] = w[ns, 0] + dt * vw0[ns]
+    w[ns, 1] = w[ns, 1] + dt * vw1[ns]
+    w[first] = pos[first, :2]
+    return w.astype(f32)
+
+
+def test_stagger():
+    """Group g = b % 13 reset before tick g: from tick 12 on exactly one group solves per tick, nobody else's MPC state
+    moves, and groups 0 and 5 are fresh lockstep controllers started at their reset tick."""
+    B, ticks = 1024, 40
+    n = 13 + ticks
+    imu, motor = W.make_tick_stream(B, n, 71)
+    vel = _vel(B, 72)
+    group = np.arange(B) % 13
+    resets = {g: group == g for g in range(13)}
+    c = _ctrl(B, "per_robot")
+    prev = {}
+    keys = ("f_ff", "grf", "status", "wpd", "xci", "first_run", "current_gait")
+
+    def before(t):
+        prev.clear()
+        prev.update({k: c.read(k) for k in keys})
+
+    eff, snaps = [], []
+    for t in range(n):
+        e, s = _run(c, B, imu, motor, vel, t, 1, resets=resets, before=before,
+                    extra=("due", "grf", "status", "position", "r_body", "gait_num"))
+        eff.append(e[0])
+        s = s[0]
+        snaps.append(s)
+        due = s["due"][:, 0] != 0
+        if t >= 12:
+            g = (t + 1) % 13
+            assert due.sum() == (group == g).sum() and np.array_equal(due, group == g), t
+        else:
+            assert not due.any(), t
+        idle = ~due
+        for k in ("f_ff", "grf", "status", "xci"):
+            assert np.array_equal(s[k][idle], prev[k][idle]), (t, k)
+        assert np.array_equal(s["wpd"][idle], _loco_wpd(prev, s, s["gait_num"][:, 0])[idle]), t
+        assert np.isfinite(e).all(), t
+        assert (s["safe"] == 1).all(), t
+    eff = np.array(eff)
+    assert c.view()["ticks"] == n
+    c.close()
+    for g in (0, 5):
+        f = _ctrl(B, "lockstep")
+        f_eff, f_snaps = _run(f, B, imu, motor, vel, g, ticks)
+        f.close()
+        rows = group == g
+        _same(eff, snaps, f_eff, f_snaps, rows, f"group {g} vs fresh lockstep", a_off=g, ticks=ticks)
+        for i in range(ticks):
+            assert np.array_equal(snaps[g + i]["counter"][rows], f_snaps[i]["counter"][rows]), (g, i)
+    assert np.abs(snaps[-1]["f_ff"]).max() > 1.0
+
+
+def test_graph_of_five_ticks_replayed():
+    """A graph of FIVE per-robot ticks (lockstep needs a multiple of 13) over a staggered fleet, replayed 8 times over
+    refreshed static inputs, equals the eager per-robot run of the same 40 ticks bit for bit."""
+    import torch
+    B, K, R = 300, 5, 8
+    n = 13 + K * R
+    imu, motor = W.make_tick_stream(B, n, 81)
+    vel = _vel(B, 82)
+    eager, cap = _ctrl(B, "per_robot"), _ctrl(B, "per_robot")
+    dev = eager.device
+    group = np.arange(B) % 13
+    # thirteen eager ticks on both: the stagger (group g reset before tick g), first visit, first run, first solves
+    for t in range(13):
+        x, y = torch.from_numpy(imu[t]).to(dev), torch.from_numpy(motor[t]).to(dev)
+        for c in (eager, cap):
+            c.reset(torch.from_numpy(group == t).to(dev))
+            _apply(c, B, 0, vel)
+            c.tick(x, y)
+    torch.cuda.synchronize()
+    bi = torch.zeros((K, B, 10), dtype=torch.float64, device=dev)
+    bm = torch.zeros((K, B, 24), dtype=torch.float64, device=dev)
+    be = torch.zeros((K, B, 12), dtype=torch.float64, device=dev)
+    graph = torch.cuda.CUDAGraph()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        with torch.cuda.graph(graph, stream=s):
+            for k in range(K):
+                cap.tick(bi[k], bm[k], be[k])
+    torch.cuda.current_stream().wait_stream(s)
+    solved = 0
+    for r in range(R):
+        lo = 13 + K * r
+        bi.copy_(torch.from_numpy(imu[lo:lo + K]))
+        bm.copy_(torch.from_numpy(motor[lo:lo + K]))
+        graph.replay()
+        torch.cuda.synchronize()
+        for k in range(K):
+            x, y = torch.from_numpy(imu[lo + k]).to(dev), torch.from_numpy(motor[lo + k]).to(dev)
+            ee = eager.tick(x, y)
+            torch.cuda.synchronize()
+            assert torch.equal(ee, be[k]), (r, k)
+            solved += int(eager.read("due").sum())
+    assert solved == sum(int((group == (t + 1) % 13).sum()) for t in range(13, n))
+    for k in STATE + ("xhat", "grf", "status", "due"):
+        assert np.array_equal(eager.read(k), cap.read(k)), k
+    assert (eager.read("counter")[:, 0] == n - group).all()
+    assert (eager.read("safe") == 1).all()
+    eager.close()
+    cap.close()
+
+
+def test_set_schedule_errors():
+    import ctypes as C
+    import torch
+    from quadruped_ctrl_amd.binding import BatchedController, QmpcError
+    B = 8
+    c = BatchedController(0, max_batch=B)
+    lib, h = c.lib, c.mpc.h
+    assert lib.qmpc_ctrl_set_schedule(h, 1) == 3            # before init: QMPC_ERR_STATE
+    with pytest.raises(QmpcError):
+        c.set_schedule("per_robot")
+    c.init(B, 500.0, PID)
+    assert lib.qmpc_ctrl_set_schedule(h, 2) == 1            # unknown mode: QMPC_ERR_ARG
+    assert lib.qmpc_ctrl_set_schedule(h, -1) == 1
+    with pytest.raises(QmpcError):
+        c.set_schedule("sometimes")
+    assert lib.qmpc_ctrl_set_schedule(h, 1) == 0
+    assert lib.qmpc_ctrl_set_schedule(h, 0) == 0            # (still before the first tick: either way)
+    c.set_schedule("per_robot")
+    x = torch.zeros((B, 10), dtype=torch.float64, device=c.device)
+    x[:, 6] = 1.0                                           # unit quaternion
+    y = torch.zeros((B, 24), dtype=torch.float64, device=c.device)
+    c.tick(x, y)
+    assert lib.qmpc_ctrl_set_schedule(h, 0) == 3            # after the first tick: QMPC_ERR_STATE
+    assert lib.qmpc_ctrl_set_schedule(h, 1) == 3
+    # a reset in per-robot mode: counter 0, whatever T is
+    m = torch.zeros(B, dtype=torch.bool, device=c.device)
+    m[2] = True
+    c.reset(m)
+    cnt = c.read("counter")[:, 0]
+    assert cnt[2] == 0 and (np.delete(cnt, 2) == 1).all() and c.view()["ticks"] == 1
+    # init returns the handle to lockstep: a reset then restarts at T mod 13
+    c.init(B, 500.0, PID)
+    c.reset(m)
+    assert lib.qmpc_ctrl_set_schedule(h, 1) == 3            # after a reset: QMPC_ERR_STATE
+    c.init(B, 500.0, PID)
+    for _ in range(3):
+        c.tick(x, y)
+    c.reset(m)
+    assert c.read("counter")[2, 0] == 3                     # lockstep: T mod 13
+    c.close()
