@@ -8,10 +8,15 @@
  * Every piece of controller state lives on the device (allocated by qmpc_ctrl_init for the handle's max_batch
  * robots); a tick only enqueues kernels on `stream`, so a run of ticks can be captured into a graph.
  *
- * Scope: robot mode 0 only -- the reference's fixed gaits at horizonLength 14 (ConvexMPCLocomotion.cpp:25-41,
- * :149-171).  Robot mode 1 (the `aio` gait, :172-233) changes the horizon per robot (10 .. 32) and so splits a
- * batch across several qmpc_setup horizons; it is not provided, and neither is a single-robot drop-in of the six
- * GaitCtrller.h:63-99 symbols (the reference's walking_simulation.py starts in mode 1).
+ * Scope: both robot modes of ConvexMPCLocomotion::run, one per controller (qmpc_ctrl_set_robot_mode), as the reference's
+ * _robotMode is one per GaitCtrller.  Mode 0 (the default): the fixed gaits at horizonLength 14, picked by gait number
+ * (ConvexMPCLocomotion.cpp:25-41, :149-172).  Mode 1 (what the reference's walking_simulation.py runs): the `aio` gait
+ * (:173-233), re-timed from the filtered velocity command to standing, walking, walk-to-trot or trot with 10 .. 16
+ * segments per robot; a robot's iterationCounter restarts when its segment count changes, so mode 1 needs the per-robot
+ * schedule.  The MPC horizon does NOT vary: `int h = 10` is a local of every tick that only a phase-0 tick changes, a
+ * tick that solves is never a phase-0 tick, so every solve of mode 1 runs at horizonLength 10 on the first ten rows of
+ * the robot's n-row contact table -- one qmpc_setup horizon serves the batch (DESIGN.md section 0 has the derivation).
+ * Not provided: robots of both modes in one batch, and a single-robot drop-in of the six GaitCtrller.h:63-99 symbols.
  *
  * Layouts (one row per robot, DEVICE pointers, the reference's own orders):
  *   imu[B][10]    double: accelerometer x y z, quaternion x y z w, gyro x y z (GaitCtrller.cpp:34-45,
@@ -72,6 +77,17 @@ int qmpc_ctrl_init(qmpc_handle h, int batch, double freq, const double pid[4], v
  * qmpc_ctrl_init); an unknown mode is QMPC_ERR_ARG.  Host state only: nothing is enqueued. */
 enum { QMPC_CTRL_LOCKSTEP = 0, QMPC_CTRL_PER_ROBOT = 1 };
 int qmpc_ctrl_set_schedule(qmpc_handle h, int mode);
+
+/* set_robot_mode (GaitCtrller.h, GaitCtrller::_robotMode) for the whole controller: 0 or 1 (QMPC_ERR_ARG otherwise).
+ * Like the schedule, only between qmpc_ctrl_init and the first qmpc_ctrl_tick or qmpc_ctrl_reset (QMPC_ERR_STATE
+ * afterwards and before qmpc_ctrl_init); qmpc_ctrl_prework calls may come first, as in the reference's protocol
+ * (init_controller, pre_work ..., set_robot_mode(1)).  Mode 1 needs QMPC_CTRL_PER_ROBOT: QMPC_ERR_STATE on a handle in
+ * lockstep (qmpc_last_error says so), and qmpc_ctrl_set_schedule(LOCKSTEP) is refused while mode 1 is selected.
+ * Selecting a mode repeats qmpc_setup with its horizon (1: 10, 0: 14; same dt, 0.4, 120): host work, nothing is enqueued.
+ * qmpc_ctrl_init always returns to mode 0.  In mode 1 the gait number still sets omni mode (>= 20) and the standing
+ * transition test of :137; every other effect of it is overridden (:176-177).  A robot's gait state (segment count,
+ * offsets, durations, phase) is device state and persists across ticks; qmpc_ctrl_reset restores the constructor's. */
+int qmpc_ctrl_set_robot_mode(qmpc_handle h, int mode);
 
 /* Re-initialise the robots whose mask_dev[b] (uint8, device) is non-zero exactly as qmpc_ctrl_init does -- in lockstep
  * except that their iteration counter restarts at T mod 13 (see Lockstep above); with the per-robot schedule without

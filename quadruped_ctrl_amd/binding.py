@@ -20,7 +20,7 @@ ST_NONFINITE = 32
 ST_ERROR_MASK = 15 | 32
 # the int32 arrays among the controller's device state (QMPC_CTRL_ARRAYS in csrc/qmpc_glue.h): what read() returns as int32
 CTRL_INT_ARRAYS = ("counter", "first_run", "first_swing", "first_visit", "gait_num", "current_gait", "offsets", "durations",
-                   "iteration", "safe", "status", "due", "due_list", "due_count")
+                   "iteration", "safe", "status", "due", "due_list", "due_count", "nseg", "mpc_offsets", "mpc_durations")
 CTRL_SCHEDULES = dict(lockstep=0, per_robot=1)   # QMPC_CTRL_LOCKSTEP / QMPC_CTRL_PER_ROBOT (include/qmpc_ctrl.h)
 
 # qmpc_ctrl_view's float arrays (include/qmpc_ctrl.h) in declaration order, elements per robot
@@ -163,6 +163,7 @@ SIGNATURES = {
 CTRL_SIGNATURES = {
     "qmpc_ctrl_init": [_P, _I, _D, C.POINTER(_D), _P],
     "qmpc_ctrl_set_schedule": [_P, _I],
+    "qmpc_ctrl_set_robot_mode": [_P, _I],
     "qmpc_ctrl_reset": [_P, _I, _P, _P],
     "qmpc_ctrl_set_gait": [_P, _I, _P, _P],
     "qmpc_ctrl_set_vel": [_P, _I, _P, _P],
@@ -591,8 +592,8 @@ class BatchedConvexMPC:
 
 
 class BatchedController:
-    """GaitCtrller::TorqueCalculator for `batch` robots on one GPU (include/qmpc_ctrl.h), robot mode 0; the MPC in
-    lockstep by default, per robot after set_schedule("per_robot").
+    """GaitCtrller::TorqueCalculator for `batch` robots on one GPU (include/qmpc_ctrl.h); the MPC in lockstep by
+    default, per robot after set_schedule("per_robot"); robot mode 0 by default, 1 after set_robot_mode(1).
 
     The reference's single-robot calls map one to one: init_controller -> init(), set_gait_type -> set_gait(),
     set_robot_vel -> set_vel(), pre_work -> prework(), torque_calculator -> tick(); reset() re-initialises chosen
@@ -630,6 +631,13 @@ class BatchedController:
         if mode not in CTRL_SCHEDULES:
             raise QmpcError(f"set_schedule: unknown mode {mode!r} (one of {sorted(CTRL_SCHEDULES)})")
         self.mpc._check(self.lib.qmpc_ctrl_set_schedule(self.mpc.h, CTRL_SCHEDULES[mode]), "qmpc_ctrl_set_schedule")
+
+    def set_robot_mode(self, mode):
+        """set_robot_mode for the whole controller: 0 (the default after every init(): the gait picked by number, MPC
+        horizon 14) or 1 (the speed-adaptive `aio` gait, 10 .. 16 segments per robot, MPC horizon 10).  Mode 1 needs
+        set_schedule("per_robot") first.  Only between init() and the first tick() or reset(); prework() may come first."""
+        self.mpc._check(self.lib.qmpc_ctrl_set_robot_mode(self.mpc.h, int(mode)), "qmpc_ctrl_set_robot_mode")
+        self.mpc.horizon = 10 if int(mode) == 1 else 14
 
     def reset(self, mask, stream=None):
         """Re-initialise the robots where mask is set; their iteration counter restarts at T mod 13 in lockstep, at 0

@@ -105,6 +105,7 @@ extern "C" hipError_t qmpc_launch_ctrl_set(const QmpcCtrlDev* S, const int32_t* 
 extern "C" hipError_t qmpc_launch_ctrl_est(const QmpcCtrlDev* S, const float geom[4], const double* imu,
                                            const double* motor, int batch, hipStream_t stream);
 extern "C" hipError_t qmpc_launch_ctrl_loco(const QmpcCtrlDev* S, int batch, int build_list, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_ctrl_loco_aio(const QmpcCtrlDev* S, int batch, hipStream_t stream);
 extern "C" hipError_t qmpc_launch_ctrl_legcmd(const QmpcCtrlDev* S, double* effort, int batch, hipStream_t stream);
 extern "C" hipError_t qmpc_launch_swing(const float* p0, const float* pf, const float* height, const float* phase,
                                         const float* swing_time, float* p, float* v, float* a, int n_feet,
@@ -215,6 +216,7 @@ struct qmpc_ctx {
     int batch = 0;       // robots initialised
     long long ticks = 0; // T: qmpc_ctrl_tick calls since qmpc_ctrl_init
     int schedule = QMPC_CTRL_LOCKSTEP;  // qmpc_ctrl_set_schedule
+    int robot_mode = 0;                 // qmpc_ctrl_set_robot_mode (GaitCtrller::_robotMode)
     bool started = false;               // a tick or a reset has been enqueued since qmpc_ctrl_init: the schedule is fixed
   };
   Ctrl* ctrl = nullptr;
@@ -1482,6 +1484,7 @@ int qmpc_ctrl_init(qmpc_handle c, int batch, double freq, const double pid[4], v
   k->batch = batch;
   k->ticks = 0;
   k->schedule = QMPC_CTRL_LOCKSTEP;
+  k->robot_mode = 0;
   k->started = false;
   return QMPC_OK;
 }
@@ -1506,7 +1509,29 @@ int qmpc_ctrl_set_schedule(qmpc_handle c, int mode) {
   if (!c->ctrl || !c->ctrl->batch) return QMPC_ERR_STATE;
   if (mode != QMPC_CTRL_LOCKSTEP && mode != QMPC_CTRL_PER_ROBOT) return QMPC_ERR_ARG;
   if (c->ctrl->started) return QMPC_ERR_STATE;
+  if (mode == QMPC_CTRL_LOCKSTEP && c->ctrl->robot_mode == 1) {
+    c->err = "robot mode 1 needs the per-robot schedule (select robot mode 0 first)";
+    return QMPC_ERR_STATE;
+  }
   c->ctrl->schedule = mode;
+  return QMPC_OK;
+}
+
+int qmpc_ctrl_set_robot_mode(qmpc_handle c, int mode) {
+  if (!c) return QMPC_ERR_ARG;
+  if (!c->ctrl || !c->ctrl->batch) return QMPC_ERR_STATE;
+  if (mode != 0 && mode != 1) return QMPC_ERR_ARG;
+  qmpc_ctx::Ctrl* k = c->ctrl;
+  if (k->started) return QMPC_ERR_STATE;
+  if (mode == 1 && k->schedule != QMPC_CTRL_PER_ROBOT) {
+    // a robot's counter restarts whenever its gait is re-timed (ConvexMPCLocomotion.cpp:182-224): no common MPC tick
+    c->err = "robot mode 1 needs the per-robot schedule: the handle is in lockstep (qmpc_ctrl_set_schedule first)";
+    return QMPC_ERR_STATE;
+  }
+  // every solve of mode 1 runs at horizonLength 10 (:174, :233), mode 0 at 14: setup_problem(dtMPC,
+  // horizonLength, 0.4, 120) (:629-630).  Host work and a table upload; nothing is enqueued
+  if (const int rc = qmpc_setup(c, (double)k->d.dt_mpc, mode == 1 ? 10 : 14, 0.4, 120.0)) return rc;
+  k->robot_mode = mode;
   return QMPC_OK;
 }
 
@@ -1550,7 +1575,9 @@ int qmpc_ctrl_tick(qmpc_handle c, int batch, const double* imu, const double* mo
   const bool per_robot = k->schedule == QMPC_CTRL_PER_ROBOT;
   k->started = true;
   if (const int rc = ctrl_prework(c, imu, motor, stream)) return rc;
-  HIP_TRY(c, qmpc_launch_ctrl_loco(&d, batch, per_robot ? 1 : 0, stream));
+  const bool aio = k->robot_mode == 1;  // (per_robot holds: qmpc_ctrl_set_robot_mode)
+  if (aio) HIP_TRY(c, qmpc_launch_ctrl_loco_aio(&d, batch, stream));
+  else HIP_TRY(c, qmpc_launch_ctrl_loco(&d, batch, per_robot ? 1 : 0, stream));
   // the locomotion kernel advances every robot's counter: T follows it here, before the launches that can still fail,
   // so that the host's MPC schedule and the device's `counter % 13` test never disagree
   // lockstep: every robot's incremented counter is a multiple of 13 on the same ticks, known from T alone.
@@ -1572,8 +1599,10 @@ int qmpc_ctrl_tick(qmpc_handle c, int batch, const double* imu, const double* mo
     cmd.stand_traj = d.stand_traj;
     cmd.rp_des = nullptr;  // _roll_des = _pitch_des = 0 (:112-113)
     cmd.gait_type = d.current_gait;
-    cmd.gait_offsets = d.offsets;
-    cmd.gait_durations = d.durations;
+    // robot mode 1: the ten rows the horizon-10 solve reads of the robot's own table, as a 10-segment gait (qmpc_glue.hip:
+    // qmpc_ctrl_window_gait); gait_type is 9 for every due robot there
+    cmd.gait_offsets = aio ? d.mpc_offsets : d.offsets;
+    cmd.gait_durations = aio ? d.mpc_durations : d.durations;
     cmd.gait_iteration = d.iteration;
     cmd.world_position_desired = d.wpd;
     cmd.x_comp_integral = d.xci;

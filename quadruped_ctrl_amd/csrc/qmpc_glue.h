@@ -174,7 +174,12 @@ __device__ __forceinline__ void qmpc_swing_axis(int axis, float p0, float pf, fl
   /* the MPC schedule of the tick (qmpc_ctrl_set_schedule) */                                                          \
   X(int, due, 1)                  /* 1: the incremented counter is a multiple of 13 (this tick solves for the robot) */\
   X(int, due_list, 1)             /* per-robot schedule: the due robots of the tick, dense, [0 .. due_count[0]) */      \
-  X(int, due_count, 1)            /* ... their number, in element 0 (the rest of the row-per-robot array is unused) */
+  X(int, due_count, 1)            /* ... their number, in element 0 (the rest of the row-per-robot array is unused) */ \
+  /* robot mode 1 (qmpc_ctrl_set_robot_mode): the `aio` gait's state beside offsets / durations, which persist there */ \
+  X(int, nseg, 1)                 /* OffsetDurationGait::_nIterations of the robot's gait (14 in mode 0) */            \
+  X(float, gait_phase, 1)         /* _phase as the last setIterations left it (0 in a fresh robot: see qmpc_glue.hip) */\
+  X(int, mpc_offsets, 4)          /* the 10 rows the solve reads of the nseg-row table, as a 10-segment gait ... */    \
+  X(int, mpc_durations, 4)        /* ... (qmpc_ctrl_window_gait); written on the robot's due ticks */
 
 struct QmpcCtrlDev {
 #define QMPC_CTRL_MEMBER(T, name, per_robot) T* name;
@@ -205,6 +210,49 @@ __device__ __forceinline__ void qmpc_ctrl_gait(int gn, int* off, int* dur) {
   else if (gn == 11) { d = 10; }                                  // walking2
   off[0] = o0; off[1] = o1; off[2] = o2; off[3] = o3;
   dur[0] = dur[1] = dur[2] = dur[3] = d;
+}
+
+// Robot mode 1: the phase-0 branch of ConvexMPCLocomotion::run (:174-232) -- the `aio` gait re-timed from the filtered
+// command.  xv, yv, yr: _x_vel_des, _y_vel_des, _yaw_turn_rate of this tick.  -> the segment count h; off / dur; the
+// return value is gaitNumber (4 inside the standing case only, 9 otherwise).
+//   vBody (:175) is `sqrt(x*x) + (y*y)`: float products, the DOUBLE sqrt (see the overload decision in qmpc_glue.hip), a
+//   double sum -- not a norm.  abs(_yaw_turn_rate) (:180) is the float overload, compared with the double 0.01.
+//   h / 2, h / 4, 3 * h / 4 are integer divisions; the walk-to-trot case (:209-211) and h = -20.0 * vBody + 42.0 (:221)
+//   are double expressions truncated by the conversion to int (Vec4<int>(double ...)).
+__device__ __forceinline__ int qmpc_ctrl_aio_gait(float xv, float yv, float yr, int& h, int* off, int* dur) {
+#pragma clang fp contract(off)
+  const double vBody = sqrt((double)(xv * xv)) + (double)(yv * yv);
+  int gaitNumber = 9;
+  h = 10;
+  int o1, o2, o3, d;
+  if (vBody < 0.002) {
+    if ((double)fabsf(yr) < 0.01) {  // standing (:181-185)
+      gaitNumber = 4;
+      o1 = 0; o2 = 0; o3 = 0; d = h;
+    } else {                         // turning on the spot: trot (:187-192)
+      h = 10;
+      o1 = h / 2; o2 = h / 2; o3 = 0; d = h / 2;
+    }
+  } else if (vBody <= 0.2) {         // walking (:196-202)
+    h = 16;
+    o1 = 1 * h / 2; o2 = 1 * h / 4; o3 = 3 * h / 4; d = 3 * h / 4;
+  } else if (vBody > 0.2 && vBody <= 0.4) {  // walking to trotting (:204-211)
+    h = 16;
+    o1 = 1 * h / 2;
+    o2 = (int)((double)h * ((5.0 / 4.0) * vBody));
+    o3 = (int)((double)h * ((5.0 / 4.0) * vBody + (1.0 / 2.0)));
+    d = (int)((double)h * ((-5.0 / 4.0) * vBody + 1.0));
+  } else if (vBody > 0.4 && vBody <= 1.4) {  // trotting (:213-218)
+    h = 14;
+    o1 = h / 2; o2 = h / 2; o3 = 0; d = h / 2;
+  } else {                           // fast trot, 13 .. 10 segments (:221-227)
+    h = (int)(-20.0 * vBody + 42.0);
+    if (h < 10) h = 10;
+    o1 = h / 2; o2 = h / 2; o3 = 0; d = h / 2;
+  }
+  off[0] = 0; off[1] = o1; off[2] = o2; off[3] = o3;
+  dur[0] = dur[1] = dur[2] = dur[3] = d;
+  return gaitNumber;
 }
 
 // OffsetDurationGait::getContactState / getSwingState (Gait.cpp:61-123) of one leg at _phase

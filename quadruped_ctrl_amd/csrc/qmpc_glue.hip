@@ -341,7 +341,7 @@ extern "C" hipError_t qmpc_launch_kf_init(float* xhat, float* P, int batch, hipS
 
 // ---------------------------------------------------------------------------------------------------
 // Batched locomotion controller (include/qmpc_ctrl.h): GaitCtrller::TorqueCalculator (src/GaitCtrller.cpp:95-145)
-// for robot mode 0, as five launches per tick:
+// in robot mode 0 or 1 (qmpc_ctrl_set_robot_mode: the locomotion kernel's template argument), as five launches per tick:
 //   qmpc_ctrl_est_kernel     pre_work: VectorNavOrientationEstimator::run (OrientationEstimator.cpp:46-110) and
 //                            LegController::updateData (one thread per (robot, leg); leg 0 also runs the estimator)
 //   qmpc_kf_kernel           the Kalman filter above, on the previous tick's leg data (the estimators run before
@@ -367,6 +367,8 @@ extern "C" hipError_t qmpc_launch_kf_init(float* xhat, float* P, int batch, hipS
 //  * timing: setIterations sees the counter before the increment (:239), the increment comes before
 //    updateMPCIfNeeded (:375, :387): the first solve is at the 13th tick, on table iteration 0.
 //  * swing state: setInitialPosition also sets _p; a stance foot's pDes is the trajectory's last _p / _v.
+//  * robot mode 1 reads OffsetDurationGait::_phase (Gait.h:57) on its first tick before anything wrote it (undefined in
+//    the reference): here it starts at 0, so the first tick takes the phase-0 branch; qmpc_ctrl_reset restores that.
 //  * omni mode per robot: qmpc_command carries ONE omni flag; the command's rBody row is the identity for omni
 //    robots (v_des_world = v_des_robot, :505-507) and f_ff = -rBody grf is formed here with the true rBody
 //    (qmpc_cmd_f2b, the solve's own arithmetic).
@@ -516,8 +518,30 @@ __global__ __launch_bounds__(256) void qmpc_ctrl_est_kernel(const QmpcCtrlDev S,
   if (leg == 0) qmpc_ctrl_orientation(S, b, imu + (size_t)b * 10);
 }
 
+// Robot mode 1, the solve's contact table.  Every solve of mode 1 runs at horizonLength 10 and
+// reads rows i = 0 .. 9 of the robot's n-row table (getMpcTable, Gait.cpp:142-166), n = 10 .. 16.  The command stage
+// of the solve builds its table from (iteration, offset, duration) with n_segments = horizon (qmpc_cmd_gait_bit), so
+// it is handed a 10-segment gait with the SAME ten rows: row i of a leg sits at place p = (i + iteration + 1) % 10 of
+// a cycle of ten; the leg's contact rows are one run of that cycle (ten consecutive rows of a cycle of n >= 10 meet
+// the contact arc in one piece, or in two pieces that touch the two ends of the window, which are neighbours in the
+// cycle of ten), so offset' = the place where the run starts and duration' = its length reproduce every row.
+// tests/test_ctrl_mode1_cpu.py checks the identity for every n, offset, duration and iteration.
+__device__ __forceinline__ void qmpc_ctrl_window_gait(int iteration, int off, int dur, int n, int& off10, int& dur10) {
+  unsigned m = 0;  // bit p: contact at place p
+  for (int i = 0; i < 10; ++i)
+    if (qmpc_cmd_gait_bit(i, iteration, off, dur, n)) m |= 1u << ((i + iteration + 1) % 10);
+  const unsigned prev = ((m << 1) | (m >> 9)) & 0x3ffu;  // bit p: contact at place p - 1
+  const unsigned start = m & ~prev;
+  off10 = start ? __ffs((int)start) - 1 : 0;
+  dur10 = __popc(m);
+}
+
 // The safety checks and ConvexMPCLocomotion::run up to updateMPCIfNeeded, one thread per robot
 // build_list (per-robot schedule): the due robots also append themselves to S.due_list, one atomic per wave
+// MODE: the controller's robot mode (qmpc_ctrl_set_robot_mode).  0: the gait picked by number, 14 segments (:150-172).
+// 1: the `aio` gait (:173-233), whose segment count, offsets and durations are the robot's own rows and change on
+// phase-0 ticks only; everything below the gait selection reads them where mode 0 has the literal 14.
+template <int MODE>
 __global__ __launch_bounds__(256) void qmpc_ctrl_loco_kernel(const QmpcCtrlDev S, const int batch, const int build_list) {
 #pragma clang fp contract(off)
   const int b = blockIdx.x * 256 + threadIdx.x;
@@ -586,13 +610,38 @@ __global__ __launch_bounds__(256) void qmpc_ctrl_loco_kernel(const QmpcCtrlDev S
     wpd[1] = st[1];
   }
   int off[4], dur[4];
-  qmpc_ctrl_gait(gn, off, dur);
-  const bool standing = gn == 4;
-  S.current_gait[b] = gn;
-  const int cnt = S.counter[b];
-  const int nseg = 14, ibm = 13;
+  int cnt = S.counter[b];
+  int nseg = 14;
+  const int ibm = 13;
+  bool standing;
+  if constexpr (MODE == 0) {
+    qmpc_ctrl_gait(gn, off, dur);
+    standing = gn == 4;
+    S.current_gait[b] = gn;
+  } else {
+    // gait = &aio; gaitNumber = 9 (:176-177).  The gait keeps its parameters from tick to tick: setGaitParam is
+    // called only where the phase the PREVIOUS tick's setIterations left is 0 (:178).  A fresh robot's phase is 0
+    // (the reference reads an uninitialised float there: INTEGRATION.md section F), so its first tick selects.
+    nseg = S.nseg[b];
+    for (int l = 0; l < 4; ++l) {
+      off[l] = S.offsets[(size_t)b * 4 + l];
+      dur[l] = S.durations[(size_t)b * 4 + l];
+    }
+    int cg = 9;
+    if (S.gait_phase[b] == 0.f) {
+      int h;
+      cg = qmpc_ctrl_aio_gait(xv, yv, yr, h, off, dur);
+      if (nseg != h) cnt = 0;  // if (gait->getGaitHorizon() != h) iterationCounter = 0
+      nseg = h;
+      S.nseg[b] = h;
+    }
+    // (horizonLength = h (:233) is 10 on every tick that solves: such a tick is never a phase-0 tick)
+    standing = false;          // `gait != &standing` (:277) holds for &aio, its standing case included
+    S.current_gait[b] = cg;    // 4 only on a phase-0 tick of the standing case: never on a tick that solves
+  }
   S.iteration[b] = (cnt / ibm) % nseg;  // setIterations (Gait.cpp:187-193) with the counter before the increment
   const float phase = (float)(cnt % (ibm * nseg)) / (float)(ibm * nseg);
+  if constexpr (MODE == 1) S.gait_phase[b] = phase;
   for (int l = 0; l < 4; ++l) {
     S.offsets[(size_t)b * 4 + l] = off[l];
     S.durations[(size_t)b * 4 + l] = dur[l];
@@ -726,6 +775,17 @@ __global__ __launch_bounds__(256) void qmpc_ctrl_loco_kernel(const QmpcCtrlDev S
   // the MPC schedule: updateMPCIfNeeded solves when the incremented counter is a multiple of 13 (:387)
   const bool due = (cnt + 1) % ibm == 0;
   S.due[b] = due ? 1 : 0;
+  if constexpr (MODE == 1) {
+    if (due) {  // the ten rows of the robot's table that the horizon-10 solve reads, as a 10-segment gait
+      const int it = (cnt / ibm) % nseg;
+      for (int l = 0; l < 4; ++l) {
+        int o10, d10;
+        qmpc_ctrl_window_gait(it, off[l], dur[l], nseg, o10, d10);
+        S.mpc_offsets[(size_t)b * 4 + l] = o10;
+        S.mpc_durations[(size_t)b * 4 + l] = d10;
+      }
+    }
+  }
   if (build_list) {
     // dense list of the due robots (what the solve's first launch consumes): the wave's due lanes take consecutive
     // places behind one atomic add of its first due lane; at most `batch` entries (every robot appends at most once)
@@ -860,6 +920,12 @@ __global__ __launch_bounds__(256) void qmpc_ctrl_init_kernel(const QmpcCtrlDev S
   S.status[b] = 0;
   S.due[b] = 0;
   S.due_list[b] = 0;
+  S.nseg[b] = 14;  // the `aio` gait as its constructor leaves it (ConvexMPCLocomotion.cpp:41); its offsets 0 and
+  S.gait_phase[b] = 0.f;  // durations 14 are replaced by the first tick's selection before anything reads them
+  for (int k = 0; k < 4; ++k) {
+    S.mpc_offsets[(size_t)b * 4 + k] = 0;
+    S.mpc_durations[(size_t)b * 4 + k] = 0;
+  }
   S.due_count[b] = 0;  // (element 0 is the count of a tick, rebuilt by every tick; the rest is never used)
 }
 
@@ -898,7 +964,13 @@ extern "C" hipError_t qmpc_launch_ctrl_est(const QmpcCtrlDev* S, const float geo
 }
 
 extern "C" hipError_t qmpc_launch_ctrl_loco(const QmpcCtrlDev* S, int batch, int build_list, hipStream_t stream) {
-  hipLaunchKernelGGL(qmpc_ctrl_loco_kernel, dim3((batch + 255) / 256), dim3(256), 0, stream, *S, batch, build_list);
+  hipLaunchKernelGGL(qmpc_ctrl_loco_kernel<0>, dim3((batch + 255) / 256), dim3(256), 0, stream, *S, batch, build_list);
+  return hipGetLastError();
+}
+
+// robot mode 1 (always with the per-robot schedule: the list of due robots is built)
+extern "C" hipError_t qmpc_launch_ctrl_loco_aio(const QmpcCtrlDev* S, int batch, hipStream_t stream) {
+  hipLaunchKernelGGL(qmpc_ctrl_loco_kernel<1>, dim3((batch + 255) / 256), dim3(256), 0, stream, *S, batch, 1);
   return hipGetLastError();
 }
 

@@ -11,8 +11,14 @@ batch size and, with --out, writes them as a JSON list.  The kernel split comes 
 phase (all solve on the same ticks, as in lockstep).  --stagger resets group b % 13 before tick b % 13 of thirteen
 untimed ticks in front of the warm-up, so that one thirteenth of the fleet solves on every tick.
 
+--robot-mode 1 selects the speed-adaptive `aio` gait (qmpc_ctrl_set_robot_mode; implies --schedule per_robot): per-robot
+x velocity commands spread evenly over [0, 2] m/s, so that standing, walking, walk-to-trot, trot and the fast trot all
+occur; the robots' counters restart on their own there, which spreads the solves over the ticks without --stagger.  The
+warm-up should then cover the settling of the velocity filter (--warmup 600).  Reports the histogram of the robots'
+segment counts at the end.
+
     python tools/ctrl_bench.py [--batches 1024,4096,16384] [--cycles 8] [--warmup 26] [--schedule lockstep|per_robot]
-                               [--stagger] [--out FILE]
+                               [--stagger] [--robot-mode 0|1] [--out FILE]
 """
 import argparse
 import json
@@ -25,7 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def run(B, cycles, warmup, schedule="lockstep", stagger=False):
+def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0):
     import torch
     from quadruped_ctrl_amd import workloads as W
     from quadruped_ctrl_amd.binding import BatchedController
@@ -33,12 +39,17 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False):
     ctrl.init(B, freq=500.0, pid=(0.0, 0.0, 3.0, 0.3))
     if schedule != "lockstep":
         ctrl.set_schedule(schedule)
+    if robot_mode:
+        ctrl.set_robot_mode(robot_mode)
     g = (np.arange(B) % 12).astype(np.int32)
     g = np.where(np.arange(B) % 24 >= 12, g + 20, g).astype(np.int32)
     g = torch.from_numpy(g).cuda()
     ctrl.set_gait(g)
     rng = np.random.default_rng(B)
     vel = np.stack([rng.uniform(-0.5, 1.2, B), rng.uniform(-0.3, 0.3, B), rng.uniform(-0.5, 0.5, B)], 1)
+    if robot_mode == 1:
+        vel[:, 0] = np.linspace(0.0, 2.0, B)[rng.permutation(B)]
+        vel[::16, 1:] = 0.0      # (x command 0 with no yaw command: the standing case for robot 0's neighbours)
     vel = torch.from_numpy(vel).cuda()
     ctrl.set_vel(vel)
     n = warmup + 13 * cycles
@@ -64,11 +75,15 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False):
     t_non, t_mpc = float(np.median(us[keep & ~mpc])), float(np.median(us[keep & mpc]))
     per_cycle = 12 * t_non + t_mpc
     v = ctrl.view()
-    res = {"batch": B, "schedule": schedule, "stagger": bool(stagger), "ticks_timed": int(keep.sum()),
+    res = {"batch": B, "schedule": schedule, "stagger": bool(stagger), "robot_mode": robot_mode, "ticks_timed": int(keep.sum()),
            "us_per_tick_median": round(float(np.median(us[keep])), 2), "us_per_tick_max": round(float(us[keep].max()), 2),
            "robot_ticks_per_s_window": float(f"{B * int(keep.sum()) / (float(us[keep].sum()) * 1e-6):.4g}")}
-    if stagger:
+    if stagger or robot_mode == 1:
         res["robot_ticks_per_s"] = res["robot_ticks_per_s_window"]
+        if robot_mode == 1:
+            n_, k_ = np.unique(ctrl.read("nseg"), return_counts=True)
+            res["nseg_histogram"] = {str(int(a)): int(b) for a, b in zip(n_, k_)}
+            res["due_last_tick"] = int(ctrl.read("due").sum())
     else:   # every robot solves on the same ticks: the two kinds of tick separately
         res.update({"us_per_nonmpc_tick": round(t_non, 2), "us_per_mpc_tick": round(t_mpc, 2),
                     "us_per_13_tick_cycle": round(per_cycle, 1),
@@ -85,13 +100,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=26)
     ap.add_argument("--schedule", choices=("lockstep", "per_robot"), default="lockstep")
     ap.add_argument("--stagger", action="store_true")
+    ap.add_argument("--robot-mode", type=int, choices=(0, 1), default=0)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.robot_mode == 1:
+        a.schedule = "per_robot"
     if a.stagger and a.schedule != "per_robot":
         ap.error("--stagger needs --schedule per_robot (a lockstep reset keeps the robot on the batch's MPC ticks)")
     out = []
     for B in [int(x) for x in a.batches.split(",")]:
-        r = run(B, a.cycles, a.warmup, a.schedule, a.stagger)
+        r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode)
         print(json.dumps(r), flush=True)
         out.append(r)
     if a.out:
