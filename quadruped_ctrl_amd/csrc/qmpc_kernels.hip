@@ -487,6 +487,19 @@ struct Smem {
 #define QMPC_STEP_TICK(k, dep) do { } while (0)
 #endif
 
+// profiling build (-DQMPC_FIXED_STAMP): shader-clock stamps of EVERY wave of the (four-wave) workgroup in front of the sweep, taken by
+// the wave's lane 0 and stored in row rid + batch of the clock buffer (which the tool allocates twice as long), slot 4 * wave + k:
+// k = 0 this wave's loads of stage 0 have landed, 1 / 2 it arrives at barrier 1 / 2, 3 its part of H is assembled
+// (tools/fixed_part_phases.py: which wave the others wait for, stage by stage)
+#ifdef QMPC_FIXED_STAMP
+#define QMPC_WAVE_TICK(k)                                                                                   \
+  do {                                                                                                      \
+    if (PK.dbg_clk && lane == 0 && tid < 256) PK.dbg_clk[(size_t)(rid + PK.batch) * 16 + (tid >> 6) * 4 + (k)] = clock64(); \
+  } while (0)
+#else
+#define QMPC_WAVE_TICK(k) do { } while (0)
+#endif
+
 // census builds (-DQMPC_STOP_AFTER=<k>, tools/census.sh; never in production): the workgroup leaves solve_one right after stage k
 // (-1: at entry), after a dump that keeps everything the stage produced alive -- every byte of the workgroup's LDS and the given
 // registers are summed into the robot's grf row -- so that the per-stage instruction counts are differences of PMC counters
@@ -631,7 +644,11 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     }
   }
   float g_r0 = 0.f, g_r1 = 0.f, g_r2 = 0.f;
-  if (tid < 72) {  // r_feet(axis, foot) = r[axis*4 + foot], RobotState.cpp:25-27
+  // (wave 1 evaluates the scheduling keys of a one-round launch below and is the wave every other one waits for at barrier 1
+  //  -- tools/fixed_part_phases.py: 2.2 k cycles at four workgroups per CU --, so nothing else of this stage is left on it: the
+  //  36 threads of wave 0 that form M_b go on to N_b, the same m0, m1, m2, instead of threads 36..71 forming them again; the
+  //  weights and the tables are the last waves')
+  if (tid < 36) {  // r_feet(axis, foot) = r[axis*4 + foot], RobotState.cpp:25-27
     if (cmdm) {
       const float* pf = PK.c_p_foot + (size_t)rid * 12 + 3 * mb;
       g_r0 = qmpc_cmd_foot_offset(pf[0], c_p0);
@@ -668,8 +685,8 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     }
   }
   float g_w12 = 0.f;
-  if (tid >= 96 && tid < 96 + 12)
-    g_w12 = cmdm ? qmpc_cmd_weight(tid - 96) : PK.weights[(size_t)rid * PK.weights_stride + (tid - 96)];
+  const int w12 = tid - (NT - 12);  // (the last twelve threads)
+  if (w12 >= 0) g_w12 = cmdm ? qmpc_cmd_weight(w12) : PK.weights[(size_t)rid * PK.weights_stride + w12];
   // (loaded here with everything else: a global load issued after barrier 1 would be waited
   //  for by barrier 2)
   float g_alpha = cmdm ? 4e-5f : PK.alpha[(size_t)rid * PK.alpha_stride];  // ConvexMPCLocomotion.cpp:604
@@ -687,14 +704,15 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       g2_ct8 = PK.ctab[8 * hh + tid + NT];
     }
   }
-  if (tid < hh) {
+  const int tix = NT - 1 - tid;  // (the first entry of the tables: taken from the LAST thread down)
+  if (tix < hh) {
     // the x_drag tables are fetched unconditionally: making them wait for the x_drag
     // value would put a second memory round trip in front of them
-    g_ct0 = PK.ctab[tid];
-    g_ct4 = PK.ctab[4 * hh + tid];
-    g_ct1 = PK.ctab[1 * hh + tid];
-    g_ct5 = PK.ctab[5 * hh + tid];
-    g_ct8 = PK.ctab[8 * hh + tid];
+    g_ct0 = PK.ctab[tix];
+    g_ct4 = PK.ctab[4 * hh + tix];
+    g_ct1 = PK.ctab[1 * hh + tix];
+    g_ct5 = PK.ctab[5 * hh + tix];
+    g_ct8 = PK.ctab[8 * hh + tix];
   }
   // ONE-ROUND launch without a usable hint (prio_cu != nullptr): the workgroups that share a CU compete for its issue
   // slots, and the CU is done when the LAST of them is -- the one that iterates longest.  Which one that will be is guessed from
@@ -719,6 +737,8 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
           prio_mine = ((unsigned long long)PK.prio_tag << 32) | ((unsigned long long)(63 - pb) << 24) | (unsigned)(rid & 0xffffff);
           __hip_atomic_fetch_max(prio_word, prio_mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
+        // (what was posted, for the thread that reads the word back at the end of stage 1: its low half, < 2^30; -1 = nothing)
+        S.prio_rank = (prio_mine != 0ull) ? (int)(unsigned)(prio_mine & 0xffffffffull) : -1;
       }
     }
   }
@@ -744,6 +764,13 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     asm volatile("" ::"v"(sink));
     dbg_clk[11] = clock64();
   }
+#ifdef QMPC_FIXED_STAMP
+  {
+    float sink = g_yaw + g_traj + (float)g_gait + (float)g_ct0 + g_q[0] + g_r0 + g_w12;
+    asm volatile("" ::"v"(sink));
+    QMPC_WAVE_TICK(0);
+  }
+#endif
   // ---- stance list (wave 0; group after group when the horizon has more than 64 foot-steps)
   if (tid < WAVE) {
     int base = 0;
@@ -773,14 +800,15 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
   const double inv_m = PK.inv_mass;
   {
     // yaw rotation (RobotState.cpp:30-35); float transcendentals like the reference
-    float syf, cyf;
-    sincosf(g_yaw, &syf, &cyf);
+    // (evaluated by the waves that use it -- wave 0 for M_b / N_b, the error rows' for the rates: wave-uniform)
+    float syf = 0.f, cyf = 1.f;
+    if (__ballot(tid < 36 || e_thr) != 0ull) sincosf(g_yaw, &syf, &cyf);
     const double cy = cyf, sy = syf;
     if (PK.dbg_aux && tid == 0) {  // test hook: the float transcendentals as evaluated here
       PK.dbg_aux[(size_t)rid * 8 + 0] = cy;
       PK.dbg_aux[(size_t)rid * 8 + 1] = sy;
     }
-    if (tid < 72) {
+    if (tid < 36) {
       // M_b = I_w^-1 [r_b]x with I_w^-1 = R diag(1/I) R^T (closed form of
       // I_world.inverse(), SolverMPC.cpp:319,:247), N_b = R^T M_b.
       const int b = mb, l = ml, ax = max_;
@@ -800,15 +828,11 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       const double m0 = I00 * cm0 + I01 * cm1;  // M_b[0][ax]
       const double m1 = I01 * cm0 + I11 * cm1;  // M_b[1][ax]
       const double m2 = iz * cm2;               // M_b[2][ax]
-      if (tid < 36) {
-        Aa.Mb[b][3 * l + ax] = (l == 0) ? m0 : (l == 1 ? m1 : m2);
-      } else {
-        // R^T = [[c, s, 0], [-s, c, 0], [0, 0, 1]]   (A(0:3,6:9), SolverMPC.cpp:244)
-        Aa.Nb[b][3 * l + ax] = (l == 0) ? (cy * m0 + sy * m1) : (l == 1 ? (-sy * m0 + cy * m1) : m2);
-      }
-    } else if (tid >= 96 && tid < 96 + 12) {
-      Aa.W[tid - 96] = (double)g_w12;
+      Aa.Mb[b][3 * l + ax] = (l == 0) ? m0 : (l == 1 ? m1 : m2);
+      // R^T = [[c, s, 0], [-s, c, 0], [0, 0, 1]]   (A(0:3,6:9), SolverMPC.cpp:244)
+      Aa.Nb[b][3 * l + ax] = (l == 0) ? (cy * m0 + sy * m1) : (l == 1 ? (-sy * m0 + cy * m1) : m2);
     }
+    if (w12 >= 0) Aa.W[w12] = (double)g_w12;
     // weighted tracking error of the free response at step k (k < h):
     //   e_k = W .* (x0 + A x0 t + A^2 x0 t^2/2 - xd_k),  t = (k+1) dt
     // ( = S (A_qp x0 - X_d), SolverMPC.cpp:399 ), closed form per state row.
@@ -853,13 +877,13 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       }
       Aa.e[eidx0] = (double)g_wt * (val - (double)g_traj);
     }
-    if (tid < hh) {
-      Aa.ct0[tid] = g_ct0;
-      Aa.ct4[tid] = g_ct4;
+    if (tix < hh) {
+      Aa.ct0[tix] = g_ct0;
+      Aa.ct4[tix] = g_ct4;
       if (drag) {
-        Aa.ct1[tid] = g_ct1;
-        Aa.ct5[tid] = g_ct5;
-        Aa.ct8[tid] = g_ct8;
+        Aa.ct1[tix] = g_ct1;
+        Aa.ct5[tix] = g_ct5;
+        Aa.ct8[tix] = g_ct8;
       }
     }
     if constexpr (TAB2) {
@@ -875,16 +899,13 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     }
   }
   if (dbg_clk && tid == 0) dbg_clk[12] = clock64();
+  QMPC_WAVE_TICK(1);
   __syncthreads();  // ---- barrier 1
   QMPC_TICK(1);
   // ... and a stage later reads the word back: the robot whose entry stands is the CU's hardest and keeps the top priority through
   // its sweep (S.prio_rank = 0), the others yield as they advance, as ever.  The barriers of stage 1 publish it
-  if constexpr (PRIO && !CMD && !ADMM && !BIG && !PHA) {
-    if (PK.prio_cu && tid == 127) {  // 0: this robot's entry stands; 1: another robot's of this call; 2: nobody on this CU posted
-      const unsigned long long pv = __hip_atomic_load(prio_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      S.prio_rank = (prio_mine != 0ull && pv == prio_mine) ? 0 : ((unsigned)(pv >> 32) == PK.prio_tag ? 1 : 2);
-    }
-  }
+  // -- at the END of stage 1, by the last wave: a workgroup that reads right behind barrier 1 reads before the neighbours that
+  // started after it have posted, the sooner it gets here the more often (profiles/fixed_part_variants.md).
   {
     const double keep0[2] = {(double)g_alpha, x_drag};
     (void)keep0;
@@ -1041,6 +1062,19 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       }
     }
   }
+  if constexpr (PRIO && !CMD && !ADMM && !BIG && !PHA) {
+    if (P.prio_cu && tid == NT - 1) {  // 0: this robot's entry stands; 1: another robot's of this call; 2: nobody on this CU posted
+      unsigned hwid, xcc;  // (the same CU as the wave that posted: the same word)
+      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+      const unsigned long long* wd = P.prio_cu + (((xcc & 7u) << 8) | ((hwid >> 8) & 0xffu));
+      const int mine32 = S.prio_rank;
+      const unsigned long long pv = __hip_atomic_load(wd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const bool call = (unsigned)(pv >> 32) == P.prio_tag;
+      S.prio_rank = (call && mine32 >= 0 && (unsigned)pv == (unsigned)mine32) ? 0 : (call ? 1 : 2);
+    }
+  }
+  QMPC_WAVE_TICK(2);
   __syncthreads();  // ---- barrier 2
   QMPC_TICK(2);
   // (the robots of a staged CU that are not its hardest step back one level from the assembly on, like the hint's robots after
@@ -1625,6 +1659,10 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     if (tid < NP) P.dbg_g[(size_t)rid * QMPC_DBG_LD + tid] = Sw.g[tid];
   }
   QMPC_TICK(3);
+#ifdef QMPC_FIXED_STAMP
+  asm volatile("" ::"v"(a[0]), "v"(a[CW - 1]));
+  QMPC_WAVE_TICK(3);
+#endif
   QMPC_STOP(2, a);
 
   // ------------------------------------------------------------ stage 3
