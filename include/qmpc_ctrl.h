@@ -22,6 +22,10 @@
  *   imu[B][10]    double: accelerometer x y z, quaternion x y z w, gyro x y z (GaitCtrller.cpp:34-45,
  *                 OrientationEstimator.cpp:49-58)
  *   motor[B][24]  double: q[3*leg + joint], then qd[3*leg + joint] (GaitCtrller.cpp:47-56)
+ *   state[B][16]  double: the simulator's ground truth in the member order of CheaterState<double>
+ *                 (src/Utilities/IMUTypes.h:25-32): columns 0..3 orientation w x y z, 4..6 position, 7..9 omegaBody,
+ *                 10..12 vBody, 13..15 acceleration (body frame).  Every value is rounded to float once
+ *                 (.template cast<float>()); the quaternion is used as given, not normalised
  *   effort[B][12] double: tau[3*leg + joint]; zeros for a robot whose safety flag has latched (:130-144)
  *   vel[B][3]     double: x, y, yaw-rate command (SetRobotVel, :75-93: |v| < 0.03 reads 0)
  *   gait[B]       int32: gait number 0 .. 11 (:149-171; 1 bounding, 2 pronking, 4 standing, 5 trot running,
@@ -47,6 +51,18 @@
  * reported, but nothing depends on it: a captured graph may hold any number of ticks, and replays continue every
  * robot's schedule (the counters are device state).  To spread the solves of a fleet over the ticks, initialise,
  * select this mode, and reset group g on tick g (g = 0 .. 12): every robot stays in a state the reference can reach.
+ *
+ * Estimator source (qmpc_ctrl_prework_state / qmpc_ctrl_tick_state): a second way into the tick for simulated robots, whose
+ * body state is known.  In place of the VectorNav orientation estimator and the Kalman filter it runs the reference's
+ * CheaterOrientationEstimator::run (OrientationEstimator.cpp:21-39) and CheaterPositionVelocityEstimator::run
+ * (PositionVelocityEstimator.cpp:229-238) on state[B][16]: orientation = the quaternion, rBody from it, omegaWorld =
+ * rBody^T omegaBody, rpy, aWorld = rBody^T acceleration, position, vWorld = rBody^T vBody, vBody -- no yaw re-basing (the
+ * cheater estimator has none) and no filter launch.  Everything after the estimators is the same tick: T and the
+ * counters advance as with qmpc_ctrl_tick, and both schedules, both robot modes, qmpc_ctrl_reset, graph capture and
+ * qmpc_ctrl_view_get work as described here.  The source is NOT a handle mode: a caller may alternate the two ticks.  A
+ * state tick leaves the filter (xhat, P, the previous tick's leg data it reads) and the orientation estimator's
+ * first-visit state (_b_first_visit, _ori_ini_inv) exactly where they were; the next IMU tick continues from them.  Only a
+ * run of ticks of ONE kind is a state the reference can reach (it is built with one estimator set).
  *
  * Errors: a tick that returns QMPC_ERR_DEVICE may have advanced some of the controller state (T and the counters
  * advance together once the locomotion kernel is enqueued, so the MPC schedule stays consistent); re-initialise the
@@ -107,6 +123,12 @@ int qmpc_ctrl_prework(qmpc_handle h, int batch, const double* imu, const double*
  * (the MPC when the incremented counter is a multiple of 13: for the whole batch in lockstep, for the due robots with
  * the per-robot schedule) and the leg commands -> effort[B][12]. */
 int qmpc_ctrl_tick(qmpc_handle h, int batch, const double* imu, const double* motor, double* effort, void* stream);
+
+/* pre_work with the cheater estimators (see Estimator source above): state[B][16] in place of imu, no Kalman filter. */
+int qmpc_ctrl_prework_state(qmpc_handle h, int batch, const double* state, const double* motor, void* stream);
+
+/* qmpc_ctrl_tick with qmpc_ctrl_prework_state as its pre_work; the same checks, ordering, schedule and outputs. */
+int qmpc_ctrl_tick_state(qmpc_handle h, int batch, const double* state, const double* motor, double* effort, void* stream);
 
 /* Read-only device views of the controller state (valid until the handle is destroyed or re-initialised). */
 typedef struct {

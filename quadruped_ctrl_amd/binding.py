@@ -169,6 +169,8 @@ CTRL_SIGNATURES = {
     "qmpc_ctrl_set_vel": [_P, _I, _P, _P],
     "qmpc_ctrl_prework": [_P, _I, _P, _P, _P],
     "qmpc_ctrl_tick": [_P, _I, _P, _P, _P, _P],
+    "qmpc_ctrl_prework_state": [_P, _I, _P, _P, _P],
+    "qmpc_ctrl_tick_state": [_P, _I, _P, _P, _P, _P],
     "qmpc_ctrl_view_get": [_P, C.POINTER(CtrlView)],
 }
 EXPORTS = list(SIGNATURES)
@@ -597,8 +599,9 @@ class BatchedController:
 
     The reference's single-robot calls map one to one: init_controller -> init(), set_gait_type -> set_gait(),
     set_robot_vel -> set_vel(), pre_work -> prework(), torque_calculator -> tick(); reset() re-initialises chosen
-    robots (RL episode ends).  Arguments are torch tensors on the controller's device: imu [B,10] and motor [B,24]
-    float64 in the reference's layouts, gait [B] int32, vel [B,3] float64, mask [B] bool / uint8.  Every call only
+    robots (RL episode ends); prework_state() / tick_state() take a simulator's ground truth (state [B,16] float64,
+    CheaterState's member order) in place of imu and skip the filter.  Arguments are torch tensors on the controller's
+    device: imu [B,10] and motor [B,24] float64 in the reference's layouts, gait [B] int32, vel [B,3] float64, mask [B] bool / uint8.  Every call only
     enqueues work on the current stream (or `stream`); view() and read() synchronise.  Owns its BatchedConvexMPC
     (`self.mpc`), whose handle holds the controller state."""
 
@@ -673,6 +676,29 @@ class BatchedController:
             effort = self.torch.empty((self.batch, 12), dtype=self.torch.float64, device=self.device)
         e = self._chk(effort, (self.batch, 12), self.torch.float64, "effort")
         self.mpc._check(self.lib.qmpc_ctrl_tick(self.mpc.h, self.batch, a, b, e, self._s(stream)), "qmpc_ctrl_tick")
+        return effort
+
+    def prework_state(self, state, motor, stream=None):
+        """pre_work from simulator ground truth: state [B,16] float64 in CheaterState's member order (orientation w x y z,
+        position, omegaBody, vBody, acceleration) through the cheater estimators -- no Kalman filter -- and the leg data."""
+        a = self._chk(state, (self.batch, 16), self.torch.float64, "state")
+        b = self._chk(motor, (self.batch, 24), self.torch.float64, "motor")
+        self.mpc._check(self.lib.qmpc_ctrl_prework_state(self.mpc.h, self.batch, a, b, self._s(stream)),
+                        "qmpc_ctrl_prework_state")
+
+    def tick_state(self, state, motor, effort=None, stream=None):
+        """tick() with prework_state() as its pre_work: the same control tick, driven by the true body state.  The filter
+        and the orientation estimator's first-visit state stay where they were; ticks of the two kinds may alternate, but
+        only a run of one kind is a state the reference can reach."""
+        if self.batch is None:
+            raise QmpcError("qmpc_ctrl_tick_state before init()")
+        a = self._chk(state, (self.batch, 16), self.torch.float64, "state")
+        b = self._chk(motor, (self.batch, 24), self.torch.float64, "motor")
+        if effort is None:
+            effort = self.torch.empty((self.batch, 12), dtype=self.torch.float64, device=self.device)
+        e = self._chk(effort, (self.batch, 12), self.torch.float64, "effort")
+        self.mpc._check(self.lib.qmpc_ctrl_tick_state(self.mpc.h, self.batch, a, b, e, self._s(stream)),
+                        "qmpc_ctrl_tick_state")
         return effort
 
     def read(self, name):

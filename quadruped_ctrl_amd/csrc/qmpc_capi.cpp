@@ -104,6 +104,8 @@ extern "C" hipError_t qmpc_launch_ctrl_set(const QmpcCtrlDev* S, const int32_t* 
                                            hipStream_t stream);
 extern "C" hipError_t qmpc_launch_ctrl_est(const QmpcCtrlDev* S, const float geom[4], const double* imu,
                                            const double* motor, int batch, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_ctrl_est_state(const QmpcCtrlDev* S, const float geom[4], const double* state,
+                                                 const double* motor, int batch, hipStream_t stream);
 extern "C" hipError_t qmpc_launch_ctrl_loco(const QmpcCtrlDev* S, int batch, int build_list, hipStream_t stream);
 extern "C" hipError_t qmpc_launch_ctrl_loco_aio(const QmpcCtrlDev* S, int batch, hipStream_t stream);
 extern "C" hipError_t qmpc_launch_ctrl_legcmd(const QmpcCtrlDev* S, double* effort, int batch, hipStream_t stream);
@@ -1455,6 +1457,60 @@ int ctrl_prework(qmpc_ctx* c, const double* imu, const double* motor, hipStream_
   return QMPC_OK;
 }
 
+// pre_work of a tick driven by simulator ground truth: the cheater estimators + leg data in one launch, no filter
+int ctrl_prework_state(qmpc_ctx* c, const double* state, const double* motor, hipStream_t stream) {
+  HIP_TRY(c, qmpc_launch_ctrl_est_state(&c->ctrl->d, c->leg_geom, state, motor, c->ctrl->batch, stream));
+  return QMPC_OK;
+}
+
+// A tick after its pre_work, whichever estimators that ran: the locomotion kernel, the solve by the handle's schedule, the
+// leg commands.  The caller holds the DeviceGuard and has ordered the stream.
+int ctrl_after_prework(qmpc_ctx* c, int batch, double* effort, hipStream_t stream) {
+  qmpc_ctx::Ctrl* k = c->ctrl;
+  const QmpcCtrlDev& d = k->d;
+  const bool per_robot = k->schedule == QMPC_CTRL_PER_ROBOT;
+  const bool aio = k->robot_mode == 1;  // (per_robot holds: qmpc_ctrl_set_robot_mode)
+  if (aio) HIP_TRY(c, qmpc_launch_ctrl_loco_aio(&d, batch, stream));
+  else HIP_TRY(c, qmpc_launch_ctrl_loco(&d, batch, per_robot ? 1 : 0, stream));
+  // the locomotion kernel advances every robot's counter: T follows it here, before the launches that can still fail,
+  // so that the host's MPC schedule and the device's `counter % 13` test never disagree
+  // lockstep: every robot's incremented counter is a multiple of 13 on the same ticks, known from T alone.
+  // per-robot schedule: nothing depends on T -- every tick enqueues the solve over the list of due robots the locomotion
+  // kernel has just built (d.due_list, d.due_count[0]); a tick on which nobody is due costs launches that find no entry
+  const bool mpc_tick = (++k->ticks % 13 == 0) || per_robot;
+  if (mpc_tick) {
+    qmpc_command cmd{};
+    cmd.position = d.position;
+    cmd.v_world = d.v_world;
+    cmd.omega_world = d.omega_world;
+    cmd.orientation = d.orientation;
+    cmd.rpy = d.rpy;
+    cmd.r_body = d.r_cmd;
+    cmd.p_foot = d.p_foot;
+    cmd.vel_des = d.vel_des;
+    cmd.yaw_des_true = d.yaw_des_true;
+    cmd.rpy_comp = d.rpy_comp;
+    cmd.stand_traj = d.stand_traj;
+    cmd.rp_des = nullptr;  // _roll_des = _pitch_des = 0 (:112-113)
+    cmd.gait_type = d.current_gait;
+    // robot mode 1: the ten rows the horizon-10 solve reads of the robot's own table, as a 10-segment gait (qmpc_glue.hip:
+    // qmpc_ctrl_window_gait); gait_type is 9 for every due robot there
+    cmd.gait_offsets = aio ? d.mpc_offsets : d.offsets;
+    cmd.gait_durations = aio ? d.mpc_durations : d.durations;
+    cmd.gait_iteration = d.iteration;
+    cmd.world_position_desired = d.wpd;
+    cmd.x_comp_integral = d.xci;
+    cmd.body_height = 0.25f;  // _SetupCommand (:79)
+    cmd.omni_mode = 0;        // per robot through r_cmd
+    qmpc_outputs out{d.grf, nullptr, d.status, nullptr};
+    if (const int rc = solve_impl(c, batch, nullptr, &cmd, &out, nullptr, stream, per_robot ? d.due_list : nullptr,
+                                  per_robot ? d.due_count : nullptr))
+      return rc;
+  }
+  HIP_TRY(c, qmpc_launch_ctrl_legcmd(&d, effort, batch, stream));
+  return QMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1570,51 +1626,30 @@ int qmpc_ctrl_tick(qmpc_handle c, int batch, const double* imu, const double* mo
   DeviceGuard g(c->device);
   hipStream_t stream = (hipStream_t)stream_;
   if (const int rc = order_after_previous(c, stream)) return rc;
-  qmpc_ctx::Ctrl* k = c->ctrl;
-  const QmpcCtrlDev& d = k->d;
-  const bool per_robot = k->schedule == QMPC_CTRL_PER_ROBOT;
-  k->started = true;
+  c->ctrl->started = true;
   if (const int rc = ctrl_prework(c, imu, motor, stream)) return rc;
-  const bool aio = k->robot_mode == 1;  // (per_robot holds: qmpc_ctrl_set_robot_mode)
-  if (aio) HIP_TRY(c, qmpc_launch_ctrl_loco_aio(&d, batch, stream));
-  else HIP_TRY(c, qmpc_launch_ctrl_loco(&d, batch, per_robot ? 1 : 0, stream));
-  // the locomotion kernel advances every robot's counter: T follows it here, before the launches that can still fail,
-  // so that the host's MPC schedule and the device's `counter % 13` test never disagree
-  // lockstep: every robot's incremented counter is a multiple of 13 on the same ticks, known from T alone.
-  // per-robot schedule: nothing depends on T -- every tick enqueues the solve over the list of due robots the locomotion
-  // kernel has just built (d.due_list, d.due_count[0]); a tick on which nobody is due costs launches that find no entry
-  const bool mpc_tick = (++k->ticks % 13 == 0) || per_robot;
-  if (mpc_tick) {
-    qmpc_command cmd{};
-    cmd.position = d.position;
-    cmd.v_world = d.v_world;
-    cmd.omega_world = d.omega_world;
-    cmd.orientation = d.orientation;
-    cmd.rpy = d.rpy;
-    cmd.r_body = d.r_cmd;
-    cmd.p_foot = d.p_foot;
-    cmd.vel_des = d.vel_des;
-    cmd.yaw_des_true = d.yaw_des_true;
-    cmd.rpy_comp = d.rpy_comp;
-    cmd.stand_traj = d.stand_traj;
-    cmd.rp_des = nullptr;  // _roll_des = _pitch_des = 0 (:112-113)
-    cmd.gait_type = d.current_gait;
-    // robot mode 1: the ten rows the horizon-10 solve reads of the robot's own table, as a 10-segment gait (qmpc_glue.hip:
-    // qmpc_ctrl_window_gait); gait_type is 9 for every due robot there
-    cmd.gait_offsets = aio ? d.mpc_offsets : d.offsets;
-    cmd.gait_durations = aio ? d.mpc_durations : d.durations;
-    cmd.gait_iteration = d.iteration;
-    cmd.world_position_desired = d.wpd;
-    cmd.x_comp_integral = d.xci;
-    cmd.body_height = 0.25f;  // _SetupCommand (:79)
-    cmd.omni_mode = 0;        // per robot through r_cmd
-    qmpc_outputs out{d.grf, nullptr, d.status, nullptr};
-    if (const int rc = solve_impl(c, batch, nullptr, &cmd, &out, nullptr, stream, per_robot ? d.due_list : nullptr,
-                                  per_robot ? d.due_count : nullptr))
-      return rc;
-  }
-  HIP_TRY(c, qmpc_launch_ctrl_legcmd(&d, effort, batch, stream));
-  return QMPC_OK;
+  return ctrl_after_prework(c, batch, effort, stream);
+}
+
+int qmpc_ctrl_prework_state(qmpc_handle c, int batch, const double* state, const double* motor, void* stream_) {
+  if (const int rc = ctrl_check(c, batch)) return rc;
+  if (!state || !motor) return QMPC_ERR_ARG;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  return ctrl_prework_state(c, state, motor, stream);
+}
+
+int qmpc_ctrl_tick_state(qmpc_handle c, int batch, const double* state, const double* motor, double* effort,
+                         void* stream_) {
+  if (const int rc = ctrl_check(c, batch)) return rc;
+  if (!state || !motor || !effort) return QMPC_ERR_ARG;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  c->ctrl->started = true;
+  if (const int rc = ctrl_prework_state(c, state, motor, stream)) return rc;
+  return ctrl_after_prework(c, batch, effort, stream);
 }
 
 int qmpc_debug_ctrl_read(qmpc_handle c, const char* name, void* dst, long long cap_bytes, int* per_robot) {

@@ -344,6 +344,8 @@ extern "C" hipError_t qmpc_launch_kf_init(float* xhat, float* P, int batch, hipS
 // in robot mode 0 or 1 (qmpc_ctrl_set_robot_mode: the locomotion kernel's template argument), as five launches per tick:
 //   qmpc_ctrl_est_kernel     pre_work: VectorNavOrientationEstimator::run (OrientationEstimator.cpp:46-110) and
 //                            LegController::updateData (one thread per (robot, leg); leg 0 also runs the estimator)
+//   (qmpc_ctrl_est_state_kernel  in its place AND the filter's on a tick driven by simulator ground truth,
+//                            qmpc_ctrl_tick_state: the reference's two Cheater estimators and the same updateData)
 //   qmpc_kf_kernel           the Kalman filter above, on the previous tick's leg data (the estimators run before
 //                            updateData, GaitCtrller.cpp:58-63) and the contact phase of the previous tick
 //   qmpc_ctrl_loco_kernel    the safety checks and ConvexMPCLocomotion::run up to the MPC (one thread per robot):
@@ -438,6 +440,22 @@ __device__ __forceinline__ void qmpc_yaw_inverse_quat(float yaw, float* q) {
 #undef QR
 }
 
+// ori::quaternionToRotationMatrix (orientation_tools.h:170-189) BEFORE its final transpose: R with rBody = R^T, so that
+// row k of R is column k of rBody (rBody^T * v is a row of R times v).  q is used as given, not normalised.
+__device__ __forceinline__ void qmpc_quat_to_rot(const float* q, float* R) {
+#pragma clang fp contract(off)
+  const float e0 = q[0], e1 = q[1], e2 = q[2], e3 = q[3];
+  R[0] = 1 - 2 * (e2 * e2 + e3 * e3);
+  R[1] = 2 * (e1 * e2 - e0 * e3);
+  R[2] = 2 * (e1 * e3 + e0 * e2);
+  R[3] = 2 * (e1 * e2 + e0 * e3);
+  R[4] = 1 - 2 * (e1 * e1 + e3 * e3);
+  R[5] = 2 * (e2 * e3 - e0 * e1);
+  R[6] = 2 * (e1 * e3 - e0 * e2);
+  R[7] = 2 * (e2 * e3 + e0 * e1);
+  R[8] = 1 - 2 * (e1 * e1 + e2 * e2);
+}
+
 // VectorNavOrientationEstimator::run for robot b
 __device__ __forceinline__ void qmpc_ctrl_orientation(const QmpcCtrlDev& S, int b, const double* u) {
 #pragma clang fp contract(off)
@@ -460,18 +478,8 @@ __device__ __forceinline__ void qmpc_ctrl_orientation(const QmpcCtrlDev& S, int 
   q[3] = (r1 * b2 + r2 * a2) + (a0 * b1 - a1 * b0);
   float rpy[3];
   qmpc_quat_to_rpy(q, rpy);
-  // quaternionToRotationMatrix (:170-189): R, then transposed
-  const float e0 = q[0], e1 = q[1], e2 = q[2], e3 = q[3];
   float R[9];
-  R[0] = 1 - 2 * (e2 * e2 + e3 * e3);
-  R[1] = 2 * (e1 * e2 - e0 * e3);
-  R[2] = 2 * (e1 * e3 + e0 * e2);
-  R[3] = 2 * (e1 * e2 + e0 * e3);
-  R[4] = 1 - 2 * (e1 * e1 + e3 * e3);
-  R[5] = 2 * (e2 * e3 - e0 * e1);
-  R[6] = 2 * (e1 * e3 - e0 * e2);
-  R[7] = 2 * (e2 * e3 + e0 * e1);
-  R[8] = 1 - 2 * (e1 * e1 + e2 * e2);
+  qmpc_quat_to_rot(q, R);
   float* rB = S.r_body + (size_t)b * 9;
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) rB[3 * i + j] = R[3 * j + i];
@@ -486,22 +494,51 @@ __device__ __forceinline__ void qmpc_ctrl_orientation(const QmpcCtrlDev& S, int 
   }
 }
 
-__global__ __launch_bounds__(256) void qmpc_ctrl_est_kernel(const QmpcCtrlDev S, const QmpcLegGeom g,
-                                                            const double* __restrict__ imu,
-                                                            const double* __restrict__ motor, const int n) {
+// CheaterOrientationEstimator::run (OrientationEstimator.cpp:21-39), then CheaterPositionVelocityEstimator::run
+// (PositionVelocityEstimator.cpp:229-238) for robot b.  u: the robot's CheaterState<double> row (IMUTypes.h:25-32) --
+// orientation w x y z, position, omegaBody, vBody, acceleration -- every member rounded to float once (.cast<T>()).
+// No yaw re-basing (the cheater estimator has none), no filter: nothing of the VectorNav / Kalman state is touched.
+__device__ __forceinline__ void qmpc_ctrl_cheater(const QmpcCtrlDev& S, int b, const double* u) {
 #pragma clang fp contract(off)
-  const int t = blockIdx.x * 256 + threadIdx.x;  // robot * 4 + leg
-  if (t >= n) return;
-  const int b = t >> 2, leg = t & 3;
-  const size_t o3 = (size_t)t * 3;
-  if (t == 0) S.due_count[0] = 0;  // the tick's list of due robots starts empty (filled by the locomotion kernel)
-  const double* m = motor + (size_t)b * 24;
-  const float q0 = (float)m[3 * leg], q1 = (float)m[3 * leg + 1], q2 = (float)m[3 * leg + 2];
-  const float d0 = (float)m[12 + 3 * leg], d1 = (float)m[12 + 3 * leg + 1], d2 = (float)m[12 + 3 * leg + 2];
-  for (int k = 0; k < 3; ++k) {  // what the Kalman filter of this tick reads: updateData has not run yet
-    S.kf_p[o3 + k] = S.leg_p[o3 + k];
-    S.kf_v[o3 + k] = S.leg_v[o3 + k];
+  float x[16];
+  for (int k = 0; k < 16; ++k) x[k] = (float)u[k];
+  const float* q = x;
+  const float *pos = x + 4, *w = x + 7, *vb = x + 10, *acc = x + 13;
+  float R[9], rpy[3];
+  qmpc_quat_to_rot(q, R);
+  qmpc_quat_to_rpy(q, rpy);
+  float* rB = S.r_body + (size_t)b * 9;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) rB[3 * i + j] = R[3 * j + i];
+  for (int k = 0; k < 4; ++k) S.orientation[(size_t)b * 4 + k] = q[k];
+  for (int k = 0; k < 3; ++k) {
+    const size_t o = (size_t)b * 3 + k;
+    S.rpy[o] = rpy[k];
+    S.omega_body[o] = w[k];
+    // rBody^T * v: column k of rBody = row k of R
+    S.omega_world[o] = (R[3 * k] * w[0] + R[3 * k + 1] * w[1]) + R[3 * k + 2] * w[2];
+    S.a_world[o] = (R[3 * k] * acc[0] + R[3 * k + 1] * acc[1]) + R[3 * k + 2] * acc[2];
+    S.position[o] = pos[k];
+    S.v_world[o] = (R[3 * k] * vb[0] + R[3 * k + 1] * vb[1]) + R[3 * k + 2] * vb[2];
+    S.v_body[o] = vb[k];
   }
+}
+
+// The leg's joint angles and rates of the robot's motor row m, rounded to float (GaitCtrller.cpp:47-56)
+struct QmpcLegJoints {
+  float q0, q1, q2, d0, d1, d2;
+};
+__device__ __forceinline__ QmpcLegJoints qmpc_ctrl_leg_joints(const double* m, int leg) {
+  return {(float)m[3 * leg],      (float)m[3 * leg + 1],      (float)m[3 * leg + 2],
+          (float)m[12 + 3 * leg], (float)m[12 + 3 * leg + 1], (float)m[12 + 3 * leg + 2]};
+}
+
+// LegController::updateData for thread t = robot * 4 + leg: q, qd, J, p, v of the leg
+__device__ __forceinline__ void qmpc_ctrl_leg_update(const QmpcCtrlDev& S, const QmpcLegGeom& g, int t, int leg,
+                                                     const QmpcLegJoints& j) {
+#pragma clang fp contract(off)
+  const size_t o3 = (size_t)t * 3;
+  const float q0 = j.q0, q1 = j.q1, q2 = j.q2, d0 = j.d0, d1 = j.d1, d2 = j.d2;
   float J[9], p[3];
   qmpc_leg_fk(g, leg, q0, q1, q2, J, p);
   for (int k = 0; k < 9; ++k) S.leg_J[(size_t)t * 9 + k] = J[k];
@@ -515,7 +552,39 @@ __global__ __launch_bounds__(256) void qmpc_ctrl_est_kernel(const QmpcCtrlDev S,
   S.qd[o3 + 0] = d0;
   S.qd[o3 + 1] = d1;
   S.qd[o3 + 2] = d2;
+}
+
+__global__ __launch_bounds__(256) void qmpc_ctrl_est_kernel(const QmpcCtrlDev S, const QmpcLegGeom g,
+                                                            const double* __restrict__ imu,
+                                                            const double* __restrict__ motor, const int n) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * 256 + threadIdx.x;  // robot * 4 + leg
+  if (t >= n) return;
+  const int b = t >> 2, leg = t & 3;
+  const size_t o3 = (size_t)t * 3;
+  if (t == 0) S.due_count[0] = 0;  // the tick's list of due robots starts empty (filled by the locomotion kernel)
+  const QmpcLegJoints j = qmpc_ctrl_leg_joints(motor + (size_t)b * 24, leg);
+  for (int k = 0; k < 3; ++k) {  // what the Kalman filter of this tick reads: updateData has not run yet
+    S.kf_p[o3 + k] = S.leg_p[o3 + k];
+    S.kf_v[o3 + k] = S.leg_v[o3 + k];
+  }
+  qmpc_ctrl_leg_update(S, g, t, leg, j);
   if (leg == 0) qmpc_ctrl_orientation(S, b, imu + (size_t)b * 10);
+}
+
+// pre_work of a tick driven by simulator ground truth (qmpc_ctrl_tick_state): the same leg data, and the two cheater
+// estimators in place of the VectorNav estimator and the Kalman filter.  state: [B][16] double.  Memory-shaped: per
+// robot 320 B in (one thread reads the 128 B state row, the four leg threads 48 B each of the motor row) and 504 B out.
+__global__ __launch_bounds__(256) void qmpc_ctrl_est_state_kernel(const QmpcCtrlDev S, const QmpcLegGeom g,
+                                                                  const double* __restrict__ state,
+                                                                  const double* __restrict__ motor, const int n) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * 256 + threadIdx.x;  // robot * 4 + leg
+  if (t >= n) return;
+  const int b = t >> 2, leg = t & 3;
+  if (t == 0) S.due_count[0] = 0;  // the tick's list of due robots starts empty (filled by the locomotion kernel)
+  qmpc_ctrl_leg_update(S, g, t, leg, qmpc_ctrl_leg_joints(motor + (size_t)b * 24, leg));
+  if (leg == 0) qmpc_ctrl_cheater(S, b, state + (size_t)b * 16);
 }
 
 // Robot mode 1, the solve's contact table.  Every solve of mode 1 runs at horizonLength 10 and
@@ -960,6 +1029,14 @@ extern "C" hipError_t qmpc_launch_ctrl_est(const QmpcCtrlDev* S, const float geo
   const QmpcLegGeom g{geom[0], geom[1], geom[2], geom[3]};
   const int n = batch * 4;
   hipLaunchKernelGGL(qmpc_ctrl_est_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, *S, g, imu, motor, n);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t qmpc_launch_ctrl_est_state(const QmpcCtrlDev* S, const float geom[4], const double* state,
+                                                 const double* motor, int batch, hipStream_t stream) {
+  const QmpcLegGeom g{geom[0], geom[1], geom[2], geom[3]};
+  const int n = batch * 4;
+  hipLaunchKernelGGL(qmpc_ctrl_est_state_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, *S, g, state, motor, n);
   return hipGetLastError();
 }
 

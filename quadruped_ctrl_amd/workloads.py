@@ -529,3 +529,38 @@ def make_tick_stream(batch, ticks, seed, dt=0.002, roll=None, joint=None):
         jb, idx, val, t0 = joint
         motor[t0:, jb, idx] = val
     return imu, motor
+
+
+def make_state_stream(batch, ticks, seed, dt=0.002, roll=None, joint=None):
+    """make_tick_stream's counterpart for the ticks driven by simulator ground truth (qmpc_ctrl_tick_state), in the
+    reference's CheaterState member order (src/Utilities/IMUTypes.h:25-32):
+
+        state [ticks, B, 16] float64: orientation w x y z, position, omegaBody, vBody, acceleration (body frame)
+        motor [ticks, B, 24] float64: as make_tick_stream
+
+    The random draws of make_tick_stream come first and in its order, so for one seed motor, the quaternion, the gyro
+    (here omegaBody) and the accelerometer (here acceleration) are make_tick_stream's numbers.  Then position near
+    (0, 0, 0.29) with a smooth drift of a few centimetres, and vBody: a per-robot base plus a small smooth wobble, inside
+    the range of the velocity commands the controller's tests track and of a size the motor stream can carry -- its joint
+    rates stay below 0.05 * 2 pi * 2 = 0.63 rad/s, i.e. feet (and so a body over stance feet) moving at up to about
+    0.2 m/s.  The yaw is make_tick_stream's, anywhere on the circle, and the cheater estimator does not re-base it: the
+    controller's yaw_des_true starts at 0 (as in the reference), so robots that start far from yaw 0 are commanded to turn
+    by radians and their MPC problems are hard ones.  roll / joint: as in make_tick_stream."""
+    imu, motor = make_tick_stream(batch, ticks, seed, dt=dt, roll=roll, joint=joint)
+    rng = np.random.default_rng(seed)
+    for shape, draw in (((1, batch, 6), "uniform"), ((1, batch, 2), "uniform"), ((1, batch), "uniform"),
+                        ((1, batch), "normal"), ((1, batch, 12), "uniform"), ((1, batch, 12), "uniform")):
+        getattr(rng, draw)(0, 1, shape)                       # make_tick_stream's draws, in its order
+    t = np.arange(ticks)[:, None, None] * dt                  # [T, 1, 1]
+    pph = rng.uniform(0, 2 * np.pi, (1, batch, 3))
+    pamp = rng.uniform(0.01, 0.04, (1, batch, 3)) * np.array([1.0, 1.0, 0.25])
+    vbase = np.stack([rng.uniform(-0.15, 0.2, batch), rng.uniform(-0.1, 0.1, batch), rng.uniform(-0.02, 0.02, batch)], -1)[None]
+    vph = rng.uniform(0, 2 * np.pi, (1, batch, 3))
+    state = np.zeros((ticks, batch, 16))
+    state[..., 0] = imu[..., 6]
+    state[..., 1:4] = imu[..., 3:6]
+    state[..., 4:7] = np.array([0.0, 0.0, 0.29]) + pamp * np.sin(2 * np.pi * 0.7 * t + pph)
+    state[..., 7:10] = imu[..., 7:10]
+    state[..., 10:13] = vbase + 0.02 * np.sin(2 * np.pi * 0.9 * t + vph)
+    state[..., 13:16] = imu[..., 0:3]
+    return state, motor

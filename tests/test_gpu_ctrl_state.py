@@ -1,0 +1,378 @@
+"""GPU suite (-m gpu) for the batched controller's ticks driven by simulator ground truth (qmpc_ctrl_prework_state /
+qmpc_ctrl_tick_state, include/qmpc_ctrl.h; BatchedController.prework_state / tick_state).
+
+The estimator stage is compared with tests/ctrl_model_state.py (the cheater estimators restated in numpy float32): bit
+for bit where no transcendental is involved -- the quaternion, rBody, the three rBody^T products, position and the
+velocities -- and within the suite's 1e-5 rad for rpy (the device's atan2f / asinf).  Everything after the estimators is
+the existing tick, so it is checked with the existing restatements (tests/ctrl_model.py, tests/ctrl_model_mode1.py)
+teacher-forced on the GPU's own estimator read-out, under the rules of tests/test_gpu_controller.py and
+tests/test_gpu_ctrl_mode1.py; the remaining tests compare two runs of the library bit for bit.
+"""
+import numpy as np
+import pytest
+
+from oracle import oracle as O
+from quadruped_ctrl_amd import workloads as W
+
+import ctrl_model as M
+import ctrl_model_mode1 as M1
+from ctrl_model_state import ACC, OMEGA, ORI, POS, VBODY, estimate_state, rebase_yaw
+from test_gpu_controller import EXACT_F32, EXACT_I32, LAND_ULPS, PID, _bound, _gaits, _gpu_est, _vel
+
+pytestmark = pytest.mark.gpu
+
+f32 = np.float32
+EST_EXACT = ("orientation", "r_body", "omega_body", "omega_world", "a_world", "position", "v_world", "v_body")
+LEG = ("q", "qd", "leg_J", "leg_p", "leg_v")
+
+
+def _ctrl(B, schedule="lockstep", mode=None):
+    from quadruped_ctrl_amd.binding import BatchedController
+    c = BatchedController(0, max_batch=B)
+    c.init(B, 500.0, PID)
+    if schedule != "lockstep":
+        c.set_schedule(schedule)
+    if mode is not None:
+        c.set_robot_mode(mode)
+    return c
+
+
+def _dev(c, a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to(c.device)
+
+
+def test_estimator_stage_bit_for_bit():
+    """257 robots (1028 threads: the last block is partial), one prework_state: the whole circle of yaw, rolls up to
+    0.45 rad, pitches up to 0.3 rad."""
+    B = 257
+    state, motor = W.make_state_stream(B, 1, 101)
+    state, motor = state[0], motor[0]
+    rng = np.random.default_rng(102)
+    rpy = np.stack([0.45 * np.cos(np.arange(B) * 0.37), rng.uniform(-0.3, 0.3, B), np.linspace(-3.14, 3.14, B)], 1)
+    rpy[1:3] = [[0.45, 0.3, 1.0], [0, 0, 0]]              # (robots 0 and 256 sit at the two ends of the circle)
+    state[:, ORI] = W._quat_from_rpy(rpy)
+    c, ref = _ctrl(B), _ctrl(B)
+    c.prework_state(_dev(c, state), _dev(c, motor))
+    imu, _ = W.make_tick_stream(B, 1, 101)
+    ref.prework(_dev(ref, imu[0]), _dev(ref, motor))
+    m = M.CtrlModel(B, 500.0, PID)
+    e = estimate_state(m, state, motor)
+    assert np.abs(e["rpy"][:, 0]).max() > 0.44 and np.ptp(e["rpy"][:, 2]) > 6.2
+    for k in EST_EXACT:
+        g = c.read(k)
+        assert np.array_equal(g, e[k]), (k, np.abs(g - e[k]).max())
+    assert np.array_equal(c.read("position"), state[:, POS].astype(f32))
+    d = np.abs(c.read("rpy") - e["rpy"]).max()
+    assert d < 1e-5, d
+    for k in LEG:
+        assert np.array_equal(c.read(k), ref.read(k)), k
+    assert (c.read("counter") == 0).all() and (c.read("first_run") == 1).all() and c.view()["ticks"] == 0
+    c.close()
+    ref.close()
+
+
+def test_one_code_path_for_the_orientation():
+    """The IMU path's orientation read-out fed back as a state quaternion gives the IMU path's derived quantities bit for
+    bit: both estimators call the same quaternionToRotationMatrix / quatToRPY / rBody^T code."""
+    B = 64
+    imu, motor = W.make_tick_stream(B, 1, 111)
+    a, b = _ctrl(B), _ctrl(B)
+    a.prework(_dev(a, imu[0]), _dev(a, motor[0]))
+    state = np.zeros((B, 16))
+    state[:, ORI] = a.read("orientation").astype(np.float64)
+    state[:, OMEGA] = imu[0][:, 7:10]
+    state[:, ACC] = imu[0][:, 0:3]
+    state[:, POS] = [0, 0, 0.29]
+    b.prework_state(_dev(b, state), _dev(b, motor[0]))
+    for k in ("orientation", "rpy", "r_body", "omega_world", "a_world"):
+        assert np.array_equal(a.read(k), b.read(k)), k
+    assert np.abs(a.read("rpy")[:, 2]).max() < 1e-6      # (the IMU path re-based yaw on this first visit)
+    a.close()
+    b.close()
+
+
+def test_filter_is_left_alone():
+    B = 32
+    c = _ctrl(B)
+    keys = ("xhat", "P", "first_visit", "ori_ini_inv", "kf_p", "kf_v")
+    before = {k: c.read(k) for k in keys}
+    assert (before["first_visit"] == 1).all() and (before["P"][:, 0] == 100).all()
+    state, motor = W.make_state_stream(B, 20, 121)
+    c.set_vel(_dev(c, _vel(B, 122)))
+    for t in range(20):
+        eff = c.tick_state(_dev(c, state[t]), _dev(c, motor[t]))
+    assert np.isfinite(eff.cpu().numpy()).all() and c.view()["ticks"] == 20
+    for k in keys:
+        assert np.array_equal(c.read(k), before[k]), k
+    c.close()
+
+
+def test_teacher_forced_tick_parity_state():
+    """tests/test_gpu_controller.py::_teacher_forced with tick_state: robot mode 0, lockstep, 257 robots, 40 ticks (three
+    MPC ticks), every gait number and omni variant, switched at tick 20.
+
+    The stream is make_state_stream's with every robot's yaw re-based on its tick-0 yaw (ctrl_model_state.rebase_yaw).
+    Why: the reference's controller starts with _yaw_des_true = 0 and re-anchors it only beyond 5 rad
+    (ConvexMPCLocomotion.cpp:106), and the cheater estimator, unlike the sensor path's, does not re-base yaw.  With the
+    raw stream (yaw uniform on the circle) the walking-gait robots with |yaw| > 2.1 rad get a yaw error of radians into
+    the MPC, and the REFERENCE's qpOASES stops at its cap of 100 working-set recalculations (SolverMPC.cpp:527-541) on
+    them -- measured on an MI355X: 20 of 257 robots at tick 12, every one with reference nWSR = 100 -- and returns an
+    iterate that is not the minimiser, i.e. nothing to compare with (the library is within 6.1e-6 of the same pipeline
+    run to convergence on 19 of them; on the 20th, gait 31 at yaw -2.72, it reports status 24 -- fallback route, working
+    set full -- and zero forces).  The whole circle of yaw is covered where no solver is involved:
+    test_estimator_stage_bit_for_bit, and the raw stream in every other test of this file.  Nobody is dropped here, and
+    the test asserts that the reference converged on every robot it compares with."""
+    B, ticks, seed, switch_at = 257, 40, 257, 20
+    c = _ctrl(B)
+    m = M.CtrlModel(B, 500.0, PID)
+    state, motor = W.make_state_stream(B, ticks, seed)
+    state = rebase_yaw(state)
+    assert np.abs(np.linalg.norm(state[..., ORI], axis=-1) - 1).max() < 1e-12
+    vel = _vel(B, seed + 1)
+    c.set_vel(_dev(c, vel))
+    m.set_vel(vel)
+    # what the model receives is what `state` gives, through estimate_state: a path that ran the filter cannot pass
+    c.prework_state(_dev(c, state[0]), _dev(c, motor[0]))
+    e0 = estimate_state(M.CtrlModel(B, 500.0, PID), state[0], motor[0])
+    g0 = _gpu_est(c)
+    for k in ("position", "v_world"):
+        assert np.array_equal(g0[k], e0[k]), k
+    assert np.array_equal(g0["position"], state[0][:, POS].astype(f32))
+    assert np.abs(g0["v_world"]).max() > 0.1 and c.view()["ticks"] == 0
+    n_mpc = 0
+    for t in range(ticks):
+        if t in (0, switch_at):
+            g = _gaits(B, t, switch_at)
+            c.set_gait(_dev(c, g))
+            m.set_gait(g)
+        eff = c.tick_state(_dev(c, state[t]), _dev(c, motor[t])).cpu().numpy()
+        e = _gpu_est(c)
+        assert np.array_equal(e["position"], state[t][:, POS].astype(f32)), t
+        e["leg_q"] = motor[t][:, :12].astype(f32)
+        gpu_pf = c.read("sw_pf")
+        out = m.loco(e, pf_override=gpu_pf)
+        scale = np.maximum(1.0, np.abs(out["pf"]))
+        land = np.abs(gpu_pf - out["pf"]) / (np.finfo(f32).eps * scale)
+        assert land.max() <= LAND_ULPS, (t, land.max())
+        zero_yr = m.vel_des[:, 2] == 0
+        assert np.array_equal(gpu_pf[zero_yr], out["pf"][zero_yr]), t
+        for k in EXACT_I32:
+            assert np.array_equal(c.read(k).reshape(getattr(m, k).shape), getattr(m, k)), (t, k)
+        for k in EXACT_F32:
+            g_ = c.read(k).reshape(getattr(m, k).shape)
+            assert np.array_equal(g_, getattr(m, k)), (t, k, np.abs(g_ - getattr(m, k)).max())
+        if (t + 1) % 13 == 0:
+            n_mpc += 1
+            rec, wpd, xci = O.pack_commands(m.command(e), float(m.dt_mpc))
+            m.wpd[:], m.xci[:] = wpd, xci
+            rec.update(dt=float(m.dt_mpc), mu=0.4, f_max=120.0)
+            f_gpu = c.read("f_ff")
+            soln, nwsr, rc = O.solve_batch(rec)
+            assert (rc == 0).all()
+            f_ref = O.forces_to_body(e["r_body"], soln[:, :12].astype(f32))
+            err = np.abs(f_gpu.astype(np.float64) - f_ref).max(1) / np.maximum(np.abs(f_ref).max(1), 1.0)
+            print(f"tick {t}: worst relative f_ff error {err.max():.3e}, {(err >= 1e-4).sum()} robots over 1e-4, "
+                  f"largest reference nWSR {nwsr.max()}, |yaw - yaw_des_true| up to {np.abs(e['rpy'][:, 2] - m.yaw_des_true).max():.3f}")
+            if (err >= 1e-4).any():
+                bnd, st = _bound(rec, err), c.read("status")[:, 0]
+                for i in np.flatnonzero(err >= 1e-4):
+                    print(f"  robot {i}: error {err[i]:.3e}, bound {bnd[i]:.3e}, reference nWSR {nwsr[i]}, status {st[i]}, "
+                          f"gait {m.gait_num[i]}, v_world {e['v_world'][i]}, command {m.vel_des[i]}")
+                assert (err <= bnd).all(), (t, err.max())
+            assert (nwsr < 100).all(), (t, np.flatnonzero(nwsr >= 100))     # the reference converged on every robot
+            assert (c.read("status")[:, 0] & 47 == 0).all(), t               # and the library reports no error bit
+            m.f_ff[:] = f_gpu
+        for k in ("wpd", "xci"):
+            assert np.array_equal(c.read(k).reshape(getattr(m, k).shape), getattr(m, k)), (t, k)
+        eff_m = m.legcmd(e, m.f_ff)
+        assert np.array_equal(eff, eff_m), (t, np.abs(eff - eff_m).max())
+    assert n_mpc == 3 and c.view()["ticks"] == ticks
+    assert np.isfinite(eff).all() and (c.read("safe") == 1).all()
+    c.close()
+
+
+def test_mode1_per_robot_schedule_state():
+    """Robot mode 1 on state ticks, 64 robots, 400 ticks, teacher-forced against CtrlModelMode1 as
+    tests/test_gpu_ctrl_mode1.py does it (without the oracle solves): x commands over [0, 2] m/s."""
+    B, ticks = 64, 400
+    c = _ctrl(B, "per_robot", 1)
+    m = M1.CtrlModelMode1(B, 500.0, PID)
+    state, motor = W.make_state_stream(B, ticks, 131)
+    g = np.array([9, 29, 4, 24, 0, 30], np.int32)[np.arange(B) % 6]
+    vel = np.zeros((B, 3))
+    vel[:, 0] = np.linspace(0.0, 2.0, B)
+    vel[1::4, 1] = 0.25
+    vel[2::8, 2] = 0.3
+    c.set_gait(_dev(c, g))
+    c.set_vel(_dev(c, vel))
+    m.set_gait(g)
+    m.set_vel(vel)
+    seen, n_solves = set(), 0
+    for t in range(ticks):
+        eff = c.tick_state(_dev(c, state[t]), _dev(c, motor[t])).cpu().numpy()
+        e = _gpu_est(c)
+        e["leg_q"] = motor[t][:, :12].astype(f32)
+        gpu_pf = c.read("sw_pf")
+        out = m.loco(e, pf_override=gpu_pf)
+        scale = np.maximum(1.0, np.abs(out["pf"]))
+        land = np.abs(gpu_pf - out["pf"]) / (np.finfo(f32).eps * scale)
+        assert land.max() <= LAND_ULPS, (t, land.max())
+        for k in EXACT_I32 + ("nseg",):          # (offsets, durations among them)
+            assert np.array_equal(c.read(k).reshape(getattr(m, k).shape), getattr(m, k)), (t, k)
+        assert np.array_equal(c.read("due")[:, 0] != 0, m.due), t
+        for k in EXACT_F32 + ("gait_phase",):
+            g_ = c.read(k).reshape(getattr(m, k).shape)
+            assert np.array_equal(g_, getattr(m, k)), (t, k, np.abs(g_ - getattr(m, k)).max())
+        due = np.flatnonzero(m.due)
+        f_gpu = c.read("f_ff")
+        if len(due):
+            n_solves += len(due)
+            cmd, tables = m.command_mode1(e, due)
+            mo, md, it = c.read("mpc_offsets"), c.read("mpc_durations"), c.read("iteration")[:, 0]
+            for k, b in enumerate(due):
+                assert np.array_equal(M.mpc_table(mo[b], md[b], int(it[b]), n=10), tables[k]), (t, b)
+            _, wpd, xci = O.pack_commands(cmd, float(m.dt_mpc))
+            m.wpd[due], m.xci[due] = wpd, xci
+            m.f_ff[due] = f_gpu[due]
+        assert np.array_equal(f_gpu[~m.due], m.f_ff[~m.due]), t
+        for k in ("wpd", "xci"):
+            assert np.array_equal(c.read(k).reshape(getattr(m, k).shape), getattr(m, k)), (t, k)
+        assert np.array_equal(eff, m.legcmd(e, m.f_ff)), t
+        seen |= set(int(x) for x in m.nseg)
+    assert len(seen) >= 3, seen
+    assert n_solves > B * (ticks // 13 - 6) and np.isfinite(eff).all()
+    c.close()
+
+
+def test_safety_latch_state():
+    """Robot 2's state quaternion has roll 0.7 rad from tick 5: it latches on that tick and outputs zeros from then on;
+    robot 1 at roll 0.45 rad keeps running."""
+    B, ticks = 6, 30
+    c = _ctrl(B)
+    state, motor = W.make_state_stream(B, ticks, 3, roll=(1, 0.45, 0))
+    s2, _ = W.make_state_stream(B, ticks, 3, roll=(2, 0.7, 5))
+    state[:, 2] = s2[:, 2]
+    for t in range(ticks):
+        eff = c.tick_state(_dev(c, state[t]), _dev(c, motor[t])).cpu().numpy()
+        safe, rpy = c.read("safe")[:, 0], c.read("rpy")
+        assert safe[1] == 1 and 0.4 < abs(rpy[1, 0]) < 0.5, (t, rpy[1])
+        assert safe[2] == (1 if t < 5 else 0), t
+        if t >= 5:
+            assert 0.5 < abs(rpy[2, 0]) < 1.0 and (eff[2] == 0).all(), (t, rpy[2])
+        assert (np.delete(safe, 2) == 1).all(), t
+        assert np.abs(eff[[0, 1, 3, 4, 5]]).max(1).min() > 0, t
+    c.close()
+
+
+def test_reset_state_per_robot():
+    """Half the robots reset before tick 17 (per-robot schedule): the others are bit-identical to the run without the
+    reset; the reset ones restart at counter 0 and first solve 13 ticks later."""
+    B, at, ticks = 32, 17, 32
+    state, motor = W.make_state_stream(B, ticks, 141)
+    a, b = _ctrl(B, "per_robot"), _ctrl(B, "per_robot")
+    g, v = _gaits(B, 0, 10 ** 9), _vel(B, 142)
+    mask = np.arange(B) % 2 == 0
+    for c in (a, b):
+        c.set_gait(_dev(c, g))
+        c.set_vel(_dev(c, v))
+    for t in range(ticks):
+        if t == at:
+            a.reset(_dev(a, mask))
+            assert (a.read("counter")[mask, 0] == 0).all() and (a.read("counter")[~mask, 0] == at).all()
+            a.set_gait(_dev(a, g))
+            a.set_vel(_dev(a, v))
+        x, y = _dev(a, state[t]), _dev(a, motor[t])
+        ea, eb = a.tick_state(x, y).cpu().numpy(), b.tick_state(x, y).cpu().numpy()
+        assert np.array_equal(ea[~mask], eb[~mask]), t
+        due = a.read("due")[:, 0]
+        if t >= at:
+            assert (a.read("counter")[mask, 0] == t - at + 1).all(), t
+            assert (due[mask] == (1 if t - at + 1 == 13 else 0)).all(), t       # the 13th tick after the reset
+        assert (due[~mask] == (1 if (t + 1) % 13 == 0 else 0)).all(), t
+    for k in EXACT_F32 + EXACT_I32 + ("f_ff", "wpd", "xci", "grf", "status", "position", "v_world"):
+        assert np.array_equal(a.read(k)[~mask], b.read(k)[~mask]), k
+    assert np.abs(a.read("f_ff")[mask]).max() > 1.0 and (a.read("safe") == 1).all()
+    a.close()
+    b.close()
+
+
+def test_graph_capture_replay_matches_eager_state():
+    """13 captured tick_state calls replayed twice equal 39 eager ticks of a second controller, bit for bit."""
+    import torch
+    B = 64
+    eager, cap = _ctrl(B), _ctrl(B)
+    dev = eager.device
+    state, motor = W.make_state_stream(B, 39, 151)
+    for c in (eager, cap):
+        c.set_gait(_dev(c, _gaits(B, 0, 10 ** 9)))
+        c.set_vel(_dev(c, _vel(B, 152)))
+    for t in range(13):          # first run and one MPC, eager on both
+        x, y = _dev(eager, state[t]), _dev(eager, motor[t])
+        eager.tick_state(x, y)
+        cap.tick_state(x, y)
+    torch.cuda.synchronize()
+    bs = torch.zeros((13, B, 16), dtype=torch.float64, device=dev)
+    bm = torch.zeros((13, B, 24), dtype=torch.float64, device=dev)
+    be = torch.zeros((13, B, 12), dtype=torch.float64, device=dev)
+    graph = torch.cuda.CUDAGraph()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        with torch.cuda.graph(graph, stream=s):
+            for k in range(13):
+                cap.tick_state(bs[k], bm[k], be[k])
+    torch.cuda.current_stream().wait_stream(s)
+    for r in range(2):
+        lo = 13 * (r + 1)
+        bs.copy_(torch.from_numpy(state[lo:lo + 13]))
+        bm.copy_(torch.from_numpy(motor[lo:lo + 13]))
+        graph.replay()
+        torch.cuda.synchronize()
+        for k in range(13):
+            ee = eager.tick_state(_dev(eager, state[lo + k]), _dev(eager, motor[lo + k]))
+            torch.cuda.synchronize()
+            assert torch.equal(ee, be[k]), (r, k)
+    for k in ("f_ff", "p_des", "counter", "xhat", "wpd", "xci", "safe"):
+        assert np.array_equal(eager.read(k), cap.read(k)), k
+    assert (eager.read("counter") == 39).all() and np.abs(eager.read("f_ff")).max() > 1.0
+    eager.close()
+    cap.close()
+
+
+def test_state_argument_errors():
+    import torch
+    from quadruped_ctrl_amd.binding import BatchedController, QmpcError
+    c = BatchedController(0, max_batch=8)
+    lib, h = c.lib, c.mpc.h
+    x = torch.zeros((8, 16), dtype=torch.float64, device=c.device)
+    x[:, 0] = 1.0
+    y = torch.zeros((8, 24), dtype=torch.float64, device=c.device)
+    e = torch.zeros((8, 12), dtype=torch.float64, device=c.device)
+    # before init: QMPC_ERR_STATE
+    assert lib.qmpc_ctrl_tick_state(h, 8, x.data_ptr(), y.data_ptr(), e.data_ptr(), None) == 3
+    assert lib.qmpc_ctrl_prework_state(h, 8, x.data_ptr(), y.data_ptr(), None) == 3
+    with pytest.raises(QmpcError):
+        c.tick_state(x, y)
+    c.init(8, 500.0, PID)
+    assert lib.qmpc_ctrl_tick_state(h, 8, None, y.data_ptr(), e.data_ptr(), None) == 1
+    assert lib.qmpc_ctrl_tick_state(h, 8, x.data_ptr(), None, e.data_ptr(), None) == 1
+    assert lib.qmpc_ctrl_tick_state(h, 8, x.data_ptr(), y.data_ptr(), None, None) == 1
+    assert lib.qmpc_ctrl_tick_state(h, 7, x.data_ptr(), y.data_ptr(), e.data_ptr(), None) == 1   # not the initialised batch
+    assert lib.qmpc_ctrl_prework_state(h, 8, None, y.data_ptr(), None) == 1
+    assert lib.qmpc_ctrl_prework_state(h, 8, x.data_ptr(), None, None) == 1
+    assert lib.qmpc_ctrl_prework_state(h, 7, x.data_ptr(), y.data_ptr(), None) == 1
+    assert c.view()["ticks"] == 0                                   # nothing above counted as a tick
+    for call in (c.tick_state, c.prework_state):
+        with pytest.raises(QmpcError):
+            call(x.float(), y)                                      # float32
+        with pytest.raises(QmpcError):
+            call(x[:, :10].contiguous(), y)                         # [B,10]: the IMU layout
+        with pytest.raises(QmpcError):
+            call(x.cpu(), y)                                        # a CPU tensor
+    # the schedule can still be chosen after a prework_state, not after a tick_state
+    c.prework_state(x, y)
+    assert lib.qmpc_ctrl_set_schedule(h, 1) == 0
+    c.tick_state(x, y, e)
+    assert lib.qmpc_ctrl_set_schedule(h, 0) == 3 and c.view()["ticks"] == 1
+    c.close()

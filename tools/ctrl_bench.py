@@ -17,8 +17,11 @@ occur; the robots' counters restart on their own there, which spreads the solves
 warm-up should then cover the settling of the velocity filter (--warmup 600).  Reports the histogram of the robots'
 segment counts at the end.
 
+--source state drives the ticks with simulator ground truth (qmpc_ctrl_tick_state on workloads.make_state_stream: the
+cheater estimators, no Kalman filter) instead of the sensor path (--source imu, the default); nothing else changes.
+
     python tools/ctrl_bench.py [--batches 1024,4096,16384] [--cycles 8] [--warmup 26] [--schedule lockstep|per_robot]
-                               [--stagger] [--robot-mode 0|1] [--out FILE]
+                               [--stagger] [--robot-mode 0|1] [--source imu|state] [--out FILE]
 """
 import argparse
 import json
@@ -31,7 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0):
+def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, source="imu"):
     import torch
     from quadruped_ctrl_amd import workloads as W
     from quadruped_ctrl_amd.binding import BatchedController
@@ -53,7 +56,12 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0):
     vel = torch.from_numpy(vel).cuda()
     ctrl.set_vel(vel)
     n = warmup + 13 * cycles
-    imu, motor = W.make_tick_stream(B, 26, seed=B)
+    if source == "state":
+        imu, motor = W.make_state_stream(B, 26, seed=B)      # (`imu` below: the tick's first input, whichever it is)
+        tick = ctrl.tick_state
+    else:
+        imu, motor = W.make_tick_stream(B, 26, seed=B)
+        tick = ctrl.tick
     imu, motor = torch.from_numpy(imu).cuda(), torch.from_numpy(motor).cuda()
     eff = torch.empty((B, 12), dtype=torch.float64, device="cuda")
     if stagger:
@@ -62,11 +70,11 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0):
             ctrl.reset(group == t)
             ctrl.set_gait(g)     # (a reset zeroes the robot's gait and velocity command)
             ctrl.set_vel(vel)
-            ctrl.tick(imu[t], motor[t], eff)
+            tick(imu[t], motor[t], eff)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
     for t in range(n):
         ev[t][0].record()
-        ctrl.tick(imu[t % 26], motor[t % 26], eff)
+        tick(imu[t % 26], motor[t % 26], eff)
         ev[t][1].record()
     torch.cuda.synchronize()
     us = np.array([a.elapsed_time(b) * 1e3 for a, b in ev])
@@ -75,7 +83,7 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0):
     t_non, t_mpc = float(np.median(us[keep & ~mpc])), float(np.median(us[keep & mpc]))
     per_cycle = 12 * t_non + t_mpc
     v = ctrl.view()
-    res = {"batch": B, "schedule": schedule, "stagger": bool(stagger), "robot_mode": robot_mode, "ticks_timed": int(keep.sum()),
+    res = {"batch": B, "source": source, "schedule": schedule, "stagger": bool(stagger), "robot_mode": robot_mode, "ticks_timed": int(keep.sum()),
            "us_per_tick_median": round(float(np.median(us[keep])), 2), "us_per_tick_max": round(float(us[keep].max()), 2),
            "robot_ticks_per_s_window": float(f"{B * int(keep.sum()) / (float(us[keep].sum()) * 1e-6):.4g}")}
     if stagger or robot_mode == 1:
@@ -101,6 +109,7 @@ def main():
     ap.add_argument("--schedule", choices=("lockstep", "per_robot"), default="lockstep")
     ap.add_argument("--stagger", action="store_true")
     ap.add_argument("--robot-mode", type=int, choices=(0, 1), default=0)
+    ap.add_argument("--source", choices=("imu", "state"), default="imu")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.robot_mode == 1:
@@ -109,7 +118,7 @@ def main():
         ap.error("--stagger needs --schedule per_robot (a lockstep reset keeps the robot on the batch's MPC ticks)")
     out = []
     for B in [int(x) for x in a.batches.split(",")]:
-        r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode)
+        r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source)
         print(json.dumps(r), flush=True)
         out.append(r)
     if a.out:
