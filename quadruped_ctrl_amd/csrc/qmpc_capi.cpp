@@ -20,6 +20,8 @@
 #include "../../include/qmpc_ctrl.h"    // batched locomotion controller (same library)
 #include "qmpc_device.h"
 #include "qmpc_glue.h"
+#include "qmpc_plan.h"  // the solve's launch plan (host-only)
+static_assert(kLongHorizon == QMPC_LONG_HORIZON, "qmpc_plan.h and qmpc.h disagree");
 
 // per-class entry points of qmpc_kernels.hip (one translation unit per size class)
 #define QMPC_DECLARE_CLASS(RB)                                                                  \
@@ -151,7 +153,7 @@ struct qmpc_ctx {
   int dense = 1;               // qmpc_set_dense: the 64-row class at five workgroups per CU -- 0 never, 1 automatic (by the handle's size), 2 whenever the chain is that class alone
   int chunks = 0;              // qmpc_set_chunks (test hook): run the item classes in at least this many chunks (0 / 1: as few as the pools allow)
   int dbg_engine_events = 0;   // test hook: events the engine may hold per robot (0 = the compiled capacity)
-  unsigned call_no = 0;
+  PlanCounters ctr;  // the host-side call counters (call_no, hint_call, so_call, prio_call): plan_solve moves them
   // order hint (qmpc_set_order_hint): 0 off, 1 automatic -- a call whose first class is launched over more robots than it has
   // resident workgroups takes them in the order of the previous call's iteration counts (same batch size), longest first
   int order_hint = 1;
@@ -161,16 +163,9 @@ struct qmpc_ctx {
   // built inside the launch (qmpc_kernels.hip: size_order_build)
   int size_order = 1;
   unsigned long long* d_so_order = nullptr;  // [max_batch] (call number << 32 | robot)
-  unsigned so_call = 0;
   unsigned long long* d_prio_cu = nullptr;  // [2048] one-round launches without a hint: one word per CU (qmpc_device.h: prio_cu)
-  unsigned prio_call = 0;
-  static constexpr int so_first_pct = 0, so_first_pct_hint = 50;  // the unsorted head beyond the first round, % of a round: keys from the records / from the hint
-  static constexpr int so_min_div = 8;  // at least a round / so_min_div robots to order (measured 2 / 4 / 8 on batches of 1.1 ... 2.5 rounds: no loss anywhere, +4 ... +13 % at 1.4 rounds)
-  static constexpr int so_tail_rounds = 5;  // a launch of many rounds orders its last five only (solve_impl)
   int hint_batch = 0;           // batch size of the call that wrote d_hint_iters (0: none yet)
-  static constexpr int hint_hard = 5;  // single-round launches: iterations in the previous call from which a robot may keep the highest issue priority (0 = off)
   int* d_hint_max = nullptr;    // [3] largest iteration count of the last calls (slots rotated by hint_call: read / fold / clear)
-  unsigned hint_call = 0;
   int* d_cu_slots = nullptr;
   int bal_debug = 0;  // qmpc_set_debug_balance
   int max_stance = 0;          // caller's bound on stance foot-steps per robot (0 = unknown)
@@ -305,9 +300,6 @@ void bind_record(QmpcParams& P, const qmpc_inputs& in) {
   P.x_drag_stride = in.x_drag_stride;
 }
 
-// leading dimension of a work item of pool sk: 0 = 128-row class, 1 = 192-row class, 2 = large problems
-size_t item_ld(int sk) { return sk == 0 ? 128 : (sk == 1 ? 192 : QMPC_BIG_LD); }
-
 // Mini Cheetah _abadLocation (MiniCheetah.h:25-26,105): the Kalman filter's hip location
 const float kAbadLocation[3] = {0.19f, 0.049f, 0.f};
 
@@ -363,7 +355,7 @@ int qmpc_create(int device_id, int max_batch, int max_horizon, qmpc_handle* out)
     // Schur-form engine.  Every flag is 0 between calls; after a call that ended in a device error they are re-armed
     // (solve_impl) -- a flag left at 1 would otherwise be lost for the life of the handle
     // (2048 slices of 192 KiB: what a call of 8192 robots needs when the 64-row class runs five per CU ahead of larger
-    //  classes -- see the launch loop of solve_impl)
+    //  classes -- qmpc_plan.h: plan_solve)
     c->ov_nslice_alloc = c->ov_nslice = max_batch < 2048 ? max_batch : 2048;
     e = hipMalloc(&c->d_ovpool, sizeof(double) * (size_t)c->ov_nslice_alloc * QMPC_OV_SLICE);
     if (e == hipSuccess) e = hipMalloc(&c->d_ovflags, sizeof(int) * (size_t)c->ov_nslice_alloc);
@@ -661,7 +653,7 @@ int qmpc_debug_ld(qmpc_handle) { return QMPC_DBG_LD; }
 int qmpc_debug_read_item(qmpc_handle c, int which, int item, double* hinv_host, double* xu_host, int* hdr4) {
   if (!c || which < 0 || which > 2 || c->wk_cap[which] <= 0 || item < 0 || item >= c->wk_cap[which]) return QMPC_ERR_ARG;
   DeviceGuard g(c->device);
-  const size_t ld = item_ld(which);
+  const size_t ld = kItems[which].ld;
   HIP_TRY(c, hipDeviceSynchronize());
   if (hinv_host) HIP_TRY(c, hipMemcpy(hinv_host, c->d_wk_hinv[which] + (size_t)item * ld * ld, sizeof(double) * ld * ld, hipMemcpyDeviceToHost));
   if (xu_host) HIP_TRY(c, hipMemcpy(xu_host, c->d_wk_xu[which] + (size_t)item * ld, sizeof(double) * ld, hipMemcpyDeviceToHost));
@@ -694,79 +686,41 @@ bool command_ok(const qmpc_command* cmd) {
          !(cmd->gait_type && !cmd->stand_traj);  // a standing robot needs its stand_traj row
 }
 
-// Which size classes a solve launches, and which of them through work items (the decoupled path): ONE rule, used by
-// the solve and by the allocation of the pools.
-//   chain 1 -> 4 -> 2 -> 3 (64 / 96 / 128 / 192 padded rows), n_r = 3 * stance foot-steps; classes k0 .. k1 - 1 are
-//   launched; long_h: the large-problem stage behind the 192-row class (192 < n_r <= 432, horizons above 16)
-struct ClassPlan {
-  int k0 = 0, k1 = 0;
-  bool long_h = false;
-  bool split[4] = {false, false, false, false};
-};
-const int kChain[4] = {1, 4, 2, 3};
-const int kRows[4] = {64, 96, 128, 192};
-
-ClassPlan plan_classes(const qmpc_ctx* c, int admm_mode, bool warm) {
-  ClassPlan pl;
-  const bool full_problem = (admm_mode == 1), exact_cold = !admm_mode && !warm;
-  const int h = c->horizon;
-  const int nmax = 12 * h;
-  int nclass = 4;
-  for (int k = 0; k < 4; ++k)
-    if (nmax <= kRows[k]) { nclass = k + 1; break; }
-  // a caller that knows its gaits can bound the reduced size (qmpc_set_max_stance):
-  // larger classes are then not even launched; violators are flagged WS_FULL
-  pl.k1 = nclass;
-  if (c->max_stance > 0 && !full_problem) {  // (use_jcqp = 1: every foot-step is a variable block, n_r = 12 h for all robots)
-    const int nb = 3 * c->max_stance;
-    int hc = 4;
-    for (int k = 0; k < 4; ++k)
-      if (nb <= kRows[k]) { hc = k + 1; break; }
-    if (hc < pl.k1) pl.k1 = hc;
-  }
-  // ... and with a lower bound the classes that are too small for every robot are skipped
-  while (pl.k0 + 1 < pl.k1 && 3 * (full_problem ? 4 * h : c->min_stance) > kRows[pl.k0]) ++pl.k0;
-  if (h > QMPC_LONG_HORIZON) {
-    // long horizons (up to K_MAX_GAIT_SEGMENTS = 36): the 192-row class alone has the threads (12 h tracking-error
-    // entries, one per thread) and the LDS (h x h coefficient tables) to assemble them -- it takes every robot; one with
-    // more than 64 stance foot-steps goes on to the large-problem path
-    pl.k0 = 3;
-    pl.k1 = 4;
-    // (the large-problem stage: skipped when the caller's size hint, qmpc_set_max_stance, rules such robots out -- a
-    //  violator is reported like any other; use_jcqp = 1 makes every robot a large problem, 12 h variables)
-    pl.long_h = full_problem || !(c->max_stance > 0 && 3 * c->max_stance <= 192);
-  }
-  // decoupled path (128- and 192-row classes, exact solve, cold start): sweep kernel -> work items -> engine kernel ->
-  // (rarely) the monolithic kernel on the robots the engine handed back.  Automatic: a small batch is latency-bound --
-  // one workgroup per CU either way -- and the one-kernel path has one launch and no trip through L2 on it: measured
-  // break-even ~300 robots in the 128-row class, below 128 in the 192-row class.  Decided by the HANDLE's size, not
-  // the call's: a robot's result does not depend on the batch it is solved in -- the two paths agree to ~1e-14
-  // relative, not bit for bit
-  for (int k = pl.k0; k < pl.k1; ++k) {
-    const bool big = c->split == 2 || c->max_batch >= (kChain[k] == 2 ? 384 : 128);
-    pl.split[k] = c->split && big && (kChain[k] == 2 || kChain[k] == 3) && exact_cold;
-  }
-  return pl;
+// the handle's settings as the launch plan reads them (qmpc_plan.h): for the solve and for the allocation of the pools
+PlanSettings plan_settings(const qmpc_ctx* c) {
+  PlanSettings s;
+  s.horizon = c->horizon; s.max_batch = c->max_batch; s.max_stance = c->max_stance; s.min_stance = c->min_stance;
+  s.split = c->split; s.dense = c->dense; s.chunks = c->chunks; s.admm_mode = c->admm_mode;
+  s.order_hint = c->order_hint; s.size_order = c->size_order; s.hint_batch = c->hint_batch;
+  for (int sk = 0; sk < 3; ++sk) s.wk_cap[sk] = c->wk_cap[sk];
+  s.has_ws = c->ws != nullptr; s.has_evflags = c->d_evflags != nullptr;
+  return s;
 }
 
-// one pool of work items: sk 0 = 128-row class, 1 = 192-row class, 2 = large problems (448-row items)
+// the kernels' occupancy numbers (cached by the kernels' translation units after the first question)
+PlanResident plan_resident() {
+  PlanResident r;
+  for (const int cls : {1, 2, 3, 4, 6}) r.blocks[cls] = qmpc_resident_blocks(cls);
+  for (const int cls : {2, 3}) r.sweep[cls] = qmpc_resident_sweep(cls);
+  for (const int cls : {2, 3, 5}) r.engine[cls] = qmpc_engine_resident(cls);
+  return r;
+}
+
+// one pool of work items (qmpc_plan.h: kItems)
 int ensure_items(qmpc_ctx* c, int sk) {
   if (c->wk_cap[sk] > 0) return QMPC_OK;  // (set last: a pool counts as present only when ALL its arrays are)
-  static const int lim[3] = {QMPC_ITEMS_C2, QMPC_ITEMS_C3, QMPC_ITEMS_BIG};
-  const int rb = sk == 0 ? 2 : (sk == 1 ? 3 : 5);
-  const size_t ld = item_ld(sk);
-  const size_t cap = (size_t)(c->max_batch < lim[sk] ? c->max_batch : lim[sk]);
+  const size_t ld = kItems[sk].ld;
+  const size_t cap = (size_t)(c->max_batch < kItems[sk].limit ? c->max_batch : kItems[sk].limit);
   // (the engine grid never exceeds the resident workgroups: slice = blockIdx.x)
-  size_t wgs = (size_t)qmpc_engine_resident(rb);
+  size_t wgs = (size_t)qmpc_engine_resident(kItems[sk].cls);
   if (wgs == 0 || wgs > cap) wgs = cap;
-  const size_t ev = sk == 0 ? 128 + 64 : (sk == 1 ? 192 + 128 : QMPC_BIG_LD + 192);
   // all or nothing: an allocation that fails half-way (the pools are up to 1.5 GiB) must not leave a pool that LOOKS
   // present -- the next solve would divide by wk_cap == 0 or launch on null arrays
   hipError_t e = hipMalloc(&c->d_wk_hinv[sk], sizeof(double) * cap * ld * ld);
   if (e == hipSuccess) e = hipMalloc(&c->d_wk_xu[sk], sizeof(double) * cap * ld);
   if (e == hipSuccess) e = hipMalloc(&c->d_wk_hdr[sk], sizeof(QmpcWorkHdr) * cap);
   if (e == hipSuccess) e = hipMalloc(&c->d_wk_order[sk], sizeof(int) * QMPC_ORDER_BUCKETS * cap);
-  if (e == hipSuccess) e = hipMalloc(&c->d_wk_ovf[sk], sizeof(double) * wgs * QMPC_ENGINE_OVF_EVENTS * ev);
+  if (e == hipSuccess) e = hipMalloc(&c->d_wk_ovf[sk], sizeof(double) * wgs * QMPC_ENGINE_OVF_EVENTS * kItems[sk].ev_doubles);
   if (e != hipSuccess) {
     if (c->d_wk_hinv[sk]) hipFree(c->d_wk_hinv[sk]);
     if (c->d_wk_xu[sk]) hipFree(c->d_wk_xu[sk]);
@@ -788,29 +742,18 @@ int ensure_items(qmpc_ctx* c, int sk) {
 int ensure_pools(qmpc_ctx* c) {
   if (!c->is_setup) return QMPC_OK;
   DeviceGuard g(c->device);
-  // the UNION of the plans a solve on this handle can make: the exact solve, and -- when the JCQP alternate is selected --
-  // its own plan (use_jcqp = 1 makes every robot of a long horizon a large problem whatever the stance hint says)
-  const int modes[2] = {0, c->admm_mode};
-  for (int m = 0; m < (c->admm_mode ? 2 : 1); ++m) {
-    const ClassPlan pl = plan_classes(c, modes[m], false);
-    for (int k = pl.k0; k < pl.k1; ++k)
-      if (pl.split[k])
-        if (const int rc = ensure_items(c, kChain[k] == 2 ? 0 : 1)) return rc;
-    if (pl.long_h)
-      if (const int rc = ensure_items(c, 2)) return rc;
-  }
+  const unsigned pools = plan_pools(plan_settings(c));  // (the union of the plans a solve on this handle can make)
+  for (int sk = 0; sk < 3; ++sk)
+    if (pools >> sk & 1u)
+      if (const int rc = ensure_items(c, sk)) return rc;
   return QMPC_OK;
 }
 
-// one solve: inputs either as the record (`in`) or as the controller command (`cmd`, record built in stage 0).
-// due_list / due_count (internal, device-resident, command mode only; nullptr: every robot of the batch): the dense list
-// of the robots this call solves and its length, both written on the device by work enqueued before the call (the
-// batched controller's per-robot schedule).  A robot that is not listed is not scheduled at all: the first class of
-// the chain maps its workgroups to robots through the list and those beyond the device-side count leave at once, as
-// the later classes do with theirs, so the robot runs no QP, reaches no later list, no engine and no overflow slice, and
-// none of its outputs or command rows is written.
-int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command* cmd, const qmpc_outputs* out,
-               float* f_ff, void* stream_, const int* due_list = nullptr, int* due_count = nullptr) {
+// everything that can refuse a solve call, BEFORE the call counter moves: the counter sets ping-pong between calls and
+// each call's first kernel zeroes the NEXT call's set, so a call that took a set without launching would leave the
+// following call on counters nobody cleared.  (batch == 0: nothing to solve, whatever else the call says)
+int check_solve_call(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command* cmd, const qmpc_outputs* out,
+                     const int* due_list, const int* due_count) {
   if (!c || (!in && !cmd) || !out) return QMPC_ERR_ARG;
   if ((due_list != nullptr) != (due_count != nullptr) || (due_list && !cmd)) return QMPC_ERR_ARG;
   if (!c->is_setup) return QMPC_ERR_STATE;
@@ -825,21 +768,22 @@ int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command
   } else if (!command_ok(cmd)) {
     return QMPC_ERR_ARG;
   }
-  hipStream_t stream = (hipStream_t)stream_;
-  DeviceGuard g(c->device);
-  const int h = c->horizon;
-  const bool capturing = is_capturing(stream);
-  if (const int rc = order_after_previous(c, stream)) return rc;
-  if (c->device_error && !capturing) {
-    // ADVICE r5: the previous call (or set-up step) of this handle failed on the device: whatever its kernels left in the
-    // recycled-slice flags and the per-CU placement words is void.  Re-armed with the fill kernel (no memset node: they
-    // replay wrongly when captured, and this path must not differ from the normal one in kind)
-    if (c->d_ovflags && c->ov_nslice > 0) HIP_TRY(c, fill_ints(c->d_ovflags, c->ov_nslice_alloc, 0, stream));
-    c->device_error = false;
-  }
+  const unsigned pools = plan_pools(plan_classes(plan_settings(c), in ? c->admm_mode : 0, c->ws != nullptr));
+  for (int sk = 0; sk < 3; ++sk)
+    if ((pools >> sk & 1u) && c->wk_cap[sk] <= 0) {
+      c->err = sk == 2 ? "large-problem pool missing (qmpc_setup / qmpc_reserve allocate it)"
+                       : "work-item pool missing (qmpc_setup / qmpc_reserve allocate it)";
+      return QMPC_ERR_STATE;
+    }
+  return QMPC_OK;
+}
 
+// the kernel parameter block of a call, but for what differs from launch to launch (lists, counters, work items, order)
+QmpcParams bind_params(const qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command* cmd,
+                       const qmpc_outputs* out, float* f_ff, bool capturing) {
   QmpcParams P;
   std::memset(&P, 0, sizeof(P));
+  const int h = c->horizon;
   if (in) {
     bind_record(P, *in);
   } else {
@@ -859,305 +803,121 @@ int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command
   const float mi = 1.f / (float)c->mu;
   P.mu_inv = (double)mi;
   P.inv_fr_norm = 1.0 / std::sqrt(P.mu_inv * P.mu_inv + 1.0);
-  P.f_max = c->f_max;
-  P.mass = c->mass;
-  for (int k = 0; k < 3; ++k) P.ibody[k] = c->ibody[k];
-  P.inv_mass = 1.0 / c->mass;
-  for (int k = 0; k < 3; ++k) P.inv_ibody[k] = 1.0 / c->ibody[k];
-  P.gravity = c->gravity;
-  P.model = c->model;
-  P.coef = c->d_tables;
-  P.ctab = c->d_tables + 3 * h;
-  P.max_iter = c->max_iter;
-  P.tol = c->tol;
-  P.ws = c->ws;
-  P.ws_shift = c->ws_shift;
+  P.f_max = c->f_max; P.mass = c->mass; P.inv_mass = 1.0 / c->mass; P.gravity = c->gravity; P.model = c->model;
+  for (int k = 0; k < 3; ++k) P.ibody[k] = c->ibody[k], P.inv_ibody[k] = 1.0 / c->ibody[k];
+  P.coef = c->d_tables; P.ctab = c->d_tables + 3 * h;
+  P.max_iter = c->max_iter; P.tol = c->tol;
+  P.ws = c->ws; P.ws_shift = c->ws_shift;
   // selective warm start: the selection reads the previous call's iteration counts, which exist only while the order hint is on,
   // the call is eager (not captured) and the previous call had this batch size; without them NOBODY qualifies (every robot
   // starts cold) -- eager and captured calls, first and later calls behave alike
   P.ws_min_iters = (c->ws_min_iters > 0 && !(c->order_hint && !capturing && c->hint_batch == batch)) ? 0x7fffffff : c->ws_min_iters;
   if (c->admm_mode && in) {  // (record mode only: the command mode always solves exactly)
-    P.admm_mode = c->admm_mode;
-    P.admm_max_iter = c->admm_max_iter;
-    P.admm_rho = c->admm_rho;
-    P.admm_sigma = c->admm_sigma;
-    P.admm_alpha = c->admm_alpha;
-    P.admm_term = c->admm_term;
+    P.admm_mode = c->admm_mode; P.admm_max_iter = c->admm_max_iter;
+    P.admm_rho = c->admm_rho; P.admm_sigma = c->admm_sigma; P.admm_alpha = c->admm_alpha; P.admm_term = c->admm_term;
   }
-  P.dbg_H = c->dbg_H;
-  P.dbg_g = c->dbg_g;
-  P.dbg_aux = c->dbg_aux;
-  P.dbg_clk = c->dbg_clk;
+  P.dbg_H = c->dbg_H; P.dbg_g = c->dbg_g; P.dbg_aux = c->dbg_aux; P.dbg_clk = c->dbg_clk;
   P.hint_iters = (c->order_hint && !capturing) ? c->d_hint_iters : nullptr;
   // (selective warm start without usable counts -- hint off, captured call: the kernel compares the count array against a
   //  threshold nobody reaches, so it needs the array; the counts it leaves there are not used while the hint is off)
   if (c->ws && c->ws_min_iters > 0 && !P.hint_iters) P.hint_iters = c->d_hint_iters;
-  P.cu_slots = c->d_cu_slots;
-  P.bal_debug = c->bal_debug;
-
-  P.ovpool = c->d_ovpool;
-  P.ov_nslice = c->ov_nslice;
-  P.ov_flags = c->d_ovflags;
-  P.ov_spin = c->ov_spin;
-  P.evpool = c->d_evpool;
-  P.evflags = c->d_evflags;
-  P.ev_nslot = c->ev_nslot;
+  P.cu_slots = c->d_cu_slots; P.bal_debug = c->bal_debug;
+  P.ovpool = c->d_ovpool; P.ov_nslice = c->ov_nslice; P.ov_flags = c->d_ovflags; P.ov_spin = c->ov_spin;
+  P.evpool = c->d_evpool; P.evflags = c->d_evflags; P.ev_nslot = c->ev_nslot;
   P.ev_spin = c->dbg_pool_busy ? 4 : (1 << 16);
+  return P;
+}
 
-  // ---- the launch plan, and everything that can refuse the call, BEFORE the call counter moves: the counter sets
-  // ping-pong between calls and each call's first kernel zeroes the NEXT call's set, so a call that took a set without
-  // launching would leave the following call on counters nobody cleared
-  const ClassPlan pl = plan_classes(c, P.admm_mode, P.ws != nullptr);
-  for (int k = pl.k0; k < pl.k1; ++k)
-    if (pl.split[k] && c->wk_cap[kChain[k] == 2 ? 0 : 1] <= 0) {
-      c->err = "work-item pool missing (qmpc_setup / qmpc_reserve allocate it)";
-      return QMPC_ERR_STATE;
+// The plan's launches, in order, on the caller's stream.  Every launch gets a COPY of the bound parameter block with its
+// own lists, counters, work items and ordering fields resolved to the handle's arrays: nothing is shared between
+// launches, so nothing has to be reset after one.
+int enqueue(qmpc_ctx* c, const QmpcParams& bound, const SolvePlan& sp, const int* due_list, int* due_count,
+            hipStream_t stream) {
+  int* const cnt = c->d_counts + QMPC_COUNTERS * sp.set;  // this call's counters
+  int* const cnt_next = sp.set == 2 ? nullptr : c->d_counts + QMPC_COUNTERS * (sp.set ^ 1);  // the next eager call's
+  const auto counter = [&](int i) { return i == kNoCounter ? nullptr : (i == kDueCounter ? due_count : cnt + i); };
+  const auto list = [&](const ListRef& r) -> const int* {
+    switch (r.kind) {
+      case LIST_SLOT: return c->d_lists + (size_t)r.idx * c->max_batch;
+      case LIST_DUE: return due_list;
+      case LIST_HANDBACK: return c->d_fb_lists + (size_t)r.idx * c->max_batch;
+      default: return nullptr;
     }
-  if (pl.long_h && c->wk_cap[2] <= 0) {
-    c->err = "large-problem pool missing (qmpc_setup / qmpc_reserve allocate it)";
-    return QMPC_ERR_STATE;
-  }
-  int* cnt;       // this call's counters
-  int* cnt_next;  // the set this call's first kernel clears (the next call's)
-  if (capturing || due_list) {
-    // (a due-list call too: its first launch is a list consumer, and those do not clear the next call's set)
-    // a call captured into a hipGraph is replayed with the SAME kernel arguments every time: it cannot take part in
-    // the ping-pong (its set would be dirty from the previous replay).  Captured calls use a set of their own, cleared
-    // by a small kernel node in front of the call's kernels; the eager calls' two sets are not touched
-    cnt = c->d_counts + QMPC_COUNTERS * 2;
-    cnt_next = nullptr;
-    HIP_TRY(c, fill_ints(cnt, QMPC_COUNTERS, 0, stream));
-  } else {
-    const unsigned set = c->call_no & 1u;
-    c->call_no++;
-    cnt = c->d_counts + QMPC_COUNTERS * set;
-    cnt_next = c->d_counts + QMPC_COUNTERS * (set ^ 1u);
-  }
-  P.ov_count = cnt + QMPC_CNT_OV;                         // slices of the overflow pool handed out in this call
-  bool first = true;                            // the next launch is the first of the call: it carries clear_counts
-
-  // one item class of the decoupled path (sk 0 / 1: sweep kernel of class rb; sk 2: the large-problem producer): the
-  // robots [0, batch) -- or the entries of `list` -- in consecutive chunks of at most wk_cap[sk], every chunk a
-  // producer launch and an engine launch on the caller's stream, the pool reused from chunk to chunk
-  auto run_items = [&](const QmpcParams& base, int sk, int rb, const int* list, int* count) -> int {
-    QmpcParams A = base;
-    A.wk_hinv = c->d_wk_hinv[sk];
-    A.wk_xu = c->d_wk_xu[sk];
-    A.wk_hdr = c->d_wk_hdr[sk];
-    A.wk_order = c->d_wk_order[sk];
-    A.wk_ovf = c->d_wk_ovf[sk];
-    A.wk_ld = (int)item_ld(sk);
-    A.wk_cap = c->wk_cap[sk];
-    A.wk_base = 0;
-    A.wk_kev = c->dbg_engine_events > 0 ? c->dbg_engine_events : (1 << 20);
-    A.fb_list = c->d_fb_lists + (size_t)sk * c->max_batch;
-    A.fb_count = cnt + QMPC_CNT_FB + sk;
-    A.list = list;
-    A.count = count;
-    int nch = (batch + c->wk_cap[sk] - 1) / c->wk_cap[sk];
-    if (c->chunks > nch) nch = c->chunks < batch ? c->chunks : batch;
-    const int per = (batch + nch - 1) / nch;  // (<= wk_cap[sk])
-    for (int ch = 0; ch < nch; ++ch) {
-      const int lo = ch * per, hi = (lo + per < batch) ? lo + per : batch;
-      if (lo >= hi) break;
-      int* grp = cnt + QMPC_CNT_GRP(sk, ch & 1);
-      A.wk_count = grp;
-      A.wk_qhead = grp + 1;
-      A.qhead = list ? grp + 2 : nullptr;
-      A.wk_bucket = grp + 8;
-      A.wk_zero = nullptr;
-      A.rid0 = lo;
-      A.list_hi = hi;
-      A.clear_counts = first ? cnt_next : nullptr;
-      first = false;
-      int grid = hi - lo;
-      if (list || sk == 2) {
-        const int res = sk == 2 ? qmpc_resident_blocks(3) : qmpc_resident_sweep(rb);  // (the large-problem producer has the 192-row class's footprint)
-        if (res > 0 && res < grid) grid = res;
-      }
-      if (sk == 2) HIP_TRY(c, qmpc_big_launch(&A, grid, stream));
-      else HIP_TRY(c, qmpc_launch_sweep(rb, &A, grid, stream));
-      QmpcParams B = A;  // the engine: one robot per workgroup, the chunk's items as a queue
-      B.list = nullptr; B.count = nullptr; B.qhead = nullptr; B.clear_counts = nullptr;
-      B.next_list = nullptr; B.next_count = nullptr;
-      B.wk_zero = (ch + 1 < nch) ? cnt + QMPC_CNT_GRP(sk, (ch + 1) & 1) : nullptr;
-      int gb = hi - lo;
-      {
-        const int res = qmpc_engine_resident(sk == 2 ? 5 : rb);
-        if (res > 0 && res < gb) gb = res;
-      }
-      if (sk == 2 && base.admm_mode) {
-        // JCQP alternate on the large problems: the producer left M^-1 and the gradient; the ADMM kernel consumes the items
-        gb = (hi - lo) < 2048 ? (hi - lo) : 2048;
-        HIP_TRY(c, qmpc_admm_big_launch(&B, gb, stream));
-      } else {
-        HIP_TRY(c, qmpc_engine_launch(sk == 2 ? 5 : rb, &B, gb, stream));
-      }
-    }
-    if (sk == 2 && base.admm_mode) return QMPC_OK;  // (the ADMM hands nothing back)
-    // robots handed back (event capacity exceeded, lost definiteness): the monolithic kernel, list-consuming.  The
-    // large problems have no class to fall back to: the 192-row class's stage 0 REPORTS them (QMPC_ST_WS_FULL)
-    QmpcParams F = base;
-    F.list = A.fb_list; F.count = A.fb_count; F.qhead = cnt + QMPC_CNT_FBQ + sk; F.clear_counts = nullptr;
-    F.list_hi = 0x7fffffff;
-    F.rid0 = 0;
-    F.next_list = nullptr; F.next_count = nullptr;
-    F.status_or = sk == 2 ? 0 : QMPC_DEV_ST_FALLBACK;
-    const int frb = sk == 0 ? 2 : 3;
-    if (frb == 3 && c->d_evflags)
-      HIP_TRY(c, fill_ints(c->d_evflags, c->ev_nslot, c->dbg_pool_busy ? 1 : 0, stream));
-    int gf = batch;
-    {
-      const int res = qmpc_resident_blocks(frb);
-      if (res > 0 && res < gf) gf = res;
-    }
-    HIP_TRY(c, qmpc_launch(frb, &F, gf, stream));
-    return QMPC_OK;
   };
-
-  // size classes by padded rows: 64 (kernel class 1), 96 (class 4), 128 (class 2), 192 (class 3);
-  // n_r = 3 * stance foot-steps.  The first class is launched over the whole batch; a robot that
-  // does not fit appends itself to the list of the next one.
-  for (int k = pl.k0; k < pl.k1; ++k) {
-    const bool listed = k > pl.k0 || due_list;
-    P.list = listed ? c->d_lists + (size_t)(k - 1) * c->max_batch : nullptr;
-    P.count = listed ? cnt + (k - 1) : nullptr;
-    P.qhead = listed ? cnt + 4 + (k - 1) : nullptr;
-    if (k == pl.k0 && due_list) {  // the first class takes the caller's list instead of the whole batch
-      P.list = due_list;
-      P.count = due_count;
-      P.qhead = cnt + QMPC_CNT_DUEQ;
-    }
-    const bool more = k + 1 < pl.k1;
-    P.next_list = more ? c->d_lists + (size_t)k * c->max_batch : nullptr;
-    P.next_count = more ? cnt + k : nullptr;
-    if (pl.long_h && kChain[k] == 3) {  // robots beyond 192 rows go on to the large-problem producer
-      P.next_list = c->d_lists + (size_t)3 * c->max_batch;
-      P.next_count = cnt + QMPC_CNT_BIGLIST;
-    }
-    if (pl.split[k]) {
-      if (const int rc = run_items(P, kChain[k] == 2 ? 0 : 1, kChain[k], P.list, P.count)) return rc;
+  for (const Launch& L : sp.launches) {
+    if (L.kind <= FILL_PRIO) {  // (FILL_EVFLAGS: no kernel of this handle is in flight on another stream -- ordered by solve_impl)
+      if (L.kind == FILL_COUNTERS) HIP_TRY(c, fill_ints(cnt, QMPC_COUNTERS, 0, stream));
+      else if (L.kind == FILL_EVFLAGS) HIP_TRY(c, fill_ints(c->d_evflags, c->ev_nslot, c->dbg_pool_busy ? 1 : 0, stream));
+      else HIP_TRY(c, fill_ints(reinterpret_cast<int*>(c->d_prio_cu), 2 * 2048, 0, stream));
       continue;
     }
-    // the first class of the chain: one workgroup per robot; the later ones: one per resident slot, the list
-    // is consumed as a queue (no workgroup is dispatched only to find its list entry missing)
-    if (kChain[k] == 3 && c->d_evflags)  // no kernel of this handle is in flight on another stream (ordered above)
-      HIP_TRY(c, fill_ints(c->d_evflags, c->ev_nslot, c->dbg_pool_busy ? 1 : 0, stream));
-    P.clear_counts = first ? cnt_next : nullptr;
-    first = false;
-    int grid = batch;
-    if (listed) {
-      const int res = qmpc_resident_blocks(kChain[k]);
-      if (res > 0 && res < grid) grid = res;
+    QmpcParams P = bound;
+    P.ov_count = cnt + QMPC_CNT_OV;  // slices of the overflow pool handed out in this call
+    P.list = list(L.list); P.count = counter(L.count); P.qhead = counter(L.qhead);
+    P.next_list = L.next.kind == LIST_SLOT ? c->d_lists + (size_t)L.next.idx * c->max_batch : nullptr;
+    P.next_count = counter(L.next_count);
+    P.clear_counts = L.clear_counts ? cnt_next : nullptr;
+    P.status_or = L.status_or; P.rid0 = L.rid0; P.list_hi = L.list_hi;
+    if (L.kind != SOLVE) {  // the work items of pool sk, the counter group of the chunk
+      const int sk = L.sk;
+      int* const grp = cnt + QMPC_CNT_GRP(sk, L.grp);
+      P.wk_hinv = c->d_wk_hinv[sk]; P.wk_xu = c->d_wk_xu[sk]; P.wk_hdr = c->d_wk_hdr[sk];
+      P.wk_order = c->d_wk_order[sk]; P.wk_ovf = c->d_wk_ovf[sk];
+      P.wk_ld = kItems[sk].ld; P.wk_cap = c->wk_cap[sk];
+      P.wk_kev = c->dbg_engine_events > 0 ? c->dbg_engine_events : (1 << 20);
+      P.fb_list = c->d_fb_lists + (size_t)sk * c->max_batch; P.fb_count = cnt + QMPC_CNT_FB + sk;
+      P.wk_count = grp; P.wk_qhead = grp + 1; P.wk_bucket = grp + 8;
+      P.wk_zero = L.wk_zero ? cnt + QMPC_CNT_GRP(sk, L.grp ^ 1) : nullptr;
     }
-    // the 64-row class alone in the chain (the stance hint says every robot fits it), on a handle made for large batches:
-    // its five-workgroups-per-CU instantiation (same arithmetic, bit-identical results: tests) -- a launch of several rounds
-    // is bound by instruction issue, and the fifth wave per SIMD fills what four leave (trot: +3.5 % at 2048 robots, +8 % at 4096, +14 % from
-    // 8192 on: 3.76e7 -> 4.30e7 QP/s at 16384; mixed gaits +3 / +7 / +11 %: tools/dense_threshold.py); one round of workgroups
-    // (batch 1024) is bound by its slowest robot and loses 1 - 11 % to the 96-VGPR code.  By the
-    // HANDLE's size, never the call's.  Not for chains with larger classes: their robots iterate long, and 16 events in LDS
-    // instead of 28 send a thousand of them to the overflow pool (configs[4]: -40 %)
-    int kcls = kChain[k];
-    // Chains with larger classes behind it (configs[4]: random contact tables): their robots iterate longer, and 16 events
-    // in LDS instead of 28 send about one in eight of them to the overflow pool; the launch still gains (configs[4] 492 -> 482 us
-    // per 8192 robots, +2 %) as long as every one of them finds a slice there -- which, the slices being RECYCLED within a call
-    // since round 5 (a flag per slice, released when its robot finishes: the need is bounded by the robots in flight), holds for
-    // any batch size.  So this choice, too, is made by the HANDLE's size alone (until round 4 it also looked at the call's:
-    // batch <= 4 x the slices)
-    if (kcls == 1 && pl.k1 - pl.k0 > 1 && !pl.long_h && c->dense == 1 && c->max_batch >= 2048) kcls = 6;
-    if (kcls == 1 && pl.k1 - pl.k0 == 1 && !pl.long_h && (c->dense == 2 || (c->dense == 1 && c->max_batch >= 2048))) kcls = 6;
-    // (a due list in front of a 64-row class: qmpc_solve_due_kernel, one workgroup per list place -- the grid is the batch, and
-    //  the workgroups beyond the device-side count leave at once; in front of any other class: that class's list consumer)
-    if (k == pl.k0 && due_list && (kcls == 1 || kcls == 6)) grid = batch;
-    // order hint: the first class of the chain, launched over more robots than it has resident workgroups (several rounds:
-    // the launch ends with whichever hard robot started last), takes the robots in the order of their iteration counts in the
-    // previous call -- the same robots one MPC cycle earlier -- longest first.  Results do not depend on the order.
-    // A launch of ONE round (the order cannot matter) uses the counts differently: the robots the previous call found hard
-    // keep the highest issue priority through their sweep (qmpc_device.h: hint_hard) -- batch 1024, trot: 2.42e7 -> 2.75e7 QP/s.
-    // (Only there: in a launch of many rounds it costs 3 %, measured at 16384 robots.)
-    P.hint_hard = 0;
-    bool use_hint_keys = false;
-    if (!listed && c->order_hint && !capturing && !P.admm_mode) {
-      if (batch > qmpc_resident_blocks(kcls)) {
-        // the permutation is built inside the launch (below), keys = the previous call's counts
-        if (c->hint_batch == batch) use_hint_keys = true;
-      } else if (2 * batch > qmpc_resident_blocks(kcls)) {  // (workgroups share CUs: below that priority has nobody to act on)
-        // the largest count of the previous one-round call / of this one / cleared for the next: three slots in rotation
-        const unsigned hc = c->hint_call++;
-        P.hint_max_r = c->d_hint_max + (hc + 2) % 3;
-        P.hint_max_w = c->d_hint_max + hc % 3;
-        P.hint_max_z = c->d_hint_max + (hc + 1) % 3;
-        if (c->hint_batch == batch) P.hint_hard = c->hint_hard;
-      }
+    if (L.hint_max_w != kNoCounter) {
+      P.hint_max_r = c->d_hint_max + L.hint_max_r; P.hint_max_w = c->d_hint_max + L.hint_max_w;
+      P.hint_max_z = c->d_hint_max + L.hint_max_z; P.hint_hard = L.hint_hard;
     }
-    // size order: no usable hint, several rounds, contact tables in memory (record mode) and 8-byte aligned.  The first round keeps
-    // robot = workgroup index (its workgroups start before anything can be known); the builders (the first workgroups, one
-    // segment of the rest each) need a few microseconds, for which the workgroups that follow robots only handed on may have to wait
-    // (measured: no loss on configs[4], where a third of the first round is handed on)
-    P.so_order = nullptr;
-    const bool by_size = c->size_order && !cmd && P.gait && ((uintptr_t)P.gait & 7u) == 0;
-    if (!listed && !capturing && !P.admm_mode && (use_hint_keys || by_size)) {
-      const int res = qmpc_resident_blocks(kcls);
-      if (res > 0 && batch > res) {
-        // (the unsorted head beyond the first round: none by size -- measured 0 / 15 / 30 / 50 % of a round: 0 is best or equal
-        //  everywhere, +2.6 % on configs[2] --, half a round by the hint's counts: 0 / 25 / 50 %: 3.92e7 / 3.96e7 / 4.05e7 on
-        //  configs[2] with exact counts, equal elsewhere -- robots of one COUNT side by side run their engine phases together)
-        const int head = (int)((long long)res * (use_hint_keys ? c->so_first_pct_hint : c->so_first_pct) / 100);
-        const int half = (batch - res) / 2 < head ? (batch - res) / 2 : head;
-        P.so_first = (res + half + 7) & ~7;
-        // (a launch of many rounds: only its last five are ordered -- a robot lasts three or four rounds at most, so nothing that
-        //  starts earlier can end the launch, and every reader pays a memory round trip for its entry: trot, 16384 robots, -3.9 %
-        //  with everything ordered)
-        if (batch - c->so_tail_rounds * res > P.so_first) P.so_first = (batch - c->so_tail_rounds * res + 7) & ~7;
-        const int n = batch - P.so_first;
-        // (next to nothing to order: the builders and the sixteen first-round places per segment cost more than the order gives)
-        if (c->so_min_div * n >= res && 17 * 8 * ((n + 8 * 4080 - 1) / (8 * 4080)) <= res) {
-          // strided segments of at most 4096 robots (QMPC_SO_SEG of qmpc_kernels.hip: the builder's LDS scratch)
-          // (a multiple of 8, and so_first too: place b of segment j has b % 8 == j % 8 -- readers and builder on one XCD)
-          // (QMPC_SO_HEAD = 16 places of the first round per segment on top: 17 nseg workgroups in front of so_first)
-          P.so_nseg = 8 * ((n + 8 * 4080 - 1) / (8 * 4080));
-          P.so_order = c->d_so_order;
-          P.so_far = c->d_so_order + c->max_batch;
-          P.so_tag = ++c->so_call;
-          if (P.so_tag == 0) P.so_tag = ++c->so_call;  // (0 is what fresh memory holds)
-          P.so_maxfit = kRows[k] / 3;
-          P.so_hint = use_hint_keys ? c->d_hint_iters : nullptr;
-        }
-      }
+    if (L.so_tag) {
+      P.so_order = c->d_so_order; P.so_far = c->d_so_order + c->max_batch;
+      P.so_hint = L.so_keys_from_hint ? c->d_hint_iters : nullptr;
+      P.so_tag = L.so_tag; P.so_first = L.so_first; P.so_nseg = L.so_nseg; P.so_maxfit = L.so_maxfit;
     }
-    // ONE round, full CUs, no usable hint: the sweep's issue priority is staged per CU by the robots' scores (one atomic maximum on
-    // the CU's word: qmpc_kernels.hip, stage 0) -- same conditions as the size order (record mode: the proxy reads the record)
-    P.prio_cu = nullptr;
-    if (!listed && !capturing && !P.admm_mode && c->size_order && !cmd && P.gait && ((uintptr_t)P.gait & 3u) == 0 && P.hint_hard <= 0) {
-      const int res = qmpc_resident_blocks(kcls);
-      // (only where the CUs are full: at three workgroups per CU -- 768 robots on 1024 slots -- the staging costs 3 %)
-      if (res > 0 && batch <= res && 8 * batch > 7 * res) {
-        P.prio_cu = c->d_prio_cu;
-        P.prio_tag = ++c->prio_call;
-        if (P.prio_tag == 0) {  // (the call number wrapped: the words start again)
-          HIP_TRY(c, fill_ints(reinterpret_cast<int*>(c->d_prio_cu), 2 * 2048, 0, stream));
-          P.prio_tag = ++c->prio_call;
-        }
-      }
+    if (L.prio_tag) P.prio_cu = c->d_prio_cu, P.prio_tag = L.prio_tag;
+    switch (L.kind) {
+      case SOLVE: HIP_TRY(c, qmpc_launch(L.cls, &P, L.grid, stream)); break;
+      case SWEEP: HIP_TRY(c, qmpc_launch_sweep(L.cls, &P, L.grid, stream)); break;
+      case BIG_PRODUCER: HIP_TRY(c, qmpc_big_launch(&P, L.grid, stream)); break;
+      case ENGINE: HIP_TRY(c, qmpc_engine_launch(L.cls, &P, L.grid, stream)); break;
+      default: HIP_TRY(c, qmpc_admm_big_launch(&P, L.grid, stream)); break;
     }
-    HIP_TRY(c, qmpc_launch(kcls, &P, grid, stream));
-    P.prio_cu = nullptr;
-    P.so_order = nullptr;
-    P.hint_hard = 0;
-    P.hint_max_z = nullptr;
-    P.hint_max_w = nullptr;  // (the later classes of a chain are queues of several rounds)
   }
-  if (c->order_hint && !capturing && !P.admm_mode && !due_list) c->hint_batch = batch;  // (a due list leaves counts for its robots only)
-  if (pl.long_h) {
-    // ---- the large problems (192 < n_r <= 432: all feet down beyond 16 segments, a trot beyond 32): H in global memory,
-    // block sweep, the seven-block engine; what that engine cannot hold is REPORTED.  Normally the list is empty: launches
-    // that find nothing to do
-    QmpcParams A = P;
-    A.next_list = nullptr; A.next_count = nullptr;
-    A.status_or = 0;
-    A.clear_counts = nullptr;
-    if (const int rc = run_items(A, 2, 3, c->d_lists + (size_t)3 * c->max_batch, cnt + QMPC_CNT_BIGLIST)) return rc;
+  return QMPC_OK;
+}
+
+// one solve: inputs either as the record (`in`) or as the controller command (`cmd`, record built in stage 0).
+// due_list / due_count (internal, device-resident, command mode only; nullptr: every robot of the batch): the dense list
+// of the robots this call solves and its length, both written on the device by work enqueued before the call (the
+// batched controller's per-robot schedule).  A robot that is not listed is not scheduled at all: the first class of
+// the chain maps its workgroups to robots through the list and those beyond the device-side count leave at once, as
+// the later classes do with theirs, so the robot runs no QP, reaches no later list, no engine and no overflow slice, and
+// none of its outputs or command rows is written.
+// Check, bind, plan (qmpc_plan.h: a value, no device involved), enqueue.
+int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command* cmd, const qmpc_outputs* out,
+               float* f_ff, void* stream_, const int* due_list = nullptr, int* due_count = nullptr) {
+  if (const int rc = check_solve_call(c, batch, in, cmd, out, due_list, due_count)) return rc;
+  if (batch == 0) return QMPC_OK;
+  hipStream_t stream = (hipStream_t)stream_;
+  DeviceGuard g(c->device);
+  const bool capturing = is_capturing(stream);
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  if (c->device_error && !capturing) {
+    // ADVICE r5: the previous call (or set-up step) of this handle failed on the device: whatever its kernels left in the
+    // recycled-slice flags and the per-CU placement words is void.  Re-armed with the fill kernel (no memset node: they
+    // replay wrongly when captured, and this path must not differ from the normal one in kind)
+    if (c->d_ovflags && c->ov_nslice > 0) HIP_TRY(c, fill_ints(c->d_ovflags, c->ov_nslice_alloc, 0, stream));
+    c->device_error = false;
   }
+  const QmpcParams P = bind_params(c, batch, in, cmd, out, f_ff, capturing);
+  const PlanCall call{batch, capturing, cmd != nullptr, due_list != nullptr, (unsigned)((uintptr_t)P.gait & 7u), P.admm_mode};
+  const SolvePlan sp = plan_solve(plan_settings(c), call, plan_resident(), c->ctr);
+  if (const int rc = enqueue(c, P, sp, due_list, due_count, stream)) return rc;
+  if (sp.leaves_hint) c->hint_batch = batch;
   return QMPC_OK;
 }
 
