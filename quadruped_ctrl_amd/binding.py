@@ -74,6 +74,17 @@ class CtrlView(C.Structure):
                                                                 ("batch", C.c_int), ("ticks", C.c_int)]
 
 
+# qmpc_plant_view's arrays (include/qmpc_plant.h) in declaration order: name -> (elements per robot, typestr)
+PLANT_VIEW_FIELDS = dict(p=(3, "<f8"), v=(3, "<f8"), q=(4, "<f8"), omega=(3, "<f8"), foot=(12, "<f8"), stance=(4, "<i4"),
+                         grf=(12, "<f8"), state=(16, "<f8"), motor=(24, "<f8"))
+
+
+class PlantView(C.Structure):
+    """qmpc_plant_view (include/qmpc_plant.h)."""
+    _fields_ = [(n, C.c_void_p) for n in PLANT_VIEW_FIELDS] + [("batch", C.c_int), ("substeps", C.c_int),
+                                                               ("mu_plant", C.c_double)]
+
+
 class LegCommand(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in LEG_F32] + [("kp_joint", C.c_float), ("kd_joint", C.c_float)]
 
@@ -173,8 +184,16 @@ CTRL_SIGNATURES = {
     "qmpc_ctrl_tick_state": [_P, _I, _P, _P, _P, _P],
     "qmpc_ctrl_view_get": [_P, C.POINTER(CtrlView)],
 }
+# the reduced-order plant's header (include/qmpc_plant.h), same library and ABI version
+PLANT_SIGNATURES = {
+    "qmpc_plant_init": [_P, _I, _D, _I, _P, _P],
+    "qmpc_plant_reset": [_P, _I, _P, _P, _P],
+    "qmpc_plant_step": [_P, _I, _P, _P, _P, _P],
+    "qmpc_plant_view_get": [_P, C.POINTER(PlantView)],
+}
 EXPORTS = list(SIGNATURES)
 CTRL_EXPORTS = list(CTRL_SIGNATURES)
+PLANT_EXPORTS = list(PLANT_SIGNATURES)
 
 _lib = None
 
@@ -208,7 +227,7 @@ def load_library():
                 f"{LIB_PATH} not found: build the HIP extension first "
                 "(python -c 'import __graft_entry__ as g; g.build()')")
         lib = C.CDLL(LIB_PATH)
-        for name, sig in {**SIGNATURES, **CTRL_SIGNATURES}.items():
+        for name, sig in {**SIGNATURES, **CTRL_SIGNATURES, **PLANT_SIGNATURES}.items():
             f = getattr(lib, name)
             f.argtypes, f.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
         _lib = lib
@@ -627,6 +646,7 @@ class BatchedController:
         self.mpc._check(self.lib.qmpc_ctrl_init(self.mpc.h, int(batch), float(freq), pid_c, self._s(stream)), "qmpc_ctrl_init")
         self.batch = int(batch)
         self.mpc.horizon = 14
+        self.schedule = "lockstep"
 
     def set_schedule(self, mode):
         """"lockstep" (the default after every init()) or "per_robot": each robot's own counter decides when it solves, and
@@ -634,6 +654,7 @@ class BatchedController:
         if mode not in CTRL_SCHEDULES:
             raise QmpcError(f"set_schedule: unknown mode {mode!r} (one of {sorted(CTRL_SCHEDULES)})")
         self.mpc._check(self.lib.qmpc_ctrl_set_schedule(self.mpc.h, CTRL_SCHEDULES[mode]), "qmpc_ctrl_set_schedule")
+        self.schedule = mode
 
     def set_robot_mode(self, mode):
         """set_robot_mode for the whole controller: 0 (the default after every init(): the gait picked by number, MPC
@@ -736,3 +757,100 @@ class _DeviceArray:
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False),
                                          "version": 2}
         self.owner = owner
+
+
+class BatchedPlant:
+    """The reduced-order plant of include/qmpc_plant.h for a BatchedController's robots: the MPC's single rigid body
+    with massless legs, scheduled contact, no slip, flat ground -- fp64 on the device.  step(effort) consumes what
+    ctrl.tick_state() produced (and reads the controller's contact_state / p_des / v_des) and returns the next
+    (state [B,16], motor [B,24]); tick_state -> step is a closed loop without the host (see rollout()).
+
+    Constructed FROM a controller (the plant lives in the controller's handle and is freed with it), after ctrl.init().
+    Every call only enqueues on the current stream (or `stream`).  `state` / `motor` are the plant's own read-out rows
+    (zero-copy, rewritten by init / reset / step): feed them to ctrl.tick_state directly."""
+
+    def __init__(self, ctrl):
+        self.ctrl, self.torch, self.lib, self.device = ctrl, ctrl.torch, ctrl.lib, ctrl.device
+        self.batch = None
+
+    def _xyyaw(self, xyyaw):
+        if xyyaw is None:
+            return None
+        return self.ctrl._chk(xyyaw, (self.ctrl.batch, 3), self.torch.float64, "init_xyyaw")
+
+    def init(self, mu_plant=0.4, substeps=1, init_xyyaw=None, stream=None):
+        """All robots of the controller into the initial state: body at (x, y, 0.29) with yaw from init_xyyaw [B,3]
+        float64 (zeros without), at rest, four feet under the hips on the ground, in stance."""
+        self.ctrl.mpc._check(self.lib.qmpc_plant_init(self.ctrl.mpc.h, self.ctrl.batch or 0, float(mu_plant), int(substeps),
+                                                      self._xyyaw(init_xyyaw), self.ctrl._s(stream)), "qmpc_plant_init")
+        self.batch = self.ctrl.batch
+        self._keep = init_xyyaw
+        v = self.view()
+        self.state, self.motor = v["state"], v["motor"]
+        self.effort = self.torch.zeros((self.batch, 12), dtype=self.torch.float64, device=self.device)
+
+    def reset(self, mask, init_xyyaw=None, stream=None):
+        """The initial state again for the robots where mask is set; the others keep every bit."""
+        m = mask.to(self.torch.uint8).contiguous() if mask is not None else None
+        ptr = self.ctrl._chk(m, (self.ctrl.batch,), self.torch.uint8, "mask") if m is not None else None
+        self.ctrl.mpc._check(self.lib.qmpc_plant_reset(self.ctrl.mpc.h, self.ctrl.batch or 0, ptr, self._xyyaw(init_xyyaw),
+                                                       self.ctrl._s(stream)), "qmpc_plant_reset")
+        self._keep = (m, init_xyyaw)   # (alive until the next call: the launch reads them asynchronously)
+
+    def step(self, effort, state=None, motor=None, stream=None):
+        """One control period -> (state, motor); written into the tensors given, or into the plant's own rows."""
+        if self.batch is None:
+            raise QmpcError("qmpc_plant_step before init()")
+        state = self.state if state is None else state
+        motor = self.motor if motor is None else motor
+        e = self.ctrl._chk(effort, (self.batch, 12), self.torch.float64, "effort")
+        a = self.ctrl._chk(state, (self.batch, 16), self.torch.float64, "state")
+        b = self.ctrl._chk(motor, (self.batch, 24), self.torch.float64, "motor")
+        self.ctrl.mpc._check(self.lib.qmpc_plant_step(self.ctrl.mpc.h, self.batch, e, a, b, self.ctrl._s(stream)),
+                             "qmpc_plant_step")
+        return state, motor
+
+    def view(self):
+        """qmpc_plant_view_get as zero-copy device tensors (p, v, q, omega, foot, stance, grf, state, motor: [B, n],
+        float64, stance int32) that alias the plant's state, like BatchedController.view(); plus batch, substeps,
+        mu_plant.  Read-only by contract."""
+        v = PlantView()
+        self.ctrl.mpc._check(self.lib.qmpc_plant_view_get(self.ctrl.mpc.h, C.byref(v)), "qmpc_plant_view_get")
+        res = {k: self.torch.as_tensor(_DeviceArray(getattr(v, k), (v.batch, n), ts, self.ctrl), device=self.device)
+               for k, (n, ts) in PLANT_VIEW_FIELDS.items()}
+        res["batch"], res["substeps"], res["mu_plant"] = v.batch, v.substeps, v.mu_plant
+        return res
+
+
+def rollout(ctrl, plant, ticks, graph=False):
+    """`ticks` closed-loop ticks, ctrl.tick_state(plant.state, plant.motor) -> plant.step(effort), on the current
+    stream, continuing from wherever the pair stands.  graph=True captures the block of `ticks` ticks into a
+    torch.cuda.graph (on a side stream) and replays it once; the graph is returned for further replays, each of which
+    runs the block again.  With the lockstep schedule a captured block must hold a multiple of 13 ticks (the host
+    decides the MPC ticks from its own count, which replays do not advance: include/qmpc_ctrl.h) -- refused otherwise.
+    -> dict(effort, state, motor, graph): the plant's own tensors, as the last tick left them."""
+    torch = ctrl.torch
+    ticks = int(ticks)
+    if ticks < 1:
+        raise QmpcError("rollout: ticks must be at least 1")
+
+    def block():
+        for _ in range(ticks):
+            ctrl.tick_state(plant.state, plant.motor, plant.effort)
+            plant.step(plant.effort)
+
+    g = None
+    if not graph:
+        block()
+    else:
+        if ctrl.schedule == "lockstep" and ticks % 13 != 0:
+            raise QmpcError(f"rollout: a captured block holds a multiple of 13 ticks in lockstep, not {ticks}")
+        g = torch.cuda.CUDAGraph()
+        s = torch.cuda.Stream(device=ctrl.device)
+        s.wait_stream(torch.cuda.current_stream(ctrl.device))
+        with torch.cuda.stream(s):
+            with torch.cuda.graph(g, stream=s):
+                block()
+        torch.cuda.current_stream(ctrl.device).wait_stream(s)
+        g.replay()
+    return dict(effort=plant.effort, state=plant.state, motor=plant.motor, graph=g)

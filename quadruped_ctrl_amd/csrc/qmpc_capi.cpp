@@ -18,9 +18,11 @@
 #include "../../include/qmpc_debug.h"   // test / profiling hooks (same library)
 #include "../../include/qmpc_expert.h"  // tuning knobs whose default is the measured optimum, warm start
 #include "../../include/qmpc_ctrl.h"    // batched locomotion controller (same library)
+#include "../../include/qmpc_plant.h"   // reduced-order plant for it (same library)
 #include "qmpc_device.h"
 #include "qmpc_glue.h"
 #include "qmpc_plan.h"  // the solve's launch plan (host-only)
+#include "qmpc_plant.h"
 static_assert(kLongHorizon == QMPC_LONG_HORIZON, "qmpc_plan.h and qmpc.h disagree");
 
 // per-class entry points of qmpc_kernels.hip (one translation unit per size class)
@@ -111,6 +113,11 @@ extern "C" hipError_t qmpc_launch_ctrl_est_state(const QmpcCtrlDev* S, const flo
 extern "C" hipError_t qmpc_launch_ctrl_loco(const QmpcCtrlDev* S, int batch, int build_list, hipStream_t stream);
 extern "C" hipError_t qmpc_launch_ctrl_loco_aio(const QmpcCtrlDev* S, int batch, hipStream_t stream);
 extern "C" hipError_t qmpc_launch_ctrl_legcmd(const QmpcCtrlDev* S, double* effort, int batch, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_plant_init(const QmpcPlantDev* S, const QmpcPlantConst* K, const uint8_t* mask,
+                                             const double* xyyaw, int batch, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_plant_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
+                                             const float* contact_state, const float* p_des, const float* v_des,
+                                             double* state_out, double* motor_out, int batch, hipStream_t stream);
 extern "C" hipError_t qmpc_launch_swing(const float* p0, const float* pf, const float* height, const float* phase,
                                         const float* swing_time, float* p, float* v, float* a, int n_feet,
                                         hipStream_t stream);
@@ -215,8 +222,18 @@ struct qmpc_ctx {
     int schedule = QMPC_CTRL_LOCKSTEP;  // qmpc_ctrl_set_schedule
     int robot_mode = 0;                 // qmpc_ctrl_set_robot_mode (GaitCtrller::_robotMode)
     bool started = false;               // a tick or a reset has been enqueued since qmpc_ctrl_init: the schedule is fixed
+    double freq = 0;                    // qmpc_ctrl_init's: the plant's dt is 1 / freq in double
   };
   Ctrl* ctrl = nullptr;
+  // reduced-order plant (qmpc_plant.h): device state for max_batch robots, made by qmpc_plant_init
+  struct Plant {
+    QmpcPlantDev d{};
+    void* buf = nullptr;
+    int batch = 0;  // robots initialised
+    double mu = 0;
+    int substeps = 1;
+  };
+  Plant* plant = nullptr;
 };
 
 namespace {
@@ -404,8 +421,10 @@ int qmpc_destroy(qmpc_handle h) {
     if (h->host_ev) hipEventDestroy(h->host_ev);
     if (h->host_stream) hipStreamDestroy(h->host_stream);
     if (h->ctrl && h->ctrl->buf) hipFree(h->ctrl->buf);
+    if (h->plant && h->plant->buf) hipFree(h->plant->buf);
   }
   delete h->ctrl;
+  delete h->plant;
   delete h;
   return QMPC_OK;
 }
@@ -1298,6 +1317,7 @@ int qmpc_ctrl_init(qmpc_handle c, int batch, double freq, const double pid[4], v
   if (const int rc = order_after_previous(c, stream)) return rc;
   HIP_TRY(c, qmpc_launch_ctrl_init(&k->d, nullptr, 0, batch, stream));
   k->batch = batch;
+  k->freq = freq;
   k->ticks = 0;
   k->schedule = QMPC_CTRL_LOCKSTEP;
   k->robot_mode = 0;
@@ -1460,6 +1480,116 @@ int qmpc_ctrl_view_get(qmpc_handle c, qmpc_ctrl_view* v) {
   v->counter = d.counter;
   v->batch = c->ctrl->batch;
   v->ticks = (int)c->ctrl->ticks;
+  return QMPC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
+// Reduced-order plant (include/qmpc_plant.h).  The kernels are in qmpc_plant.hip.
+namespace {
+
+size_t plant_carve(QmpcPlantDev& d, char* base, int M) {
+  size_t off = 0;
+#define QMPC_PLANT_CARVE(T, name, per_robot)                    \
+  off = (off + 255) & ~(size_t)255;                            \
+  d.name = base ? reinterpret_cast<T*>(base + off) : nullptr;  \
+  off += sizeof(T) * (size_t)(per_robot) * (size_t)M;
+  QMPC_PLANT_ARRAYS(QMPC_PLANT_CARVE)
+#undef QMPC_PLANT_CARVE
+  return off;
+}
+
+// the constants of a launch, from the handle as it stands now
+QmpcPlantConst plant_const(const qmpc_ctx* c, double mu, int substeps) {
+  QmpcPlantConst K{};
+  K.mass = c->mass;
+  for (int k = 0; k < 3; ++k) K.ibody[k] = c->ibody[k];
+  for (int k = 0; k < 4; ++k) K.geom[k] = (double)c->leg_geom[k];
+  K.mu = mu;
+  K.substeps = substeps;
+  K.h = (1.0 / c->ctrl->freq) / (double)substeps;
+  const double l1 = K.geom[0] + K.geom[3], l2 = K.geom[1], l3 = K.geom[2];
+  const double base = (l1 * l1 + l2 * l2) + l3 * l3;
+  K.r2_lo = base + (2 * l2 * l3) * std::cos(QMPC_PLANT_KNEE_MAX);
+  K.r2_hi = base + (2 * l2 * l3) * std::cos(QMPC_PLANT_KNEE_MIN);
+  return K;
+}
+
+int plant_check(qmpc_ctx* c, int batch) {
+  if (!c) return QMPC_ERR_ARG;
+  if (!c->ctrl || !c->ctrl->batch || !c->plant || !c->plant->batch) return QMPC_ERR_STATE;
+  if (batch != c->plant->batch || batch != c->ctrl->batch) return QMPC_ERR_ARG;
+  return QMPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qmpc_plant_init(qmpc_handle c, int batch, double mu_plant, int substeps, const double* init_xyyaw, void* stream_) {
+  if (!c) return QMPC_ERR_ARG;
+  if (!c->ctrl || !c->ctrl->batch) return QMPC_ERR_STATE;
+  if (batch != c->ctrl->batch || substeps < 1 || !(mu_plant >= 0)) return QMPC_ERR_ARG;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!c->plant) c->plant = new qmpc_ctx::Plant();
+  qmpc_ctx::Plant* k = c->plant;
+  if (!k->buf) {
+    const size_t bytes = plant_carve(k->d, nullptr, c->max_batch);
+    HIP_TRY(c, hipMalloc(&k->buf, bytes));
+  }
+  plant_carve(k->d, static_cast<char*>(k->buf), c->max_batch);
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  const QmpcPlantConst K = plant_const(c, mu_plant, substeps);
+  HIP_TRY(c, qmpc_launch_plant_init(&k->d, &K, nullptr, init_xyyaw, batch, stream));
+  k->batch = batch;
+  k->mu = mu_plant;
+  k->substeps = substeps;
+  return QMPC_OK;
+}
+
+int qmpc_plant_reset(qmpc_handle c, int batch, const uint8_t* mask_dev, const double* init_xyyaw, void* stream_) {
+  if (const int rc = plant_check(c, batch)) return rc;
+  if (!mask_dev) return QMPC_ERR_ARG;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  const QmpcPlantConst K = plant_const(c, c->plant->mu, c->plant->substeps);
+  HIP_TRY(c, qmpc_launch_plant_init(&c->plant->d, &K, mask_dev, init_xyyaw, batch, stream));
+  return QMPC_OK;
+}
+
+int qmpc_plant_step(qmpc_handle c, int batch, const double* effort, double* state_out, double* motor_out,
+                    void* stream_) {
+  if (const int rc = plant_check(c, batch)) return rc;
+  if (!effort || !state_out || !motor_out) return QMPC_ERR_ARG;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  const QmpcCtrlDev& d = c->ctrl->d;
+  const QmpcPlantConst K = plant_const(c, c->plant->mu, c->plant->substeps);
+  HIP_TRY(c, qmpc_launch_plant_step(&c->plant->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out,
+                                    batch, stream));
+  return QMPC_OK;
+}
+
+int qmpc_plant_view_get(qmpc_handle c, qmpc_plant_view* v) {
+  if (!c || !v) return QMPC_ERR_ARG;
+  if (!c->plant || !c->plant->batch) return QMPC_ERR_STATE;
+  const QmpcPlantDev& d = c->plant->d;
+  v->p = d.p;
+  v->v = d.v;
+  v->q = d.q;
+  v->omega = d.omega;
+  v->foot = d.foot;
+  v->stance = d.stance;
+  v->grf = d.grf;
+  v->state = d.state;
+  v->motor = d.motor;
+  v->batch = c->plant->batch;
+  v->substeps = c->plant->substeps;
+  v->mu_plant = c->plant->mu;
   return QMPC_OK;
 }
 

@@ -1,0 +1,44 @@
+// qmpc_plant.h -- device state of the reduced-order plant (include/qmpc_plant.h), shared by qmpc_plant.hip (kernels)
+// and qmpc_capi.cpp (entry points).  Views into one allocation made by qmpc_plant_init for the handle's max_batch.
+#ifndef QMPC_PLANT_DEV_H
+#define QMPC_PLANT_DEV_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+// X(element type, name, elements per robot): members, carving and the view are generated from the list
+#define QMPC_PLANT_ARRAYS(X)                                                        \
+  X(double, p, 3)       /* body position, world */                                  \
+  X(double, v, 3)       /* body velocity, world */                                  \
+  X(double, q, 4)       /* w x y z */                                               \
+  X(double, omega, 3)   /* body frame */                                            \
+  X(double, foot, 12)   /* world */                                                 \
+  X(double, grf, 12)    /* ground reactions of the last substep, world */           \
+  X(double, state, 16)  /* the last read-out (qmpc_ctrl.h: state[B][16]) */         \
+  X(double, motor, 24)  /* ... motor[B][24] */                                      \
+  X(int, stance, 4)
+
+struct QmpcPlantDev {
+#define QMPC_PLANT_MEMBER(T, name, per_robot) T* name;
+  QMPC_PLANT_ARRAYS(QMPC_PLANT_MEMBER)
+#undef QMPC_PLANT_MEMBER
+};
+
+// the constants of a launch (by value)
+struct QmpcPlantConst {
+  double mass, ibody[3];     // qmpc_set_robot
+  double geom[4];            // abad, hip, knee, knee_y (the handle's floats, widened)
+  double mu;                 // mu_plant
+  double h;                  // dt / substeps
+  double r2_lo, r2_hi;       // the swing clamp's shell: |r|^2 at knee angle QMPC_PLANT_KNEE_MAX / _MIN
+  int substeps;
+};
+
+#define QMPC_PLANT_GRAVITY 9.81
+#define QMPC_PLANT_HEIGHT 0.29      /* ConvexMPCLocomotion::_body_height */
+#define QMPC_PLANT_SIDE_OFFSET 0.065
+#define QMPC_PLANT_DET_MIN 1e-5     /* |det J| below this: no force, no joint rates */
+#define QMPC_PLANT_KNEE_MIN 0.05    /* the swing clamp's shell, as knee angles */
+#define QMPC_PLANT_KNEE_MAX 2.6
+
+#endif

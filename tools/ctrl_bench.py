@@ -20,8 +20,13 @@ segment counts at the end.
 --source state drives the ticks with simulator ground truth (qmpc_ctrl_tick_state on workloads.make_state_stream: the
 cheater estimators, no Kalman filter) instead of the sensor path (--source imu, the default); nothing else changes.
 
+--source plant closes the loop on the device: qmpc_ctrl_tick_state on the read-out of the reduced-order plant
+(include/qmpc_plant.h), qmpc_plant_step on the tick's efforts -- states a walking robot visits.  Gaits from {0, 4, 5, 10},
+x commands over [0, 0.5] m/s and small yaw rates (the family tests/plant_loop.py walks on); the warm-up should cover the
+first steps (--warmup 260).  The tick and the plant step are timed separately (us_per_plant_step_median).
+
     python tools/ctrl_bench.py [--batches 1024,4096,16384] [--cycles 8] [--warmup 26] [--schedule lockstep|per_robot]
-                               [--stagger] [--robot-mode 0|1] [--source imu|state] [--out FILE]
+                               [--stagger] [--robot-mode 0|1] [--source imu|state|plant] [--out FILE]
 """
 import argparse
 import json
@@ -39,7 +44,8 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
     from quadruped_ctrl_amd import workloads as W
     from quadruped_ctrl_amd.binding import BatchedController
     ctrl = BatchedController(0, max_batch=B)
-    ctrl.init(B, freq=500.0, pid=(0.0, 0.0, 3.0, 0.3))
+    # (the plant takes the reference's simulation gains: a joint spring towards q = 0 pushes a real leg off its stance)
+    ctrl.init(B, freq=500.0, pid=(100.0, 1.0, 0.0, 0.05) if source == "plant" else (0.0, 0.0, 3.0, 0.3))
     if schedule != "lockstep":
         ctrl.set_schedule(schedule)
     if robot_mode:
@@ -53,16 +59,31 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
     if robot_mode == 1:
         vel[:, 0] = np.linspace(0.0, 2.0, B)[rng.permutation(B)]
         vel[::16, 1:] = 0.0      # (x command 0 with no yaw command: the standing case for robot 0's neighbours)
+    if source == "plant":
+        g = torch.from_numpy(np.array([0, 4, 5, 10], np.int32)[np.arange(B) % 4]).cuda()
+        ctrl.set_gait(g)
+        vel = np.stack([rng.uniform(0.0, 0.5, B), np.zeros(B), rng.uniform(-0.1, 0.1, B)], 1)
+        if robot_mode == 0:
+            vel[np.arange(B) % 4 == 1] = 0.0     # (gait 4 stands)
     vel = torch.from_numpy(vel).cuda()
     ctrl.set_vel(vel)
     n = warmup + 13 * cycles
-    if source == "state":
+    plant = None
+    if source == "plant":
+        from quadruped_ctrl_amd.binding import BatchedPlant
+        plant = BatchedPlant(ctrl)
+        xyyaw = np.stack([np.arange(B) % 128 * 1.0, np.arange(B) // 128 * 1.0, rng.uniform(-0.1, 0.1, B)], 1)
+        plant.init(0.4, 1, torch.from_numpy(xyyaw).cuda())
+        imu, motor = plant.state.expand(26, B, 16), plant.motor.expand(26, B, 24)    # (every "slot" is the plant's read-out)
+        tick = ctrl.tick_state
+    elif source == "state":
         imu, motor = W.make_state_stream(B, 26, seed=B)      # (`imu` below: the tick's first input, whichever it is)
         tick = ctrl.tick_state
     else:
         imu, motor = W.make_tick_stream(B, 26, seed=B)
         tick = ctrl.tick
-    imu, motor = torch.from_numpy(imu).cuda(), torch.from_numpy(motor).cuda()
+    if plant is None:
+        imu, motor = torch.from_numpy(imu).cuda(), torch.from_numpy(motor).cuda()
     eff = torch.empty((B, 12), dtype=torch.float64, device="cuda")
     if stagger:
         group = torch.arange(B, device="cuda") % 13
@@ -71,13 +92,18 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
             ctrl.set_gait(g)     # (a reset zeroes the robot's gait and velocity command)
             ctrl.set_vel(vel)
             tick(imu[t], motor[t], eff)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
+            if plant is not None:
+                plant.step(eff)
+    ev = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) for _ in range(n)]
     for t in range(n):
         ev[t][0].record()
         tick(imu[t % 26], motor[t % 26], eff)
         ev[t][1].record()
+        if plant is not None:
+            plant.step(eff)
+            ev[t][2].record()
     torch.cuda.synchronize()
-    us = np.array([a.elapsed_time(b) * 1e3 for a, b in ev])
+    us = np.array([e[0].elapsed_time(e[1]) * 1e3 for e in ev])
     mpc = (np.arange(n) + 1) % 13 == 0
     keep = np.arange(n) >= warmup
     t_non, t_mpc = float(np.median(us[keep & ~mpc])), float(np.median(us[keep & mpc]))
@@ -96,6 +122,12 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
         res.update({"us_per_nonmpc_tick": round(t_non, 2), "us_per_mpc_tick": round(t_mpc, 2),
                     "us_per_13_tick_cycle": round(per_cycle, 1),
                     "robot_ticks_per_s": float(f"{13 * B / (per_cycle * 1e-6):.4g}")})
+    if plant is not None:
+        us_p = np.array([e[1].elapsed_time(e[2]) * 1e3 for e in ev])[keep]
+        pz = plant.view()["p"][:, 2]
+        res.update({"us_per_plant_step_median": round(float(np.median(us_p)), 2), "us_per_plant_step_max": round(float(us_p.max()), 2),
+                    "body_height_min": round(float(pz.min().item()), 4), "body_height_max": round(float(pz.max().item()), 4),
+                    "status_error_robots": int((torch.from_numpy(ctrl.read("status")[:, 0]) & 47 != 0).sum())})
     res.update({"all_finite": bool(torch.isfinite(eff).all().item()), "latched": int((v["safe"] == 0).sum())})
     ctrl.close()
     return res
@@ -109,7 +141,7 @@ def main():
     ap.add_argument("--schedule", choices=("lockstep", "per_robot"), default="lockstep")
     ap.add_argument("--stagger", action="store_true")
     ap.add_argument("--robot-mode", type=int, choices=(0, 1), default=0)
-    ap.add_argument("--source", choices=("imu", "state"), default="imu")
+    ap.add_argument("--source", choices=("imu", "state", "plant"), default="imu")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.robot_mode == 1:
