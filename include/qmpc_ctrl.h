@@ -85,7 +85,10 @@ extern "C" {
  * robots 0 .. batch-1: firstRun, firstSwing, f_ff = 0, Kalman filter setup(), contact phase 0.5
  * (GaitCtrller.cpp:21-24), orientation first visit, safety flag set, iteration counters 0, gait 0, velocity
  * command 0.  pid[2], pid[3] are the joint PD gains of LegController::updateCommand (ctrlParam(2..3)).
- * The handle's max_horizon must be at least 14.  Synchronises the device (allocation); resets T to 0. */
+ * The handle's max_horizon must be at least 14.  Synchronises the device (allocation); resets T to 0.
+ * Handle constants: the estimators read qmpc_set_leg_geometry's lengths at every prework / tick (so the setter may
+ * come before or after this call), the solve reads qmpc_set_robot's body at every MPC tick; freq fixes dt and dt_mpc
+ * here, and the Kalman filter keeps the reference's own dt = 0.002 at any freq. */
 int qmpc_ctrl_init(qmpc_handle h, int batch, double freq, const double pid[4], void* stream);
 
 /* The MPC schedule (see above).  qmpc_ctrl_init always leaves the handle in lockstep; the mode can be changed only

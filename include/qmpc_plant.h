@@ -18,7 +18,9 @@
  *   velocity w; per foot a world position c_i and a stance flag; the ground reactions f_i of the last substep.
  * Constants: mass and body inertia of the handle (qmpc_set_robot; 9 kg, diag(0.07, 0.26, 0.242)); g = 9.81 (the
  *   plant's own constant: the handle's gravity is the MPC's model value, -9.8f); leg geometry qmpc_set_leg_geometry;
- *   hip locations (+-0.19, +-0.049, 0); dt = 1 / freq of qmpc_ctrl_init, h = dt / substeps.
+ *   hip locations (+-0.19, +-0.049, 0); dt = 1 / freq of qmpc_ctrl_init, h = dt / substeps.  Mass, inertia and
+ *   geometry are read from the handle at every qmpc_plant_step / qmpc_plant_reset: a setter called between two
+ *   steps takes effect on the next one (mu_plant and substeps are qmpc_plant_init's).
  *
  * One step, from effort and the controller's view after the tick that produced it (contact_state, p_des, v_des):
  *  1. Contact schedule.  Foot i stands iff contact_state[i] > 0.  On a swing -> stance edge c_i,z = 0 (x, y stay);

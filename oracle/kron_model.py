@@ -28,11 +28,13 @@ def quat_to_rpy(q):
     return roll, pitch, yaw
 
 
-def ct_mats(r, yaw, x_drag, mass=9.0, ibody=(.07, .26, .242), trig=None):
+def ct_mats(r, yaw, x_drag, mass=9.0, ibody=None, trig=None):
+    """ibody None: the reference's float literals (RobotState.cpp:38); given: doubles, taken as they are."""
     yaw = np.float64(yaw)
     c, s = (np.cos(yaw), np.sin(yaw)) if trig is None else (np.float64(trig[0]), np.float64(trig[1]))
     Ry = np.array([[c, -s, 0], [s, c, 0], [0, 0, 1.0]])
-    Ib = np.diag(np.array(ibody, np.float32).astype(np.float64))
+    Ib = np.diag(np.array((.07, .26, .242), np.float32).astype(np.float64) if ibody is None
+                 else np.asarray(ibody, np.float64))
     Iinv = np.linalg.inv(Ry @ Ib @ Ry.T)
     A = np.zeros((13, 13))
     A[3, 9] = A[4, 10] = A[5, 11] = 1
@@ -72,10 +74,16 @@ def assemble(b, i, trig=None, rpy=None):
     trig = (cos yaw, sin yaw) and rpy = (roll, pitch, yaw) override the fp64
     transcendentals with externally evaluated ones (the reference and the GPU
     evaluate them in float: RobotState.cpp:30-35, SolverMPC.cpp:257-267), so that a
-    comparison can pin the ALGEBRA to ~1e-13 independently of libm bits."""
+    comparison can pin the ALGEBRA to ~1e-13 independently of libm bits.
+    Optional b["mass"], b["ibody"], b["gravity"]: the doubles a caller hands qmpc_set_robot, taken as given; absent,
+    the handle's defaults, i.e. the reference's literals (9.0, and the float literals of RobotState.cpp:38 and
+    SolverMPC.cpp:318 widened)."""
     h = b["horizon"]
     dt = np.float64(np.float32(b["dt"]))
-    A, B = ct_mats(b["r"][i], b["yaw"][i], np.float64(b["x_drag"][i]), trig=trig)
+    mass = np.float64(b.get("mass", 9.0))
+    ibody = np.asarray(b["ibody"], np.float64) if "ibody" in b else None
+    gravity = np.float64(b["gravity"]) if "gravity" in b else np.float64(np.float32(-9.8))
+    A, B = ct_mats(b["r"][i], b["yaw"][i], np.float64(b["x_drag"][i]), mass=mass, ibody=ibody, trig=trig)
     Bp = [B, A @ B, A @ A @ B]
     W = np.zeros(13)
     W[:12] = b["weights"][i].astype(np.float64)
@@ -91,7 +99,7 @@ def assemble(b, i, trig=None, rpy=None):
     H = 2 * (H + np.float64(b["alpha"][i]) * np.eye(n))
     roll, pitch, yaw = quat_to_rpy(b["q"][i]) if rpy is None else [np.float64(v) for v in rpy]
     x0 = np.concatenate([[roll, pitch, yaw], b["p"][i], b["w"][i], b["v"][i],
-                         [np.float64(np.float32(-9.8))]]).astype(np.float64)
+                         [gravity]]).astype(np.float64)
     Ax, AAx = A @ x0, A @ A @ x0
     traj = b["traj"][i].astype(np.float64).reshape(h, 12)
     e = np.zeros((h, 13))

@@ -285,6 +285,10 @@ class BatchedConvexMPC:
         arr = (C.c_double * 3)(*ibody)
         self._check(self.lib.qmpc_set_robot(self.h, mass, arr, gravity), "qmpc_set_robot")
 
+    def set_leg_geometry(self, abad, hip, knee, knee_y):
+        """Link lengths (m) for the leg kernels, the controller's estimators and the plant; read at every launch."""
+        self._check(self.lib.qmpc_set_leg_geometry(self.h, abad, hip, knee, knee_y), "qmpc_set_leg_geometry")
+
     def set_model(self, model):
         """0 = the dense path's zero-order-hold model, 1 = SparseCMPC's (QMPC_MODEL_SPARSE)."""
         self._check(self.lib.qmpc_set_model(self.h, int(model)), "qmpc_set_model")

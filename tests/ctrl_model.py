@@ -148,11 +148,30 @@ def yaw_inverse_quat(yaw):
     return q
 
 
+# the commands of the GPU suites' runs (tests/test_gpu_controller.py and the files that follow it)
+def command_gaits(B, t, switch_at):
+    """Every gait number 0 .. 11 and its omni variant, switched part-way (into and out of standing)."""
+    g = (np.arange(B) % 12).astype(np.int32)
+    g = np.where(np.arange(B) % 24 >= 12, g + 20, g)
+    if t >= switch_at:
+        g = np.where(np.arange(B) % 3 == 0, 4, np.where(g % 20 == 4, 9 + 20 * (g >= 20), (g + 5) % 12)).astype(np.int32)
+    return g
+
+
+def command_vel(B, seed):
+    rng = np.random.default_rng(seed)
+    v = np.stack([rng.uniform(-0.8, 1.5, B), rng.uniform(-0.4, 0.4, B), rng.uniform(-0.6, 0.6, B)], 1)
+    v[::7] = 0.0           # robots standing still in command (yaw rate 0: coordinateRotation is exact there)
+    v[1::11, 0] = 0.02     # inside the 0.03 dead band
+    return v
+
+
 class CtrlModel:
     """State of GaitCtrller / ConvexMPCLocomotion for B robots (numpy), same names as QmpcCtrlDev."""
 
-    def __init__(self, B, freq=500.0, pid=(0.0, 0.0, 0.0, 0.0), float_sqrt=False):
+    def __init__(self, B, freq=500.0, pid=(0.0, 0.0, 0.0, 0.0), float_sqrt=False, geom=G.GEOM):
         self.B = B
+        self.geom = np.asarray(geom, f32)        # qmpc_set_leg_geometry's four lengths (the handle's floats)
         self.dt = f32(1.0 / freq)
         self.dt_mpc = self.dt * f32(13)
         self.kp_joint, self.kd_joint = f32(pid[2]), f32(pid[3])
@@ -206,7 +225,7 @@ class CtrlModel:
         self.kf_leg_p, self.kf_leg_v = self.leg_p.copy(), self.leg_v.copy()
         motor = np.asarray(motor, f64)
         qj, qd = motor[:, :12].astype(f32), motor[:, 12:].astype(f32)
-        J, p, v = G.leg_update(qj, qd)
+        J, p, v = G.leg_update(qj, qd, self.geom)
         self.leg_p, self.leg_v = p, v
         pos, vw, _ = G.kf_step(self.xhat, self.P, est["r_body"], est["a_world"], est["omega_body"], self.contact_phase,
                                self.kf_leg_p, self.kf_leg_v)
@@ -396,5 +415,5 @@ class CtrlModel:
         kd[:, :, 0] = kd[:, :, 4] = kd[:, :, 8] = 10
         tau, _ = G.leg_command(dict(tau_ff=np.zeros((B, 12), f32), force_ff=force, kp_cart=kp, kd_cart=kd, p_des=self.p_des,
                                     v_des=self.v_des, q=self.q, qd=est["qd"], J=est["leg_J"].reshape(B, 4, 9),
-                                    p=est["leg_p"], v=est["leg_v"], kp_joint=self.kp_joint, kd_joint=self.kd_joint))
+                                    p=est["leg_p"], v=est["leg_v"], kp_joint=self.kp_joint, kd_joint=self.kd_joint), self.geom)
         return np.where(self.safe[:, None] != 0, tau.astype(f64), 0.0)

@@ -42,7 +42,7 @@ def estimate_state(model, state, motor):
     est["a_world"] = np.stack([M.rowT(rB, k, a[:, 0], a[:, 1], a[:, 2]) for k in range(3)], 1)
     motor = np.asarray(motor, f64)
     qj, qd = motor[:, :12].astype(f32), motor[:, 12:].astype(f32)
-    J, p, v = G.leg_update(qj, qd)
+    J, p, v = G.leg_update(qj, qd, model.geom)
     model.leg_p, model.leg_v = p, v
     est.update(position=state[:, POS].astype(f32),
                v_world=np.stack([M.rowT(rB, k, vb[:, 0], vb[:, 1], vb[:, 2]) for k in range(3)], 1), v_body=vb,

@@ -28,6 +28,7 @@ from oracle import oracle as O
 from quadruped_ctrl_amd import workloads as W
 
 import ctrl_model as M
+from ctrl_model import command_gaits as _gaits, command_vel as _vel
 
 pytestmark = pytest.mark.gpu
 
@@ -38,33 +39,18 @@ EXACT_I32 = ("counter", "first_run", "first_swing", "current_gait", "offsets", "
 PID = (0.0, 0.0, 3.0, 0.3)
 
 
-def _ctrl(B):
+def _ctrl(B, freq=500.0, geom=None):
     from quadruped_ctrl_amd.binding import BatchedController
     c = BatchedController(0, max_batch=B)
-    c.init(B, 500.0, PID)
+    c.init(B, freq, PID)
+    if geom is not None:
+        c.mpc.set_leg_geometry(*geom)
     return c
 
 
 def _gpu_est(c):
     return {k: c.read(k) for k in ("orientation", "rpy", "r_body", "omega_world", "omega_body", "a_world", "position",
                                 "v_world", "leg_p", "leg_v", "leg_J", "qd")}
-
-
-def _gaits(B, t, switch_at):
-    """Every gait number 0 .. 11 and its omni variant, switched part-way (into and out of standing)."""
-    g = (np.arange(B) % 12).astype(np.int32)
-    g = np.where(np.arange(B) % 24 >= 12, g + 20, g)
-    if t >= switch_at:
-        g = np.where(np.arange(B) % 3 == 0, 4, np.where(g % 20 == 4, 9 + 20 * (g >= 20), (g + 5) % 12)).astype(np.int32)
-    return g
-
-
-def _vel(B, seed):
-    rng = np.random.default_rng(seed)
-    v = np.stack([rng.uniform(-0.8, 1.5, B), rng.uniform(-0.4, 0.4, B), rng.uniform(-0.6, 0.6, B)], 1)
-    v[::7] = 0.0           # robots standing still in command (yaw rate 0: coordinateRotation is exact there)
-    v[1::11, 0] = 0.02     # inside the 0.03 dead band
-    return v
 
 
 def _bound(rec, err):
@@ -75,12 +61,14 @@ def _bound(rec, err):
     return bnd
 
 
-def _teacher_forced(B, ticks, seed, switch_at=20, roll=None, joint=None, check_mpc=True):
+def _teacher_forced(B, ticks, seed, switch_at=20, roll=None, joint=None, check_mpc=True, freq=500.0, geom=None):
+    """freq: qmpc_ctrl_init's (the stream is sampled at 1 / freq); geom: qmpc_set_leg_geometry's four lengths, None for
+    the handle's default."""
     import torch
-    c = _ctrl(B)
-    m = M.CtrlModel(B, 500.0, PID)
+    c = _ctrl(B, freq, geom)
+    m = M.CtrlModel(B, freq, PID) if geom is None else M.CtrlModel(B, freq, PID, geom=geom)
     dev = c.device
-    imu, motor = W.make_tick_stream(B, ticks, seed, roll=roll, joint=joint)
+    imu, motor = W.make_tick_stream(B, ticks, seed, dt=1.0 / freq, roll=roll, joint=joint)
     vel = _vel(B, seed + 1)
     c.set_vel(torch.from_numpy(vel).to(dev))
     m.set_vel(vel)

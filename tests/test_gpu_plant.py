@@ -17,27 +17,34 @@ from quadruped_ctrl_amd import workloads as W
 
 import plant_loop as L
 import plant_model as PM
+from plant_cases import DEFAULTS, parity_case as _parity_case
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 1e-10
 f32 = np.float32
-STAND = np.stack([np.zeros(4), PM.SIDE * PM.SIDE_OFFSET, np.full(4, -PM.HEIGHT)], -1)
 PLANT_KEYS = ("p", "v", "q", "omega", "foot", "grf", "stance", "state", "motor")
+assert DEFAULTS["freq"] == L.FREQ
 
 
-def _pair(B, schedule="lockstep", mode=None, substeps=1, xyyaw=None, max_batch=None):
+def _pair(B, schedule="lockstep", mode=None, substeps=1, xyyaw=None, max_batch=None, consts=None):
+    """consts: a dict like DEFAULTS; its body goes to qmpc_set_robot (gravity -9.81, which the plant does not read) and
+    its geometry to qmpc_set_leg_geometry, None leaves the handle as created."""
     import torch
     from quadruped_ctrl_amd.binding import BatchedController, BatchedPlant
+    k = consts or DEFAULTS
     c = BatchedController(0, max_batch=max_batch or B)
-    c.init(B, L.FREQ, L.PID)
+    c.init(B, k["freq"], L.PID)
+    if consts is not None:
+        c.mpc.set_robot(float(k["mass"]), [float(x) for x in k["ibody"]], -9.81)
+        c.mpc.set_leg_geometry(*[float(x) for x in k["geom"]])
     if schedule != "lockstep":
         c.set_schedule(schedule)
     if mode is not None:
         c.set_robot_mode(mode)
     p = BatchedPlant(c)
-    p.init(0.4, substeps, None if xyyaw is None else torch.from_numpy(np.ascontiguousarray(xyyaw, np.float64)).to(c.device))
+    p.init(k["mu"], substeps, None if xyyaw is None else torch.from_numpy(np.ascontiguousarray(xyyaw, np.float64)).to(c.device))
     return c, p
 
 
@@ -67,63 +74,17 @@ def _compare(snap, model, what):
     assert np.array_equal(snap["stance"] != 0, model.stance), what
 
 
-def _hold(model, f_world):
-    """tau = J^T (-rBody f): the torques that ask the ground for f."""
-    R = PM.rot(model.q)
-    rb = PM.mulT(R[:, None, :], model.foot - model.p[:, None, :])
-    J, _ = PM.leg_fk(PM.leg_ik(rb - PM.HIP))
-    fb = -PM.mulT(R[:, None, :], f_world)
-    return np.stack([(J[..., k] * fb[..., 0] + J[..., 3 + k] * fb[..., 1]) + J[..., 6 + k] * fb[..., 2] for k in range(3)], -1)
-
-
-def _parity_case(substeps):
-    B = 257
-    rng = np.random.default_rng(257 + substeps)
-    m = PM.PlantModel(B, L.FREQ, 0.4, substeps)
-    k = np.arange(B)
-    rpy = np.stack([rng.uniform(-0.15, 0.15, B), rng.uniform(-0.15, 0.15, B), rng.uniform(-3.1, 3.1, B)], 1)
-    q = W._quat_from_rpy(rpy)                                        # (x y z w or w x y z: normalised below either way)
-    q = np.asarray(q, np.float64)
-    q /= np.linalg.norm(q, axis=1, keepdims=True)
-    m.q = q
-    m.p = np.stack([rng.uniform(-2, 2, B), rng.uniform(-2, 2, B), rng.uniform(0.24, 0.30, B)], 1)
-    m.v = rng.uniform(-0.6, 0.6, (B, 3))
-    m.w = rng.uniform(-1.5, 1.5, (B, 3))
-    R = PM.rot(m.q)
-    body_foot = PM.HIP + STAND + rng.uniform(-0.05, 0.05, (B, 4, 3))
-    m.foot = m.p[:, None, :] + PM.mul(R[:, None, :], body_foot)
-    old = ((k[:, None] >> np.arange(4)) & 1).astype(bool)            # all 16 old patterns ...
-    new = (((k // 16)[:, None] >> np.arange(4)) & 1).astype(bool)    # ... against all 16 new ones
-    m.foot[..., 2] = np.where(old, 0.0, m.foot[..., 2] + 0.05)       # pinned feet are on the ground, the others above it
-    m.stance = old.copy()
-    # robot 256: legs nearly straight (all four pinned, the body as high as the legs reach less 1e-11 m)
-    l1, l2, l3 = PM.GEOM[0] + PM.GEOM[3], PM.GEOM[1], PM.GEOM[2]
-    m.q[256], m.p[256] = [1, 0, 0, 0], [0.5, 0.5, l2 + l3 - 1e-11]
-    m.foot[256] = m.p[256] + PM.HIP + np.stack([np.zeros(4), PM.SIDE * l1, np.full(4, -(l2 + l3 - 1e-11))], -1)
-    m.stance[256], new[256], old[256] = True, True, True
-    f = np.zeros((B, 4, 3))
-    f[..., 2] = rng.uniform(5, 40, (B, 4))
-    f[..., :2] = rng.uniform(-0.3, 0.3, (B, 4, 2)) * f[..., 2:3]
-    f[0::7, :, 2] *= -1                                              # pulling legs
-    f[3::7, :, 0] = 2 * 0.4 * f[3::7, :, 2]                          # demand outside the cone
-    tau = _hold(m, f) + rng.uniform(-0.5, 0.5, (B, 4, 3))
-    det = PM.leg(PM.mulT(PM.rot(m.q)[:, None, :], m.foot - m.p[:, None, :]) - PM.HIP)[2]
-    assert (np.abs(det[256]) < PM.DET_MIN / 10).all() and (np.abs(det[:256][old[:256] & new[:256]]) > PM.DET_MIN * 10).all()
-    cs = np.where(new, rng.uniform(0.05, 1.0, (B, 4)), 0.0).astype(f32)
-    pd = (STAND[None] + rng.uniform(-0.06, 0.06, (B, 4, 3))).astype(f32)
-    pd[5], pd[6] = [0.0, -0.065, -0.6], 0.0                          # out of reach; the zero command
-    vd = rng.uniform(-1.0, 1.0, (B, 4, 3)).astype(f32)
-    return B, m, old, new, tau, cs, pd, vd
-
-
 @pytest.mark.parametrize("substeps", [1, 4])
 def test_single_step_parity(substeps):
     """B = 257 (the last block is partial, 1028 lanes are no multiple of 64): random poses and joint states, every old
     and new stance pattern (both edges, all-swing, all-stance), a saturated cone, pulling legs, a near-straight knee, a
     swing command out of reach and a zero one."""
-    B, m, old, new, tau, cs, pd, vd = _parity_case(substeps)
-    c, plant = _pair(B, substeps=substeps)
-    # the same start on the device: the views alias the state
+    _single_step(substeps)
+
+
+def _start(c, plant, m, cs, pd, vd):
+    """The model's state and the controller outputs the plant reads, put on the device: the views alias the state."""
+    B = m.B
     pv, cv = plant.view(), c.view()
     for key, val in (("p", m.p), ("v", m.v), ("q", m.q), ("omega", m.w), ("foot", m.foot.reshape(B, 12))):
         pv[key].copy_(_dev(c, val))
@@ -131,6 +92,13 @@ def test_single_step_parity(substeps):
     cv["contact_state"].copy_(_dev(c, cs))
     cv["p_des"].copy_(_dev(c, pd.reshape(B, 12)))
     cv["v_des"].copy_(_dev(c, vd.reshape(B, 12)))
+
+
+def _single_step(substeps, consts=None):
+    """The body of test_single_step_parity; consts: see _pair."""
+    B, m, old, new, tau, cs, pd, vd = _parity_case(substeps, consts or DEFAULTS)
+    c, plant = _pair(B, substeps=substeps, consts=consts)
+    _start(c, plant, m, cs, pd, vd)
     state, motor = plant.step(_dev(c, tau.reshape(B, 12)))
     want_state, want_motor = m.step(tau.reshape(B, 12), cs, pd, vd)
     s = _snap(plant)
@@ -140,7 +108,7 @@ def test_single_step_parity(substeps):
     # the cases are there: both edges, zero and saturated forces, the clamp
     assert (new & ~old).any() and (old & ~new).any() and (~new).all(1).any() and new.all(1).any()
     g = m.grf
-    on_cone = np.abs(np.hypot(g[..., 0], g[..., 1]) - 0.4 * g[..., 2]) < 1e-12
+    on_cone = np.abs(np.hypot(g[..., 0], g[..., 1]) - m.mu * g[..., 2]) < 1e-12
     assert (on_cone & (g[..., 2] > 1)).sum() > 20 and (g[0][new[0]] == 0).all()
     assert substeps > 1 or (g[256] == 0).all()      # (with substeps the body has dropped off the singularity by the second)
     assert abs(m.motor[5, 2] - PM.KNEE_MIN) < 1e-9 or new[5, 0]
@@ -155,12 +123,17 @@ def _walk_setup(mode, reps):
 def test_teacher_forced_closed_loop():
     """64 robots, 40 ticks (three solves): at every tick the numpy plant is stepped from the device plant's previous
     state with the device's effort and controller view, and compared with the device's step."""
-    B, ticks = 64, 40
-    gait, vel, xyyaw = _walk_setup(0, 4)
-    c, plant = _pair(B, xyyaw=xyyaw)
+    _closed_loop(64, 40)
+
+
+def _closed_loop(B, ticks, consts=None):
+    """The body of test_teacher_forced_closed_loop; consts: see _pair."""
+    k = consts or DEFAULTS
+    gait, vel, xyyaw = _walk_setup(0, B // L.N_CMD)
+    c, plant = _pair(B, xyyaw=xyyaw, consts=consts)
     c.set_gait(_dev(c, gait))
     c.set_vel(_dev(c, vel))
-    m = PM.PlantModel(B, L.FREQ, 0.4, 1, xyyaw)
+    m = PM.PlantModel(B, k["freq"], k["mu"], 1, xyyaw, mass=k["mass"], ibody=k["ibody"], geom=k["geom"])
     s = _snap(plant)
     s["foot"], s["grf"] = s["foot"].reshape(B, 4, 3), s["grf"].reshape(B, 4, 3)
     _compare(s, m, "init")

@@ -1,18 +1,20 @@
 """CPU suite for the reduced-order plant (include/qmpc_plant.h): the exported surface, and the numpy restatement
 tests/plant_model.py on the closed forms it must reproduce -- the same model the GPU suite (tests/test_gpu_plant.py)
-holds the kernel to -- and the CPU closed loop against the reference pipeline that the GPU walk is measured by."""
+holds the kernel to; the closed forms themselves are functions of the model's constructor arguments in
+tests/plant_cases.py, run here at the handle's defaults -- and the CPU closed loop against the reference pipeline that
+the GPU walk is measured by."""
 import json
 import os
 import re
 
 import numpy as np
 
+import plant_cases as PC
 import plant_loop as L
 import plant_model as PM
+from plant_cases import STAND, none as _none
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# the stand pose of a leg in its hip frame, and the joint angles of that pose
-STAND = np.stack([np.zeros(4), PM.SIDE * PM.SIDE_OFFSET, np.full(4, -PM.HEIGHT)], -1)
 
 
 def test_plant_symbols_exported_and_abi_version_kept():
@@ -50,103 +52,20 @@ def test_fk_ik_round_trip():
     assert (np.abs(s[:, 0]) < 0.02).all() and (s[:, 1] < -0.5).all() and (s[:, 2] > 1.0).all()
 
 
-def _hold_torques(plant, f_world):
-    """tau_i = J^T (-rBody f_i): what the controller commands for the ground reaction f_i (f_ff = -rBody grf)."""
-    R = PM.rot(plant.q)
-    rb = PM.mulT(R[:, None, :], plant.foot - plant.p[:, None, :])
-    ang = PM.leg_ik(rb - PM.HIP)
-    J, _ = PM.leg_fk(ang)
-    fb = -PM.mulT(R[:, None, :], f_world)
-    return np.stack([(J[..., k] * fb[..., 0] + J[..., 3 + k] * fb[..., 1]) + J[..., 6 + k] * fb[..., 2] for k in range(3)], -1)
-
-
-def _none(B):
-    return np.zeros((B, 4), np.float32), np.tile(STAND.reshape(1, 12), (B, 1)).astype(np.float32), np.zeros((B, 12), np.float32)
-
-
 def test_free_fall_matches_the_recurrence_exactly():
-    B, n = 3, 25
-    for sub in (1, 4):
-        pl = PM.PlantModel(B, 500.0, 0.4, sub, np.array([[0, 0, 0], [1, 2, 0.3], [-1, 0.5, -2.0]]))
-        pl.v[:] = [[0.0, 0.0, 0.0], [0.3, -0.2, 1.0], [0.0, 0.1, -0.5]]
-        z, vz, x, vx = pl.p[:, 2].copy(), pl.v[:, 2].copy(), pl.p[:, 0].copy(), pl.v[:, 0].copy()
-        cs, pd, vd = _none(B)
-        h = (1.0 / 500.0) / float(sub)
-        for _ in range(n):
-            st, _ = pl.step(np.zeros((B, 12)), cs, pd, vd)
-            for _ in range(sub):
-                vz = vz + h * (0.0 / 9.0 - 9.81)
-                z = z + h * vz
-                x = x + h * vx
-        assert np.array_equal(pl.p[:, 2], z) and np.array_equal(pl.v[:, 2], vz) and np.array_equal(pl.p[:, 0], x)
-        assert np.array_equal(st[:, 4:7], pl.p) and not pl.stance.any()
-        # free fall: the accelerometer reads nothing
-        assert np.abs(st[:, 13:16]).max() < 1e-14
+    PC.free_fall()
 
 
 def test_symmetric_stance_is_an_equilibrium():
-    B = 4
-    pl = PM.PlantModel(B, 500.0, 0.4, 1, np.array([[0, 0, 0], [1, 1, 0.7], [0, 0, -2.5], [3, -1, 3.1]]))
-    f = np.zeros((B, 4, 3))
-    f[..., 2] = pl.mass * PM.GRAVITY / 4
-    tau = _hold_torques(pl, f)
-    cs = np.ones((B, 4), np.float32)
-    _, pd, vd = _none(B)
-    p0, q0 = pl.p.copy(), pl.q.copy()
-    st, mo = pl.step(tau.reshape(B, 12), cs, pd, vd)
-    assert np.abs(pl.grf - f).max() < 1e-11                       # forces of 22 N
-    assert np.abs(pl.v).max() / pl.h < 1e-12 and np.abs(pl.w).max() / pl.h < 1e-12   # vdot, wdot
-    assert np.abs(pl.p - p0).max() < 1e-15 and np.abs(pl.q - q0).max() < 1e-15
-    assert np.abs(st[:, 13:16] - [0, 0, PM.GRAVITY]).max() < 1e-12   # a body at rest reads g upwards
-    assert np.abs(mo[:, 12:]).max() < 1e-12
+    PC.hover()
 
 
 def test_quaternion_stays_normalised_and_principal_axis_rotation_keeps_omega():
-    B = 3
-    pl = PM.PlantModel(B, 500.0, 0.4, 2)
-    pl.w[:] = [[3.0, 0, 0], [0, -2.0, 0], [0, 0, 5.0]]
-    w0 = pl.w.copy()
-    cs, pd, vd = _none(B)
-    for _ in range(200):
-        pl.step(np.zeros((B, 12)), cs, pd, vd)
-        assert np.abs(np.linalg.norm(pl.q, axis=1) - 1).max() < 4e-16
-    assert np.array_equal(pl.w, w0)                               # w x I w = 0 exactly on a principal axis
-    # 200 ticks of 2 ms at |w|: the angle turned is |w| * 0.4
-    ang = 2 * np.arctan2(np.linalg.norm(pl.q[:, 1:], axis=1), pl.q[:, 0])
-    assert np.abs(ang - np.abs(w0).sum(1) * 0.4).max() < 1e-12
-    # a general spin: the norm still holds and omega moves (Euler's equations)
-    pl = PM.PlantModel(1, 500.0, 0.4, 1)
-    pl.w[:] = [[1.0, 2.0, -1.5]]
-    for _ in range(300):
-        pl.step(np.zeros((1, 12)), cs[:1], pd[:1], vd[:1])
-    assert abs(np.linalg.norm(pl.q) - 1) < 4e-16 and np.abs(pl.w - [[1.0, 2.0, -1.5]]).max() > 1e-3
+    PC.spin()
 
 
 def test_unilateral_friction_and_straight_knee():
-    B = 3
-    mu = 0.4
-    pl = PM.PlantModel(B, 500.0, mu, 1, np.array([[0, 0, 0.4], [0, 0, 0.4], [0, 0, 0.0]]))
-    fz = 20.0
-    f = np.zeros((B, 4, 3))
-    f[0, :, 2] = -fz                                              # robot 0: every leg pulls
-    f[1, :, 2] = fz
-    f[1, :, 0], f[1, :, 1] = 2 * mu * fz * 0.6, -2 * mu * fz * 0.8   # robot 1: tangential demand twice the cone
-    f[2, :, 2] = fz
-    tau = _hold_torques(pl, f)
-    # robot 2: straight legs -- the body lifted until the feet are at full reach below the hips
-    l1, l2, l3 = PM.GEOM[0] + PM.GEOM[3], PM.GEOM[1], PM.GEOM[2]
-    pl.p[2, 2] = l2 + l3
-    pl.foot[2, :, 1] = pl.p[2, 1] + PM.HIP[:, 1] + PM.SIDE * l1
-    assert (np.abs(PM.leg(pl.foot[2:3] - pl.p[2:3, None, :] - PM.HIP)[2]) < PM.DET_MIN).all()   # (yaw 0: rBody = 1)
-    cs = np.ones((B, 4), np.float32)
-    _, pd, vd = _none(B)
-    pl.step(tau.reshape(B, 12), cs, pd, vd)
-    assert np.array_equal(pl.grf[0], np.zeros((4, 3)))
-    g = pl.grf[1]
-    assert np.abs(g[:, 2] - fz).max() < 1e-11
-    assert np.abs(np.hypot(g[:, 0], g[:, 1]) - mu * g[:, 2]).max() < 1e-12   # exactly on the cone
-    assert np.abs(g[:, 0] * (-0.8) - g[:, 1] * 0.6).max() < 1e-11            # in the demanded direction
-    assert np.array_equal(pl.grf[2], np.zeros((4, 3)))
+    PC.friction_and_straight_knee()
 
 
 def test_joint_rates_against_a_finite_difference_of_the_angles():
