@@ -74,7 +74,9 @@ extern "C" {
 #define QMPC_ST_FALLBACK 16  /* informational, NOT an error: the robot was solved by a slower engine than
                                 its class's first choice: the Schur-form engine (the fast engine's working-set
                                 slots were exhausted), or the one-kernel path after the decoupled path's engine
-                                kernel handed it back (more rank-1 events than its registers hold) */
+                                kernel handed it back (more rank-1 events than its registers hold), or a
+                                second time from a cold start after a warm start (qmpc_expert.h) that could not
+                                be repaired */
 #define QMPC_ST_NONFINITE 32 /* the result contains NaN / Inf (non-finite input) */
 #define QMPC_ST_COMPACTED 64 /* informational, NOT an error: the fast engine ran out of pool with
                                 constraints that had entered and left the working set again, and

@@ -90,7 +90,11 @@ int qmpc_reserve(qmpc_handle h);
  * those constraints first without search, drops the ones whose multiplier comes out negative, and
  * continues with the normal dual active-set iteration; (b) writes the final working set back.
  * The result is the same unique minimiser as a cold solve (the QP is strictly convex); only the
- * iteration path is shorter.  Row order must follow the robots (row b belongs to robot b of every
+ * iteration path is shorter.  The buffer is caller data and may hold ANYTHING -- a stale or another robot's set, ids on swing
+ * foot-steps, at or beyond 20 * horizon or negative (discarded before they index anything), duplicates and dependent rows
+ * (skipped), rows with the wrong sign of multiplier (dropped again); the 64-row class reads the first 32 entries of a row,
+ * a robot beyond 192 rows neither reads nor writes its row: any content yields the same minimiser
+ * (tests/test_gpu_warm_start.py).  Row order must follow the robots (row b belongs to robot b of every
  * call).  NULL switches warm starting off.  Warm-started solves take the one-kernel path in every size class (the
  * decoupled engine of the 128- / 192-row classes starts cold); qmpc_solve_commands always starts cold (warm starting is
  * wired into the record entry points). */

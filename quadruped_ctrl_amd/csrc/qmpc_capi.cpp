@@ -837,9 +837,9 @@ QmpcParams bind_params(const qmpc_ctx* c, int batch, const qmpc_inputs* in, cons
   }
   P.dbg_H = c->dbg_H; P.dbg_g = c->dbg_g; P.dbg_aux = c->dbg_aux; P.dbg_clk = c->dbg_clk;
   P.hint_iters = (c->order_hint && !capturing) ? c->d_hint_iters : nullptr;
-  // (selective warm start without usable counts -- hint off, captured call: the kernel compares the count array against a
-  //  threshold nobody reaches, so it needs the array; the counts it leaves there are not used while the hint is off)
-  if (c->ws && c->ws_min_iters > 0 && !P.hint_iters) P.hint_iters = c->d_hint_iters;
+  // (selective warm start without usable counts -- hint off, captured call: P.hint_iters stays null, which the kernel reads as
+  //  "nobody qualifies", and the call -- and every replay of it -- leaves d_hint_iters alone: a later eager call of the batch
+  //  size in hint_batch never selects or orders by counts that an unrelated call wrote)
   P.cu_slots = c->d_cu_slots; P.bal_debug = c->bal_debug;
   P.ovpool = c->d_ovpool; P.ov_nslice = c->ov_nslice; P.ov_flags = c->d_ovflags; P.ov_spin = c->ov_spin;
   P.evpool = c->d_evpool; P.evflags = c->d_evflags; P.ev_nslot = c->ev_nslot;

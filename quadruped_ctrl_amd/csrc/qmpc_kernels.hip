@@ -542,7 +542,8 @@ __device__ __forceinline__ void qmpc_census_dump(Smem<RB>& S, const QmpcParams& 
 // resident) instead of LDS and the workgroup moves on; the active set is run by qmpc_engine_kernel
 // (qmpc_engine.hip) -- a workgroup of the large classes no longer pins a whole CU while one of its waves iterates.
 template <int RB, bool V5, bool CMD, bool ADMM = false, bool WARM = false, bool PHA = false, bool BIG = false, bool PRIO = false>
-__device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>& S, const QmpcParams& PK) {
+__device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>& S, const QmpcParams& PK,
+                                          const bool ws_cold = false) {  // (WARM: ignore the robot's previous working set)
   using C = Cfg<RB>;
   constexpr int NP = C::NP, CW = C::CW, NT = C::NT, KMAX = C::KMAX, KW = C::KW, RE = C::RE;
   const QmpcParams& P = S.par;  // parked copy: everything after stage 0
@@ -2439,7 +2440,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       int cand = -1;
       // (selective: a robot the previous call found easy starts cold -- a cold dual active set needs ~|W*| iterations
       //  anyway, and a wrong guess costs two events; wave-uniform scalar load)
-      bool ws_take = WARM && P.ws != nullptr;
+      bool ws_take = WARM && P.ws != nullptr && !ws_cold;
       if (WARM && ws_take && P.ws_min_iters > 0) ws_take = P.hint_iters != nullptr && P.hint_iters[rid] >= P.ws_min_iters;
       if (WARM && ws_take && lane < (KS < QMPC_WS_STRIDE ? KS : QMPC_WS_STRIDE)) {
         const int eg = P.ws[(size_t)rid * QMPC_WS_STRIDE + lane];  // global id 5 * (4 step + foot) + type
@@ -3440,6 +3441,22 @@ __device__ __forceinline__ void solve_robot(const int rid, const int tid, Smem<R
     bool again;
     if (Cfg<RB>::GLOBAL_EVENTS && S.evslot < 0) again = true;  // no pool slice (pool_acquire timed out): Schur form only
     else again = solve_one<RB, true, CMD, false, WARM, false, false, PRIO>(rid, tid, S, P);
+    bool warm_again = false;
+    if constexpr (WARM) {
+      // a warm start that asked for the re-run (a guess the repair phase could not mend within the iteration limit, or one
+      // that cost it its slots, its pool or definiteness) starts over COLD with the SAME engine first: that is the run the
+      // cold kernel makes, with the cold kernel's capacity -- the Schur-form engine of the 192-row class holds 64 working-set
+      // rows where this one holds 128, and a robot with more active rows ended QMPC_ST_WS_FULL there (found by
+      // tests/test_gpu_warm_start.py, family H7).  Only what the cold start cannot do either goes on to the Schur form
+      // (not a robot without a pool slice: the event engine did not run and cannot)
+      if (again && P.ws && !(Cfg<RB>::GLOBAL_EVENTS && S.evslot < 0)) {
+        __syncthreads();
+        int tid2 = tid;
+        asm volatile("" : "+v"(tid2));
+        again = solve_one<RB, true, CMD, false, WARM>(rid, tid2, S, P, true);
+        warm_again = true;
+      }
+    }
     if (again) {
       __syncthreads();
       // opaque thread id: without it the compiler keeps per-thread values of the
@@ -3449,6 +3466,9 @@ __device__ __forceinline__ void solve_robot(const int rid, const int tid, Smem<R
       solve_one<RB, false, CMD, false, WARM>(rid, tid2, S, P);
       __syncthreads();
       if (tid2 == 0) P.status[rid] |= QMPC_DEV_ST_FALLBACK;  // informational
+    } else if (WARM && warm_again) {
+      __syncthreads();
+      if (tid == 0) P.status[rid] |= QMPC_DEV_ST_FALLBACK;  // informational: solved twice
     }
   } else {
     solve_one<RB, false, CMD, false, WARM>(rid, tid, S, P);
