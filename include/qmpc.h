@@ -30,6 +30,9 @@
  * solved (QMPC_ST_WS_FULL, QMPC_ST_INFEASIBLE) reads zero forces -- never a previous
  * call's values and never an abandoned, primal-infeasible iterate -- and in command
  * mode its controller state is advanced like everybody else's.
+ * A robot stopped by the iteration cap (QMPC_ST_MAXITER) is NOT zeroed: grf and soln
+ * hold the iterate it stopped at, which violates at least one constraint (see
+ * QMPC_ST_MAXITER below); its controller state is advanced as well.
  *
  * Streams: a handle owns device state (coefficient tables, size-class work lists and
  * their counters) that ONE stream at a time orders.  Calls on the same stream need
@@ -66,7 +69,15 @@ extern "C" {
 #define QMPC_ERR_STATE 3   /* call order (solve before setup) */
 
 /* per-robot status bits */
-#define QMPC_ST_MAXITER 1    /* active-set iteration limit reached */
+#define QMPC_ST_MAXITER 1    /* active-set iteration limit reached (qmpc_settings).  The robot returns the iterate of the
+                                dual method it stopped at: the EXACT minimiser of the objective over its current
+                                working set (those rows hold with equality, their multipliers are >= 0), hence a lower
+                                objective than the solution's -- and CONSTRAINT-VIOLATING: at least one row outside
+                                the working set is violated by more than the tolerance (a friction cone left, fz above
+                                f_max, fz < 0 are all possible).  It is not zeroed.  The iteration only stops between
+                                two adds, never inside a step (a point part of the way along a step minimises
+                                nothing).  A robot whose solve needs no more than max_iter working-set changes is
+                                untouched by the cap, bit for bit */
 #define QMPC_ST_NOT_PD 2     /* condensed Hessian not positive definite */
 #define QMPC_ST_INFEASIBLE 4 /* constraints inconsistent (cannot happen for
                                 friction pyramids with f_max >= 0) */
@@ -137,7 +148,15 @@ int qmpc_set_robot(qmpc_handle h, double mass, const double ibody_diag[3],
 /* Replaces update_solver_settings (convexMPC_interface.cpp:107-119): the
  * reference's JCQP knobs have no meaning for the exact active-set solve;
  * what remains is the iteration cap (the role of nWSR=100,
- * SolverMPC.cpp:435) and the constraint-violation tolerance [N]. */
+ * SolverMPC.cpp:435) and the constraint-violation tolerance [N].
+ *   max_iter  > 0 (default 1000).  `iters` counts working-set changes: one per constraint added, one per constraint
+ *             dropped.  The cap is looked at when the NEXT constraint is chosen, so a robot stops (QMPC_ST_MAXITER)
+ *             with iters >= max_iter: iters may exceed max_iter by the drops of the last add.  A robot that another
+ *             engine solves again (QMPC_ST_FALLBACK) is counted from 0 by that engine, under the same cap.
+ *   tol       >= 0, in NEWTONS on NORMALISED rows (default 1e-9): a friction row  fz +- fx / mu >= 0  is divided by its
+ *             norm sqrt(1 + mu^-2), the row  f_max - fz >= 0  has norm 1.  The solve ends when no row outside the
+ *             working set is violated by more than tol; a larger tol ends the same path earlier.
+ * QMPC_ERR_ARG (max_iter <= 0, tol negative or NaN) leaves both settings as they were. */
 int qmpc_settings(qmpc_handle h, int max_iter, double tol);
 
 /* The reference's SPARSE formulation: SparseCMPC (src/MPC_Ctrl/SparseCMPC.cpp:31-73) keeps

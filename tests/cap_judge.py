@@ -1,0 +1,270 @@
+"""The judge of a CAPPED exact solve (tests/test_gpu_iteration_cap.py, tests/test_cap_judge_cpu.py): pure numpy.
+
+qmpc_settings(max_iter, tol) stops the Goldfarb-Idnani iteration early.  The three engines do not take the same path
+(their selection keys drop 9 or 10 bits of the violation), so a capped result cannot be judged against another engine.
+What the METHOD guarantees of every iterate it can stop at is the judge (k = the cap, c = the robot's count with the cap
+lifted, T = the tolerance; a robot is `flagged` when it carries QMPC_ST_MAXITER):
+
+  2. flagged  ->  k <= iters < c;  a robot whose uncapped run never dropped a row (c == |active set of its solution|) is
+     flagged exactly when c > k, and then iters == k (`counts`).
+  3. x minimises the QP that keeps only the rows ACTIVE at x -- normalised residual below 1e-7 N in magnitude -- : the method
+     stops between two adds, where x is the minimiser on its working set with non-negative multipliers.  The sub-QP is
+     solved by the reference's qpOASES (cap lifted) and x lies within the family's tolerance of that; a flagged x has a
+     row violated by more than T; its objective is at most the optimum's and does not decrease with the cap (`minimiser`,
+     `violation`, `objective`).
+  5. tol = T: iters(T) <= iters(1e-9), no row violated by more than T, and 3.
+
+A row whose residual lies in BAND = (1e-7, 1e-5) would make "active" a matter of rounding: such a (robot, cap) pair is
+left out of 3 (`minimiser` returns None) and counted; the fp64 model leaves out none (test_cap_judge_cpu.py).
+
+`model` is warm_sets.gi_iters with the kernels' flag rule (converged is looked at before the cap); `mid_add_iterates` is
+a copy of that loop which returns INSIDE the inner loop, after a partial step and before the constraint is in: points
+that minimise nothing, which the judge must refuse.
+"""
+import numpy as np
+
+import warm_sets as WS
+from oracle import kron_model as K
+from oracle import oracle as O
+
+ACT_EPS = WS.ACT_EPS              # 1e-7 N: the feasibility slack of tests/test_gpu_warm_start.py
+BAND = (1e-7, 1e-5)
+BIG = float(np.float32(5e10))     # the reference's "no upper bound" (SolverMPC.cpp:15)
+SLOTS64 = 32                      # working-set slots of the 64-row class's fast engine (warm_sets.lanes_read)
+# tolerances of the families' existing UNCAPPED comparisons: relative x in general (test_gpu_stress), the many-active
+# family (test_many_active_constraints_engine_fallback), and beyond 192 rows on the fp64 model's QP
+# (test_stress_large_problems: x, relative objective, infeasibility)
+X_TOL, X_TOL_MANY, BIG_TOL = 1e-8, 1e-7, (1e-6, 1e-12, 1e-9)
+
+
+def many_active():
+    """The record of test_many_active_constraints_engine_fallback (tests/test_gpu_parity.py)."""
+    from quadruped_ctrl_amd import workloads as W
+    b = W.make_config(1, batch=12)
+    b["f_max"] = 22.0
+    b["traj"].reshape(12, 10, 12)[:, :, 10] = 3.0
+    b["traj"].reshape(12, 10, 12)[:, :, 4] += 0.5
+    b["weights"][:, 10] = 50.0
+    b["weights"][:, 4] = 200.0
+    return b
+
+
+def _records():
+    from quadruped_ctrl_amd import workloads as W
+    # record -> (maker, x tolerance or BIG_TOL, caps judged besides the three computed ones)
+    return {
+        "trot": (lambda: W.make_config(1, batch=24), X_TOL, ()),
+        "mixed": (lambda: W.make_config(4, batch=48), X_TOL, ()),
+        "standing_h10": (lambda: W.make_standing(16, 10), X_TOL, (20,)),
+        "standing_h14": (lambda: W.make_standing(12, 14), X_TOL, ()),
+        "many_active": (many_active, X_TOL_MANY, ()),
+        "trot_h36": (lambda: W.make_long_horizon(8, 36, "trot"), BIG_TOL, ()),
+    }
+
+
+RECORDS = _records()
+MIXED = ("mixed",)                # families whose robots differ widely in count: the middle cap must leave some alone
+
+
+def caps_of(counts):
+    """The judged caps of a family: 1, half the median uncapped count, the largest uncapped count minus 1."""
+    c = np.asarray(counts)
+    return sorted({1, max(1, int(np.median(c)) // 2), max(1, int(c.max()) - 1)})
+
+
+def take(b, idx):
+    """The robots `idx` of a record, in that order."""
+    B = int(b["batch"])
+    out = {k: (np.ascontiguousarray(v[idx]) if isinstance(v, np.ndarray) and v.shape[:1] == (B,) else v) for k, v in b.items()}
+    out["batch"] = len(idx)
+    return out
+
+
+# ---- a robot's rows and QP
+def var_index(b, i):
+    """Positions of robot i's reduced variables in its full solution [12 h]."""
+    return (3 * WS.stance(b, i)[:, None] + np.arange(3)).reshape(-1)
+
+
+def all_ids(b, i):
+    return [5 * int(k) + t for k in WS.stance(b, i) for t in range(5)]
+
+
+def residuals(b, i, x):
+    """(ids, r): the normalised residuals [N] of every row of robot i at the reduced solution x; r >= 0 is feasible.
+    Friction rows are divided by their norm sqrt(mu^-2 + 1), as the engines' selection does; the f_max row has norm 1."""
+    ids = all_ids(b, i)
+    Cm, d = WS.coef_rows(b, i, ids)
+    mi = WS.mu_inv(b)
+    nrm = np.array([1.0 if e % 5 == 4 else 1.0 / np.sqrt(mi * mi + 1.0) for e in ids])
+    return ids, (Cm @ np.asarray(x, np.float64) - d) * nrm
+
+
+def violation(b, i, x):
+    """Worst normalised violation [N] (0 when feasible)."""
+    _, r = residuals(b, i, x)
+    return float(max(-r.min(), 0.0)) if r.size else 0.0
+
+
+def active_rows(b, i, x, eps=ACT_EPS):
+    ids, r = residuals(b, i, x)
+    return [e for e, v in zip(ids, r) if abs(v) < eps]
+
+
+def rank_active(b, i, x):
+    """Rank of the active rows: the size of the working set x is the minimiser on (a fourth friction row of an apex and
+    the like are active without being in it, and are dependent)."""
+    act = active_rows(b, i, x)
+    return int(np.linalg.matrix_rank(WS.coef_rows(b, i, act)[0])) if act else 0
+
+
+def in_band(b, i, x):
+    _, r = residuals(b, i, x)
+    a = np.abs(r)
+    return bool(((a > BAND[0]) & (a < BAND[1])).any())
+
+
+def model_qp(b, i):
+    """Robot i's reduced QP in the fp64 Kronecker model (what stands in beyond 192 rows, and on the host)."""
+    H, g = K.assemble(b, i)
+    vi = var_index(b, i)
+    return H[np.ix_(vi, vi)], g[vi]
+
+
+def objective(H, g, x):
+    return float(0.5 * x @ H @ x + g @ x)
+
+
+def objective_slack(H, g, x):
+    """Rounding of an fp64 evaluation of the objective: n u sum|terms| with n <= 432 and u = 1.1e-16 is 5e-14 sum|terms|;
+    1e-12 sum|terms| leaves a factor 20 for the iterate's own rounding."""
+    a = np.abs(x)
+    return 1e-12 * float(0.5 * a @ np.abs(H) @ a + np.abs(g) @ a)
+
+
+def sub_qp(b, i, ids):
+    """(A, lb, ub): the rows `ids` alone, as qpOASES takes them."""
+    Cm, d = WS.coef_rows(b, i, ids)
+    return Cm, d, np.full(len(ids), BIG)
+
+
+def minimiser(b, i, H, g, x, tol):
+    """Property 3 for one iterate.  None: a row's residual lies in BAND, the pair is left out.  Otherwise
+    (passed, distances): `tol` a relative x tolerance, distances = (x,); or BIG_TOL, distances = (x, objective,
+    infeasibility) on the sub-QP as in test_stress_large_problems."""
+    if in_band(b, i, x):
+        return None
+    x = np.asarray(x, np.float64)
+    act = active_rows(b, i, x)
+    if act:
+        A, lb, ub = sub_qp(b, i, act)
+        xs, _, _, rc, irc = O.qpoases(H, g, A, lb, ub, nwsr=100000)
+        assert rc == 0 and irc == 0, (i, rc, irc)
+    else:
+        xs = -np.linalg.solve(H, g)
+    dx = float(np.abs(x - xs).max() / max(np.abs(xs).max(), 1.0))
+    if not isinstance(tol, tuple):
+        return dx < tol, (dx,)
+    fs = objective(H, g, xs)
+    df = abs(objective(H, g, x) - fs) / max(abs(fs), 1e-30)
+    inf = float(np.maximum(lb - A @ x, 0).max()) if act else 0.0
+    return (dx < tol[0] and df < tol[1] and inf < tol[2]), (dx, df, inf)
+
+
+# ---- property 2
+def never_dropped(b, soln, iters):
+    """[B] bool: the uncapped count equals the number of rows active at the uncapped solution (as in test_gpu_warm_start)."""
+    return np.array([int(iters[i]) == len(WS.active_set(b, soln[i], i)) for i in range(int(b["batch"]))])
+
+
+def counts(k, flagged, iters, c, nd):
+    """Property 2 over a batch; raises AssertionError naming the robot."""
+    for i in range(len(c)):
+        if flagged[i]:
+            assert k <= iters[i] < c[i], ("flagged outside k <= iters < c", i, k, int(iters[i]), int(c[i]))
+        if c[i] <= k:
+            assert not flagged[i], ("flagged with c <= k", i, k, int(c[i]))
+        if nd[i]:
+            assert bool(flagged[i]) == bool(c[i] > k), ("never dropped: flagged must be c > k", i, k, int(c[i]))
+            if flagged[i]:
+                assert iters[i] == k, ("never dropped: iters must be k", i, k, int(iters[i]))
+
+
+# ---- the fp64 model with the kernels' flag rule
+def model(b, i, H, g, max_iter=1000, tol=1e-9):
+    """-> (x, iters, flagged).  The kernels look for a violated row first and at the cap second: flagged means the
+    loop stopped on the cap with a row still violated by more than tol."""
+    x, _, it = WS.gi_iters(b, i, H, g, tol=tol, max_iter=max_iter)
+    return x, it, bool(it >= max_iter and violation(b, i, x) > tol)
+
+
+def full_solution(b, i, x):
+    s = np.zeros(12 * int(b["horizon"]))
+    s[var_index(b, i)] = x
+    return s
+
+
+def mid_add_iterates(b, i, H, g, tol=1e-9, min_step=1e-3):
+    """warm_sets.gi_iters' cold loop, returning the iterates INSIDE the inner loop: x after a partial step (a row was
+    dropped, the constraint being added is still violated and not in the working set) that moved x by more than
+    min_step N.  -> list of x."""
+    allid = all_ids(b, i)
+    Ca, da = WS.coef_rows(b, i, allid)
+    mi = WS.mu_inv(b)
+    nrm = np.array([1.0 if e % 5 == 4 else 1.0 / np.sqrt(mi * mi + 1.0) for e in allid])
+    Hi = np.linalg.inv(H)
+    x = -Hi @ g
+    Wk, lam, out = [], np.zeros(0), []
+
+    def operators():
+        if not Wk:
+            return Hi, np.zeros((0, g.size))
+        N = Ca[Wk].T
+        S = np.linalg.inv(N.T @ Hi @ N)
+        Ns = S @ N.T @ Hi
+        return Hi - Hi @ N @ Ns, Ns
+
+    for _ in range(1000):
+        viol = (Ca @ x - da) * nrm
+        viol[Wk] = 0.0
+        p = int(np.argmin(viol))
+        if not viol[p] < -tol:
+            break
+        lp = 0.0
+        while True:
+            P, Ns = operators()
+            c = Ca[p]
+            z, r = P @ c, Ns @ c
+            delta = c @ z
+            dep = not delta > 1e-11 * (c @ Hi @ c)
+            t2 = np.inf if dep else -(c @ x - da[p]) / delta
+            ratio = np.where(r > 0, np.maximum(lam, 0.0) / np.where(r > 0, r, 1.0), np.inf) if Wk else np.zeros(0)
+            t1 = ratio.min() if Wk else np.inf
+            t = min(t1, t2)
+            assert np.isfinite(t), "infeasible"
+            if not dep:
+                x = x + t * z
+            lam = lam - t * r
+            lp += t
+            if t2 <= t1:
+                Wk.append(p)
+                lam = np.append(lam, lp)
+                break
+            l = int(np.argmin(ratio))
+            Wk.pop(l)
+            lam = np.delete(lam, l)
+            if not dep and np.abs(t * z).max() > min_step:
+                out.append(x.copy())            # <- the return inside the inner `while`
+    return out
+
+
+def negated_multiplier(b, i, H, g):
+    """(g', x): the uncapped optimum x of (H, g) and a gradient g' under which x is still the minimiser ON its active
+    rows but the largest multiplier has changed sign: H x + g' = C' lam' with lam'_j = -lam_j.  x does not minimise
+    the QP that keeps those rows as inequalities; the judge must refuse it."""
+    x, Wk, _ = WS.gi_iters(b, i, H, g)
+    Cm, d = WS.coef_rows(b, i, Wk)
+    _, lam = WS.eqp_multipliers(H, g, Cm, d)
+    j = int(np.argmax(lam))
+    assert lam[j] > 1e-3, lam
+    return g - 2.0 * lam[j] * Cm[j], x
