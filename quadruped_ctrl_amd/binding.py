@@ -85,6 +85,22 @@ class PlantView(C.Structure):
                                                                ("mu_plant", C.c_double)]
 
 
+# qmpc_plant_stats' arrays (include/qmpc_plant_vary.h) in declaration order: name -> typestr, [B] each
+PLANT_STATS_FIELDS = dict(n="<i4", z_min="<f8", z_max="<f8", roll_max="<f8", pitch_max="<f8", vx_sum="<f8", vy_sum="<f8")
+# qmpc_plant_params' members in declaration order: name -> elements per robot
+PLANT_PARAM_FIELDS = dict(mass=1, ibody=3, mu=1, force=3, torque=3)
+
+
+class PlantParams(C.Structure):
+    """qmpc_plant_params (include/qmpc_plant_vary.h)."""
+    _fields_ = [(n, C.c_void_p) for n in PLANT_PARAM_FIELDS]
+
+
+class PlantStats(C.Structure):
+    """qmpc_plant_stats (include/qmpc_plant_vary.h)."""
+    _fields_ = [(n, C.c_void_p) for n in PLANT_STATS_FIELDS] + [("batch", C.c_int), ("enabled", C.c_int)]
+
+
 class LegCommand(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in LEG_F32] + [("kp_joint", C.c_float), ("kd_joint", C.c_float)]
 
@@ -191,9 +207,17 @@ PLANT_SIGNATURES = {
     "qmpc_plant_step": [_P, _I, _P, _P, _P, _P],
     "qmpc_plant_view_get": [_P, C.POINTER(PlantView)],
 }
+# per-robot plant parameters and on-device statistics (include/qmpc_plant_vary.h), same library and ABI version
+PLANT_VARY_SIGNATURES = {
+    "qmpc_plant_set_params": [_P, _I, C.POINTER(PlantParams)],
+    "qmpc_plant_stats_enable": [_P, _I],
+    "qmpc_plant_stats_reset": [_P, _I, _P, _P],
+    "qmpc_plant_stats_get": [_P, C.POINTER(PlantStats)],
+}
 EXPORTS = list(SIGNATURES)
 CTRL_EXPORTS = list(CTRL_SIGNATURES)
 PLANT_EXPORTS = list(PLANT_SIGNATURES)
+PLANT_VARY_EXPORTS = list(PLANT_VARY_SIGNATURES)
 
 _lib = None
 
@@ -227,7 +251,7 @@ def load_library():
                 f"{LIB_PATH} not found: build the HIP extension first "
                 "(python -c 'import __graft_entry__ as g; g.build()')")
         lib = C.CDLL(LIB_PATH)
-        for name, sig in {**SIGNATURES, **CTRL_SIGNATURES, **PLANT_SIGNATURES}.items():
+        for name, sig in {**SIGNATURES, **CTRL_SIGNATURES, **PLANT_SIGNATURES, **PLANT_VARY_SIGNATURES}.items():
             f = getattr(lib, name)
             f.argtypes, f.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
         _lib = lib
@@ -776,6 +800,7 @@ class BatchedPlant:
     def __init__(self, ctrl):
         self.ctrl, self.torch, self.lib, self.device = ctrl, ctrl.torch, ctrl.lib, ctrl.device
         self.batch = None
+        self._params = {}
 
     def _xyyaw(self, xyyaw):
         if xyyaw is None:
@@ -789,6 +814,7 @@ class BatchedPlant:
                                                       self._xyyaw(init_xyyaw), self.ctrl._s(stream)), "qmpc_plant_init")
         self.batch = self.ctrl.batch
         self._keep = init_xyyaw
+        self._params = {}     # (qmpc_plant_init unbinds: a new plant is the plain plant)
         v = self.view()
         self.state, self.motor = v["state"], v["motor"]
         self.effort = self.torch.zeros((self.batch, 12), dtype=self.torch.float64, device=self.device)
@@ -823,6 +849,51 @@ class BatchedPlant:
         res = {k: self.torch.as_tensor(_DeviceArray(getattr(v, k), (v.batch, n), ts, self.ctrl), device=self.device)
                for k, (n, ts) in PLANT_VIEW_FIELDS.items()}
         res["batch"], res["substeps"], res["mu_plant"] = v.batch, v.substeps, v.mu_plant
+        return res
+
+
+    # -- include/qmpc_plant_vary.h -------------------------------------------------------------------------------------
+    def set_params(self, mass=None, ibody=None, mu=None, force=None, torque=None):
+        """Per-robot body, floor and pushes of the PLANT (the controller is not told): float64 device tensors mass [B],
+        ibody [B,3], mu [B], force [B,3] (world frame, N, on the body origin), torque [B,3] (body frame, N m); None keeps
+        the handle's value / none.  The plant reads the tensors at every later step -- write into them in place (on the
+        stream) to change a push, also between replays of a captured graph; they are kept referenced here.  All None
+        unbinds; init() unbinds, reset() does not."""
+        if self.batch is None:
+            raise QmpcError("qmpc_plant_set_params before init()")
+        given = dict(mass=mass, ibody=ibody, mu=mu, force=force, torque=torque)
+        prm = PlantParams()
+        for name, per_robot in PLANT_PARAM_FIELDS.items():
+            t = given[name]
+            if t is not None:
+                shape = (self.batch,) if per_robot == 1 else (self.batch, per_robot)
+                setattr(prm, name, self.ctrl._chk(t, shape, self.torch.float64, name))
+        self.ctrl.mpc._check(self.lib.qmpc_plant_set_params(self.ctrl.mpc.h, self.batch, C.byref(prm)),
+                             "qmpc_plant_set_params")
+        self._params = {k: t for k, t in given.items() if t is not None}
+
+    def enable_stats(self, on=True):
+        """Per-robot statistics on the device, updated by every step while on (see stats()).  The first enable
+        allocates and synchronises, once."""
+        self.ctrl.mpc._check(self.lib.qmpc_plant_stats_enable(self.ctrl.mpc.h, 1 if on else 0), "qmpc_plant_stats_enable")
+
+    def reset_stats(self, mask=None, stream=None):
+        """The initial values (n 0, z_min +inf, z_max -inf, the rest 0) for the robots where mask is set; None: all."""
+        m = mask.to(self.torch.uint8).contiguous() if mask is not None else None
+        ptr = self.ctrl._chk(m, (self.ctrl.batch,), self.torch.uint8, "mask") if m is not None else None
+        self.ctrl.mpc._check(self.lib.qmpc_plant_stats_reset(self.ctrl.mpc.h, self.ctrl.batch or 0, ptr,
+                                                             self.ctrl._s(stream)), "qmpc_plant_stats_reset")
+        self._keep = m
+
+    def stats(self):
+        """qmpc_plant_stats_get as zero-copy device tensors [B] that alias the accumulators, like view(): n (int32),
+        z_min, z_max, roll_max, pitch_max, vx_sum, vy_sum (float64); plus batch, enabled.  A window's mean velocity is
+        the difference of two (copied) reads of a sum over the difference of n.  Read-only by contract."""
+        v = PlantStats()
+        self.ctrl.mpc._check(self.lib.qmpc_plant_stats_get(self.ctrl.mpc.h, C.byref(v)), "qmpc_plant_stats_get")
+        res = {k: self.torch.as_tensor(_DeviceArray(getattr(v, k), (v.batch,), ts, self.ctrl), device=self.device)
+               for k, ts in PLANT_STATS_FIELDS.items()}
+        res["batch"], res["enabled"] = v.batch, bool(v.enabled)
         return res
 
 

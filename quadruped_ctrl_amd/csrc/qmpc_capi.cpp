@@ -19,6 +19,7 @@
 #include "../../include/qmpc_expert.h"  // tuning knobs whose default is the measured optimum, warm start
 #include "../../include/qmpc_ctrl.h"    // batched locomotion controller (same library)
 #include "../../include/qmpc_plant.h"   // reduced-order plant for it (same library)
+#include "../../include/qmpc_plant_vary.h"  // ... its per-robot parameters and on-device statistics
 #include "qmpc_device.h"
 #include "qmpc_glue.h"
 #include "qmpc_plan.h"  // the solve's launch plan (host-only)
@@ -117,7 +118,10 @@ extern "C" hipError_t qmpc_launch_plant_init(const QmpcPlantDev* S, const QmpcPl
                                              const double* xyyaw, int batch, hipStream_t stream);
 extern "C" hipError_t qmpc_launch_plant_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
                                              const float* contact_state, const float* p_des, const float* v_des,
-                                             double* state_out, double* motor_out, int batch, hipStream_t stream);
+                                             double* state_out, double* motor_out, int batch, hipStream_t stream,
+                                             const QmpcPlantVary* V, int vary, int stats);
+extern "C" hipError_t qmpc_launch_plant_stats_reset(const QmpcPlantVary* V, const uint8_t* mask, int batch,
+                                                    hipStream_t stream);
 extern "C" hipError_t qmpc_launch_swing(const float* p0, const float* pf, const float* height, const float* phase,
                                         const float* swing_time, float* p, float* v, float* a, int n_feet,
                                         hipStream_t stream);
@@ -232,6 +236,11 @@ struct qmpc_ctx {
     int batch = 0;  // robots initialised
     double mu = 0;
     int substeps = 1;
+    // qmpc_plant_vary.h: the caller's arrays as bound (all null: none), the statistics' allocation and switch
+    QmpcPlantVary vary{};
+    bool bound = false;
+    void* stats_buf = nullptr;
+    bool stats_on = false;
   };
   Plant* plant = nullptr;
 };
@@ -422,6 +431,7 @@ int qmpc_destroy(qmpc_handle h) {
     if (h->host_stream) hipStreamDestroy(h->host_stream);
     if (h->ctrl && h->ctrl->buf) hipFree(h->ctrl->buf);
     if (h->plant && h->plant->buf) hipFree(h->plant->buf);
+    if (h->plant && h->plant->stats_buf) hipFree(h->plant->stats_buf);
   }
   delete h->ctrl;
   delete h->plant;
@@ -1546,6 +1556,9 @@ int qmpc_plant_init(qmpc_handle c, int batch, double mu_plant, int substeps, con
   k->batch = batch;
   k->mu = mu_plant;
   k->substeps = substeps;
+  // a new plant is the plain plant: nothing bound (the statistics keep their switch and their values)
+  k->vary.mass = k->vary.ibody = k->vary.mu = k->vary.force = k->vary.torque = nullptr;
+  k->bound = false;
   return QMPC_OK;
 }
 
@@ -1569,8 +1582,11 @@ int qmpc_plant_step(qmpc_handle c, int batch, const double* effort, double* stat
   if (const int rc = order_after_previous(c, stream)) return rc;
   const QmpcCtrlDev& d = c->ctrl->d;
   const QmpcPlantConst K = plant_const(c, c->plant->mu, c->plant->substeps);
-  HIP_TRY(c, qmpc_launch_plant_step(&c->plant->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out,
-                                    batch, stream));
+  // nothing bound and the statistics off: the plain instantiation, which is given no QmpcPlantVary to read
+  const qmpc_ctx::Plant* k = c->plant;
+  const bool extra = k->bound || k->stats_on;
+  HIP_TRY(c, qmpc_launch_plant_step(&k->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out, batch,
+                                    stream, extra ? &k->vary : nullptr, k->bound, k->stats_on));
   return QMPC_OK;
 }
 
@@ -1590,6 +1606,78 @@ int qmpc_plant_view_get(qmpc_handle c, qmpc_plant_view* v) {
   v->batch = c->plant->batch;
   v->substeps = c->plant->substeps;
   v->mu_plant = c->plant->mu;
+  return QMPC_OK;
+}
+
+// ---- include/qmpc_plant_vary.h: per-robot parameters and statistics of the plant ----
+
+int qmpc_plant_set_params(qmpc_handle c, int batch, const qmpc_plant_params* prm) {
+  if (const int rc = plant_check(c, batch)) return rc;
+  qmpc_ctx::Plant* k = c->plant;
+  k->vary.mass = prm ? prm->mass : nullptr;
+  k->vary.ibody = prm ? prm->ibody : nullptr;
+  k->vary.mu = prm ? prm->mu : nullptr;
+  k->vary.force = prm ? prm->force : nullptr;
+  k->vary.torque = prm ? prm->torque : nullptr;
+  k->bound = k->vary.mass || k->vary.ibody || k->vary.mu || k->vary.force || k->vary.torque;
+  return QMPC_OK;
+}
+
+int qmpc_plant_stats_enable(qmpc_handle c, int on) {
+  if (!c) return QMPC_ERR_ARG;
+  if (!c->ctrl || !c->ctrl->batch || !c->plant || !c->plant->batch) return QMPC_ERR_STATE;
+  qmpc_ctx::Plant* k = c->plant;
+  if (on && !k->stats_buf) {
+    // acc[QMPC_PLANT_STATS][M] doubles, then n[M] ints; the initial values come from the host, which synchronises
+    DeviceGuard g(c->device);
+    const size_t M = (size_t)c->max_batch;
+    const size_t bytes = (QMPC_PLANT_STATS * sizeof(double) + sizeof(int)) * M;
+    std::vector<char> init(bytes, 0);
+    double* a = reinterpret_cast<double*>(init.data());
+    for (size_t b = 0; b < M; ++b) {
+      a[QMPC_PLANT_STAT_Z_MIN * M + b] = HUGE_VAL;
+      a[QMPC_PLANT_STAT_Z_MAX * M + b] = -HUGE_VAL;
+    }
+    void* buf = nullptr;
+    HIP_TRY(c, hipMalloc(&buf, bytes));
+    const hipError_t e = hipMemcpy(buf, init.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      hipFree(buf);
+      return fail(c, e, "hipMemcpy(plant statistics)");
+    }
+    k->stats_buf = buf;
+    k->vary.acc = static_cast<double*>(buf);
+    k->vary.n = reinterpret_cast<int*>(k->vary.acc + QMPC_PLANT_STATS * M);
+    k->vary.acc_stride = c->max_batch;
+  }
+  k->stats_on = on != 0;
+  return QMPC_OK;
+}
+
+int qmpc_plant_stats_reset(qmpc_handle c, int batch, const uint8_t* mask_dev, void* stream_) {
+  if (const int rc = plant_check(c, batch)) return rc;
+  if (!c->plant->stats_buf) return QMPC_ERR_STATE;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  HIP_TRY(c, qmpc_launch_plant_stats_reset(&c->plant->vary, mask_dev, batch, stream));
+  return QMPC_OK;
+}
+
+int qmpc_plant_stats_get(qmpc_handle c, qmpc_plant_stats* v) {
+  if (!c || !v) return QMPC_ERR_ARG;
+  if (!c->plant || !c->plant->batch || !c->plant->stats_buf) return QMPC_ERR_STATE;
+  const qmpc_ctx::Plant* k = c->plant;
+  const size_t M = (size_t)k->vary.acc_stride;
+  v->n = k->vary.n;
+  v->z_min = k->vary.acc + QMPC_PLANT_STAT_Z_MIN * M;
+  v->z_max = k->vary.acc + QMPC_PLANT_STAT_Z_MAX * M;
+  v->roll_max = k->vary.acc + QMPC_PLANT_STAT_ROLL_MAX * M;
+  v->pitch_max = k->vary.acc + QMPC_PLANT_STAT_PITCH_MAX * M;
+  v->vx_sum = k->vary.acc + QMPC_PLANT_STAT_VX_SUM * M;
+  v->vy_sum = k->vary.acc + QMPC_PLANT_STAT_VY_SUM * M;
+  v->batch = k->batch;
+  v->enabled = k->stats_on ? 1 : 0;
   return QMPC_OK;
 }
 

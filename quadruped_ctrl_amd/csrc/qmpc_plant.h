@@ -34,6 +34,25 @@ struct QmpcPlantConst {
   int substeps;
 };
 
+// include/qmpc_plant_vary.h: the caller's per-robot arrays (null: the handle's value / none) and the statistics'
+// accumulators (one allocation for max_batch robots, made by the first qmpc_plant_stats_enable: acc[k][max_batch] in the
+// order of QMPC_PLANT_STAT_*, then n[max_batch]).  By value, after the step's other arguments; the plain instantiation
+// reads none of it.
+struct QmpcPlantVary {
+  const double* mass;    // [B]
+  const double* ibody;   // [B][3]
+  const double* mu;      // [B]
+  const double* force;   // [B][3] world
+  const double* torque;  // [B][3] body
+  double* acc;           // [QMPC_PLANT_STATS][acc_stride]
+  int* n;                // [B] steps accumulated
+  int acc_stride;        // max_batch
+};
+enum {
+  QMPC_PLANT_STAT_Z_MIN, QMPC_PLANT_STAT_Z_MAX, QMPC_PLANT_STAT_ROLL_MAX, QMPC_PLANT_STAT_PITCH_MAX,
+  QMPC_PLANT_STAT_VX_SUM, QMPC_PLANT_STAT_VY_SUM, QMPC_PLANT_STATS
+};
+
 #define QMPC_PLANT_GRAVITY 9.81
 #define QMPC_PLANT_HEIGHT 0.29      /* ConvexMPCLocomotion::_body_height */
 #define QMPC_PLANT_SIDE_OFFSET 0.065

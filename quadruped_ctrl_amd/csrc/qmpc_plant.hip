@@ -225,12 +225,17 @@ __global__ __launch_bounds__(256) void qmpc_plant_init_kernel(const QmpcPlantDev
 
 // One control period.  n = batch * 4 lanes; the lanes past n in the last wave repeat lane n - 1 and store nothing, so
 // that every shuffle has its partner.
+// VARY (include/qmpc_plant_vary.h): the robot's own mass, inertia and friction where the caller bound an array (every
+// lane of the quad loads its robot's values once, before the substeps: the same address in four lanes), and an external
+// force / moment added to the quad sums.  STATS: the lane that writes the state row folds the new pose into the robot's
+// accumulators.  <false, false> reads nothing of V and is the plain step.
+template <bool VARY, bool STATS>
 __global__ __launch_bounds__(256) void qmpc_plant_step_kernel(const QmpcPlantDev S, const QmpcPlantConst K,
                                                               const double* __restrict__ effort,
                                                               const float* __restrict__ contact_state,
                                                               const float* __restrict__ p_des,
                                                               const float* __restrict__ v_des, double* state_out,
-                                                              double* motor_out, const int n) {
+                                                              double* motor_out, const int n, const QmpcPlantVary V) {
 #pragma clang fp contract(off)
   const int t = blockIdx.x * 256 + threadIdx.x;
   const bool live = t < n;
@@ -251,6 +256,22 @@ __global__ __launch_bounds__(256) void qmpc_plant_step_kernel(const QmpcPlantDev
   const bool stance = contact_state[tt] > 0.f;
   if (stance && !S.stance[tt]) c[2] = 0.0;  // touch-down: pinned on the ground plane
   double f[3] = {0.0, 0.0, 0.0}, vdot[3] = {0.0, 0.0, 0.0};
+  // the robot's own constants and the external wrench (VARY only; a member that is not bound keeps the handle's value)
+  double mass_b = K.mass, mu_b = K.mu, ib_b[3] = {K.ibody[0], K.ibody[1], K.ibody[2]};
+  double fext[3] = {0.0, 0.0, 0.0}, text[3] = {0.0, 0.0, 0.0};
+  if constexpr (VARY) {
+    if (V.mass) mass_b = V.mass[b];
+    if (V.mu) mu_b = V.mu[b];
+    for (int k = 0; k < 3; ++k) {
+      if (V.ibody) ib_b[k] = V.ibody[(size_t)b * 3 + k];
+      if (V.force) fext[k] = V.force[(size_t)b * 3 + k];
+      if (V.torque) text[k] = V.torque[(size_t)b * 3 + k];
+    }
+  }
+  // (the plain step reads K where it always did: with the inertia copied into a local array in front of the loop it
+  //  took 225 VGPRs and parked 17 scalar registers in scratch -- tests/test_plant_varied_cpu.py holds 221 and none)
+  const double mass = VARY ? mass_b : K.mass, mu = VARY ? mu_b : K.mu;
+  const double* ib = VARY ? ib_b : K.ibody;
   for (int s = 0; s < K.substeps; ++s) {
     double R[9], rb[3], fb[3], m[3];
     plant_rot(q, R);
@@ -270,7 +291,7 @@ __global__ __launch_bounds__(256) void qmpc_plant_step_kernel(const QmpcPlantDev
           f[0] = -Fw[0];
           f[1] = -Fw[1];
           f[2] = -Fw[2];
-          const double ft = sqrt(f[0] * f[0] + f[1] * f[1]), cap = K.mu * f[2];
+          const double ft = sqrt(f[0] * f[0] + f[1] * f[1]), cap = mu * f[2];
           if (ft > cap) {
             const double sc = cap / ft;
             f[0] = f[0] * sc;
@@ -286,15 +307,21 @@ __global__ __launch_bounds__(256) void qmpc_plant_step_kernel(const QmpcPlantDev
       F[k] = plant_quad_sum(f[k]);
       N[k] = plant_quad_sum(m[k]);
     }
-    vdot[0] = F[0] / K.mass;
-    vdot[1] = F[1] / K.mass;
-    vdot[2] = F[2] / K.mass - QMPC_PLANT_GRAVITY;
-    const double Iw[3] = {K.ibody[0] * w[0], K.ibody[1] * w[1], K.ibody[2] * w[2]};
+    if constexpr (VARY) {
+      if (V.force)
+        for (int k = 0; k < 3; ++k) F[k] = F[k] + fext[k];
+      if (V.torque)
+        for (int k = 0; k < 3; ++k) N[k] = N[k] + text[k];
+    }
+    vdot[0] = F[0] / mass;
+    vdot[1] = F[1] / mass;
+    vdot[2] = F[2] / mass - QMPC_PLANT_GRAVITY;
+    const double Iw[3] = {ib[0] * w[0], ib[1] * w[1], ib[2] * w[2]};
     double wIw[3];
     plant_cross(w, Iw, wIw);
     for (int k = 0; k < 3; ++k) {
       v[k] = v[k] + K.h * vdot[k];
-      w[k] = w[k] + K.h * ((N[k] - wIw[k]) / K.ibody[k]);
+      w[k] = w[k] + K.h * ((N[k] - wIw[k]) / ib[k]);
     }
     for (int k = 0; k < 3; ++k) p[k] = p[k] + K.h * v[k];
     const double wn = sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
@@ -323,6 +350,45 @@ __global__ __launch_bounds__(256) void qmpc_plant_step_kernel(const QmpcPlantDev
     S.stance[tt] = stance ? 1 : 0;
   }
   plant_readout(S, K, tt, live, p, v, q, w, c, stance, vdot, p_des + o3, v_des + o3, state_out, motor_out);
+  if constexpr (STATS) {
+    if (live && leg == 0) {
+      // the state row's own numbers: p_z, the quaternion, rBody v (the read-out's expression again: the same bits)
+      double R[9], vb[3];
+      plant_rot(q, R);
+      plant_mulT(R, v, vb);
+      const double roll = atan2(2 * (q[2] * q[3] + q[0] * q[1]), 1 - 2 * (q[1] * q[1] + q[2] * q[2]));
+      double sp = 2 * (q[0] * q[2] - q[1] * q[3]);
+      if (sp > 1.0) sp = 1.0;
+      if (sp < -1.0) sp = -1.0;
+      const double pitch = asin(sp);
+      double* a = V.acc + b;  // a[k * acc_stride]: QMPC_PLANT_STAT_*
+      const size_t M = (size_t)V.acc_stride;
+      V.n[b] = V.n[b] + 1;
+      a[QMPC_PLANT_STAT_Z_MIN * M] = fmin(a[QMPC_PLANT_STAT_Z_MIN * M], p[2]);
+      a[QMPC_PLANT_STAT_Z_MAX * M] = fmax(a[QMPC_PLANT_STAT_Z_MAX * M], p[2]);
+      a[QMPC_PLANT_STAT_ROLL_MAX * M] = fmax(a[QMPC_PLANT_STAT_ROLL_MAX * M], fabs(roll));
+      a[QMPC_PLANT_STAT_PITCH_MAX * M] = fmax(a[QMPC_PLANT_STAT_PITCH_MAX * M], fabs(pitch));
+      a[QMPC_PLANT_STAT_VX_SUM * M] = a[QMPC_PLANT_STAT_VX_SUM * M] + vb[0];
+      a[QMPC_PLANT_STAT_VY_SUM * M] = a[QMPC_PLANT_STAT_VY_SUM * M] + vb[1];
+    }
+  }
+}
+
+// qmpc_plant_stats_reset (mask == NULL: every robot): one lane per robot
+__global__ __launch_bounds__(256) void qmpc_plant_stats_reset_kernel(const QmpcPlantVary V,
+                                                                     const uint8_t* __restrict__ mask, const int batch) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= batch) return;
+  if (mask && !mask[b]) return;
+  double* a = V.acc + b;
+  const size_t M = (size_t)V.acc_stride;
+  V.n[b] = 0;
+  a[QMPC_PLANT_STAT_Z_MIN * M] = __builtin_inf();
+  a[QMPC_PLANT_STAT_Z_MAX * M] = -__builtin_inf();
+  a[QMPC_PLANT_STAT_ROLL_MAX * M] = 0.0;
+  a[QMPC_PLANT_STAT_PITCH_MAX * M] = 0.0;
+  a[QMPC_PLANT_STAT_VX_SUM * M] = 0.0;
+  a[QMPC_PLANT_STAT_VY_SUM * M] = 0.0;
 }
 
 }  // namespace
@@ -334,11 +400,33 @@ extern "C" hipError_t qmpc_launch_plant_init(const QmpcPlantDev* S, const QmpcPl
   return hipGetLastError();
 }
 
+// V == NULL: the plain step.  Otherwise vary (per-robot parameters bound) and stats (statistics on) pick the instantiation.
 extern "C" hipError_t qmpc_launch_plant_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
                                              const float* contact_state, const float* p_des, const float* v_des,
-                                             double* state_out, double* motor_out, int batch, hipStream_t stream) {
+                                             double* state_out, double* motor_out, int batch, hipStream_t stream,
+                                             const QmpcPlantVary* V, int vary, int stats) {
   const int n = batch * 4;
-  hipLaunchKernelGGL(qmpc_plant_step_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, *S, *K, effort, contact_state,
-                     p_des, v_des, state_out, motor_out, n);
+  const dim3 grid((n + 255) / 256), block(256);
+  const QmpcPlantVary none{};
+  vary = V && vary;
+  stats = V && stats;
+#define QMPC_PLANT_STEP(VARY, STATS, v)                                                                            \
+  hipLaunchKernelGGL((qmpc_plant_step_kernel<VARY, STATS>), grid, block, 0, stream, *S, *K, effort, contact_state, \
+                     p_des, v_des, state_out, motor_out, n, v)
+  if (vary && stats)
+    QMPC_PLANT_STEP(true, true, *V);
+  else if (vary)
+    QMPC_PLANT_STEP(true, false, *V);
+  else if (stats)
+    QMPC_PLANT_STEP(false, true, *V);
+  else
+    QMPC_PLANT_STEP(false, false, none);
+#undef QMPC_PLANT_STEP
+  return hipGetLastError();
+}
+
+extern "C" hipError_t qmpc_launch_plant_stats_reset(const QmpcPlantVary* V, const uint8_t* mask, int batch,
+                                                    hipStream_t stream) {
+  hipLaunchKernelGGL(qmpc_plant_stats_reset_kernel, dim3((batch + 255) / 256), dim3(256), 0, stream, *V, mask, batch);
   return hipGetLastError();
 }

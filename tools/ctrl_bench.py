@@ -23,10 +23,12 @@ cheater estimators, no Kalman filter) instead of the sensor path (--source imu, 
 --source plant closes the loop on the device: qmpc_ctrl_tick_state on the read-out of the reduced-order plant
 (include/qmpc_plant.h), qmpc_plant_step on the tick's efforts -- states a walking robot visits.  Gaits from {0, 4, 5, 10},
 x commands over [0, 0.5] m/s and small yaw rates (the family tests/plant_loop.py walks on); the warm-up should cover the
-first steps (--warmup 260).  The tick and the plant step are timed separately (us_per_plant_step_median).
+first steps (--warmup 260).  The tick and the plant step are timed separately (us_per_plant_step_median).  --vary binds
+the per-robot body, floor and push of include/qmpc_plant_vary.h (the set the closed-loop tests walk on: payloads, floors, and a
+30 N lateral push during ticks 300 .. 349 of the run, written into the bound array between two ticks) and turns the plant's statistics on: the step then runs its <VARY, STATS> instantiation.
 
     python tools/ctrl_bench.py [--batches 1024,4096,16384] [--cycles 8] [--warmup 26] [--schedule lockstep|per_robot]
-                               [--stagger] [--robot-mode 0|1] [--source imu|state|plant] [--out FILE]
+                               [--stagger] [--robot-mode 0|1] [--source imu|state|plant] [--vary] [--out FILE]
 """
 import argparse
 import json
@@ -39,7 +41,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, source="imu"):
+def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, source="imu", vary=False):
     import torch
     from quadruped_ctrl_amd import workloads as W
     from quadruped_ctrl_amd.binding import BatchedController
@@ -74,6 +76,16 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
         plant = BatchedPlant(ctrl)
         xyyaw = np.stack([np.arange(B) % 128 * 1.0, np.arange(B) // 128 * 1.0, rng.uniform(-0.1, 0.1, B)], 1)
         plant.init(0.4, 1, torch.from_numpy(xyyaw).cuda())
+        if vary:   # tests/plant_loop_varied.py: variation(), restated (the tools do not import the test tree)
+            k = np.arange(B) % 16
+            scale = np.array([0.8, 1.0, 1.2, 1.4])[(k // 4) % 4]
+            push = np.zeros((B, 3))
+            push[:, 1] = np.where(k % 2 == 1, 30.0, -30.0)
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).cuda()
+            push, force = dev(push), dev(np.zeros((B, 3)))
+            plant.set_params(mass=dev(9.0 * scale), ibody=dev(np.array([0.07, 0.26, 0.242])[None, :] * scale[:, None]),
+                             mu=dev(np.array([0.3, 0.4, 0.6, 0.8])[k % 4]), force=force, torque=dev(np.zeros((B, 3))))
+            plant.enable_stats()
         imu, motor = plant.state.expand(26, B, 16), plant.motor.expand(26, B, 24)    # (every "slot" is the plant's read-out)
         tick = ctrl.tick_state
     elif source == "state":
@@ -96,6 +108,8 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
                 plant.step(eff)
     ev = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) for _ in range(n)]
     for t in range(n):
+        if vary and t in (300, 350):     # (outside the timed pairs: the push starts and ends)
+            force.copy_(push) if t == 300 else force.zero_()
         ev[t][0].record()
         tick(imu[t % 26], motor[t % 26], eff)
         ev[t][1].record()
@@ -112,6 +126,9 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
     res = {"batch": B, "source": source, "schedule": schedule, "stagger": bool(stagger), "robot_mode": robot_mode, "ticks_timed": int(keep.sum()),
            "us_per_tick_median": round(float(np.median(us[keep])), 2), "us_per_tick_max": round(float(us[keep].max()), 2),
            "robot_ticks_per_s_window": float(f"{B * int(keep.sum()) / (float(us[keep].sum()) * 1e-6):.4g}")}
+    if vary:
+        res["vary"] = True
+        res["stats_steps"] = int(plant.stats()["n"].min().item())
     if stagger or robot_mode == 1:
         res["robot_ticks_per_s"] = res["robot_ticks_per_s_window"]
         if robot_mode == 1:
@@ -142,15 +159,18 @@ def main():
     ap.add_argument("--stagger", action="store_true")
     ap.add_argument("--robot-mode", type=int, choices=(0, 1), default=0)
     ap.add_argument("--source", choices=("imu", "state", "plant"), default="imu")
+    ap.add_argument("--vary", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.vary and a.source != "plant":
+        ap.error("--vary needs --source plant")
     if a.robot_mode == 1:
         a.schedule = "per_robot"
     if a.stagger and a.schedule != "per_robot":
         ap.error("--stagger needs --schedule per_robot (a lockstep reset keeps the robot on the batch's MPC ticks)")
     out = []
     for B in [int(x) for x in a.batches.split(",")]:
-        r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source)
+        r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source, a.vary)
         print(json.dumps(r), flush=True)
         out.append(r)
     if a.out:
