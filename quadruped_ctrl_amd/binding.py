@@ -101,6 +101,20 @@ class PlantStats(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in PLANT_STATS_FIELDS] + [("batch", C.c_int), ("enabled", C.c_int)]
 
 
+# qmpc_sense_params' members (include/qmpc_sense.h) in declaration order: name -> elements per robot
+SENSE_PARAM_FIELDS = dict(acc_bias=3, gyro_bias=3, acc_sigma=1, gyro_sigma=1, q_sigma=1, qd_sigma=1)
+
+
+class SenseParams(C.Structure):
+    """qmpc_sense_params (include/qmpc_sense.h)."""
+    _fields_ = [(n, C.c_void_p) for n in SENSE_PARAM_FIELDS]
+
+
+class SenseView(C.Structure):
+    """qmpc_sense_view (include/qmpc_sense.h)."""
+    _fields_ = [("n", C.c_void_p), ("epoch", C.c_void_p), ("batch", C.c_int), ("seed", C.c_uint64)]
+
+
 class LegCommand(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in LEG_F32] + [("kp_joint", C.c_float), ("kd_joint", C.c_float)]
 
@@ -214,10 +228,19 @@ PLANT_VARY_SIGNATURES = {
     "qmpc_plant_stats_reset": [_P, _I, _P, _P],
     "qmpc_plant_stats_get": [_P, C.POINTER(PlantStats)],
 }
+# the sensor model between the plant and the controller's sensor path (include/qmpc_sense.h), same library and ABI version
+SENSE_SIGNATURES = {
+    "qmpc_sense_init": [_P, _I, C.c_uint64, _P],
+    "qmpc_sense_set_params": [_P, _I, C.POINTER(SenseParams)],
+    "qmpc_sense_reset": [_P, _I, _P, _P],
+    "qmpc_sense": [_P, _I, _P, _P, _P],
+    "qmpc_sense_view_get": [_P, C.POINTER(SenseView)],
+}
 EXPORTS = list(SIGNATURES)
 CTRL_EXPORTS = list(CTRL_SIGNATURES)
 PLANT_EXPORTS = list(PLANT_SIGNATURES)
 PLANT_VARY_EXPORTS = list(PLANT_VARY_SIGNATURES)
+SENSE_EXPORTS = list(SENSE_SIGNATURES)
 
 _lib = None
 
@@ -251,7 +274,8 @@ def load_library():
                 f"{LIB_PATH} not found: build the HIP extension first "
                 "(python -c 'import __graft_entry__ as g; g.build()')")
         lib = C.CDLL(LIB_PATH)
-        for name, sig in {**SIGNATURES, **CTRL_SIGNATURES, **PLANT_SIGNATURES, **PLANT_VARY_SIGNATURES}.items():
+        for name, sig in {**SIGNATURES, **CTRL_SIGNATURES, **PLANT_SIGNATURES, **PLANT_VARY_SIGNATURES,
+                          **SENSE_SIGNATURES}.items():
             f = getattr(lib, name)
             f.argtypes, f.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
         _lib = lib
@@ -897,6 +921,89 @@ class BatchedPlant:
         return res
 
 
+class BatchedSensors:
+    """The sensor model of include/qmpc_sense.h for a BatchedPlant's robots: sense() turns the plant's last read-out into
+    imu [B,10] / motor [B,24] float64 as ctrl.tick() takes them -- exactly (nothing bound) or with per-robot
+    accelerometer and gyro bias and white noise on the accelerometer, the gyro and the joint encoders (set_params).
+    tick -> plant.step -> sense is a closed loop through the controller's estimators without the host (see
+    rollout_sensed()); settle() first, or most of the fleet falls (the Kalman filter starts at height 0).
+
+    Constructed FROM a plant (the sensors live in the same handle), after plant.init().  Every call only enqueues on
+    the current stream (or `stream`).  `imu` / `motor` are the sensors' own output tensors, rewritten by sense()."""
+
+    def __init__(self, plant):
+        self.plant, self.ctrl = plant, plant.ctrl
+        self.torch, self.lib, self.device = plant.torch, plant.lib, plant.device
+        self.batch = None
+        self._params = {}
+
+    def init(self, seed=0, stream=None):
+        """Counters n = 0, epoch = 0 for every robot, the noise stream's 64-bit seed, nothing bound."""
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.ctrl.mpc._check(self.lib.qmpc_sense_init(self.ctrl.mpc.h, self.plant.batch or 0, seed, self.ctrl._s(stream)),
+                             "qmpc_sense_init")
+        self.batch = self.plant.batch
+        self._params = {}
+        self.imu = self.torch.zeros((self.batch, 10), dtype=self.torch.float64, device=self.device)
+        self.motor = self.torch.zeros((self.batch, 24), dtype=self.torch.float64, device=self.device)
+
+    def set_params(self, acc_bias=None, gyro_bias=None, acc_sigma=None, gyro_sigma=None, q_sigma=None, qd_sigma=None):
+        """Per-robot sensor errors: float64 device tensors acc_bias [B,3] (m/s^2, body frame), gyro_bias [B,3] (rad/s),
+        acc_sigma, gyro_sigma, q_sigma (rad, all 12 joints), qd_sigma (rad/s) [B]; None: that term is absent.  The
+        tensors are read at every later sense() -- write into them in place (on the stream) to change a value, also
+        between replays of a captured graph; they are kept referenced here.  All None unbinds; init() unbinds."""
+        if self.batch is None:
+            raise QmpcError("qmpc_sense_set_params before init()")
+        given = dict(acc_bias=acc_bias, gyro_bias=gyro_bias, acc_sigma=acc_sigma, gyro_sigma=gyro_sigma, q_sigma=q_sigma,
+                     qd_sigma=qd_sigma)
+        prm = SenseParams()
+        for name, per_robot in SENSE_PARAM_FIELDS.items():
+            t = given[name]
+            if t is not None:
+                shape = (self.batch,) if per_robot == 1 else (self.batch, per_robot)
+                setattr(prm, name, self.ctrl._chk(t, shape, self.torch.float64, name))
+        self.ctrl.mpc._check(self.lib.qmpc_sense_set_params(self.ctrl.mpc.h, self.batch, C.byref(prm)),
+                             "qmpc_sense_set_params")
+        self._params = {k: t for k, t in given.items() if t is not None}
+
+    def reset(self, mask=None, stream=None):
+        """A new noise epoch (epoch += 1, n = 0) for the robots where mask is set; None: all."""
+        m = mask.to(self.torch.uint8).contiguous() if mask is not None else None
+        ptr = self.ctrl._chk(m, (self.ctrl.batch,), self.torch.uint8, "mask") if m is not None else None
+        self.ctrl.mpc._check(self.lib.qmpc_sense_reset(self.ctrl.mpc.h, self.batch or 0, ptr, self.ctrl._s(stream)),
+                             "qmpc_sense_reset")
+        self._keep = m   # (alive until the next call: the launch reads it asynchronously)
+
+    def sense(self, imu=None, motor=None, stream=None):
+        """One reading of the plant's last read-out -> (imu, motor); written into the tensors given, or into the
+        sensors' own."""
+        if self.batch is None:
+            raise QmpcError("qmpc_sense before init()")
+        imu = self.imu if imu is None else imu
+        motor = self.motor if motor is None else motor
+        a = self.ctrl._chk(imu, (self.batch, 10), self.torch.float64, "imu")
+        b = self.ctrl._chk(motor, (self.batch, 24), self.torch.float64, "motor")
+        self.ctrl.mpc._check(self.lib.qmpc_sense(self.ctrl.mpc.h, self.batch, a, b, self.ctrl._s(stream)), "qmpc_sense")
+        return imu, motor
+
+    def settle(self, n=50, stream=None):
+        """n x (sense -> ctrl.prework) with the plant not stepping: the reference's warm-up (init_controller, pre_work
+        ..., then torques), which lets the Kalman filter find the standing body before the first tick."""
+        for _ in range(int(n)):
+            self.sense(stream=stream)
+            self.ctrl.prework(self.imu, self.motor, stream=stream)
+
+    def view(self):
+        """qmpc_sense_view_get as zero-copy device tensors n, epoch ([B] int32) that alias the counters, like
+        BatchedPlant.view(); plus batch, seed.  Read-only by contract."""
+        v = SenseView()
+        self.ctrl.mpc._check(self.lib.qmpc_sense_view_get(self.ctrl.mpc.h, C.byref(v)), "qmpc_sense_view_get")
+        res = {k: self.torch.as_tensor(_DeviceArray(getattr(v, k), (v.batch,), "<i4", self.ctrl), device=self.device)
+               for k in ("n", "epoch")}
+        res["batch"], res["seed"] = v.batch, v.seed
+        return res
+
+
 def rollout(ctrl, plant, ticks, graph=False):
     """`ticks` closed-loop ticks, ctrl.tick_state(plant.state, plant.motor) -> plant.step(effort), on the current
     stream, continuing from wherever the pair stands.  graph=True captures the block of `ticks` ticks into a
@@ -929,3 +1036,37 @@ def rollout(ctrl, plant, ticks, graph=False):
         torch.cuda.current_stream(ctrl.device).wait_stream(s)
         g.replay()
     return dict(effort=plant.effort, state=plant.state, motor=plant.motor, graph=g)
+
+
+def rollout_sensed(ctrl, plant, sensors, ticks, graph=False):
+    """rollout() through the sensor path: `ticks` closed-loop ticks ctrl.tick(sensors.imu, sensors.motor) ->
+    plant.step(effort) -> sensors.sense(), continuing from wherever the three stand -- sensors.imu / motor must hold a
+    reading (sensors.settle() or one sensors.sense() leaves one).  graph=True as in rollout(): the block is captured and
+    replayed once, the graph returned for further replays; in lockstep a captured block holds a multiple of 13 ticks.
+    -> dict(effort, state, motor, imu, graph): the plant's own tensors and the sensors' imu, as the last tick left them."""
+    torch = ctrl.torch
+    ticks = int(ticks)
+    if ticks < 1:
+        raise QmpcError("rollout_sensed: ticks must be at least 1")
+
+    def block():
+        for _ in range(ticks):
+            ctrl.tick(sensors.imu, sensors.motor, plant.effort)
+            plant.step(plant.effort)
+            sensors.sense()
+
+    g = None
+    if not graph:
+        block()
+    else:
+        if ctrl.schedule == "lockstep" and ticks % 13 != 0:
+            raise QmpcError(f"rollout_sensed: a captured block holds a multiple of 13 ticks in lockstep, not {ticks}")
+        g = torch.cuda.CUDAGraph()
+        s = torch.cuda.Stream(device=ctrl.device)
+        s.wait_stream(torch.cuda.current_stream(ctrl.device))
+        with torch.cuda.stream(s):
+            with torch.cuda.graph(g, stream=s):
+                block()
+        torch.cuda.current_stream(ctrl.device).wait_stream(s)
+        g.replay()
+    return dict(effort=plant.effort, state=plant.state, motor=plant.motor, imu=sensors.imu, graph=g)

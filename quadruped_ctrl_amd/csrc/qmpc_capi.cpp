@@ -20,10 +20,12 @@
 #include "../../include/qmpc_ctrl.h"    // batched locomotion controller (same library)
 #include "../../include/qmpc_plant.h"   // reduced-order plant for it (same library)
 #include "../../include/qmpc_plant_vary.h"  // ... its per-robot parameters and on-device statistics
+#include "../../include/qmpc_sense.h"   // sensor model between the plant and the controller's sensor path
 #include "qmpc_device.h"
 #include "qmpc_glue.h"
 #include "qmpc_plan.h"  // the solve's launch plan (host-only)
 #include "qmpc_plant.h"
+#include "qmpc_sense.h"
 static_assert(kLongHorizon == QMPC_LONG_HORIZON, "qmpc_plan.h and qmpc.h disagree");
 
 // per-class entry points of qmpc_kernels.hip (one translation unit per size class)
@@ -120,6 +122,10 @@ extern "C" hipError_t qmpc_launch_plant_step(const QmpcPlantDev* S, const QmpcPl
                                              const float* contact_state, const float* p_des, const float* v_des,
                                              double* state_out, double* motor_out, int batch, hipStream_t stream,
                                              const QmpcPlantVary* V, int vary, int stats);
+extern "C" hipError_t qmpc_launch_sense(const QmpcSenseArgs* A, double* imu_out, double* motor_out, int batch, int noisy,
+                                        hipStream_t stream);
+extern "C" hipError_t qmpc_launch_sense_reset(const QmpcSenseArgs* A, const uint8_t* mask, int batch,
+                                              hipStream_t stream);
 extern "C" hipError_t qmpc_launch_plant_stats_reset(const QmpcPlantVary* V, const uint8_t* mask, int batch,
                                                     hipStream_t stream);
 extern "C" hipError_t qmpc_launch_swing(const float* p0, const float* pf, const float* height, const float* phase,
@@ -243,6 +249,16 @@ struct qmpc_ctx {
     bool stats_on = false;
   };
   Plant* plant = nullptr;
+  // sensor model (qmpc_sense.h): the counters n[max_batch], epoch[max_batch] in one allocation made by qmpc_sense_init,
+  // the seed, and the caller's arrays as bound (all null: the ideal sensor)
+  struct Sense {
+    void* buf = nullptr;
+    int batch = 0;  // robots initialised
+    uint64_t seed = 0;
+    QmpcSenseArgs a{};
+    bool bound = false;
+  };
+  Sense* sense = nullptr;
 };
 
 namespace {
@@ -432,9 +448,11 @@ int qmpc_destroy(qmpc_handle h) {
     if (h->ctrl && h->ctrl->buf) hipFree(h->ctrl->buf);
     if (h->plant && h->plant->buf) hipFree(h->plant->buf);
     if (h->plant && h->plant->stats_buf) hipFree(h->plant->stats_buf);
+    if (h->sense && h->sense->buf) hipFree(h->sense->buf);
   }
   delete h->ctrl;
   delete h->plant;
+  delete h->sense;
   delete h;
   return QMPC_OK;
 }
@@ -1678,6 +1696,99 @@ int qmpc_plant_stats_get(qmpc_handle c, qmpc_plant_stats* v) {
   v->vy_sum = k->vary.acc + QMPC_PLANT_STAT_VY_SUM * M;
   v->batch = k->batch;
   v->enabled = k->stats_on ? 1 : 0;
+  return QMPC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
+// Sensor model (include/qmpc_sense.h).  The kernels are in qmpc_sense.hip.
+namespace {
+
+int sense_check(qmpc_ctx* c, int batch) {
+  if (const int rc = plant_check(c, batch)) return rc;
+  if (!c->sense || !c->sense->batch) return QMPC_ERR_STATE;
+  if (batch != c->sense->batch) return QMPC_ERR_ARG;
+  return QMPC_OK;
+}
+
+void sense_unbind(QmpcSenseArgs& a) {
+  a.acc_bias = a.gyro_bias = a.acc_sigma = a.gyro_sigma = a.q_sigma = a.qd_sigma = nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qmpc_sense_init(qmpc_handle c, int batch, uint64_t seed, void* stream_) {
+  if (const int rc = plant_check(c, batch)) return rc;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!c->sense) c->sense = new qmpc_ctx::Sense();
+  qmpc_ctx::Sense* k = c->sense;
+  const size_t bytes = 2 * sizeof(int) * (size_t)c->max_batch;
+  if (!k->buf) HIP_TRY(c, hipMalloc(&k->buf, bytes));
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  HIP_TRY(c, hipMemsetAsync(k->buf, 0, bytes, stream));
+  k->a.n = static_cast<int*>(k->buf);
+  k->a.epoch = k->a.n + c->max_batch;
+  k->a.key0 = (uint32_t)(seed & 0xFFFFFFFFu);
+  k->a.key1 = (uint32_t)(seed >> 32);
+  sense_unbind(k->a);
+  k->bound = false;
+  k->seed = seed;
+  k->batch = batch;
+  return QMPC_OK;
+}
+
+int qmpc_sense_set_params(qmpc_handle c, int batch, const qmpc_sense_params* prm) {
+  if (const int rc = sense_check(c, batch)) return rc;
+  QmpcSenseArgs& a = c->sense->a;
+  sense_unbind(a);
+  if (prm) {
+    a.acc_bias = prm->acc_bias;
+    a.gyro_bias = prm->gyro_bias;
+    a.acc_sigma = prm->acc_sigma;
+    a.gyro_sigma = prm->gyro_sigma;
+    a.q_sigma = prm->q_sigma;
+    a.qd_sigma = prm->qd_sigma;
+  }
+  c->sense->bound = a.acc_bias || a.gyro_bias || a.acc_sigma || a.gyro_sigma || a.q_sigma || a.qd_sigma;
+  return QMPC_OK;
+}
+
+int qmpc_sense_reset(qmpc_handle c, int batch, const uint8_t* mask_dev, void* stream_) {
+  if (const int rc = sense_check(c, batch)) return rc;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  HIP_TRY(c, qmpc_launch_sense_reset(&c->sense->a, mask_dev, batch, stream));
+  return QMPC_OK;
+}
+
+int qmpc_sense(qmpc_handle c, int batch, double* imu_out, double* motor_out, void* stream_) {
+  if (const int rc = sense_check(c, batch)) return rc;
+  const QmpcPlantDev& p = c->plant->d;
+  if (!imu_out || !motor_out) return QMPC_ERR_ARG;
+  // the kernel reads the plant's rows while it writes the outputs
+  if (imu_out == p.state || imu_out == p.motor || motor_out == p.state || motor_out == p.motor) return QMPC_ERR_ARG;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  QmpcSenseArgs a = c->sense->a;
+  a.state = p.state;
+  a.motor = p.motor;
+  HIP_TRY(c, qmpc_launch_sense(&a, imu_out, motor_out, batch, c->sense->bound, stream));
+  return QMPC_OK;
+}
+
+int qmpc_sense_view_get(qmpc_handle c, qmpc_sense_view* v) {
+  if (!c || !v) return QMPC_ERR_ARG;
+  if (!c->plant || !c->plant->batch || !c->sense || !c->sense->batch) return QMPC_ERR_STATE;
+  v->n = c->sense->a.n;
+  v->epoch = c->sense->a.epoch;
+  v->batch = c->sense->batch;
+  v->seed = c->sense->seed;
   return QMPC_OK;
 }
 

@@ -1,0 +1,346 @@
+"""GPU suite (-m gpu) for the sensor model (include/qmpc_sense.h; BatchedSensors, rollout_sensed).
+
+The kernel is compared with tests/sense_model.py BIT FOR BIT (np.array_equal): the path holds integer arithmetic, one
+conversion, and one fp64 operation at a time -- no transcendental function, no contraction.  The closed-loop walk through
+the controller's estimators is held to the CPU loop's recorded statistics (tests/golden/sense_closed_loop_cpu.json) by
+plant_loop.envelope(); everything else compares two runs of the library bit for bit.
+"""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import pytest
+
+import plant_loop as L
+import sense_loop as SL
+import sense_model as SM
+import test_gpu_plant as TP
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_pair, _dev, _snap = TP._pair, TP._dev, TP._snap
+
+
+def _trio(B, schedule="lockstep", mode=None, seed=SL.SEED):
+    """Controller + plant + sensors on plant_loop's commands, repeated over B robots (B need not be a multiple of 16)."""
+    from quadruped_ctrl_amd.binding import BatchedSensors
+    gait, vel, xyyaw = L.commands(mode or 0)
+    k = np.arange(B) % L.N_CMD
+    gait, vel, xyyaw = gait[k], vel[k], xyyaw[k]
+    c, plant = _pair(B, schedule, mode, xyyaw=xyyaw)
+    c.set_gait(_dev(c, gait))
+    c.set_vel(_dev(c, vel))
+    s = BatchedSensors(plant)
+    s.init(seed)
+    return c, plant, s, (gait, vel, xyyaw)
+
+
+def _values(B, seed):
+    """All six arrays, every robot its own values."""
+    rng = np.random.default_rng(seed)
+    return dict(acc_bias=rng.uniform(-0.5, 0.5, (B, 3)), gyro_bias=rng.uniform(-0.05, 0.05, (B, 3)),
+                acc_sigma=rng.uniform(0.05, 0.5, B), gyro_sigma=rng.uniform(0.005, 0.05, B),
+                q_sigma=rng.uniform(0.0005, 0.005, B), qd_sigma=rng.uniform(0.01, 0.1, B))
+
+
+def _bind(c, s, vals):
+    t = {k: _dev(c, v) for k, v in vals.items()}
+    s.set_params(**t)
+    return t
+
+
+def _out(s):
+    """imu, motor, n, epoch as numpy copies (synchronises)."""
+    import torch
+    torch.cuda.synchronize()
+    v = s.view()
+    return dict(imu=s.imu.cpu().numpy().copy(), motor=s.motor.cpu().numpy().copy(), n=v["n"].cpu().numpy().copy(),
+                epoch=v["epoch"].cpu().numpy().copy())
+
+
+def _stats(plant):
+    import torch
+    torch.cuda.synchronize()
+    st = plant.stats()
+    return {k: st[k].cpu().numpy().copy() for k in ("n", "z_min", "z_max", "roll_max", "pitch_max", "vx_sum", "vy_sum")}
+
+
+@pytest.mark.parametrize("B", [5, 67])
+def test_ideal_sensor_is_the_rearranged_read_out(B):
+    """Nothing bound, after 20 settle calls and 14 closed-loop ticks (one MPC solve) (B = 67: 1072 lanes, a partial last wave of three
+    robots; B = 5: one partial wave): imu / motor are the plant's rows rearranged, bit for bit, and n counts the calls."""
+    from quadruped_ctrl_amd.binding import rollout_sensed
+    c, plant, s, _ = _trio(B)
+    s.settle(20)
+    first = _out(s)
+    assert (first["n"] == 20).all() and (first["epoch"] == 0).all()
+    res = rollout_sensed(c, plant, s, 14)
+    got, p = _out(s), _snap(plant)
+    assert np.array_equal(got["imu"], SM.as_imu(p["state"])) and np.array_equal(got["motor"], p["motor"])
+    assert (got["n"] == 34).all() and (got["epoch"] == 0).all()
+    assert res["imu"] is s.imu and np.abs(plant.effort.cpu().numpy()).max() > 1.0
+    # the robots moved, the rows are the robots' own, and the caller's tensors are written when given
+    assert np.abs(got["imu"] - first["imu"]).max() > 1e-3 and np.abs(got["motor"][:, 12:]).max() > 1e-3
+    assert len(np.unique(got["imu"][:, 6])) > 1 or B < 3
+    import torch
+    imu2, mo2 = torch.zeros_like(s.imu), torch.zeros_like(s.motor)
+    s.sense(imu2, mo2)
+    torch.cuda.synchronize()
+    assert np.array_equal(imu2.cpu().numpy(), got["imu"]) and np.array_equal(mo2.cpu().numpy(), got["motor"])
+    assert (_out(s)["n"] == 35).all()
+    v = s.view()
+    assert v["batch"] == B and v["seed"] == SL.SEED
+    c.close()
+
+
+def test_noisy_sensor_is_the_model_bit_for_bit():
+    """B = 67, all six arrays bound with per-robot values, a 64-bit seed with both words set: four readings with a reset
+    on a strided mask after the second (and a plant step in between, so the inputs move); then only gyro_sigma bound --
+    a NULL term is absent, not zero.  np.array_equal against tests/sense_model.py for imu, motor, n and epoch."""
+    from quadruped_ctrl_amd.binding import rollout_sensed
+    B, seed = 67, 0x9E3779B97F4A7C15
+    c, plant, s, _ = _trio(B, seed=seed)
+    s.settle(13)
+    rollout_sensed(c, plant, s, 6)                     # (ideal so far: a walking state, n = 19)
+    m = SM.SenseModel(B, seed)
+    m.n[:] = 19
+    vals = _values(B, 11)
+    keep = _bind(c, s, vals)
+    m.set_params(**vals)
+    mask = np.arange(B) % 3 == 1
+    moved = 0.0
+
+    def reading(what):
+        nonlocal moved
+        p = _snap(plant)
+        s.sense()
+        got = _out(s)
+        imu, motor = m.sense(p["state"], p["motor"])
+        for k, want in (("imu", imu), ("motor", motor), ("n", m.n), ("epoch", m.epoch)):
+            assert np.array_equal(got[k], want), (what, k, np.abs(got[k] - want).max())
+        assert np.array_equal(got["imu"][:, 3:7], SM.as_imu(p["state"])[:, 3:7])      # the quaternion passes through
+        moved = max(moved, float(np.abs(got["motor"] - p["motor"]).min()))
+        return got, p
+
+    reading("first")
+    reading("second")
+    s.reset(_dev(c, mask))
+    m.reset(mask)
+    plant.step(plant.effort)
+    g3, p3 = reading("third")
+    assert list(g3["n"][:4]) == [21 + 1, 1, 21 + 1, 21 + 1] and list(g3["epoch"][:4]) == [0, 1, 0, 0]
+    reading("fourth")
+    assert moved > 0                                               # every joint reading of every robot was moved
+    assert (g3["imu"][:, 0:3] != p3["state"][:, 13:16]).all() and (g3["imu"][:, 7:10] != p3["state"][:, 7:10]).all()
+    # only gyro_sigma: the other five terms are gone, the gyro rows have no bias left
+    only = dict(gyro_sigma=vals["gyro_sigma"])
+    keep2 = _bind(c, s, only)
+    m.set_params(**only)
+    g5, p5 = reading("gyro_sigma alone")
+    assert np.array_equal(g5["motor"], p5["motor"]) and np.array_equal(g5["imu"][:, 0:3], p5["state"][:, 13:16])
+    assert (g5["imu"][:, 7:10] != p5["state"][:, 7:10]).all()
+    # unbound again: the ideal sensor
+    s.set_params()
+    m.set_params()
+    g6, p6 = reading("unbound")
+    assert np.array_equal(g6["imu"], SM.as_imu(p6["state"]))
+    # NULL mask: every robot starts a new epoch
+    s.reset()
+    m.reset()
+    got = _out(s)
+    assert np.array_equal(got["n"], m.n) and np.array_equal(got["epoch"], m.epoch) and (got["n"] == 0).all()
+    del keep, keep2
+    c.close()
+
+
+def test_sense_writes_nothing_of_the_plant_or_the_controller():
+    import torch
+    from quadruped_ctrl_amd.binding import rollout_sensed
+    B = 64
+    c, plant, s, _ = _trio(B)
+    keep = _bind(c, s, _values(B, 2))
+    plant.enable_stats()
+    s.settle(13)
+    rollout_sensed(c, plant, s, 14)
+
+    def everything():
+        torch.cuda.synchronize()
+        snap = {"plant_" + k: v for k, v in _snap(plant).items()}
+        snap.update({"stats_" + k: v.cpu().numpy().copy() for k, v in plant.stats().items() if hasattr(v, "cpu")})
+        snap.update({"ctrl_" + k: v.cpu().numpy().copy() for k, v in c.view().items() if hasattr(v, "cpu")})
+        for name in ("xhat", "P", "status", "counter", "first_visit", "f_ff"):
+            snap["read_" + name] = c.read(name).copy()
+        snap["effort"] = plant.effort.cpu().numpy().copy()
+        return snap
+
+    before, old = everything(), _out(s)
+    s.sense()
+    after, new = everything(), _out(s)
+    assert len(before) > 30
+    for k in before:
+        assert before[k].tobytes() == after[k].tobytes(), k
+    assert (new["n"] == old["n"] + 1).all() and not np.array_equal(new["imu"], old["imu"])
+    del keep
+    c.close()
+
+
+def test_bad_values_stay_inside_their_robot():
+    """A NaN sigma (accelerometer, encoders) and an infinite gyro bias in robot 3: over three readings every other robot's
+    outputs and counters are those of the run without them, bit for bit."""
+    from quadruped_ctrl_amd.binding import rollout_sensed
+    B = 16
+    good = np.arange(B) != 3
+    out = []
+    for spoil in (False, True):
+        c, plant, s, _ = _trio(B)
+        s.settle(13)
+        rollout_sensed(c, plant, s, 5)
+        vals = _values(B, 5)
+        if spoil:
+            vals["acc_sigma"][3] = np.nan
+            vals["q_sigma"][3] = np.nan
+            vals["gyro_bias"][3, 1] = np.inf
+        keep = _bind(c, s, vals)
+        got = []
+        for _ in range(3):
+            s.sense()
+            got.append(_out(s))
+        out.append(got)
+        del keep
+        c.close()
+    for a, b in zip(*out):
+        for k in a:
+            assert np.array_equal(a[k][good], b[k][good]), k
+        assert np.isfinite(a["imu"]).all() and np.isfinite(a["motor"]).all()
+        assert np.isnan(b["imu"][3, 0:3]).all() and np.isnan(b["motor"][3, :12]).all() and np.isinf(b["imu"][3, 8])
+        assert np.isfinite(b["imu"][3, 3:7]).all() and np.isfinite(b["motor"][3, 12:]).all()
+
+
+def test_graph_replays_continue_the_noise():
+    """Lockstep, noisy, 13 settle calls and 13 eager ticks: a captured block of 13 ticks of rollout_sensed replayed three times is 39 eager
+    ticks from the same start, bit for bit -- the noise counter is device state, so every replay draws new noise."""
+    from quadruped_ctrl_amd.binding import rollout_sensed
+    B = 64
+    out = []
+    for graph in (False, True):
+        c, plant, s, _ = _trio(B)
+        keep = _bind(c, s, SL.noise(B))
+        s.settle(13)
+        rollout_sensed(c, plant, s, 13)                 # (first run, first swing, one MPC: eager on both)
+        if graph:
+            res = rollout_sensed(c, plant, s, 13, graph=True)
+            first = _out(s)["imu"]
+            res["graph"].replay()
+            res["graph"].replay()
+        else:
+            rollout_sensed(c, plant, s, 39)
+        snap = _snap(plant)
+        snap.update(_out(s))
+        snap["effort"] = plant.effort.cpu().numpy().copy()
+        out.append(snap)
+        del keep
+        c.close()
+    for k in ("state", "motor", "imu", "effort", "n", "p", "v", "q", "omega", "foot", "epoch"):
+        assert np.array_equal(out[0][k], out[1][k]), k
+    assert (out[1]["n"] == 13 + 13 + 39).all() and np.abs(out[1]["effort"]).max() > 1.0
+    assert not np.array_equal(first, out[1]["imu"])
+    with pytest.raises(Exception, match="multiple of 13"):
+        c, plant, s, _ = _trio(16)
+        s.settle(1)
+        try:
+            rollout_sensed(c, plant, s, 12, graph=True)
+        finally:
+            c.close()
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_the_fleet_walks_on_noisy_sensors(mode):
+    """The CPU yardstick's commands, four robots per command, sense_loop.noise() bound, settle(50), then 650 ticks of
+    ctrl.tick -> plant.step -> sense.  No robot is latched, no solve reports an error bit, and the five statistics --
+    read from the plant's device accumulators at tick 150 and at the end -- lie inside plant_loop.envelope() of the CPU
+    run through the numpy estimators.  (The four robots of a command share its biases and differ in their noise: the
+    robot's index is in the generator's counter.)"""
+    from quadruped_ctrl_amd.binding import rollout_sensed
+    reps = 4
+    B = L.N_CMD * reps
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "sense_closed_loop_cpu.json")))
+    rec = gold[f"mode{mode}"]["noisy"]
+    nz = SL.noise(B)
+    for k, v in nz.items():
+        assert np.array_equal(np.asarray(gold["noise"][k]), v[:L.N_CMD]), k
+    c, plant, s, (gait, vel, xyyaw) = _trio(B, "per_robot" if mode == 1 else "lockstep", mode if mode == 1 else None,
+                                            seed=gold["seed"])
+    assert np.array_equal(gold[f"mode{mode}"]["vel"], vel[:L.N_CMD]) and np.array_equal(gold[f"mode{mode}"]["gait"], gait[:L.N_CMD])
+    keep = _bind(c, s, nz)
+    plant.enable_stats()
+    start = plant.state.cpu().numpy().copy()
+    s.settle(gold["settle"])
+    for t in range(L.TICKS):
+        rollout_sensed(c, plant, s, 1)
+        if mode == 1 or (t + 1) % 13 == 0:
+            assert (c.read("status")[:, 0] & 47 == 0).all(), t
+        if t + 1 == L.TICKS - int(L.FREQ):
+            at150 = _stats(plant)
+    end = _stats(plant)
+    assert (c.read("safe") == 1).all()
+    assert (at150["n"] == 150).all() and (end["n"] == L.TICKS).all() and (_out(s)["n"] == gold["settle"] + L.TICKS).all()
+    rpy0 = L.rpy_of(start[:, 0:4])
+    stats = dict(z_min=np.minimum(end["z_min"], start[:, 6]), z_max=np.maximum(end["z_max"], start[:, 6]),
+                 roll_max=np.maximum(end["roll_max"], np.abs(rpy0[:, 0])),
+                 pitch_max=np.maximum(end["pitch_max"], np.abs(rpy0[:, 1])),
+                 vx_mean=(end["vx_sum"] - at150["vx_sum"]) / (end["n"] - at150["n"]))
+    env = L.envelope(rec)
+    for k in L.STATS:
+        lo, hi = np.tile(env[k][0], reps), np.tile(env[k][1], reps)
+        want = np.tile(np.asarray(rec[k]), reps)
+        print(f"mode {mode} {k}: largest distance from the CPU run {np.abs(stats[k] - want).max():.3e}, "
+              f"allowed {float((hi - want).max()):.3e}")
+        assert (stats[k] >= lo).all() and (stats[k] <= hi).all(), (k, stats[k], lo, hi)
+    del keep
+    c.close()
+
+
+def test_argument_and_state_errors():
+    import torch
+    from quadruped_ctrl_amd.binding import BatchedController, SenseParams, SenseView
+    OK, ARG, STATE = 0, 1, 3
+    B = 8
+    c = BatchedController(0, max_batch=16)
+    lib, h = c.lib, c.mpc.h
+    imu = torch.zeros((B, 10), dtype=torch.float64, device=c.device)
+    motor = torch.zeros((B, 24), dtype=torch.float64, device=c.device)
+    sg = torch.full((B,), 0.1, dtype=torch.float64, device=c.device)
+    prm, v = SenseParams(q_sigma=sg.data_ptr()), SenseView()
+    c.init(B, 500.0, L.PID)
+    assert lib.qmpc_sense_init(h, B, 1, None) == STATE                          # before qmpc_plant_init
+    assert lib.qmpc_sense(h, B, imu.data_ptr(), motor.data_ptr(), None) == STATE
+    assert lib.qmpc_plant_init(h, B, 0.4, 1, None, None) == OK
+    assert lib.qmpc_sense(h, B, imu.data_ptr(), motor.data_ptr(), None) == STATE   # before qmpc_sense_init
+    assert lib.qmpc_sense_set_params(h, B, C.byref(prm)) == STATE
+    assert lib.qmpc_sense_reset(h, B, None, None) == STATE
+    assert lib.qmpc_sense_view_get(h, C.byref(v)) == STATE
+    assert lib.qmpc_sense_init(None, B, 1, None) == ARG
+    assert lib.qmpc_sense_init(h, B + 1, 1, None) == ARG                        # a batch other than the plant's
+    assert lib.qmpc_sense_init(h, B, (7 << 32) | 5, None) == OK
+    assert lib.qmpc_sense_view_get(h, None) == ARG
+    assert lib.qmpc_sense_view_get(h, C.byref(v)) == OK and (v.batch, v.seed) == (B, (7 << 32) | 5)
+    assert lib.qmpc_sense_set_params(h, B - 1, C.byref(prm)) == ARG
+    assert lib.qmpc_sense_set_params(h, B, C.byref(prm)) == OK
+    assert lib.qmpc_sense_set_params(h, B, None) == OK                           # unbinds
+    assert lib.qmpc_sense_reset(h, B + 1, None, None) == ARG
+    assert lib.qmpc_sense_reset(h, B, None, None) == OK
+    assert lib.qmpc_sense(h, B + 1, imu.data_ptr(), motor.data_ptr(), None) == ARG
+    assert lib.qmpc_sense(h, B, None, motor.data_ptr(), None) == ARG
+    assert lib.qmpc_sense(h, B, imu.data_ptr(), None, None) == ARG
+    from quadruped_ctrl_amd.binding import PlantView
+    pv = PlantView()
+    assert lib.qmpc_plant_view_get(h, C.byref(pv)) == OK
+    assert lib.qmpc_sense(h, B, pv.state, motor.data_ptr(), None) == ARG        # the plant's own rows as outputs
+    assert lib.qmpc_sense(h, B, imu.data_ptr(), pv.motor, None) == ARG
+    assert lib.qmpc_sense(h, B, pv.motor, pv.state, None) == ARG
+    assert lib.qmpc_sense(h, B, imu.data_ptr(), motor.data_ptr(), None) == OK
+    torch.cuda.synchronize()
+    assert imu.cpu().numpy()[:, 6].min() == 1.0 and v.n and v.epoch
+    c.close()

@@ -27,8 +27,16 @@ first steps (--warmup 260).  The tick and the plant step are timed separately (u
 the per-robot body, floor and push of include/qmpc_plant_vary.h (the set the closed-loop tests walk on: payloads, floors, and a
 30 N lateral push during ticks 300 .. 349 of the run, written into the bound array between two ticks) and turns the plant's statistics on: the step then runs its <VARY, STATS> instantiation.
 
+--source sensor closes the same loop through the SENSOR path: qmpc_ctrl_tick -- the VectorNav orientation estimator and
+the Kalman filter -- on the readings of the sensor model (include/qmpc_sense.h), qmpc_plant_step on the tick's efforts,
+qmpc_sense on the plant's read-out; 50 untimed qmpc_sense -> qmpc_ctrl_prework calls on the standing plant come first
+(without them the filter, which starts at height 0, makes most of the fleet fall).  The same commands as --source plant.
+The tick, the plant step and the sensor launch are timed separately (us_per_sense_median).  --noise binds per-robot
+accelerometer and gyro biases (within +-0.2 m/s^2, +-0.02 rad/s) and white noise (sigma 0.3 m/s^2, 0.02 rad/s, encoders
+0.002 rad and 0.05 rad/s: the levels the closed-loop tests walk on); without it the sensors are ideal.
+
     python tools/ctrl_bench.py [--batches 1024,4096,16384] [--cycles 8] [--warmup 26] [--schedule lockstep|per_robot]
-                               [--stagger] [--robot-mode 0|1] [--source imu|state|plant] [--vary] [--out FILE]
+                               [--stagger] [--robot-mode 0|1] [--source imu|state|plant|sensor] [--vary] [--noise] [--out FILE]
 """
 import argparse
 import json
@@ -41,13 +49,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, source="imu", vary=False):
+def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, source="imu", vary=False, noise=False):
     import torch
     from quadruped_ctrl_amd import workloads as W
     from quadruped_ctrl_amd.binding import BatchedController
     ctrl = BatchedController(0, max_batch=B)
     # (the plant takes the reference's simulation gains: a joint spring towards q = 0 pushes a real leg off its stance)
-    ctrl.init(B, freq=500.0, pid=(100.0, 1.0, 0.0, 0.05) if source == "plant" else (0.0, 0.0, 3.0, 0.3))
+    closed = source in ("plant", "sensor")
+    ctrl.init(B, freq=500.0, pid=(100.0, 1.0, 0.0, 0.05) if closed else (0.0, 0.0, 3.0, 0.3))
     if schedule != "lockstep":
         ctrl.set_schedule(schedule)
     if robot_mode:
@@ -61,7 +70,7 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
     if robot_mode == 1:
         vel[:, 0] = np.linspace(0.0, 2.0, B)[rng.permutation(B)]
         vel[::16, 1:] = 0.0      # (x command 0 with no yaw command: the standing case for robot 0's neighbours)
-    if source == "plant":
+    if closed:
         g = torch.from_numpy(np.array([0, 4, 5, 10], np.int32)[np.arange(B) % 4]).cuda()
         ctrl.set_gait(g)
         vel = np.stack([rng.uniform(0.0, 0.5, B), np.zeros(B), rng.uniform(-0.1, 0.1, B)], 1)
@@ -70,8 +79,8 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
     vel = torch.from_numpy(vel).cuda()
     ctrl.set_vel(vel)
     n = warmup + 13 * cycles
-    plant = None
-    if source == "plant":
+    plant = sensors = None
+    if closed:
         from quadruped_ctrl_amd.binding import BatchedPlant
         plant = BatchedPlant(ctrl)
         xyyaw = np.stack([np.arange(B) % 128 * 1.0, np.arange(B) // 128 * 1.0, rng.uniform(-0.1, 0.1, B)], 1)
@@ -88,6 +97,18 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
             plant.enable_stats()
         imu, motor = plant.state.expand(26, B, 16), plant.motor.expand(26, B, 24)    # (every "slot" is the plant's read-out)
         tick = ctrl.tick_state
+        if source == "sensor":
+            from quadruped_ctrl_amd.binding import BatchedSensors
+            sensors = BatchedSensors(plant)
+            sensors.init(seed=B)
+            if noise:   # tests/sense_loop.py: noise(), restated (the tools do not import the test tree)
+                dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).cuda()
+                full = lambda x: dev(np.full(B, x))
+                sensors.set_params(acc_bias=dev(rng.uniform(-0.2, 0.2, (B, 3))), gyro_bias=dev(rng.uniform(-0.02, 0.02, (B, 3))),
+                                   acc_sigma=full(0.3), gyro_sigma=full(0.02), q_sigma=full(0.002), qd_sigma=full(0.05))
+            sensors.settle(50)
+            imu, motor = sensors.imu.expand(26, B, 10), sensors.motor.expand(26, B, 24)
+            tick = ctrl.tick
     elif source == "state":
         imu, motor = W.make_state_stream(B, 26, seed=B)      # (`imu` below: the tick's first input, whichever it is)
         tick = ctrl.tick_state
@@ -106,7 +127,9 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
             tick(imu[t], motor[t], eff)
             if plant is not None:
                 plant.step(eff)
-    ev = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(3)) for _ in range(n)]
+            if sensors is not None:
+                sensors.sense()
+    ev = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(4)) for _ in range(n)]
     for t in range(n):
         if vary and t in (300, 350):     # (outside the timed pairs: the push starts and ends)
             force.copy_(push) if t == 300 else force.zero_()
@@ -116,6 +139,9 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
         if plant is not None:
             plant.step(eff)
             ev[t][2].record()
+        if sensors is not None:
+            sensors.sense()
+            ev[t][3].record()
     torch.cuda.synchronize()
     us = np.array([e[0].elapsed_time(e[1]) * 1e3 for e in ev])
     mpc = (np.arange(n) + 1) % 13 == 0
@@ -126,6 +152,10 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
     res = {"batch": B, "source": source, "schedule": schedule, "stagger": bool(stagger), "robot_mode": robot_mode, "ticks_timed": int(keep.sum()),
            "us_per_tick_median": round(float(np.median(us[keep])), 2), "us_per_tick_max": round(float(us[keep].max()), 2),
            "robot_ticks_per_s_window": float(f"{B * int(keep.sum()) / (float(us[keep].sum()) * 1e-6):.4g}")}
+    if sensors is not None:
+        us_s = np.array([e[2].elapsed_time(e[3]) * 1e3 for e in ev])[keep]
+        res.update({"noise": bool(noise), "us_per_sense_median": round(float(np.median(us_s)), 2),
+                    "us_per_sense_max": round(float(us_s.max()), 2), "sense_calls": int(sensors.view()["n"].min().item())})
     if vary:
         res["vary"] = True
         res["stats_steps"] = int(plant.stats()["n"].min().item())
@@ -158,19 +188,22 @@ def main():
     ap.add_argument("--schedule", choices=("lockstep", "per_robot"), default="lockstep")
     ap.add_argument("--stagger", action="store_true")
     ap.add_argument("--robot-mode", type=int, choices=(0, 1), default=0)
-    ap.add_argument("--source", choices=("imu", "state", "plant"), default="imu")
+    ap.add_argument("--source", choices=("imu", "state", "plant", "sensor"), default="imu")
     ap.add_argument("--vary", action="store_true")
+    ap.add_argument("--noise", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.vary and a.source != "plant":
-        ap.error("--vary needs --source plant")
+    if a.vary and a.source not in ("plant", "sensor"):
+        ap.error("--vary needs --source plant or sensor")
+    if a.noise and a.source != "sensor":
+        ap.error("--noise needs --source sensor")
     if a.robot_mode == 1:
         a.schedule = "per_robot"
     if a.stagger and a.schedule != "per_robot":
         ap.error("--stagger needs --schedule per_robot (a lockstep reset keeps the robot on the batch's MPC ticks)")
     out = []
     for B in [int(x) for x in a.batches.split(",")]:
-        r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source, a.vary)
+        r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source, a.vary, a.noise)
         print(json.dumps(r), flush=True)
         out.append(r)
     if a.out:
