@@ -692,10 +692,46 @@ class BatchedController:
             raise QmpcError(f"{what}: expected a contiguous {dtype} tensor of shape {tuple(shape)} on {self.device}")
         return t.data_ptr()
 
+    # ---- what the controller, its plant and its sensors (one handle) all do around a C call ----
+    def _call(self, name, *args):
+        """The C function `name` on the handle, checked."""
+        self.mpc._check(getattr(self.lib, name)(self.mpc.h, *args), name)
+
+    def _mask(self, mask):
+        """A [B] bool / uint8 mask -> (its uint8 copy, which the caller keeps alive until its next call: the launch reads
+        it asynchronously; the copy's pointer).  None -> (None, None)."""
+        if mask is None:
+            return None, None
+        m = mask.to(self.torch.uint8).contiguous()
+        return m, self._chk(m, (self.batch,), self.torch.uint8, "mask")
+
+    def _bind(self, name, batch, struct, fields, given):
+        """`name`(handle, batch, &struct) over the float64 tensors in `given` (fields: member -> elements per robot;
+        None: the member stays null) -> the tensors bound, for the caller to keep referenced."""
+        if batch is None:
+            raise QmpcError(f"{name} before init()")
+        prm = struct()
+        for k, per_robot in fields.items():
+            if given[k] is not None:
+                shape = (batch,) if per_robot == 1 else (batch, per_robot)
+                setattr(prm, k, self._chk(given[k], shape, self.torch.float64, k))
+        self._call(name, batch, C.byref(prm))
+        return {k: t for k, t in given.items() if t is not None}
+
+    def _views(self, name, struct, fields, scalars):
+        """`name`(handle, &struct) as a dict: zero-copy device tensors over the struct's pointers (fields: member ->
+        (elements per robot, or None for [B]; typestr)) that keep this controller alive, then the members in `scalars`."""
+        v = struct()
+        self._call(name, C.byref(v))
+        res = {k: self.torch.as_tensor(_DeviceArray(getattr(v, k), (v.batch,) if n is None else (v.batch, n), ts, self),
+                                       device=self.device) for k, (n, ts) in fields.items()}
+        res.update((k, getattr(v, k)) for k in scalars)
+        return res
+
     def init(self, batch, freq=500.0, pid=(0.0, 0.0, 0.0, 0.0), stream=None):
         """GaitCtrller(freq, PIDParam) for robots 0 .. batch-1; pid[2], pid[3] are the joint PD gains."""
         pid_c = (C.c_double * 4)(*[float(x) for x in pid])
-        self.mpc._check(self.lib.qmpc_ctrl_init(self.mpc.h, int(batch), float(freq), pid_c, self._s(stream)), "qmpc_ctrl_init")
+        self._call("qmpc_ctrl_init", int(batch), float(freq), pid_c, self._s(stream))
         self.batch = int(batch)
         self.mpc.horizon = 14
         self.schedule = "lockstep"
@@ -705,74 +741,63 @@ class BatchedController:
         reset() is init_controller exactly (counter 0).  Only between init() and the first tick() or reset()."""
         if mode not in CTRL_SCHEDULES:
             raise QmpcError(f"set_schedule: unknown mode {mode!r} (one of {sorted(CTRL_SCHEDULES)})")
-        self.mpc._check(self.lib.qmpc_ctrl_set_schedule(self.mpc.h, CTRL_SCHEDULES[mode]), "qmpc_ctrl_set_schedule")
+        self._call("qmpc_ctrl_set_schedule", CTRL_SCHEDULES[mode])
         self.schedule = mode
 
     def set_robot_mode(self, mode):
         """set_robot_mode for the whole controller: 0 (the default after every init(): the gait picked by number, MPC
         horizon 14) or 1 (the speed-adaptive `aio` gait, 10 .. 16 segments per robot, MPC horizon 10).  Mode 1 needs
         set_schedule("per_robot") first.  Only between init() and the first tick() or reset(); prework() may come first."""
-        self.mpc._check(self.lib.qmpc_ctrl_set_robot_mode(self.mpc.h, int(mode)), "qmpc_ctrl_set_robot_mode")
+        self._call("qmpc_ctrl_set_robot_mode", int(mode))
         self.mpc.horizon = 10 if int(mode) == 1 else 14
 
     def reset(self, mask, stream=None):
         """Re-initialise the robots where mask is set; their iteration counter restarts at T mod 13 in lockstep, at 0
         with the per-robot schedule."""
-        m = mask.to(self.torch.uint8).contiguous() if mask is not None else None
-        ptr = self._chk(m, (self.batch,), self.torch.uint8, "mask") if m is not None else None
-        self.mpc._check(self.lib.qmpc_ctrl_reset(self.mpc.h, self.batch or 0, ptr, self._s(stream)), "qmpc_ctrl_reset")
-        self._keep = m   # (alive until the next call: the launch reads it asynchronously)
+        self._keep, ptr = self._mask(mask)
+        self._call("qmpc_ctrl_reset", self.batch or 0, ptr, self._s(stream))
 
     def set_gait(self, gait, stream=None):
         """set_gait_type: gait numbers 0 .. 11, +20 for omni mode."""
         ptr = self._chk(gait, (self.batch,), self.torch.int32, "gait")
-        self.mpc._check(self.lib.qmpc_ctrl_set_gait(self.mpc.h, self.batch, ptr, self._s(stream)), "qmpc_ctrl_set_gait")
+        self._call("qmpc_ctrl_set_gait", self.batch, ptr, self._s(stream))
 
     def set_vel(self, vel, stream=None):
         """set_robot_vel: [B,3] float64 (x, y, yaw rate), dead band 0.03."""
         ptr = self._chk(vel, (self.batch, 3), self.torch.float64, "vel")
-        self.mpc._check(self.lib.qmpc_ctrl_set_vel(self.mpc.h, self.batch, ptr, self._s(stream)), "qmpc_ctrl_set_vel")
+        self._call("qmpc_ctrl_set_vel", self.batch, ptr, self._s(stream))
+
+    def _tick(self, name, what, width, first, motor, effort, stream, tick=True):
+        """prework / tick and their _state pair: `first` is imu [B,10] or state [B,16] (`what`, `width`)."""
+        if tick and self.batch is None:
+            raise QmpcError(f"{name} before init()")
+        args = [self._chk(first, (self.batch, width), self.torch.float64, what),
+                self._chk(motor, (self.batch, 24), self.torch.float64, "motor")]
+        if tick:
+            if effort is None:
+                effort = self.torch.empty((self.batch, 12), dtype=self.torch.float64, device=self.device)
+            args.append(self._chk(effort, (self.batch, 12), self.torch.float64, "effort"))
+        self._call(name, self.batch, *args, self._s(stream))
+        return effort
 
     def prework(self, imu, motor, stream=None):
         """pre_work: the estimators and the leg data, no control."""
-        a = self._chk(imu, (self.batch, 10), self.torch.float64, "imu")
-        b = self._chk(motor, (self.batch, 24), self.torch.float64, "motor")
-        self.mpc._check(self.lib.qmpc_ctrl_prework(self.mpc.h, self.batch, a, b, self._s(stream)), "qmpc_ctrl_prework")
+        self._tick("qmpc_ctrl_prework", "imu", 10, imu, motor, None, stream, tick=False)
 
     def tick(self, imu, motor, effort=None, stream=None):
         """torque_calculator for every robot -> effort [B,12] float64 (zeros for a latched robot)."""
-        if self.batch is None:
-            raise QmpcError("qmpc_ctrl_tick before init()")
-        a = self._chk(imu, (self.batch, 10), self.torch.float64, "imu")
-        b = self._chk(motor, (self.batch, 24), self.torch.float64, "motor")
-        if effort is None:
-            effort = self.torch.empty((self.batch, 12), dtype=self.torch.float64, device=self.device)
-        e = self._chk(effort, (self.batch, 12), self.torch.float64, "effort")
-        self.mpc._check(self.lib.qmpc_ctrl_tick(self.mpc.h, self.batch, a, b, e, self._s(stream)), "qmpc_ctrl_tick")
-        return effort
+        return self._tick("qmpc_ctrl_tick", "imu", 10, imu, motor, effort, stream)
 
     def prework_state(self, state, motor, stream=None):
         """pre_work from simulator ground truth: state [B,16] float64 in CheaterState's member order (orientation w x y z,
         position, omegaBody, vBody, acceleration) through the cheater estimators -- no Kalman filter -- and the leg data."""
-        a = self._chk(state, (self.batch, 16), self.torch.float64, "state")
-        b = self._chk(motor, (self.batch, 24), self.torch.float64, "motor")
-        self.mpc._check(self.lib.qmpc_ctrl_prework_state(self.mpc.h, self.batch, a, b, self._s(stream)),
-                        "qmpc_ctrl_prework_state")
+        self._tick("qmpc_ctrl_prework_state", "state", 16, state, motor, None, stream, tick=False)
 
     def tick_state(self, state, motor, effort=None, stream=None):
         """tick() with prework_state() as its pre_work: the same control tick, driven by the true body state.  The filter
         and the orientation estimator's first-visit state stay where they were; ticks of the two kinds may alternate, but
         only a run of one kind is a state the reference can reach."""
-        if self.batch is None:
-            raise QmpcError("qmpc_ctrl_tick_state before init()")
-        a = self._chk(state, (self.batch, 16), self.torch.float64, "state")
-        b = self._chk(motor, (self.batch, 24), self.torch.float64, "motor")
-        if effort is None:
-            effort = self.torch.empty((self.batch, 12), dtype=self.torch.float64, device=self.device)
-        e = self._chk(effort, (self.batch, 12), self.torch.float64, "effort")
-        self.mpc._check(self.lib.qmpc_ctrl_tick_state(self.mpc.h, self.batch, a, b, e, self._s(stream)),
-                        "qmpc_ctrl_tick_state")
-        return effort
+        return self._tick("qmpc_ctrl_tick_state", "state", 16, state, motor, effort, stream)
 
     def read(self, name):
         """One array of the controller's device state (qmpc_debug_ctrl_read) -> numpy [B, n] (float32 or int32)."""
@@ -792,14 +817,8 @@ class BatchedController:
         state: no copy, no synchronisation; they show what the last enqueued work left once the stream has reached it,
         and are valid until close() or the next init().  Read-only by contract.  Plus batch and ticks (T: the ticks
         enqueued since init, captured ones included)."""
-        v = CtrlView()
-        self.mpc._check(self.lib.qmpc_ctrl_view_get(self.mpc.h, C.byref(v)), "qmpc_ctrl_view_get")
-        res = {}
-        for k, n in CTRL_VIEW_WIDTH.items():
-            typestr = "<i4" if k in ("safe", "counter") else "<f4"
-            res[k] = self.torch.as_tensor(_DeviceArray(getattr(v, k), (v.batch, n), typestr, self), device=self.device)
-        res["batch"], res["ticks"] = v.batch, v.ticks
-        return res
+        fields = {k: (n, "<i4" if k in ("safe", "counter") else "<f4") for k, n in CTRL_VIEW_WIDTH.items()}
+        return self._views("qmpc_ctrl_view_get", CtrlView, fields, ("batch", "ticks"))
 
 
 class _DeviceArray:
@@ -834,8 +853,8 @@ class BatchedPlant:
     def init(self, mu_plant=0.4, substeps=1, init_xyyaw=None, stream=None):
         """All robots of the controller into the initial state: body at (x, y, 0.29) with yaw from init_xyyaw [B,3]
         float64 (zeros without), at rest, four feet under the hips on the ground, in stance."""
-        self.ctrl.mpc._check(self.lib.qmpc_plant_init(self.ctrl.mpc.h, self.ctrl.batch or 0, float(mu_plant), int(substeps),
-                                                      self._xyyaw(init_xyyaw), self.ctrl._s(stream)), "qmpc_plant_init")
+        self.ctrl._call("qmpc_plant_init", self.ctrl.batch or 0, float(mu_plant), int(substeps), self._xyyaw(init_xyyaw),
+                        self.ctrl._s(stream))
         self.batch = self.ctrl.batch
         self._keep = init_xyyaw
         self._params = {}     # (qmpc_plant_init unbinds: a new plant is the plain plant)
@@ -845,10 +864,8 @@ class BatchedPlant:
 
     def reset(self, mask, init_xyyaw=None, stream=None):
         """The initial state again for the robots where mask is set; the others keep every bit."""
-        m = mask.to(self.torch.uint8).contiguous() if mask is not None else None
-        ptr = self.ctrl._chk(m, (self.ctrl.batch,), self.torch.uint8, "mask") if m is not None else None
-        self.ctrl.mpc._check(self.lib.qmpc_plant_reset(self.ctrl.mpc.h, self.ctrl.batch or 0, ptr, self._xyyaw(init_xyyaw),
-                                                       self.ctrl._s(stream)), "qmpc_plant_reset")
+        m, ptr = self.ctrl._mask(mask)
+        self.ctrl._call("qmpc_plant_reset", self.ctrl.batch or 0, ptr, self._xyyaw(init_xyyaw), self.ctrl._s(stream))
         self._keep = (m, init_xyyaw)   # (alive until the next call: the launch reads them asynchronously)
 
     def step(self, effort, state=None, motor=None, stream=None):
@@ -860,21 +877,14 @@ class BatchedPlant:
         e = self.ctrl._chk(effort, (self.batch, 12), self.torch.float64, "effort")
         a = self.ctrl._chk(state, (self.batch, 16), self.torch.float64, "state")
         b = self.ctrl._chk(motor, (self.batch, 24), self.torch.float64, "motor")
-        self.ctrl.mpc._check(self.lib.qmpc_plant_step(self.ctrl.mpc.h, self.batch, e, a, b, self.ctrl._s(stream)),
-                             "qmpc_plant_step")
+        self.ctrl._call("qmpc_plant_step", self.batch, e, a, b, self.ctrl._s(stream))
         return state, motor
 
     def view(self):
         """qmpc_plant_view_get as zero-copy device tensors (p, v, q, omega, foot, stance, grf, state, motor: [B, n],
         float64, stance int32) that alias the plant's state, like BatchedController.view(); plus batch, substeps,
         mu_plant.  Read-only by contract."""
-        v = PlantView()
-        self.ctrl.mpc._check(self.lib.qmpc_plant_view_get(self.ctrl.mpc.h, C.byref(v)), "qmpc_plant_view_get")
-        res = {k: self.torch.as_tensor(_DeviceArray(getattr(v, k), (v.batch, n), ts, self.ctrl), device=self.device)
-               for k, (n, ts) in PLANT_VIEW_FIELDS.items()}
-        res["batch"], res["substeps"], res["mu_plant"] = v.batch, v.substeps, v.mu_plant
-        return res
-
+        return self.ctrl._views("qmpc_plant_view_get", PlantView, PLANT_VIEW_FIELDS, ("batch", "substeps", "mu_plant"))
 
     # -- include/qmpc_plant_vary.h -------------------------------------------------------------------------------------
     def set_params(self, mass=None, ibody=None, mu=None, force=None, torque=None):
@@ -883,41 +893,26 @@ class BatchedPlant:
         the handle's value / none.  The plant reads the tensors at every later step -- write into them in place (on the
         stream) to change a push, also between replays of a captured graph; they are kept referenced here.  All None
         unbinds; init() unbinds, reset() does not."""
-        if self.batch is None:
-            raise QmpcError("qmpc_plant_set_params before init()")
-        given = dict(mass=mass, ibody=ibody, mu=mu, force=force, torque=torque)
-        prm = PlantParams()
-        for name, per_robot in PLANT_PARAM_FIELDS.items():
-            t = given[name]
-            if t is not None:
-                shape = (self.batch,) if per_robot == 1 else (self.batch, per_robot)
-                setattr(prm, name, self.ctrl._chk(t, shape, self.torch.float64, name))
-        self.ctrl.mpc._check(self.lib.qmpc_plant_set_params(self.ctrl.mpc.h, self.batch, C.byref(prm)),
-                             "qmpc_plant_set_params")
-        self._params = {k: t for k, t in given.items() if t is not None}
+        self._params = self.ctrl._bind("qmpc_plant_set_params", self.batch, PlantParams, PLANT_PARAM_FIELDS,
+                                       dict(mass=mass, ibody=ibody, mu=mu, force=force, torque=torque))
 
     def enable_stats(self, on=True):
         """Per-robot statistics on the device, updated by every step while on (see stats()).  The first enable
         allocates and synchronises, once."""
-        self.ctrl.mpc._check(self.lib.qmpc_plant_stats_enable(self.ctrl.mpc.h, 1 if on else 0), "qmpc_plant_stats_enable")
+        self.ctrl._call("qmpc_plant_stats_enable", 1 if on else 0)
 
     def reset_stats(self, mask=None, stream=None):
         """The initial values (n 0, z_min +inf, z_max -inf, the rest 0) for the robots where mask is set; None: all."""
-        m = mask.to(self.torch.uint8).contiguous() if mask is not None else None
-        ptr = self.ctrl._chk(m, (self.ctrl.batch,), self.torch.uint8, "mask") if m is not None else None
-        self.ctrl.mpc._check(self.lib.qmpc_plant_stats_reset(self.ctrl.mpc.h, self.ctrl.batch or 0, ptr,
-                                                             self.ctrl._s(stream)), "qmpc_plant_stats_reset")
-        self._keep = m
+        self._keep, ptr = self.ctrl._mask(mask)
+        self.ctrl._call("qmpc_plant_stats_reset", self.ctrl.batch or 0, ptr, self.ctrl._s(stream))
 
     def stats(self):
         """qmpc_plant_stats_get as zero-copy device tensors [B] that alias the accumulators, like view(): n (int32),
         z_min, z_max, roll_max, pitch_max, vx_sum, vy_sum (float64); plus batch, enabled.  A window's mean velocity is
         the difference of two (copied) reads of a sum over the difference of n.  Read-only by contract."""
-        v = PlantStats()
-        self.ctrl.mpc._check(self.lib.qmpc_plant_stats_get(self.ctrl.mpc.h, C.byref(v)), "qmpc_plant_stats_get")
-        res = {k: self.torch.as_tensor(_DeviceArray(getattr(v, k), (v.batch,), ts, self.ctrl), device=self.device)
-               for k, ts in PLANT_STATS_FIELDS.items()}
-        res["batch"], res["enabled"] = v.batch, bool(v.enabled)
+        res = self.ctrl._views("qmpc_plant_stats_get", PlantStats, {k: (None, ts) for k, ts in PLANT_STATS_FIELDS.items()},
+                               ("batch", "enabled"))
+        res["enabled"] = bool(res["enabled"])
         return res
 
 
@@ -940,8 +935,7 @@ class BatchedSensors:
     def init(self, seed=0, stream=None):
         """Counters n = 0, epoch = 0 for every robot, the noise stream's 64-bit seed, nothing bound."""
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        self.ctrl.mpc._check(self.lib.qmpc_sense_init(self.ctrl.mpc.h, self.plant.batch or 0, seed, self.ctrl._s(stream)),
-                             "qmpc_sense_init")
+        self.ctrl._call("qmpc_sense_init", self.plant.batch or 0, seed, self.ctrl._s(stream))
         self.batch = self.plant.batch
         self._params = {}
         self.imu = self.torch.zeros((self.batch, 10), dtype=self.torch.float64, device=self.device)
@@ -952,27 +946,14 @@ class BatchedSensors:
         acc_sigma, gyro_sigma, q_sigma (rad, all 12 joints), qd_sigma (rad/s) [B]; None: that term is absent.  The
         tensors are read at every later sense() -- write into them in place (on the stream) to change a value, also
         between replays of a captured graph; they are kept referenced here.  All None unbinds; init() unbinds."""
-        if self.batch is None:
-            raise QmpcError("qmpc_sense_set_params before init()")
-        given = dict(acc_bias=acc_bias, gyro_bias=gyro_bias, acc_sigma=acc_sigma, gyro_sigma=gyro_sigma, q_sigma=q_sigma,
-                     qd_sigma=qd_sigma)
-        prm = SenseParams()
-        for name, per_robot in SENSE_PARAM_FIELDS.items():
-            t = given[name]
-            if t is not None:
-                shape = (self.batch,) if per_robot == 1 else (self.batch, per_robot)
-                setattr(prm, name, self.ctrl._chk(t, shape, self.torch.float64, name))
-        self.ctrl.mpc._check(self.lib.qmpc_sense_set_params(self.ctrl.mpc.h, self.batch, C.byref(prm)),
-                             "qmpc_sense_set_params")
-        self._params = {k: t for k, t in given.items() if t is not None}
+        self._params = self.ctrl._bind("qmpc_sense_set_params", self.batch, SenseParams, SENSE_PARAM_FIELDS,
+                                       dict(acc_bias=acc_bias, gyro_bias=gyro_bias, acc_sigma=acc_sigma,
+                                            gyro_sigma=gyro_sigma, q_sigma=q_sigma, qd_sigma=qd_sigma))
 
     def reset(self, mask=None, stream=None):
         """A new noise epoch (epoch += 1, n = 0) for the robots where mask is set; None: all."""
-        m = mask.to(self.torch.uint8).contiguous() if mask is not None else None
-        ptr = self.ctrl._chk(m, (self.ctrl.batch,), self.torch.uint8, "mask") if m is not None else None
-        self.ctrl.mpc._check(self.lib.qmpc_sense_reset(self.ctrl.mpc.h, self.batch or 0, ptr, self.ctrl._s(stream)),
-                             "qmpc_sense_reset")
-        self._keep = m   # (alive until the next call: the launch reads it asynchronously)
+        self._keep, ptr = self.ctrl._mask(mask)
+        self.ctrl._call("qmpc_sense_reset", self.batch or 0, ptr, self.ctrl._s(stream))
 
     def sense(self, imu=None, motor=None, stream=None):
         """One reading of the plant's last read-out -> (imu, motor); written into the tensors given, or into the
@@ -983,7 +964,7 @@ class BatchedSensors:
         motor = self.motor if motor is None else motor
         a = self.ctrl._chk(imu, (self.batch, 10), self.torch.float64, "imu")
         b = self.ctrl._chk(motor, (self.batch, 24), self.torch.float64, "motor")
-        self.ctrl.mpc._check(self.lib.qmpc_sense(self.ctrl.mpc.h, self.batch, a, b, self.ctrl._s(stream)), "qmpc_sense")
+        self.ctrl._call("qmpc_sense", self.batch, a, b, self.ctrl._s(stream))
         return imu, motor
 
     def settle(self, n=50, stream=None):
@@ -996,12 +977,36 @@ class BatchedSensors:
     def view(self):
         """qmpc_sense_view_get as zero-copy device tensors n, epoch ([B] int32) that alias the counters, like
         BatchedPlant.view(); plus batch, seed.  Read-only by contract."""
-        v = SenseView()
-        self.ctrl.mpc._check(self.lib.qmpc_sense_view_get(self.ctrl.mpc.h, C.byref(v)), "qmpc_sense_view_get")
-        res = {k: self.torch.as_tensor(_DeviceArray(getattr(v, k), (v.batch,), "<i4", self.ctrl), device=self.device)
-               for k in ("n", "epoch")}
-        res["batch"], res["seed"] = v.batch, v.seed
-        return res
+        return self.ctrl._views("qmpc_sense_view_get", SenseView, dict(n=(None, "<i4"), epoch=(None, "<i4")),
+                                ("batch", "seed"))
+
+
+def _run_ticks(ctrl, who, ticks, graph, tick):
+    """The runner behind rollout() and rollout_sensed() (`who`: the caller's name, which starts its messages): tick()
+    `ticks` times on the current stream, or that block captured on a side stream and replayed once -> the graph, or None."""
+    torch = ctrl.torch
+    ticks = int(ticks)
+    if ticks < 1:
+        raise QmpcError(f"{who}: ticks must be at least 1")
+
+    def block():
+        for _ in range(ticks):
+            tick()
+
+    if not graph:
+        block()
+        return None
+    if ctrl.schedule == "lockstep" and ticks % 13 != 0:
+        raise QmpcError(f"{who}: a captured block holds a multiple of 13 ticks in lockstep, not {ticks}")
+    g = torch.cuda.CUDAGraph()
+    s = torch.cuda.Stream(device=ctrl.device)
+    s.wait_stream(torch.cuda.current_stream(ctrl.device))
+    with torch.cuda.stream(s):
+        with torch.cuda.graph(g, stream=s):
+            block()
+    torch.cuda.current_stream(ctrl.device).wait_stream(s)
+    g.replay()
+    return g
 
 
 def rollout(ctrl, plant, ticks, graph=False):
@@ -1011,30 +1016,11 @@ def rollout(ctrl, plant, ticks, graph=False):
     runs the block again.  With the lockstep schedule a captured block must hold a multiple of 13 ticks (the host
     decides the MPC ticks from its own count, which replays do not advance: include/qmpc_ctrl.h) -- refused otherwise.
     -> dict(effort, state, motor, graph): the plant's own tensors, as the last tick left them."""
-    torch = ctrl.torch
-    ticks = int(ticks)
-    if ticks < 1:
-        raise QmpcError("rollout: ticks must be at least 1")
+    def tick():
+        ctrl.tick_state(plant.state, plant.motor, plant.effort)
+        plant.step(plant.effort)
 
-    def block():
-        for _ in range(ticks):
-            ctrl.tick_state(plant.state, plant.motor, plant.effort)
-            plant.step(plant.effort)
-
-    g = None
-    if not graph:
-        block()
-    else:
-        if ctrl.schedule == "lockstep" and ticks % 13 != 0:
-            raise QmpcError(f"rollout: a captured block holds a multiple of 13 ticks in lockstep, not {ticks}")
-        g = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream(device=ctrl.device)
-        s.wait_stream(torch.cuda.current_stream(ctrl.device))
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(g, stream=s):
-                block()
-        torch.cuda.current_stream(ctrl.device).wait_stream(s)
-        g.replay()
+    g = _run_ticks(ctrl, "rollout", ticks, graph, tick)
     return dict(effort=plant.effort, state=plant.state, motor=plant.motor, graph=g)
 
 
@@ -1044,29 +1030,10 @@ def rollout_sensed(ctrl, plant, sensors, ticks, graph=False):
     reading (sensors.settle() or one sensors.sense() leaves one).  graph=True as in rollout(): the block is captured and
     replayed once, the graph returned for further replays; in lockstep a captured block holds a multiple of 13 ticks.
     -> dict(effort, state, motor, imu, graph): the plant's own tensors and the sensors' imu, as the last tick left them."""
-    torch = ctrl.torch
-    ticks = int(ticks)
-    if ticks < 1:
-        raise QmpcError("rollout_sensed: ticks must be at least 1")
+    def tick():
+        ctrl.tick(sensors.imu, sensors.motor, plant.effort)
+        plant.step(plant.effort)
+        sensors.sense()
 
-    def block():
-        for _ in range(ticks):
-            ctrl.tick(sensors.imu, sensors.motor, plant.effort)
-            plant.step(plant.effort)
-            sensors.sense()
-
-    g = None
-    if not graph:
-        block()
-    else:
-        if ctrl.schedule == "lockstep" and ticks % 13 != 0:
-            raise QmpcError(f"rollout_sensed: a captured block holds a multiple of 13 ticks in lockstep, not {ticks}")
-        g = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream(device=ctrl.device)
-        s.wait_stream(torch.cuda.current_stream(ctrl.device))
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(g, stream=s):
-                block()
-        torch.cuda.current_stream(ctrl.device).wait_stream(s)
-        g.replay()
+    g = _run_ticks(ctrl, "rollout_sensed", ticks, graph, tick)
     return dict(effort=plant.effort, state=plant.state, motor=plant.motor, imu=sensors.imu, graph=g)

@@ -10,8 +10,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/qmpc.h"
@@ -22,34 +24,12 @@
 #include "../../include/qmpc_plant_vary.h"  // ... its per-robot parameters and on-device statistics
 #include "../../include/qmpc_sense.h"   // sensor model between the plant and the controller's sensor path
 #include "qmpc_device.h"
-#include "qmpc_glue.h"
+#include "qmpc_glue.h"    // each launcher is declared once, in the header its defining file includes too:
+#include "qmpc_launch.h"  // qmpc_glue.h, qmpc_plant.h, qmpc_sense.h, and qmpc_launch.h for the rest
 #include "qmpc_plan.h"  // the solve's launch plan (host-only)
 #include "qmpc_plant.h"
 #include "qmpc_sense.h"
 static_assert(kLongHorizon == QMPC_LONG_HORIZON, "qmpc_plan.h and qmpc.h disagree");
-
-// per-class entry points of qmpc_kernels.hip (one translation unit per size class)
-#define QMPC_DECLARE_CLASS(RB)                                                                  \
-  extern "C" size_t qmpc_c##RB##_smem(void);                                                    \
-  extern "C" hipError_t qmpc_c##RB##_prepare(void);                                             \
-  extern "C" int qmpc_c##RB##_resident(void);                                                   \
-  extern "C" hipError_t qmpc_c##RB##_launch(const QmpcParams* P, int grid, hipStream_t stream);   \
-  extern "C" int qmpc_c##RB##_resident_sweep(void);                                              \
-  extern "C" hipError_t qmpc_c##RB##_launch_sweep(const QmpcParams* P, int grid, hipStream_t stream);
-QMPC_DECLARE_CLASS(1)
-QMPC_DECLARE_CLASS(2)
-QMPC_DECLARE_CLASS(3)
-QMPC_DECLARE_CLASS(4)
-QMPC_DECLARE_CLASS(6)
-
-// the decoupled path's consumer (qmpc_engine.hip)
-extern "C" hipError_t qmpc_engine_prepare(void);
-extern "C" hipError_t qmpc_big_prepare(void);
-extern "C" hipError_t qmpc_big_launch(const QmpcParams* P, int grid, hipStream_t stream);
-extern "C" int qmpc_engine_resident(int rb);
-extern "C" int qmpc_engine_capacity(int rb);
-extern "C" hipError_t qmpc_engine_launch(int rb, const QmpcParams* P, int grid, hipStream_t stream);
-extern "C" hipError_t qmpc_admm_big_launch(const QmpcParams* P, int grid, hipStream_t stream);
 
 extern "C" size_t qmpc_smem_bytes(int rb) {
   switch (rb) {
@@ -95,42 +75,6 @@ static hipError_t qmpc_launch(int rb, const QmpcParams* P, int grid, hipStream_t
   }
   return hipErrorInvalidValue;
 }
-extern "C" hipError_t qmpc_launch_keys(const QmpcParams* P, int* nst, float* score, float* demand, hipStream_t stream);
-extern "C" hipError_t qmpc_launch_pack(const qmpc_command* c, const qmpc_record* rec, int batch, int horizon, float dt_mpc,
-                                       hipStream_t stream);
-extern "C" hipError_t qmpc_launch_f2b(const float* r_body, const float* grf, float* f_ff, int batch, hipStream_t stream);
-extern "C" hipError_t qmpc_launch_leg_kin(const float geom[4], const float* q, const float* qd, float* J, float* p,
-                                          float* v, int batch, hipStream_t stream);
-extern "C" hipError_t qmpc_launch_leg_cmd(const float geom[4], const qmpc_leg_command* c, float* tau, float* q_des,
-                                          int batch, hipStream_t stream);
-extern "C" hipError_t qmpc_launch_kf(const qmpc_kf_state* st, const float hip[3], int batch, hipStream_t stream);
-extern "C" hipError_t qmpc_launch_kf_init(float* xhat, float* P, int batch, hipStream_t stream);
-extern "C" hipError_t qmpc_launch_ctrl_init(const QmpcCtrlDev* S, const uint8_t* mask, int counter0, int batch,
-                                            hipStream_t stream);
-extern "C" hipError_t qmpc_launch_ctrl_set(const QmpcCtrlDev* S, const int32_t* gait, const double* vel, int batch,
-                                           hipStream_t stream);
-extern "C" hipError_t qmpc_launch_ctrl_est(const QmpcCtrlDev* S, const float geom[4], const double* imu,
-                                           const double* motor, int batch, hipStream_t stream);
-extern "C" hipError_t qmpc_launch_ctrl_est_state(const QmpcCtrlDev* S, const float geom[4], const double* state,
-                                                 const double* motor, int batch, hipStream_t stream);
-extern "C" hipError_t qmpc_launch_ctrl_loco(const QmpcCtrlDev* S, int batch, int build_list, hipStream_t stream);
-extern "C" hipError_t qmpc_launch_ctrl_loco_aio(const QmpcCtrlDev* S, int batch, hipStream_t stream);
-extern "C" hipError_t qmpc_launch_ctrl_legcmd(const QmpcCtrlDev* S, double* effort, int batch, hipStream_t stream);
-extern "C" hipError_t qmpc_launch_plant_init(const QmpcPlantDev* S, const QmpcPlantConst* K, const uint8_t* mask,
-                                             const double* xyyaw, int batch, hipStream_t stream);
-extern "C" hipError_t qmpc_launch_plant_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
-                                             const float* contact_state, const float* p_des, const float* v_des,
-                                             double* state_out, double* motor_out, int batch, hipStream_t stream,
-                                             const QmpcPlantVary* V, int vary, int stats);
-extern "C" hipError_t qmpc_launch_sense(const QmpcSenseArgs* A, double* imu_out, double* motor_out, int batch, int noisy,
-                                        hipStream_t stream);
-extern "C" hipError_t qmpc_launch_sense_reset(const QmpcSenseArgs* A, const uint8_t* mask, int batch,
-                                              hipStream_t stream);
-extern "C" hipError_t qmpc_launch_plant_stats_reset(const QmpcPlantVary* V, const uint8_t* mask, int batch,
-                                                    hipStream_t stream);
-extern "C" hipError_t qmpc_launch_swing(const float* p0, const float* pf, const float* height, const float* phase,
-                                        const float* swing_time, float* p, float* v, float* a, int n_feet,
-                                        hipStream_t stream);
 
 // Small device arrays are (re)set by this kernel, never by hipMemsetAsync: a memset node captured into a hipGraph writes
 // garbage on replay with this runtime (ROCm 7.2: the counters came back as {512, 24111, 1, 24106, ...}; measured with
@@ -143,7 +87,35 @@ static hipError_t fill_ints(int* p, int n, int v, hipStream_t stream) {
   return hipGetLastError();
 }
 
-struct qmpc_ctx {
+namespace {
+
+// A hipMalloc block and its element count, freed with its owner -- the owner goes with the handle's device current
+// (qmpc_destroy).  Move-only; reads as the pointer.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t n = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {  // (the block held so far goes with o)
+    std::swap(p, o.p), std::swap(n, o.n);
+    return *this;
+  }
+  ~DevBuf() {
+    if (p) hipFree(p);
+  }
+  hipError_t alloc(size_t count) {  // (of an empty owner)
+    const hipError_t e = hipMalloc(&p, sizeof(T) * count);
+    n = e == hipSuccess ? count : 0;
+    return e;
+  }
+  operator T*() const { return p; }
+};
+
+}  // namespace
+
+// (hidden: the library exports the C functions of include/*.h and nothing of this type)
+struct __attribute__((visibility("hidden"))) qmpc_ctx {
   int device = 0;
   int max_batch = 0, max_horizon = 0;
   bool is_setup = false;
@@ -155,18 +127,18 @@ struct qmpc_ctx {
   int max_iter = 1000;
   double tol = 1e-9;
   float leg_geom[4] = {0.062f, 0.209f, 0.195f, 0.004f};  // MiniCheetah.h:31-37 (abad, hip, knee, knee Y offset)
-  double* d_tables = nullptr;  // coef[3][H] then ctab[9][H + 1][H + 1] (zero last row and column: the kernels' identity padding reads them)
-  int* d_lists = nullptr;      // [4][max_batch] robot ids handed to classes 4, 2 and 3, and to the large-problem producer
-  int* d_counts = nullptr;     // [3 sets][QMPC_COUNTERS] (layout in qmpc_device.h); sets 0 / 1 ping-ponged between calls, set 2: calls captured into a graph
+  DevBuf<double> d_tables;  // coef[3][H] then ctab[9][H + 1][H + 1] (zero last row and column: the kernels' identity padding reads them)
+  DevBuf<int> d_lists;      // [4][max_batch] robot ids handed to classes 4, 2 and 3, and to the large-problem producer
+  DevBuf<int> d_counts;     // [3 sets][QMPC_COUNTERS] (layout in qmpc_device.h); sets 0 / 1 ping-ponged between calls, set 2: calls captured into a graph
   // decoupled path (sweep kernel -> work items -> engine kernel) of the 128- and 192-row classes: [0] class 2, [1] class 3
   int split = 1;               // qmpc_set_split: 0 off, 1 automatic (by batch size), 2 always; QMPC_NO_SPLIT=1 in the environment: 0 at creation
-  double* d_wk_hinv[3] = {nullptr, nullptr, nullptr};
-  double* d_wk_xu[3] = {nullptr, nullptr, nullptr};
-  QmpcWorkHdr* d_wk_hdr[3] = {nullptr, nullptr, nullptr};  // [2]: the large problems (192 < n_r <= 432)
-  int* d_wk_order[3] = {nullptr, nullptr, nullptr};
-  double* d_wk_ovf[3] = {nullptr, nullptr, nullptr};  // engine kernels' overflow event pools (one slice per resident workgroup)  // [QMPC_ORDER_BUCKETS][max_batch] item indices, hardest robots first
+  DevBuf<double> d_wk_hinv[3];
+  DevBuf<double> d_wk_xu[3];
+  DevBuf<QmpcWorkHdr> d_wk_hdr[3];  // [2]: the large problems (192 < n_r <= 432)
+  DevBuf<int> d_wk_order[3];
+  DevBuf<double> d_wk_ovf[3];  // engine kernels' overflow event pools (one slice per resident workgroup)  // [QMPC_ORDER_BUCKETS][max_batch] item indices, hardest robots first
   int wk_cap[3] = {0, 0, 0};    // work items per class: a bounded pool, min(max_batch, QMPC_ITEMS_*) -- ensure_pools
-  int* d_fb_lists = nullptr;   // [3][max_batch] robots the engine kernels hand back (128-row, 192-row, large problems)
+  DevBuf<int> d_fb_lists;   // [3][max_batch] robots the engine kernels hand back (128-row, 192-row, large problems)
   int dense = 1;               // qmpc_set_dense: the 64-row class at five workgroups per CU -- 0 never, 1 automatic (by the handle's size), 2 whenever the chain is that class alone
   int chunks = 0;              // qmpc_set_chunks (test hook): run the item classes in at least this many chunks (0 / 1: as few as the pools allow)
   int dbg_engine_events = 0;   // test hook: events the engine may hold per robot (0 = the compiled capacity)
@@ -174,29 +146,28 @@ struct qmpc_ctx {
   // order hint (qmpc_set_order_hint): 0 off, 1 automatic -- a call whose first class is launched over more robots than it has
   // resident workgroups takes them in the order of the previous call's iteration counts (same batch size), longest first
   int order_hint = 1;
-  int* d_hint_iters = nullptr;  // [max_batch] iteration counts the one-kernel classes left in the previous call
+  DevBuf<int> d_hint_iters;  // [max_batch] iteration counts the one-kernel classes left in the previous call, then d_hint_max, d_cu_slots
   // size order (qmpc_set_size_order, default on): no hint usable (first call, another batch size, hint off) -> the first class of a
   // chain, launched over several rounds, takes the robots that fit it largest first by their contact tables; the permutation is
   // built inside the launch (qmpc_kernels.hip: size_order_build)
   int size_order = 1;
-  unsigned long long* d_so_order = nullptr;  // [max_batch] (call number << 32 | robot)
-  unsigned long long* d_prio_cu = nullptr;  // [2048] one-round launches without a hint: one word per CU (qmpc_device.h: prio_cu)
+  DevBuf<unsigned long long> d_so_order;  // [max_batch] (call number << 32 | robot)
+  DevBuf<unsigned long long> d_prio_cu;  // [2048] one-round launches without a hint: one word per CU (qmpc_device.h: prio_cu)
   int hint_batch = 0;           // batch size of the call that wrote d_hint_iters (0: none yet)
-  int* d_hint_max = nullptr;    // [3] largest iteration count of the last calls (slots rotated by hint_call: read / fold / clear)
-  int* d_cu_slots = nullptr;
+  int* d_hint_max = nullptr;    // (a view into d_hint_iters' block) [3] largest iteration count of the last calls (slots rotated by hint_call: read / fold / clear)
+  int* d_cu_slots = nullptr;    // (a view into d_hint_iters' block)
   int bal_debug = 0;  // qmpc_set_debug_balance
   int max_stance = 0;          // caller's bound on stance foot-steps per robot (0 = unknown)
   int min_stance = 0;          // ... and lower bound (0 = unknown)
   int admm_mode = 0, admm_max_iter = 10000;  // JCQP alternate, see qmpc_settings_jcqp
   double admm_rho = 1e-7, admm_sigma = 1e-8, admm_alpha = 1.5, admm_term = 0.1;
-  double* d_evpool = nullptr;  // largest size class: global event pool (allocated on first use)
-  double* d_ovpool = nullptr;  // the other classes: overflow event pool, ov_nslice slices, recycled within a call (one flag per slice)
-  int* d_ovflags = nullptr;    // [ov_nslice_alloc] 0 = free
-  int ov_nslice_alloc = 0;     // slices allocated: min(max_batch, 2048)
+  DevBuf<double> d_evpool;  // largest size class: global event pool (allocated on first use)
+  DevBuf<double> d_ovpool;  // the other classes: overflow event pool, ov_nslice slices, recycled within a call (one flag per slice)
+  DevBuf<int> d_ovflags;    // one per slice allocated (min(max_batch, 2048)): 0 = free
   int ov_nslice = 0;           // slices in use (all of them unless qmpc_set_debug_overflow_slices says fewer)
   int ov_spin = 1 << 22;       // probes of a robot that finds every slice taken before it gives up (test hook: qmpc_set_debug_overflow_slices)
   bool device_error = false;   // a HIP call of this handle failed since the last successful solve (fail()): see solve_impl
-  int* d_evflags = nullptr;
+  DevBuf<int> d_evflags;
   int ev_nslot = 0;
   bool dbg_pool_busy = false;  // test hook: every slice of the 192-row class's pool looks taken (qmpc_set_debug_pool_busy)
   int32_t* ws = nullptr;  // warm-start buffer (device), see qmpc_set_warm_start
@@ -207,8 +178,7 @@ struct qmpc_ctx {
   double* dbg_aux = nullptr;
   long long* dbg_clk = nullptr;
   // staging for qmpc_solve_host
-  void* d_stage = nullptr;
-  size_t stage_bytes = 0;
+  DevBuf<char> d_stage;
   // the handle's device state (tables, work lists, counters) is ordered by ONE stream at a
   // time: a call that arrives on a different stream is made to wait for the previous one
   hipStream_t last_stream = nullptr;
@@ -226,7 +196,7 @@ struct qmpc_ctx {
   // batched locomotion controller (qmpc_ctrl.h): device state for max_batch robots, made by qmpc_ctrl_init
   struct Ctrl {
     QmpcCtrlDev d{};
-    void* buf = nullptr;
+    DevBuf<char> buf;
     int batch = 0;       // robots initialised
     long long ticks = 0; // T: qmpc_ctrl_tick calls since qmpc_ctrl_init
     int schedule = QMPC_CTRL_LOCKSTEP;  // qmpc_ctrl_set_schedule
@@ -234,31 +204,38 @@ struct qmpc_ctx {
     bool started = false;               // a tick or a reset has been enqueued since qmpc_ctrl_init: the schedule is fixed
     double freq = 0;                    // qmpc_ctrl_init's: the plant's dt is 1 / freq in double
   };
-  Ctrl* ctrl = nullptr;
+  std::unique_ptr<Ctrl> ctrl;
   // reduced-order plant (qmpc_plant.h): device state for max_batch robots, made by qmpc_plant_init
   struct Plant {
     QmpcPlantDev d{};
-    void* buf = nullptr;
+    DevBuf<char> buf;
     int batch = 0;  // robots initialised
     double mu = 0;
     int substeps = 1;
     // qmpc_plant_vary.h: the caller's arrays as bound (all null: none), the statistics' allocation and switch
     QmpcPlantVary vary{};
     bool bound = false;
-    void* stats_buf = nullptr;
+    DevBuf<char> stats_buf;
     bool stats_on = false;
   };
-  Plant* plant = nullptr;
+  std::unique_ptr<Plant> plant;
   // sensor model (qmpc_sense.h): the counters n[max_batch], epoch[max_batch] in one allocation made by qmpc_sense_init,
   // the seed, and the caller's arrays as bound (all null: the ideal sensor)
   struct Sense {
-    void* buf = nullptr;
+    DevBuf<int> buf;
     int batch = 0;  // robots initialised
     uint64_t seed = 0;
     QmpcSenseArgs a{};
     bool bound = false;
   };
-  Sense* sense = nullptr;
+  std::unique_ptr<Sense> sense;
+  // (the device arrays and the sub-states free themselves)
+  ~qmpc_ctx() {
+    if (h_pin) hipHostFree(h_pin);
+    if (order_ev) hipEventDestroy(order_ev);
+    if (host_ev) hipEventDestroy(host_ev);
+    if (host_stream) hipStreamDestroy(host_stream);
+  }
 };
 
 namespace {
@@ -307,6 +284,15 @@ int order_after_previous(qmpc_ctx* c, hipStream_t stream) {
   return QMPC_OK;
 }
 
+// The preamble of an entry point that enqueues, after its checks: the handle's device current for as long as this lives,
+// the caller's stream, ordered after whatever stream served the handle before.  rc != QMPC_OK: enqueue nothing
+struct Enqueue {
+  DeviceGuard g;
+  hipStream_t stream;
+  int rc;
+  Enqueue(qmpc_ctx* c, void* stream_) : g(c->device), stream((hipStream_t)stream_), rc(order_after_previous(c, stream)) {}
+};
+
 // The solve record (qmpc_inputs), described once: f(array, bytes per robot at horizon h, per robot?) for each of its
 // arrays in declaration order.  weights / alpha / x_drag with stride 0 are one row shared by the batch.  `in` may be a
 // copy whose pointers f rebinds.
@@ -349,7 +335,49 @@ const float kAbadLocation[3] = {0.19f, 0.049f, 0.f};
 
 namespace {
 int ensure_pools(qmpc_ctx* c);
+
+// an allocation of n elements, zeroed
+template <class T>
+hipError_t alloc_zeroed(DevBuf<T>& b, size_t n) {
+  const hipError_t e = b.alloc(n);
+  return e == hipSuccess ? hipMemset(b, 0, sizeof(T) * n) : e;
 }
+
+// qmpc_create's device side: every array a handle has from the start, the kernels' attributes, the first launch
+hipError_t create_device_state(qmpc_ctx* c) {
+#define HIP_OK(call)                        \
+  do {                                      \
+    const hipError_t e__ = (call);          \
+    if (e__ != hipSuccess) return e__;      \
+  } while (0)
+  const size_t H = (size_t)c->max_horizon, B = (size_t)c->max_batch;
+  HIP_OK(c->d_tables.alloc(3 * H + 9 * (H + 1) * (H + 1)));
+  HIP_OK(c->d_lists.alloc(4 * B));  // ([3]: the large problems, horizons > 16)
+  HIP_OK(alloc_zeroed(c->d_counts, 3 * QMPC_COUNTERS));
+  HIP_OK(c->d_fb_lists.alloc(3 * B));
+  HIP_OK(alloc_zeroed(c->d_hint_iters, B + 4 + 2048));  // [max_batch] hint iterations, [4] d_hint_max, [2048] d_cu_slots
+  c->d_hint_max = c->d_hint_iters + B;
+  c->d_cu_slots = c->d_hint_max + 4;  // [2048] the 96-row class's per-CU placement words (zero whenever no kernel runs)
+  HIP_OK(alloc_zeroed(c->d_prio_cu, 2048));
+  HIP_OK(alloc_zeroed(c->d_so_order, 2 * B));  // near copy, far copy (call numbers start at 1)
+  // a robot whose on-chip event pool fills up continues here.  The slices are RECYCLED within a call (one flag per slice,
+  // taken with a compare-and-swap, released when its robot is done): ov_nslice bounds the robots that hold one AT THE SAME
+  // TIME, not the robots of a call; a robot that finds every slice taken waits (ov_spin probes), then falls back to the
+  // Schur-form engine.  Every flag is 0 between calls; after a call that ended in a device error they are re-armed
+  // (solve_impl) -- a flag left at 1 would otherwise be lost for the life of the handle
+  // (2048 slices of 192 KiB: what a call of 8192 robots needs when the 64-row class runs five per CU ahead of larger
+  //  classes -- qmpc_plan.h: plan_solve)
+  c->ov_nslice = c->max_batch < 2048 ? c->max_batch : 2048;
+  HIP_OK(c->d_ovpool.alloc((size_t)c->ov_nslice * QMPC_OV_SLICE));
+  HIP_OK(alloc_zeroed(c->d_ovflags, (size_t)c->ov_nslice));
+  HIP_OK(qmpc_prepare());
+  // the runtime loads a translation unit's code object at the first launch of one of its kernels (2 MiB of device
+  // memory): this file's small kernel (fill) is first launched HERE, not inside some later solve call
+  HIP_OK(fill_ints(c->d_hint_max, 4, 0, nullptr));
+  return hipStreamSynchronize(nullptr);
+#undef HIP_OK
+}
+}  // namespace
 
 extern "C" {
 
@@ -368,49 +396,10 @@ int qmpc_create(int device_id, int max_batch, int max_horizon, qmpc_handle* out)
   c->device = device_id;
   c->max_batch = max_batch;
   c->max_horizon = max_horizon;
+  const char* ns = std::getenv("QMPC_NO_SPLIT");
+  c->split = (ns && ns[0] == '1') ? 0 : 1;
   DeviceGuard g(device_id);
-  const size_t H = (size_t)max_horizon;
-  hipError_t e = hipMalloc(&c->d_tables, sizeof(double) * (3 * H + 9 * (H + 1) * (H + 1)));
-  if (e == hipSuccess) e = hipMalloc(&c->d_lists, sizeof(int) * 4 * (size_t)max_batch);  // ([3]: the large problems, horizons > 16)
-  if (e == hipSuccess) e = hipMalloc(&c->d_counts, sizeof(int) * 3 * QMPC_COUNTERS);
-  if (e == hipSuccess) e = hipMemset(c->d_counts, 0, sizeof(int) * 3 * QMPC_COUNTERS);
-  if (e == hipSuccess) e = hipMalloc(&c->d_fb_lists, sizeof(int) * 3 * (size_t)max_batch);
-  // [max_batch] hint iterations, [4] d_hint_max, [2048] d_cu_slots
-  if (e == hipSuccess) e = hipMalloc(&c->d_hint_iters, sizeof(int) * ((size_t)max_batch + 4 + 2048));
-  if (e == hipSuccess) e = hipMemset(c->d_hint_iters, 0, sizeof(int) * ((size_t)max_batch + 4 + 2048));
-  if (e == hipSuccess) {
-    c->d_hint_max = c->d_hint_iters + max_batch;
-    c->d_cu_slots = c->d_hint_max + 4;  // [2048] the 96-row class's per-CU placement words (zero whenever no kernel runs)
-  }
-  if (e == hipSuccess) e = hipMalloc(&c->d_prio_cu, sizeof(unsigned long long) * 2048);
-  if (e == hipSuccess) e = hipMemset(c->d_prio_cu, 0, sizeof(unsigned long long) * 2048);
-  if (e == hipSuccess) e = hipMalloc(&c->d_so_order, sizeof(unsigned long long) * 2 * (size_t)max_batch);  // near copy, far copy
-  if (e == hipSuccess) e = hipMemset(c->d_so_order, 0, sizeof(unsigned long long) * 2 * (size_t)max_batch);  // (call numbers start at 1)
-  {
-    const char* ns = std::getenv("QMPC_NO_SPLIT");
-    c->split = (ns && ns[0] == '1') ? 0 : 1;
-  }
-  if (e == hipSuccess) {
-    // a robot whose on-chip event pool fills up continues here.  The slices are RECYCLED within a call (one flag per slice,
-    // taken with a compare-and-swap, released when its robot is done): ov_nslice bounds the robots that hold one AT THE SAME
-    // TIME, not the robots of a call; a robot that finds every slice taken waits (ov_spin probes), then falls back to the
-    // Schur-form engine.  Every flag is 0 between calls; after a call that ended in a device error they are re-armed
-    // (solve_impl) -- a flag left at 1 would otherwise be lost for the life of the handle
-    // (2048 slices of 192 KiB: what a call of 8192 robots needs when the 64-row class runs five per CU ahead of larger
-    //  classes -- qmpc_plan.h: plan_solve)
-    c->ov_nslice_alloc = c->ov_nslice = max_batch < 2048 ? max_batch : 2048;
-    e = hipMalloc(&c->d_ovpool, sizeof(double) * (size_t)c->ov_nslice_alloc * QMPC_OV_SLICE);
-    if (e == hipSuccess) e = hipMalloc(&c->d_ovflags, sizeof(int) * (size_t)c->ov_nslice_alloc);
-    if (e == hipSuccess) e = hipMemset(c->d_ovflags, 0, sizeof(int) * (size_t)c->ov_nslice_alloc);
-  }
-  if (e == hipSuccess) e = qmpc_prepare();
-  if (e == hipSuccess) {
-    // the runtime loads a translation unit's code object at the first launch of one of its kernels (2 MiB of device
-    // memory): this file's small kernel (fill) is first launched HERE, not inside some later solve call
-    e = fill_ints(c->d_hint_max, 4, 0, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-  }
-  if (e != hipSuccess) {
+  if (create_device_state(c) != hipSuccess) {
     qmpc_destroy(c);
     return QMPC_ERR_DEVICE;
   }
@@ -420,39 +409,7 @@ int qmpc_create(int device_id, int max_batch, int max_horizon, qmpc_handle* out)
 
 int qmpc_destroy(qmpc_handle h) {
   if (!h) return QMPC_ERR_ARG;
-  {
-    DeviceGuard g(h->device);
-    if (h->d_tables) hipFree(h->d_tables);
-    if (h->d_lists) hipFree(h->d_lists);
-    if (h->d_counts) hipFree(h->d_counts);
-    if (h->d_stage) hipFree(h->d_stage);
-    if (h->d_evpool) hipFree(h->d_evpool);
-    if (h->d_ovpool) hipFree(h->d_ovpool);
-    if (h->d_ovflags) hipFree(h->d_ovflags);
-    if (h->d_evflags) hipFree(h->d_evflags);
-    if (h->d_fb_lists) hipFree(h->d_fb_lists);
-    if (h->d_hint_iters) hipFree(h->d_hint_iters);
-    if (h->d_so_order) hipFree(h->d_so_order);
-    if (h->d_prio_cu) hipFree(h->d_prio_cu);
-    for (int k = 0; k < 3; ++k) {
-      if (h->d_wk_hinv[k]) hipFree(h->d_wk_hinv[k]);
-      if (h->d_wk_xu[k]) hipFree(h->d_wk_xu[k]);
-      if (h->d_wk_hdr[k]) hipFree(h->d_wk_hdr[k]);
-      if (h->d_wk_order[k]) hipFree(h->d_wk_order[k]);
-      if (h->d_wk_ovf[k]) hipFree(h->d_wk_ovf[k]);
-    }
-    if (h->h_pin) hipHostFree(h->h_pin);
-    if (h->order_ev) hipEventDestroy(h->order_ev);
-    if (h->host_ev) hipEventDestroy(h->host_ev);
-    if (h->host_stream) hipStreamDestroy(h->host_stream);
-    if (h->ctrl && h->ctrl->buf) hipFree(h->ctrl->buf);
-    if (h->plant && h->plant->buf) hipFree(h->plant->buf);
-    if (h->plant && h->plant->stats_buf) hipFree(h->plant->stats_buf);
-    if (h->sense && h->sense->buf) hipFree(h->sense->buf);
-  }
-  delete h->ctrl;
-  delete h->plant;
-  delete h->sense;
+  DeviceGuard g(h->device);
   delete h;
   return QMPC_OK;
 }
@@ -474,9 +431,8 @@ int qmpc_setup(qmpc_handle c, double dt, int horizon, double mu, double f_max) {
     // synchronises the device and cannot be captured into a graph)
     DeviceGuard g0(c->device);
     const int nslot = c->max_batch < 1024 ? c->max_batch : 1024;
-    HIP_TRY(c, hipMalloc(&c->d_evpool, sizeof(double) * (size_t)nslot * QMPC_EV_SLICE3));
-    HIP_TRY(c, hipMalloc(&c->d_evflags, sizeof(int) * (size_t)nslot));
-    HIP_TRY(c, hipMemset(c->d_evflags, 0, sizeof(int) * (size_t)nslot));
+    HIP_TRY(c, c->d_evpool.alloc((size_t)nslot * QMPC_EV_SLICE3));
+    HIP_TRY(c, alloc_zeroed(c->d_evflags, (size_t)nslot));
     c->ev_nslot = nslot;
   }
   // the tables depend on (dt, horizon) only: the reference's caller repeats setup_problem with the
@@ -605,8 +561,9 @@ int qmpc_set_debug_overflow_spin(qmpc_handle c, int probes) {
 
 int qmpc_set_debug_overflow_slices(qmpc_handle c, int n) {
   if (!c) return QMPC_ERR_ARG;
-  if (n > c->ov_nslice_alloc) return QMPC_ERR_ARG;  // more slices than allocated
-  c->ov_nslice = n < 0 ? c->ov_nslice_alloc : n;
+  const int allocated = (int)c->d_ovflags.n;
+  if (n > allocated) return QMPC_ERR_ARG;  // more slices than allocated
+  c->ov_nslice = n < 0 ? allocated : n;
   return QMPC_OK;
 }
 
@@ -740,7 +697,7 @@ PlanSettings plan_settings(const qmpc_ctx* c) {
   s.split = c->split; s.dense = c->dense; s.chunks = c->chunks; s.admm_mode = c->admm_mode;
   s.order_hint = c->order_hint; s.size_order = c->size_order; s.hint_batch = c->hint_batch;
   for (int sk = 0; sk < 3; ++sk) s.wk_cap[sk] = c->wk_cap[sk];
-  s.has_ws = c->ws != nullptr; s.has_evflags = c->d_evflags != nullptr;
+  s.has_ws = c->ws != nullptr; s.has_evflags = c->d_evflags.p != nullptr;
   return s;
 }
 
@@ -762,25 +719,27 @@ int ensure_items(qmpc_ctx* c, int sk) {
   size_t wgs = (size_t)qmpc_engine_resident(kItems[sk].cls);
   if (wgs == 0 || wgs > cap) wgs = cap;
   // all or nothing: an allocation that fails half-way (the pools are up to 1.5 GiB) must not leave a pool that LOOKS
-  // present -- the next solve would divide by wk_cap == 0 or launch on null arrays
-  hipError_t e = hipMalloc(&c->d_wk_hinv[sk], sizeof(double) * cap * ld * ld);
-  if (e == hipSuccess) e = hipMalloc(&c->d_wk_xu[sk], sizeof(double) * cap * ld);
-  if (e == hipSuccess) e = hipMalloc(&c->d_wk_hdr[sk], sizeof(QmpcWorkHdr) * cap);
-  if (e == hipSuccess) e = hipMalloc(&c->d_wk_order[sk], sizeof(int) * QMPC_ORDER_BUCKETS * cap);
-  if (e == hipSuccess) e = hipMalloc(&c->d_wk_ovf[sk], sizeof(double) * wgs * QMPC_ENGINE_OVF_EVENTS * kItems[sk].ev_doubles);
-  if (e != hipSuccess) {
-    if (c->d_wk_hinv[sk]) hipFree(c->d_wk_hinv[sk]);
-    if (c->d_wk_xu[sk]) hipFree(c->d_wk_xu[sk]);
-    if (c->d_wk_hdr[sk]) hipFree(c->d_wk_hdr[sk]);
-    if (c->d_wk_order[sk]) hipFree(c->d_wk_order[sk]);
-    if (c->d_wk_ovf[sk]) hipFree(c->d_wk_ovf[sk]);
-    c->d_wk_hinv[sk] = nullptr; c->d_wk_xu[sk] = nullptr; c->d_wk_hdr[sk] = nullptr;
-    c->d_wk_order[sk] = nullptr; c->d_wk_ovf[sk] = nullptr;
-    (void)hipGetLastError();
-    return fail(c, e, "work-item pool allocation");
+  // present -- the next solve would divide by wk_cap == 0 or launch on null arrays.  So: into locals, which free what they
+  // got when one of them fails, and into the handle by move when all of them succeeded
+  hipError_t e;
+  {
+    DevBuf<double> hinv, xu, ovf;
+    DevBuf<QmpcWorkHdr> hdr;
+    DevBuf<int> order;
+    e = hinv.alloc(cap * ld * ld);
+    if (e == hipSuccess) e = xu.alloc(cap * ld);
+    if (e == hipSuccess) e = hdr.alloc(cap);
+    if (e == hipSuccess) e = order.alloc(QMPC_ORDER_BUCKETS * cap);
+    if (e == hipSuccess) e = ovf.alloc(wgs * QMPC_ENGINE_OVF_EVENTS * kItems[sk].ev_doubles);
+    if (e == hipSuccess) {
+      c->d_wk_hinv[sk] = std::move(hinv); c->d_wk_xu[sk] = std::move(xu); c->d_wk_hdr[sk] = std::move(hdr);
+      c->d_wk_order[sk] = std::move(order); c->d_wk_ovf[sk] = std::move(ovf);
+      c->wk_cap[sk] = (int)cap;
+      return QMPC_OK;
+    }
   }
-  c->wk_cap[sk] = (int)cap;
-  return QMPC_OK;
+  (void)hipGetLastError();
+  return fail(c, e, "work-item pool allocation");
 }
 
 // Every pool the current setup, stance hints and split mode can reach, allocated NOW (qmpc_setup, the hint setters,
@@ -895,7 +854,7 @@ int enqueue(qmpc_ctx* c, const QmpcParams& bound, const SolvePlan& sp, const int
     if (L.kind <= FILL_PRIO) {  // (FILL_EVFLAGS: no kernel of this handle is in flight on another stream -- ordered by solve_impl)
       if (L.kind == FILL_COUNTERS) HIP_TRY(c, fill_ints(cnt, QMPC_COUNTERS, 0, stream));
       else if (L.kind == FILL_EVFLAGS) HIP_TRY(c, fill_ints(c->d_evflags, c->ev_nslot, c->dbg_pool_busy ? 1 : 0, stream));
-      else HIP_TRY(c, fill_ints(reinterpret_cast<int*>(c->d_prio_cu), 2 * 2048, 0, stream));
+      else HIP_TRY(c, fill_ints(reinterpret_cast<int*>(c->d_prio_cu.p), 2 * 2048, 0, stream));
       continue;
     }
     QmpcParams P = bound;
@@ -949,15 +908,15 @@ int solve_impl(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_command
                float* f_ff, void* stream_, const int* due_list = nullptr, int* due_count = nullptr) {
   if (const int rc = check_solve_call(c, batch, in, cmd, out, due_list, due_count)) return rc;
   if (batch == 0) return QMPC_OK;
-  hipStream_t stream = (hipStream_t)stream_;
-  DeviceGuard g(c->device);
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  hipStream_t stream = q.stream;
   const bool capturing = is_capturing(stream);
-  if (const int rc = order_after_previous(c, stream)) return rc;
   if (c->device_error && !capturing) {
     // the previous call (or set-up step) of this handle failed on the device: whatever its kernels left in the
     // recycled-slice flags and the per-CU placement words is void.  Re-armed with the fill kernel (no memset node: they
     // replay wrongly when captured, and this path must not differ from the normal one in kind)
-    if (c->d_ovflags && c->ov_nslice > 0) HIP_TRY(c, fill_ints(c->d_ovflags, c->ov_nslice_alloc, 0, stream));
+    if (c->d_ovflags && c->ov_nslice > 0) HIP_TRY(c, fill_ints(c->d_ovflags, (int)c->d_ovflags.n, 0, stream));
     c->device_error = false;
   }
   const QmpcParams P = bind_params(c, batch, in, cmd, out, f_ff, capturing);
@@ -991,9 +950,9 @@ int qmpc_pack(qmpc_handle c, int batch, const qmpc_command* cmd, const qmpc_reco
   if (!command_ok(cmd)) return QMPC_ERR_ARG;
   if (!rec->p || !rec->v || !rec->q || !rec->w || !rec->r || !rec->yaw || !rec->traj || !rec->gait || !rec->x_drag)
     return QMPC_ERR_ARG;
-  DeviceGuard g(c->device);
-  if (const int rc = order_after_previous(c, (hipStream_t)stream_)) return rc;
-  HIP_TRY(c, qmpc_launch_pack(cmd, rec, batch, c->horizon, (float)c->dt, (hipStream_t)stream_));
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  HIP_TRY(c, qmpc_launch_pack(cmd, rec, batch, c->horizon, (float)c->dt, q.stream));
   return QMPC_OK;
 }
 
@@ -1001,9 +960,9 @@ int qmpc_forces_to_body(qmpc_handle c, int batch, const float* r_body, const flo
   if (!c || !r_body || !grf || !f_ff) return QMPC_ERR_ARG;
   if (batch < 0 || batch > c->max_batch) return QMPC_ERR_ARG;
   if (batch == 0) return QMPC_OK;
-  DeviceGuard g(c->device);
-  if (const int rc = order_after_previous(c, (hipStream_t)stream_)) return rc;
-  HIP_TRY(c, qmpc_launch_f2b(r_body, grf, f_ff, batch, (hipStream_t)stream_));
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  HIP_TRY(c, qmpc_launch_f2b(r_body, grf, f_ff, batch, q.stream));
   return QMPC_OK;
 }
 
@@ -1063,16 +1022,13 @@ int host_enqueue(qmpc_ctx* c, int batch, const qmpc_inputs* in, const qmpc_outpu
   if (!c->host_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->host_stream, hipStreamNonBlocking));
   if (!c->host_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->host_ev, hipEventDisableTiming));
   const bool in_place = batch <= 64;
-  if (!in_place && total > c->stage_bytes) {
-    if (c->d_stage) hipFree(c->d_stage);
-    c->d_stage = nullptr;
-    c->stage_bytes = 0;
-    HIP_TRY(c, hipMalloc(&c->d_stage, total));
-    c->stage_bytes = total;
+  if (!in_place && total > c->d_stage.n) {
+    c->d_stage = DevBuf<char>();  // (the smaller block goes first)
+    HIP_TRY(c, c->d_stage.alloc(total));
   }
   char* hb = (char*)c->h_pin;
   hipStream_t s = c->host_stream;
-  char* base = in_place ? hb : (char*)c->d_stage;
+  char* base = in_place ? hb : c->d_stage.p;
   // gather the record into the pinned block; the solve reads it at `base`
   qmpc_inputs din = *in;
   n = 0;
@@ -1234,46 +1190,52 @@ int qmpc_solve_sharded(const qmpc_handle* handles, int n_handles, int batch, con
 // Batched locomotion controller (include/qmpc_ctrl.h).  The kernels are in qmpc_glue.hip.
 namespace {
 
-// Lay the controller's arrays out in one allocation (base == nullptr: only count), each array 256-byte aligned
-size_t ctrl_carve(QmpcCtrlDev& d, char* base, int M) {
+// One array of an X-macro list (QMPC_CTRL_ARRAYS, QMPC_PLANT_ARRAYS) laid out in an allocation: 256-byte aligned,
+// per_robot elements for each of M robots (base == nullptr: only count)
+template <class T>
+void carve_array(T*& member, char* base, size_t& off, int per_robot, int M) {
+  off = (off + 255) & ~(size_t)255;
+  member = base ? reinterpret_cast<T*>(base + off) : nullptr;
+  off += sizeof(T) * (size_t)per_robot * (size_t)M;
+}
+#define QMPC_CARVE(T, name, per_robot) carve_array(d.name, base, off, per_robot, M);
+size_t carve(QmpcCtrlDev& d, char* base, int M) {
   size_t off = 0;
-#define QMPC_CTRL_CARVE(T, name, per_robot)                     \
-  off = (off + 255) & ~(size_t)255;                            \
-  d.name = base ? reinterpret_cast<T*>(base + off) : nullptr;  \
-  off += sizeof(T) * (size_t)(per_robot) * (size_t)M;
-  QMPC_CTRL_ARRAYS(QMPC_CTRL_CARVE)
-#undef QMPC_CTRL_CARVE
+  QMPC_CTRL_ARRAYS(QMPC_CARVE)
   return off;
 }
+size_t carve(QmpcPlantDev& d, char* base, int M) {
+  size_t off = 0;
+  QMPC_PLANT_ARRAYS(QMPC_CARVE)
+  return off;
+}
+#undef QMPC_CARVE
+
+// d's arrays as views into buf, which is allocated on first use (a later init of the same handle reuses the block)
+template <class Dev>
+hipError_t carve_block(DevBuf<char>& buf, Dev& d, int M) {
+  if (!buf) {
+    const hipError_t e = buf.alloc(carve(d, nullptr, M));
+    if (e != hipSuccess) return e;
+  }
+  carve(d, buf, M);
+  return hipSuccess;
+}
+
+bool ctrl_ready(const qmpc_ctx* c) { return c->ctrl && c->ctrl->batch; }
+bool plant_ready(const qmpc_ctx* c) { return c->plant && c->plant->batch; }
 
 int ctrl_check(qmpc_ctx* c, int batch) {
   if (!c) return QMPC_ERR_ARG;
-  if (!c->ctrl || !c->ctrl->batch) return QMPC_ERR_STATE;
+  if (!ctrl_ready(c)) return QMPC_ERR_STATE;
   if (batch != c->ctrl->batch) return QMPC_ERR_ARG;
-  return QMPC_OK;
-}
-
-// pre_work: orientation estimator + leg data, then the Kalman filter (previous tick's leg data and contact phase)
-int ctrl_prework(qmpc_ctx* c, const double* imu, const double* motor, hipStream_t stream) {
-  const QmpcCtrlDev& d = c->ctrl->d;
-  const int B = c->ctrl->batch;
-  HIP_TRY(c, qmpc_launch_ctrl_est(&d, c->leg_geom, imu, motor, B, stream));
-  qmpc_kf_state st{d.xhat, d.P, d.r_body, d.a_world, d.omega_body, d.contact_phase, d.kf_p, d.kf_v,
-                   d.position, d.v_world, d.v_body};
-  HIP_TRY(c, qmpc_launch_kf(&st, kAbadLocation, B, stream));
-  return QMPC_OK;
-}
-
-// pre_work of a tick driven by simulator ground truth: the cheater estimators + leg data in one launch, no filter
-int ctrl_prework_state(qmpc_ctx* c, const double* state, const double* motor, hipStream_t stream) {
-  HIP_TRY(c, qmpc_launch_ctrl_est_state(&c->ctrl->d, c->leg_geom, state, motor, c->ctrl->batch, stream));
   return QMPC_OK;
 }
 
 // A tick after its pre_work, whichever estimators that ran: the locomotion kernel, the solve by the handle's schedule, the
 // leg commands.  The caller holds the DeviceGuard and has ordered the stream.
 int ctrl_after_prework(qmpc_ctx* c, int batch, double* effort, hipStream_t stream) {
-  qmpc_ctx::Ctrl* k = c->ctrl;
+  qmpc_ctx::Ctrl* k = c->ctrl.get();
   const QmpcCtrlDev& d = k->d;
   const bool per_robot = k->schedule == QMPC_CTRL_PER_ROBOT;
   const bool aio = k->robot_mode == 1;  // (per_robot holds: qmpc_ctrl_set_robot_mode)
@@ -1318,6 +1280,29 @@ int ctrl_after_prework(qmpc_ctx* c, int batch, double* effort, hipStream_t strea
   return QMPC_OK;
 }
 
+// The one body of qmpc_ctrl_prework / _tick and their _state pair: pre_work through the estimator launch `est`, then, when
+// `tick`, the rest of the tick.
+//   qmpc_launch_ctrl_est (in = imu): orientation estimator + leg data, then the Kalman filter (previous tick's leg data and
+//   contact phase);  qmpc_launch_ctrl_est_state (in = simulator ground truth): the cheater estimators + leg data in one
+//   launch, no filter
+using EstLaunch = hipError_t (*)(const QmpcCtrlDev*, const float*, const double*, const double*, int, hipStream_t);
+int ctrl_tick(qmpc_ctx* c, int batch, EstLaunch est, const double* in, const double* motor, double* effort, bool tick,
+              void* stream_) {
+  if (const int rc = ctrl_check(c, batch)) return rc;
+  if (!in || !motor || (tick && !effort)) return QMPC_ERR_ARG;
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  if (tick) c->ctrl->started = true;
+  const QmpcCtrlDev& d = c->ctrl->d;
+  HIP_TRY(c, est(&d, c->leg_geom, in, motor, batch, q.stream));
+  if (est == qmpc_launch_ctrl_est) {
+    qmpc_kf_state st{d.xhat, d.P, d.r_body, d.a_world, d.omega_body, d.contact_phase, d.kf_p, d.kf_v,
+                     d.position, d.v_world, d.v_body};
+    HIP_TRY(c, qmpc_launch_kf(&st, kAbadLocation, batch, q.stream));
+  }
+  return tick ? ctrl_after_prework(c, batch, effort, q.stream) : QMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1331,13 +1316,9 @@ int qmpc_ctrl_init(qmpc_handle c, int batch, double freq, const double pid[4], v
   if (const int rc = qmpc_setup(c, (double)dt_mpc, 14, 0.4, 120.0)) return rc;
   DeviceGuard g(c->device);
   hipStream_t stream = (hipStream_t)stream_;
-  if (!c->ctrl) c->ctrl = new qmpc_ctx::Ctrl();
-  qmpc_ctx::Ctrl* k = c->ctrl;
-  if (!k->buf) {
-    const size_t bytes = ctrl_carve(k->d, nullptr, c->max_batch);
-    HIP_TRY(c, hipMalloc(&k->buf, bytes));
-  }
-  ctrl_carve(k->d, static_cast<char*>(k->buf), c->max_batch);
+  if (!c->ctrl) c->ctrl.reset(new qmpc_ctx::Ctrl());
+  qmpc_ctx::Ctrl* k = c->ctrl.get();
+  HIP_TRY(c, carve_block(k->buf, k->d, c->max_batch));
   k->d.dt = dt;
   k->d.dt_mpc = dt_mpc;
   k->d.kp_joint = (float)pid[2];  // Vec4<float> ctrlParam (GaitCtrller.cpp:14-16)
@@ -1356,21 +1337,20 @@ int qmpc_ctrl_init(qmpc_handle c, int batch, double freq, const double pid[4], v
 int qmpc_ctrl_reset(qmpc_handle c, int batch, const uint8_t* mask_dev, void* stream_) {
   if (const int rc = ctrl_check(c, batch)) return rc;
   if (!mask_dev) return QMPC_ERR_ARG;
-  DeviceGuard g(c->device);
-  hipStream_t stream = (hipStream_t)stream_;
-  if (const int rc = order_after_previous(c, stream)) return rc;
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
   // lockstep: the counter restarts at T mod 13 (the batch keeps solving on the same ticks); per-robot schedule: at 0, as
   // init_controller leaves it
-  qmpc_ctx::Ctrl* k = c->ctrl;
+  qmpc_ctx::Ctrl* k = c->ctrl.get();
   k->started = true;
   const int counter0 = k->schedule == QMPC_CTRL_PER_ROBOT ? 0 : (int)(k->ticks % 13);
-  HIP_TRY(c, qmpc_launch_ctrl_init(&k->d, mask_dev, counter0, batch, stream));
+  HIP_TRY(c, qmpc_launch_ctrl_init(&k->d, mask_dev, counter0, batch, q.stream));
   return QMPC_OK;
 }
 
 int qmpc_ctrl_set_schedule(qmpc_handle c, int mode) {
   if (!c) return QMPC_ERR_ARG;
-  if (!c->ctrl || !c->ctrl->batch) return QMPC_ERR_STATE;
+  if (!ctrl_ready(c)) return QMPC_ERR_STATE;
   if (mode != QMPC_CTRL_LOCKSTEP && mode != QMPC_CTRL_PER_ROBOT) return QMPC_ERR_ARG;
   if (c->ctrl->started) return QMPC_ERR_STATE;
   if (mode == QMPC_CTRL_LOCKSTEP && c->ctrl->robot_mode == 1) {
@@ -1383,9 +1363,9 @@ int qmpc_ctrl_set_schedule(qmpc_handle c, int mode) {
 
 int qmpc_ctrl_set_robot_mode(qmpc_handle c, int mode) {
   if (!c) return QMPC_ERR_ARG;
-  if (!c->ctrl || !c->ctrl->batch) return QMPC_ERR_STATE;
+  if (!ctrl_ready(c)) return QMPC_ERR_STATE;
   if (mode != 0 && mode != 1) return QMPC_ERR_ARG;
-  qmpc_ctx::Ctrl* k = c->ctrl;
+  qmpc_ctx::Ctrl* k = c->ctrl.get();
   if (k->started) return QMPC_ERR_STATE;
   if (mode == 1 && k->schedule != QMPC_CTRL_PER_ROBOT) {
     // a robot's counter restarts whenever its gait is re-timed (ConvexMPCLocomotion.cpp:182-224): no common MPC tick
@@ -1402,67 +1382,41 @@ int qmpc_ctrl_set_robot_mode(qmpc_handle c, int mode) {
 int qmpc_ctrl_set_gait(qmpc_handle c, int batch, const int32_t* gait_dev, void* stream_) {
   if (const int rc = ctrl_check(c, batch)) return rc;
   if (!gait_dev) return QMPC_ERR_ARG;
-  DeviceGuard g(c->device);
-  hipStream_t stream = (hipStream_t)stream_;
-  if (const int rc = order_after_previous(c, stream)) return rc;
-  HIP_TRY(c, qmpc_launch_ctrl_set(&c->ctrl->d, gait_dev, nullptr, batch, stream));
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  HIP_TRY(c, qmpc_launch_ctrl_set(&c->ctrl->d, gait_dev, nullptr, batch, q.stream));
   return QMPC_OK;
 }
 
 int qmpc_ctrl_set_vel(qmpc_handle c, int batch, const double* vel_dev, void* stream_) {
   if (const int rc = ctrl_check(c, batch)) return rc;
   if (!vel_dev) return QMPC_ERR_ARG;
-  DeviceGuard g(c->device);
-  hipStream_t stream = (hipStream_t)stream_;
-  if (const int rc = order_after_previous(c, stream)) return rc;
-  HIP_TRY(c, qmpc_launch_ctrl_set(&c->ctrl->d, nullptr, vel_dev, batch, stream));
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  HIP_TRY(c, qmpc_launch_ctrl_set(&c->ctrl->d, nullptr, vel_dev, batch, q.stream));
   return QMPC_OK;
 }
 
-int qmpc_ctrl_prework(qmpc_handle c, int batch, const double* imu, const double* motor, void* stream_) {
-  if (const int rc = ctrl_check(c, batch)) return rc;
-  if (!imu || !motor) return QMPC_ERR_ARG;
-  DeviceGuard g(c->device);
-  hipStream_t stream = (hipStream_t)stream_;
-  if (const int rc = order_after_previous(c, stream)) return rc;
-  return ctrl_prework(c, imu, motor, stream);
+int qmpc_ctrl_prework(qmpc_handle c, int batch, const double* imu, const double* motor, void* stream) {
+  return ctrl_tick(c, batch, qmpc_launch_ctrl_est, imu, motor, nullptr, false, stream);
 }
 
-int qmpc_ctrl_tick(qmpc_handle c, int batch, const double* imu, const double* motor, double* effort, void* stream_) {
-  if (const int rc = ctrl_check(c, batch)) return rc;
-  if (!imu || !motor || !effort) return QMPC_ERR_ARG;
-  DeviceGuard g(c->device);
-  hipStream_t stream = (hipStream_t)stream_;
-  if (const int rc = order_after_previous(c, stream)) return rc;
-  c->ctrl->started = true;
-  if (const int rc = ctrl_prework(c, imu, motor, stream)) return rc;
-  return ctrl_after_prework(c, batch, effort, stream);
+int qmpc_ctrl_tick(qmpc_handle c, int batch, const double* imu, const double* motor, double* effort, void* stream) {
+  return ctrl_tick(c, batch, qmpc_launch_ctrl_est, imu, motor, effort, true, stream);
 }
 
-int qmpc_ctrl_prework_state(qmpc_handle c, int batch, const double* state, const double* motor, void* stream_) {
-  if (const int rc = ctrl_check(c, batch)) return rc;
-  if (!state || !motor) return QMPC_ERR_ARG;
-  DeviceGuard g(c->device);
-  hipStream_t stream = (hipStream_t)stream_;
-  if (const int rc = order_after_previous(c, stream)) return rc;
-  return ctrl_prework_state(c, state, motor, stream);
+int qmpc_ctrl_prework_state(qmpc_handle c, int batch, const double* state, const double* motor, void* stream) {
+  return ctrl_tick(c, batch, qmpc_launch_ctrl_est_state, state, motor, nullptr, false, stream);
 }
 
 int qmpc_ctrl_tick_state(qmpc_handle c, int batch, const double* state, const double* motor, double* effort,
-                         void* stream_) {
-  if (const int rc = ctrl_check(c, batch)) return rc;
-  if (!state || !motor || !effort) return QMPC_ERR_ARG;
-  DeviceGuard g(c->device);
-  hipStream_t stream = (hipStream_t)stream_;
-  if (const int rc = order_after_previous(c, stream)) return rc;
-  c->ctrl->started = true;
-  if (const int rc = ctrl_prework_state(c, state, motor, stream)) return rc;
-  return ctrl_after_prework(c, batch, effort, stream);
+                         void* stream) {
+  return ctrl_tick(c, batch, qmpc_launch_ctrl_est_state, state, motor, effort, true, stream);
 }
 
 int qmpc_debug_ctrl_read(qmpc_handle c, const char* name, void* dst, long long cap_bytes, int* per_robot) {
   if (!c || !name || !dst) return QMPC_ERR_ARG;
-  if (!c->ctrl || !c->ctrl->batch) return QMPC_ERR_STATE;
+  if (!ctrl_ready(c)) return QMPC_ERR_STATE;
   const QmpcCtrlDev& d = c->ctrl->d;
   struct Arr {
     const char* n;
@@ -1487,7 +1441,7 @@ int qmpc_debug_ctrl_read(qmpc_handle c, const char* name, void* dst, long long c
 
 int qmpc_ctrl_view_get(qmpc_handle c, qmpc_ctrl_view* v) {
   if (!c || !v) return QMPC_ERR_ARG;
-  if (!c->ctrl || !c->ctrl->batch) return QMPC_ERR_STATE;
+  if (!ctrl_ready(c)) return QMPC_ERR_STATE;
   const QmpcCtrlDev& d = c->ctrl->d;
   v->position = d.position;
   v->v_world = d.v_world;
@@ -1517,17 +1471,6 @@ int qmpc_ctrl_view_get(qmpc_handle c, qmpc_ctrl_view* v) {
 // Reduced-order plant (include/qmpc_plant.h).  The kernels are in qmpc_plant.hip.
 namespace {
 
-size_t plant_carve(QmpcPlantDev& d, char* base, int M) {
-  size_t off = 0;
-#define QMPC_PLANT_CARVE(T, name, per_robot)                    \
-  off = (off + 255) & ~(size_t)255;                            \
-  d.name = base ? reinterpret_cast<T*>(base + off) : nullptr;  \
-  off += sizeof(T) * (size_t)(per_robot) * (size_t)M;
-  QMPC_PLANT_ARRAYS(QMPC_PLANT_CARVE)
-#undef QMPC_PLANT_CARVE
-  return off;
-}
-
 // the constants of a launch, from the handle as it stands now
 QmpcPlantConst plant_const(const qmpc_ctx* c, double mu, int substeps) {
   QmpcPlantConst K{};
@@ -1546,7 +1489,7 @@ QmpcPlantConst plant_const(const qmpc_ctx* c, double mu, int substeps) {
 
 int plant_check(qmpc_ctx* c, int batch) {
   if (!c) return QMPC_ERR_ARG;
-  if (!c->ctrl || !c->ctrl->batch || !c->plant || !c->plant->batch) return QMPC_ERR_STATE;
+  if (!ctrl_ready(c) || !plant_ready(c)) return QMPC_ERR_STATE;
   if (batch != c->plant->batch || batch != c->ctrl->batch) return QMPC_ERR_ARG;
   return QMPC_OK;
 }
@@ -1557,17 +1500,13 @@ extern "C" {
 
 int qmpc_plant_init(qmpc_handle c, int batch, double mu_plant, int substeps, const double* init_xyyaw, void* stream_) {
   if (!c) return QMPC_ERR_ARG;
-  if (!c->ctrl || !c->ctrl->batch) return QMPC_ERR_STATE;
+  if (!ctrl_ready(c)) return QMPC_ERR_STATE;
   if (batch != c->ctrl->batch || substeps < 1 || !(mu_plant >= 0)) return QMPC_ERR_ARG;
   DeviceGuard g(c->device);
   hipStream_t stream = (hipStream_t)stream_;
-  if (!c->plant) c->plant = new qmpc_ctx::Plant();
-  qmpc_ctx::Plant* k = c->plant;
-  if (!k->buf) {
-    const size_t bytes = plant_carve(k->d, nullptr, c->max_batch);
-    HIP_TRY(c, hipMalloc(&k->buf, bytes));
-  }
-  plant_carve(k->d, static_cast<char*>(k->buf), c->max_batch);
+  if (!c->plant) c->plant.reset(new qmpc_ctx::Plant());
+  qmpc_ctx::Plant* k = c->plant.get();
+  HIP_TRY(c, carve_block(k->buf, k->d, c->max_batch));
   if (const int rc = order_after_previous(c, stream)) return rc;
   const QmpcPlantConst K = plant_const(c, mu_plant, substeps);
   HIP_TRY(c, qmpc_launch_plant_init(&k->d, &K, nullptr, init_xyyaw, batch, stream));
@@ -1583,11 +1522,10 @@ int qmpc_plant_init(qmpc_handle c, int batch, double mu_plant, int substeps, con
 int qmpc_plant_reset(qmpc_handle c, int batch, const uint8_t* mask_dev, const double* init_xyyaw, void* stream_) {
   if (const int rc = plant_check(c, batch)) return rc;
   if (!mask_dev) return QMPC_ERR_ARG;
-  DeviceGuard g(c->device);
-  hipStream_t stream = (hipStream_t)stream_;
-  if (const int rc = order_after_previous(c, stream)) return rc;
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
   const QmpcPlantConst K = plant_const(c, c->plant->mu, c->plant->substeps);
-  HIP_TRY(c, qmpc_launch_plant_init(&c->plant->d, &K, mask_dev, init_xyyaw, batch, stream));
+  HIP_TRY(c, qmpc_launch_plant_init(&c->plant->d, &K, mask_dev, init_xyyaw, batch, q.stream));
   return QMPC_OK;
 }
 
@@ -1595,22 +1533,21 @@ int qmpc_plant_step(qmpc_handle c, int batch, const double* effort, double* stat
                     void* stream_) {
   if (const int rc = plant_check(c, batch)) return rc;
   if (!effort || !state_out || !motor_out) return QMPC_ERR_ARG;
-  DeviceGuard g(c->device);
-  hipStream_t stream = (hipStream_t)stream_;
-  if (const int rc = order_after_previous(c, stream)) return rc;
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
   const QmpcCtrlDev& d = c->ctrl->d;
   const QmpcPlantConst K = plant_const(c, c->plant->mu, c->plant->substeps);
   // nothing bound and the statistics off: the plain instantiation, which is given no QmpcPlantVary to read
-  const qmpc_ctx::Plant* k = c->plant;
+  const qmpc_ctx::Plant* k = c->plant.get();
   const bool extra = k->bound || k->stats_on;
   HIP_TRY(c, qmpc_launch_plant_step(&k->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out, batch,
-                                    stream, extra ? &k->vary : nullptr, k->bound, k->stats_on));
+                                    q.stream, extra ? &k->vary : nullptr, k->bound, k->stats_on));
   return QMPC_OK;
 }
 
 int qmpc_plant_view_get(qmpc_handle c, qmpc_plant_view* v) {
   if (!c || !v) return QMPC_ERR_ARG;
-  if (!c->plant || !c->plant->batch) return QMPC_ERR_STATE;
+  if (!plant_ready(c)) return QMPC_ERR_STATE;
   const QmpcPlantDev& d = c->plant->d;
   v->p = d.p;
   v->v = d.v;
@@ -1631,7 +1568,7 @@ int qmpc_plant_view_get(qmpc_handle c, qmpc_plant_view* v) {
 
 int qmpc_plant_set_params(qmpc_handle c, int batch, const qmpc_plant_params* prm) {
   if (const int rc = plant_check(c, batch)) return rc;
-  qmpc_ctx::Plant* k = c->plant;
+  qmpc_ctx::Plant* k = c->plant.get();
   k->vary.mass = prm ? prm->mass : nullptr;
   k->vary.ibody = prm ? prm->ibody : nullptr;
   k->vary.mu = prm ? prm->mu : nullptr;
@@ -1643,8 +1580,8 @@ int qmpc_plant_set_params(qmpc_handle c, int batch, const qmpc_plant_params* prm
 
 int qmpc_plant_stats_enable(qmpc_handle c, int on) {
   if (!c) return QMPC_ERR_ARG;
-  if (!c->ctrl || !c->ctrl->batch || !c->plant || !c->plant->batch) return QMPC_ERR_STATE;
-  qmpc_ctx::Plant* k = c->plant;
+  if (!ctrl_ready(c) || !plant_ready(c)) return QMPC_ERR_STATE;
+  qmpc_ctx::Plant* k = c->plant.get();
   if (on && !k->stats_buf) {
     // acc[QMPC_PLANT_STATS][M] doubles, then n[M] ints; the initial values come from the host, which synchronises
     DeviceGuard g(c->device);
@@ -1656,15 +1593,12 @@ int qmpc_plant_stats_enable(qmpc_handle c, int on) {
       a[QMPC_PLANT_STAT_Z_MIN * M + b] = HUGE_VAL;
       a[QMPC_PLANT_STAT_Z_MAX * M + b] = -HUGE_VAL;
     }
-    void* buf = nullptr;
-    HIP_TRY(c, hipMalloc(&buf, bytes));
+    DevBuf<char> buf;  // (the handle's only once it holds the initial values)
+    HIP_TRY(c, buf.alloc(bytes));
     const hipError_t e = hipMemcpy(buf, init.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      hipFree(buf);
-      return fail(c, e, "hipMemcpy(plant statistics)");
-    }
-    k->stats_buf = buf;
-    k->vary.acc = static_cast<double*>(buf);
+    if (e != hipSuccess) return fail(c, e, "hipMemcpy(plant statistics)");
+    k->stats_buf = std::move(buf);
+    k->vary.acc = reinterpret_cast<double*>(k->stats_buf.p);
     k->vary.n = reinterpret_cast<int*>(k->vary.acc + QMPC_PLANT_STATS * M);
     k->vary.acc_stride = c->max_batch;
   }
@@ -1675,17 +1609,16 @@ int qmpc_plant_stats_enable(qmpc_handle c, int on) {
 int qmpc_plant_stats_reset(qmpc_handle c, int batch, const uint8_t* mask_dev, void* stream_) {
   if (const int rc = plant_check(c, batch)) return rc;
   if (!c->plant->stats_buf) return QMPC_ERR_STATE;
-  DeviceGuard g(c->device);
-  hipStream_t stream = (hipStream_t)stream_;
-  if (const int rc = order_after_previous(c, stream)) return rc;
-  HIP_TRY(c, qmpc_launch_plant_stats_reset(&c->plant->vary, mask_dev, batch, stream));
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  HIP_TRY(c, qmpc_launch_plant_stats_reset(&c->plant->vary, mask_dev, batch, q.stream));
   return QMPC_OK;
 }
 
 int qmpc_plant_stats_get(qmpc_handle c, qmpc_plant_stats* v) {
   if (!c || !v) return QMPC_ERR_ARG;
-  if (!c->plant || !c->plant->batch || !c->plant->stats_buf) return QMPC_ERR_STATE;
-  const qmpc_ctx::Plant* k = c->plant;
+  if (!plant_ready(c) || !c->plant->stats_buf) return QMPC_ERR_STATE;
+  const qmpc_ctx::Plant* k = c->plant.get();
   const size_t M = (size_t)k->vary.acc_stride;
   v->n = k->vary.n;
   v->z_min = k->vary.acc + QMPC_PLANT_STAT_Z_MIN * M;
@@ -1724,13 +1657,12 @@ int qmpc_sense_init(qmpc_handle c, int batch, uint64_t seed, void* stream_) {
   if (const int rc = plant_check(c, batch)) return rc;
   DeviceGuard g(c->device);
   hipStream_t stream = (hipStream_t)stream_;
-  if (!c->sense) c->sense = new qmpc_ctx::Sense();
-  qmpc_ctx::Sense* k = c->sense;
-  const size_t bytes = 2 * sizeof(int) * (size_t)c->max_batch;
-  if (!k->buf) HIP_TRY(c, hipMalloc(&k->buf, bytes));
+  if (!c->sense) c->sense.reset(new qmpc_ctx::Sense());
+  qmpc_ctx::Sense* k = c->sense.get();
+  if (!k->buf) HIP_TRY(c, k->buf.alloc(2 * (size_t)c->max_batch));  // n[max_batch], epoch[max_batch]
   if (const int rc = order_after_previous(c, stream)) return rc;
-  HIP_TRY(c, hipMemsetAsync(k->buf, 0, bytes, stream));
-  k->a.n = static_cast<int*>(k->buf);
+  HIP_TRY(c, fill_ints(k->buf, (int)k->buf.n, 0, stream));
+  k->a.n = k->buf;
   k->a.epoch = k->a.n + c->max_batch;
   k->a.key0 = (uint32_t)(seed & 0xFFFFFFFFu);
   k->a.key1 = (uint32_t)(seed >> 32);
@@ -1759,10 +1691,9 @@ int qmpc_sense_set_params(qmpc_handle c, int batch, const qmpc_sense_params* prm
 
 int qmpc_sense_reset(qmpc_handle c, int batch, const uint8_t* mask_dev, void* stream_) {
   if (const int rc = sense_check(c, batch)) return rc;
-  DeviceGuard g(c->device);
-  hipStream_t stream = (hipStream_t)stream_;
-  if (const int rc = order_after_previous(c, stream)) return rc;
-  HIP_TRY(c, qmpc_launch_sense_reset(&c->sense->a, mask_dev, batch, stream));
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  HIP_TRY(c, qmpc_launch_sense_reset(&c->sense->a, mask_dev, batch, q.stream));
   return QMPC_OK;
 }
 
@@ -1772,19 +1703,18 @@ int qmpc_sense(qmpc_handle c, int batch, double* imu_out, double* motor_out, voi
   if (!imu_out || !motor_out) return QMPC_ERR_ARG;
   // the kernel reads the plant's rows while it writes the outputs
   if (imu_out == p.state || imu_out == p.motor || motor_out == p.state || motor_out == p.motor) return QMPC_ERR_ARG;
-  DeviceGuard g(c->device);
-  hipStream_t stream = (hipStream_t)stream_;
-  if (const int rc = order_after_previous(c, stream)) return rc;
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
   QmpcSenseArgs a = c->sense->a;
   a.state = p.state;
   a.motor = p.motor;
-  HIP_TRY(c, qmpc_launch_sense(&a, imu_out, motor_out, batch, c->sense->bound, stream));
+  HIP_TRY(c, qmpc_launch_sense(&a, imu_out, motor_out, batch, c->sense->bound, q.stream));
   return QMPC_OK;
 }
 
 int qmpc_sense_view_get(qmpc_handle c, qmpc_sense_view* v) {
   if (!c || !v) return QMPC_ERR_ARG;
-  if (!c->plant || !c->plant->batch || !c->sense || !c->sense->batch) return QMPC_ERR_STATE;
+  if (!plant_ready(c) || !c->sense || !c->sense->batch) return QMPC_ERR_STATE;
   v->n = c->sense->a.n;
   v->epoch = c->sense->a.epoch;
   v->batch = c->sense->batch;

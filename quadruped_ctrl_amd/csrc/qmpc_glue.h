@@ -11,6 +11,9 @@
 #define QMPC_GLUE_H
 
 #include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/qmpc.h"  // qmpc_leg_command, qmpc_kf_state
 
 struct QmpcLegGeom {
   float abad, hip, knee, knee_y;  // _abadLinkLength, _hipLinkLength, _kneeLinkLength, _kneeLinkY_offset
@@ -270,5 +273,29 @@ __device__ __forceinline__ void qmpc_ctrl_gait_state(float phase, int off, int d
   if (pr > sd) swing = 0.f;
   else swing = ((double)sd < 0.0000000001) ? 0.f : pr / sd;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Launchers of qmpc_glue.hip, declared once: qmpc_glue.hip (which defines them) and qmpc_capi.cpp (which calls them)
+// both read these lines, so a signature that drifts fails to compile.
+extern "C" hipError_t qmpc_launch_leg_kin(const float geom[4], const float* q, const float* qd, float* J, float* p,
+                                          float* v, int batch, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_leg_cmd(const float geom[4], const qmpc_leg_command* c, float* tau, float* q_des,
+                                          int batch, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_swing(const float* p0, const float* pf, const float* height, const float* phase,
+                                        const float* swing_time, float* p, float* v, float* a, int n_feet,
+                                        hipStream_t stream);
+extern "C" hipError_t qmpc_launch_kf(const qmpc_kf_state* st, const float hip[3], int batch, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_kf_init(float* xhat, float* P, int batch, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_ctrl_init(const QmpcCtrlDev* S, const uint8_t* mask, int counter0, int batch,
+                                            hipStream_t stream);
+extern "C" hipError_t qmpc_launch_ctrl_set(const QmpcCtrlDev* S, const int32_t* gait, const double* vel, int batch,
+                                           hipStream_t stream);
+extern "C" hipError_t qmpc_launch_ctrl_est(const QmpcCtrlDev* S, const float geom[4], const double* imu,
+                                           const double* motor, int batch, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_ctrl_est_state(const QmpcCtrlDev* S, const float geom[4], const double* state,
+                                                 const double* motor, int batch, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_ctrl_loco(const QmpcCtrlDev* S, int batch, int build_list, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_ctrl_loco_aio(const QmpcCtrlDev* S, int batch, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_ctrl_legcmd(const QmpcCtrlDev* S, double* effort, int batch, hipStream_t stream);
 
 #endif

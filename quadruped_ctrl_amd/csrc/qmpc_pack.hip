@@ -19,6 +19,7 @@
 #include "../../include/qmpc.h"
 
 #include "qmpc_cmd.h"
+#include "qmpc_launch.h"
 
 namespace {
 

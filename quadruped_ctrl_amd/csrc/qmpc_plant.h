@@ -60,4 +60,15 @@ enum {
 #define QMPC_PLANT_KNEE_MIN 0.05    /* the swing clamp's shell, as knee angles */
 #define QMPC_PLANT_KNEE_MAX 2.6
 
+// Launchers of qmpc_plant.hip, declared once for the file that defines them and for qmpc_capi.cpp, which calls them: a
+// signature that drifts fails to compile.
+extern "C" hipError_t qmpc_launch_plant_init(const QmpcPlantDev* S, const QmpcPlantConst* K, const uint8_t* mask,
+                                             const double* xyyaw, int batch, hipStream_t stream);
+extern "C" hipError_t qmpc_launch_plant_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
+                                             const float* contact_state, const float* p_des, const float* v_des,
+                                             double* state_out, double* motor_out, int batch, hipStream_t stream,
+                                             const QmpcPlantVary* V, int vary, int stats);
+extern "C" hipError_t qmpc_launch_plant_stats_reset(const QmpcPlantVary* V, const uint8_t* mask, int batch,
+                                                    hipStream_t stream);
+
 #endif

@@ -24,4 +24,11 @@ struct QmpcSenseArgs {
 // channel numbers of a robot (the third counter word of the generator)
 enum { QMPC_SENSE_CH_ACC = 0, QMPC_SENSE_CH_GYRO = 3, QMPC_SENSE_CH_Q = 6, QMPC_SENSE_CH_QD = 18 };
 
+// Launchers of qmpc_sense.hip, declared once for the file that defines them and for qmpc_capi.cpp, which calls them: a
+// signature that drifts fails to compile.
+extern "C" hipError_t qmpc_launch_sense(const QmpcSenseArgs* A, double* imu_out, double* motor_out, int batch, int noisy,
+                                        hipStream_t stream);
+extern "C" hipError_t qmpc_launch_sense_reset(const QmpcSenseArgs* A, const uint8_t* mask, int batch,
+                                              hipStream_t stream);
+
 #endif
