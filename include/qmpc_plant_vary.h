@@ -18,8 +18,8 @@
  * The read-out is unchanged, so the accelerometer rows feel the push; the grf view stays the ground's reactions only.
  *
  * Still out of scope: per-robot constants in the MPC (the solve keeps one mass, inertia, mu and f_max per handle);
- * centre-of-mass offsets, slip, terrain, contact detection (the plant stays "not a physics engine").  (The sensor path
- * closed loop -- plant -> imu -> qmpc_ctrl_tick's estimators -- is qmpc_sense.h.)
+ * centre-of-mass offsets, slip, contact detection (the plant stays "not a physics engine").  (The sensor path closed
+ * loop -- plant -> imu -> qmpc_ctrl_tick's estimators -- is qmpc_sense.h; per-robot slopes and stairs are qmpc_terrain.h.)
  *
  * Errors as in qmpc_plant.h: QMPC_ERR_STATE before qmpc_plant_init (and, for the statistics' reset and get, before the
  * first enable); QMPC_ERR_ARG for a batch other than the plant's or a null view.

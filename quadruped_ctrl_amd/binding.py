@@ -96,6 +96,15 @@ class PlantParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in PLANT_PARAM_FIELDS]
 
 
+class TerrainView(C.Structure):
+    """qmpc_terrain_view (include/qmpc_terrain.h)."""
+    _fields_ = [("ground", C.c_void_p), ("support", C.c_void_p), ("terrain", C.c_void_p), ("flags", C.c_int),
+                ("batch", C.c_int)]
+
+
+TERRAIN_CLAMP_SWING, TERRAIN_REBASE_Z = 1, 2
+
+
 class PlantStats(C.Structure):
     """qmpc_plant_stats (include/qmpc_plant_vary.h)."""
     _fields_ = [(n, C.c_void_p) for n in PLANT_STATS_FIELDS] + [("batch", C.c_int), ("enabled", C.c_int)]
@@ -228,6 +237,11 @@ PLANT_VARY_SIGNATURES = {
     "qmpc_plant_stats_reset": [_P, _I, _P, _P],
     "qmpc_plant_stats_get": [_P, C.POINTER(PlantStats)],
 }
+# per-robot slopes and stairs under the plant (include/qmpc_terrain.h), same library and ABI version
+TERRAIN_SIGNATURES = {
+    "qmpc_plant_set_terrain": [_P, _I, _P, _I],
+    "qmpc_terrain_view_get": [_P, C.POINTER(TerrainView)],
+}
 # the sensor model between the plant and the controller's sensor path (include/qmpc_sense.h), same library and ABI version
 SENSE_SIGNATURES = {
     "qmpc_sense_init": [_P, _I, C.c_uint64, _P],
@@ -241,6 +255,7 @@ CTRL_EXPORTS = list(CTRL_SIGNATURES)
 PLANT_EXPORTS = list(PLANT_SIGNATURES)
 PLANT_VARY_EXPORTS = list(PLANT_VARY_SIGNATURES)
 SENSE_EXPORTS = list(SENSE_SIGNATURES)
+TERRAIN_EXPORTS = list(TERRAIN_SIGNATURES)
 
 _lib = None
 
@@ -274,7 +289,7 @@ def load_library():
                 f"{LIB_PATH} not found: build the HIP extension first "
                 "(python -c 'import __graft_entry__ as g; g.build()')")
         lib = C.CDLL(LIB_PATH)
-        for name, sig in {**SIGNATURES, **CTRL_SIGNATURES, **PLANT_SIGNATURES, **PLANT_VARY_SIGNATURES,
+        for name, sig in {**SIGNATURES, **CTRL_SIGNATURES, **PLANT_SIGNATURES, **PLANT_VARY_SIGNATURES, **TERRAIN_SIGNATURES,
                           **SENSE_SIGNATURES}.items():
             f = getattr(lib, name)
             f.argtypes, f.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
@@ -844,6 +859,7 @@ class BatchedPlant:
         self.ctrl, self.torch, self.lib, self.device = ctrl, ctrl.torch, ctrl.lib, ctrl.device
         self.batch = None
         self._params = {}
+        self._terrain = None
 
     def _xyyaw(self, xyyaw):
         if xyyaw is None:
@@ -858,6 +874,7 @@ class BatchedPlant:
         self.batch = self.ctrl.batch
         self._keep = init_xyyaw
         self._params = {}     # (qmpc_plant_init unbinds: a new plant is the plain plant)
+        self._terrain = None  # (... on flat ground)
         v = self.view()
         self.state, self.motor = v["state"], v["motor"]
         self.effort = self.torch.zeros((self.batch, 12), dtype=self.torch.float64, device=self.device)
@@ -913,6 +930,32 @@ class BatchedPlant:
         res = self.ctrl._views("qmpc_plant_stats_get", PlantStats, {k: (None, ts) for k, ts in PLANT_STATS_FIELDS.items()},
                                ("batch", "enabled"))
         res["enabled"] = bool(res["enabled"])
+        return res
+
+
+    # -- include/qmpc_terrain.h ----------------------------------------------------------------------------------------
+    def set_terrain(self, rows, clamp_swing=False, rebase_z=False):
+        """Per-robot slopes and stairs under the PLANT (the controller is not told): rows is a float64 device tensor
+        [B, 8] of (z0, gx, gy, rise, run, count, s0, psi) -- height(x, y) = z0 + gx x + gy y + rise k with k the tread
+        index along heading psi from abscissa s0 -- or None to unbind (flat ground).  The plant reads the tensor at every
+        later step and reset -- write into it in place (on the stream) to change the ground, also between replays of a
+        captured graph; it is kept referenced here.  clamp_swing lifts a swing foot commanded below the surface onto
+        it; rebase_z makes column 6 of the state row the height above the stance feet.  init() unbinds, reset() does
+        not and places the robots on the terrain: init() -> set_terrain() -> reset(all)."""
+        if self.batch is None:
+            raise QmpcError("qmpc_plant_set_terrain before init()")
+        ptr = None if rows is None else self.ctrl._chk(rows, (self.batch, 8), self.torch.float64, "rows")
+        flags = (TERRAIN_CLAMP_SWING if clamp_swing else 0) | (TERRAIN_REBASE_Z if rebase_z else 0)
+        self.ctrl._call("qmpc_plant_set_terrain", self.batch, ptr, flags)
+        self._terrain = rows
+
+    def terrain(self):
+        """qmpc_terrain_view_get as zero-copy device tensors [B] that alias the plant's arrays, like view(): ground (the
+        height under the body origin at the last pose on terrain), support (the mean height of the stance feet); plus
+        flags, batch and bound.  Read-only by contract."""
+        res = self.ctrl._views("qmpc_terrain_view_get", TerrainView, dict(ground=(None, "<f8"), support=(None, "<f8")),
+                               ("terrain", "flags", "batch"))
+        res["bound"] = bool(res.pop("terrain"))
         return res
 
 

@@ -22,6 +22,7 @@
 #include "../../include/qmpc_ctrl.h"    // batched locomotion controller (same library)
 #include "../../include/qmpc_plant.h"   // reduced-order plant for it (same library)
 #include "../../include/qmpc_plant_vary.h"  // ... its per-robot parameters and on-device statistics
+#include "../../include/qmpc_terrain.h"  // ... its per-robot slopes and stairs
 #include "../../include/qmpc_sense.h"   // sensor model between the plant and the controller's sensor path
 #include "qmpc_device.h"
 #include "qmpc_glue.h"    // each launcher is declared once, in the header its defining file includes too:
@@ -217,6 +218,9 @@ struct __attribute__((visibility("hidden"))) qmpc_ctx {
     bool bound = false;
     DevBuf<char> stats_buf;
     bool stats_on = false;
+    // qmpc_terrain.h: the caller's rows as bound (null: flat ground) and the flags; ground[max_batch], support[max_batch]
+    QmpcTerrainArgs terrain{};
+    DevBuf<double> terrain_buf;
   };
   std::unique_ptr<Plant> plant;
   // sensor model (qmpc_sense.h): the counters n[max_batch], epoch[max_batch] in one allocation made by qmpc_sense_init,
@@ -1507,6 +1511,16 @@ int qmpc_plant_init(qmpc_handle c, int batch, double mu_plant, int substeps, con
   if (!c->plant) c->plant.reset(new qmpc_ctx::Plant());
   qmpc_ctx::Plant* k = c->plant.get();
   HIP_TRY(c, carve_block(k->buf, k->d, c->max_batch));
+  if (!k->terrain_buf) {
+    // ground[M], support[M] of qmpc_terrain.h, zero until a reset on terrain writes them (first use only)
+    DevBuf<double> buf;
+    HIP_TRY(c, buf.alloc(2 * (size_t)c->max_batch));
+    const hipError_t e = hipMemset(buf, 0, 2 * sizeof(double) * (size_t)c->max_batch);
+    if (e != hipSuccess) return fail(c, e, "hipMemset(plant terrain)");
+    k->terrain_buf = std::move(buf);
+    k->terrain.ground = k->terrain_buf.p;
+    k->terrain.support = k->terrain_buf.p + c->max_batch;
+  }
   if (const int rc = order_after_previous(c, stream)) return rc;
   const QmpcPlantConst K = plant_const(c, mu_plant, substeps);
   HIP_TRY(c, qmpc_launch_plant_init(&k->d, &K, nullptr, init_xyyaw, batch, stream));
@@ -1516,6 +1530,8 @@ int qmpc_plant_init(qmpc_handle c, int batch, double mu_plant, int substeps, con
   // a new plant is the plain plant: nothing bound (the statistics keep their switch and their values)
   k->vary.mass = k->vary.ibody = k->vary.mu = k->vary.force = k->vary.torque = nullptr;
   k->bound = false;
+  k->terrain.rows = nullptr;  // ... and stands on flat ground
+  k->terrain.flags = 0;
   return QMPC_OK;
 }
 
@@ -1525,7 +1541,11 @@ int qmpc_plant_reset(qmpc_handle c, int batch, const uint8_t* mask_dev, const do
   const Enqueue q(c, stream_);
   if (q.rc) return q.rc;
   const QmpcPlantConst K = plant_const(c, c->plant->mu, c->plant->substeps);
-  HIP_TRY(c, qmpc_launch_plant_init(&c->plant->d, &K, mask_dev, init_xyyaw, batch, q.stream));
+  const qmpc_ctx::Plant* k = c->plant.get();
+  if (k->terrain.rows)
+    HIP_TRY(c, qmpc_launch_terrain_init(&k->d, &K, mask_dev, init_xyyaw, batch, q.stream, &k->terrain));
+  else
+    HIP_TRY(c, qmpc_launch_plant_init(&k->d, &K, mask_dev, init_xyyaw, batch, q.stream));
   return QMPC_OK;
 }
 
@@ -1540,8 +1560,12 @@ int qmpc_plant_step(qmpc_handle c, int batch, const double* effort, double* stat
   // nothing bound and the statistics off: the plain instantiation, which is given no QmpcPlantVary to read
   const qmpc_ctx::Plant* k = c->plant.get();
   const bool extra = k->bound || k->stats_on;
-  HIP_TRY(c, qmpc_launch_plant_step(&k->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out, batch,
-                                    q.stream, extra ? &k->vary : nullptr, k->bound, k->stats_on));
+  if (k->terrain.rows)
+    HIP_TRY(c, qmpc_launch_terrain_step(&k->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out,
+                                        batch, q.stream, extra ? &k->vary : nullptr, k->bound, k->stats_on, &k->terrain));
+  else
+    HIP_TRY(c, qmpc_launch_plant_step(&k->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out, batch,
+                                      q.stream, extra ? &k->vary : nullptr, k->bound, k->stats_on));
   return QMPC_OK;
 }
 
@@ -1629,6 +1653,29 @@ int qmpc_plant_stats_get(qmpc_handle c, qmpc_plant_stats* v) {
   v->vy_sum = k->vary.acc + QMPC_PLANT_STAT_VY_SUM * M;
   v->batch = k->batch;
   v->enabled = k->stats_on ? 1 : 0;
+  return QMPC_OK;
+}
+
+// ---- include/qmpc_terrain.h: per-robot slopes and stairs under the plant ----
+
+int qmpc_plant_set_terrain(qmpc_handle c, int batch, const double* terrain_dev, int flags) {
+  if (const int rc = plant_check(c, batch)) return rc;
+  if (flags & ~(QMPC_TERRAIN_CLAMP_SWING | QMPC_TERRAIN_REBASE_Z)) return QMPC_ERR_ARG;
+  qmpc_ctx::Plant* k = c->plant.get();
+  k->terrain.rows = terrain_dev;
+  k->terrain.flags = terrain_dev ? flags : 0;
+  return QMPC_OK;
+}
+
+int qmpc_terrain_view_get(qmpc_handle c, qmpc_terrain_view* v) {
+  if (!c || !v) return QMPC_ERR_ARG;
+  if (!plant_ready(c)) return QMPC_ERR_STATE;
+  const qmpc_ctx::Plant* k = c->plant.get();
+  v->ground = k->terrain.ground;
+  v->support = k->terrain.support;
+  v->terrain = k->terrain.rows;
+  v->flags = k->terrain.flags;
+  v->batch = k->batch;
   return QMPC_OK;
 }
 

@@ -53,6 +53,15 @@ enum {
   QMPC_PLANT_STAT_VX_SUM, QMPC_PLANT_STAT_VY_SUM, QMPC_PLANT_STATS
 };
 
+// include/qmpc_terrain.h: the caller's terrain rows as bound (null: flat ground, the kernels of qmpc_plant.hip), the
+// plant's ground[max_batch] and support[max_batch] (one allocation made by qmpc_plant_init) and the flags.  By value.
+struct QmpcTerrainArgs {
+  const double* rows;  // [B][8] z0, gx, gy, rise, run, count, s0, psi
+  double* ground;      // [B] height under the body origin at the last pose
+  double* support;     // [B] mean height of the stance feet (kept through a flight phase)
+  int flags;           // QMPC_TERRAIN_*
+};
+
 #define QMPC_PLANT_GRAVITY 9.81
 #define QMPC_PLANT_HEIGHT 0.29      /* ConvexMPCLocomotion::_body_height */
 #define QMPC_PLANT_SIDE_OFFSET 0.065
@@ -70,5 +79,14 @@ extern "C" hipError_t qmpc_launch_plant_step(const QmpcPlantDev* S, const QmpcPl
                                              const QmpcPlantVary* V, int vary, int stats);
 extern "C" hipError_t qmpc_launch_plant_stats_reset(const QmpcPlantVary* V, const uint8_t* mask, int batch,
                                                     hipStream_t stream);
+// ... and of qmpc_terrain.hip, which capi picks while terrain rows are bound (T->rows is not null): the same arguments
+// with the terrain's after them.
+extern "C" hipError_t qmpc_launch_terrain_init(const QmpcPlantDev* S, const QmpcPlantConst* K, const uint8_t* mask,
+                                               const double* xyyaw, int batch, hipStream_t stream,
+                                               const QmpcTerrainArgs* T);
+extern "C" hipError_t qmpc_launch_terrain_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
+                                               const float* contact_state, const float* p_des, const float* v_des,
+                                               double* state_out, double* motor_out, int batch, hipStream_t stream,
+                                               const QmpcPlantVary* V, int vary, int stats, const QmpcTerrainArgs* T);
 
 #endif

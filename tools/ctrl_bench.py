@@ -26,6 +26,11 @@ x commands over [0, 0.5] m/s and small yaw rates (the family tests/plant_loop.py
 first steps (--warmup 260).  The tick and the plant step are timed separately (us_per_plant_step_median).  --vary binds
 the per-robot body, floor and push of include/qmpc_plant_vary.h (the set the closed-loop tests walk on: payloads, floors, and a
 30 N lateral push during ticks 300 .. 349 of the run, written into the bound array between two ticks) and turns the plant's statistics on: the step then runs its <VARY, STATS> instantiation.
+--terrain binds the per-robot ground of include/qmpc_terrain.h (the set the closed-loop tests walk on, by robot index mod 4:
+four treads of 0.1 m x 0.04 m up, a cross slope of 0.15, the same treads down, 0.15 uphill; flights start 0.10 m ahead of
+each robot along its start yaw), with swing feet clamped to the surface and, for --source plant, the state row's height
+re-based on the stance feet; the robots are reset onto their ground first.  The step then runs the terrain kernels of
+csrc/qmpc_terrain.hip (with --vary: their <VARY, STATS> instantiation).
 
 --source sensor closes the same loop through the SENSOR path: qmpc_ctrl_tick -- the VectorNav orientation estimator and
 the Kalman filter -- on the readings of the sensor model (include/qmpc_sense.h), qmpc_plant_step on the tick's efforts,
@@ -36,7 +41,8 @@ accelerometer and gyro biases (within +-0.2 m/s^2, +-0.02 rad/s) and white noise
 0.002 rad and 0.05 rad/s: the levels the closed-loop tests walk on); without it the sensors are ideal.
 
     python tools/ctrl_bench.py [--batches 1024,4096,16384] [--cycles 8] [--warmup 26] [--schedule lockstep|per_robot]
-                               [--stagger] [--robot-mode 0|1] [--source imu|state|plant|sensor] [--vary] [--noise] [--out FILE]
+                               [--stagger] [--robot-mode 0|1] [--source imu|state|plant|sensor] [--vary] [--terrain] [--noise]
+                               [--out FILE]
 """
 import argparse
 import json
@@ -49,7 +55,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, source="imu", vary=False, noise=False):
+def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, source="imu", vary=False, noise=False, terrain=False):
     import torch
     from quadruped_ctrl_amd import workloads as W
     from quadruped_ctrl_amd.binding import BatchedController
@@ -95,6 +101,18 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
             plant.set_params(mass=dev(9.0 * scale), ibody=dev(np.array([0.07, 0.26, 0.242])[None, :] * scale[:, None]),
                              mu=dev(np.array([0.3, 0.4, 0.6, 0.8])[k % 4]), force=force, torque=dev(np.zeros((B, 3))))
             plant.enable_stats()
+        if terrain:   # tests/plant_loop_terrain.py: terrain(), restated (the tools do not import the test tree)
+            kind, psi = np.arange(B) % 4, xyyaw[:, 2]
+            rows = np.zeros((B, 8))
+            stairs = (kind == 0) | (kind == 2)
+            rows[stairs, 3] = np.where(kind == 0, 0.04, -0.04)[stairs]
+            rows[stairs, 4], rows[stairs, 5] = 0.1, 4.0
+            rows[stairs, 6] = ((xyyaw[:, 0] * np.cos(psi) + xyyaw[:, 1] * np.sin(psi)) + 0.10)[stairs]
+            rows[stairs, 7] = psi[stairs]
+            rows[kind == 1, 2], rows[kind == 3, 1] = 0.15, 0.15
+            rows = torch.from_numpy(rows).cuda()
+            plant.set_terrain(rows, clamp_swing=True, rebase_z=source == "plant")
+            plant.reset(torch.ones(B, dtype=torch.bool, device="cuda"), torch.from_numpy(xyyaw).cuda())
         imu, motor = plant.state.expand(26, B, 16), plant.motor.expand(26, B, 24)    # (every "slot" is the plant's read-out)
         tick = ctrl.tick_state
         if source == "sensor":
@@ -159,6 +177,10 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
     if vary:
         res["vary"] = True
         res["stats_steps"] = int(plant.stats()["n"].min().item())
+    if terrain:
+        t_ = plant.terrain()
+        res.update({"terrain": True, "support_min": round(float(t_["support"].min().item()), 4),
+                    "support_max": round(float(t_["support"].max().item()), 4)})
     if stagger or robot_mode == 1:
         res["robot_ticks_per_s"] = res["robot_ticks_per_s_window"]
         if robot_mode == 1:
@@ -190,11 +212,14 @@ def main():
     ap.add_argument("--robot-mode", type=int, choices=(0, 1), default=0)
     ap.add_argument("--source", choices=("imu", "state", "plant", "sensor"), default="imu")
     ap.add_argument("--vary", action="store_true")
+    ap.add_argument("--terrain", action="store_true")
     ap.add_argument("--noise", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.vary and a.source not in ("plant", "sensor"):
         ap.error("--vary needs --source plant or sensor")
+    if a.terrain and a.source not in ("plant", "sensor"):
+        ap.error("--terrain needs --source plant or sensor")
     if a.noise and a.source != "sensor":
         ap.error("--noise needs --source sensor")
     if a.robot_mode == 1:
@@ -203,7 +228,7 @@ def main():
         ap.error("--stagger needs --schedule per_robot (a lockstep reset keeps the robot on the batch's MPC ticks)")
     out = []
     for B in [int(x) for x in a.batches.split(",")]:
-        r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source, a.vary, a.noise)
+        r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source, a.vary, a.noise, a.terrain)
         print(json.dumps(r), flush=True)
         out.append(r)
     if a.out:
