@@ -328,6 +328,185 @@ __device__ __forceinline__ QmpcKeys qmpc_robot_keys_wave(const QmpcParams& P, co
   }
   return {nst, score, demand, pattern};
 }
+// ---- the kernel arguments the head of the first-class kernel and stage 0 read (the 64-row classes) ----
+// Left to itself the compiler fetches every pointer and stride from the kernarg segment just in time, inside the conditional
+// block that uses it: a scalar load, a wait, then the block's vector loads -- a dozen scalar round trips one behind the other on
+// a cold scalar cache (eight different 64-byte lines), in front of the stage's last vector load.  The first-class kernel of the
+// 64-row classes therefore fetches them all in ONE batch of wide scalar loads behind ONE wait (qmpc_kernarg_batch) and hands
+// them down in this struct; every other kernel reads them in place, as ever.
+struct QmpcStage0Args {
+  const float *p, *v, *q, *w, *r, *yaw, *traj;
+  const uint8_t* gait;
+  const float *weights, *alpha, *x_drag;
+  int weights_stride, alpha_stride, x_drag_stride, horizon;
+  const double* ctab;
+  long long* dbg_clk;
+  const int32_t* hint_iters;
+  int hint_hard;
+  const int32_t* hint_max_r;
+  unsigned long long* prio_cu;
+  unsigned prio_tag;
+};
+// ... and what the kernel head itself reads
+struct QmpcHeadArgs {
+  int* clear_counts;
+  int32_t* hint_max_z;
+  unsigned long long* so_order;
+  int so_first, so_nseg;
+};
+typedef uint32_t qmpc_u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t qmpc_u32x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t qmpc_u32x16 __attribute__((ext_vector_type(16)));
+typedef int32_t qmpc_i32x16 __attribute__((ext_vector_type(16)));
+#define QMPC_AS4 __attribute__((address_space(4)))
+template <class T, class V>
+__device__ __forceinline__ T* qmpc_ka_ptr(const V& blk, const size_t off, const size_t field) {
+  // (a GLOBAL pointer, as the compiler takes a pointer kernel argument to be: rebuilt from integers it would be a generic one, and
+  //  every access through it a flat one)
+  const unsigned k = (unsigned)((field - off) / 4);
+  return (T*)reinterpret_cast<T __attribute__((address_space(1)))*>((unsigned long long)blk[k] | ((unsigned long long)blk[k + 1] << 32));
+}
+// The batch: the blocks of the parameter block that hold those fields (the layout is checked below), loaded back to back and
+// made opaque TOGETHER, so that everything downstream depends on them through this one point: one s_waitcnt for the lot, and
+// the compiler cannot sink a load back into the block that uses it.  `kb`: the kernarg segment (the parameter block is the only
+// explicit kernel argument: offset 0).
+__device__ __forceinline__ void qmpc_kernarg_batch(const QMPC_AS4 unsigned char* kb, QmpcStage0Args& A, QmpcHeadArgs& H) {
+#define QMPC_KA_IN(f, lo, hi) static_assert(offsetof(QmpcParams, f) >= (lo) && offsetof(QmpcParams, f) + sizeof(QmpcParams::f) <= (hi), "kernarg batch: " #f)
+  constexpr size_t O0 = 0x00, O1 = 0x40, O3 = 0x300, O4 = 0x340;
+  QMPC_KA_IN(p, O0, O0 + 64); QMPC_KA_IN(v, O0, O0 + 64); QMPC_KA_IN(q, O0, O0 + 64); QMPC_KA_IN(w, O0, O0 + 64);
+  QMPC_KA_IN(r, O0, O0 + 64); QMPC_KA_IN(yaw, O0, O0 + 64); QMPC_KA_IN(traj, O0, O0 + 64); QMPC_KA_IN(gait, O0, O0 + 64);
+  QMPC_KA_IN(weights, O1, O1 + 32); QMPC_KA_IN(alpha, O1, O1 + 32); QMPC_KA_IN(x_drag, O1, O1 + 32);
+  QMPC_KA_IN(weights_stride, O1, O1 + 32); QMPC_KA_IN(alpha_stride, O1, O1 + 32);
+  QMPC_KA_IN(hint_iters, O3, O3 + 64); QMPC_KA_IN(hint_hard, O3, O3 + 64); QMPC_KA_IN(hint_max_r, O3, O3 + 64);
+  QMPC_KA_IN(hint_max_z, O3, O3 + 64); QMPC_KA_IN(prio_cu, O3, O3 + 64); QMPC_KA_IN(prio_tag, O3, O3 + 64);
+  QMPC_KA_IN(so_order, O4, O4 + 32); QMPC_KA_IN(so_first, O4, O4 + 32);
+#undef QMPC_KA_IN
+  qmpc_u32x16 b0 = *reinterpret_cast<const QMPC_AS4 qmpc_u32x16*>(kb + O0);
+  qmpc_u32x8 b1 = *reinterpret_cast<const QMPC_AS4 qmpc_u32x8*>(kb + O1);
+  qmpc_u32x16 b3 = *reinterpret_cast<const QMPC_AS4 qmpc_u32x16*>(kb + O3);
+  qmpc_u32x8 b4 = *reinterpret_cast<const QMPC_AS4 qmpc_u32x8*>(kb + O4);
+  uint32_t xds = *reinterpret_cast<const QMPC_AS4 uint32_t*>(kb + offsetof(QmpcParams, x_drag_stride));
+  uint32_t hz = *reinterpret_cast<const QMPC_AS4 uint32_t*>(kb + offsetof(QmpcParams, horizon));
+  uint32_t nsg = *reinterpret_cast<const QMPC_AS4 uint32_t*>(kb + offsetof(QmpcParams, so_nseg));
+  qmpc_u32x2 ct = *reinterpret_cast<const QMPC_AS4 qmpc_u32x2*>(kb + offsetof(QmpcParams, ctab));
+  qmpc_u32x2 cc = *reinterpret_cast<const QMPC_AS4 qmpc_u32x2*>(kb + offsetof(QmpcParams, clear_counts));
+  qmpc_u32x2 dc = *reinterpret_cast<const QMPC_AS4 qmpc_u32x2*>(kb + offsetof(QmpcParams, dbg_clk));
+  asm volatile("; qmpc kernarg batch back"
+               : "+s"(b0), "+s"(b1), "+s"(b3), "+s"(b4), "+s"(xds), "+s"(hz), "+s"(nsg), "+s"(ct), "+s"(cc), "+s"(dc));
+#define QMPC_KA(T, blk, off, f) qmpc_ka_ptr<T>(blk, off, offsetof(QmpcParams, f))
+#define QMPC_KA_I(blk, off, f) blk[(offsetof(QmpcParams, f) - (off)) / 4]
+  A.p = QMPC_KA(const float, b0, O0, p); A.v = QMPC_KA(const float, b0, O0, v); A.q = QMPC_KA(const float, b0, O0, q);
+  A.w = QMPC_KA(const float, b0, O0, w); A.r = QMPC_KA(const float, b0, O0, r); A.yaw = QMPC_KA(const float, b0, O0, yaw);
+  A.traj = QMPC_KA(const float, b0, O0, traj); A.gait = QMPC_KA(const uint8_t, b0, O0, gait);
+  A.weights = QMPC_KA(const float, b1, O1, weights); A.alpha = QMPC_KA(const float, b1, O1, alpha);
+  A.x_drag = QMPC_KA(const float, b1, O1, x_drag);
+  A.weights_stride = (int)QMPC_KA_I(b1, O1, weights_stride); A.alpha_stride = (int)QMPC_KA_I(b1, O1, alpha_stride);
+  A.x_drag_stride = (int)xds; A.horizon = (int)hz;
+  A.ctab = qmpc_ka_ptr<const double>(ct, 0, 0); A.dbg_clk = qmpc_ka_ptr<long long>(dc, 0, 0);
+  A.hint_iters = QMPC_KA(const int32_t, b3, O3, hint_iters); A.hint_hard = (int)QMPC_KA_I(b3, O3, hint_hard);
+  A.hint_max_r = QMPC_KA(const int32_t, b3, O3, hint_max_r);
+  A.prio_cu = QMPC_KA(unsigned long long, b3, O3, prio_cu); A.prio_tag = QMPC_KA_I(b3, O3, prio_tag);
+  H.clear_counts = qmpc_ka_ptr<int>(cc, 0, 0); H.hint_max_z = QMPC_KA(int32_t, b3, O3, hint_max_z);
+  H.so_order = QMPC_KA(unsigned long long, b4, O4, so_order); H.so_first = (int)QMPC_KA_I(b4, O4, so_first);
+  H.so_nseg = (int)nsg;
+#undef QMPC_KA
+#undef QMPC_KA_I
+}
+
+// qmpc_robot_keys_wave once more for the kernels that batch their kernel arguments (the 64-row classes' first-class kernels; the
+// other classes keep the function above as it is), the same arithmetic in two halves: the LOADS (every address depends on the lane alone, so they all go
+// out together, with the wave's other loads of stage 0 -- the lanes outside a set read an element of the same robot's row that
+// lies inside it and drop it afterwards) and the arithmetic, which the caller runs once the loads are back.
+struct QmpcKeysRaw {
+  uint32_t graw;
+  float rraw, pk, wv, tr0, tr1, wk;
+  float q __attribute__((ext_vector_type(4)));
+};
+__device__ __forceinline__ QmpcKeysRaw qmpc_robot_keys_wave_load(const QmpcStage0Args& A, const int i, const int lane) {
+  const int h = A.horizon;
+  const uint32_t* g4 = reinterpret_cast<const uint32_t*>(A.gait + (size_t)i * 4 * h);
+  QmpcKeysRaw R;
+  R.graw = g4[lane < h ? lane : 0];
+  R.rraw = A.r[(size_t)i * 12 + (lane < 12 ? lane : 0)];  // r[axis * 4 + foot]
+  // error rows: lane 0..2 orientation k, lane 3..5 position k
+  const int k = (lane < 3) ? lane : (lane < 6 ? lane - 3 : 0);
+  const bool rot = lane < 3;
+  const float* q = A.q + (size_t)i * 4;
+  const float* tr = A.traj + (size_t)i * 12 * h;
+  typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+  R.q = *reinterpret_cast<const f32x4u*>(q);
+  R.pk = A.p[(size_t)i * 3 + k];
+  R.wv = (rot ? A.w : A.v)[(size_t)i * 3 + k];
+  R.tr0 = tr[(rot ? 0 : 3) + k];
+  R.tr1 = tr[(rot ? 6 : 9) + k];
+  R.wk = A.weights[(size_t)i * A.weights_stride + (rot ? 0 : 3) + k];
+  return R;
+}
+// (yaw, alpha: the robot's P.yaw and P.alpha entries, which stage 0 loads for itself)
+__device__ __forceinline__ QmpcKeys qmpc_robot_keys_wave_eval(const QmpcParams& P, const QmpcKeysRaw& R, const float yaw, const float alpha,
+                                                              const int h, const int lane) {
+  const uint32_t graw = (lane < h) ? R.graw : 0u;
+  const float rraw = (lane < 12) ? R.rraw : 0.f;
+  const unsigned m = qmpc_stance_set(graw);
+  int nst = 0, first3 = 0;
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+    const unsigned long long bf = __ballot((m >> f) & 1u);
+    nst += __popcll(bf);
+    first3 += __popcll(bf & 7ull);
+  }
+  const unsigned long long nz = __ballot(m != 0u);
+  unsigned set0 = 0u;
+  int run = 0;
+  if (nz != 0ull) {  // (uniform)
+    const int k0 = __builtin_ctzll(nz);
+    set0 = (unsigned)__builtin_amdgcn_readlane((int)m, k0);
+    const unsigned long long ne = ~(__ballot(m == set0 && lane < h) >> k0);
+    run = ne ? __builtin_ctzll(ne) : 64;
+    run = run < h - k0 ? run : h - k0;
+  }
+  const int k = (lane < 3) ? lane : (lane < 6 ? lane - 3 : 0);
+  const bool rot = lane < 3;
+  const float T = (float)h * (float)P.dt;
+  const float qw = R.q[0], qx = R.q[1], qy = R.q[2], qz = R.q[3];
+  const float ang = (k == 0) ? 2.f * (qw * qx + qy * qz) : (k == 1 ? 2.f * (qw * qy - qz * qx) : yaw);
+  const float x0 = rot ? ang : R.pk;
+  const float xd = R.wv;
+  const float e = (x0 - R.tr0) + T * (xd - R.tr1);
+  const float wk = R.wk;
+  const float ialpha = 1.f / (alpha + 1e-30f);
+  // (the six rows and the twelve foot coordinates are put together with v_readlane -- uniform scalars, a few cycles each and
+  //  independent of one another; butterflies through the LDS crossbar, ~17 dependent ds_bpermute, cost the stage ~1 k cycles)
+  const float t_acc = wk * __builtin_fabsf(e), t_dem = __builtin_sqrtf(wk * ialpha) * __builtin_fabsf(e);
+  float acc = 0.f, wsum = 1e-30f, dem = 0.f;
+#pragma unroll
+  for (int l = 0; l < 6; ++l) {
+    acc += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, t_acc), l));
+    wsum += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wk), l));
+    dem += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, t_dem), l));
+  }
+  float score = acc / wsum * (float)first3;
+  const float demand = dem * (float)first3 / ((float)P.mass * __builtin_fabsf((float)P.gravity) + 1e-30f);
+  float pattern = 0.f;
+  if (set0 != 0u) {  // (uniform)
+    float c3[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax)
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        const float rv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rraw), 4 * ax + f));
+        c3[ax] += ((set0 >> f) & 1u) ? rv : 0.f;
+      }
+    const float inv = 1.f / (float)__builtin_popcount(set0);
+    const float cx = c3[0] * inv, cy = c3[1] * inv, cz = __builtin_fabsf(c3[2] * inv);
+    const float sat = __builtin_sqrtf(cx * cx + cy * cy) * (float)P.mu_inv / (cz > 1e-3f ? cz : 1e-3f);
+    const float sa = sat > 0.6f ? (sat < 1.f ? sat : 1.f) : 0.f;
+    const float pat = (float)run * sa - 1.5f;
+    pattern = pat > 0.f ? pat : 0.f;
+    score += 0.15f * pattern;
+  }
+  return {nst, score, demand, pattern};
+}
 // score -> `per` logarithmic levels per octave from 2^-6 on, `levels` of them, HARDEST = 0 (a NaN: the easiest)
 __device__ __forceinline__ int qmpc_score_level(const float score, const float per, const int levels) {
   int b = (score > 0.f) ? (int)(per * (__log2f(score) + 6.f)) : 0;
@@ -490,14 +669,33 @@ struct Smem {
 // profiling build (-DQMPC_FIXED_STAMP): shader-clock stamps of EVERY wave of the (four-wave) workgroup in front of the sweep, taken by
 // the wave's lane 0 and stored in row rid + batch of the clock buffer (which the tool allocates twice as long), slot 4 * wave + k:
 // k = 0 this wave's loads of stage 0 have landed, 1 / 2 it arrives at barrier 1 / 2, 3 its part of H is assembled
-// (tools/fixed_part_phases.py: which wave the others wait for, stage by stage)
+// (tools/fixed_part_phases.py: which wave the others wait for, stage by stage).
+// The batched first-class kernels (64-row classes) add the front of the workgroup, which thread 0's stamp 0 does not see, in row
+// rid + 2 * batch (the tool allocates three times as long), slot 4 * wave + k: k = 0 the wave enters the kernel, 1 its batch of
+// kernel arguments is back, 2 the last load of its stage 0 is issued
 #ifdef QMPC_FIXED_STAMP
+#define QMPC_ENTRY_TICK(k) const long long qmpc_entry_clk##k = clock64()
+#define QMPC_ENTRY_STORE(rid)                                                                  \
+  do {                                                                                         \
+    if (A.dbg_clk && (threadIdx.x & 63) == 0 && threadIdx.x < 256) {                           \
+      long long* row__ = A.dbg_clk + (size_t)((rid) + P.batch * 2) * 16 + (threadIdx.x >> 6) * 4; \
+      row__[0] = qmpc_entry_clk0;                                                              \
+      row__[1] = qmpc_entry_clk1;                                                              \
+    }                                                                                          \
+  } while (0)
+#define QMPC_ISSUED_TICK()                                                                                  \
+  do {                                                                                                      \
+    if (PRE && PK.dbg_clk && lane == 0 && tid < 256) PK.dbg_clk[(size_t)(rid + PK.batch * 2) * 16 + (tid >> 6) * 4 + 2] = clock64(); \
+  } while (0)
 #define QMPC_WAVE_TICK(k)                                                                                   \
   do {                                                                                                      \
     if (PK.dbg_clk && lane == 0 && tid < 256) PK.dbg_clk[(size_t)(rid + PK.batch) * 16 + (tid >> 6) * 4 + (k)] = clock64(); \
   } while (0)
 #else
 #define QMPC_WAVE_TICK(k) do { } while (0)
+#define QMPC_ENTRY_TICK(k) do { } while (0)
+#define QMPC_ENTRY_STORE(rid) do { } while (0)
+#define QMPC_ISSUED_TICK() do { } while (0)
 #endif
 
 // census builds (-DQMPC_STOP_AFTER=<k>, tools/census.sh; never in production): the workgroup leaves solve_one right after stage k
@@ -541,20 +739,27 @@ __device__ __forceinline__ void qmpc_census_dump(Smem<RB>& S, const QmpcParams& 
 // minimiser as below, then the inverse goes to the robot's work item in global memory (L2 / Infinity-Cache
 // resident) instead of LDS and the workgroup moves on; the active set is run by qmpc_engine_kernel
 // (qmpc_engine.hip) -- a workgroup of the large classes no longer pins a whole CU while one of its waves iterates.
-template <int RB, bool V5, bool CMD, bool ADMM = false, bool WARM = false, bool PHA = false, bool BIG = false, bool PRIO = false>
+// PRE = true: the caller fetched the kernel arguments of stage 0 in one batch (qmpc_kernarg_batch): *pre; otherwise they are read
+// from PK where they are used.
+template <int RB, bool V5, bool CMD, bool ADMM = false, bool WARM = false, bool PHA = false, bool BIG = false, bool PRIO = false,
+          bool PRE = false>
 __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>& S, const QmpcParams& PK,
-                                          const bool ws_cold = false) {  // (WARM: ignore the robot's previous working set)
+                                          const bool ws_cold = false,  // (WARM: ignore the robot's previous working set)
+                                          const QmpcStage0Args* pre = nullptr) {
   using C = Cfg<RB>;
   constexpr int NP = C::NP, CW = C::CW, NT = C::NT, KMAX = C::KMAX, KW = C::KW, RE = C::RE;
   const QmpcParams& P = S.par;  // parked copy: everything after stage 0
   const int lane = tid & (WAVE - 1);
   const int i = tid % NP;  // matrix row owned by this thread
   const int c = tid / NP;  // column group (0..3): columns c*CW .. c*CW+CW-1
-  const int h = PK.horizon;
+  // (a kernel argument of stage 0: the batched value, or read in place -- the text of PK.f, so that the kernels that do not batch
+  //  compile to what they compiled to)
+#define QMPC_A(f) (PRE ? pre->f : PK.f)
+  const int h = QMPC_A(horizon);
   const int nfs = 4 * h;   // foot-steps in the horizon (<= 64; <= 144 in the 192-row class, horizons up to 36)
   constexpr int HMAX = C::HMAX;
   constexpr int NFG = (4 * HMAX + 63) / 64;  // 64-foot-step groups of the contact table
-  long long* dbg_clk = PK.dbg_clk ? PK.dbg_clk + (size_t)rid * 16 : nullptr;
+  long long* dbg_clk = QMPC_A(dbg_clk) ? QMPC_A(dbg_clk) + (size_t)rid * 16 : nullptr;
   QMPC_TICK(0);
   {
     const double none[1] = {0.0};
@@ -562,14 +767,26 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     QMPC_STOP(-1, none);
   }
   __builtin_amdgcn_s_setprio(3);  // a workgroup that is just starting is behind everybody else on its CU
-  // order hint, single-round launches: a robot the previous call found hard (wave-uniform: two scalar loads)
+  // order hint, single-round launches: a robot the previous call found hard (wave-uniform.  The batched kernels: two scalar loads;
+  // the others read the group with vector loads, lane by lane)
   bool hard = false;
   int hfloor = 0;  // the priority the robot does not fall below while it sweeps
-  if (PK.hint_hard > 0) {
+  [[maybe_unused]] qmpc_i32x16 hint_grp = {};
+  [[maybe_unused]] int hint_top = 0;
+  if constexpr (PRE) {
+    // the batched kernels: the sixteen counts of the robot's aligned group with ONE 64-byte scalar load (the robot is
+    // wave-uniform, the group 64-byte aligned) and the previous call's maximum with another, both issued here, in front of the
+    // stage's vector loads, and looked at behind them (below): scalar arithmetic, no vector round trip in front of the stage
+    if (QMPC_A(hint_hard) > 0) {
+      const int ru = __builtin_amdgcn_readfirstlane(rid);
+      hint_grp = *reinterpret_cast<const QMPC_AS4 qmpc_i32x16*>((unsigned long long)(QMPC_A(hint_iters) + (ru & ~15)));
+      hint_top = *reinterpret_cast<const QMPC_AS4 int32_t*>((unsigned long long)QMPC_A(hint_max_r));
+    }
+  } else if (QMPC_A(hint_hard) > 0) {
     // hard = at least hint_hard iterations, at least 3/5 of the previous call's maximum, AND among the top two of the sixteen
-    // robots of its aligned group (one 64-byte scalar load): where every robot iterates about equally long nobody is
+    // robots of its aligned group: where every robot iterates about equally long nobody is
     // singled out and the staging below stays what it is -- everybody at the top priority is no staging at all (-13 %)
-    const int32_t* grp = (const int32_t*)__builtin_assume_aligned(PK.hint_iters + (rid & ~15), 64);
+    const int32_t* grp = (const int32_t*)__builtin_assume_aligned(QMPC_A(hint_iters) + (rid & ~15), 64);
     int mine = 0, ge = 0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) mine = ((rid & 15) == k) ? grp[k] : mine;
@@ -577,16 +794,18 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     for (int k = 0; k < 16; ++k) ge += (grp[k] >= mine) ? 1 : 0;
     mine = __builtin_amdgcn_readfirstlane(mine);
     ge = __builtin_amdgcn_readfirstlane(ge);
-    const int top = __builtin_amdgcn_readfirstlane(*PK.hint_max_r);
-    hard = mine >= PK.hint_hard && 5 * mine >= 3 * top && ge <= 2;
-    hfloor = hard ? 3 : ((mine >= PK.hint_hard && 5 * mine >= 2 * top && ge <= 4) ? 2 : 0);
+    const int top = __builtin_amdgcn_readfirstlane(*QMPC_A(hint_max_r));
+    hard = mine >= QMPC_A(hint_hard) && 5 * mine >= 3 * top && ge <= 2;
+    hfloor = hard ? 3 : ((mine >= QMPC_A(hint_hard) && 5 * mine >= 2 * top && ge <= 4) ? 2 : 0);
   }
 
   unsigned long long prio_mine = 0ull;
   unsigned long long* prio_word = nullptr;
   // ------------------------------------------------------------ stage 0
-  // Every global load of the robot's record is issued up front (one memory
-  // latency for the whole stage); then: contact table -> compact stance list
+  // Every global load of the robot's record is issued up front -- in the batched kernels (PRE) behind ONE wait for the kernel
+  // arguments and with no wait for memory in any wave before the stage's last load is out (tools/stage0_waits.py counts both in
+  // the compiled kernel: one scalar and one vector round trip for the stage); the other kernels fetch each pointer where its
+  // block uses it --; then: contact table -> compact stance list
   // (SolverMPC.cpp:441-469 finds the same set by scanning for ub ~ 0 rows) and
   // everything that needs no LDS input.
   auto& Aa = S.u.aw.a;
@@ -607,8 +826,8 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
   static_assert(sizeof(QmpcParams) % 4 == 0 && sizeof(QmpcParams) / 4 <= 256, "parameter block copy");
   uint32_t g_par = 0;
   if (tid < (int)(sizeof(QmpcParams) / 4)) g_par = reinterpret_cast<const uint32_t*>(&PK)[tid];
-  float g_yaw = cmdm ? PK.c_rpy[(size_t)rid * 3 + 2] : PK.yaw[rid];
-  float g_xdrag = cmdm ? PK.c_xci[rid] : PK.x_drag[(size_t)rid * PK.x_drag_stride];
+  float g_yaw = cmdm ? PK.c_rpy[(size_t)rid * 3 + 2] : QMPC_A(yaw)[rid];
+  float g_xdrag = cmdm ? PK.c_xci[rid] : QMPC_A(x_drag)[(size_t)rid * QMPC_A(x_drag_stride)];
   float c_p0 = 0.f, c_p1 = 0.f, c_p2 = 0.f;
   QmpcTrajGen tg;
   if (cmdm) {
@@ -632,7 +851,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       return (unsigned char)qmpc_cmd_gait_bit(fs >> 2, PK.c_gait_iteration[rid], PK.c_gait_offsets[(size_t)rid * 4 + leg],
                                               PK.c_gait_durations[(size_t)rid * 4 + leg], h);
     }
-    return (unsigned char)PK.gait[(size_t)rid * nfs + fs];
+    return (unsigned char)QMPC_A(gait)[(size_t)rid * nfs + fs];
   };
   unsigned char g_gait = 0;
   unsigned char g_gaitx[NFG > 1 ? NFG - 1 : 1] = {};
@@ -656,41 +875,54 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       g_r1 = qmpc_cmd_foot_offset(pf[1], c_p1);
       g_r2 = qmpc_cmd_foot_offset(pf[2], c_p2);
     } else {
-      const float* r = PK.r + (size_t)rid * 12;
+      const float* r = QMPC_A(r) + (size_t)rid * 12;
       g_r0 = r[0 * 4 + mb];
       g_r1 = r[1 * 4 + mb];
       g_r2 = r[2 * 4 + mb];
     }
   }
+  // (the batched kernels: the quaternion and the two rates are loaded AS the register tuples they are merged into: merged element by element with
+  //  separate defaults, the wide loads' results had to be copied at the block's exit -- a wait for memory inside the block, and a
+  //  second round trip for every load of waves 2 / 3 that follows it)
+  typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
+  typedef float f32x3u __attribute__((ext_vector_type(3), aligned(4)));
+  [[maybe_unused]] f32x4u t_q = {1.f, 0.f, 0.f, 0.f};
+  [[maybe_unused]] f32x3u t_w = {0.f, 0.f, 0.f}, t_v = {0.f, 0.f, 0.f};
   float g_q[4] = {1.f, 0.f, 0.f, 0.f}, g_w[3] = {0.f, 0.f, 0.f}, g_v[3] = {0.f, 0.f, 0.f};
   float g_p = 0.f, g_traj = 0.f, g_wt = 0.f;
   if (e_thr) {
-    const float* q = (cmdm ? PK.c_orientation : PK.q) + (size_t)rid * 4;
-    const float* om = (cmdm ? PK.c_omega_world : PK.w) + (size_t)rid * 3;
-    const float* v = (cmdm ? PK.c_v_world : PK.v) + (size_t)rid * 3;
+    const float* q = (cmdm ? PK.c_orientation : QMPC_A(q)) + (size_t)rid * 4;
+    const float* om = (cmdm ? PK.c_omega_world : QMPC_A(w)) + (size_t)rid * 3;
+    const float* v = (cmdm ? PK.c_v_world : QMPC_A(v)) + (size_t)rid * 3;
+    if constexpr (PRE) {
+      t_q = *reinterpret_cast<const f32x4u*>(q);
+      t_w = *reinterpret_cast<const f32x3u*>(om);
+      t_v = *reinterpret_cast<const f32x3u*>(v);
+    } else {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) g_q[k] = q[k];
+      for (int k = 0; k < 4; ++k) g_q[k] = q[k];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      g_w[k] = om[k];
-      g_v[k] = v[k];
+      for (int k = 0; k < 3; ++k) {
+        g_w[k] = om[k];
+        g_v[k] = v[k];
+      }
     }
     if (cmdm) {
       if (erow >= 3 && erow < 6) g_p = (erow == 3) ? c_p0 : (erow == 4 ? c_p1 : c_p2);
       g_traj = qmpc_cmd_traj_value(tg, ek, erow);
       g_wt = qmpc_cmd_weight(erow);
     } else {
-      if (erow >= 3 && erow < 6) g_p = PK.p[(size_t)rid * 3 + (erow - 3)];
-      g_traj = PK.traj[(size_t)rid * 12 * h + eidx0];
-      g_wt = PK.weights[(size_t)rid * PK.weights_stride + erow];
+      if (erow >= 3 && erow < 6) g_p = QMPC_A(p)[(size_t)rid * 3 + (erow - 3)];
+      g_traj = QMPC_A(traj)[(size_t)rid * 12 * h + eidx0];
+      g_wt = QMPC_A(weights)[(size_t)rid * QMPC_A(weights_stride) + erow];
     }
   }
   float g_w12 = 0.f;
   const int w12 = tid - (NT - 12);  // (the last twelve threads)
-  if (w12 >= 0) g_w12 = cmdm ? qmpc_cmd_weight(w12) : PK.weights[(size_t)rid * PK.weights_stride + w12];
+  if (w12 >= 0) g_w12 = cmdm ? qmpc_cmd_weight(w12) : QMPC_A(weights)[(size_t)rid * QMPC_A(weights_stride) + w12];
   // (loaded here with everything else: a global load issued after barrier 1 would be waited
   //  for by barrier 2)
-  float g_alpha = cmdm ? 4e-5f : PK.alpha[(size_t)rid * PK.alpha_stride];  // ConvexMPCLocomotion.cpp:604
+  float g_alpha = cmdm ? 4e-5f : QMPC_A(alpha)[(size_t)rid * QMPC_A(alpha_stride)];  // ConvexMPCLocomotion.cpp:604
   double g_ct0 = 0.0, g_ct4 = 0.0, g_ct1 = 0.0, g_ct5 = 0.0, g_ct8 = 0.0;
   // ((h + 1)^2 <= 256 == NT in the 64-row class up to h = 15; h = 16 there, and the 192-row class -- 768 threads, up to 37 x 37
   //  entries -- take a second entry)
@@ -698,22 +930,22 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
   double g2_ct0 = 0.0, g2_ct4 = 0.0, g2_ct1 = 0.0, g2_ct5 = 0.0, g2_ct8 = 0.0;
   if constexpr (TAB2) {
     if (tid + NT < hh) {
-      g2_ct0 = PK.ctab[tid + NT];
-      g2_ct4 = PK.ctab[4 * hh + tid + NT];
-      g2_ct1 = PK.ctab[1 * hh + tid + NT];
-      g2_ct5 = PK.ctab[5 * hh + tid + NT];
-      g2_ct8 = PK.ctab[8 * hh + tid + NT];
+      g2_ct0 = QMPC_A(ctab)[tid + NT];
+      g2_ct4 = QMPC_A(ctab)[4 * hh + tid + NT];
+      g2_ct1 = QMPC_A(ctab)[1 * hh + tid + NT];
+      g2_ct5 = QMPC_A(ctab)[5 * hh + tid + NT];
+      g2_ct8 = QMPC_A(ctab)[8 * hh + tid + NT];
     }
   }
   const int tix = NT - 1 - tid;  // (the first entry of the tables: taken from the LAST thread down)
   if (tix < hh) {
     // the x_drag tables are fetched unconditionally: making them wait for the x_drag
     // value would put a second memory round trip in front of them
-    g_ct0 = PK.ctab[tix];
-    g_ct4 = PK.ctab[4 * hh + tix];
-    g_ct1 = PK.ctab[1 * hh + tix];
-    g_ct5 = PK.ctab[5 * hh + tix];
-    g_ct8 = PK.ctab[8 * hh + tix];
+    g_ct0 = QMPC_A(ctab)[tix];
+    g_ct4 = QMPC_A(ctab)[4 * hh + tix];
+    g_ct1 = QMPC_A(ctab)[1 * hh + tix];
+    g_ct5 = QMPC_A(ctab)[5 * hh + tix];
+    g_ct8 = QMPC_A(ctab)[8 * hh + tix];
   }
   // ONE-ROUND launch without a usable hint (prio_cu != nullptr): the workgroups that share a CU compete for its issue
   // slots, and the CU is done when the LAST of them is -- the one that iterates longest.  Which one that will be is guessed from
@@ -724,18 +956,30 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
   // (qmpc_robot_keys_wave), and its last lane posts (call number, score level, robot) with ONE atomic maximum on its CU's word
   // (four arrivals per word, served by the XCD's L2; a newer call's number beats whatever an older call left: nothing to reset) ...
   if constexpr (PRIO && !CMD && !ADMM && !BIG && !PHA) {
-    if (PK.prio_cu && (tid >> 6) == 1) {  // (wave 1, all lanes; its last lane posts)
-      const QmpcKeys kk = qmpc_robot_keys_wave(PK, rid, lane);
+    [[maybe_unused]] QmpcKeysRaw kraw = {};
+    if constexpr (PRE) {
+      // (the batched kernels: the keys' own loads go out with the stage's -- one round trip for wave 1 as well -- and the
+      //  arithmetic follows once everything is in flight)
+      if (QMPC_A(prio_cu) && (tid >> 6) == 1) kraw = qmpc_robot_keys_wave_load(*pre, rid, lane);
+      asm volatile("; qmpc stage0 loads end");
+      QMPC_ISSUED_TICK();
+      asm volatile("" : "+v"(kraw.graw), "+v"(kraw.rraw), "+v"(kraw.q), "+v"(kraw.pk), "+v"(kraw.wv), "+v"(kraw.tr0), "+v"(kraw.tr1),
+                   "+v"(kraw.wk));
+    }
+    if (QMPC_A(prio_cu) && (tid >> 6) == 1) {  // (wave 1, all lanes; its last lane posts)
+      QmpcKeys kk;
+      if constexpr (PRE) kk = qmpc_robot_keys_wave_eval(PK, kraw, g_yaw, g_alpha, h, lane);
+      else kk = qmpc_robot_keys_wave(PK, rid, lane);
       // (posted only by a robot that is likely to meet its bounds at all: where nobody does, lifting one robot of four over its
       //  neighbours only delays the other three -- SparseCMPC's parameters on configs[1]'s states: -9 %)
       if (tid == 127) {
         unsigned hwid, xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        prio_word = PK.prio_cu + (((xcc & 7u) << 8) | ((hwid >> 8) & 0xffu));
+        prio_word = QMPC_A(prio_cu) + (((xcc & 7u) << 8) | ((hwid >> 8) & 0xffu));
         if (kk.demand >= 12.f || kk.pattern > 0.5f) {
           const int pb = qmpc_score_level(kk.score, 6.f, 64);
-          prio_mine = ((unsigned long long)PK.prio_tag << 32) | ((unsigned long long)(63 - pb) << 24) | (unsigned)(rid & 0xffffff);
+          prio_mine = ((unsigned long long)QMPC_A(prio_tag) << 32) | ((unsigned long long)(63 - pb) << 24) | (unsigned)(rid & 0xffffff);
           __hip_atomic_fetch_max(prio_word, prio_mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         // (what was posted, for the thread that reads the word back at the end of stage 1: its low half, < 2^30; -1 = nothing)
@@ -743,18 +987,52 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       }
     }
   }
+  if constexpr (PRE && !(PRIO && !CMD && !ADMM && !BIG && !PHA)) {
+    asm volatile("; qmpc stage0 loads end");
+    QMPC_ISSUED_TICK();
+  }
   // Every load above is in flight now.  The compiler otherwise sinks the first use
   // of each value (a conversion) into the conditional block of its load and waits for
   // memory there -- one full round trip per block, eight in a row.  Touching all the
   // values here, after the last load has been issued, leaves one wait for the lot.
   {
     int gg = g_gait;
-    asm volatile("" : "+v"(g_par), "+v"(g_yaw), "+v"(g_xdrag), "+v"(g_alpha), "+v"(gg), "+v"(g_r0), "+v"(g_r1),
-                 "+v"(g_r2), "+v"(g_q[0]), "+v"(g_q[1]), "+v"(g_q[2]), "+v"(g_q[3]), "+v"(g_w[0]), "+v"(g_w[1]),
-                 "+v"(g_w[2]), "+v"(g_v[0]), "+v"(g_v[1]), "+v"(g_v[2]), "+v"(g_p), "+v"(g_traj), "+v"(g_wt),
-                 "+v"(g_w12), "+v"(g_ct0), "+v"(g_ct4), "+v"(g_ct1), "+v"(g_ct5), "+v"(g_ct8));
+    if constexpr (PRE) {
+      asm volatile("" : "+v"(g_par), "+v"(g_yaw), "+v"(g_xdrag), "+v"(g_alpha), "+v"(gg), "+v"(g_r0), "+v"(g_r1),
+                   "+v"(g_r2), "+v"(t_q), "+v"(t_w), "+v"(t_v), "+v"(g_p), "+v"(g_traj), "+v"(g_wt),
+                   "+v"(g_w12), "+v"(g_ct0), "+v"(g_ct4), "+v"(g_ct1), "+v"(g_ct5), "+v"(g_ct8));
+#pragma unroll
+      for (int k = 0; k < 4; ++k) g_q[k] = t_q[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        g_w[k] = t_w[k];
+        g_v[k] = t_v[k];
+      }
+    } else {
+      asm volatile("" : "+v"(g_par), "+v"(g_yaw), "+v"(g_xdrag), "+v"(g_alpha), "+v"(gg), "+v"(g_r0), "+v"(g_r1),
+                   "+v"(g_r2), "+v"(g_q[0]), "+v"(g_q[1]), "+v"(g_q[2]), "+v"(g_q[3]), "+v"(g_w[0]), "+v"(g_w[1]),
+                   "+v"(g_w[2]), "+v"(g_v[0]), "+v"(g_v[1]), "+v"(g_v[2]), "+v"(g_p), "+v"(g_traj), "+v"(g_wt),
+                   "+v"(g_w12), "+v"(g_ct0), "+v"(g_ct4), "+v"(g_ct1), "+v"(g_ct5), "+v"(g_ct8));
+    }
     g_gait = (unsigned char)gg;
     if constexpr (TAB2) asm volatile("" : "+v"(g2_ct0), "+v"(g2_ct4), "+v"(g2_ct1), "+v"(g2_ct5), "+v"(g2_ct8));
+  }
+  if constexpr (PRE) {
+    if (QMPC_A(hint_hard) > 0) {
+      // hard = at least hint_hard iterations, at least 3/5 of the previous call's maximum, AND among the top two of the sixteen
+      // robots of its aligned group: where every robot iterates about equally long nobody is singled out and the staging below
+      // stays what it is -- everybody at the top priority is no staging at all (-13 %)
+      asm volatile("" : "+s"(hint_grp), "+s"(hint_top));
+      const int me = rid & 15;
+      int mine = 0, ge = 0;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) mine = (me == k) ? hint_grp[k] : mine;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) ge += (hint_grp[k] >= mine) ? 1 : 0;
+      const int top = hint_top;
+      hard = mine >= QMPC_A(hint_hard) && 5 * mine >= 3 * top && ge <= 2;
+      hfloor = hard ? 3 : ((mine >= QMPC_A(hint_hard) && 5 * mine >= 2 * top && ge <= 4) ? 2 : 0);
+    }
   }
   if (tid < (int)(sizeof(QmpcParams) / 4)) reinterpret_cast<uint32_t*>(&S.par)[tid] = g_par;
   const double x_drag = (double)g_xdrag;
@@ -913,7 +1191,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     QMPC_STOP(0, keep0);
   }
   // one-round launch with the order hint: everybody started at the highest priority (a tie); from here to the sweep the
-  // robots the previous call did not find hard step back one level (the hint's two scalar loads have landed with the record)
+  // robots the previous call did not find hard step back one level (the hint's loads have landed with the record)
   if (PK.hint_hard > 0 && !hard) __builtin_amdgcn_s_setprio(2);
   const int nst = S.nst;
   const int n = 3 * nst;
@@ -3432,15 +3710,19 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
 
 }  // namespace
 
+#undef QMPC_A
+
 // one robot with the engine pair of its class: event-form engine first (it continues in global memory when its
 // on-chip pool fills up); the (rare) robot that runs out of working-set SLOTS there is solved again from scratch
 // with the Schur-form engine, which has more of them
-template <int RB, bool CMD, bool WARM, bool PRIO = false>
-__device__ __forceinline__ void solve_robot(const int rid, const int tid, Smem<RB>& S, const QmpcParams& P) {
+// (PRE: the first solve takes the kernel arguments of its stage 0 from *pre, qmpc_kernarg_batch; a re-run reads them in place)
+template <int RB, bool CMD, bool WARM, bool PRIO = false, bool PRE = false>
+__device__ __forceinline__ void solve_robot(const int rid, const int tid, Smem<RB>& S, const QmpcParams& P,
+                                            const QmpcStage0Args* pre = nullptr) {
   if constexpr (Cfg<RB>::EVENT_ENGINE) {
     bool again;
     if (Cfg<RB>::GLOBAL_EVENTS && S.evslot < 0) again = true;  // no pool slice (pool_acquire timed out): Schur form only
-    else again = solve_one<RB, true, CMD, false, WARM, false, false, PRIO>(rid, tid, S, P);
+    else again = solve_one<RB, true, CMD, false, WARM, false, false, PRIO, PRE>(rid, tid, S, P, false, pre);
     bool warm_again = false;
     if constexpr (WARM) {
       // a warm start that asked for the re-run (a guess the repair phase could not mend within the iteration limit, or one
@@ -3752,7 +4034,40 @@ __global__ __launch_bounds__(Cfg<RB>::NT_LAUNCH, Cfg<RB>::MIN_WAVES) void qmpc_s
   // (the 96-row class: eight waves launched, six stay -- the logical thread index from here on)
   const int tid0 = balance_waves<RB>(S, P);
   if (tid0 < 0) return;
-  if constexpr (!LISTED) {
+  if constexpr (!LISTED && Cfg<RB>::C1) {
+    // The 64-row classes: every kernel argument that this head and stage 0 of the solve read comes in ONE batch of scalar loads
+    // behind one wait (qmpc_kernarg_batch) -- the launch starts on a cold scalar cache, and fetched where they are used they
+    // were a dozen round trips in a row in front of the stage's vector loads.
+    static_assert(!Cfg<RB>::GLOBAL_EVENTS && !Cfg<RB>::BALANCE, "the 64-row classes: no pool slice, no wave placement");
+    typedef const QMPC_AS4 unsigned char* KernargBytes;
+    KernargBytes kb = (KernargBytes)__builtin_amdgcn_kernarg_segment_ptr();
+    QMPC_ENTRY_TICK(0);
+    QmpcStage0Args A;
+    QmpcHeadArgs H;
+    qmpc_kernarg_batch(kb, A, H);
+    QMPC_ENTRY_TICK(1);
+    if (blockIdx.x == 0 && H.clear_counts)
+      for (int k = tid0; k < QMPC_COUNTERS; k += Cfg<RB>::NT) H.clear_counts[k] = 0;  // 3 counters + 3 heads
+    if (blockIdx.x == 0 && tid0 == 0 && H.hint_max_z) *H.hint_max_z = 0;
+    int rid = (int)blockIdx.x;
+    // (size order / order hint: the first workgroups build the permutation, a segment each, before they solve their own robots;
+    //  the workgroups of the later rounds read it)
+    if (H.so_order) {
+      asm volatile("; qmpc size order begin");
+      if ((int)blockIdx.x < H.so_nseg) size_order_build<RB, CMD>(tid0, S, P);
+      else if ((int)blockIdx.x >= H.so_first || (int)blockIdx.x < H.so_nseg * (QMPC_SO_HEAD + 1)) rid = size_order_take(P);
+      // (a launch of several rounds: the batch is fetched again behind the builder -- from a warm scalar cache -- instead of
+      //  being kept in scalar registers across it)
+      asm volatile("" : "+s"(kb));
+      qmpc_kernarg_batch(kb, A, H);
+      asm volatile("; qmpc size order end");
+    }
+    QMPC_ENTRY_STORE(rid);
+    __builtin_assume(tid0 >= 0 && tid0 < Cfg<RB>::NT);
+    // (the first class of a chain: the only launch that can be one round.  Not the five-per-CU instantiation: it exists for launches
+    //  of several rounds, and at 96 registers the staging's code in stage 0 costs it spills on the main path)
+    solve_robot<RB, CMD, WARM, RB != 6, true>(rid, tid0, S, P, &A);
+  } else if constexpr (!LISTED) {
     // (block index first: only block 0 waits for the kernel argument)
     if (blockIdx.x == 0 && P.clear_counts)
       for (int k = tid0; k < QMPC_COUNTERS; k += Cfg<RB>::NT) P.clear_counts[k] = 0;  // 3 counters + 3 heads
@@ -3766,9 +4081,8 @@ __global__ __launch_bounds__(Cfg<RB>::NT_LAUNCH, Cfg<RB>::MIN_WAVES) void qmpc_s
       else if ((int)blockIdx.x >= P.so_first || (int)blockIdx.x < P.so_nseg * (QMPC_SO_HEAD + 1)) rid = size_order_take(P);
     }
     __builtin_assume(tid0 >= 0 && tid0 < Cfg<RB>::NT);
-    // (the first class of a chain: the only launch that can be one round.  Not the five-per-CU instantiation: it exists for launches
-    //  of several rounds, and at 96 registers the staging's code in stage 0 costs it spills on the main path)
-    solve_robot<RB, CMD, WARM, RB != 6>(rid, tid0, S, P);
+    // (the first class of a chain: the only launch that can be one round)
+    solve_robot<RB, CMD, WARM, true>(rid, tid0, S, P);
     pool_release<RB>(S, P);
     balance_release<RB>(tid0, S, P);
   } else {

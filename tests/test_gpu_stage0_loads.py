@@ -1,0 +1,152 @@
+"""GPU suite (-m gpu): stage 0's loads in the 64-row classes' first-class kernels, which fetch their kernel arguments in one batch
+and form every address of the robot's record from it -- at the smallest shapes at which a hoisted address can go wrong.
+
+Shapes.
+  * horizons 1, 10, 15 and 16.  h = 16 with ONE foot in stance per segment (48 rows): (h + 1)^2 = 289 > 256 threads, so the
+    tables' second entry per thread is read; 12 h = 192 error rows reach into wave 0.  h = 1 leaves most lanes without a row.
+  * batches 1, 3 and 65 (the last robot of an exactly-sized buffer; an odd count) on a handle of 65 -- the four-per-CU
+    instantiation -- and the same robots on a handle of 2048 -- the five-per-CU one.
+  * weights, alpha and x_drag per robot and shared (one row, stride 0).
+
+Checks.
+  (a) every robot's grf, status and iters are byte-identical solved in the full batch, alone in a batch of one, and in the batch
+      reversed (a result never depends on the batch around the robot); the first and the last three as batches of three;
+  (b) the forces agree with the oracle pipeline, per robot, within max(1e-4, 1.5 x the reference's float-order spread)
+      (test_gpu_parity.bound_for, the bound the parity suite uses for these families);
+  (c) the order hint: the same inputs twice with set_order_hint(1) give the bytes of the run with the hint off;
+  (d) qmpc_solve_commands (which shares the prologue) against qmpc_pack -> qmpc_solve -> qmpc_forces_to_body, byte-identical.
+"""
+import numpy as np
+import pytest
+
+from oracle import oracle as O
+from quadruped_ctrl_amd import workloads as W
+from test_gpu_parity import _pack_setup, _take, bound_for, rel_f0, report
+
+pytestmark = pytest.mark.gpu
+HORIZONS = (1, 10, 15, 16)
+KEYS = ("grf", "status", "iters")
+_CASES = {}
+
+
+def make_case(h, shared):
+    """65 robots that fit the 64-row class, every one with its own attitude, drag, weights and regularisation (or one shared row
+    of the last three), and -- computed once per case -- the oracle pipeline's forces."""
+    key = (h, shared)
+    if key in _CASES:
+        return _CASES[key]
+    B = 65
+    rng = np.random.default_rng(9100 + 10 * h + int(shared))
+    b = W.make_standing(B, h, seed=500 + h)
+    g = np.zeros((B, 4 * h), np.uint8)
+    for i in range(B):
+        if h == 16 or i % 3 == 0:
+            g[i].reshape(h, 4)[np.arange(h), rng.integers(0, 4, h)] = 1   # one foot in stance per segment: 3 h <= 48 rows
+        elif i % 3 == 1:
+            t = (rng.random(4 * h) < 0.5).astype(np.uint8)                # random table, thinned to 21 stance foot-steps
+            on = np.flatnonzero(t)
+            if on.size > 21:
+                t[rng.choice(on, on.size - 21, replace=False)] = 0
+            g[i] = t
+        else:
+            g[i, 4 * (h - 1) + int(rng.integers(0, 4))] = 1               # one foot, last step only
+    b["gait"] = g
+    rpy = np.stack([rng.uniform(-0.3, 0.3, B), rng.uniform(-0.3, 0.3, B), rng.uniform(-3.0, 3.0, B)], 1)
+    b["q"] = W._quat_from_rpy(rpy).astype(np.float32)
+    b["yaw"] = rpy[:, 2].astype(np.float32)
+    b["traj"].reshape(B, h, 12)[:, :, 2] = b["yaw"][:, None]
+    b["x_drag"] = rng.normal(0, 0.5, B).astype(np.float32)
+    b["alpha"] = (4e-5 * rng.uniform(0.25, 2.0, B)).astype(np.float32)
+    b["weights"] = (np.broadcast_to(b["weights"], (B, 12)) * rng.uniform(0.5, 2.0, (B, 12))).astype(np.float32)
+    if shared:
+        b["weights"] = b["weights"][7].copy()      # [12] -> stride 0
+        b["alpha"] = b["alpha"][7:8].copy()
+        b["x_drag"] = b["x_drag"][7:8].copy()
+    assert 3 * (g != 0).sum(1).max() <= 64
+    ref, nwsr, rc = O.solve_batch(_per_robot(b))
+    assert (rc == 0).all()
+    ref.setflags(write=False)
+    _CASES[key] = (b, ref)
+    return _CASES[key]
+
+
+def _per_robot(b):
+    """The same batch with the shared rows written out per robot (what the oracle and a sub-batch take)."""
+    B = b["batch"]
+    out = dict(b)
+    out["weights"] = np.ascontiguousarray(np.broadcast_to(b["weights"].reshape(-1, 12), (B, 12)))
+    out["alpha"] = np.ascontiguousarray(np.broadcast_to(b["alpha"].reshape(-1), (B,)))
+    out["x_drag"] = np.ascontiguousarray(np.broadcast_to(b["x_drag"].reshape(-1), (B,)))
+    return out
+
+
+def sub_batch(b, idx):
+    """Robots idx of the batch; a shared row stays the shared row (stride 0)."""
+    out = _take(b, np.asarray(idx))
+    for k, n in (("weights", 12), ("alpha", 1), ("x_drag", 1)):
+        if b[k].size == n:
+            out[k] = b[k]
+    return out
+
+
+def solve(m, b):
+    res = m.solve(b)
+    assert ((res["status"] & 47) == 0).all(), np.unique(res["status"])
+    return res
+
+
+@pytest.mark.parametrize("shared", [False, True], ids=["per-robot", "stride0"])
+@pytest.mark.parametrize("max_batch", [65, 2048], ids=["four-per-CU", "five-per-CU"])
+@pytest.mark.parametrize("h", HORIZONS)
+def test_stage0_loads(h, max_batch, shared, mpc_factory):
+    b, ref = make_case(h, shared)
+    B = b["batch"]
+    m = mpc_factory(b, max_batch=max_batch)
+    m.set_max_stance(21)
+    m.set_order_hint(0)
+    full = solve(m, b)
+    # (b) the oracle pipeline
+    err = rel_f0(full["grf"], ref)
+    bd = bound_for(_per_robot(b), err=err)
+    report(f"stage 0 loads h={h} handle={max_batch} shared={shared}", err, bd)
+    assert (err < bd).all()
+    # (a) the batch reversed, batches of 3 (the first robots, and the last ones of the buffer), batches of one
+    rev = solve(m, sub_batch(b, np.arange(B)[::-1]))
+    for k in KEYS:
+        assert np.array_equal(rev[k][::-1], full[k]), k
+    for idx in [[0, 1, 2], [B - 3, B - 2, B - 1]] + [[i] for i in range(B)]:
+        one = solve(m, sub_batch(b, idx))
+        for k in KEYS:
+            assert np.array_equal(one[k], full[k][idx]), (k, idx)
+    # (c) the order hint: the second call with the same inputs runs on the first call's counts
+    m.set_order_hint(1)
+    solve(m, b)
+    hinted = solve(m, b)
+    for k in KEYS:
+        assert np.array_equal(hinted[k], full[k]), k
+
+
+def test_commands_share_the_prologue(mpc_factory):
+    """One fused qmpc_solve_commands launch against the three calls, the 64-row class alone (trot at h = 10: 60 rows)."""
+    import torch
+    B = 65
+    cmd = W.make_commands(B, horizon=10, seed=77, omni_mode=0, stand_fraction=0.0, calm=True)
+    m = mpc_factory(_pack_setup(cmd))
+    d1 = m.upload_command(cmd)
+    rec = m.alloc_record(B)
+    o1 = m.alloc_outputs(B, full=True)
+    inp, out1 = m.make_args(rec, o1)
+    f1 = torch.empty_like(o1["grf"])
+    m.pack_async(d1, rec)
+    m.solve_async(B, inp, out1)
+    m.forces_to_body_async(B, d1["r_body"], o1["grf"], f1)
+    d2 = m.upload_command(cmd)
+    o2 = m.alloc_outputs(B, full=True)
+    _, out2 = m.make_args(rec, o2)
+    f2 = torch.empty_like(o2["grf"])
+    m.solve_commands_async(B, m.make_command_args(d2), out2, f2)
+    torch.cuda.synchronize()
+    assert ((o2["status"].cpu().numpy() & 47) == 0).all()
+    for k in ("grf", "soln", "status", "iters"):
+        assert torch.equal(o1[k], o2[k]), k
+    assert torch.equal(f1, f2)
