@@ -10,8 +10,9 @@
  * controller's gait decides which feet stand, not the ground), no slip (the force saturates, the foot stays), flat
  * ground at z = 0.  It closes the loop on the model the controller plans with; it is not a physics engine.
  * (qmpc_plant_vary.h gives each robot its own mass, inertia, friction and external pushes, and keeps per-robot
- * statistics on the device; qmpc_terrain.h puts per-robot slopes and stairs under the feet; with nothing bound in
- * either, this header is the whole description.)
+ * statistics on the device; qmpc_terrain.h puts per-robot slopes and stairs under the feet; qmpc_contact.h lifts the
+ * two limits on contact, opt-in: the ground decides which feet stand -- early and late touch-down -- and a saturated
+ * foot slips; with nothing bound or set in any of them, this header is the whole description.)
  *
  * The model, in double precision (every decision below is restated above the kernel in csrc/qmpc_plant.hip and in
  * tests/plant_model.py, which makes the same choices operation by operation):

@@ -105,6 +105,20 @@ class TerrainView(C.Structure):
 TERRAIN_CLAMP_SWING, TERRAIN_REBASE_Z = 1, 2
 
 
+class ContactParams(C.Structure):
+    """qmpc_contact_params (include/qmpc_contact.h)."""
+    _fields_ = [("flags", C.c_int), ("drop_speed", C.c_double), ("slip_gain", C.c_double), ("slip_vmax", C.c_double)]
+
+
+class ContactView(C.Structure):
+    """qmpc_contact_view (include/qmpc_contact.h)."""
+    _fields_ = [("early", C.c_void_p), ("late", C.c_void_p), ("slip", C.c_void_p), ("drop", C.c_void_p),
+                ("params", ContactParams), ("batch", C.c_int)]
+
+
+CONTACT_EARLY, CONTACT_LATE, CONTACT_SLIP = 1, 2, 4
+
+
 class PlantStats(C.Structure):
     """qmpc_plant_stats (include/qmpc_plant_vary.h)."""
     _fields_ = [(n, C.c_void_p) for n in PLANT_STATS_FIELDS] + [("batch", C.c_int), ("enabled", C.c_int)]
@@ -242,6 +256,11 @@ TERRAIN_SIGNATURES = {
     "qmpc_plant_set_terrain": [_P, _I, _P, _I],
     "qmpc_terrain_view_get": [_P, C.POINTER(TerrainView)],
 }
+# contact decided by the ground under the plant (include/qmpc_contact.h), same library and ABI version
+CONTACT_SIGNATURES = {
+    "qmpc_plant_set_contact": [_P, _I, C.POINTER(ContactParams)],
+    "qmpc_contact_view_get": [_P, C.POINTER(ContactView)],
+}
 # the sensor model between the plant and the controller's sensor path (include/qmpc_sense.h), same library and ABI version
 SENSE_SIGNATURES = {
     "qmpc_sense_init": [_P, _I, C.c_uint64, _P],
@@ -256,6 +275,7 @@ PLANT_EXPORTS = list(PLANT_SIGNATURES)
 PLANT_VARY_EXPORTS = list(PLANT_VARY_SIGNATURES)
 SENSE_EXPORTS = list(SENSE_SIGNATURES)
 TERRAIN_EXPORTS = list(TERRAIN_SIGNATURES)
+CONTACT_EXPORTS = list(CONTACT_SIGNATURES)
 
 _lib = None
 
@@ -290,7 +310,7 @@ def load_library():
                 "(python -c 'import __graft_entry__ as g; g.build()')")
         lib = C.CDLL(LIB_PATH)
         for name, sig in {**SIGNATURES, **CTRL_SIGNATURES, **PLANT_SIGNATURES, **PLANT_VARY_SIGNATURES, **TERRAIN_SIGNATURES,
-                          **SENSE_SIGNATURES}.items():
+                          **CONTACT_SIGNATURES, **SENSE_SIGNATURES}.items():
             f = getattr(lib, name)
             f.argtypes, f.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
         _lib = lib
@@ -956,6 +976,34 @@ class BatchedPlant:
         res = self.ctrl._views("qmpc_terrain_view_get", TerrainView, dict(ground=(None, "<f8"), support=(None, "<f8")),
                                ("terrain", "flags", "batch"))
         res["bound"] = bool(res.pop("terrain"))
+        return res
+
+    # -- include/qmpc_contact.h ----------------------------------------------------------------------------------------
+    def set_contact(self, early=False, late=False, slip=False, drop_speed=1.0, slip_gain=0.01, slip_vmax=1.0):
+        """Contact decided by the ground under the PLANT (the controller is not told), with or without terrain bound:
+        `early` pins a swing foot that meets the surface, `late` leaves a foot scheduled to stand in the air until it
+        lands (lowered at drop_speed m/s), `slip` lets a foot whose force leaves the friction cone slide at slip_gain m/s
+        per newton of excess, capped at slip_vmax.  The defaults are modelling choices, not measurements.  Host state
+        only; all three False, or set_contact(None), switches it off.  init() switches it off, reset() keeps it and
+        zeroes the masked robots' counters.  With contact on the plant view's `stance` is the physical pinned flag."""
+        if self.batch is None:
+            raise QmpcError("qmpc_plant_set_contact before init()")
+        if early is None:
+            self.ctrl._call("qmpc_plant_set_contact", self.batch, None)
+            return
+        flags = (CONTACT_EARLY if early else 0) | (CONTACT_LATE if late else 0) | (CONTACT_SLIP if slip else 0)
+        prm = ContactParams(flags, float(drop_speed), float(slip_gain), float(slip_vmax))
+        self.ctrl._call("qmpc_plant_set_contact", self.batch, C.byref(prm))
+
+    def contact(self):
+        """qmpc_contact_view_get as zero-copy device tensors that alias the plant's arrays, like terrain(): early, late
+        ([B] int32, foot-ticks), slip ([B] float64, metres), drop ([B, 4] float64); plus flags, drop_speed, slip_gain,
+        slip_vmax and batch.  Read-only by contract."""
+        res = self.ctrl._views("qmpc_contact_view_get", ContactView,
+                               dict(early=(None, "<i4"), late=(None, "<i4"), slip=(None, "<f8"), drop=(4, "<f8")),
+                               ("params", "batch"))
+        prm = res.pop("params")
+        res.update(flags=prm.flags, drop_speed=prm.drop_speed, slip_gain=prm.slip_gain, slip_vmax=prm.slip_vmax)
         return res
 
 

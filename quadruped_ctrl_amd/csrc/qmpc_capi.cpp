@@ -23,6 +23,7 @@
 #include "../../include/qmpc_plant.h"   // reduced-order plant for it (same library)
 #include "../../include/qmpc_plant_vary.h"  // ... its per-robot parameters and on-device statistics
 #include "../../include/qmpc_terrain.h"  // ... its per-robot slopes and stairs
+#include "../../include/qmpc_contact.h"  // ... contact decided by the ground
 #include "../../include/qmpc_sense.h"   // sensor model between the plant and the controller's sensor path
 #include "qmpc_device.h"
 #include "qmpc_glue.h"    // each launcher is declared once, in the header its defining file includes too:
@@ -221,6 +222,11 @@ struct __attribute__((visibility("hidden"))) qmpc_ctx {
     // qmpc_terrain.h: the caller's rows as bound (null: flat ground) and the flags; ground[max_batch], support[max_batch]
     QmpcTerrainArgs terrain{};
     DevBuf<double> terrain_buf;
+    // qmpc_contact.h: the flags and scalars as set (flags 0: off); slip[max_batch], drop[max_batch][4], early[max_batch],
+    // late[max_batch] in one allocation; whether a contact step has written them since they were last all zero
+    QmpcContactArgs contact{};
+    DevBuf<double> contact_buf;
+    bool contact_dirty = false;
   };
   std::unique_ptr<Plant> plant;
   // sensor model (qmpc_sense.h): the counters n[max_batch], epoch[max_batch] in one allocation made by qmpc_sense_init,
@@ -1521,9 +1527,28 @@ int qmpc_plant_init(qmpc_handle c, int batch, double mu_plant, int substeps, con
     k->terrain.ground = k->terrain_buf.p;
     k->terrain.support = k->terrain_buf.p + c->max_batch;
   }
+  if (!k->contact_buf) {
+    // slip[M], drop[M][4] (double), early[M], late[M] (int32) of qmpc_contact.h, zero (first use only)
+    const size_t M = (size_t)c->max_batch;
+    DevBuf<double> buf;
+    HIP_TRY(c, buf.alloc(6 * M));
+    const hipError_t e = hipMemset(buf, 0, 6 * sizeof(double) * M);
+    if (e != hipSuccess) return fail(c, e, "hipMemset(plant contact)");
+    k->contact_buf = std::move(buf);
+    k->contact.slip = k->contact_buf.p;
+    k->contact.drop = k->contact_buf.p + M;
+    k->contact.early = reinterpret_cast<int32_t*>(k->contact_buf.p + 5 * M);
+    k->contact.late = k->contact.early + M;
+  }
   if (const int rc = order_after_previous(c, stream)) return rc;
   const QmpcPlantConst K = plant_const(c, mu_plant, substeps);
   HIP_TRY(c, qmpc_launch_plant_init(&k->d, &K, nullptr, init_xyyaw, batch, stream));
+  if (k->contact_dirty) {
+    // a plant that stepped with contact on starts again with its counters at zero (no other plant launches this)
+    const QmpcTerrainArgs flat{nullptr, k->terrain.ground, k->terrain.support, 0};
+    HIP_TRY(c, qmpc_launch_contact_reset(nullptr, c->max_batch, stream, &flat, &k->contact));
+    k->contact_dirty = false;
+  }
   k->batch = batch;
   k->mu = mu_plant;
   k->substeps = substeps;
@@ -1532,6 +1557,7 @@ int qmpc_plant_init(qmpc_handle c, int batch, double mu_plant, int substeps, con
   k->bound = false;
   k->terrain.rows = nullptr;  // ... and stands on flat ground
   k->terrain.flags = 0;
+  k->contact.flags = 0;       // ... with scheduled contact
   return QMPC_OK;
 }
 
@@ -1546,6 +1572,7 @@ int qmpc_plant_reset(qmpc_handle c, int batch, const uint8_t* mask_dev, const do
     HIP_TRY(c, qmpc_launch_terrain_init(&k->d, &K, mask_dev, init_xyyaw, batch, q.stream, &k->terrain));
   else
     HIP_TRY(c, qmpc_launch_plant_init(&k->d, &K, mask_dev, init_xyyaw, batch, q.stream));
+  if (k->contact.flags) HIP_TRY(c, qmpc_launch_contact_reset(mask_dev, batch, q.stream, &k->terrain, &k->contact));
   return QMPC_OK;
 }
 
@@ -1558,9 +1585,15 @@ int qmpc_plant_step(qmpc_handle c, int batch, const double* effort, double* stat
   const QmpcCtrlDev& d = c->ctrl->d;
   const QmpcPlantConst K = plant_const(c, c->plant->mu, c->plant->substeps);
   // nothing bound and the statistics off: the plain instantiation, which is given no QmpcPlantVary to read
-  const qmpc_ctx::Plant* k = c->plant.get();
+  qmpc_ctx::Plant* k = c->plant.get();
   const bool extra = k->bound || k->stats_on;
-  if (k->terrain.rows)
+  if (k->contact.flags) {
+    k->contact.dt = 1.0 / c->ctrl->freq;
+    k->contact_dirty = true;
+    HIP_TRY(c, qmpc_launch_contact_step(&k->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out,
+                                        batch, q.stream, extra ? &k->vary : nullptr, k->bound, k->stats_on, &k->terrain,
+                                        &k->contact));
+  } else if (k->terrain.rows)
     HIP_TRY(c, qmpc_launch_terrain_step(&k->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out,
                                         batch, q.stream, extra ? &k->vary : nullptr, k->bound, k->stats_on, &k->terrain));
   else
@@ -1675,6 +1708,41 @@ int qmpc_terrain_view_get(qmpc_handle c, qmpc_terrain_view* v) {
   v->support = k->terrain.support;
   v->terrain = k->terrain.rows;
   v->flags = k->terrain.flags;
+  v->batch = k->batch;
+  return QMPC_OK;
+}
+
+// ---- include/qmpc_contact.h: contact decided by the ground ----
+
+int qmpc_plant_set_contact(qmpc_handle c, int batch, const qmpc_contact_params* prm) {
+  if (const int rc = plant_check(c, batch)) return rc;
+  qmpc_ctx::Plant* k = c->plant.get();
+  if (!prm || prm->flags == 0) {
+    k->contact.flags = 0;
+    return QMPC_OK;
+  }
+  if (prm->flags & ~(QMPC_CONTACT_EARLY | QMPC_CONTACT_LATE | QMPC_CONTACT_SLIP)) return QMPC_ERR_ARG;
+  for (const double x : {prm->drop_speed, prm->slip_gain, prm->slip_vmax})
+    if (!std::isfinite(x) || !(x >= 0)) return QMPC_ERR_ARG;
+  k->contact.flags = prm->flags;
+  k->contact.drop_speed = prm->drop_speed;
+  k->contact.slip_gain = prm->slip_gain;
+  k->contact.slip_vmax = prm->slip_vmax;
+  return QMPC_OK;
+}
+
+int qmpc_contact_view_get(qmpc_handle c, qmpc_contact_view* v) {
+  if (!c || !v) return QMPC_ERR_ARG;
+  if (!plant_ready(c)) return QMPC_ERR_STATE;
+  const qmpc_ctx::Plant* k = c->plant.get();
+  v->early = k->contact.early;
+  v->late = k->contact.late;
+  v->slip = k->contact.slip;
+  v->drop = k->contact.drop;
+  v->params.flags = k->contact.flags;
+  v->params.drop_speed = k->contact.drop_speed;
+  v->params.slip_gain = k->contact.slip_gain;
+  v->params.slip_vmax = k->contact.slip_vmax;
   v->batch = k->batch;
   return QMPC_OK;
 }

@@ -62,6 +62,17 @@ struct QmpcTerrainArgs {
   int flags;           // QMPC_TERRAIN_*
 };
 
+// include/qmpc_contact.h: the flags and scalars as set (flags 0: off, the kernels of qmpc_plant.hip / qmpc_terrain.hip), dt =
+// 1 / freq, and the plant's counters (one allocation made by qmpc_plant_init for max_batch robots).  By value.
+struct QmpcContactArgs {
+  double drop_speed, slip_gain, slip_vmax, dt;
+  int32_t* early;  // [B] foot-ticks pinned while scheduled to swing
+  int32_t* late;   // [B] foot-ticks unpinned while scheduled to stand
+  double* slip;    // [B] metres slid
+  double* drop;    // [B][4] how far a late foot has been lowered
+  int flags;       // QMPC_CONTACT_*
+};
+
 #define QMPC_PLANT_GRAVITY 9.81
 #define QMPC_PLANT_HEIGHT 0.29      /* ConvexMPCLocomotion::_body_height */
 #define QMPC_PLANT_SIDE_OFFSET 0.065
@@ -88,5 +99,14 @@ extern "C" hipError_t qmpc_launch_terrain_step(const QmpcPlantDev* S, const Qmpc
                                                const float* contact_state, const float* p_des, const float* v_des,
                                                double* state_out, double* motor_out, int batch, hipStream_t stream,
                                                const QmpcPlantVary* V, int vary, int stats, const QmpcTerrainArgs* T);
+// ... and of qmpc_contact.hip, which capi picks while contact flags are set: the step on any ground (T->rows may be
+// null: height 0, normal (0, 0, 1)) and the reset of the counters, enqueued after the plant's or the terrain's own reset.
+extern "C" hipError_t qmpc_launch_contact_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
+                                               const float* contact_state, const float* p_des, const float* v_des,
+                                               double* state_out, double* motor_out, int batch, hipStream_t stream,
+                                               const QmpcPlantVary* V, int vary, int stats, const QmpcTerrainArgs* T,
+                                               const QmpcContactArgs* C);
+extern "C" hipError_t qmpc_launch_contact_reset(const uint8_t* mask, int batch, hipStream_t stream,
+                                                const QmpcTerrainArgs* T, const QmpcContactArgs* C);
 
 #endif

@@ -31,6 +31,9 @@ four treads of 0.1 m x 0.04 m up, a cross slope of 0.15, the same treads down, 0
 each robot along its start yaw), with swing feet clamped to the surface and, for --source plant, the state row's height
 re-based on the stance feet; the robots are reset onto their ground first.  The step then runs the terrain kernels of
 csrc/qmpc_terrain.hip (with --vary: their <VARY, STATS> instantiation).
+--contact lets the ground decide contact (include/qmpc_contact.h: early and late touch-down and slip, the binding's default
+parameters), on flat ground or with --terrain on its ground: the step then runs the kernels of csrc/qmpc_contact.hip; the
+counters are reported.
 
 --source sensor closes the same loop through the SENSOR path: qmpc_ctrl_tick -- the VectorNav orientation estimator and
 the Kalman filter -- on the readings of the sensor model (include/qmpc_sense.h), qmpc_plant_step on the tick's efforts,
@@ -41,7 +44,7 @@ accelerometer and gyro biases (within +-0.2 m/s^2, +-0.02 rad/s) and white noise
 0.002 rad and 0.05 rad/s: the levels the closed-loop tests walk on); without it the sensors are ideal.
 
     python tools/ctrl_bench.py [--batches 1024,4096,16384] [--cycles 8] [--warmup 26] [--schedule lockstep|per_robot]
-                               [--stagger] [--robot-mode 0|1] [--source imu|state|plant|sensor] [--vary] [--terrain] [--noise]
+                               [--stagger] [--robot-mode 0|1] [--source imu|state|plant|sensor] [--vary] [--terrain] [--contact] [--noise]
                                [--out FILE]
 """
 import argparse
@@ -55,7 +58,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, source="imu", vary=False, noise=False, terrain=False):
+def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, source="imu", vary=False, noise=False, terrain=False,
+        contact=False):
     import torch
     from quadruped_ctrl_amd import workloads as W
     from quadruped_ctrl_amd.binding import BatchedController
@@ -113,6 +117,8 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
             rows = torch.from_numpy(rows).cuda()
             plant.set_terrain(rows, clamp_swing=True, rebase_z=source == "plant")
             plant.reset(torch.ones(B, dtype=torch.bool, device="cuda"), torch.from_numpy(xyyaw).cuda())
+        if contact:
+            plant.set_contact(early=True, late=True, slip=True)
         imu, motor = plant.state.expand(26, B, 16), plant.motor.expand(26, B, 24)    # (every "slot" is the plant's read-out)
         tick = ctrl.tick_state
         if source == "sensor":
@@ -181,6 +187,10 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
         t_ = plant.terrain()
         res.update({"terrain": True, "support_min": round(float(t_["support"].min().item()), 4),
                     "support_max": round(float(t_["support"].max().item()), 4)})
+    if contact:
+        c_ = plant.contact()
+        res.update({"contact": True, "early_foot_ticks": int(c_["early"].sum().item()), "late_foot_ticks": int(c_["late"].sum().item()),
+                    "slip_m": round(float(c_["slip"].sum().item()), 4)})
     if stagger or robot_mode == 1:
         res["robot_ticks_per_s"] = res["robot_ticks_per_s_window"]
         if robot_mode == 1:
@@ -213,6 +223,7 @@ def main():
     ap.add_argument("--source", choices=("imu", "state", "plant", "sensor"), default="imu")
     ap.add_argument("--vary", action="store_true")
     ap.add_argument("--terrain", action="store_true")
+    ap.add_argument("--contact", action="store_true")
     ap.add_argument("--noise", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -220,6 +231,8 @@ def main():
         ap.error("--vary needs --source plant or sensor")
     if a.terrain and a.source not in ("plant", "sensor"):
         ap.error("--terrain needs --source plant or sensor")
+    if a.contact and a.source not in ("plant", "sensor"):
+        ap.error("--contact needs --source plant or sensor")
     if a.noise and a.source != "sensor":
         ap.error("--noise needs --source sensor")
     if a.robot_mode == 1:
@@ -228,7 +241,7 @@ def main():
         ap.error("--stagger needs --schedule per_robot (a lockstep reset keeps the robot on the batch's MPC ticks)")
     out = []
     for B in [int(x) for x in a.batches.split(",")]:
-        r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source, a.vary, a.noise, a.terrain)
+        r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source, a.vary, a.noise, a.terrain, a.contact)
         print(json.dumps(r), flush=True)
         out.append(r)
     if a.out:
