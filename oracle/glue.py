@@ -83,3 +83,10 @@ def kf_step(xhat, P, r_body, a_world, omega_body, contact, leg_p, leg_v):
     pos, vw, vb = (np.zeros((B, 3), np.float32) for _ in range(3))
     lib().oracle_kf_step_batch(_p(HIP), C.c_int(B), _p(xhat), _p(P), *[_p(x) for x in a], _p(pos), _p(vw), _p(vb))
     return pos, vw, vb
+
+
+def kf_counters(reset=False):
+    """(row swaps, pivot searches with a tie for the largest magnitude) of every kf_step since the last reset."""
+    out = (C.c_int * 2)()
+    lib().oracle_kf_counters(out, C.c_int(1 if reset else 0))
+    return int(out[0]), int(out[1])

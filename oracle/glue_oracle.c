@@ -165,6 +165,16 @@ void oracle_swing_batch(int n, const float* p0, const float* pf, const float* he
 #define KF_N 18
 #define KF_M 28
 
+/* Test-side counters of the pivot search below, summed over every oracle_kf_step since the last reset: [0] row swaps,
+ * [1] pivot searches in which a second row has exactly the pivot's magnitude (a tie: "first largest wins" decides).
+ * They read the matrix only; the arithmetic does not depend on them. */
+static int kf_counters[2];
+void oracle_kf_counters(int out[2], int reset) {
+  out[0] = kf_counters[0];
+  out[1] = kf_counters[1];
+  if (reset) kf_counters[0] = kf_counters[1] = 0;
+}
+
 static float kf_q_process(int k, float dt) { /* run() :73-76 with _Q0 of setup() :56-60 */
   const float process_noise_pimu = 0.02f, process_noise_vimu = 0.02f, process_noise_pfoot = 0.002f;
   if (k < 3) return (dt / 20.f) * process_noise_pimu;
@@ -266,12 +276,19 @@ void oracle_kf_step(const float hip[3], float xhat[KF_N], float P[KF_N * KF_N], 
         best = fabsf(Saug[r * W + k]);
         piv = r;
       }
-    if (piv != k)
+    for (int r = k; r < KF_M; r++)
+      if (r != piv && fabsf(Saug[r * W + k]) == best) {
+        kf_counters[1]++;
+        break;
+      }
+    if (piv != k) {
+      kf_counters[0]++;
       for (int c = 0; c < W; c++) {
         const float t = Saug[k * W + c];
         Saug[k * W + c] = Saug[piv * W + c];
         Saug[piv * W + c] = t;
       }
+    }
     for (int r = k + 1; r < KF_M; r++) {
       const float l = Saug[r * W + k] / Saug[k * W + k];
       for (int c = k + 1; c < W; c++) Saug[r * W + c] = Saug[r * W + c] - l * Saug[k * W + c];

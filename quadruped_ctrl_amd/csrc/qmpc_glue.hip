@@ -387,7 +387,9 @@ __device__ __forceinline__ void qmpc_mat3_mul(const float* A, const float* B, fl
 __device__ __forceinline__ void qmpc_quat_to_rpy(const float* q, float* rpy) {
 #pragma clang fp contract(off)
   const double m = -2. * (double)(q[1] * q[3] - q[0] * q[2]);
-  const float as = (float)(m < .99999 ? m : .99999);  // std::min(double, double)
+  // std::min(m, .99999) in its operand order, (b < a) ? b : a: a NaN m (NaN quaternion) stays NaN, so that rpy is NaN and
+  // the orientation check, abs(NaN) >= 0.5, does not latch -- as in the reference
+  const float as = (float)(.99999 < m ? .99999 : m);
   rpy[2] = atan2f(2 * (q[1] * q[2] + q[0] * q[3]), ((q[0] * q[0] + q[1] * q[1]) - q[2] * q[2]) - q[3] * q[3]);
   rpy[1] = asinf(as);
   rpy[0] = atan2f(2 * (q[2] * q[3] + q[0] * q[1]), ((q[0] * q[0] - q[1] * q[1]) - q[2] * q[2]) + q[3] * q[3]);
