@@ -639,7 +639,8 @@ struct Smem {
 
 // phase timestamps (profiling hook; dbg_clk == nullptr in production)
 #ifndef QMPC_DBG_ITER
-#define QMPC_DBG_ITER 0  // the event-engine iteration the stamps 8 / 9 / 10 are taken in (> 0: stamp 14 = its start; tools/iter_phase.py)
+#define QMPC_DBG_ITER 0  // > 0 (a profiling build, tools/build_variant.sh): the event-engine iteration whose phases are stamped -- 14 = its
+                         // start, 8 / 15 / 9 inside, 10 = its end (tools/iter_phase.py).  0, production: the iteration carries no stamp
 #endif
 // fine-grained stamps inside the FIRST active-set iteration
 #define QMPC_TICK1(k)                                                \
@@ -2646,39 +2647,54 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     // z -= +-y z~ , r += y g~ with y = z~^T c_p over the stored events, four (TR) per trip; rows past the last event of
     // a trip are zero.  Wave w of nw takes the trips w, w + nw, ... of the add events (front of the pool, DIR = +1)
     // and then of the drop events (back of the pool, DIR = -1)
+    // One trip in its two halves, so that a caller can issue a trip's loads ahead of the arithmetic in front of it: the
+    // loads of the TR records from ev on (DIR = +1 / -1: towards higher / lower records) ...
+    auto trip_load = [&](auto dirc, const auto ev, int oj1, int oj2, auto& ya, auto& yb, auto& zl, auto& gl) __attribute__((always_inline)) {
+      constexpr int DIR = decltype(dirc)::value;
+      constexpr int TR = (int)std::extent<std::remove_reference_t<decltype(ya)>>::value;
+#pragma unroll
+      for (int u = 0; u < TR; ++u) {
+        const auto eu = ev + DIR * u * EV;
+        ya[u] = eu[oj1];
+        yb[u] = eu[oj2];
+        rec_load(eu, zl[u], gl[u]);
+      }
+    };
+    // ... and their share of z and r, record by record in the order they were loaded
+    auto trip_acc = [&](auto dirc, double pa1, double pa2, const auto& ya, const auto& yb, const auto& zl, const auto& gl,
+                        double (&z)[RE], double (&rw)[KQ]) __attribute__((always_inline)) {
+      constexpr int DIR = decltype(dirc)::value;
+      constexpr int TR = (int)std::extent<std::remove_reference_t<decltype(ya)>>::value;
+#pragma unroll
+      for (int u = 0; u < TR; ++u) {
+        const double y = __builtin_fma(pa2, yb[u], pa1 * ya[u]);
+#pragma unroll
+        for (int q = 0; q < RE; ++q) z[q] = __builtin_fma(DIR > 0 ? -y : y, zl[u][q], z[q]);
+#pragma unroll
+        for (int k = 0; k < KQ; ++k) rw[k] = __builtin_fma(y, gl[u][k], rw[k]);
+      }
+    };
+    // (`done`: add events from the front of the pool the caller has accumulated already -- 0, or one trip's TR when it
+    //  issued the first trip's loads itself, nw = 1)
     auto ev_part = [&](auto gpc, const auto pool, int pj1, int pj2, double pa1, double pa2, int neva, int nevd, int w, int nw,
-                       double (&z)[RE], double (&rw)[KQ]) __attribute__((always_inline)) {
+                       int done, double (&z)[RE], double (&rw)[KQ]) __attribute__((always_inline)) {
       constexpr bool GPOOL = decltype(gpc)::value;
       constexpr int KEV = GPOOL ? KEV_G : KEV_L, TR = GPOOL ? TR_G : 4;
       const int oj1 = off_z(pj1), oj2 = off_z(pj2);
-      auto part = [&](auto dirc, int base, int cnt, int w0) __attribute__((always_inline)) {
+      auto part = [&](auto dirc, int base, int cnt, int first) __attribute__((always_inline)) {
         constexpr int DIR = decltype(dirc)::value;
 #pragma unroll 1
-        for (int t0 = TR * w0; t0 < cnt; t0 += TR * nw) {
-          const auto ev = pool + (base + DIR * t0) * EV;
+        for (int t0 = first; t0 < cnt; t0 += TR * nw) {
           double ya[TR], yb[TR], zl[TR][RE], gl[TR][KQ];
-#pragma unroll
-          for (int u = 0; u < TR; ++u) {
-            const auto eu = ev + DIR * u * EV;
-            ya[u] = eu[oj1];
-            yb[u] = eu[oj2];
-            rec_load(eu, zl[u], gl[u]);
-          }
-#pragma unroll
-          for (int u = 0; u < TR; ++u) {
-            const double y = __builtin_fma(pa2, yb[u], pa1 * ya[u]);
-#pragma unroll
-            for (int q = 0; q < RE; ++q) z[q] = __builtin_fma(DIR > 0 ? -y : y, zl[u][q], z[q]);
-#pragma unroll
-            for (int k = 0; k < KQ; ++k) rw[k] = __builtin_fma(y, gl[u][k], rw[k]);
-          }
+          trip_load(dirc, pool + (base + DIR * t0) * EV, oj1, oj2, ya, yb, zl, gl);
+          trip_acc(dirc, pa1, pa2, ya, yb, zl, gl, z, rw);
         }
       };
-      part(std::integral_constant<int, 1>{}, 0, neva, w);
+      part(std::integral_constant<int, 1>{}, 0, neva, TR * w + done);
       if (nevd > 0) {
         // (the drop trips continue the round-robin where the add trips stopped)
         const int ta = (neva + TR - 1) / TR;
-        part(std::integral_constant<int, -1>{}, KEV - 1, nevd, nw == 1 ? 0 : (w + nw - ta % nw) % nw);
+        part(std::integral_constant<int, -1>{}, KEV - 1, nevd, TR * (nw == 1 ? 0 : (w + nw - ta % nw) % nw));
       }
     };
     if (engine) {
@@ -2741,7 +2757,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
 #pragma unroll
         for (int q = 0; q < RE; ++q) {
           const double cand = __shfl(v[q], j & 63);
-          if ((j >> 6) == q) out = cand;
+          if (RE == 1 || (j >> 6) == q) out = cand;  // (one block of rows: every index the callers ask for is below 64)
         }
         return out;
       };
@@ -2749,10 +2765,16 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
         return lane_elem<RE>(v, j);
       };
       // element (row = lane + 64 q, column j) of H^-1 for a wave-uniform j
+      // (one select between the two addresses, and the load outside every lane mask: both addresses lie inside the packed
+      //  triangle for every row < NP and column < NP, whatever the robot's n, so the rows past n load too -- and drop what
+      //  they loaded; only a class whose last block of 64 rows reaches past NP keeps those rows on an address that exists)
       auto Hcol = [&](int q, int j) __attribute__((always_inline)) {
         const int row = lane + 64 * q;
-        const int tj = j * (j + 1) / 2;
-        return Sb.Hp[(j <= row) ? rbl[q] + j : tj + row];
+        const int tj = __builtin_amdgcn_readfirstlane(j * (j + 1) / 2);
+        const int lo = rbl[q] + j, up = tj + row;
+        int idx = (j <= row) ? lo : up;
+        if (64 * q + 63 >= NP) idx = (row < NP) ? idx : 0;
+        return Sb.Hp[idx];
       };
       // 1/sqrt(d), d > 0, to full double precision: v_rsq_f64 seed + two Newton steps
       auto rsqrt_full = [&](double d) __attribute__((always_inline)) {
@@ -2772,6 +2794,25 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
         constexpr int TR = GPOOL ? TR_G : 4;  // events per trip of the accumulation loops
         // (locals, not captures: a flag that nested lambdas reach through two closures ends up in scratch)
         bool need_p = need_p0, retry = false;
+        // this stance lane's three entries of x for the search, taken where x is written and a search follows -- on entry,
+        // behind a full step (in front of the event it builds, so that the next trip does not start with a wait for the
+        // gather) and behind a warm start's repair -- and carried to the trip that searches.  A partial step does not
+        // search next: the same constraint is tried again, and the full step that ends the run of partial ones gathers
+        constexpr int SEARCH_LIVE = (NP / 3 <= 32) ? 32 : 64;  // stance lanes a robot of this class can have (3 nst <= NP)
+        const int xg_j0 = 3 * (lane < nst ? lane : 0);
+        // (CARRY: the classes of one block of rows, whose gather is three plain lane reads; with more blocks every read
+        //  is followed by a select that waits for it, and the three values cost registers those classes do not have: their
+        //  search gathers for itself, as before)
+        constexpr bool CARRY = (RE == 1);
+        double xg0 = 0.0, xg1 = 0.0, xg2 = 0.0;
+        auto xgather = [&]() __attribute__((always_inline)) {
+          if constexpr (CARRY) {
+            xg0 = gather(xv, xg_j0);
+            xg1 = gather(xv, xg_j0 + 1);
+            xg2 = gather(xv, xg_j0 + 2);
+          }
+        };
+        xgather();
         const auto pool = [&]() __attribute__((always_inline)) {
           if constexpr (GPOOL) return gpool; else return (double*)Sb.Sinv;
         }();
@@ -2837,6 +2878,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
             for (int q = 0; q < RE; ++q) xv[q] = __builtin_fma(-coef, u[q], xv[q]);
 #pragma unroll
             for (int k = 0; k < KQ; ++k) lam[k] = __builtin_fma(-coef, sc[k], lam[k]);
+            xgather();
           }
           const double sg = rsqrt_full(gamma);
           const int de = lane_elem<KQ>(wcid, l);
@@ -2877,6 +2919,11 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
           pty = __builtin_amdgcn_readfirstlane(pty);
           pj1 = __builtin_amdgcn_readfirstlane(pj1);
           pj2 = __builtin_amdgcn_readfirstlane(pj2);
+          if constexpr (!GPOOL) asm volatile("; qmpc iter top");  // (markers: tools/engine_iter_shape.py)
+          // The carried gather (and the event's LDS stores behind it) land HERE on every path: the trip that searches needs
+          // them at once anyway, and a trip that does not has none in flight.  Left to the compiler, the wait comes back
+          // between the column loads and the event loads below (a register of the gather is reused there): s_waitcnt lgkmcnt(0)
+          if constexpr (CARRY) __builtin_amdgcn_s_waitcnt(0xC07F);
           if (QMPC_DBG_ITER > 0 && dbg_clk && lane == 0 && iters == QMPC_DBG_ITER) dbg_clk[14] = clock64();
           // ---- room for one more event of either kind?  Checked here, between iterations, where the state is
           // consistent.  LDS pool: no -> leave the loop, the events move to this robot's slice of the overflow pool
@@ -2953,8 +3000,8 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
           if (uni(need_p)) {
             // ---- most violated constraint outside the working set (normalised), or done
             unsigned key = 0;
-            const int j0 = 3 * (lane < nst ? lane : 0);
-            const double x0 = gather(xv, j0), x1 = gather(xv, j0 + 1), x2 = gather(xv, j0 + 2);
+            const double x0 = CARRY ? xg0 : gather(xv, xg_j0), x1 = CARRY ? xg1 : gather(xv, xg_j0 + 1),
+                         x2 = CARRY ? xg2 : gather(xv, xg_j0 + 2);
             if (lane < nst) {
               const double fx = mi * x0, fy = mi * x1;
               double vmin = 0.0;
@@ -2968,7 +3015,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
               }
               if (vmin < -tol) key = (__float_as_uint((float)(-vmin)) & ~0x1FFu) | (unsigned)(5 * lane + tmin);
             }
-            const unsigned best = wave_max_u32(key);
+            const unsigned best = wave_max_u32_first<SEARCH_LIVE>(key);  // (key = 0 from lane nst on)
             if (best == 0u) break;
             if (iters >= max_iter) {
               status |= QMPC_DEV_ST_MAXITER;
@@ -2984,18 +3031,40 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
             forced = false;
           }
           }  // (!rebuild)
-          if (dbg_clk && lane == 0 && iters == QMPC_DBG_ITER) dbg_clk[8] = clock64();
+          if (QMPC_DBG_ITER > 0 && dbg_clk && lane == 0 && iters == QMPC_DBG_ITER) dbg_clk[8] = clock64();
           // ---- z = P c_p (index-major lanes), r = N*^T c_p (slot lanes)
-          double z[RE];
+          // Everything this needs from memory depends on the constraint alone (pj1, pj2), not on z: the two columns of
+          // H^-1, the two diagonal entries of cn and the first trip over the stored events (the four records at the
+          // front of the pool exist in every pool; past the last event they read zero or are not used) are issued
+          // together, so that the wave waits for LDS once.  The helper waves' split keeps its own order of loads, and so
+          // do the classes of more than one block of rows (PEEL = false): a trip's records next to the columns do not
+          // fit their register budget
+          constexpr bool PEEL = C::C1;
+          bool helped = false;
+          if constexpr (NHELP > 0) helped = (neva + TR - 1) / TR + (nevd + TR - 1) / TR >= C::HELP_MIN_TRIPS;
+          double z[RE], hc1[RE], hc2[RE];
+          if constexpr (!GPOOL) asm volatile("; qmpc iter hcol begin");
+#pragma unroll
+          for (int q = 0; q < RE; ++q) {
+            hc1[q] = Hcol(q, pj1);
+            hc2[q] = Hcol(q, pj2);
+          }
+          if constexpr (!GPOOL) asm volatile("; qmpc iter hcol end");
+          const double hd1 = Sb.Hp[pj1 * (pj1 + 3) / 2], hd2 = Sb.Hp[pj2 * (pj2 + 3) / 2];  // diag(H^-1)
+          pool_sync();
+          double ya0[TR], yb0[TR], zl0[TR][RE], gl0[TR][KQ];
+          if constexpr (PEEL) {
+            if (!helped) trip_load(std::integral_constant<int, 1>{}, pool, off_z(pj1), off_z(pj2), ya0, yb0, zl0, gl0);
+            __builtin_amdgcn_sched_barrier(0);  // (every load above is issued before the first is used)
+          }
 #pragma unroll
           for (int q = 0; q < RE; ++q) {
             const int row = lane + 64 * q;
-            z[q] = (row < n) ? __builtin_fma(pa2, Hcol(q, pj2), pa1 * Hcol(q, pj1)) : 0.0;
+            z[q] = (row < n) ? __builtin_fma(pa2, hc2[q], pa1 * hc1[q]) : 0.0;
           }
           double rw[KQ];
 #pragma unroll
           for (int k = 0; k < KQ; ++k) rw[k] = 0.0;
-          pool_sync();
           if (QMPC_DBG_ITER > 0 && dbg_clk && lane == 0 && iters == QMPC_DBG_ITER) {
             double zs = 0.0;  // (the stamp waits for z)
 #pragma unroll
@@ -3006,12 +3075,10 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
           // (measured, not kept: computing every event's y first -- one lane per event -- and streaming the rows
           //  afterwards saves two loads and two multiply-adds per event; +5 % for the 128-row class, -1 % for the
           //  64- and 96-row classes whose robots hold few events)
-          bool helped = false;
           if constexpr (NHELP > 0) {
             // enough events for two barriers to pay: waves 1..NHELP take their share (fixed split, fixed order of the
             // final sum: the result does not depend on timing)
-            if ((neva + TR - 1) / TR + (nevd + TR - 1) / TR >= C::HELP_MIN_TRIPS) {
-              helped = true;
+            if (helped) {
               if (lane == 0) {
                 S.hd.cmd = 1;
                 S.hd.pj1 = pj1;
@@ -3024,7 +3091,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
                 if constexpr (GPOOL) S.hd.gptr = (unsigned long long)(size_t)pool;
               }
               __syncthreads();  // (A) the request is up (and, global pool: this wave's event stores are drained)
-              ev_part(gpc, pool, pj1, pj2, pa1, pa2, neva, nevd, 0, NHELP + 1, z, rw);
+              ev_part(gpc, pool, pj1, pj2, pa1, pa2, neva, nevd, 0, NHELP + 1, 0, z, rw);
               __syncthreads();  // (B) the partial sums are in LDS
 #pragma unroll
               for (int w = 0; w < NHELP; ++w) {
@@ -3035,11 +3102,27 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
               }
             }
           }
-          if (!helped) ev_part(gpc, pool, pj1, pj2, pa1, pa2, neva, nevd, 0, 1, z, rw);
+          if (!PEEL && !helped) ev_part(gpc, pool, pj1, pj2, pa1, pa2, neva, nevd, 0, 1, 0, z, rw);
+          if (PEEL && !helped) {
+            // (without a single add event the four records are not the robot's: computed on all the same, so that the
+            //  loads stay where they were issued, and dropped)
+            double z1[RE], rw1[KQ];
+#pragma unroll
+            for (int q = 0; q < RE; ++q) z1[q] = z[q];
+#pragma unroll
+            for (int k = 0; k < KQ; ++k) rw1[k] = rw[k];
+            trip_acc(std::integral_constant<int, 1>{}, pa1, pa2, ya0, yb0, zl0, gl0, z1, rw1);
+#pragma unroll
+            for (int q = 0; q < RE; ++q) z[q] = (neva > 0) ? z1[q] : z[q];
+#pragma unroll
+            for (int k = 0; k < KQ; ++k) rw[k] = (neva > 0) ? rw1[k] : rw[k];
+            ev_part(gpc, pool, pj1, pj2, pa1, pa2, neva, nevd, 0, 1, TR, z, rw);
+          }
           const double delta = __builtin_fma(pa2, bcast(z, pj2), pa1 * bcast(z, pj1));
-          const double cn = __builtin_fma(pa2 * pa2, Sb.Hp[pj2 * (pj2 + 3) / 2], pa1 * pa1 * Sb.Hp[pj1 * (pj1 + 3) / 2]);  // scale of c_p^T H^-1 c_p: diag(H^-1)
+          const double cn = __builtin_fma(pa2 * pa2, hd2, pa1 * pa1 * hd1);  // scale of c_p^T H^-1 c_p: diag(H^-1)
           const double sp = __builtin_fma(pa2, bcast(xv, pj2), pa1 * bcast(xv, pj1)) - p_rhs;
-          if (dbg_clk && lane == 0 && iters == QMPC_DBG_ITER) dbg_clk[9] = clock64();
+          if constexpr (!GPOOL) asm volatile("; qmpc iter delta");
+          if (QMPC_DBG_ITER > 0 && dbg_clk && lane == 0 && iters == QMPC_DBG_ITER) dbg_clk[9] = clock64();
           const bool dep = uni(!(delta > 1e-11 * cn));
           if (rebuild) {
             // the add event of slot rl, exactly as in the full step below (r is zero for the slots not rebuilt yet)
@@ -3081,7 +3164,10 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
           double t1 = __builtin_inf();
           int l = -1;
           if (khw > 0 && !(WARM && forced)) {
-            t1 = wave_min_pos_f64(rmin);
+            // (the ratio is +inf from slot lane khw on: a class of 32 slots stops at lane 31, a working set that has
+            //  never reached past slot 16 at lane 15; same values compared, same minimum)
+            if constexpr (KS <= 32) t1 = (khw <= 16) ? wave_min_pos_f64<16>(rmin) : wave_min_pos_f64<32>(rmin);
+            else t1 = wave_min_pos_f64(rmin);
             if (uni(t1 < __builtin_inf())) {
 #pragma unroll
               for (int k = 0; k < KQ; ++k) {
@@ -3105,6 +3191,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
           iters += 1;
           if (uni(t2 <= t1)) {
             // ---- full step: p joins the working set in the first free slot (an add event)
+            xgather();  // (x is final, the next trip searches: the gather flies while the event is built)
             int qslot = -1;
 #pragma unroll
             for (int k = 0; k < KQ; ++k) {
@@ -3141,7 +3228,8 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
             if (!drop_slot(l, false)) break;
           }
           __builtin_amdgcn_wave_barrier();
-          if (dbg_clk && lane == 0 && iters == QMPC_DBG_ITER + 1) dbg_clk[10] = clock64();
+          if constexpr (!GPOOL) asm volatile("; qmpc iter end");
+          if (QMPC_DBG_ITER > 0 && dbg_clk && lane == 0 && iters == QMPC_DBG_ITER + 1) dbg_clk[10] = clock64();
         }
         need_p0 = need_p;
         return retry;
@@ -3288,9 +3376,9 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
 #pragma unroll
           for (int k = 0; k < KQ; ++k) rp[k] = 0.0;
           if (__builtin_amdgcn_readfirstlane(S.hd.glob) != 0)
-            ev_part(std::true_type{}, (GlobalF64*)(size_t)S.hd.gptr, hj1, hj2, ha1, ha2, hna, hnd, wv, NHELP + 1, zp, rp);
+            ev_part(std::true_type{}, (GlobalF64*)(size_t)S.hd.gptr, hj1, hj2, ha1, ha2, hna, hnd, wv, NHELP + 1, 0, zp, rp);
           else
-            ev_part(std::false_type{}, (double*)Sb.Sinv, hj1, hj2, ha1, ha2, hna, hnd, wv, NHELP + 1, zp, rp);
+            ev_part(std::false_type{}, (double*)Sb.Sinv, hj1, hj2, ha1, ha2, hna, hnd, wv, NHELP + 1, 0, zp, rp);
           double* const mine = hpart + (wv - 1) * EV;
 #pragma unroll
           for (int q = 0; q < RE; ++q)

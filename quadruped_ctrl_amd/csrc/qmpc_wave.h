@@ -49,14 +49,43 @@ __device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
   t = dpp_u32<0x143, 0xc>(~0u, v); v = v < t ? v : t;
   return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
+// The same reductions over the FIRST LIVE lanes only (16, 32 or 64): for callers whose lanes from LIVE on hold the
+// identity, so that the steps which would fold them in change nothing.  Four row_shr steps leave a row's reduction in
+// its lane 15, row_bcast:15 carries it to lane 31, row_bcast:31 to lane 63: read where the last step needed ends.
+template <int LIVE>
+__device__ __forceinline__ unsigned wave_max_u32_first(unsigned v) {
+  static_assert(LIVE == 16 || LIVE == 32 || LIVE == 64, "whole rows");
+  unsigned t;
+  t = dpp_u32<0x111, 0xf>(0u, v); v = v > t ? v : t;
+  t = dpp_u32<0x112, 0xf>(0u, v); v = v > t ? v : t;
+  t = dpp_u32<0x114, 0xf>(0u, v); v = v > t ? v : t;
+  t = dpp_u32<0x118, 0xf>(0u, v); v = v > t ? v : t;
+  if constexpr (LIVE > 16) { t = dpp_u32<0x142, 0xa>(0u, v); v = v > t ? v : t; }
+  if constexpr (LIVE > 32) { t = dpp_u32<0x143, 0xc>(0u, v); v = v > t ? v : t; }
+  return (unsigned)__builtin_amdgcn_readlane((int)v, LIVE - 1);
+}
+template <int LIVE>
+__device__ __forceinline__ unsigned wave_min_u32_first(unsigned v) {
+  static_assert(LIVE == 16 || LIVE == 32 || LIVE == 64, "whole rows");
+  unsigned t;
+  t = dpp_u32<0x111, 0xf>(~0u, v); v = v < t ? v : t;
+  t = dpp_u32<0x112, 0xf>(~0u, v); v = v < t ? v : t;
+  t = dpp_u32<0x114, 0xf>(~0u, v); v = v < t ? v : t;
+  t = dpp_u32<0x118, 0xf>(~0u, v); v = v < t ? v : t;
+  if constexpr (LIVE > 16) { t = dpp_u32<0x142, 0xa>(~0u, v); v = v < t ? v : t; }
+  if constexpr (LIVE > 32) { t = dpp_u32<0x143, 0xc>(~0u, v); v = v < t ? v : t; }
+  return (unsigned)__builtin_amdgcn_readlane((int)v, LIVE - 1);
+}
 // min over the wave of NON-NEGATIVE doubles (bit pattern order == value order):
 // two 32-bit reductions (high words, then the low words of the lanes that tie on
-// the high word) instead of one 64-bit compare/select ladder
+// the high word) instead of one 64-bit compare/select ladder.  LIVE < 64: the lanes from LIVE on hold +inf (they
+// tie on the high word only when every lane does, and then their low word, zero, is the minimum anyway)
+template <int LIVE = 64>
 __device__ __forceinline__ double wave_min_pos_f64(double x) {
   const unsigned long long v = (unsigned long long)__double_as_longlong(x);
   const unsigned hi = (unsigned)(v >> 32), lo = (unsigned)v;
-  const unsigned mhi = wave_min_u32(hi);
-  const unsigned mlo = wave_min_u32(hi == mhi ? lo : ~0u);
+  const unsigned mhi = wave_min_u32_first<LIVE>(hi);
+  const unsigned mlo = wave_min_u32_first<LIVE>(hi == mhi ? lo : ~0u);
   return __longlong_as_double((long long)(((unsigned long long)mhi << 32) | mlo));
 }
 // max over the wave of NON-NEGATIVE doubles: the min reduction on the bitwise complement (larger
