@@ -61,24 +61,39 @@ def _bound(rec, err):
     return bnd
 
 
-def _teacher_forced(B, ticks, seed, switch_at=20, roll=None, joint=None, check_mpc=True, freq=500.0, geom=None):
+def _teacher_forced(B, ticks, seed, switch_at=20, roll=None, joint=None, check_mpc=True, freq=500.0, geom=None,
+                    gaits_at=None, vel_at=None, capped=None, stream=None, each_tick=None):
     """freq: qmpc_ctrl_init's (the stream is sampled at 1 / freq); geom: qmpc_set_leg_geometry's four lengths, None for
-    the handle's default."""
+    the handle's default.
+    gaits_at / vel_at: {tick: command}, given before that tick (default: the suite's gaits at 0 and switch_at, its
+    velocities at 0).  capped: None compares with whatever the reference returned; "converged" compares a robot on which
+    the reference stopped at its nWSR cap with the same pipeline run to convergence (test_gpu_ctrl_mode1._converged).
+    stream: (imu, motor) instead of make_tick_stream(seed).  each_tick(t, c, m, e): called at the end of every tick with
+    the controller, the model and the estimator read-out."""
     import torch
+    assert capped in (None, "converged")
     c = _ctrl(B, freq, geom)
     m = M.CtrlModel(B, freq, PID) if geom is None else M.CtrlModel(B, freq, PID, geom=geom)
     dev = c.device
-    imu, motor = W.make_tick_stream(B, ticks, seed, dt=1.0 / freq, roll=roll, joint=joint)
-    vel = _vel(B, seed + 1)
+    imu, motor = W.make_tick_stream(B, ticks, seed, dt=1.0 / freq, roll=roll, joint=joint) if stream is None else stream
+    if gaits_at is None:
+        gaits_at = {0: _gaits(B, 0, switch_at)}
+        gaits_at[switch_at] = _gaits(B, switch_at, switch_at)
+    if vel_at is None:
+        vel_at = {0: _vel(B, seed + 1)}
+    vel = vel_at[0]
     c.set_vel(torch.from_numpy(vel).to(dev))
     m.set_vel(vel)
     n_mpc = 0
     eff_hist = []
     for t in range(ticks):
-        if t in (0, switch_at):
-            g = _gaits(B, t, switch_at)
+        if t in gaits_at:
+            g = gaits_at[t]
             c.set_gait(torch.from_numpy(g).to(dev))
             m.set_gait(g)
+        if t in vel_at and t > 0:
+            c.set_vel(torch.from_numpy(vel_at[t]).to(dev))
+            m.set_vel(vel_at[t])
         eff = c.tick(torch.from_numpy(imu[t]).to(dev), torch.from_numpy(motor[t]).to(dev)).cpu().numpy()
         e = _gpu_est(c)
         e["leg_q"] = motor[t][:, :12].astype(np.float32)
@@ -103,8 +118,14 @@ def _teacher_forced(B, ticks, seed, switch_at=20, roll=None, joint=None, check_m
             rec.update(dt=float(m.dt_mpc), mu=0.4, f_max=120.0)
             f_gpu = c.read("f_ff")
             if check_mpc:
-                soln, _, rc = O.solve_batch(rec)
+                soln, nwsr, rc = O.solve_batch(rec)
                 assert (rc == 0).all()
+                if capped == "converged":
+                    from test_gpu_ctrl_mode1 import _converged
+                    over_cap = np.flatnonzero(nwsr >= 100)
+                    for i in over_cap:                            # (the reference stopped at its cap: see there)
+                        soln[i] = _converged(rec, int(i))
+                    print(f"tick {t}: {len(over_cap)} robots compared with the pipeline run to convergence {over_cap.tolist()}")
                 f_ref = O.forces_to_body(e["r_body"], soln[:, :12].astype(np.float32))
                 err = np.abs(f_gpu.astype(np.float64) - f_ref).max(1) / np.maximum(np.abs(f_ref).max(1), 1.0)
                 over = err >= 1e-4
@@ -117,6 +138,8 @@ def _teacher_forced(B, ticks, seed, switch_at=20, roll=None, joint=None, check_m
         eff_m = m.legcmd(e, m.f_ff)
         assert np.array_equal(eff, eff_m), (t, np.abs(eff - eff_m).max())
         eff_hist.append(eff)
+        if each_tick is not None:
+            each_tick(t, c, m, e)
     assert n_mpc == ticks // 13
     return c, m, np.array(eff_hist)
 
