@@ -46,8 +46,9 @@
  *       flow is therefore init -> set_terrain -> reset(all).
  * A non-finite value, or run <= 0 with count > 0, affects that robot only.
  *
- * Still out of scope: risers and lateral collisions; pitch adaptation of the controller to a slope; height maps from
- * memory.  (Contact decided by the ground -- early or late touch-down -- and slip are qmpc_contact.h, opt-in.)
+ * Still out of scope: risers and lateral collisions; pitch adaptation of the controller to a slope.  (Contact decided by
+ * the ground -- early or late touch-down -- and slip are qmpc_contact.h, height maps from memory are qmpc_field.h, both
+ * opt-in.)
  *
  * Errors as in qmpc_plant.h: QMPC_ERR_STATE before qmpc_plant_init; QMPC_ERR_ARG for a batch other than the plant's,
  * unknown flag bits or a null view.

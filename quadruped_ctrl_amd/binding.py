@@ -119,6 +119,16 @@ class ContactView(C.Structure):
 CONTACT_EARLY, CONTACT_LATE, CONTACT_SLIP = 1, 2, 4
 
 
+class FieldBank(C.Structure):
+    """qmpc_field_bank (include/qmpc_field.h)."""
+    _fields_ = [("z", C.c_void_p), ("nx", C.c_int), ("ny", C.c_int), ("count", C.c_int), ("cell", C.c_double)]
+
+
+class FieldView(C.Structure):
+    """qmpc_field_view (include/qmpc_field.h)."""
+    _fields_ = [("bank", FieldBank), ("place", C.c_void_p), ("flags", C.c_int), ("batch", C.c_int)]
+
+
 class PlantStats(C.Structure):
     """qmpc_plant_stats (include/qmpc_plant_vary.h)."""
     _fields_ = [(n, C.c_void_p) for n in PLANT_STATS_FIELDS] + [("batch", C.c_int), ("enabled", C.c_int)]
@@ -261,6 +271,11 @@ CONTACT_SIGNATURES = {
     "qmpc_plant_set_contact": [_P, _I, C.POINTER(ContactParams)],
     "qmpc_contact_view_get": [_P, C.POINTER(ContactView)],
 }
+# height-field terrain from memory under the plant (include/qmpc_field.h), same library and ABI version
+FIELD_SIGNATURES = {
+    "qmpc_plant_set_field": [_P, _I, C.POINTER(FieldBank), _P, _I],
+    "qmpc_field_view_get": [_P, C.POINTER(FieldView)],
+}
 # the sensor model between the plant and the controller's sensor path (include/qmpc_sense.h), same library and ABI version
 SENSE_SIGNATURES = {
     "qmpc_sense_init": [_P, _I, C.c_uint64, _P],
@@ -276,6 +291,7 @@ PLANT_VARY_EXPORTS = list(PLANT_VARY_SIGNATURES)
 SENSE_EXPORTS = list(SENSE_SIGNATURES)
 TERRAIN_EXPORTS = list(TERRAIN_SIGNATURES)
 CONTACT_EXPORTS = list(CONTACT_SIGNATURES)
+FIELD_EXPORTS = list(FIELD_SIGNATURES)
 
 _lib = None
 
@@ -310,7 +326,7 @@ def load_library():
                 "(python -c 'import __graft_entry__ as g; g.build()')")
         lib = C.CDLL(LIB_PATH)
         for name, sig in {**SIGNATURES, **CTRL_SIGNATURES, **PLANT_SIGNATURES, **PLANT_VARY_SIGNATURES, **TERRAIN_SIGNATURES,
-                          **CONTACT_SIGNATURES, **SENSE_SIGNATURES}.items():
+                          **CONTACT_SIGNATURES, **FIELD_SIGNATURES, **SENSE_SIGNATURES}.items():
             f = getattr(lib, name)
             f.argtypes, f.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
         _lib = lib
@@ -880,6 +896,7 @@ class BatchedPlant:
         self.batch = None
         self._params = {}
         self._terrain = None
+        self._field = None
 
     def _xyyaw(self, xyyaw):
         if xyyaw is None:
@@ -895,6 +912,7 @@ class BatchedPlant:
         self._keep = init_xyyaw
         self._params = {}     # (qmpc_plant_init unbinds: a new plant is the plain plant)
         self._terrain = None  # (... on flat ground)
+        self._field = None    # (... with no height field)
         v = self.view()
         self.state, self.motor = v["state"], v["motor"]
         self.effort = self.torch.zeros((self.batch, 12), dtype=self.torch.float64, device=self.device)
@@ -1005,6 +1023,43 @@ class BatchedPlant:
         prm = res.pop("params")
         res.update(flags=prm.flags, drop_speed=prm.drop_speed, slip_gain=prm.slip_gain, slip_vmax=prm.slip_vmax)
         return res
+
+    # -- include/qmpc_field.h ------------------------------------------------------------------------------------------
+    def set_field(self, z, place=None, cell=None, clamp_swing=False, rebase_z=False):
+        """Height-field terrain from memory under the PLANT (the controller is not told), added to the ground of
+        set_terrain() where that is bound: z is a contiguous float32 device tensor [M, ny, nx] (a bank of M maps, x
+        fastest, `cell` metres between samples), place a float64 device tensor [B, 4] of (map, ox, oy, zs) per robot -- the
+        robot stands on map `map`, whose sample (0, 0) lies at world (ox, oy), scaled by zs; heights are bilinear and the
+        edge samples extend outward.  The plant reads both tensors at every later step and reset -- write into them in
+        place (on the stream) to move a robot or change the ground, also between replays of a captured graph; they are
+        kept referenced here.  The flags are set_terrain()'s and are OR-ed with its.  set_field(None) unbinds; init()
+        unbinds, reset() does not and places the robots on the surface: init() -> set_field() -> reset(all)."""
+        if self.batch is None:
+            raise QmpcError("qmpc_plant_set_field before init()")
+        if z is None:
+            self.ctrl._call("qmpc_plant_set_field", self.batch, None, None, 0)
+            self._field = None
+            return
+        t = self.torch
+        if not (isinstance(z, t.Tensor) and z.dim() == 3 and z.dtype == t.float32 and z.is_contiguous()
+                and z.device == t.device(self.device)):
+            raise QmpcError("z: a contiguous float32 tensor [M, ny, nx] on the plant's device")
+        if cell is None:
+            raise QmpcError("cell: metres between samples")
+        ptr = self.ctrl._chk(place, (self.batch, 4), t.float64, "place")
+        bank = FieldBank(z.data_ptr(), int(z.shape[2]), int(z.shape[1]), int(z.shape[0]), float(cell))
+        flags = (TERRAIN_CLAMP_SWING if clamp_swing else 0) | (TERRAIN_REBASE_Z if rebase_z else 0)
+        self.ctrl._call("qmpc_plant_set_field", self.batch, C.byref(bank), ptr, flags)
+        self._field = (z, place)
+
+    def field(self):
+        """qmpc_field_view_get: bound, nx, ny, count, cell, flags, batch, and the tensors as bound (z, place; None
+        without a field)."""
+        v = FieldView()
+        self.ctrl._call("qmpc_field_view_get", C.byref(v))
+        z, place = self._field if self._field is not None else (None, None)
+        return dict(bound=bool(v.bank.z), nx=v.bank.nx, ny=v.bank.ny, count=v.bank.count, cell=v.bank.cell,
+                    flags=v.flags, batch=v.batch, z=z, place=place)
 
 
 class BatchedSensors:

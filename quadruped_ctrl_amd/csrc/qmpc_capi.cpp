@@ -24,6 +24,7 @@
 #include "../../include/qmpc_plant_vary.h"  // ... its per-robot parameters and on-device statistics
 #include "../../include/qmpc_terrain.h"  // ... its per-robot slopes and stairs
 #include "../../include/qmpc_contact.h"  // ... contact decided by the ground
+#include "../../include/qmpc_field.h"    // ... height-field terrain from memory
 #include "../../include/qmpc_sense.h"   // sensor model between the plant and the controller's sensor path
 #include "qmpc_device.h"
 #include "qmpc_glue.h"    // each launcher is declared once, in the header its defining file includes too:
@@ -227,6 +228,15 @@ struct __attribute__((visibility("hidden"))) qmpc_ctx {
     QmpcContactArgs contact{};
     DevBuf<double> contact_buf;
     bool contact_dirty = false;
+    // qmpc_field.h: the caller's bank and placements as bound (z null: no field) and the binding's QMPC_TERRAIN_* flags
+    QmpcFieldArgs field{};
+    int field_flags = 0;
+    // what a field launcher is given for the terrain: the rows as bound (or none) under both bindings' flags
+    QmpcTerrainArgs field_terrain() const {
+      QmpcTerrainArgs t = terrain;
+      t.flags |= field_flags;
+      return t;
+    }
   };
   std::unique_ptr<Plant> plant;
   // sensor model (qmpc_sense.h): the counters n[max_batch], epoch[max_batch] in one allocation made by qmpc_sense_init,
@@ -1558,6 +1568,8 @@ int qmpc_plant_init(qmpc_handle c, int batch, double mu_plant, int substeps, con
   k->terrain.rows = nullptr;  // ... and stands on flat ground
   k->terrain.flags = 0;
   k->contact.flags = 0;       // ... with scheduled contact
+  k->field = QmpcFieldArgs{};  // ... and no height field
+  k->field_flags = 0;
   return QMPC_OK;
 }
 
@@ -1568,6 +1580,13 @@ int qmpc_plant_reset(qmpc_handle c, int batch, const uint8_t* mask_dev, const do
   if (q.rc) return q.rc;
   const QmpcPlantConst K = plant_const(c, c->plant->mu, c->plant->substeps);
   const qmpc_ctx::Plant* k = c->plant.get();
+  if (k->field.z) {
+    // (the counters' reset first: with no rows bound it zeroes support and ground, which the field's reset then writes)
+    if (k->contact.flags) HIP_TRY(c, qmpc_launch_contact_reset(mask_dev, batch, q.stream, &k->terrain, &k->contact));
+    const QmpcTerrainArgs T = k->field_terrain();
+    HIP_TRY(c, qmpc_launch_field_init(&k->d, &K, mask_dev, init_xyyaw, batch, q.stream, &T, &k->field));
+    return QMPC_OK;
+  }
   if (k->terrain.rows)
     HIP_TRY(c, qmpc_launch_terrain_init(&k->d, &K, mask_dev, init_xyyaw, batch, q.stream, &k->terrain));
   else
@@ -1587,7 +1606,19 @@ int qmpc_plant_step(qmpc_handle c, int batch, const double* effort, double* stat
   // nothing bound and the statistics off: the plain instantiation, which is given no QmpcPlantVary to read
   qmpc_ctx::Plant* k = c->plant.get();
   const bool extra = k->bound || k->stats_on;
-  if (k->contact.flags) {
+  if (k->field.z) {
+    // a height field is bound: the same step, one kernel, on the summed surface (the rows may be null, the contact flags 0)
+    const QmpcTerrainArgs T = k->field_terrain();
+    if (k->contact.flags) {
+      k->contact.dt = 1.0 / c->ctrl->freq;
+      k->contact_dirty = true;
+      HIP_TRY(c, qmpc_launch_field_contact_step(&k->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out,
+                                                batch, q.stream, extra ? &k->vary : nullptr, k->bound, k->stats_on, &T,
+                                                &k->contact, &k->field));
+    } else
+      HIP_TRY(c, qmpc_launch_field_step(&k->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out, batch,
+                                        q.stream, extra ? &k->vary : nullptr, k->bound, k->stats_on, &T, &k->field));
+  } else if (k->contact.flags) {
     k->contact.dt = 1.0 / c->ctrl->freq;
     k->contact_dirty = true;
     HIP_TRY(c, qmpc_launch_contact_step(&k->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out,
@@ -1743,6 +1774,39 @@ int qmpc_contact_view_get(qmpc_handle c, qmpc_contact_view* v) {
   v->params.drop_speed = k->contact.drop_speed;
   v->params.slip_gain = k->contact.slip_gain;
   v->params.slip_vmax = k->contact.slip_vmax;
+  v->batch = k->batch;
+  return QMPC_OK;
+}
+
+// ---- include/qmpc_field.h: height-field terrain from memory ----
+
+int qmpc_plant_set_field(qmpc_handle c, int batch, const qmpc_field_bank* bank, const double* place_dev, int flags) {
+  if (const int rc = plant_check(c, batch)) return rc;
+  qmpc_ctx::Plant* k = c->plant.get();
+  if (!bank) {
+    k->field = QmpcFieldArgs{};
+    k->field_flags = 0;
+    return QMPC_OK;
+  }
+  if (flags & ~(QMPC_TERRAIN_CLAMP_SWING | QMPC_TERRAIN_REBASE_Z)) return QMPC_ERR_ARG;
+  if (!bank->z || !place_dev || bank->nx < 2 || bank->ny < 2 || bank->count < 1) return QMPC_ERR_ARG;
+  if (!std::isfinite(bank->cell) || !(bank->cell > 0)) return QMPC_ERR_ARG;
+  k->field = QmpcFieldArgs{bank->z, place_dev, bank->cell, bank->nx, bank->ny, bank->count};
+  k->field_flags = flags;
+  return QMPC_OK;
+}
+
+int qmpc_field_view_get(qmpc_handle c, qmpc_field_view* v) {
+  if (!c || !v) return QMPC_ERR_ARG;
+  if (!plant_ready(c)) return QMPC_ERR_STATE;
+  const qmpc_ctx::Plant* k = c->plant.get();
+  v->bank.z = k->field.z;
+  v->bank.nx = k->field.nx;
+  v->bank.ny = k->field.ny;
+  v->bank.count = k->field.count;
+  v->bank.cell = k->field.cell;
+  v->place = k->field.place;
+  v->flags = k->field_flags;
   v->batch = k->batch;
   return QMPC_OK;
 }

@@ -1,0 +1,174 @@
+// qmpc_field.hip -- the plant of include/qmpc_plant.h on height-field terrain from memory (include/qmpc_field.h): a bank
+// of float maps in device memory, every robot placed on one of them, added to the analytic ground of
+// include/qmpc_terrain.h.  The host picks these kernels only while a bank is bound; with none the plant launches the
+// kernels of qmpc_plant.hip / qmpc_terrain.hip / qmpc_contact.hip as it always did, with the arguments it always gave.
+//
+// Nothing here is a step of its own: the scheduled-contact step is the statements of qmpc_plant_step_body.h with
+// TERRAIN = FIELD = true, the contact step those of qmpc_contact_step_body.h with FIELD = true, each in the four
+// <VARY, STATS> combinations, and the reset is qmpc_terrain.hip's on the summed surface.  The sampler and the per-foot
+// normal are qmpc_plant_dev.h's plant_field_*; the index logic is qmpc_field_index.h, which tests/field_index_dump.cpp
+// compiles for the CPU.  One lane per (robot, leg): a lane's foot has its own four taps, so the per-foot normal costs no
+// shuffle.  The taps are dependent gathers of 4 bytes each from a map that, at the reference's 256 x 256, is 256 KiB and
+// lives in L2; the sampler issues the four loads before the first use, and the place row is loaded once per step.
+// tests/plant_model_field.py restates every expression in the same order.
+#include "qmpc_plant_dev.h"
+
+namespace {
+
+// (i_0 + i_1) + (i_2 + i_3) over the quad, in every lane
+__device__ __forceinline__ int contact_quad_count(int x) {
+  x = x + __shfl_xor(x, 1);
+  x = x + __shfl_xor(x, 2);
+  return x;
+}
+
+// qmpc_plant_reset while a field is bound (mask == NULL: every robot): qmpc_terrain_init_kernel on the summed surface.
+// T.rows may be null (the field alone).  Every lane computes (the shuffles need their partners); masked ones store.
+__global__ __launch_bounds__(256) void qmpc_field_init_kernel(const QmpcPlantDev S, const QmpcPlantConst K,
+                                                              const uint8_t* __restrict__ mask,
+                                                              const double* __restrict__ xyyaw, const int n,
+                                                              const QmpcTerrainArgs T, const QmpcFieldArgs Fd) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  const bool in = t < n;
+  const int tt = in ? t : n - 1;
+  const int b = tt >> 2, leg = tt & 3;
+  const bool live = in && (!mask || mask[b]);
+  const double x0 = xyyaw ? xyyaw[(size_t)b * 3] : 0.0, y0 = xyyaw ? xyyaw[(size_t)b * 3 + 1] : 0.0;
+  const double yaw = xyyaw ? xyyaw[(size_t)b * 3 + 2] : 0.0;
+  PlantGround G;
+  PlantField Fl;
+  if (T.rows)
+    plant_ground_load(T.rows + (size_t)b * 8, T.flags, G);
+  else
+    plant_ground_flat(G);
+  G.flags = T.flags;
+  plant_field_load(Fd, b, Fl);
+  const double ground = plant_field_height(G, Fl, x0, y0);
+  const double p[3] = {x0, y0, QMPC_PLANT_HEIGHT + ground}, v[3] = {0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
+  const double q[4] = {cos(yaw / 2), 0.0, 0.0, sin(yaw / 2)};
+  const double side = (leg & 1) ? 1.0 : -1.0;
+  double hip[3], R[9], fw[3];
+  plant_hip(leg, hip);
+  plant_rot(q, R);
+  const double fb[3] = {hip[0], hip[1] + side * QMPC_PLANT_SIDE_OFFSET, -QMPC_PLANT_HEIGHT};
+  plant_mul(R, fb, fw);
+  double c[3] = {p[0] + fw[0], p[1] + fw[1], 0.0};
+  c[2] = plant_field_height(G, Fl, c[0], c[1]);
+  G.support = plant_quad_sum(c[2]) / 4.0;
+  if (live) {
+    for (int k = 0; k < 3; ++k) S.grf[(size_t)tt * 3 + k] = 0.0;
+    S.stance[tt] = 1;
+    if (leg == 0) {
+      T.support[b] = G.support;
+      T.ground[b] = ground;
+    }
+  }
+  plant_readout<true, true>(S, K, tt, live, p, v, q, w, c, true, v /* vdot = 0 */, nullptr, nullptr, nullptr, nullptr, G,
+                            Fl);
+}
+
+// One control period with scheduled contact on the summed surface: qmpc_plant_step_body.h with TERRAIN = FIELD = true
+template <bool VARY, bool STATS>
+__global__ __launch_bounds__(256) void qmpc_field_step_kernel(const QmpcPlantDev S, const QmpcPlantConst K,
+                                                              const double* __restrict__ effort,
+                                                              const float* __restrict__ contact_state,
+                                                              const float* __restrict__ p_des,
+                                                              const float* __restrict__ v_des, double* state_out,
+                                                              double* motor_out, const int n, const QmpcPlantVary V,
+                                                              const QmpcTerrainArgs T, const QmpcFieldArgs Fd) {
+#pragma clang fp contract(off)
+  constexpr bool TERRAIN = true;
+  constexpr bool FIELD = true;
+#include "qmpc_plant_step_body.h"
+}
+
+// The arguments of a contact step on the field: qmpc_contact.hip's ContactStepArgs member for member, then the field's.
+struct FieldContactStepArgs {
+  QmpcPlantDev S;
+  QmpcPlantConst K;
+  const double* effort;
+  const float *contact_state, *p_des, *v_des;
+  double *state_out, *motor_out;
+  int n;
+  QmpcPlantVary V;
+  QmpcTerrainArgs T;
+  QmpcContactArgs C;
+  QmpcFieldArgs Fd;
+};
+
+// One control period with contact decided by the summed surface: qmpc_contact_step_body.h with FIELD = true, under the
+// launch bounds of qmpc_contact_step_kernel.
+template <bool VARY, bool STATS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void qmpc_field_contact_step_kernel(
+    const FieldContactStepArgs A) {
+#pragma clang fp contract(off)
+  constexpr bool FIELD = true;
+  const QmpcFieldArgs& Fd = A.Fd;
+  typedef FieldContactStepArgs StepArgs;
+#include "qmpc_contact_step_body.h"
+}
+
+}  // namespace
+
+extern "C" hipError_t qmpc_launch_field_init(const QmpcPlantDev* S, const QmpcPlantConst* K, const uint8_t* mask,
+                                             const double* xyyaw, int batch, hipStream_t stream, const QmpcTerrainArgs* T,
+                                             const QmpcFieldArgs* Fd) {
+  const int n = batch * 4;
+  hipLaunchKernelGGL(qmpc_field_init_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, *S, *K, mask, xyyaw, n, *T,
+                     *Fd);
+  return hipGetLastError();
+}
+
+// V == NULL: nothing bound and the statistics off.  Otherwise vary and stats pick the instantiation, as in
+// qmpc_launch_plant_step.
+extern "C" hipError_t qmpc_launch_field_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
+                                             const float* contact_state, const float* p_des, const float* v_des,
+                                             double* state_out, double* motor_out, int batch, hipStream_t stream,
+                                             const QmpcPlantVary* V, int vary, int stats, const QmpcTerrainArgs* T,
+                                             const QmpcFieldArgs* Fd) {
+  const int n = batch * 4;
+  const dim3 grid((n + 255) / 256), block(256);
+  const QmpcPlantVary none{};
+  vary = V && vary;
+  stats = V && stats;
+#define QMPC_FIELD_STEP(VARY, STATS, v)                                                                            \
+  hipLaunchKernelGGL((qmpc_field_step_kernel<VARY, STATS>), grid, block, 0, stream, *S, *K, effort, contact_state, \
+                     p_des, v_des, state_out, motor_out, n, v, *T, *Fd)
+  if (vary && stats)
+    QMPC_FIELD_STEP(true, true, *V);
+  else if (vary)
+    QMPC_FIELD_STEP(true, false, *V);
+  else if (stats)
+    QMPC_FIELD_STEP(false, true, *V);
+  else
+    QMPC_FIELD_STEP(false, false, none);
+#undef QMPC_FIELD_STEP
+  return hipGetLastError();
+}
+
+extern "C" hipError_t qmpc_launch_field_contact_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
+                                                     const float* contact_state, const float* p_des, const float* v_des,
+                                                     double* state_out, double* motor_out, int batch, hipStream_t stream,
+                                                     const QmpcPlantVary* V, int vary, int stats,
+                                                     const QmpcTerrainArgs* T, const QmpcContactArgs* C,
+                                                     const QmpcFieldArgs* Fd) {
+  const int n = batch * 4;
+  const dim3 grid((n + 255) / 256), block(256);
+  vary = V && vary;
+  stats = V && stats;
+  const FieldContactStepArgs A{*S, *K, effort, contact_state, p_des, v_des, state_out, motor_out, n,
+                               vary || stats ? *V : QmpcPlantVary{}, *T, *C, *Fd};
+#define QMPC_FIELD_CONTACT_STEP(VARY, STATS) \
+  hipLaunchKernelGGL((qmpc_field_contact_step_kernel<VARY, STATS>), grid, block, 0, stream, A)
+  if (vary && stats)
+    QMPC_FIELD_CONTACT_STEP(true, true);
+  else if (vary)
+    QMPC_FIELD_CONTACT_STEP(true, false);
+  else if (stats)
+    QMPC_FIELD_CONTACT_STEP(false, true);
+  else
+    QMPC_FIELD_CONTACT_STEP(false, false);
+#undef QMPC_FIELD_CONTACT_STEP
+  return hipGetLastError();
+}

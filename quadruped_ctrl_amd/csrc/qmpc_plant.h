@@ -73,6 +73,15 @@ struct QmpcContactArgs {
   int flags;       // QMPC_CONTACT_*
 };
 
+// include/qmpc_field.h: the caller's bank and placements as bound (z null: no field, the kernels above).  By value.  The
+// flags of the binding are OR-ed into the QmpcTerrainArgs a field launcher is given.
+struct QmpcFieldArgs {
+  const float* z;       // [count][ny][nx], x fastest
+  const double* place;  // [B][4] map, ox, oy, zs
+  double cell;
+  int nx, ny, count;
+};
+
 #define QMPC_PLANT_GRAVITY 9.81
 #define QMPC_PLANT_HEIGHT 0.29      /* ConvexMPCLocomotion::_body_height */
 #define QMPC_PLANT_SIDE_OFFSET 0.065
@@ -108,5 +117,22 @@ extern "C" hipError_t qmpc_launch_contact_step(const QmpcPlantDev* S, const Qmpc
                                                const QmpcContactArgs* C);
 extern "C" hipError_t qmpc_launch_contact_reset(const uint8_t* mask, int batch, hipStream_t stream,
                                                 const QmpcTerrainArgs* T, const QmpcContactArgs* C);
+// ... and of qmpc_field.hip, which capi picks while a height field is bound: the reset, the scheduled-contact step and
+// the contact step on the summed surface of include/qmpc_field.h (T->rows may be null: the field alone; T->flags is the
+// OR of both bindings' flags), with the field's arguments after the others.
+extern "C" hipError_t qmpc_launch_field_init(const QmpcPlantDev* S, const QmpcPlantConst* K, const uint8_t* mask,
+                                             const double* xyyaw, int batch, hipStream_t stream, const QmpcTerrainArgs* T,
+                                             const QmpcFieldArgs* Fd);
+extern "C" hipError_t qmpc_launch_field_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
+                                             const float* contact_state, const float* p_des, const float* v_des,
+                                             double* state_out, double* motor_out, int batch, hipStream_t stream,
+                                             const QmpcPlantVary* V, int vary, int stats, const QmpcTerrainArgs* T,
+                                             const QmpcFieldArgs* Fd);
+extern "C" hipError_t qmpc_launch_field_contact_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
+                                                     const float* contact_state, const float* p_des, const float* v_des,
+                                                     double* state_out, double* motor_out, int batch, hipStream_t stream,
+                                                     const QmpcPlantVary* V, int vary, int stats,
+                                                     const QmpcTerrainArgs* T, const QmpcContactArgs* C,
+                                                     const QmpcFieldArgs* Fd);
 
 #endif

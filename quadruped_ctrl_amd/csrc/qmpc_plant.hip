@@ -61,6 +61,8 @@ __global__ __launch_bounds__(256) void qmpc_plant_step_kernel(const QmpcPlantDev
 #pragma clang fp contract(off)
   constexpr bool TERRAIN = false;
   const QmpcTerrainArgs T{};
+  constexpr bool FIELD = false;
+  const QmpcFieldArgs Fd{};
 #include "qmpc_plant_step_body.h"
 }
 

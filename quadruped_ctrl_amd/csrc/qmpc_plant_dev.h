@@ -1,6 +1,7 @@
 // qmpc_plant_dev.h -- device code of the reduced-order plant shared by qmpc_plant.hip (include/qmpc_plant.h: flat
-// ground) and qmpc_terrain.hip (include/qmpc_terrain.h: per-robot slopes and stairs): the leg helpers, the terrain's
-// height and the read-out.  (The statements of one control period are qmpc_plant_step_body.h, which a step kernel
+// ground), qmpc_terrain.hip (include/qmpc_terrain.h: per-robot slopes and stairs), qmpc_contact.hip (include/qmpc_contact.h)
+// and qmpc_field.hip (include/qmpc_field.h: height fields from memory): the leg helpers, the terrain's height, the
+// field's sampler and per-foot normal, and the read-out.  (The statements of one control period are qmpc_plant_step_body.h, which a step kernel
 // includes as text.)  One lane per (robot, leg) as in the glue kernels.  Every lane of a robot's quad carries a copy of
 // the body state; a leg's force and moment are summed over the quad with two xor-shuffles, (f_0 + f_1) + (f_2 + f_3) in
 // every lane (the sum is commutative, so the four lanes hold the same bits), and the four lanes integrate the same body
@@ -9,11 +10,13 @@
 // TERRAIN) restates every expression in the same order.
 //
 // Everything here is force-inlined and lives in an unnamed namespace: each translation unit gets its own copy and
-// defines only its own kernels.  TERRAIN = false reads nothing of the terrain and is the flat plant, bit for bit.
+// defines only its own kernels.  TERRAIN = false reads nothing of the terrain and is the flat plant, bit for bit;
+// FIELD = false reads nothing of the field and leaves every kernel of the other three files as it was.
 #ifndef QMPC_PLANT_DEV_CODE_H
 #define QMPC_PLANT_DEV_CODE_H
 
 #include "qmpc_plant.h"
+#include "qmpc_field_index.h"
 
 namespace {
 
@@ -153,17 +156,107 @@ __device__ __forceinline__ double plant_height(const PlantGround& G, double x, d
   return ((G.z0 + G.gx * x) + G.gy * y) + G.rise * k;
 }
 
+// No terrain bound: an all-zero row under flags 0 (height 0, n = (-0, -0, 1): the additive identities of qmpc_terrain.h)
+__device__ __forceinline__ void plant_ground_flat(PlantGround& G) {
+  G.z0 = G.gx = G.gy = G.rise = G.run = G.count = G.s0 = 0.0;
+  G.cpsi = 1.0;
+  G.spsi = 0.0;
+  G.n[0] = -0.0;
+  G.n[1] = -0.0;
+  G.n[2] = 1.0;
+  G.support = 0.0;
+  G.flags = 0;
+}
+
+// A robot's placement on the height-field bank (include/qmpc_field.h) in registers: its map's first sample, the origin,
+// the scale and the grid.  Loaded once per step (the same address in the four lanes of a quad).  An empty struct's worth
+// of dead registers where FIELD is false.
+struct PlantField {
+  const float* z;  // the robot's own map: bank + m ny nx
+  double ox, oy, zs, cell;
+  int nx, ny;
+};
+
+__device__ __forceinline__ void plant_field_load(const QmpcFieldArgs& Fd, int b, PlantField& Fl) {
+  const double* __restrict__ row = Fd.place + (size_t)b * 4;
+  const double map = row[0];
+  Fl.ox = row[1];
+  Fl.oy = row[2];
+  Fl.zs = row[3];
+  Fl.z = Fd.z + qmpc_field_base(qmpc_field_map(map, Fd.count), Fd.nx, Fd.ny);
+  Fl.cell = Fd.cell;
+  Fl.nx = Fd.nx;
+  Fl.ny = Fd.ny;
+}
+
+// f, fx, fy of include/qmpc_field.h at (x, y), from one set of four taps.  The taps are dependent gathers (their address
+// hangs on the foot's position): all four loads are issued before the first use, so they share one wait.
+__device__ __forceinline__ void plant_field_sample(const PlantField& Fl, double x, double y, double& f, double& fx,
+                                                   double& fy) {
+#pragma clang fp contract(off)
+  double a, b;
+  bool in_x, in_y;
+  const int i = qmpc_field_axis((x - Fl.ox) / Fl.cell, Fl.nx, &a, &in_x);
+  const int j = qmpc_field_axis((y - Fl.oy) / Fl.cell, Fl.ny, &b, &in_y);
+  const float* __restrict__ t = Fl.z + qmpc_field_tap(i, j, Fl.nx);
+  const float s00 = t[0], s10 = t[1], s01 = t[Fl.nx], s11 = t[Fl.nx + 1];
+  const double z00 = (double)s00, z10 = (double)s10, z01 = (double)s01, z11 = (double)s11;
+  const double d0 = z10 - z00, d1 = z11 - z01;
+  const double e0 = z00 + a * d0, e1 = z01 + a * d1;
+  const double e = e1 - e0;
+  f = Fl.zs * (e0 + b * e);
+  fx = in_x ? Fl.zs * ((d0 + b * (d1 - d0)) / Fl.cell) : 0.0;
+  fy = in_y ? Fl.zs * (e / Fl.cell) : 0.0;
+}
+
+// height(x, y) of include/qmpc_field.h from the analytic height h and the field's f: f == 0 (either sign) leaves h's bits
+__device__ __forceinline__ double plant_field_add(double h, double f) {
+#pragma clang fp contract(off)
+  return f == 0.0 ? h : h + f;
+}
+
+// The summed surface at (x, y) where only the height is wanted
+__device__ __forceinline__ double plant_field_height(const PlantGround& G, const PlantField& Fl, double x, double y) {
+  double f, fx, fy;
+  plant_field_sample(Fl, x, y, f, fx, fy);
+  return plant_field_add(plant_height(G, x, y), f);
+}
+
+// The summed surface at a foot's (x, y) and the contact normal there, into G.n: this lane's own foot, so G.n is per foot
+// from here on.  fx == fy == 0 gives plant_ground_load's bits.
+__device__ __forceinline__ double plant_field_foot(PlantGround& G, const PlantField& Fl, double x, double y) {
+#pragma clang fp contract(off)
+  double f, fx, fy;
+  plant_field_sample(Fl, x, y, f, fx, fy);
+  const double gx = fx == 0.0 ? G.gx : G.gx + fx, gy = fy == 0.0 ? G.gy : G.gy + fy;
+  const double norm = sqrt((gx * gx + gy * gy) + 1);
+  G.n[0] = -gx / norm;
+  G.n[1] = -gy / norm;
+  G.n[2] = 1 / norm;
+  return plant_field_add(plant_height(G, x, y), f);
+}
+
+// The surface of a kernel: the summed one with FIELD, the analytic one without
+template <bool FIELD>
+__device__ __forceinline__ double plant_surface(const PlantGround& G, const PlantField& Fl, double x, double y) {
+  if constexpr (FIELD)
+    return plant_field_height(G, Fl, x, y);
+  else
+    return plant_height(G, x, y);
+}
+
 // The read-out of lane tt = robot * 4 + leg at pose (p, v, q, w): the foot's hip-frame position and velocity -> joint
 // angles and rates; leg 0 also writes the body's state row.  A swing foot (stance == 0) takes r, rdot from pdes / vdes
 // (clamped) and moves c to it.  Rows go to the plant's own copy and, when given, to the caller's.
 // TERRAIN: with QMPC_TERRAIN_CLAMP_SWING a swing foot placed below the surface is lifted onto it and r follows; with
 // QMPC_TERRAIN_REBASE_Z column 6 of the state row is p_z - G.support (the view's p stays world truth).
-template <bool TERRAIN>
+// FIELD (include/qmpc_field.h): the surface the swing foot is lifted onto is the summed one, through Fl.
+template <bool TERRAIN, bool FIELD = false>
 __device__ __forceinline__ void plant_readout(const QmpcPlantDev& S, const QmpcPlantConst& K, int tt, bool live,
                                               const double* p, const double* v, const double* q, const double* w,
                                               double* c, bool stance, const double* vdot, const float* pdes,
                                               const float* vdes, double* state_out, double* motor_out,
-                                              const PlantGround& G) {
+                                              const PlantGround& G, const PlantField& Fl = PlantField{}) {
 #pragma clang fp contract(off)
   const int b = tt >> 2, leg = tt & 3;
   const double side = (leg & 1) ? 1.0 : -1.0;
@@ -201,7 +294,7 @@ __device__ __forceinline__ void plant_readout(const QmpcPlantDev& S, const QmpcP
     for (int k = 0; k < 3; ++k) c[k] = p[k] + hw[k];
     if constexpr (TERRAIN) {
       if (G.flags & 1 /* QMPC_TERRAIN_CLAMP_SWING */) {
-        const double hz = plant_height(G, c[0], c[1]);
+        const double hz = plant_surface<FIELD>(G, Fl, c[0], c[1]);
         if (c[2] < hz) {
           c[2] = hz;  // the encoders see the shortened leg; rdot stays v_des
           const double d[3] = {c[0] - p[0], c[1] - p[1], c[2] - p[2]};

@@ -1,9 +1,10 @@
 // qmpc_plant_step_body.h -- the statements of one control period of the plant, as TEXT: included inside the body of a
 // step kernel (qmpc_plant.hip: TERRAIN false; qmpc_terrain.hip: TERRAIN true) after qmpc_plant_dev.h, with in scope
 //   #pragma clang fp contract(off) at the head of the kernel's body (the pragma is only allowed there);
-//   the template parameters bool VARY, bool STATS, and constexpr bool TERRAIN;
-//   the kernel's parameters S, K, effort, contact_state, p_des, v_des, state_out, motor_out, n, V, and
-//   T (QmpcTerrainArgs: a parameter of the terrain kernels, an empty local of the flat ones).
+//   the template parameters bool VARY, bool STATS, and constexpr bool TERRAIN, FIELD (qmpc_field.hip: both true);
+//   the kernel's parameters S, K, effort, contact_state, p_des, v_des, state_out, motor_out, n, V,
+//   T (QmpcTerrainArgs: a parameter of the terrain kernels, an empty local of the flat ones) and
+//   Fd (QmpcFieldArgs: a parameter of the field kernels, an empty local of the others).
 // It is text and not a function on purpose.  As a force-inlined function template plant_step_body<VARY, STATS, TERRAIN>
 // the same statements cost the plain step 225 VGPRs and 17 scalar registers parked in scratch (arguments by value or by
 // reference, with or without __restrict__), against 221 and none when the kernel holds them itself -- the figures
@@ -16,8 +17,10 @@
 // force / moment added to the quad sums.  STATS: the lane that writes the state row folds the new pose into the robot's
 // accumulators.  TERRAIN (include/qmpc_terrain.h): the robot's terrain row is loaded once in front of the substeps (the
 // same address in four lanes), touch-down lands on height(c_x, c_y), the cone is taken about the contact normal, and the
-// stance feet's mean height and the ground under the body are kept.  VARY = STATS = TERRAIN = false reads nothing of V
-// or T and is the plain step.
+// stance feet's mean height and the ground under the body are kept.  FIELD (include/qmpc_field.h, with TERRAIN): the
+// robot's place row is loaded once beside the terrain row (T.rows may be null: the field alone), every height is the
+// summed surface, and the contact normal is this lane's own foot's, from the taps of its touch-down.  VARY = STATS =
+// TERRAIN = false reads nothing of V or T and is the plain step; FIELD = false reads nothing of Fd.
   const int t = blockIdx.x * 256 + threadIdx.x;
   const bool live = t < n;
   const int tt = live ? t : n - 1;
@@ -36,9 +39,22 @@
   plant_hip(leg, hip);
   const bool stance = contact_state[tt] > 0.f;
   PlantGround G;
+  PlantField Fl;
   if constexpr (TERRAIN) {
-    plant_ground_load(T.rows + (size_t)b * 8, T.flags, G);
-    if (stance && !S.stance[tt]) c[2] = plant_height(G, c[0], c[1]);  // touch-down: pinned on the surface
+    if constexpr (FIELD) {
+      if (T.rows)
+        plant_ground_load(T.rows + (size_t)b * 8, T.flags, G);
+      else
+        plant_ground_flat(G);
+      G.flags = T.flags;
+      plant_field_load(Fd, b, Fl);
+      // the surface and the contact normal under this lane's foot, from one set of taps
+      const double hz = plant_field_foot(G, Fl, c[0], c[1]);
+      if (stance && !S.stance[tt]) c[2] = hz;  // touch-down: pinned on the surface
+    } else {
+      plant_ground_load(T.rows + (size_t)b * 8, T.flags, G);
+      if (stance && !S.stance[tt]) c[2] = plant_height(G, c[0], c[1]);  // touch-down: pinned on the surface
+    }
     // the stance feet's mean height (the previous value through a flight phase)
     const double cnt = plant_quad_sum(stance ? 1.0 : 0.0);
     const double sum = plant_quad_sum(stance ? c[2] : 0.0);
@@ -157,11 +173,12 @@
     for (int k = 0; k < 3; ++k) S.grf[o3 + k] = f[k];
     S.stance[tt] = stance ? 1 : 0;
   }
-  plant_readout<TERRAIN>(S, K, tt, live, p, v, q, w, c, stance, vdot, p_des + o3, v_des + o3, state_out, motor_out, G);
+  plant_readout<TERRAIN, FIELD>(S, K, tt, live, p, v, q, w, c, stance, vdot, p_des + o3, v_des + o3, state_out, motor_out,
+                                G, Fl);
   if constexpr (TERRAIN) {
     if (live && leg == 0) {
       T.support[b] = G.support;
-      T.ground[b] = plant_height(G, p[0], p[1]);
+      T.ground[b] = plant_surface<FIELD>(G, Fl, p[0], p[1]);
     }
   }
   if constexpr (STATS) {

@@ -60,6 +60,8 @@ __global__ __launch_bounds__(256) void qmpc_terrain_step_kernel(const QmpcPlantD
                                                                 const QmpcTerrainArgs T) {
 #pragma clang fp contract(off)
   constexpr bool TERRAIN = true;
+  constexpr bool FIELD = false;
+  const QmpcFieldArgs Fd{};
 #include "qmpc_plant_step_body.h"
 }
 

@@ -564,3 +564,14 @@ def make_state_stream(batch, ticks, seed, dt=0.002, roll=None, joint=None):
     state[..., 10:13] = vbase + 0.02 * np.sin(2 * np.pi * 0.9 * t + vph)
     state[..., 13:16] = imu[..., 0:3]
     return state, motor
+
+
+def random_blocks(seed, n=256, block=2, amp=0.06):
+    """One height map [n, n] float32 (y, x) of the kind the reference's simulation calls `random1`: every block x block
+    patch of samples shares one height drawn from uniform(0, amp) -- at the reference's n = 256, block = 2, amp = 0.06 m
+    on 0.05 m cells, a 12.75 m square of 0.1 m plateaus.  For BatchedPlant.set_field (include/qmpc_field.h); the map is
+    data made from the seed, never stored."""
+    rng = np.random.default_rng(seed)
+    nb = -(-n // block)
+    h = rng.uniform(0.0, amp, (nb, nb))
+    return np.ascontiguousarray(np.repeat(np.repeat(h, block, 0), block, 1)[:n, :n].astype(np.float32))

@@ -34,6 +34,11 @@ csrc/qmpc_terrain.hip (with --vary: their <VARY, STATS> instantiation).
 --contact lets the ground decide contact (include/qmpc_contact.h: early and late touch-down and slip, the binding's default
 parameters), on flat ground or with --terrain on its ground: the step then runs the kernels of csrc/qmpc_contact.hip; the
 counters are reported.
+--field binds height-field terrain from memory (include/qmpc_field.h): one 256 x 256 map of workloads.random_blocks on
+0.05 m cells at amplitude 0.02 m (the reference simulation's `random1` recipe; the amplitude both closed-loop ladders walk),
+shared by the fleet, the robots' start positions spread over 13 x 13 patches of it; swing feet clamped to the surface and,
+for --source plant, the height re-based, as with --terrain.  It combines with --terrain (the field lies on the slopes and
+stairs), --contact and --vary: the step then runs the kernels of csrc/qmpc_field.hip.
 
 --source sensor closes the same loop through the SENSOR path: qmpc_ctrl_tick -- the VectorNav orientation estimator and
 the Kalman filter -- on the readings of the sensor model (include/qmpc_sense.h), qmpc_plant_step on the tick's efforts,
@@ -44,8 +49,8 @@ accelerometer and gyro biases (within +-0.2 m/s^2, +-0.02 rad/s) and white noise
 0.002 rad and 0.05 rad/s: the levels the closed-loop tests walk on); without it the sensors are ideal.
 
     python tools/ctrl_bench.py [--batches 1024,4096,16384] [--cycles 8] [--warmup 26] [--schedule lockstep|per_robot]
-                               [--stagger] [--robot-mode 0|1] [--source imu|state|plant|sensor] [--vary] [--terrain] [--contact] [--noise]
-                               [--out FILE]
+                               [--stagger] [--robot-mode 0|1] [--source imu|state|plant|sensor] [--vary] [--terrain] [--contact] [--field]
+                               [--noise] [--out FILE]
 """
 import argparse
 import json
@@ -59,7 +64,7 @@ sys.path.insert(0, ROOT)
 
 
 def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, source="imu", vary=False, noise=False, terrain=False,
-        contact=False):
+        contact=False, field=False):
     import torch
     from quadruped_ctrl_amd import workloads as W
     from quadruped_ctrl_amd.binding import BatchedController
@@ -116,6 +121,13 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
             rows[kind == 1, 2], rows[kind == 3, 1] = 0.15, 0.15
             rows = torch.from_numpy(rows).cuda()
             plant.set_terrain(rows, clamp_swing=True, rebase_z=source == "plant")
+        if field:
+            k = np.arange(B)
+            place = np.stack([np.zeros(B), xyyaw[:, 0] - (1.5 + 0.75 * (k % 13)), xyyaw[:, 1] - (1.5 + 0.75 * (k // 13 % 13)),
+                              np.ones(B)], 1)
+            zmap, place = torch.from_numpy(W.random_blocks(B, amp=0.02)[None]).cuda(), torch.from_numpy(place).cuda()
+            plant.set_field(zmap, place, 0.05, clamp_swing=True, rebase_z=source == "plant")
+        if terrain or field:
             plant.reset(torch.ones(B, dtype=torch.bool, device="cuda"), torch.from_numpy(xyyaw).cuda())
         if contact:
             plant.set_contact(early=True, late=True, slip=True)
@@ -187,6 +199,10 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
         t_ = plant.terrain()
         res.update({"terrain": True, "support_min": round(float(t_["support"].min().item()), 4),
                     "support_max": round(float(t_["support"].max().item()), 4)})
+    if field:
+        f_ = plant.field()
+        res.update({"field": True, "field_samples": [f_["count"], f_["ny"], f_["nx"]], "ground_min": round(float(plant.terrain()["ground"].min().item()), 4),
+                    "ground_max": round(float(plant.terrain()["ground"].max().item()), 4)})
     if contact:
         c_ = plant.contact()
         res.update({"contact": True, "early_foot_ticks": int(c_["early"].sum().item()), "late_foot_ticks": int(c_["late"].sum().item()),
@@ -224,6 +240,7 @@ def main():
     ap.add_argument("--vary", action="store_true")
     ap.add_argument("--terrain", action="store_true")
     ap.add_argument("--contact", action="store_true")
+    ap.add_argument("--field", action="store_true")
     ap.add_argument("--noise", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -233,6 +250,8 @@ def main():
         ap.error("--terrain needs --source plant or sensor")
     if a.contact and a.source not in ("plant", "sensor"):
         ap.error("--contact needs --source plant or sensor")
+    if a.field and a.source not in ("plant", "sensor"):
+        ap.error("--field needs --source plant or sensor")
     if a.noise and a.source != "sensor":
         ap.error("--noise needs --source sensor")
     if a.robot_mode == 1:
@@ -241,7 +260,7 @@ def main():
         ap.error("--stagger needs --schedule per_robot (a lockstep reset keeps the robot on the batch's MPC ticks)")
     out = []
     for B in [int(x) for x in a.batches.split(",")]:
-        r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source, a.vary, a.noise, a.terrain, a.contact)
+        r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source, a.vary, a.noise, a.terrain, a.contact, a.field)
         print(json.dumps(r), flush=True)
         out.append(r)
     if a.out:
