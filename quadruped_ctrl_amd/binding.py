@@ -148,6 +148,36 @@ class SenseView(C.Structure):
     _fields_ = [("n", C.c_void_p), ("epoch", C.c_void_p), ("batch", C.c_int), ("seed", C.c_uint64)]
 
 
+# qmpc_episode_view's arrays (include/qmpc_episode.h) in declaration order: name -> (elements per robot or None, typestr)
+EPISODE_VIEW_FIELDS = dict(age=(None, "<i4"), episode=(None, "<i4"), start=(2, "<f8"), count=(6, "<i4"),
+                           ticks_sum=(None, "<i8"), last_cause=(None, "<i4"), last_ticks=(None, "<i4"), mask=(None, "|u1"),
+                           xyyaw=(3, "<f8"))
+EP_UNSAFE, EP_NONFINITE, EP_TILT, EP_HEIGHT, EP_RANGE, EP_TIMEOUT = 1, 2, 4, 8, 16, 32
+EP_CAUSES = dict(unsafe=EP_UNSAFE, nonfinite=EP_NONFINITE, tilt=EP_TILT, height=EP_HEIGHT, range=EP_RANGE,
+                 timeout=EP_TIMEOUT)   # in bit order: the columns of the view's count
+EP_SPAWN_PER_ROBOT = 1
+EPISODE_LOG_COLUMNS = ("robot", "episode", "cause", "age", "dx", "dy", "height", "tilt")
+
+
+class EpisodeRule(C.Structure):
+    """qmpc_episode_rule (include/qmpc_episode.h)."""
+    _fields_ = [("causes", C.c_int), ("max_ticks", C.c_int), ("cos_tilt_min", C.c_double), ("z_min", C.c_double),
+                ("range", C.c_double)]
+
+
+class EpisodeBind(C.Structure):
+    """qmpc_episode_bind (include/qmpc_episode.h)."""
+    _fields_ = [("vel", C.c_void_p), ("gait", C.c_void_p), ("spawn", C.c_void_p), ("commands", C.c_void_p),
+                ("log", C.c_void_p), ("n_spawn", C.c_int), ("n_commands", C.c_int), ("log_rows", C.c_int),
+                ("flags", C.c_int)]
+
+
+class EpisodeView(C.Structure):
+    """qmpc_episode_view (include/qmpc_episode.h)."""
+    _fields_ = [(n, C.c_void_p) for n in EPISODE_VIEW_FIELDS] + [("log_count", C.c_void_p), ("log_dropped", C.c_void_p),
+                                                                 ("batch", C.c_int), ("seed", C.c_uint64)]
+
+
 class LegCommand(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in LEG_F32] + [("kp_joint", C.c_float), ("kd_joint", C.c_float)]
 
@@ -284,6 +314,14 @@ SENSE_SIGNATURES = {
     "qmpc_sense": [_P, _I, _P, _P, _P],
     "qmpc_sense_view_get": [_P, C.POINTER(SenseView)],
 }
+# episodes on the device: termination, respawn, result log (include/qmpc_episode.h), same library and ABI version
+EPISODE_SIGNATURES = {
+    "qmpc_episode_init": [_P, _I, C.c_uint64, _P],
+    "qmpc_episode_set": [_P, _I, C.POINTER(EpisodeRule), C.POINTER(EpisodeBind)],
+    "qmpc_episode_step": [_P, _I, _I, _P],
+    "qmpc_episode_log_clear": [_P, _P],
+    "qmpc_episode_view_get": [_P, C.POINTER(EpisodeView)],
+}
 EXPORTS = list(SIGNATURES)
 CTRL_EXPORTS = list(CTRL_SIGNATURES)
 PLANT_EXPORTS = list(PLANT_SIGNATURES)
@@ -292,6 +330,7 @@ SENSE_EXPORTS = list(SENSE_SIGNATURES)
 TERRAIN_EXPORTS = list(TERRAIN_SIGNATURES)
 CONTACT_EXPORTS = list(CONTACT_SIGNATURES)
 FIELD_EXPORTS = list(FIELD_SIGNATURES)
+EPISODE_EXPORTS = list(EPISODE_SIGNATURES)
 
 _lib = None
 
@@ -326,7 +365,7 @@ def load_library():
                 "(python -c 'import __graft_entry__ as g; g.build()')")
         lib = C.CDLL(LIB_PATH)
         for name, sig in {**SIGNATURES, **CTRL_SIGNATURES, **PLANT_SIGNATURES, **PLANT_VARY_SIGNATURES, **TERRAIN_SIGNATURES,
-                          **CONTACT_SIGNATURES, **FIELD_SIGNATURES, **SENSE_SIGNATURES}.items():
+                          **CONTACT_SIGNATURES, **FIELD_SIGNATURES, **SENSE_SIGNATURES, **EPISODE_SIGNATURES}.items():
             f = getattr(lib, name)
             f.argtypes, f.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
         _lib = lib
@@ -1127,6 +1166,105 @@ class BatchedSensors:
                                 ("batch", "seed"))
 
 
+class BatchedEpisodes:
+    """The episode manager of include/qmpc_episode.h for a BatchedPlant's robots: step() decides on the device which
+    robots are done (latched, not finite, tilted, too low, out of range, timed out), logs how each run ended, draws
+    where the robot starts again and what it is told next, and resets controller, commands, plant and statistics for
+    exactly those robots -- tick_state -> plant.step -> episodes.step is a closed loop in which robots fall and get up
+    without the host (see rollout_episodes()).
+
+    Constructed FROM a plant (the manager lives in the same handle), after plant.init().  Every call only enqueues on
+    the current stream (or `stream`); log() synchronises.  `vel` / `gait` are the fleet's commands as bound by set():
+    the manager hands them to the controller at every step and rewrites a reset robot's rows."""
+
+    def __init__(self, plant):
+        self.plant, self.ctrl = plant, plant.ctrl
+        self.torch, self.lib, self.device = plant.torch, plant.lib, plant.device
+        self.batch = None
+        self._bound = {}
+
+    def init(self, seed=0, stream=None):
+        """Ages, episode numbers, counters and the log's words zero, start = the plant's x, y, the draws' 64-bit seed;
+        no rule, nothing bound."""
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.ctrl._call("qmpc_episode_init", self.plant.batch or 0, seed, self.ctrl._s(stream))
+        self.batch = self.plant.batch
+        self._bound = {}
+        self.vel = self.gait = None
+
+    def set(self, vel, gait, spawn, commands=None, log_rows=0, causes=0, max_ticks=0, cos_tilt_min=float("nan"),
+            z_min=float("nan"), range=float("nan")):
+        """The rule and the bindings.  causes: an int of EP_* bits or an iterable of EP_CAUSES' names; a threshold that
+        is not finite switches its criterion off.  vel [B,3] float64 and gait [B] int32 are the fleet's commands (the
+        tensors ctrl.set_vel / set_gait were given, or copies); spawn float64 [S,3] of (x, y, yaw), or [B,S,3] for a
+        table per robot; commands float64 [C,4] of (vx, vy, yaw rate, gait number) or None: a reset robot keeps its
+        commands; log_rows > 0 allocates the log [log_rows, 8] (see log()).  The tensors are read and written at every
+        later step() -- rewrite them in place (on the stream), also between replays of a captured graph; they are kept
+        referenced here.  Host state only."""
+        if self.batch is None:
+            raise QmpcError("qmpc_episode_set before init()")
+        t = self.torch
+        if not isinstance(causes, int):
+            causes = sum(EP_CAUSES[k] for k in causes)
+        B = self.batch
+        bind = EpisodeBind()
+        bind.vel = self.ctrl._chk(vel, (B, 3), t.float64, "vel")
+        bind.gait = self.ctrl._chk(gait, (B,), t.int32, "gait")
+        per_robot = spawn is not None and spawn.dim() == 3
+        if spawn is None or spawn.dim() not in (2, 3) or spawn.shape[-1] != 3 or (per_robot and spawn.shape[0] != B):
+            raise QmpcError(f"spawn: expected a float64 tensor of shape (S, 3) or ({B}, S, 3)")
+        bind.spawn = self.ctrl._chk(spawn, tuple(spawn.shape), t.float64, "spawn")
+        bind.n_spawn = int(spawn.shape[-2])
+        bind.flags = EP_SPAWN_PER_ROBOT if per_robot else 0
+        if commands is not None:
+            if commands.dim() != 2:
+                raise QmpcError("commands: expected a float64 tensor of shape (C, 4)")
+            bind.commands = self.ctrl._chk(commands, (commands.shape[0], 4), t.float64, "commands")
+            bind.n_commands = int(commands.shape[0])
+        log = None
+        if int(log_rows) > 0:
+            log = self._bound.get("log")
+            if log is None or log.shape[0] != int(log_rows):
+                log = t.zeros((int(log_rows), 8), dtype=t.float64, device=self.device)
+            bind.log = log.data_ptr()
+        bind.log_rows = int(log_rows)
+        rule = EpisodeRule(int(causes), int(max_ticks), float(cos_tilt_min), float(z_min), float(range))
+        self.ctrl._call("qmpc_episode_set", B, C.byref(rule), C.byref(bind))
+        self._bound = dict(vel=vel, gait=gait, spawn=spawn, commands=commands, log=log)
+        self.vel, self.gait = vel, gait
+
+    def step(self, elapsed=1, stream=None):
+        """After plant.step(): `elapsed` control periods have passed since the previous step()."""
+        if self.batch is None:
+            raise QmpcError("qmpc_episode_step before init()")
+        self.ctrl._call("qmpc_episode_step", self.batch, int(elapsed), self.ctrl._s(stream))
+
+    def clear_log(self, stream=None):
+        """The log starts again at its row 0, dropped = 0 (on the stream)."""
+        self.ctrl._call("qmpc_episode_log_clear", self.ctrl._s(stream))
+
+    def view(self):
+        """qmpc_episode_view_get as zero-copy device tensors that alias the manager's state, like BatchedPlant.view():
+        age, episode, last_cause, last_ticks ([B] int32), ticks_sum ([B] int64), start ([B,2] float64), count ([B,6]
+        int32, one column per cause in bit order), mask ([B] uint8), xyyaw ([B,3] float64), log_count and log_dropped
+        ([1] int32); plus batch, seed.  Read-only by contract."""
+        res = self.ctrl._views("qmpc_episode_view_get", EpisodeView, EPISODE_VIEW_FIELDS,
+                               ("log_count", "log_dropped", "batch", "seed"))
+        for k in ("log_count", "log_dropped"):
+            res[k] = self.torch.as_tensor(_DeviceArray(res[k], (1,), "<i4", self.ctrl), device=self.device)
+        return res
+
+    def log(self):
+        """-> dict(rows, dropped): the rows written so far, copied to the host (synchronises) and sorted by (robot,
+        episode) -- float64 [n, 8] in EPISODE_LOG_COLUMNS' order --, and how many rows found the log full."""
+        v = self.view()
+        self.torch.cuda.synchronize(self.device)
+        n, dropped = int(v["log_count"].cpu()[0]), int(v["log_dropped"].cpu()[0])
+        log = self._bound.get("log")
+        rows = np.zeros((0, 8)) if log is None else log[:n].cpu().numpy().copy()
+        return dict(rows=rows[np.lexsort((rows[:, 1], rows[:, 0]))], dropped=dropped)
+
+
 def _run_ticks(ctrl, who, ticks, graph, tick):
     """The runner behind rollout() and rollout_sensed() (`who`: the caller's name, which starts its messages): tick()
     `ticks` times on the current stream, or that block captured on a side stream and replayed once -> the graph, or None."""
@@ -1183,3 +1321,26 @@ def rollout_sensed(ctrl, plant, sensors, ticks, graph=False):
 
     g = _run_ticks(ctrl, "rollout_sensed", ticks, graph, tick)
     return dict(effort=plant.effort, state=plant.state, motor=plant.motor, imu=sensors.imu, graph=g)
+
+
+def rollout_episodes(ctrl, plant, episodes, ticks, graph=False, every=1):
+    """rollout() with the episode manager in the loop: `ticks` closed-loop ticks ctrl.tick_state(plant.state,
+    plant.motor) -> plant.step(effort), and after every `every`-th tick of this call episodes.step(elapsed=every).
+    graph=True as in rollout(): the block is captured and replayed once, the graph returned for further replays; in
+    lockstep a captured block holds a multiple of 13 ticks.  `ticks` must be a multiple of `every`, so that consecutive
+    calls and replays check at the same spacing.
+    -> dict(effort, state, motor, graph): the plant's own tensors, as the last tick left them."""
+    every = int(every)
+    if every < 1 or int(ticks) % every != 0:
+        raise QmpcError(f"rollout_episodes: ticks ({ticks}) must be a multiple of every ({every}) >= 1")
+    n = [0]
+
+    def tick():
+        ctrl.tick_state(plant.state, plant.motor, plant.effort)
+        plant.step(plant.effort)
+        n[0] += 1
+        if n[0] % every == 0:
+            episodes.step(every)
+
+    g = _run_ticks(ctrl, "rollout_episodes", ticks, graph, tick)
+    return dict(effort=plant.effort, state=plant.state, motor=plant.motor, graph=g)

@@ -26,12 +26,14 @@
 #include "../../include/qmpc_contact.h"  // ... contact decided by the ground
 #include "../../include/qmpc_field.h"    // ... height-field terrain from memory
 #include "../../include/qmpc_sense.h"   // sensor model between the plant and the controller's sensor path
+#include "../../include/qmpc_episode.h"  // episodes on the device: termination, respawn, result log
 #include "qmpc_device.h"
 #include "qmpc_glue.h"    // each launcher is declared once, in the header its defining file includes too:
-#include "qmpc_launch.h"  // qmpc_glue.h, qmpc_plant.h, qmpc_sense.h, and qmpc_launch.h for the rest
+#include "qmpc_launch.h"  // qmpc_glue.h, qmpc_plant.h, qmpc_sense.h, qmpc_episode.h, and qmpc_launch.h for the rest
 #include "qmpc_plan.h"  // the solve's launch plan (host-only)
 #include "qmpc_plant.h"
 #include "qmpc_sense.h"
+#include "qmpc_episode.h"
 static_assert(kLongHorizon == QMPC_LONG_HORIZON, "qmpc_plan.h and qmpc.h disagree");
 
 extern "C" size_t qmpc_smem_bytes(int rb) {
@@ -249,6 +251,18 @@ struct __attribute__((visibility("hidden"))) qmpc_ctx {
     bool bound = false;
   };
   std::unique_ptr<Sense> sense;
+  // episode manager (qmpc_episode.h): the per-robot state and the two log words in one allocation made by
+  // qmpc_episode_init, the seed, and the rule and the caller's arrays as set (is_set: qmpc_episode_set has been called)
+  struct Episode {
+    QmpcEpisodeDev d{};
+    DevBuf<char> buf;
+    int batch = 0;  // robots initialised
+    uint64_t seed = 0;
+    qmpc_episode_rule rule{};
+    qmpc_episode_bind bind{};
+    bool is_set = false;
+  };
+  std::unique_ptr<Episode> episode;
   // (the device arrays and the sub-states free themselves)
   ~qmpc_ctx() {
     if (h_pin) hipHostFree(h_pin);
@@ -1229,6 +1243,12 @@ size_t carve(QmpcPlantDev& d, char* base, int M) {
   QMPC_PLANT_ARRAYS(QMPC_CARVE)
   return off;
 }
+size_t carve(QmpcEpisodeDev& d, char* base, int M) {
+  size_t off = 0;
+  QMPC_EPISODE_ARRAYS(QMPC_CARVE)
+  carve_array(d.log_words, base, off, 2, 1);
+  return off;
+}
 #undef QMPC_CARVE
 
 // d's arrays as views into buf, which is allocated on first use (a later init of the same handle reuses the block)
@@ -1249,6 +1269,17 @@ int ctrl_check(qmpc_ctx* c, int batch) {
   if (!c) return QMPC_ERR_ARG;
   if (!ctrl_ready(c)) return QMPC_ERR_STATE;
   if (batch != c->ctrl->batch) return QMPC_ERR_ARG;
+  return QMPC_OK;
+}
+
+// The controller's reset of the masked robots (qmpc_ctrl_reset, and the episode manager's): in lockstep the counter
+// restarts at T mod 13 (the batch keeps solving on the same ticks), with the per-robot schedule at 0, as init_controller
+// leaves it.  The caller holds the DeviceGuard and has ordered the stream.
+int ctrl_reset_enqueue(qmpc_ctx* c, int batch, const uint8_t* mask_dev, hipStream_t stream) {
+  qmpc_ctx::Ctrl* k = c->ctrl.get();
+  k->started = true;
+  const int counter0 = k->schedule == QMPC_CTRL_PER_ROBOT ? 0 : (int)(k->ticks % 13);
+  HIP_TRY(c, qmpc_launch_ctrl_init(&k->d, mask_dev, counter0, batch, stream));
   return QMPC_OK;
 }
 
@@ -1359,13 +1390,7 @@ int qmpc_ctrl_reset(qmpc_handle c, int batch, const uint8_t* mask_dev, void* str
   if (!mask_dev) return QMPC_ERR_ARG;
   const Enqueue q(c, stream_);
   if (q.rc) return q.rc;
-  // lockstep: the counter restarts at T mod 13 (the batch keeps solving on the same ticks); per-robot schedule: at 0, as
-  // init_controller leaves it
-  qmpc_ctx::Ctrl* k = c->ctrl.get();
-  k->started = true;
-  const int counter0 = k->schedule == QMPC_CTRL_PER_ROBOT ? 0 : (int)(k->ticks % 13);
-  HIP_TRY(c, qmpc_launch_ctrl_init(&k->d, mask_dev, counter0, batch, q.stream));
-  return QMPC_OK;
+  return ctrl_reset_enqueue(c, batch, mask_dev, q.stream);
 }
 
 int qmpc_ctrl_set_schedule(qmpc_handle c, int mode) {
@@ -1514,6 +1539,26 @@ int plant_check(qmpc_ctx* c, int batch) {
   return QMPC_OK;
 }
 
+// The plant's reset of the masked robots on whatever ground is bound (qmpc_plant_reset, and the episode manager's).  The
+// caller holds the DeviceGuard and has ordered the stream.
+int plant_reset_enqueue(qmpc_ctx* c, int batch, const uint8_t* mask_dev, const double* init_xyyaw, hipStream_t stream) {
+  const QmpcPlantConst K = plant_const(c, c->plant->mu, c->plant->substeps);
+  const qmpc_ctx::Plant* k = c->plant.get();
+  if (k->field.z) {
+    // (the counters' reset first: with no rows bound it zeroes support and ground, which the field's reset then writes)
+    if (k->contact.flags) HIP_TRY(c, qmpc_launch_contact_reset(mask_dev, batch, stream, &k->terrain, &k->contact));
+    const QmpcTerrainArgs T = k->field_terrain();
+    HIP_TRY(c, qmpc_launch_field_init(&k->d, &K, mask_dev, init_xyyaw, batch, stream, &T, &k->field));
+    return QMPC_OK;
+  }
+  if (k->terrain.rows)
+    HIP_TRY(c, qmpc_launch_terrain_init(&k->d, &K, mask_dev, init_xyyaw, batch, stream, &k->terrain));
+  else
+    HIP_TRY(c, qmpc_launch_plant_init(&k->d, &K, mask_dev, init_xyyaw, batch, stream));
+  if (k->contact.flags) HIP_TRY(c, qmpc_launch_contact_reset(mask_dev, batch, stream, &k->terrain, &k->contact));
+  return QMPC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1578,21 +1623,7 @@ int qmpc_plant_reset(qmpc_handle c, int batch, const uint8_t* mask_dev, const do
   if (!mask_dev) return QMPC_ERR_ARG;
   const Enqueue q(c, stream_);
   if (q.rc) return q.rc;
-  const QmpcPlantConst K = plant_const(c, c->plant->mu, c->plant->substeps);
-  const qmpc_ctx::Plant* k = c->plant.get();
-  if (k->field.z) {
-    // (the counters' reset first: with no rows bound it zeroes support and ground, which the field's reset then writes)
-    if (k->contact.flags) HIP_TRY(c, qmpc_launch_contact_reset(mask_dev, batch, q.stream, &k->terrain, &k->contact));
-    const QmpcTerrainArgs T = k->field_terrain();
-    HIP_TRY(c, qmpc_launch_field_init(&k->d, &K, mask_dev, init_xyyaw, batch, q.stream, &T, &k->field));
-    return QMPC_OK;
-  }
-  if (k->terrain.rows)
-    HIP_TRY(c, qmpc_launch_terrain_init(&k->d, &K, mask_dev, init_xyyaw, batch, q.stream, &k->terrain));
-  else
-    HIP_TRY(c, qmpc_launch_plant_init(&k->d, &K, mask_dev, init_xyyaw, batch, q.stream));
-  if (k->contact.flags) HIP_TRY(c, qmpc_launch_contact_reset(mask_dev, batch, q.stream, &k->terrain, &k->contact));
-  return QMPC_OK;
+  return plant_reset_enqueue(c, batch, mask_dev, init_xyyaw, q.stream);
 }
 
 int qmpc_plant_step(qmpc_handle c, int batch, const double* effort, double* state_out, double* motor_out,
@@ -1898,6 +1929,106 @@ int qmpc_sense_view_get(qmpc_handle c, qmpc_sense_view* v) {
   v->epoch = c->sense->a.epoch;
   v->batch = c->sense->batch;
   v->seed = c->sense->seed;
+  return QMPC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
+// Episode manager (include/qmpc_episode.h).  The kernels are in qmpc_episode.hip.
+namespace {
+
+int episode_check(qmpc_ctx* c, int batch) {
+  if (const int rc = plant_check(c, batch)) return rc;
+  if (!c->episode || !c->episode->batch) return QMPC_ERR_STATE;
+  if (batch != c->episode->batch) return QMPC_ERR_ARG;
+  return QMPC_OK;
+}
+
+const int kEpisodeCauses = QMPC_EP_UNSAFE | QMPC_EP_NONFINITE | QMPC_EP_TILT | QMPC_EP_HEIGHT | QMPC_EP_RANGE | QMPC_EP_TIMEOUT;
+
+}  // namespace
+
+extern "C" {
+
+int qmpc_episode_init(qmpc_handle c, int batch, uint64_t seed, void* stream_) {
+  if (const int rc = plant_check(c, batch)) return rc;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!c->episode) c->episode.reset(new qmpc_ctx::Episode());
+  qmpc_ctx::Episode* k = c->episode.get();
+  HIP_TRY(c, carve_block(k->buf, k->d, c->max_batch));
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  HIP_TRY(c, qmpc_launch_episode_init(&k->d, c->plant->d.p, batch, c->max_batch, stream));
+  k->rule = qmpc_episode_rule{};
+  k->bind = qmpc_episode_bind{};
+  k->is_set = false;
+  k->seed = seed;
+  k->batch = batch;
+  return QMPC_OK;
+}
+
+int qmpc_episode_set(qmpc_handle c, int batch, const qmpc_episode_rule* rule, const qmpc_episode_bind* bind) {
+  if (const int rc = episode_check(c, batch)) return rc;
+  if (!rule || !bind) return QMPC_ERR_ARG;
+  if ((rule->causes & ~kEpisodeCauses) || (bind->flags & ~QMPC_EP_SPAWN_PER_ROBOT)) return QMPC_ERR_ARG;
+  if (!bind->vel || !bind->gait || !bind->spawn || bind->n_spawn < 1) return QMPC_ERR_ARG;
+  if ((bind->commands && bind->n_commands < 1) || bind->log_rows < 0) return QMPC_ERR_ARG;
+  qmpc_ctx::Episode* k = c->episode.get();
+  k->rule = *rule;
+  k->bind = *bind;
+  k->is_set = true;
+  return QMPC_OK;
+}
+
+int qmpc_episode_step(qmpc_handle c, int batch, int elapsed, void* stream_) {
+  if (const int rc = episode_check(c, batch)) return rc;
+  qmpc_ctx::Episode* k = c->episode.get();
+  if (!k->is_set) return QMPC_ERR_STATE;
+  if (elapsed < 1) return QMPC_ERR_ARG;
+  if (!k->rule.causes) return QMPC_OK;  // the manager is off: nothing is enqueued
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  const qmpc_ctx::Plant* pl = c->plant.get();
+  // the plant writes ground[b] on terrain, on a field and with contact on (there 0 without rows); the flat plant never does
+  const bool ground = pl->terrain.rows || pl->field.z || pl->contact.flags;
+  const QmpcEpisodeIn in{pl->d.p, pl->d.q, c->ctrl->d.safe, ground ? pl->terrain.ground : nullptr,
+                         (uint32_t)(k->seed & 0xFFFFFFFFu), (uint32_t)(k->seed >> 32)};
+  HIP_TRY(c, qmpc_launch_episode_decide(&k->d, &in, &k->rule, &k->bind, elapsed, batch, q.stream));
+  // the existing resets under the kernel's mask: controller, its commands (the reset zeroed them), plant, statistics
+  if (const int rc = ctrl_reset_enqueue(c, batch, k->d.mask, q.stream)) return rc;
+  HIP_TRY(c, qmpc_launch_ctrl_set(&c->ctrl->d, k->bind.gait, k->bind.vel, batch, q.stream));
+  if (const int rc = plant_reset_enqueue(c, batch, k->d.mask, k->d.xyyaw, q.stream)) return rc;
+  if (pl->stats_on) HIP_TRY(c, qmpc_launch_plant_stats_reset(&pl->vary, k->d.mask, batch, q.stream));
+  return QMPC_OK;
+}
+
+int qmpc_episode_log_clear(qmpc_handle c, void* stream_) {
+  if (!c) return QMPC_ERR_ARG;
+  if (!ctrl_ready(c) || !plant_ready(c) || !c->episode || !c->episode->batch) return QMPC_ERR_STATE;
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  HIP_TRY(c, qmpc_launch_episode_log_clear(&c->episode->d, q.stream));
+  return QMPC_OK;
+}
+
+int qmpc_episode_view_get(qmpc_handle c, qmpc_episode_view* v) {
+  if (!c || !v) return QMPC_ERR_ARG;
+  if (!plant_ready(c) || !c->episode || !c->episode->batch) return QMPC_ERR_STATE;
+  const QmpcEpisodeDev& d = c->episode->d;
+  v->age = d.age;
+  v->episode = d.episode;
+  v->start = d.start;
+  v->count = d.count;
+  v->ticks_sum = d.ticks_sum;
+  v->last_cause = d.last_cause;
+  v->last_ticks = d.last_ticks;
+  v->mask = d.mask;
+  v->xyyaw = d.xyyaw;
+  v->log_count = d.log_words;
+  v->log_dropped = d.log_words + 1;
+  v->batch = c->episode->batch;
+  v->seed = c->episode->seed;
   return QMPC_OK;
 }
 

@@ -1,5 +1,6 @@
 // qmpc_launch.h -- launchers that qmpc_capi.cpp calls and that have no per-unit header of their own (those of
-// qmpc_glue.hip, qmpc_plant.hip and qmpc_sense.hip are declared in qmpc_glue.h, qmpc_plant.h and qmpc_sense.h).
+// qmpc_glue.hip, qmpc_plant.hip, qmpc_sense.hip and qmpc_episode.hip are declared in qmpc_glue.h, qmpc_plant.h, qmpc_sense.h
+// and qmpc_episode.h).
 #ifndef QMPC_LAUNCH_H
 #define QMPC_LAUNCH_H
 

@@ -7,35 +7,16 @@
 // No LDS, no atomics, no shuffles.  fp contraction is off: tests/sense_model.py restates every expression in the same
 // order and agrees bit for bit (integer arithmetic up to the one conversion, then a subtraction and a multiplication).
 // <false> is the ideal sensor: nothing bound, no generator call.
+#include "qmpc_philox.h"  // Random123's Philox4x32 with ten rounds
 #include "qmpc_sense.h"
 
 namespace {
-
-// Random123's Philox4x32 with ten rounds
-__device__ __forceinline__ void sense_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                             uint32_t k1, uint32_t* w) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  w[0] = c0;
-  w[1] = c1;
-  w[2] = c2;
-  w[3] = c3;
-}
 
 // the centred sum of the four words, scaled to unit variance: |z| <= 2 sqrt(3)
 __device__ __forceinline__ double sense_z(const QmpcSenseArgs& A, int b, int n, int channel, int epoch) {
 #pragma clang fp contract(off)
   uint32_t w[4];
-  sense_philox((uint32_t)b, (uint32_t)n, (uint32_t)channel, (uint32_t)epoch, A.key0, A.key1, w);
+  qmpc_philox4x32_10((uint32_t)b, (uint32_t)n, (uint32_t)channel, (uint32_t)epoch, A.key0, A.key1, w);
   const uint64_t s = ((uint64_t)w[0] + (uint64_t)w[1]) + ((uint64_t)w[2] + (uint64_t)w[3]);
   return ((double)s - 8589934590.0) * (1.7320508075688772 * 0x1p-32);
 }

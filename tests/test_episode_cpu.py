@@ -1,0 +1,242 @@
+"""CPU suite for the episode manager (include/qmpc_episode.h): the exported surface, the decision and the draw of
+csrc/qmpc_episode_rule.h under the sanitizers in a stand-alone host program against the numpy restatement
+tests/episode_model.py -- the model the GPU suite (tests/test_gpu_episode.py) holds the kernels to --, the draws' coverage
+of both tables, the model's bookkeeping, and the compiled kernels' resources."""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import episode_model as EM
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+no_hipcc = pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="no hipcc")
+INT_MAX = 2 ** 31 - 1
+
+
+def _decl(name):
+    return set(re.findall(r"^int (qmpc_\w+)\(", open(os.path.join(ROOT, "include", name)).read(), re.M))
+
+
+def _members(hdr, struct):
+    body = re.search(r"typedef struct \{([^}]*)\} %s;" % struct, hdr).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    return [n for decl in body.split(";") if decl.strip() for n in re.findall(r"(\w+)\s*(?:,|$)", decl.strip())]
+
+
+def test_episode_symbols_exported_and_abi_version_kept():
+    from quadruped_ctrl_amd import binding
+    lib = binding.load_library()
+    hdr = open(os.path.join(ROOT, "include", "qmpc_episode.h")).read()
+    want = {"qmpc_episode_init", "qmpc_episode_set", "qmpc_episode_step", "qmpc_episode_log_clear", "qmpc_episode_view_get"}
+    assert _decl("qmpc_episode.h") == want == set(binding.EPISODE_EXPORTS)
+    for name in want:
+        assert hasattr(lib, name), name
+    assert lib.qmpc_abi_version() == binding.ABI_VERSION == 23
+    assert _members(hdr, "qmpc_episode_rule") == [n for n, _ in binding.EpisodeRule._fields_]
+    assert _members(hdr, "qmpc_episode_bind") == [n for n, _ in binding.EpisodeBind._fields_]
+    assert _members(hdr, "qmpc_episode_view") == [n for n, _ in binding.EpisodeView._fields_]
+    for k, name in enumerate(EM.NAMES):
+        bit = int(re.search(r"#define QMPC_EP_%s (\d+)" % name.upper(), hdr).group(1))
+        assert bit == 1 << k == binding.EP_CAUSES[name] == getattr(EM, name.upper())
+    assert list(binding.EP_CAUSES) == list(EM.NAMES)
+    # the older headers still declare exactly what they declared
+    assert _decl("qmpc_sense.h") == set(binding.SENSE_EXPORTS) and _decl("qmpc_plant.h") == set(binding.PLANT_EXPORTS)
+    # without a device every entry point refuses a null handle
+    assert lib.qmpc_episode_init(None, 4, 0, None) == 1 and lib.qmpc_episode_step(None, 4, 1, None) == 1
+    assert lib.qmpc_episode_log_clear(None, None) == 1 and lib.qmpc_episode_view_get(None, None) == 1
+
+
+def test_one_philox_in_the_tree():
+    """The generator is defined once, in csrc/qmpc_philox.h, and both users include it."""
+    csrc = os.path.join(ROOT, "quadruped_ctrl_amd", "csrc")
+    holders = [f for f in sorted(os.listdir(csrc)) if os.path.isfile(os.path.join(csrc, f))
+               and "0xD2511F53" in open(os.path.join(csrc, f)).read()]
+    assert holders == ["qmpc_philox.h"]
+    for f in ("qmpc_sense.hip", "qmpc_episode_rule.h"):
+        assert '#include "qmpc_philox.h"' in open(os.path.join(csrc, f)).read(), f
+
+
+# ---- the decision and the draw, on the CPU under the sanitizers ---------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def dump(tmp_path_factory):
+    """tests/episode_rule_dump.cpp: csrc/qmpc_episode_rule.h alone, host only, built with AddressSanitizer and UBSan and run
+    directly -> (its C lines, its D lines, its G lines) as arrays."""
+    exe = str(tmp_path_factory.mktemp("episode") / "episode_rule_dump")
+    # host code only (-x c++: no device pass), and the sanitizers named for the host side alone
+    subprocess.run([HIPCC, "-x", "c++", "-std=c++17", "-Wall", "-Werror", "-g", "-Xarch_host", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", os.path.join(ROOT, "tests", "episode_rule_dump.cpp"), "-o", exe],
+                   check=True)
+    syms = subprocess.run(["nm", exe], capture_output=True, text=True, check=True).stdout
+    assert "__asan_init" in syms and "__ubsan_handle" in syms              # both runtimes are linked in
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0, run.stderr[-2000:]
+    assert "runtime error" not in run.stderr and "Sanitizer" not in run.stderr and run.stderr.startswith("checksum"), run.stderr[-2000:]
+    lines = run.stdout.splitlines()
+    c = np.array([ln.split()[1:] for ln in lines if ln.startswith("C ")], dtype=np.float64)
+    d = np.array([ln.split()[1:] for ln in lines if ln.startswith("D ")], dtype=np.int64)
+    g = np.array([ln.split()[1:] for ln in lines if ln.startswith("G ")], dtype=np.float64)
+    return c, d, g
+
+
+def _same_bits(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return np.array_equal(a.view(np.uint64)[~np.isnan(a)], b.view(np.uint64)[~np.isnan(a)]) and np.array_equal(np.isnan(a), np.isnan(b))
+
+
+@no_hipcc
+def test_rule_header_decides_what_the_model_decides(dump):
+    """Every threshold at its boundary and one ulp either side, NaN and +-inf in every field of p, q, ground, start and
+    each threshold, ages at max_ticks - 1, max_ticks, max_ticks + 1 and at the end of int, elapsed 1 and 13, under ten
+    cause sets: the cause bits, the age and the four facts of the log row are the model's, bit for bit."""
+    c = dump[0]
+    assert len(c) > 5000 and c.shape[1] == 24
+    causes, max_ticks = c[:, 0].astype(int), c[:, 1].astype(np.int64)
+    thr, safe, p, q, ground, start = c[:, 2:5], c[:, 5], c[:, 6:9], c[:, 9:13], c[:, 13], c[:, 14:16]
+    age_in, elapsed, age, cause, facts = c[:, 16].astype(np.int64), c[:, 17].astype(int), c[:, 18], c[:, 19], c[:, 20:24]
+    # the inputs are what the docstring says
+    for col in list(thr.T) + list(p.T) + list(q.T):
+        assert np.isnan(col).any() and np.isposinf(col).any() and np.isneginf(col).any()
+    assert set(np.unique(elapsed)) == {1, 13} and set(np.unique(causes)) >= {0, 1, 2, 4, 8, 16, 32, 63}
+    for k in (-1, 0, 1):
+        assert ((age == max_ticks + k) & (max_ticks == 40)).any()
+    assert (age_in == INT_MAX).any() and (age == INT_MAX).any()
+    want_age = np.array([EM.age_after(a, e) for a, e in zip(age_in, elapsed)])
+    assert np.array_equal(want_age, age)
+    got_any = np.zeros(6, bool)
+    for i in range(len(c)):
+        rule = dict(causes=causes[i], max_ticks=max_ticks[i], cos_tilt_min=thr[i, 0], z_min=thr[i, 1], range=thr[i, 2])
+        wc, wf = EM.cause_of(rule, safe[i:i + 1], p[i:i + 1], q[i:i + 1], ground[i:i + 1], start[i:i + 1], want_age[i:i + 1])
+        assert wc[0] == cause[i], (i, c[i])
+        assert _same_bits(wf[0], facts[i]), (i, c[i])
+        got_any |= (int(cause[i]) >> np.arange(6)) & 1 == 1
+    assert got_any.all()
+    # the boundaries: a strict comparison fires one ulp beyond its threshold and not on it
+    base = (causes == 63) & (safe == 1) & (age == 39) & np.isfinite(c[:, 2:16]).all(1)
+    for col, fact, bit, below in ((2, 3, EM.TILT, True), (3, 2, EM.HEIGHT, True)):
+        on = base & (thr[:, col - 2] == facts[:, fact])
+        up = base & (thr[:, col - 2] == np.nextafter(facts[:, fact], np.inf))
+        assert on.any() and up.any() and not (cause[on].astype(int) & bit).any() and (cause[up].astype(int) & bit).all()
+    big = np.maximum(np.abs(facts[:, 0]), np.abs(facts[:, 1]))
+    on, dn = base & (thr[:, 2] == big), base & (thr[:, 2] == np.nextafter(big, -np.inf))
+    assert on.any() and dn.any() and not (cause[on].astype(int) & EM.RANGE).any() and (cause[dn].astype(int) & EM.RANGE).all()
+    # a threshold that is not finite never fires; a NaN in the pose fires NONFINITE and no comparison
+    for k, bit in ((0, EM.TILT), (1, EM.HEIGHT), (2, EM.RANGE)):
+        assert not (cause[~np.isfinite(thr[:, k])].astype(int) & bit).any()
+    nan_pose = np.isnan(p).any(1) | np.isnan(q).any(1)
+    assert ((cause[nan_pose & (causes == 63)].astype(int) & EM.NONFINITE) != 0).all()
+    assert not (cause.astype(int) & ~causes).any()
+
+
+@no_hipcc
+def test_rule_header_draws_what_the_model_draws_inside_the_tables(dump):
+    """S in {1, 7}, C in {0, 1, 5}, robots up to 2^20, episode indices 0, 1, 2^31 - 1, three keys: the rows are the
+    model's, lie inside their tables (the program read them under AddressSanitizer), and the offsets are the layout's."""
+    d = dump[1]
+    assert len(d) > 20000 and d.shape[1] == 10
+    k0, k1, b, e, S, C, sr, cr, o0, o1 = d.T
+    assert b.max() == 1 << 20 and e.max() == INT_MAX and set(np.unique(S)) == {1, 7} and set(np.unique(C)) == {0, 1, 5}
+    assert (sr >= 0).all() and (sr < S).all() and (cr >= 0).all() and (cr < np.maximum(C, 1)).all()
+    for s in (1, 7):
+        for cn in (0, 1, 5):
+            m = (S == s) & (C == cn)
+            wr, wc = EM.draw_keys(k0[m], k1[m], b[m], e[m], s, cn)
+            assert np.array_equal(wr, sr[m]) and np.array_equal(wc, cr[m])
+    assert np.array_equal(o0, sr * 3) and np.array_equal(o1, (b * S + sr) * 3)
+    # the seed's two words are the key: EM.draw splits them as the library does
+    wr, wc = EM.draw((0x85A308D3 << 32) | 0x243F6A88, np.arange(64), 1, 7, 5)
+    m = (S == 7) & (C == 5) & (k0 == 0x243F6A88) & (e == 1) & (b < 64)
+    first = {int(bb): (int(x), int(y)) for bb, x, y in zip(b[m], sr[m], cr[m])}
+    assert all(first[k] == (int(wr[k]), int(wc[k])) for k in range(64))
+
+
+@no_hipcc
+def test_draws_cover_every_row(dump):
+    """Over 4096 (b, episode) pairs with S = 7 and C = 5 every spawn row and every command row is drawn (and none is
+    rare: each within a third of its share)."""
+    d = dump[1]
+    k0, k1, b, e, S, C, sr, cr, o0, o1 = d.T
+    m = (S == 7) & (C == 5) & (k0 == 0x243F6A88) & (b < 64) & (e >= 1) & (e <= 64)
+    pairs = set(zip(b[m].tolist(), e[m].tolist()))
+    assert len(pairs) == 4096
+    ns, nc = np.bincount(sr[m], minlength=7), np.bincount(cr[m], minlength=5)
+    print("spawn rows", ns, "command rows", nc)
+    assert (ns > 0).all() and (nc > 0).all()
+    assert (np.abs(ns / ns.sum() - 1 / 7) < 1 / 21).all() and (np.abs(nc / nc.sum() - 1 / 5) < 1 / 15).all()
+
+
+@no_hipcc
+def test_rule_header_clamps_the_gait_column(dump):
+    """NaN, +-inf, +-1e300, the limits of int and fractions as a command row's gait: the number lies in [0, 31], is the
+    model's, and the conversion raised nothing under UBSan."""
+    g = dump[2]
+    assert len(g) >= 20 and np.isnan(g[:, 0]).any() and np.isinf(g[:, 0]).any() and (np.abs(g[:, 0]) == 1e300).any()
+    assert (g[:, 1] >= 0).all() and (g[:, 1] <= 31).all() and np.array_equal(EM.gait_of(g[:, 0]), g[:, 1].astype(np.int32))
+    ok = (g[:, 0] >= 0) & (g[:, 0] <= 31)
+    assert np.array_equal(g[ok, 1], np.floor(g[ok, 0])) and set(g[ok, 1]) >= {0, 4, 11, 30, 31}
+
+
+# ---- the model's bookkeeping --------------------------------------------------------------------------------------------
+
+def test_model_bookkeeping():
+    """A self-check of tests/episode_model.py alone (it runs no code of the library): the reference the GPU suite compares
+    with keeps its books as the header says."""
+    B = 5
+    p = np.tile([0.0, 0.0, 0.29], (B, 1))
+    p[:, 0] = np.arange(B)
+    q = np.tile([1.0, 0, 0, 0], (B, 1))
+    m = EM.EpisodeModel(B, 7, p)
+    vel, gait = np.zeros((B, 3)), np.full(B, 9, np.int32)
+    spawn = np.arange(21.0).reshape(7, 3)
+    cmds = np.array([[0.1, 0, 0, 9], [0.2, 0, 0, 5], [0.3, 0, 0, 4]])
+    m.set(vel, gait, spawn, cmds, log_rows=3, causes=EM.ALL, max_ticks=4, cos_tilt_min=0.5, z_min=0.1, range=100.0)
+    safe = np.ones(B, int)
+    safe[2] = 0
+    for t in range(3):
+        mask, xy = m.step(p, q, safe)
+        assert mask.tolist() == [False, False, True, False, False]
+    assert m.episode.tolist() == [0, 0, 3, 0, 0] and m.age.tolist() == [3, 3, 0, 3, 3] and m.count[2].tolist() == [3, 0, 0, 0, 0, 0]
+    mask, xy = m.step(p, q, safe)                                        # everybody times out, robot 2 at age 1 latched
+    assert mask.all() and m.count[:, 5].tolist() == [1, 1, 0, 1, 1] and m.ticks_sum.tolist() == [4, 4, 4, 4, 4]
+    assert m.total == 8 and m.log_count == 3 and m.dropped == 5 and len(m.certain_rows()) == 3 and len(m.all_rows()) == 8
+    sr, cr = EM.draw(7, np.arange(B), m.episode, 7, 3)
+    assert np.array_equal(m.xyyaw, spawn[sr]) and np.array_equal(m.start, spawn[sr][:, :2]) and np.array_equal(m.vel, cmds[cr, :3])
+    assert np.array_equal(m.gait, cmds[cr, 3].astype(np.int32)) and (m.age == 0).all()
+    m.clear_log()
+    assert m.total == 0 and m.dropped == 0
+    off = EM.EpisodeModel(B, 7, p)
+    off.set(vel, gait, spawn, causes=0)
+    assert not off.step(p, q, safe)[0].any() and (off.age == 0).all()
+
+
+# ---- the kernels --------------------------------------------------------------------------------------------------------
+
+@no_hipcc
+def test_episode_kernel_resources(tmp_path):
+    """The decision kernel, the init kernel and the log clear compile for gfx950, with the build's own flags, without
+    scratch and without LDS."""
+    src = os.path.join(ROOT, "quadruped_ctrl_amd", "csrc", "qmpc_episode.hip")
+    import __graft_entry__ as G                     # the flags the shipped object is compiled with
+    out = subprocess.run([HIPCC] + G.HIPFLAGS + ["-c", src, "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "episode.o")],
+                         capture_output=True, text=True, check=True).stderr
+    res, name = {}, None
+    for line in out.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            res[name] = {}
+        for key, pat in (("vgpr", r" VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
+                         ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
+            m = re.search(pat, line)
+            if m and name:
+                res[name][key] = int(m.group(1))
+    assert len(res) == 3 and all(any(k in n for n in res) for k in ("qmpc_episode_decide_kernel", "qmpc_episode_init_kernel",
+                                                                     "qmpc_episode_log_clear_kernel")), sorted(res)
+    for k, v in res.items():
+        print(k, v)
+        assert v["scratch"] == 0 and v["lds"] == 0, (k, v)

@@ -39,6 +39,11 @@ counters are reported.
 shared by the fleet, the robots' start positions spread over 13 x 13 patches of it; swing feet clamped to the surface and,
 for --source plant, the height re-based, as with --terrain.  It combines with --terrain (the field lies on the slopes and
 stairs), --contact and --vary: the step then runs the kernels of csrc/qmpc_field.hip.
+--episodes (with --source plant) puts the episode manager of include/qmpc_episode.h behind the plant step: all six causes
+(time-out after 300 ticks, tilt cosine below 0.8, height below 0.15 m, 2 m from the start), the fleet's start poses as the
+shared spawn table, a table of eight commands of the same family, a log of 4096 rows; --every k checks on every k-th tick
+only (qmpc_episode_step(elapsed = k)).  The step is timed separately on the ticks it runs on (us_per_episode_step_median);
+the episodes finished per cause and the log's words are reported.
 
 --source sensor closes the same loop through the SENSOR path: qmpc_ctrl_tick -- the VectorNav orientation estimator and
 the Kalman filter -- on the readings of the sensor model (include/qmpc_sense.h), qmpc_plant_step on the tick's efforts,
@@ -50,7 +55,7 @@ accelerometer and gyro biases (within +-0.2 m/s^2, +-0.02 rad/s) and white noise
 
     python tools/ctrl_bench.py [--batches 1024,4096,16384] [--cycles 8] [--warmup 26] [--schedule lockstep|per_robot]
                                [--stagger] [--robot-mode 0|1] [--source imu|state|plant|sensor] [--vary] [--terrain] [--contact] [--field]
-                               [--noise] [--out FILE]
+                               [--noise] [--episodes] [--every K] [--out FILE]
 """
 import argparse
 import json
@@ -64,7 +69,7 @@ sys.path.insert(0, ROOT)
 
 
 def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, source="imu", vary=False, noise=False, terrain=False,
-        contact=False, field=False):
+        contact=False, field=False, episodes=False, every=1):
     import torch
     from quadruped_ctrl_amd import workloads as W
     from quadruped_ctrl_amd.binding import BatchedController
@@ -94,7 +99,7 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
     vel = torch.from_numpy(vel).cuda()
     ctrl.set_vel(vel)
     n = warmup + 13 * cycles
-    plant = sensors = None
+    plant = sensors = manager = None
     if closed:
         from quadruped_ctrl_amd.binding import BatchedPlant
         plant = BatchedPlant(ctrl)
@@ -131,6 +136,15 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
             plant.reset(torch.ones(B, dtype=torch.bool, device="cuda"), torch.from_numpy(xyyaw).cuda())
         if contact:
             plant.set_contact(early=True, late=True, slip=True)
+        if episodes:
+            from quadruped_ctrl_amd.binding import BatchedEpisodes
+            manager = BatchedEpisodes(plant)
+            manager.init(seed=B)
+            table = np.array([[0.0, 0, 0, 4], [0.1, 0, 0.05, 0], [0.2, 0, -0.05, 5], [0.3, 0, 0, 10], [0.4, 0, 0.1, 0],
+                              [0.5, 0, 0, 5], [0.25, 0, -0.1, 10], [0.0, 0, 0, 4]])
+            ep_vel, ep_gait = vel.clone(), g.clone()      # (the fleet's commands: the manager rewrites a reset robot's rows)
+            manager.set(ep_vel, ep_gait, torch.from_numpy(xyyaw).cuda(), torch.from_numpy(table).cuda(), log_rows=4096,
+                        causes=63, max_ticks=300, cos_tilt_min=0.8, z_min=0.15, range=2.0)
         imu, motor = plant.state.expand(26, B, 16), plant.motor.expand(26, B, 24)    # (every "slot" is the plant's read-out)
         tick = ctrl.tick_state
         if source == "sensor":
@@ -165,7 +179,7 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
                 plant.step(eff)
             if sensors is not None:
                 sensors.sense()
-    ev = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(4)) for _ in range(n)]
+    ev = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(5 if manager is not None else 4)) for _ in range(n)]
     for t in range(n):
         if vary and t in (300, 350):     # (outside the timed pairs: the push starts and ends)
             force.copy_(push) if t == 300 else force.zero_()
@@ -178,6 +192,9 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
         if sensors is not None:
             sensors.sense()
             ev[t][3].record()
+        if manager is not None and (t + 1) % every == 0:
+            manager.step(every)
+            ev[t][4].record()
     torch.cuda.synchronize()
     us = np.array([e[0].elapsed_time(e[1]) * 1e3 for e in ev])
     mpc = (np.arange(n) + 1) % 13 == 0
@@ -223,6 +240,15 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
         res.update({"us_per_plant_step_median": round(float(np.median(us_p)), 2), "us_per_plant_step_max": round(float(us_p.max()), 2),
                     "body_height_min": round(float(pz.min().item()), 4), "body_height_max": round(float(pz.max().item()), 4),
                     "status_error_robots": int((torch.from_numpy(ctrl.read("status")[:, 0]) & 47 != 0).sum())})
+    if manager is not None:
+        ran = keep & ((np.arange(n) + 1) % every == 0)
+        us_e = np.array([ev[t][2].elapsed_time(ev[t][4]) * 1e3 for t in np.flatnonzero(ran)])
+        ev_, lg = manager.view(), manager.log()
+        res.update({"episodes": True, "every": every, "episode_steps_timed": int(ran.sum()),
+                    "us_per_episode_step_median": round(float(np.median(us_e)), 2), "us_per_episode_step_max": round(float(us_e.max()), 2),
+                    "episodes_finished": int(ev_["episode"].sum().item()),
+                    "episodes_per_cause": [int(x) for x in ev_["count"].sum(0).tolist()],
+                    "log_rows_written": int(len(lg["rows"])), "log_dropped": int(lg["dropped"])})
     res.update({"all_finite": bool(torch.isfinite(eff).all().item()), "latched": int((v["safe"] == 0).sum())})
     ctrl.close()
     return res
@@ -242,6 +268,8 @@ def main():
     ap.add_argument("--contact", action="store_true")
     ap.add_argument("--field", action="store_true")
     ap.add_argument("--noise", action="store_true")
+    ap.add_argument("--episodes", action="store_true")
+    ap.add_argument("--every", type=int, default=1)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.vary and a.source not in ("plant", "sensor"):
@@ -252,6 +280,10 @@ def main():
         ap.error("--contact needs --source plant or sensor")
     if a.field and a.source not in ("plant", "sensor"):
         ap.error("--field needs --source plant or sensor")
+    if a.episodes and a.source != "plant":
+        ap.error("--episodes needs --source plant (the sensor path is out of the manager's scope)")
+    if a.every < 1 or (a.every != 1 and not a.episodes):
+        ap.error("--every K >= 1 goes with --episodes")
     if a.noise and a.source != "sensor":
         ap.error("--noise needs --source sensor")
     if a.robot_mode == 1:
@@ -260,7 +292,8 @@ def main():
         ap.error("--stagger needs --schedule per_robot (a lockstep reset keeps the robot on the batch's MPC ticks)")
     out = []
     for B in [int(x) for x in a.batches.split(",")]:
-        r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source, a.vary, a.noise, a.terrain, a.contact, a.field)
+        r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source, a.vary, a.noise, a.terrain, a.contact, a.field,
+                a.episodes, a.every)
         print(json.dumps(r), flush=True)
         out.append(r)
     if a.out:
