@@ -73,9 +73,9 @@
  *     and with contact; the statistics' of qmpc_plant_vary.h while they are enabled.
  *  With causes == 0 the step enqueues nothing and changes nothing.
  *
- * Out of scope: episodes on the sensor path -- a reset robot needs the warm-up of qmpc_sense.h for itself, and
- * qmpc_ctrl_prework runs on the whole batch; nothing of qmpc_sense.h is called.  Rewards and observations.  Anything
- * inside the controller's or the plant's kernels.
+ * Out of scope here: episodes on the sensor path -- a reset robot needs the warm-up of qmpc_sense.h for itself, and
+ * qmpc_ctrl_prework runs on the whole batch; nothing of qmpc_sense.h is called: qmpc_episode_sense.h does that, with this
+ * header's rule, bindings, log and view.  Rewards and observations.  Anything inside the controller's or the plant's kernels.
  *
  * Errors as in qmpc_plant.h: QMPC_ERR_STATE before qmpc_plant_init, and before qmpc_episode_init for every call but
  * qmpc_episode_init itself; qmpc_episode_step before qmpc_episode_set is QMPC_ERR_STATE too.  QMPC_ERR_ARG for a batch

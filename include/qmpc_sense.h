@@ -42,7 +42,8 @@
  * speed within 0.013 m/s of the command, the filter's height error at the end below 3 mm.  Other noise seeds move the
  * statistics by at most 0.39 of the closed-loop tests' envelope.
  *
- * Out of scope: sensor latency, attitude error, contact sensing.
+ * Out of scope: sensor latency, attitude error, contact sensing.  (The warm-up of a single robot that is reset while its
+ * neighbours walk: qmpc_episode_sense.h.)
  *
  * Errors as in qmpc_plant.h: QMPC_ERR_STATE before qmpc_plant_init, and before qmpc_sense_init for every call but
  * qmpc_sense_init itself; QMPC_ERR_ARG for a batch other than the plant's, a null output or view, or an output pointer

@@ -178,6 +178,11 @@ class EpisodeView(C.Structure):
                                                                  ("batch", C.c_int), ("seed", C.c_uint64)]
 
 
+class EpisodeSenseView(C.Structure):
+    """qmpc_episode_sense_view (include/qmpc_episode_sense.h)."""
+    _fields_ = [("warm", C.c_void_p), ("hold", C.c_void_p), ("warm_ticks", C.c_int), ("batch", C.c_int)]
+
+
 class LegCommand(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in LEG_F32] + [("kp_joint", C.c_float), ("kd_joint", C.c_float)]
 
@@ -322,6 +327,13 @@ EPISODE_SIGNATURES = {
     "qmpc_episode_log_clear": [_P, _P],
     "qmpc_episode_view_get": [_P, C.POINTER(EpisodeView)],
 }
+# episodes on the sensor path: per-robot warm-up after a reset (include/qmpc_episode_sense.h), same library and ABI version
+EPISODE_SENSE_SIGNATURES = {
+    "qmpc_episode_sense_init": [_P, _I, _I, _P],
+    "qmpc_episode_sense_hold": [_P, _I, _P, _I, _P],
+    "qmpc_episode_sense_step": [_P, _I, _P, _P],
+    "qmpc_episode_sense_view_get": [_P, C.POINTER(EpisodeSenseView)],
+}
 EXPORTS = list(SIGNATURES)
 CTRL_EXPORTS = list(CTRL_SIGNATURES)
 PLANT_EXPORTS = list(PLANT_SIGNATURES)
@@ -331,6 +343,7 @@ TERRAIN_EXPORTS = list(TERRAIN_SIGNATURES)
 CONTACT_EXPORTS = list(CONTACT_SIGNATURES)
 FIELD_EXPORTS = list(FIELD_SIGNATURES)
 EPISODE_EXPORTS = list(EPISODE_SIGNATURES)
+EPISODE_SENSE_EXPORTS = list(EPISODE_SENSE_SIGNATURES)
 
 _lib = None
 
@@ -365,7 +378,8 @@ def load_library():
                 "(python -c 'import __graft_entry__ as g; g.build()')")
         lib = C.CDLL(LIB_PATH)
         for name, sig in {**SIGNATURES, **CTRL_SIGNATURES, **PLANT_SIGNATURES, **PLANT_VARY_SIGNATURES, **TERRAIN_SIGNATURES,
-                          **CONTACT_SIGNATURES, **FIELD_SIGNATURES, **SENSE_SIGNATURES, **EPISODE_SIGNATURES}.items():
+                          **CONTACT_SIGNATURES, **FIELD_SIGNATURES, **SENSE_SIGNATURES, **EPISODE_SIGNATURES,
+                          **EPISODE_SENSE_SIGNATURES}.items():
             f = getattr(lib, name)
             f.argtypes, f.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
         _lib = lib
@@ -1265,6 +1279,56 @@ class BatchedEpisodes:
         return dict(rows=rows[np.lexsort((rows[:, 1], rows[:, 0]))], dropped=dropped)
 
 
+class SensedEpisodes:
+    """Episodes on the sensor path (include/qmpc_episode_sense.h) for a BatchedEpisodes manager and the BatchedSensors of
+    the same plant: step() is episodes.step() for a fleet that walks on its sensors -- a robot that finishes is reset,
+    its sensors start a new noise epoch, and for the next `warm_ticks` control periods it is HELD: the whole tick and
+    the plant step run for it as for everybody, and step() undoes all of it except what pre_work would have done, so
+    the robot gets sensors.settle() for itself while its neighbours walk (see rollout_sensed_episodes()).  The held
+    robots' ticks and solves are computed and thrown away: that, and one launch more per step, is the cost.
+
+    Constructed from the two (all three live in the plant's handle), after episodes.init() and sensors.init().  Every
+    call only enqueues on the current stream (or `stream`)."""
+
+    def __init__(self, episodes, sensors):
+        if episodes.plant is not sensors.plant:
+            raise QmpcError("SensedEpisodes: the episodes and the sensors of one plant")
+        self.episodes, self.sensors, self.plant, self.ctrl = episodes, sensors, episodes.plant, episodes.ctrl
+        self.torch, self.lib, self.device = self.plant.torch, self.plant.lib, self.plant.device
+        self.batch = None
+        self.warm_ticks = None
+
+    def init(self, warm_ticks=50, stream=None):
+        """Nobody in warm-up; warm_ticks >= 0: the control periods of warm-up a robot gets when step() resets it."""
+        self.ctrl._call("qmpc_episode_sense_init", self.plant.batch or 0, int(warm_ticks), self.ctrl._s(stream))
+        self.batch, self.warm_ticks = self.plant.batch, int(warm_ticks)
+
+    def hold(self, mask=None, ticks=None, stream=None):
+        """`ticks` (None: warm_ticks) control periods of warm-up, from the next step() on, for the robots where mask is
+        set (None: all), on the pose the plant holds them in now: the fleet's initial settle, or the warm-up of robots
+        the caller has reset (ctrl.reset, plant.reset, sensors.reset, then this, between step() and sensors.sense())."""
+        if self.batch is None:
+            raise QmpcError("qmpc_episode_sense_hold before init()")
+        self._keep, ptr = self.ctrl._mask(mask)
+        self.ctrl._call("qmpc_episode_sense_hold", self.batch, ptr, int(self.warm_ticks if ticks is None else ticks),
+                        self.ctrl._s(stream))
+
+    def step(self, effort=None, stream=None):
+        """After plant.step() and before sensors.sense(), on every tick.  effort: the tick's output [B,12] float64, whose
+        rows are zeroed for the robots reset or held; None: left alone."""
+        if self.batch is None:
+            raise QmpcError("qmpc_episode_sense_step before init()")
+        ptr = None if effort is None else self.ctrl._chk(effort, (self.batch, 12), self.torch.float64, "effort")
+        self.ctrl._call("qmpc_episode_sense_step", self.batch, ptr, self.ctrl._s(stream))
+
+    def view(self):
+        """qmpc_episode_sense_view_get as zero-copy device tensors that alias the state, like BatchedEpisodes.view():
+        warm ([B] int32: control periods of warm-up still to come), hold ([B] uint8: held by the last step()); plus
+        warm_ticks, batch.  Read-only by contract."""
+        return self.ctrl._views("qmpc_episode_sense_view_get", EpisodeSenseView, dict(warm=(None, "<i4"), hold=(None, "|u1")),
+                                ("warm_ticks", "batch"))
+
+
 def _run_ticks(ctrl, who, ticks, graph, tick):
     """The runner behind rollout() and rollout_sensed() (`who`: the caller's name, which starts its messages): tick()
     `ticks` times on the current stream, or that block captured on a side stream and replayed once -> the graph, or None."""
@@ -1344,3 +1408,20 @@ def rollout_episodes(ctrl, plant, episodes, ticks, graph=False, every=1):
 
     g = _run_ticks(ctrl, "rollout_episodes", ticks, graph, tick)
     return dict(effort=plant.effort, state=plant.state, motor=plant.motor, graph=g)
+
+
+def rollout_sensed_episodes(ctrl, plant, sensors, sensed, ticks, graph=False):
+    """rollout_sensed() with the episode manager in the loop: `ticks` closed-loop ticks ctrl.tick(sensors.imu,
+    sensors.motor) -> plant.step(effort) -> sensed.step(effort) -> sensors.sense(), continuing from wherever the four
+    stand -- sensors.imu / motor must hold a reading (one sensors.sense() leaves one; sensed.hold() beforehand gives the
+    whole fleet its warm-up inside the loop).  graph=True as in rollout(): the block is captured and replayed once, the
+    graph returned for further replays; in lockstep a captured block holds a multiple of 13 ticks.
+    -> dict(effort, state, motor, imu, graph): the plant's own tensors and the sensors' imu, as the last tick left them."""
+    def tick():
+        ctrl.tick(sensors.imu, sensors.motor, plant.effort)
+        plant.step(plant.effort)
+        sensed.step(plant.effort)
+        sensors.sense()
+
+    g = _run_ticks(ctrl, "rollout_sensed_episodes", ticks, graph, tick)
+    return dict(effort=plant.effort, state=plant.state, motor=plant.motor, imu=sensors.imu, graph=g)

@@ -27,13 +27,15 @@
 #include "../../include/qmpc_field.h"    // ... height-field terrain from memory
 #include "../../include/qmpc_sense.h"   // sensor model between the plant and the controller's sensor path
 #include "../../include/qmpc_episode.h"  // episodes on the device: termination, respawn, result log
+#include "../../include/qmpc_episode_sense.h"  // ... on the sensor path: per-robot warm-up after a reset
 #include "qmpc_device.h"
 #include "qmpc_glue.h"    // each launcher is declared once, in the header its defining file includes too:
-#include "qmpc_launch.h"  // qmpc_glue.h, qmpc_plant.h, qmpc_sense.h, qmpc_episode.h, and qmpc_launch.h for the rest
+#include "qmpc_launch.h"  // qmpc_glue.h, qmpc_plant.h, qmpc_sense.h, qmpc_episode.h, qmpc_episode_sense.h, and qmpc_launch.h for the rest
 #include "qmpc_plan.h"  // the solve's launch plan (host-only)
 #include "qmpc_plant.h"
 #include "qmpc_sense.h"
 #include "qmpc_episode.h"
+#include "qmpc_episode_sense.h"
 static_assert(kLongHorizon == QMPC_LONG_HORIZON, "qmpc_plan.h and qmpc.h disagree");
 
 extern "C" size_t qmpc_smem_bytes(int rb) {
@@ -263,6 +265,15 @@ struct __attribute__((visibility("hidden"))) qmpc_ctx {
     bool is_set = false;
   };
   std::unique_ptr<Episode> episode;
+  // episodes on the sensor path (qmpc_episode_sense.h): warm[max_batch], hold[max_batch] and the union the plant's reset is
+  // given in one allocation made by qmpc_episode_sense_init, and the warm-up a robot gets when the manager resets it
+  struct EpisodeSense {
+    QmpcEpisodeSenseDev d{};
+    DevBuf<char> buf;
+    int batch = 0;  // robots initialised
+    int warm_ticks = 0;
+  };
+  std::unique_ptr<EpisodeSense> episode_sense;
   // (the device arrays and the sub-states free themselves)
   ~qmpc_ctx() {
     if (h_pin) hipHostFree(h_pin);
@@ -1249,6 +1260,11 @@ size_t carve(QmpcEpisodeDev& d, char* base, int M) {
   carve_array(d.log_words, base, off, 2, 1);
   return off;
 }
+size_t carve(QmpcEpisodeSenseDev& d, char* base, int M) {
+  size_t off = 0;
+  QMPC_EPISODE_SENSE_ARRAYS(QMPC_CARVE)
+  return off;
+}
 #undef QMPC_CARVE
 
 // d's arrays as views into buf, which is allocated on first use (a later init of the same handle reuses the block)
@@ -1272,13 +1288,19 @@ int ctrl_check(qmpc_ctx* c, int batch) {
   return QMPC_OK;
 }
 
-// The controller's reset of the masked robots (qmpc_ctrl_reset, and the episode manager's): in lockstep the counter
-// restarts at T mod 13 (the batch keeps solving on the same ticks), with the per-robot schedule at 0, as init_controller
-// leaves it.  The caller holds the DeviceGuard and has ordered the stream.
+// Where a reset robot's counter restarts (qmpc_ctrl_reset, and both episode managers'): in lockstep at T mod 13 (the
+// batch keeps solving on the same ticks), with the per-robot schedule at 0, as init_controller leaves it.  A reset
+// starts the controller (qmpc_ctrl_set_schedule's window closes).
+int ctrl_reset_counter0(qmpc_ctx::Ctrl* k) {
+  k->started = true;
+  return k->schedule == QMPC_CTRL_PER_ROBOT ? 0 : (int)(k->ticks % 13);
+}
+
+// The controller's reset of the masked robots (qmpc_ctrl_reset, and the episode manager's).  The caller holds the
+// DeviceGuard and has ordered the stream.
 int ctrl_reset_enqueue(qmpc_ctx* c, int batch, const uint8_t* mask_dev, hipStream_t stream) {
   qmpc_ctx::Ctrl* k = c->ctrl.get();
-  k->started = true;
-  const int counter0 = k->schedule == QMPC_CTRL_PER_ROBOT ? 0 : (int)(k->ticks % 13);
+  const int counter0 = ctrl_reset_counter0(k);
   HIP_TRY(c, qmpc_launch_ctrl_init(&k->d, mask_dev, counter0, batch, stream));
   return QMPC_OK;
 }
@@ -1945,6 +1967,15 @@ int episode_check(qmpc_ctx* c, int batch) {
   return QMPC_OK;
 }
 
+// what a decision kernel reads of the handle's other state
+QmpcEpisodeIn episode_inputs(const qmpc_ctx* c) {
+  const qmpc_ctx::Plant* pl = c->plant.get();
+  // the plant writes ground[b] on terrain, on a field and with contact on (there 0 without rows); the flat plant never does
+  const bool ground = pl->terrain.rows || pl->field.z || pl->contact.flags;
+  return QmpcEpisodeIn{pl->d.p, pl->d.q, c->ctrl->d.safe, ground ? pl->terrain.ground : nullptr,
+                       (uint32_t)(c->episode->seed & 0xFFFFFFFFu), (uint32_t)(c->episode->seed >> 32)};
+}
+
 const int kEpisodeCauses = QMPC_EP_UNSAFE | QMPC_EP_NONFINITE | QMPC_EP_TILT | QMPC_EP_HEIGHT | QMPC_EP_RANGE | QMPC_EP_TIMEOUT;
 
 }  // namespace
@@ -1990,10 +2021,7 @@ int qmpc_episode_step(qmpc_handle c, int batch, int elapsed, void* stream_) {
   const Enqueue q(c, stream_);
   if (q.rc) return q.rc;
   const qmpc_ctx::Plant* pl = c->plant.get();
-  // the plant writes ground[b] on terrain, on a field and with contact on (there 0 without rows); the flat plant never does
-  const bool ground = pl->terrain.rows || pl->field.z || pl->contact.flags;
-  const QmpcEpisodeIn in{pl->d.p, pl->d.q, c->ctrl->d.safe, ground ? pl->terrain.ground : nullptr,
-                         (uint32_t)(k->seed & 0xFFFFFFFFu), (uint32_t)(k->seed >> 32)};
+  const QmpcEpisodeIn in = episode_inputs(c);
   HIP_TRY(c, qmpc_launch_episode_decide(&k->d, &in, &k->rule, &k->bind, elapsed, batch, q.stream));
   // the existing resets under the kernel's mask: controller, its commands (the reset zeroed them), plant, statistics
   if (const int rc = ctrl_reset_enqueue(c, batch, k->d.mask, q.stream)) return rc;
@@ -2029,6 +2057,84 @@ int qmpc_episode_view_get(qmpc_handle c, qmpc_episode_view* v) {
   v->log_dropped = d.log_words + 1;
   v->batch = c->episode->batch;
   v->seed = c->episode->seed;
+  return QMPC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
+// Episodes on the sensor path (include/qmpc_episode_sense.h).  The kernels are in qmpc_episode_sense.hip.
+namespace {
+
+// the three inits this header stands on, then its own (own == false: qmpc_episode_sense_init itself)
+int episode_sense_check(qmpc_ctx* c, int batch, bool own = true) {
+  if (const int rc = episode_check(c, batch)) return rc;
+  if (const int rc = sense_check(c, batch)) return rc;
+  if (!own) return QMPC_OK;
+  if (!c->episode_sense || !c->episode_sense->batch) return QMPC_ERR_STATE;
+  if (batch != c->episode_sense->batch) return QMPC_ERR_ARG;
+  return QMPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qmpc_episode_sense_init(qmpc_handle c, int batch, int warm_ticks, void* stream_) {
+  if (const int rc = episode_sense_check(c, batch, false)) return rc;
+  if (warm_ticks < 0) return QMPC_ERR_ARG;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!c->episode_sense) c->episode_sense.reset(new qmpc_ctx::EpisodeSense());
+  qmpc_ctx::EpisodeSense* k = c->episode_sense.get();
+  HIP_TRY(c, carve_block(k->buf, k->d, c->max_batch));
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  HIP_TRY(c, qmpc_launch_episode_sense_init(&k->d, c->max_batch, stream));
+  k->warm_ticks = warm_ticks;
+  k->batch = batch;
+  return QMPC_OK;
+}
+
+int qmpc_episode_sense_hold(qmpc_handle c, int batch, const uint8_t* mask_dev, int ticks, void* stream_) {
+  if (const int rc = episode_sense_check(c, batch)) return rc;
+  if (ticks < 0) return QMPC_ERR_ARG;
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  const QmpcPlantDev& p = c->plant->d;
+  HIP_TRY(c, qmpc_launch_episode_sense_hold(&c->episode_sense->d, &c->episode->d, p.p, p.q, mask_dev, ticks, batch, q.stream));
+  return QMPC_OK;
+}
+
+int qmpc_episode_sense_step(qmpc_handle c, int batch, double* effort, void* stream_) {
+  if (const int rc = episode_sense_check(c, batch)) return rc;
+  qmpc_ctx::Episode* k = c->episode.get();
+  const qmpc_ctx::EpisodeSense* w = c->episode_sense.get();
+  if (!k->is_set) return QMPC_ERR_STATE;
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  const qmpc_ctx::Plant* pl = c->plant.get();
+  const QmpcEpisodeIn in = episode_inputs(c);
+  // (with causes == 0 nobody is judged, but the robots in warm-up are still held: the launches are the same)
+  HIP_TRY(c, qmpc_launch_episode_sense_decide(&w->d, &k->d, &in, &k->rule, &k->bind, w->warm_ticks, batch, q.stream));
+  // the controller: full under mask, all but the pre_work set under hold, one launch; then its commands, as
+  // qmpc_episode_step hands them over (both forms zeroed them)
+  const int counter0 = ctrl_reset_counter0(c->ctrl.get());
+  HIP_TRY(c, qmpc_launch_episode_sense_reinit(&w->d, &k->d, &c->ctrl->d, counter0, effort, batch, q.stream));
+  HIP_TRY(c, qmpc_launch_ctrl_set(&c->ctrl->d, k->bind.gait, k->bind.vel, batch, q.stream));
+  // the plant and its statistics under the union; the sensors' new epoch for the robots that finished only
+  if (const int rc = plant_reset_enqueue(c, batch, w->d.both, k->d.xyyaw, q.stream)) return rc;
+  if (pl->stats_on) HIP_TRY(c, qmpc_launch_plant_stats_reset(&pl->vary, w->d.both, batch, q.stream));
+  HIP_TRY(c, qmpc_launch_sense_reset(&c->sense->a, k->d.mask, batch, q.stream));
+  return QMPC_OK;
+}
+
+int qmpc_episode_sense_view_get(qmpc_handle c, qmpc_episode_sense_view* v) {
+  if (!c || !v) return QMPC_ERR_ARG;
+  if (!plant_ready(c) || !c->episode_sense || !c->episode_sense->batch) return QMPC_ERR_STATE;
+  v->warm = c->episode_sense->d.warm;
+  v->hold = c->episode_sense->d.hold;
+  v->warm_ticks = c->episode_sense->warm_ticks;
+  v->batch = c->episode_sense->batch;
   return QMPC_OK;
 }
 

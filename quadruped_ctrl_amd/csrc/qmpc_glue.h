@@ -274,6 +274,98 @@ __device__ __forceinline__ void qmpc_ctrl_gait_state(float phase, int off, int d
   else swing = ((double)sd < 0.0000000001) ? 0.f : pr / sd;
 }
 
+// The state of a fresh GaitCtrller for robot b, every array of QMPC_CTRL_ARRAYS exactly once: what qmpc_ctrl_init and
+// qmpc_ctrl_reset write (FULL = true, qmpc_glue.hip), and what a robot in warm-up on the sensor path gets after a tick
+// that is to count as pre_work alone (FULL = false, qmpc_episode_sense.hip): everything EXCEPT the pre_work set -- what
+// qmpc_ctrl_prework writes: the inputs, the leg data, the state estimate, both estimators' own state --, which is kept.
+// One function with a compile-time switch, so that the two lists cannot drift: an array is either inside the FULL block
+// or behind it (tests/test_episode_sense_cpu.py holds the partition to the array list).  The partial form does not touch
+// the 324-float P row.
+template <bool FULL>
+__device__ __forceinline__ void qmpc_ctrl_init_robot(const QmpcCtrlDev& S, const int b, const int counter0) {
+  if constexpr (FULL) {  // the pre_work set
+    for (int e = 0; e < 18 * 18; ++e) S.P[(size_t)b * 324 + e] = (e / 18 == e % 18) ? 100.f : 0.f;
+    for (int k = 0; k < 18; ++k) S.xhat[(size_t)b * 18 + k] = 0.f;
+    for (int k = 0; k < 36; ++k) S.leg_J[(size_t)b * 36 + k] = 0.f;
+    for (int k = 0; k < 12; ++k) {
+      S.q[(size_t)b * 12 + k] = 0.f;
+      S.qd[(size_t)b * 12 + k] = 0.f;
+      S.leg_p[(size_t)b * 12 + k] = 0.f;
+      S.leg_v[(size_t)b * 12 + k] = 0.f;
+      S.kf_p[(size_t)b * 12 + k] = 0.f;
+      S.kf_v[(size_t)b * 12 + k] = 0.f;
+    }
+    for (int k = 0; k < 9; ++k) S.r_body[(size_t)b * 9 + k] = 0.f;
+    for (int k = 0; k < 4; ++k) {
+      S.orientation[(size_t)b * 4 + k] = 0.f;
+      S.ori_ini_inv[(size_t)b * 4 + k] = 0.f;
+    }
+    for (int k = 0; k < 3; ++k) {
+      S.rpy[(size_t)b * 3 + k] = 0.f;
+      S.omega_body[(size_t)b * 3 + k] = 0.f;
+      S.omega_world[(size_t)b * 3 + k] = 0.f;
+      S.a_world[(size_t)b * 3 + k] = 0.f;
+      S.position[(size_t)b * 3 + k] = 0.f;
+      S.v_world[(size_t)b * 3 + k] = 0.f;
+      S.v_body[(size_t)b * 3 + k] = 0.f;
+    }
+    S.first_visit[b] = 1;
+  }
+  // everything else
+  for (int k = 0; k < 12; ++k) {
+    S.p_foot[(size_t)b * 12 + k] = 0.f;
+    S.sw_p0[(size_t)b * 12 + k] = 0.f;
+    S.sw_pf[(size_t)b * 12 + k] = 0.f;
+    S.sw_p[(size_t)b * 12 + k] = 0.f;
+    S.sw_v[(size_t)b * 12 + k] = 0.f;
+    S.p_des[(size_t)b * 12 + k] = 0.f;
+    S.v_des[(size_t)b * 12 + k] = 0.f;
+    S.f_ff[(size_t)b * 12 + k] = 0.f;
+    S.grf[(size_t)b * 12 + k] = 0.f;
+  }
+  for (int k = 0; k < 8; ++k) S.pf_rel[(size_t)b * 8 + k] = 0.f;
+  for (int k = 0; k < 9; ++k) S.r_cmd[(size_t)b * 9 + k] = 0.f;
+  for (int k = 0; k < 4; ++k) {
+    S.contact_phase[(size_t)b * 4 + k] = 0.5f;  // GaitCtrller.cpp:22-24
+    S.swing_time[(size_t)b * 4 + k] = 0.f;
+    S.swing_rem[(size_t)b * 4 + k] = 0.f;
+    S.contact_state[(size_t)b * 4 + k] = 0.f;
+    S.swing_state[(size_t)b * 4 + k] = 0.f;
+    S.first_swing[(size_t)b * 4 + k] = 1;
+    S.offsets[(size_t)b * 4 + k] = 0;
+    S.durations[(size_t)b * 4 + k] = 0;
+  }
+  for (int k = 0; k < 3; ++k) {
+    S.vel_cmd[(size_t)b * 3 + k] = 0.f;
+    S.vel_des[(size_t)b * 3 + k] = 0.f;
+  }
+  for (int k = 0; k < 2; ++k) {
+    S.rpy_int[(size_t)b * 2 + k] = 0.f;
+    S.rpy_comp[(size_t)b * 2 + k] = 0.f;
+    S.wpd[(size_t)b * 2 + k] = 0.f;
+  }
+  for (int k = 0; k < 6; ++k) S.stand_traj[(size_t)b * 6 + k] = 0.f;
+  S.yaw_des[b] = 0.f;
+  S.yaw_des_true[b] = 0.f;
+  S.xci[b] = 0.f;
+  S.counter[b] = counter0;
+  S.first_run[b] = 1;
+  S.gait_num[b] = 0;
+  S.current_gait[b] = -1;
+  S.iteration[b] = 0;
+  S.safe[b] = 1;
+  S.status[b] = 0;
+  S.due[b] = 0;
+  S.due_list[b] = 0;
+  S.nseg[b] = 14;  // the `aio` gait as its constructor leaves it (ConvexMPCLocomotion.cpp:41); its offsets 0 and
+  S.gait_phase[b] = 0.f;  // durations 14 are replaced by the first tick's selection before anything reads them
+  for (int k = 0; k < 4; ++k) {
+    S.mpc_offsets[(size_t)b * 4 + k] = 0;
+    S.mpc_durations[(size_t)b * 4 + k] = 0;
+  }
+  S.due_count[b] = 0;  // (element 0 is the count of a tick, rebuilt by every tick; the rest is never used)
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Launchers of qmpc_glue.hip, declared once: qmpc_glue.hip (which defines them) and qmpc_capi.cpp (which calls them)
 // both read these lines, so a signature that drifts fails to compile.

@@ -52,10 +52,16 @@ qmpc_sense on the plant's read-out; 50 untimed qmpc_sense -> qmpc_ctrl_prework c
 The tick, the plant step and the sensor launch are timed separately (us_per_sense_median).  --noise binds per-robot
 accelerometer and gyro biases (within +-0.2 m/s^2, +-0.02 rad/s) and white noise (sigma 0.3 m/s^2, 0.02 rad/s, encoders
 0.002 rad and 0.05 rad/s: the levels the closed-loop tests walk on); without it the sensors are ideal.
+us_per_period_median is the whole period, tick to reading.
+--episodes with --source sensor puts the manager of include/qmpc_episode_sense.h between the plant step and the reading
+(qmpc_episode_sense_step on every tick; --every stays 1): a robot that finishes is reset and warmed up for --warm W periods
+(50) while the others walk.  The timed window runs twice: as it comes (robots_held_per_step says how quiet it was), and again
+after qmpc_episode_sense_hold has put every 100th robot into a warm-up longer than the run, so that 1 % of the fleet is
+held on every step (the held_* fields).  launches_per_episode_step counts what one step enqueues in this configuration.
 
     python tools/ctrl_bench.py [--batches 1024,4096,16384] [--cycles 8] [--warmup 26] [--schedule lockstep|per_robot]
                                [--stagger] [--robot-mode 0|1] [--source imu|state|plant|sensor] [--vary] [--terrain] [--contact] [--field]
-                               [--noise] [--episodes] [--every K] [--out FILE]
+                               [--noise] [--episodes] [--every K] [--warm W] [--out FILE]
 """
 import argparse
 import json
@@ -69,7 +75,7 @@ sys.path.insert(0, ROOT)
 
 
 def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, source="imu", vary=False, noise=False, terrain=False,
-        contact=False, field=False, episodes=False, every=1):
+        contact=False, field=False, episodes=False, every=1, warm=50):
     import torch
     from quadruped_ctrl_amd import workloads as W
     from quadruped_ctrl_amd.binding import BatchedController
@@ -99,7 +105,7 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
     vel = torch.from_numpy(vel).cuda()
     ctrl.set_vel(vel)
     n = warmup + 13 * cycles
-    plant = sensors = manager = None
+    plant = sensors = manager = sensed = None
     if closed:
         from quadruped_ctrl_amd.binding import BatchedPlant
         plant = BatchedPlant(ctrl)
@@ -157,6 +163,10 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
                 sensors.set_params(acc_bias=dev(rng.uniform(-0.2, 0.2, (B, 3))), gyro_bias=dev(rng.uniform(-0.02, 0.02, (B, 3))),
                                    acc_sigma=full(0.3), gyro_sigma=full(0.02), q_sigma=full(0.002), qd_sigma=full(0.05))
             sensors.settle(50)
+            if manager is not None:
+                from quadruped_ctrl_amd.binding import SensedEpisodes
+                sensed = SensedEpisodes(manager, sensors)
+                sensed.init(warm)
             imu, motor = sensors.imu.expand(26, B, 10), sensors.motor.expand(26, B, 24)
             tick = ctrl.tick
     elif source == "state":
@@ -179,23 +189,36 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
                 plant.step(eff)
             if sensors is not None:
                 sensors.sense()
-    ev = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(5 if manager is not None else 4)) for _ in range(n)]
-    for t in range(n):
-        if vary and t in (300, 350):     # (outside the timed pairs: the push starts and ends)
-            force.copy_(push) if t == 300 else force.zero_()
-        ev[t][0].record()
-        tick(imu[t % 26], motor[t % 26], eff)
-        ev[t][1].record()
-        if plant is not None:
-            plant.step(eff)
-            ev[t][2].record()
-        if sensors is not None:
-            sensors.sense()
-            ev[t][3].record()
-        if manager is not None and (t + 1) % every == 0:
-            manager.step(every)
-            ev[t][4].record()
-    torch.cuda.synchronize()
+    held_seen = []
+
+    hold_flags = sensed.view()["hold"] if sensed is not None else None
+
+    def window():
+        ev = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(5 if manager is not None else 4)) for _ in range(n)]
+        for t in range(n):
+            if vary and t in (300, 350):     # (outside the timed pairs: the push starts and ends)
+                force.copy_(push) if t == 300 else force.zero_()
+            ev[t][0].record()
+            tick(imu[t % 26], motor[t % 26], eff)
+            ev[t][1].record()
+            if plant is not None:
+                plant.step(eff)
+                ev[t][2].record()
+            if sensed is not None:       # the sensor path's manager sits between the plant step and the reading
+                sensed.step(eff)
+                ev[t][4].record()
+            if sensors is not None:
+                sensors.sense()
+                ev[t][3].record()
+            if sensed is not None:       # (behind the period's last event; a device scalar: no synchronisation)
+                held_seen.append(hold_flags.sum(dtype=torch.int32))
+            if manager is not None and sensed is None and (t + 1) % every == 0:
+                manager.step(every)
+                ev[t][4].record()
+        torch.cuda.synchronize()
+        return ev
+
+    ev = window()
     us = np.array([e[0].elapsed_time(e[1]) * 1e3 for e in ev])
     mpc = (np.arange(n) + 1) % 13 == 0
     keep = np.arange(n) >= warmup
@@ -206,7 +229,9 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
            "us_per_tick_median": round(float(np.median(us[keep])), 2), "us_per_tick_max": round(float(us[keep].max()), 2),
            "robot_ticks_per_s_window": float(f"{B * int(keep.sum()) / (float(us[keep].sum()) * 1e-6):.4g}")}
     if sensors is not None:
-        us_s = np.array([e[2].elapsed_time(e[3]) * 1e3 for e in ev])[keep]
+        us_s = np.array([e[4 if sensed is not None else 2].elapsed_time(e[3]) * 1e3 for e in ev])[keep]
+        us_all = np.array([e[0].elapsed_time(e[3]) * 1e3 for e in ev])[keep]
+        res.update({"us_per_period_median": round(float(np.median(us_all)), 2), "us_per_period_max": round(float(us_all.max()), 2)})
         res.update({"noise": bool(noise), "us_per_sense_median": round(float(np.median(us_s)), 2),
                     "us_per_sense_max": round(float(us_s.max()), 2), "sense_calls": int(sensors.view()["n"].min().item())})
     if vary:
@@ -249,6 +274,25 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
                     "episodes_finished": int(ev_["episode"].sum().item()),
                     "episodes_per_cause": [int(x) for x in ev_["count"].sum(0).tolist()],
                     "log_rows_written": int(len(lg["rows"])), "log_dropped": int(lg["dropped"])})
+    if sensed is not None:
+        # what one qmpc_episode_sense_step enqueues here, by include/qmpc_episode_sense.h's list (a count from the
+        # configuration, not a trace: it follows qmpc_capi.cpp's entry point by hand): decision, re-initialisation,
+        # commands, plant reset (+ the contact counters'), statistics' reset (while on), sensors' reset
+        held = np.array([int(x) for x in torch.stack(held_seen).cpu()])[keep]
+        res.update({"warm": warm, "launches_per_episode_step": 5 + int(bool(contact)) + int(bool(vary)),
+                    "robots_held_per_step_mean": round(float(held.mean()), 2), "robots_held_per_step_max": int(held.max())})
+        # ... and the window again with every 100th robot in a warm-up longer than the run: 1 % of the fleet held on every step
+        del held_seen[:]
+        sensed.hold(torch.arange(B, device="cuda") % 100 == 99, 10 * n)
+        ev2 = window()
+        us2 = np.array([e[0].elapsed_time(e[3]) * 1e3 for e in ev2])[keep]
+        us_e2 = np.array([e[2].elapsed_time(e[4]) * 1e3 for e in ev2])[keep]
+        held = np.array([int(x) for x in torch.stack(held_seen).cpu()])[keep]
+        res.update({"held_us_per_period_median": round(float(np.median(us2)), 2), "held_us_per_period_max": round(float(us2.max()), 2),
+                    "held_us_per_episode_step_median": round(float(np.median(us_e2)), 2),
+                    "held_robots_per_step_mean": round(float(held.mean()), 2),
+                    "episodes_finished_end": int(manager.view()["episode"].sum().item())})
+        v = ctrl.view()
     res.update({"all_finite": bool(torch.isfinite(eff).all().item()), "latched": int((v["safe"] == 0).sum())})
     ctrl.close()
     return res
@@ -270,6 +314,7 @@ def main():
     ap.add_argument("--noise", action="store_true")
     ap.add_argument("--episodes", action="store_true")
     ap.add_argument("--every", type=int, default=1)
+    ap.add_argument("--warm", type=int, default=50)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.vary and a.source not in ("plant", "sensor"):
@@ -280,8 +325,12 @@ def main():
         ap.error("--contact needs --source plant or sensor")
     if a.field and a.source not in ("plant", "sensor"):
         ap.error("--field needs --source plant or sensor")
-    if a.episodes and a.source != "plant":
-        ap.error("--episodes needs --source plant (the sensor path is out of the manager's scope)")
+    if a.episodes and a.source not in ("plant", "sensor"):
+        ap.error("--episodes needs --source plant or sensor")
+    if a.episodes and a.source == "sensor" and a.every != 1:
+        ap.error("--every K > 1 is out of scope on the sensor path (qmpc_episode_sense_step runs on every tick)")
+    if a.warm < 0 or (a.warm != 50 and not (a.episodes and a.source == "sensor")):
+        ap.error("--warm W >= 0 goes with --source sensor --episodes")
     if a.every < 1 or (a.every != 1 and not a.episodes):
         ap.error("--every K >= 1 goes with --episodes")
     if a.noise and a.source != "sensor":
@@ -293,7 +342,7 @@ def main():
     out = []
     for B in [int(x) for x in a.batches.split(",")]:
         r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source, a.vary, a.noise, a.terrain, a.contact, a.field,
-                a.episodes, a.every)
+                a.episodes, a.every, a.warm)
         print(json.dumps(r), flush=True)
         out.append(r)
     if a.out:
