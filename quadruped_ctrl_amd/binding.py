@@ -178,6 +178,35 @@ class EpisodeView(C.Structure):
                                                                  ("batch", C.c_int), ("seed", C.c_uint64)]
 
 
+# qmpc_act_config's scalar members after gear[3] (include/qmpc_act.h) in declaration order
+ACT_CONFIG_FIELDS = dict(kt=C.c_double, R=C.c_double, battery_v=C.c_double, damping=C.c_double, dry_friction=C.c_double,
+                         tau_max=C.c_double, friction=C.c_int, max_delay=C.c_int)
+# qmpc_act_params' members in declaration order: name -> dtype name (one element per robot)
+ACT_PARAM_FIELDS = dict(battery_v="float64", tau_max="float64", strength="float64", damping="float64",
+                        dry_friction="float64", delay="int32")
+# qmpc_act_view's per-robot arrays in declaration order (after ring): name -> typestr
+ACT_VIEW_FIELDS = dict(head="<i4", age="<i4", n="<i4", n_vsat="<i8", n_tsat="<i8", tau_peak="<f8", e_heat="<f8",
+                       e_mech="<f8", e_pos="<f8")
+ACT_STATS = ("n", "n_vsat", "n_tsat", "tau_peak", "e_heat", "e_mech", "e_pos")
+ACT_MAX_DELAY = 64
+
+
+class ActConfig(C.Structure):
+    """qmpc_act_config (include/qmpc_act.h)."""
+    _fields_ = [("gear", C.c_double * 3)] + list(ACT_CONFIG_FIELDS.items())
+
+
+class ActParams(C.Structure):
+    """qmpc_act_params (include/qmpc_act.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ACT_PARAM_FIELDS]
+
+
+class ActView(C.Structure):
+    """qmpc_act_view (include/qmpc_act.h)."""
+    _fields_ = ([("ring", C.c_void_p)] + [(n, C.c_void_p) for n in ACT_VIEW_FIELDS]
+                + [("config", ActConfig), ("dt", C.c_double), ("batch", C.c_int)])
+
+
 class EpisodeSenseView(C.Structure):
     """qmpc_episode_sense_view (include/qmpc_episode_sense.h)."""
     _fields_ = [("warm", C.c_void_p), ("hold", C.c_void_p), ("warm_ticks", C.c_int), ("batch", C.c_int)]
@@ -334,6 +363,15 @@ EPISODE_SENSE_SIGNATURES = {
     "qmpc_episode_sense_step": [_P, _I, _P, _P],
     "qmpc_episode_sense_view_get": [_P, C.POINTER(EpisodeSenseView)],
 }
+# actuators between the controller's effort and the plant (include/qmpc_act.h), same library and ABI version
+ACT_SIGNATURES = {
+    "qmpc_act_config_default": [C.POINTER(ActConfig)],
+    "qmpc_act_init": [_P, _I, C.POINTER(ActConfig), _P],
+    "qmpc_act_set_params": [_P, _I, C.POINTER(ActParams)],
+    "qmpc_act_reset": [_P, _I, _P, _P, _I, _P],
+    "qmpc_act": [_P, _I, _P, _P, _P],
+    "qmpc_act_view_get": [_P, C.POINTER(ActView)],
+}
 EXPORTS = list(SIGNATURES)
 CTRL_EXPORTS = list(CTRL_SIGNATURES)
 PLANT_EXPORTS = list(PLANT_SIGNATURES)
@@ -344,6 +382,7 @@ CONTACT_EXPORTS = list(CONTACT_SIGNATURES)
 FIELD_EXPORTS = list(FIELD_SIGNATURES)
 EPISODE_EXPORTS = list(EPISODE_SIGNATURES)
 EPISODE_SENSE_EXPORTS = list(EPISODE_SENSE_SIGNATURES)
+ACT_EXPORTS = list(ACT_SIGNATURES)
 
 _lib = None
 
@@ -379,7 +418,7 @@ def load_library():
         lib = C.CDLL(LIB_PATH)
         for name, sig in {**SIGNATURES, **CTRL_SIGNATURES, **PLANT_SIGNATURES, **PLANT_VARY_SIGNATURES, **TERRAIN_SIGNATURES,
                           **CONTACT_SIGNATURES, **FIELD_SIGNATURES, **SENSE_SIGNATURES, **EPISODE_SIGNATURES,
-                          **EPISODE_SENSE_SIGNATURES}.items():
+                          **EPISODE_SENSE_SIGNATURES, **ACT_SIGNATURES}.items():
             f = getattr(lib, name)
             f.argtypes, f.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
         _lib = lib
@@ -1180,6 +1219,106 @@ class BatchedSensors:
                                 ("batch", "seed"))
 
 
+class BatchedActuators:
+    """The actuator stage of include/qmpc_act.h for a BatchedPlant's robots: apply() turns the effort the controller
+    wrote into the torque the joints receive -- the reference's motor model (gear, torque constant, winding resistance,
+    back-EMF against the battery, a motor-side torque cap, damping and dry friction), a per-robot command latency of up
+    to max_delay ticks, and per-robot saturation counters and energies (stats()).  tick -> apply -> plant.step is a
+    closed loop without the host (the rollout functions' `actuators` argument).
+
+    Constructed FROM a plant (the stage lives in the same handle), after plant.init().  Every call only enqueues on the
+    current stream (or `stream`)."""
+
+    def __init__(self, plant):
+        self.plant, self.ctrl = plant, plant.ctrl
+        self.torch, self.lib, self.device = plant.torch, plant.lib, plant.device
+        self.batch = None
+        self._params = {}
+
+    @staticmethod
+    def default_config():
+        """qmpc_act_config_default as a dict: the Mini Cheetah's motor, friction on, max_delay 0."""
+        cfg = ActConfig()
+        rc = load_library().qmpc_act_config_default(C.byref(cfg))
+        if rc != QMPC_OK:
+            raise QmpcError(f"qmpc_act_config_default failed rc={rc}")
+        return BatchedActuators._config_dict(cfg)
+
+    @staticmethod
+    def _config_dict(cfg):
+        return dict(gear=tuple(cfg.gear), **{k: getattr(cfg, k) for k in ACT_CONFIG_FIELDS})
+
+    def init(self, config=None, stream=None, **overrides):
+        """The ring, the counters and the accumulators zero, nothing bound.  config: a dict as default_config() returns
+        (None: the default); keyword overrides replace single members, e.g. init(max_delay=8, tau_max=1.5)."""
+        cfg = dict(self.default_config() if config is None else config)
+        unknown = set(overrides) - set(cfg)
+        if unknown:
+            raise QmpcError(f"BatchedActuators.init: unknown config member(s) {sorted(unknown)}")
+        cfg.update(overrides)
+        c = ActConfig()
+        c.gear = (C.c_double * 3)(*[float(g) for g in cfg["gear"]])
+        for k, ty in ACT_CONFIG_FIELDS.items():
+            setattr(c, k, int(cfg[k]) if ty is C.c_int else float(cfg[k]))
+        self.ctrl._call("qmpc_act_init", self.plant.batch or 0, C.byref(c), self.ctrl._s(stream))
+        self.batch = self.plant.batch
+        self.config = self._config_dict(c)
+        self._params = {}
+
+    def set_params(self, battery_v=None, tau_max=None, strength=None, damping=None, dry_friction=None, delay=None):
+        """Per-robot motors: float64 device tensors [B] battery_v (V), tau_max (motor-side cap, N m), strength (a factor on
+        the joint torque), damping, dry_friction, and delay, int32 [B] in ticks (clamped to 0 .. max_delay); None: the
+        config's value (strength: no factor, delay: 0).  The tensors are read at every later apply() -- write into them
+        in place (on the stream) to change a value, also between replays of a captured graph; they are kept referenced
+        here.  All None unbinds; init() unbinds."""
+        if self.batch is None:
+            raise QmpcError("qmpc_act_set_params before init()")
+        given = dict(battery_v=battery_v, tau_max=tau_max, strength=strength, damping=damping, dry_friction=dry_friction,
+                     delay=delay)
+        prm = ActParams()
+        for k, dt in ACT_PARAM_FIELDS.items():
+            if given[k] is not None:
+                setattr(prm, k, self.ctrl._chk(given[k], (self.batch,), getattr(self.torch, dt), k))
+        self.ctrl._call("qmpc_act_set_params", self.batch, C.byref(prm))
+        self._params = {k: t for k, t in given.items() if t is not None}
+
+    def reset(self, mask_a=None, mask_b=None, stats=False, stream=None):
+        """age = 0 -- the next command is applied at once, the ring fills again -- for the robots where either mask is
+        set (both None: all); stats=True also zeroes their accumulators."""
+        a, pa = self.ctrl._mask(mask_a)
+        b, pb = self.ctrl._mask(mask_b)
+        self._keep = (a, b)
+        self.ctrl._call("qmpc_act_reset", self.batch or 0, pa, pb, 1 if stats else 0, self.ctrl._s(stream))
+
+    def apply(self, effort=None, out=None, stream=None):
+        """One control period: effort [B,12] float64 (None: plant.effort) -> out (None: in place) -> the output."""
+        if self.batch is None:
+            raise QmpcError("qmpc_act before init()")
+        effort = self.plant.effort if effort is None else effort
+        out = effort if out is None else out
+        a = self.ctrl._chk(effort, (self.batch, 12), self.torch.float64, "effort")
+        b = self.ctrl._chk(out, (self.batch, 12), self.torch.float64, "out")
+        self.ctrl._call("qmpc_act", self.batch, a, b, self.ctrl._s(stream))
+        return out
+
+    def view(self):
+        """qmpc_act_view_get as zero-copy device tensors that alias the state, like BatchedPlant.view(): ring
+        [max_delay + 1, B, 12] float64, head, age, n ([B] int32), n_vsat, n_tsat ([B] int64), tau_peak, e_heat, e_mech,
+        e_pos ([B] float64); plus config (a dict), dt, batch.  Read-only by contract."""
+        res = self.ctrl._views("qmpc_act_view_get", ActView, {k: (None, ts) for k, ts in ACT_VIEW_FIELDS.items()},
+                               ("ring", "config", "dt", "batch"))
+        res["config"] = self._config_dict(res["config"])
+        shape = (res["config"]["max_delay"] + 1, res["batch"], 12)
+        res["ring"] = self.torch.as_tensor(_DeviceArray(res["ring"], shape, "<f8", self.ctrl), device=self.device)
+        return res
+
+    def stats(self):
+        """The accumulators of view() alone: n, n_vsat, n_tsat, tau_peak, e_heat, e_mech, e_pos ([B] each); plus dt,
+        batch.  Read-only by contract."""
+        v = self.view()
+        return {k: v[k] for k in ACT_STATS + ("dt", "batch")}
+
+
 class BatchedEpisodes:
     """The episode manager of include/qmpc_episode.h for a BatchedPlant's robots: step() decides on the device which
     robots are done (latched, not finite, tilted, too low, out of range, timed out), logs how each run ended, draws
@@ -1357,29 +1496,36 @@ def _run_ticks(ctrl, who, ticks, graph, tick):
     return g
 
 
-def rollout(ctrl, plant, ticks, graph=False):
+def rollout(ctrl, plant, ticks, graph=False, actuators=None):
     """`ticks` closed-loop ticks, ctrl.tick_state(plant.state, plant.motor) -> plant.step(effort), on the current
     stream, continuing from wherever the pair stands.  graph=True captures the block of `ticks` ticks into a
     torch.cuda.graph (on a side stream) and replays it once; the graph is returned for further replays, each of which
     runs the block again.  With the lockstep schedule a captured block must hold a multiple of 13 ticks (the host
     decides the MPC ticks from its own count, which replays do not advance: include/qmpc_ctrl.h) -- refused otherwise.
+    actuators: a BatchedActuators of the plant, whose apply() then stands between the tick and the step (in place on
+    plant.effort); None: nothing is added.
     -> dict(effort, state, motor, graph): the plant's own tensors, as the last tick left them."""
     def tick():
         ctrl.tick_state(plant.state, plant.motor, plant.effort)
+        if actuators is not None:
+            actuators.apply()
         plant.step(plant.effort)
 
     g = _run_ticks(ctrl, "rollout", ticks, graph, tick)
     return dict(effort=plant.effort, state=plant.state, motor=plant.motor, graph=g)
 
 
-def rollout_sensed(ctrl, plant, sensors, ticks, graph=False):
+def rollout_sensed(ctrl, plant, sensors, ticks, graph=False, actuators=None):
     """rollout() through the sensor path: `ticks` closed-loop ticks ctrl.tick(sensors.imu, sensors.motor) ->
     plant.step(effort) -> sensors.sense(), continuing from wherever the three stand -- sensors.imu / motor must hold a
     reading (sensors.settle() or one sensors.sense() leaves one).  graph=True as in rollout(): the block is captured and
     replayed once, the graph returned for further replays; in lockstep a captured block holds a multiple of 13 ticks.
+    actuators: as in rollout(), between the tick and the step.
     -> dict(effort, state, motor, imu, graph): the plant's own tensors and the sensors' imu, as the last tick left them."""
     def tick():
         ctrl.tick(sensors.imu, sensors.motor, plant.effort)
+        if actuators is not None:
+            actuators.apply()
         plant.step(plant.effort)
         sensors.sense()
 
@@ -1387,40 +1533,56 @@ def rollout_sensed(ctrl, plant, sensors, ticks, graph=False):
     return dict(effort=plant.effort, state=plant.state, motor=plant.motor, imu=sensors.imu, graph=g)
 
 
-def rollout_episodes(ctrl, plant, episodes, ticks, graph=False, every=1):
+def rollout_episodes(ctrl, plant, episodes, ticks, graph=False, every=1, actuators=None, actuator_stats=False):
     """rollout() with the episode manager in the loop: `ticks` closed-loop ticks ctrl.tick_state(plant.state,
     plant.motor) -> plant.step(effort), and after every `every`-th tick of this call episodes.step(elapsed=every).
     graph=True as in rollout(): the block is captured and replayed once, the graph returned for further replays; in
     lockstep a captured block holds a multiple of 13 ticks.  `ticks` must be a multiple of `every`, so that consecutive
-    calls and replays check at the same spacing.
+    calls and replays check at the same spacing.  actuators: as in rollout(), between the tick and the step, and after
+    every episodes.step() actuators.reset(the manager's mask, stats=actuator_stats): a robot that starts again starts
+    with an empty ring (and, with actuator_stats, fresh accumulators).
     -> dict(effort, state, motor, graph): the plant's own tensors, as the last tick left them."""
     every = int(every)
     if every < 1 or int(ticks) % every != 0:
         raise QmpcError(f"rollout_episodes: ticks ({ticks}) must be a multiple of every ({every}) >= 1")
     n = [0]
+    mask = episodes.view()["mask"] if actuators is not None else None
 
     def tick():
         ctrl.tick_state(plant.state, plant.motor, plant.effort)
+        if actuators is not None:
+            actuators.apply()
         plant.step(plant.effort)
         n[0] += 1
         if n[0] % every == 0:
             episodes.step(every)
+            if actuators is not None:
+                actuators.reset(mask, stats=actuator_stats)
 
     g = _run_ticks(ctrl, "rollout_episodes", ticks, graph, tick)
     return dict(effort=plant.effort, state=plant.state, motor=plant.motor, graph=g)
 
 
-def rollout_sensed_episodes(ctrl, plant, sensors, sensed, ticks, graph=False):
+def rollout_sensed_episodes(ctrl, plant, sensors, sensed, ticks, graph=False, actuators=None, actuator_stats=False):
     """rollout_sensed() with the episode manager in the loop: `ticks` closed-loop ticks ctrl.tick(sensors.imu,
     sensors.motor) -> plant.step(effort) -> sensed.step(effort) -> sensors.sense(), continuing from wherever the four
     stand -- sensors.imu / motor must hold a reading (one sensors.sense() leaves one; sensed.hold() beforehand gives the
     whole fleet its warm-up inside the loop).  graph=True as in rollout(): the block is captured and replayed once, the
-    graph returned for further replays; in lockstep a captured block holds a multiple of 13 ticks.
+    graph returned for further replays; in lockstep a captured block holds a multiple of 13 ticks.  actuators: as in
+    rollout_episodes(); the reset takes the manager's mask and the robots held by the last step, so a robot leaves its
+    warm-up with an empty ring.
     -> dict(effort, state, motor, imu, graph): the plant's own tensors and the sensors' imu, as the last tick left them."""
+    if actuators is not None:
+        mask, hold = sensed.episodes.view()["mask"], sensed.view()["hold"]
+
     def tick():
         ctrl.tick(sensors.imu, sensors.motor, plant.effort)
+        if actuators is not None:
+            actuators.apply()
         plant.step(plant.effort)
         sensed.step(plant.effort)
+        if actuators is not None:
+            actuators.reset(mask, hold, stats=actuator_stats)
         sensors.sense()
 
     g = _run_ticks(ctrl, "rollout_sensed_episodes", ticks, graph, tick)

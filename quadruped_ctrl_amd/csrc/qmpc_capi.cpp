@@ -28,14 +28,16 @@
 #include "../../include/qmpc_sense.h"   // sensor model between the plant and the controller's sensor path
 #include "../../include/qmpc_episode.h"  // episodes on the device: termination, respawn, result log
 #include "../../include/qmpc_episode_sense.h"  // ... on the sensor path: per-robot warm-up after a reset
+#include "../../include/qmpc_act.h"     // actuators between the controller's effort and the plant
 #include "qmpc_device.h"
 #include "qmpc_glue.h"    // each launcher is declared once, in the header its defining file includes too:
-#include "qmpc_launch.h"  // qmpc_glue.h, qmpc_plant.h, qmpc_sense.h, qmpc_episode.h, qmpc_episode_sense.h, and qmpc_launch.h for the rest
+#include "qmpc_launch.h"  // qmpc_glue.h, qmpc_plant.h, qmpc_sense.h, qmpc_episode.h, qmpc_episode_sense.h, qmpc_act.h, and qmpc_launch.h for the rest
 #include "qmpc_plan.h"  // the solve's launch plan (host-only)
 #include "qmpc_plant.h"
 #include "qmpc_sense.h"
 #include "qmpc_episode.h"
 #include "qmpc_episode_sense.h"
+#include "qmpc_act.h"
 static_assert(kLongHorizon == QMPC_LONG_HORIZON, "qmpc_plan.h and qmpc.h disagree");
 
 extern "C" size_t qmpc_smem_bytes(int rb) {
@@ -253,6 +255,15 @@ struct __attribute__((visibility("hidden"))) qmpc_ctx {
     bool bound = false;
   };
   std::unique_ptr<Sense> sense;
+  // actuator stage (qmpc_act.h): head, age and the accumulators for max_batch robots in one allocation and the ring in
+  // another, both made by qmpc_act_init; the config as given and the caller's arrays as bound (all null: the config's)
+  struct Act {
+    QmpcActArgs a{};
+    DevBuf<char> buf;
+    DevBuf<double> ring;
+    int batch = 0;  // robots initialised
+  };
+  std::unique_ptr<Act> act;
   // episode manager (qmpc_episode.h): the per-robot state and the two log words in one allocation made by
   // qmpc_episode_init, the seed, and the rule and the caller's arrays as set (is_set: qmpc_episode_set has been called)
   struct Episode {
@@ -1265,6 +1276,11 @@ size_t carve(QmpcEpisodeSenseDev& d, char* base, int M) {
   QMPC_EPISODE_SENSE_ARRAYS(QMPC_CARVE)
   return off;
 }
+size_t carve(QmpcActDev& d, char* base, int M) {
+  size_t off = 0;
+  QMPC_ACT_ARRAYS(QMPC_CARVE)
+  return off;
+}
 #undef QMPC_CARVE
 
 // d's arrays as views into buf, which is allocated on first use (a later init of the same handle reuses the block)
@@ -1951,6 +1967,125 @@ int qmpc_sense_view_get(qmpc_handle c, qmpc_sense_view* v) {
   v->epoch = c->sense->a.epoch;
   v->batch = c->sense->batch;
   v->seed = c->sense->seed;
+  return QMPC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
+// Actuator stage (include/qmpc_act.h).  The kernels are in qmpc_act.hip.
+namespace {
+
+int act_check(qmpc_ctx* c, int batch) {
+  if (const int rc = plant_check(c, batch)) return rc;
+  if (!c->act || !c->act->batch) return QMPC_ERR_STATE;
+  if (batch != c->act->batch) return QMPC_ERR_ARG;
+  return QMPC_OK;
+}
+
+void act_unbind(QmpcActArgs& a) {
+  a.battery_v = a.tau_max = a.strength = a.damping = a.dry_friction = nullptr;
+  a.delay = nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qmpc_act_config_default(qmpc_act_config* cfg) {
+  if (!cfg) return QMPC_ERR_ARG;
+  // MiniCheetah.h:28-46 as Quadruped::buildActuatorModels assembles them (abad and hip share a gear ratio)
+  *cfg = qmpc_act_config{{6.0, 6.0, 9.33}, 0.05, 0.173, 24.0, 0.01, 0.2, 3.0, 1, 0};
+  return QMPC_OK;
+}
+
+int qmpc_act_init(qmpc_handle c, int batch, const qmpc_act_config* cfg_, void* stream_) {
+  if (const int rc = plant_check(c, batch)) return rc;
+  qmpc_act_config cfg;
+  qmpc_act_config_default(&cfg);
+  if (cfg_) cfg = *cfg_;
+  if (cfg.max_delay < 0 || cfg.max_delay > QMPC_ACT_MAX_DELAY) return QMPC_ERR_ARG;
+  if (!(cfg.kt > 0.0) || !(cfg.R > 0.0)) return QMPC_ERR_ARG;
+  for (const double g : cfg.gear)
+    if (!(g > 0.0)) return QMPC_ERR_ARG;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!c->act) c->act.reset(new qmpc_ctx::Act());
+  qmpc_ctx::Act* k = c->act.get();
+  HIP_TRY(c, carve_block(k->buf, k->a.d, c->max_batch));
+  const size_t ring_n = (size_t)(cfg.max_delay + 1) * (size_t)c->max_batch * 12;
+  if (k->ring.n < ring_n) {
+    // (a longer ring than the handle has had so far: the old block goes, after the device has finished with it)
+    k->batch = 0;
+    DevBuf<double> grown;
+    HIP_TRY(c, grown.alloc(ring_n));
+    k->ring = std::move(grown);
+  }
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  HIP_TRY(c, hipMemsetAsync(k->buf, 0, k->buf.n, stream));
+  HIP_TRY(c, hipMemsetAsync(k->ring, 0, sizeof(double) * (size_t)(cfg.max_delay + 1) * (size_t)batch * 12, stream));
+  k->a.ring = k->ring;
+  k->a.cfg = cfg;
+  act_unbind(k->a);
+  k->batch = batch;
+  return QMPC_OK;
+}
+
+int qmpc_act_set_params(qmpc_handle c, int batch, const qmpc_act_params* prm) {
+  if (const int rc = act_check(c, batch)) return rc;
+  QmpcActArgs& a = c->act->a;
+  act_unbind(a);
+  if (prm) {
+    a.battery_v = prm->battery_v;
+    a.tau_max = prm->tau_max;
+    a.strength = prm->strength;
+    a.damping = prm->damping;
+    a.dry_friction = prm->dry_friction;
+    a.delay = prm->delay;
+  }
+  return QMPC_OK;
+}
+
+int qmpc_act_reset(qmpc_handle c, int batch, const uint8_t* mask_a, const uint8_t* mask_b, int stats, void* stream_) {
+  if (const int rc = act_check(c, batch)) return rc;
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  HIP_TRY(c, qmpc_launch_act_reset(&c->act->a.d, mask_a, mask_b, stats, batch, q.stream));
+  return QMPC_OK;
+}
+
+int qmpc_act(qmpc_handle c, int batch, const double* effort_in, double* effort_out, void* stream_) {
+  if (const int rc = act_check(c, batch)) return rc;
+  if (!effort_in || !effort_out) return QMPC_ERR_ARG;
+  // the kernel reads the rates in the plant's motor rows while it writes the output
+  const double* motor = c->plant->d.motor;
+  if (effort_out < motor + (size_t)batch * 24 && motor < effort_out + (size_t)batch * 12) return QMPC_ERR_ARG;
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  QmpcActArgs a = c->act->a;
+  a.motor = motor;
+  a.dt = 1.0 / c->ctrl->freq;
+  HIP_TRY(c, qmpc_launch_act(&a, effort_in, effort_out, batch, q.stream));
+  return QMPC_OK;
+}
+
+int qmpc_act_view_get(qmpc_handle c, qmpc_act_view* v) {
+  if (!c || !v) return QMPC_ERR_ARG;
+  if (!ctrl_ready(c) || !plant_ready(c) || !c->act || !c->act->batch) return QMPC_ERR_STATE;
+  const QmpcActArgs& a = c->act->a;
+  v->ring = a.ring;
+  v->head = a.d.head;
+  v->age = a.d.age;
+  v->n = a.d.n;
+  v->n_vsat = a.d.n_vsat;
+  v->n_tsat = a.d.n_tsat;
+  v->tau_peak = a.d.tau_peak;
+  v->e_heat = a.d.e_heat;
+  v->e_mech = a.d.e_mech;
+  v->e_pos = a.d.e_pos;
+  v->config = a.cfg;
+  v->dt = 1.0 / c->ctrl->freq;
+  v->batch = c->act->batch;
   return QMPC_OK;
 }
 

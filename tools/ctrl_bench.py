@@ -59,9 +59,17 @@ us_per_period_median is the whole period, tick to reading.
 after qmpc_episode_sense_hold has put every 100th robot into a warm-up longer than the run, so that 1 % of the fleet is
 held on every step (the held_* fields).  launches_per_episode_step counts what one step enqueues in this configuration.
 
+--actuators puts the actuator stage of include/qmpc_act.h (the Mini Cheetah's motor, friction on) between the tick and the
+plant step of every --source -- with --source imu / state, which have no plant in the loop, a plant standing beside the
+stream supplies the joint rates the launch reads --; --delay D gives the ring D + 1 rows and robot b a latency of b mod
+(D + 1) ticks.  The timed window then runs 2 x --repeats times in ONE session, alternating without and with the launch
+(off, on, off, on, ...): us_per_period_without_act / _with_act are the medians over the windows' median periods (tick to the
+period's last launch), us_added_per_period their difference, us_per_act_median the event pair around the launch itself.
+Without --actuators the stage is never initialised and the loop enqueues what it enqueued before.
+
     python tools/ctrl_bench.py [--batches 1024,4096,16384] [--cycles 8] [--warmup 26] [--schedule lockstep|per_robot]
                                [--stagger] [--robot-mode 0|1] [--source imu|state|plant|sensor] [--vary] [--terrain] [--contact] [--field]
-                               [--noise] [--episodes] [--every K] [--warm W] [--out FILE]
+                               [--noise] [--episodes] [--every K] [--warm W] [--actuators] [--delay D] [--repeats R] [--out FILE]
 """
 import argparse
 import json
@@ -75,7 +83,7 @@ sys.path.insert(0, ROOT)
 
 
 def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, source="imu", vary=False, noise=False, terrain=False,
-        contact=False, field=False, episodes=False, every=1, warm=50):
+        contact=False, field=False, episodes=False, every=1, warm=50, actuators=False, delay=0, repeats=3):
     import torch
     from quadruped_ctrl_amd import workloads as W
     from quadruped_ctrl_amd.binding import BatchedController
@@ -178,6 +186,19 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
     if plant is None:
         imu, motor = torch.from_numpy(imu).cuda(), torch.from_numpy(motor).cuda()
     eff = torch.empty((B, 12), dtype=torch.float64, device="cuda")
+    acts = None
+    if actuators:
+        from quadruped_ctrl_amd.binding import BatchedActuators, BatchedPlant
+        rates = plant
+        if rates is None:        # (no plant in the loop: one standing beside the stream, for the rates the launch reads)
+            rates = BatchedPlant(ctrl)
+            rates.init()
+        acts = BatchedActuators(rates)
+        acts.init(max_delay=delay)
+        if delay:
+            act_delay = (torch.arange(B, device="cuda") % (delay + 1)).to(torch.int32)
+            acts.set_params(delay=act_delay)
+        ep_mask = manager.view()["mask"] if manager is not None else None
     if stagger:
         group = torch.arange(B, device="cuda") % 13
         for t in range(13):
@@ -193,19 +214,26 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
 
     hold_flags = sensed.view()["hold"] if sensed is not None else None
 
-    def window():
-        ev = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(5 if manager is not None else 4)) for _ in range(n)]
+    def window(act_on=actuators):
+        ev = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(6 if actuators else 5 if manager is not None else 4))
+              for _ in range(n)]
         for t in range(n):
             if vary and t in (300, 350):     # (outside the timed pairs: the push starts and ends)
                 force.copy_(push) if t == 300 else force.zero_()
             ev[t][0].record()
             tick(imu[t % 26], motor[t % 26], eff)
             ev[t][1].record()
+            if acts is not None:         # (the pair 1 -> 5 is recorded either way; it brackets the launch when it is on)
+                if act_on:
+                    acts.apply(eff)
+                ev[t][5].record()
             if plant is not None:
                 plant.step(eff)
                 ev[t][2].record()
             if sensed is not None:       # the sensor path's manager sits between the plant step and the reading
                 sensed.step(eff)
+                if acts is not None and act_on:
+                    acts.reset(ep_mask, hold_flags)
                 ev[t][4].record()
             if sensors is not None:
                 sensors.sense()
@@ -214,11 +242,37 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
                 held_seen.append(hold_flags.sum(dtype=torch.int32))
             if manager is not None and sensed is None and (t + 1) % every == 0:
                 manager.step(every)
+                if acts is not None and act_on:
+                    acts.reset(ep_mask)
                 ev[t][4].record()
         torch.cuda.synchronize()
         return ev
 
-    ev = window()
+    act_res = None
+    if acts is None:
+        ev = window()
+    else:
+        # the period's last event: the reading, else the plant step, else the (possibly empty) actuator pair
+        last = 3 if sensors is not None else 2 if plant is not None else 5
+        kept = np.arange(n) >= warmup
+        med = {False: [], True: []}
+        act_us = []
+        for _ in range(repeats):
+            for on in (False, True):
+                ev = window(on)
+                med[on].append(float(np.median(np.array([e[0].elapsed_time(e[last]) * 1e3 for e in ev])[kept])))
+                if on:
+                    act_us.append(float(np.median(np.array([e[1].elapsed_time(e[5]) * 1e3 for e in ev])[kept])))
+        st = acts.stats()
+        off_, on_ = float(np.median(med[False])), float(np.median(med[True]))
+        act_res = {"actuators": True, "delay": delay, "repeats": repeats,
+                   "us_per_period_without_act": round(off_, 2), "us_per_period_with_act": round(on_, 2),
+                   "us_added_per_period": round(on_ - off_, 2), "us_per_act_median": round(float(np.median(act_us)), 2),
+                   "us_per_period_without_act_windows": [round(x, 2) for x in med[False]],
+                   "us_per_period_with_act_windows": [round(x, 2) for x in med[True]],
+                   "act_calls": int(st["n"].min().item()), "n_vsat": int(st["n_vsat"].sum().item()),
+                   "n_tsat": int(st["n_tsat"].sum().item()), "e_heat_mean_J": round(float(st["e_heat"].mean().item()), 3),
+                   "tau_peak_max": round(float(st["tau_peak"].max().item()), 3)}
     us = np.array([e[0].elapsed_time(e[1]) * 1e3 for e in ev])
     mpc = (np.arange(n) + 1) % 13 == 0
     keep = np.arange(n) >= warmup
@@ -259,8 +313,10 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
         res.update({"us_per_nonmpc_tick": round(t_non, 2), "us_per_mpc_tick": round(t_mpc, 2),
                     "us_per_13_tick_cycle": round(per_cycle, 1),
                     "robot_ticks_per_s": float(f"{13 * B / (per_cycle * 1e-6):.4g}")})
+    if act_res is not None:
+        res.update(act_res)
     if plant is not None:
-        us_p = np.array([e[1].elapsed_time(e[2]) * 1e3 for e in ev])[keep]
+        us_p = np.array([e[5 if acts is not None else 1].elapsed_time(e[2]) * 1e3 for e in ev])[keep]
         pz = plant.view()["p"][:, 2]
         res.update({"us_per_plant_step_median": round(float(np.median(us_p)), 2), "us_per_plant_step_max": round(float(us_p.max()), 2),
                     "body_height_min": round(float(pz.min().item()), 4), "body_height_max": round(float(pz.max().item()), 4),
@@ -315,6 +371,9 @@ def main():
     ap.add_argument("--episodes", action="store_true")
     ap.add_argument("--every", type=int, default=1)
     ap.add_argument("--warm", type=int, default=50)
+    ap.add_argument("--actuators", action="store_true")
+    ap.add_argument("--delay", type=int, default=0)
+    ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.vary and a.source not in ("plant", "sensor"):
@@ -333,6 +392,8 @@ def main():
         ap.error("--warm W >= 0 goes with --source sensor --episodes")
     if a.every < 1 or (a.every != 1 and not a.episodes):
         ap.error("--every K >= 1 goes with --episodes")
+    if not 0 <= a.delay <= 64 or a.repeats < 1 or ((a.delay or a.repeats != 3) and not a.actuators):
+        ap.error("--delay D (0 .. 64) and --repeats R >= 1 go with --actuators")
     if a.noise and a.source != "sensor":
         ap.error("--noise needs --source sensor")
     if a.robot_mode == 1:
@@ -342,7 +403,7 @@ def main():
     out = []
     for B in [int(x) for x in a.batches.split(",")]:
         r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source, a.vary, a.noise, a.terrain, a.contact, a.field,
-                a.episodes, a.every, a.warm)
+                a.episodes, a.every, a.warm, a.actuators, a.delay, a.repeats)
         print(json.dumps(r), flush=True)
         out.append(r)
     if a.out:
