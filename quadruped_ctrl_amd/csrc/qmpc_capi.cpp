@@ -237,8 +237,9 @@ struct __attribute__((visibility("hidden"))) qmpc_ctx {
     // qmpc_field.h: the caller's bank and placements as bound (z null: no field) and the binding's QMPC_TERRAIN_* flags
     QmpcFieldArgs field{};
     int field_flags = 0;
-    // what a field launcher is given for the terrain: the rows as bound (or none) under both bindings' flags
-    QmpcTerrainArgs field_terrain() const {
+    // what a launcher is given for the terrain: the rows as bound (or none) under both bindings' flags (field_flags is 0
+    // while no field is bound: without one this is `terrain` as it stands)
+    QmpcTerrainArgs ground() const {
       QmpcTerrainArgs t = terrain;
       t.flags |= field_flags;
       return t;
@@ -1577,23 +1578,59 @@ int plant_check(qmpc_ctx* c, int batch) {
   return QMPC_OK;
 }
 
+// One launcher per entry of qmpc_plant_pick.h's lists, in the enums' order
+typedef hipError_t (*PlantStepLauncher)(const QmpcPlantStepArgs*, int vary, int stats, hipStream_t);
+typedef hipError_t (*PlantResetLauncher)(const QmpcPlantResetArgs*, hipStream_t);
+#define QMPC_PLANT_ENTRY(NAME, name) qmpc_launch_##name##_step,
+const PlantStepLauncher kPlantStep[QMPC_STEP_KINDS] = {QMPC_PLANT_STEP_KINDS(QMPC_PLANT_ENTRY)};
+#undef QMPC_PLANT_ENTRY
+#define QMPC_PLANT_ENTRY(NAME, name) qmpc_launch_##name##_init,
+const PlantResetLauncher kPlantReset[QMPC_RESET_KINDS] = {QMPC_PLANT_RESET_KINDS(QMPC_PLANT_ENTRY)};
+#undef QMPC_PLANT_ENTRY
+
+QmpcPlantPick plant_pick(const qmpc_ctx::Plant* k) {
+  return qmpc_plant_pick(k->field.z != nullptr, k->contact.flags != 0, k->terrain.rows != nullptr);
+}
+
+// The argument block of a step, from the handle as it stands now and the call's three pointers.  Every step kernel is
+// given the same block and reads what it knows of.
+QmpcPlantStepArgs plant_step_args(qmpc_ctx* c, int batch, const double* effort, double* state_out, double* motor_out) {
+  qmpc_ctx::Plant* k = c->plant.get();
+  const QmpcCtrlDev& d = c->ctrl->d;
+  QmpcPlantStepArgs A{};
+  A.S = k->d;
+  A.K = plant_const(c, k->mu, k->substeps);
+  A.effort = effort;
+  A.contact_state = d.contact_state;
+  A.p_des = d.p_des;
+  A.v_des = d.v_des;
+  A.state_out = state_out;
+  A.motor_out = motor_out;
+  A.n = batch * 4;
+  // nothing bound and the statistics off: the plain instantiation, which is given no QmpcPlantVary to read
+  if (k->bound || k->stats_on) A.V = k->vary;
+  A.T = k->ground();
+  if (k->contact.flags) {
+    k->contact.dt = 1.0 / c->ctrl->freq;
+    k->contact_dirty = true;
+  }
+  A.C = k->contact;
+  A.Fd = k->field;
+  return A;
+}
+
 // The plant's reset of the masked robots on whatever ground is bound (qmpc_plant_reset, and the episode manager's).  The
 // caller holds the DeviceGuard and has ordered the stream.
 int plant_reset_enqueue(qmpc_ctx* c, int batch, const uint8_t* mask_dev, const double* init_xyyaw, hipStream_t stream) {
-  const QmpcPlantConst K = plant_const(c, c->plant->mu, c->plant->substeps);
   const qmpc_ctx::Plant* k = c->plant.get();
-  if (k->field.z) {
-    // (the counters' reset first: with no rows bound it zeroes support and ground, which the field's reset then writes)
-    if (k->contact.flags) HIP_TRY(c, qmpc_launch_contact_reset(mask_dev, batch, stream, &k->terrain, &k->contact));
-    const QmpcTerrainArgs T = k->field_terrain();
-    HIP_TRY(c, qmpc_launch_field_init(&k->d, &K, mask_dev, init_xyyaw, batch, stream, &T, &k->field));
-    return QMPC_OK;
-  }
-  if (k->terrain.rows)
-    HIP_TRY(c, qmpc_launch_terrain_init(&k->d, &K, mask_dev, init_xyyaw, batch, stream, &k->terrain));
-  else
-    HIP_TRY(c, qmpc_launch_plant_init(&k->d, &K, mask_dev, init_xyyaw, batch, stream));
-  if (k->contact.flags) HIP_TRY(c, qmpc_launch_contact_reset(mask_dev, batch, stream, &k->terrain, &k->contact));
+  const QmpcPlantPick pick = plant_pick(k);
+  // The counters' reset first, on every ground.  With no rows bound it also zeroes support and ground, which the flat
+  // reset does not know; the flat init writes none of what it writes, and the terrain's and the field's inits write
+  // support and ground after it on the same stream: the same bytes at the end as with the init first.
+  if (pick.contact) HIP_TRY(c, qmpc_launch_contact_reset(mask_dev, batch, stream, &k->terrain, &k->contact));
+  const QmpcPlantResetArgs A{k->d, plant_const(c, k->mu, k->substeps), mask_dev, init_xyyaw, batch * 4,
+                             k->ground(), k->field};
+  HIP_TRY(c, kPlantReset[pick.reset](&A, stream));
   return QMPC_OK;
 }
 
@@ -1634,8 +1671,8 @@ int qmpc_plant_init(qmpc_handle c, int batch, double mu_plant, int substeps, con
     k->contact.late = k->contact.early + M;
   }
   if (const int rc = order_after_previous(c, stream)) return rc;
-  const QmpcPlantConst K = plant_const(c, mu_plant, substeps);
-  HIP_TRY(c, qmpc_launch_plant_init(&k->d, &K, nullptr, init_xyyaw, batch, stream));
+  const QmpcPlantResetArgs A{k->d, plant_const(c, mu_plant, substeps), nullptr, init_xyyaw, batch * 4, {}, {}};
+  HIP_TRY(c, qmpc_launch_plant_init(&A, stream));
   if (k->contact_dirty) {
     // a plant that stepped with contact on starts again with its counters at zero (no other plant launches this)
     const QmpcTerrainArgs flat{nullptr, k->terrain.ground, k->terrain.support, 0};
@@ -1670,35 +1707,9 @@ int qmpc_plant_step(qmpc_handle c, int batch, const double* effort, double* stat
   if (!effort || !state_out || !motor_out) return QMPC_ERR_ARG;
   const Enqueue q(c, stream_);
   if (q.rc) return q.rc;
-  const QmpcCtrlDev& d = c->ctrl->d;
-  const QmpcPlantConst K = plant_const(c, c->plant->mu, c->plant->substeps);
-  // nothing bound and the statistics off: the plain instantiation, which is given no QmpcPlantVary to read
-  qmpc_ctx::Plant* k = c->plant.get();
-  const bool extra = k->bound || k->stats_on;
-  if (k->field.z) {
-    // a height field is bound: the same step, one kernel, on the summed surface (the rows may be null, the contact flags 0)
-    const QmpcTerrainArgs T = k->field_terrain();
-    if (k->contact.flags) {
-      k->contact.dt = 1.0 / c->ctrl->freq;
-      k->contact_dirty = true;
-      HIP_TRY(c, qmpc_launch_field_contact_step(&k->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out,
-                                                batch, q.stream, extra ? &k->vary : nullptr, k->bound, k->stats_on, &T,
-                                                &k->contact, &k->field));
-    } else
-      HIP_TRY(c, qmpc_launch_field_step(&k->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out, batch,
-                                        q.stream, extra ? &k->vary : nullptr, k->bound, k->stats_on, &T, &k->field));
-  } else if (k->contact.flags) {
-    k->contact.dt = 1.0 / c->ctrl->freq;
-    k->contact_dirty = true;
-    HIP_TRY(c, qmpc_launch_contact_step(&k->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out,
-                                        batch, q.stream, extra ? &k->vary : nullptr, k->bound, k->stats_on, &k->terrain,
-                                        &k->contact));
-  } else if (k->terrain.rows)
-    HIP_TRY(c, qmpc_launch_terrain_step(&k->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out,
-                                        batch, q.stream, extra ? &k->vary : nullptr, k->bound, k->stats_on, &k->terrain));
-  else
-    HIP_TRY(c, qmpc_launch_plant_step(&k->d, &K, effort, d.contact_state, d.p_des, d.v_des, state_out, motor_out, batch,
-                                      q.stream, extra ? &k->vary : nullptr, k->bound, k->stats_on));
+  const qmpc_ctx::Plant* k = c->plant.get();
+  const QmpcPlantStepArgs A = plant_step_args(c, batch, effort, state_out, motor_out);
+  HIP_TRY(c, kPlantStep[plant_pick(k).step](&A, k->bound, k->stats_on, q.stream));
   return QMPC_OK;
 }
 

@@ -15,16 +15,9 @@
 
 namespace {
 
-// (i_0 + i_1) + (i_2 + i_3) over the quad, in every lane
-__device__ __forceinline__ int contact_quad_count(int x) {
-  x = x + __shfl_xor(x, 1);
-  x = x + __shfl_xor(x, 2);
-  return x;
-}
-
-// qmpc_plant_reset while contact is on, after the plant's or the terrain's own reset kernel (mask == NULL: every
-// robot): the masked robots' counters and drop are zeroed; with no terrain bound so are support and ground, which the
-// flat reset does not know.  n = batch * 4 lanes, one per (robot, leg).
+// qmpc_plant_reset while contact is on, before the ground's own reset kernel (mask == NULL: every robot): the masked
+// robots' counters and drop are zeroed; with no terrain bound so are support and ground, which the flat reset does not
+// know and the field's reset writes afterwards.  n = batch * 4 lanes, one per (robot, leg).
 __global__ __launch_bounds__(256) void qmpc_contact_reset_kernel(const uint8_t* __restrict__ mask, const int n,
                                                                  const QmpcTerrainArgs T, const QmpcContactArgs C) {
   const int t = blockIdx.x * 256 + threadIdx.x;
@@ -42,31 +35,20 @@ __global__ __launch_bounds__(256) void qmpc_contact_reset_kernel(const uint8_t* 
   }
 }
 
-// The arguments of a step, one struct by value: it IS the kernarg segment, so the kernel can read it a second time.
-struct ContactStepArgs {
-  QmpcPlantDev S;
-  QmpcPlantConst K;
-  const double* effort;
-  const float *contact_state, *p_des, *v_des;
-  double *state_out, *motor_out;
-  int n;
-  QmpcPlantVary V;
-  QmpcTerrainArgs T;
-  QmpcContactArgs C;
-};
-
-// One control period with contact decided by the ground.  The step holds the registers of the terrain step plus the
+// One control period with contact decided by the ground.  The arguments are one struct by value, qmpc_plant.h's
+// QmpcPlantStepArgs: it IS the kernarg segment, so the kernel can read it a second time (its last member, the field's
+// arguments, is kernarg bytes this kernel never loads).  The step holds the registers of the terrain step plus the
 // sliding velocity, the drop and the counters: one wave per SIMD, which a launch of this size (bound by its launch gap)
 // does not feel.  The two dozen pointers that only the stores at the end need would sit in scalar registers through
 // the whole step and push others out; they are read from the kernarg segment again behind the arithmetic instead (the
 // empty asm keeps the compiler from hoisting those loads to the top).
 template <bool VARY, bool STATS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void qmpc_contact_step_kernel(
-    const ContactStepArgs A) {
+    const QmpcPlantStepArgs A) {
 #pragma clang fp contract(off)
   constexpr bool FIELD = false;
   const QmpcFieldArgs Fd{};
-  typedef ContactStepArgs StepArgs;
+  typedef QmpcPlantStepArgs StepArgs;
 #include "qmpc_contact_step_body.h"
 }
 
@@ -75,33 +57,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 extern "C" hipError_t qmpc_launch_contact_reset(const uint8_t* mask, int batch, hipStream_t stream,
                                                 const QmpcTerrainArgs* T, const QmpcContactArgs* C) {
   const int n = batch * 4;
-  hipLaunchKernelGGL(qmpc_contact_reset_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, mask, n, *T, *C);
+  hipLaunchKernelGGL(qmpc_contact_reset_kernel, plant_grid(n), dim3(256), 0, stream, mask, n, *T, *C);
   return hipGetLastError();
 }
 
-// V == NULL: nothing bound and the statistics off.  Otherwise vary and stats pick the instantiation, as in
-// qmpc_launch_plant_step.
-extern "C" hipError_t qmpc_launch_contact_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
-                                               const float* contact_state, const float* p_des, const float* v_des,
-                                               double* state_out, double* motor_out, int batch, hipStream_t stream,
-                                               const QmpcPlantVary* V, int vary, int stats, const QmpcTerrainArgs* T,
-                                               const QmpcContactArgs* C) {
-  const int n = batch * 4;
-  const dim3 grid((n + 255) / 256), block(256);
-  vary = V && vary;
-  stats = V && stats;
-  const ContactStepArgs A{*S, *K, effort, contact_state, p_des, v_des, state_out, motor_out, n,
-                          vary || stats ? *V : QmpcPlantVary{}, *T, *C};
-#define QMPC_CONTACT_STEP(VARY, STATS) \
-  hipLaunchKernelGGL((qmpc_contact_step_kernel<VARY, STATS>), grid, block, 0, stream, A)
-  if (vary && stats)
-    QMPC_CONTACT_STEP(true, true);
-  else if (vary)
-    QMPC_CONTACT_STEP(true, false);
-  else if (stats)
-    QMPC_CONTACT_STEP(false, true);
-  else
-    QMPC_CONTACT_STEP(false, false);
-#undef QMPC_CONTACT_STEP
+extern "C" hipError_t qmpc_launch_contact_step(const QmpcPlantStepArgs* A, int vary, int stats, hipStream_t stream) {
+  plant_vary_stats(vary, stats, [&](auto VARY, auto STATS) {
+    hipLaunchKernelGGL((qmpc_contact_step_kernel<VARY.value, STATS.value>), plant_grid(A->n), dim3(256), 0, stream, *A);
+  });
   return hipGetLastError();
 }

@@ -1,10 +1,9 @@
 // qmpc_contact_step_body.h -- the statements of one control period with contact decided by the ground, as TEXT: included
 // inside the body of a contact step kernel (qmpc_contact.hip: FIELD false; qmpc_field.hip: FIELD true) after
-// qmpc_plant_dev.h and contact_quad_count, for the reason qmpc_plant_step_body.h gives, with in scope
+// qmpc_plant_dev.h, for the reason qmpc_plant_step_body.h gives, with in scope
 //   #pragma clang fp contract(off) at the head of the kernel's body;
 //   the template parameters bool VARY, bool STATS, and constexpr bool FIELD;
-//   the kernel's one parameter A and its type StepArgs (ContactStepArgs, or with FIELD the struct that adds the field's
-//   arguments as its LAST member, so that the kernarg segment's head is the same), and
+//   the kernel's one parameter A and its type StepArgs (qmpc_plant.h's QmpcPlantStepArgs in both files), and
 //   Fd (QmpcFieldArgs: A's member in the field kernels, an empty local of the others).
 // The numbered comments are the steps of include/qmpc_contact.h.  FIELD (include/qmpc_field.h): the robot's place row is
 // loaded once beside the terrain row, every height is the summed surface, and G.n is this lane's own foot's normal,

@@ -15,13 +15,6 @@
 
 namespace {
 
-// (i_0 + i_1) + (i_2 + i_3) over the quad, in every lane
-__device__ __forceinline__ int contact_quad_count(int x) {
-  x = x + __shfl_xor(x, 1);
-  x = x + __shfl_xor(x, 2);
-  return x;
-}
-
 // qmpc_plant_reset while a field is bound (mask == NULL: every robot): qmpc_terrain_init_kernel on the summed surface.
 // T.rows may be null (the field alone).  Every lane computes (the shuffles need their partners); masked ones store.
 __global__ __launch_bounds__(256) void qmpc_field_init_kernel(const QmpcPlantDev S, const QmpcPlantConst K,
@@ -83,92 +76,40 @@ __global__ __launch_bounds__(256) void qmpc_field_step_kernel(const QmpcPlantDev
 #include "qmpc_plant_step_body.h"
 }
 
-// The arguments of a contact step on the field: qmpc_contact.hip's ContactStepArgs member for member, then the field's.
-struct FieldContactStepArgs {
-  QmpcPlantDev S;
-  QmpcPlantConst K;
-  const double* effort;
-  const float *contact_state, *p_des, *v_des;
-  double *state_out, *motor_out;
-  int n;
-  QmpcPlantVary V;
-  QmpcTerrainArgs T;
-  QmpcContactArgs C;
-  QmpcFieldArgs Fd;
-};
-
 // One control period with contact decided by the summed surface: qmpc_contact_step_body.h with FIELD = true, under the
 // launch bounds of qmpc_contact_step_kernel.
 template <bool VARY, bool STATS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void qmpc_field_contact_step_kernel(
-    const FieldContactStepArgs A) {
+    const QmpcPlantStepArgs A) {
 #pragma clang fp contract(off)
   constexpr bool FIELD = true;
   const QmpcFieldArgs& Fd = A.Fd;
-  typedef FieldContactStepArgs StepArgs;
+  typedef QmpcPlantStepArgs StepArgs;
 #include "qmpc_contact_step_body.h"
 }
 
 }  // namespace
 
-extern "C" hipError_t qmpc_launch_field_init(const QmpcPlantDev* S, const QmpcPlantConst* K, const uint8_t* mask,
-                                             const double* xyyaw, int batch, hipStream_t stream, const QmpcTerrainArgs* T,
-                                             const QmpcFieldArgs* Fd) {
-  const int n = batch * 4;
-  hipLaunchKernelGGL(qmpc_field_init_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, *S, *K, mask, xyyaw, n, *T,
-                     *Fd);
+extern "C" hipError_t qmpc_launch_field_init(const QmpcPlantResetArgs* A, hipStream_t stream) {
+  hipLaunchKernelGGL(qmpc_field_init_kernel, plant_grid(A->n), dim3(256), 0, stream, A->S, A->K, A->mask, A->xyyaw, A->n,
+                     A->T, A->Fd);
   return hipGetLastError();
 }
 
-// V == NULL: nothing bound and the statistics off.  Otherwise vary and stats pick the instantiation, as in
-// qmpc_launch_plant_step.
-extern "C" hipError_t qmpc_launch_field_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
-                                             const float* contact_state, const float* p_des, const float* v_des,
-                                             double* state_out, double* motor_out, int batch, hipStream_t stream,
-                                             const QmpcPlantVary* V, int vary, int stats, const QmpcTerrainArgs* T,
-                                             const QmpcFieldArgs* Fd) {
-  const int n = batch * 4;
-  const dim3 grid((n + 255) / 256), block(256);
-  const QmpcPlantVary none{};
-  vary = V && vary;
-  stats = V && stats;
-#define QMPC_FIELD_STEP(VARY, STATS, v)                                                                            \
-  hipLaunchKernelGGL((qmpc_field_step_kernel<VARY, STATS>), grid, block, 0, stream, *S, *K, effort, contact_state, \
-                     p_des, v_des, state_out, motor_out, n, v, *T, *Fd)
-  if (vary && stats)
-    QMPC_FIELD_STEP(true, true, *V);
-  else if (vary)
-    QMPC_FIELD_STEP(true, false, *V);
-  else if (stats)
-    QMPC_FIELD_STEP(false, true, *V);
-  else
-    QMPC_FIELD_STEP(false, false, none);
-#undef QMPC_FIELD_STEP
+extern "C" hipError_t qmpc_launch_field_step(const QmpcPlantStepArgs* A, int vary, int stats, hipStream_t stream) {
+  plant_vary_stats(vary, stats, [&](auto VARY, auto STATS) {
+    hipLaunchKernelGGL((qmpc_field_step_kernel<VARY.value, STATS.value>), plant_grid(A->n), dim3(256), 0, stream, A->S,
+                       A->K, A->effort, A->contact_state, A->p_des, A->v_des, A->state_out, A->motor_out, A->n, A->V,
+                       A->T, A->Fd);
+  });
   return hipGetLastError();
 }
 
-extern "C" hipError_t qmpc_launch_field_contact_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
-                                                     const float* contact_state, const float* p_des, const float* v_des,
-                                                     double* state_out, double* motor_out, int batch, hipStream_t stream,
-                                                     const QmpcPlantVary* V, int vary, int stats,
-                                                     const QmpcTerrainArgs* T, const QmpcContactArgs* C,
-                                                     const QmpcFieldArgs* Fd) {
-  const int n = batch * 4;
-  const dim3 grid((n + 255) / 256), block(256);
-  vary = V && vary;
-  stats = V && stats;
-  const FieldContactStepArgs A{*S, *K, effort, contact_state, p_des, v_des, state_out, motor_out, n,
-                               vary || stats ? *V : QmpcPlantVary{}, *T, *C, *Fd};
-#define QMPC_FIELD_CONTACT_STEP(VARY, STATS) \
-  hipLaunchKernelGGL((qmpc_field_contact_step_kernel<VARY, STATS>), grid, block, 0, stream, A)
-  if (vary && stats)
-    QMPC_FIELD_CONTACT_STEP(true, true);
-  else if (vary)
-    QMPC_FIELD_CONTACT_STEP(true, false);
-  else if (stats)
-    QMPC_FIELD_CONTACT_STEP(false, true);
-  else
-    QMPC_FIELD_CONTACT_STEP(false, false);
-#undef QMPC_FIELD_CONTACT_STEP
+extern "C" hipError_t qmpc_launch_field_contact_step(const QmpcPlantStepArgs* A, int vary, int stats,
+                                                     hipStream_t stream) {
+  plant_vary_stats(vary, stats, [&](auto VARY, auto STATS) {
+    hipLaunchKernelGGL((qmpc_field_contact_step_kernel<VARY.value, STATS.value>), plant_grid(A->n), dim3(256), 0, stream,
+                       *A);
+  });
   return hipGetLastError();
 }

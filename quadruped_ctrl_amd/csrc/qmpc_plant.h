@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qmpc_plant_pick.h"
+
 // X(element type, name, elements per robot): members, carving and the view are generated from the list
 #define QMPC_PLANT_ARRAYS(X)                                                        \
   X(double, p, 3)       /* body position, world */                                  \
@@ -89,50 +91,51 @@ struct QmpcFieldArgs {
 #define QMPC_PLANT_KNEE_MIN 0.05    /* the swing clamp's shell, as knee angles */
 #define QMPC_PLANT_KNEE_MAX 2.6
 
-// Launchers of qmpc_plant.hip, declared once for the file that defines them and for qmpc_capi.cpp, which calls them: a
-// signature that drifts fails to compile.
-extern "C" hipError_t qmpc_launch_plant_init(const QmpcPlantDev* S, const QmpcPlantConst* K, const uint8_t* mask,
-                                             const double* xyyaw, int batch, hipStream_t stream);
-extern "C" hipError_t qmpc_launch_plant_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
-                                             const float* contact_state, const float* p_des, const float* v_des,
-                                             double* state_out, double* motor_out, int batch, hipStream_t stream,
-                                             const QmpcPlantVary* V, int vary, int stats);
+// The arguments of a step, filled in one place (qmpc_capi.cpp: plant_step_args) and given to every step launcher.  The
+// contact kernels take this struct itself, by value: it IS their kernarg segment, which they read a second time
+// (qmpc_contact_step_body.h), so a member a kernel does not read costs it kernarg bytes and no instruction.  The
+// scheduled-contact kernels keep separate parameters (profiles/plant_kernel_resources.txt); their launchers spread the
+// members they take.  V is an empty QmpcPlantVary when nothing is bound and the statistics are off; T carries the OR of
+// the terrain's and the field's flags; n = batch * 4 lanes.
+struct QmpcPlantStepArgs {
+  QmpcPlantDev S;
+  QmpcPlantConst K;
+  const double* effort;
+  const float *contact_state, *p_des, *v_des;
+  double *state_out, *motor_out;
+  int n;
+  QmpcPlantVary V;
+  QmpcTerrainArgs T;
+  QmpcContactArgs C;
+  QmpcFieldArgs Fd;
+};
+
+// ... and of a reset that stands the masked robots on the ground (mask == NULL: every robot; xyyaw == NULL: the origin).
+struct QmpcPlantResetArgs {
+  QmpcPlantDev S;
+  QmpcPlantConst K;
+  const uint8_t* mask;
+  const double* xyyaw;
+  int n;
+  QmpcTerrainArgs T;  // qmpc_launch_plant_init reads neither T nor Fd
+  QmpcFieldArgs Fd;   // qmpc_launch_terrain_init does not read Fd
+};
+
+// Launchers, declared once for the files that define them and for qmpc_capi.cpp, which calls them: a signature that
+// drifts fails to compile.  One step and one reset launcher per entry of qmpc_plant_pick.h's lists, all of one signature;
+// vary (per-robot parameters bound) and stats (statistics on) pick the step's instantiation.
+#define QMPC_PLANT_DECLARE(NAME, name)                                                                             \
+  extern "C" hipError_t qmpc_launch_##name##_step(const QmpcPlantStepArgs* A, int vary, int stats, hipStream_t stream);
+QMPC_PLANT_STEP_KINDS(QMPC_PLANT_DECLARE)
+#undef QMPC_PLANT_DECLARE
+#define QMPC_PLANT_DECLARE(NAME, name) \
+  extern "C" hipError_t qmpc_launch_##name##_init(const QmpcPlantResetArgs* A, hipStream_t stream);
+QMPC_PLANT_RESET_KINDS(QMPC_PLANT_DECLARE)
+#undef QMPC_PLANT_DECLARE
 extern "C" hipError_t qmpc_launch_plant_stats_reset(const QmpcPlantVary* V, const uint8_t* mask, int batch,
                                                     hipStream_t stream);
-// ... and of qmpc_terrain.hip, which capi picks while terrain rows are bound (T->rows is not null): the same arguments
-// with the terrain's after them.
-extern "C" hipError_t qmpc_launch_terrain_init(const QmpcPlantDev* S, const QmpcPlantConst* K, const uint8_t* mask,
-                                               const double* xyyaw, int batch, hipStream_t stream,
-                                               const QmpcTerrainArgs* T);
-extern "C" hipError_t qmpc_launch_terrain_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
-                                               const float* contact_state, const float* p_des, const float* v_des,
-                                               double* state_out, double* motor_out, int batch, hipStream_t stream,
-                                               const QmpcPlantVary* V, int vary, int stats, const QmpcTerrainArgs* T);
-// ... and of qmpc_contact.hip, which capi picks while contact flags are set: the step on any ground (T->rows may be
-// null: height 0, normal (0, 0, 1)) and the reset of the counters, enqueued after the plant's or the terrain's own reset.
-extern "C" hipError_t qmpc_launch_contact_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
-                                               const float* contact_state, const float* p_des, const float* v_des,
-                                               double* state_out, double* motor_out, int batch, hipStream_t stream,
-                                               const QmpcPlantVary* V, int vary, int stats, const QmpcTerrainArgs* T,
-                                               const QmpcContactArgs* C);
+// qmpc_contact.hip: the reset of the contact counters, enqueued before the ground's own reset (T->rows may be null)
 extern "C" hipError_t qmpc_launch_contact_reset(const uint8_t* mask, int batch, hipStream_t stream,
                                                 const QmpcTerrainArgs* T, const QmpcContactArgs* C);
-// ... and of qmpc_field.hip, which capi picks while a height field is bound: the reset, the scheduled-contact step and
-// the contact step on the summed surface of include/qmpc_field.h (T->rows may be null: the field alone; T->flags is the
-// OR of both bindings' flags), with the field's arguments after the others.
-extern "C" hipError_t qmpc_launch_field_init(const QmpcPlantDev* S, const QmpcPlantConst* K, const uint8_t* mask,
-                                             const double* xyyaw, int batch, hipStream_t stream, const QmpcTerrainArgs* T,
-                                             const QmpcFieldArgs* Fd);
-extern "C" hipError_t qmpc_launch_field_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
-                                             const float* contact_state, const float* p_des, const float* v_des,
-                                             double* state_out, double* motor_out, int batch, hipStream_t stream,
-                                             const QmpcPlantVary* V, int vary, int stats, const QmpcTerrainArgs* T,
-                                             const QmpcFieldArgs* Fd);
-extern "C" hipError_t qmpc_launch_field_contact_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
-                                                     const float* contact_state, const float* p_des, const float* v_des,
-                                                     double* state_out, double* motor_out, int batch, hipStream_t stream,
-                                                     const QmpcPlantVary* V, int vary, int stats,
-                                                     const QmpcTerrainArgs* T, const QmpcContactArgs* C,
-                                                     const QmpcFieldArgs* Fd);
 
 #endif

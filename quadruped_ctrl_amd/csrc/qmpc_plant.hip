@@ -85,35 +85,16 @@ __global__ __launch_bounds__(256) void qmpc_plant_stats_reset_kernel(const QmpcP
 
 }  // namespace
 
-extern "C" hipError_t qmpc_launch_plant_init(const QmpcPlantDev* S, const QmpcPlantConst* K, const uint8_t* mask,
-                                             const double* xyyaw, int batch, hipStream_t stream) {
-  const int n = batch * 4;
-  hipLaunchKernelGGL(qmpc_plant_init_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, *S, *K, mask, xyyaw, n);
+extern "C" hipError_t qmpc_launch_plant_init(const QmpcPlantResetArgs* A, hipStream_t stream) {
+  hipLaunchKernelGGL(qmpc_plant_init_kernel, plant_grid(A->n), dim3(256), 0, stream, A->S, A->K, A->mask, A->xyyaw, A->n);
   return hipGetLastError();
 }
 
-// V == NULL: the plain step.  Otherwise vary (per-robot parameters bound) and stats (statistics on) pick the instantiation.
-extern "C" hipError_t qmpc_launch_plant_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
-                                             const float* contact_state, const float* p_des, const float* v_des,
-                                             double* state_out, double* motor_out, int batch, hipStream_t stream,
-                                             const QmpcPlantVary* V, int vary, int stats) {
-  const int n = batch * 4;
-  const dim3 grid((n + 255) / 256), block(256);
-  const QmpcPlantVary none{};
-  vary = V && vary;
-  stats = V && stats;
-#define QMPC_PLANT_STEP(VARY, STATS, v)                                                                            \
-  hipLaunchKernelGGL((qmpc_plant_step_kernel<VARY, STATS>), grid, block, 0, stream, *S, *K, effort, contact_state, \
-                     p_des, v_des, state_out, motor_out, n, v)
-  if (vary && stats)
-    QMPC_PLANT_STEP(true, true, *V);
-  else if (vary)
-    QMPC_PLANT_STEP(true, false, *V);
-  else if (stats)
-    QMPC_PLANT_STEP(false, true, *V);
-  else
-    QMPC_PLANT_STEP(false, false, none);
-#undef QMPC_PLANT_STEP
+extern "C" hipError_t qmpc_launch_plant_step(const QmpcPlantStepArgs* A, int vary, int stats, hipStream_t stream) {
+  plant_vary_stats(vary, stats, [&](auto VARY, auto STATS) {
+    hipLaunchKernelGGL((qmpc_plant_step_kernel<VARY.value, STATS.value>), plant_grid(A->n), dim3(256), 0, stream, A->S,
+                       A->K, A->effort, A->contact_state, A->p_des, A->v_des, A->state_out, A->motor_out, A->n, A->V);
+  });
   return hipGetLastError();
 }
 

@@ -15,6 +15,8 @@
 #ifndef QMPC_PLANT_DEV_CODE_H
 #define QMPC_PLANT_DEV_CODE_H
 
+#include <type_traits>
+
 #include "qmpc_plant.h"
 #include "qmpc_field_index.h"
 
@@ -117,6 +119,12 @@ __device__ __forceinline__ void plant_leg(const QmpcPlantConst& K, double side, 
 // (f_0 + f_1) + (f_2 + f_3) over the quad, in every lane
 __device__ __forceinline__ double plant_quad_sum(double x) {
 #pragma clang fp contract(off)
+  x = x + __shfl_xor(x, 1);
+  x = x + __shfl_xor(x, 2);
+  return x;
+}
+// (i_0 + i_1) + (i_2 + i_3) over the quad, in every lane
+__device__ __forceinline__ int contact_quad_count(int x) {
   x = x + __shfl_xor(x, 1);
   x = x + __shfl_xor(x, 2);
   return x;
@@ -345,6 +353,23 @@ __device__ __forceinline__ void plant_readout(const QmpcPlantDev& S, const QmpcP
     S.omega[(size_t)b * 3 + k] = w[k];
   }
   for (int k = 0; k < 4; ++k) S.q[(size_t)b * 4 + k] = q[k];
+}
+
+// Host side of every launcher here: 256 lanes per block over n = batch * 4 lanes ...
+inline dim3 plant_grid(int n) { return dim3((n + 255) / 256); }
+
+// ... and the <VARY, STATS> instantiation of a step kernel from the launcher's two flags: launch(VARY, STATS) is called
+// with two std::bool_constants, whose ::value a generic lambda can use as a template argument.
+template <class Launch>
+void plant_vary_stats(bool vary, bool stats, Launch launch) {
+  if (vary && stats)
+    launch(std::true_type{}, std::true_type{});
+  else if (vary)
+    launch(std::true_type{}, std::false_type{});
+  else if (stats)
+    launch(std::false_type{}, std::true_type{});
+  else
+    launch(std::false_type{}, std::false_type{});
 }
 
 }  // namespace

@@ -67,36 +67,17 @@ __global__ __launch_bounds__(256) void qmpc_terrain_step_kernel(const QmpcPlantD
 
 }  // namespace
 
-extern "C" hipError_t qmpc_launch_terrain_init(const QmpcPlantDev* S, const QmpcPlantConst* K, const uint8_t* mask,
-                                               const double* xyyaw, int batch, hipStream_t stream,
-                                               const QmpcTerrainArgs* T) {
-  const int n = batch * 4;
-  hipLaunchKernelGGL(qmpc_terrain_init_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, *S, *K, mask, xyyaw, n, *T);
+extern "C" hipError_t qmpc_launch_terrain_init(const QmpcPlantResetArgs* A, hipStream_t stream) {
+  hipLaunchKernelGGL(qmpc_terrain_init_kernel, plant_grid(A->n), dim3(256), 0, stream, A->S, A->K, A->mask, A->xyyaw,
+                     A->n, A->T);
   return hipGetLastError();
 }
 
-// V == NULL: nothing bound and the statistics off.  Otherwise vary and stats pick the instantiation, as in
-// qmpc_launch_plant_step.
-extern "C" hipError_t qmpc_launch_terrain_step(const QmpcPlantDev* S, const QmpcPlantConst* K, const double* effort,
-                                               const float* contact_state, const float* p_des, const float* v_des,
-                                               double* state_out, double* motor_out, int batch, hipStream_t stream,
-                                               const QmpcPlantVary* V, int vary, int stats, const QmpcTerrainArgs* T) {
-  const int n = batch * 4;
-  const dim3 grid((n + 255) / 256), block(256);
-  const QmpcPlantVary none{};
-  vary = V && vary;
-  stats = V && stats;
-#define QMPC_TERRAIN_STEP(VARY, STATS, v)                                                                            \
-  hipLaunchKernelGGL((qmpc_terrain_step_kernel<VARY, STATS>), grid, block, 0, stream, *S, *K, effort, contact_state, \
-                     p_des, v_des, state_out, motor_out, n, v, *T)
-  if (vary && stats)
-    QMPC_TERRAIN_STEP(true, true, *V);
-  else if (vary)
-    QMPC_TERRAIN_STEP(true, false, *V);
-  else if (stats)
-    QMPC_TERRAIN_STEP(false, true, *V);
-  else
-    QMPC_TERRAIN_STEP(false, false, none);
-#undef QMPC_TERRAIN_STEP
+extern "C" hipError_t qmpc_launch_terrain_step(const QmpcPlantStepArgs* A, int vary, int stats, hipStream_t stream) {
+  plant_vary_stats(vary, stats, [&](auto VARY, auto STATS) {
+    hipLaunchKernelGGL((qmpc_terrain_step_kernel<VARY.value, STATS.value>), plant_grid(A->n), dim3(256), 0, stream, A->S,
+                       A->K, A->effort, A->contact_state, A->p_des, A->v_des, A->state_out, A->motor_out, A->n, A->V,
+                       A->T);
+  });
   return hipGetLastError();
 }

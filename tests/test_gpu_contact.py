@@ -180,10 +180,71 @@ def test_flags_zero_change_no_bit(schedule, terrain):
     cb.close()
 
 
+def _masked_reset_is_the_models(ground):
+    """Contact on, on `ground` = "flat", "terrain" or "field": five robots (20 lanes, a third of one wave: every lane past
+    n is a padding lane) walk 13 closed-loop ticks, every counter, drop, support and ground is then made non-zero, and
+    reset(robots 1 and 3) leaves what tests/plant_model_field.py's reset leaves from the same state: the two robots
+    standing on their ground with their counters and drop at zero (without rows, support and ground too), at the parity's
+    tolerance and the integers exactly; the other three bit for bit as they were."""
+    from quadruped_ctrl_amd.binding import rollout
+    import plant_loop_field as LF
+    import plant_model_field as PF
+    B = 5
+    gait, vel, xyyaw = (a[:B] for a in L.commands(0))
+    c, plant = _pair(B, xyyaw=xyyaw)
+    c.set_gait(_dev(c, gait))
+    c.set_vel(_dev(c, vel))
+    m = PF.FieldPlantModel(B, DEFAULTS["freq"], DEFAULTS["mu"], 1, xyyaw)
+    keep = []
+    if ground == "terrain":
+        rows = LT.terrain(B)
+        keep.append(_dev(c, rows))
+        plant.set_terrain(keep[-1], clamp_swing=True, rebase_z=True)
+        m.set_terrain(rows, clamp_swing=True, rebase_z=True)
+    if ground == "field":
+        z, place, cell = LF.field_for(B, 0.06)
+        keep += [_dev(c, z), _dev(c, place)]
+        plant.set_field(keep[-2], keep[-1], cell, clamp_swing=True, rebase_z=True)
+        m.set_field(z, place, cell, clamp_swing=True, rebase_z=True)
+    plant.set_contact(**ON)
+    m.set_contact(**ON)
+    plant.reset(_all(c, B), _dev(c, xyyaw))
+    rollout(c, plant, 13)
+    v, t = plant.contact(), plant.terrain()
+    print(ground, "after 13 ticks:", {k: float(np.abs(a).max()) for k, a in _snap4(plant, B).items() if k in CONTACT_KEYS + ("support", "ground")})
+    for k in CONTACT_KEYS:
+        v[k].add_(1)
+    for k in ("support", "ground"):
+        t[k].add_(0.125)
+    before = _snap4(plant, B)
+    assert all(before[k].all() for k in CONTACT_KEYS + ("support", "ground"))
+    m.load(before)
+    for k in ("grf", "state", "motor", "ground", "support") + CONTACT_KEYS:
+        setattr(m, k, before[k].copy())
+    mask = np.zeros(B, bool)
+    mask[[1, 3]] = True
+    plant.reset(_dev(c, mask), _dev(c, xyyaw))
+    m.reset(mask, xyyaw)
+    after = _snap4(plant, B)
+    _compare_contact(after, m, f"masked reset on {ground}")
+    for k in CONTACT_KEYS + (("support", "ground") if ground == "flat" else ()):
+        assert not after[k][mask].any(), (ground, k)
+    if ground != "flat":
+        assert np.array_equal(after["p"][mask][:, 2], 0.29 + after["ground"][mask])
+    for k in before:
+        assert np.array_equal(after[k][~mask], before[k][~mask]), (ground, k)
+    assert (after["stance"][mask] == 1).all() and plant.contact()["flags"] == 7
+    del keep
+    c.close()
+
+
 def test_init_switches_contact_off_and_reset_keeps_it():
     """reset(mask) keeps contact on and zeroes the masked robots' counters and drop only; init() switches it off, zeroes
-    the counters, and the plant is the plain plant again, bit for bit."""
+    the counters, and the plant is the plain plant again, bit for bit.  The masked reset is the model's on flat ground
+    and on terrain (_masked_reset_is_the_models; tests/test_gpu_field.py runs it on the field)."""
     from quadruped_ctrl_amd.binding import rollout
+    for ground in ("flat", "terrain"):
+        _masked_reset_is_the_models(ground)
     B = 64
     ca, pa, (gait, vel, xyyaw) = _walk_pair(B)
     cb, pb, _ = _walk_pair(B)

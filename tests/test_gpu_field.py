@@ -343,9 +343,11 @@ def test_the_fleet_walks_on_the_field(kind, mode, path):
 
 def test_reset_keeps_the_binding_and_init_unbinds():
     """reset(mask) stands the masked robots on the summed surface -- the field over slope and stairs -- and leaves the
-    others alone; init() unbinds, and the plant is the plain plant again, bit for bit."""
+    others alone; init() unbinds, and the plant is the plain plant again, bit for bit.  With contact decided by the ground
+    the masked reset is the model's too, counters included (tests/test_gpu_contact.py: _masked_reset_is_the_models)."""
     from quadruped_ctrl_amd.binding import rollout
     import plant_model_field as PF
+    TCN._masked_reset_is_the_models("field")
     B = 32
     ca, pa, keep, (gait, vel, xyyaw) = _walk_on_field(B, "scheduled", amp=0.06)
     cb, pb, _ = _walk_pair(B)

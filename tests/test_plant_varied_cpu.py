@@ -139,6 +139,30 @@ def test_cpu_closed_loop_on_the_varied_plant_is_safe_and_is_what_the_fixture_rec
 
 
 @pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="no hipcc")
+def test_kernel_choice_for_every_binding(tmp_path):
+    """tests/plant_pick_dump.cpp: csrc/qmpc_plant_pick.h alone, host only.  The step and the reset kernel for all eight
+    combinations of (field bound, contact flags set, rows bound) are the public headers' rules: a bound field takes the
+    kernels of include/qmpc_field.h whatever else is bound; without one, contact flags take include/qmpc_contact.h's step
+    on any ground; without either, rows take include/qmpc_terrain.h's; else the flat plant.  The reset stands the robots
+    on the ground -- field, rows or flat -- and ignores contact, whose counters it zeroes exactly when contact is on."""
+    exe = str(tmp_path / "plant_pick_dump")
+    subprocess.run([HIPCC, "-x", "c++", "-std=c++17", "-Wall", "-Werror", os.path.join(ROOT, "tests", "plant_pick_dump.cpp"), "-o", exe],
+                   check=True)
+    got = json.loads(subprocess.run([exe], check=True, capture_output=True, text=True).stdout)
+    #           field contact rows   step             reset
+    want = [(0, 0, 0, "plant", "plant"),
+            (0, 0, 1, "terrain", "terrain"),
+            (0, 1, 0, "contact", "plant"),
+            (0, 1, 1, "contact", "terrain"),
+            (1, 0, 0, "field", "field"),
+            (1, 0, 1, "field", "field"),
+            (1, 1, 0, "field_contact", "field"),
+            (1, 1, 1, "field_contact", "field")]
+    assert [(g["field"], g["contact"], g["rows"], g["step"], g["reset"]) for g in got] == want
+    assert [g["counters"] for g in got] == [w[1] for w in want]
+
+
+@pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="no hipcc")
 def test_plant_kernel_resources(tmp_path):
     """Every plant kernel -- init, the statistics' reset and the four <VARY, STATS> instantiations of the step --
     compiles for gfx950 without scratch, and the plain step keeps the 221 VGPRs INTEGRATION.md G records for it."""
