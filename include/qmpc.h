@@ -78,9 +78,18 @@ extern "C" {
                                 two adds, never inside a step (a point part of the way along a step minimises
                                 nothing).  A robot whose solve needs no more than max_iter working-set changes is
                                 untouched by the cap, bit for bit */
-#define QMPC_ST_NOT_PD 2     /* condensed Hessian not positive definite */
-#define QMPC_ST_INFEASIBLE 4 /* constraints inconsistent (cannot happen for
-                                friction pyramids with f_max >= 0) */
+#define QMPC_ST_NOT_PD 2     /* condensed Hessian not positive definite: a pivot of its sweep was not positive (weights and
+                                alpha all zero, a negative alpha, non-finite input).  JCQP alternate: the sweep runs on the
+                                ADMM's matrix P + sigma I + A^T R A, so the bit says that THAT matrix is not positive
+                                definite, or that a diagonal entry of the condensed Hessian P is not positive (P = 0
+                                included); an indefinite P with a positive diagonal that sigma and rho make definite
+                                is not detected there */
+#define QMPC_ST_INFEASIBLE 4 /* constraints inconsistent (cannot happen for friction pyramids with f_max >= 0).  With
+                                f_max < 0 -- which qmpc_setup accepts -- every stance foot-step's box is empty; the dual
+                                method can only tell once its working set has grown to about the reduced size n_r, so a
+                                robot with n_r <= 96 reports QMPC_ST_INFEASIBLE (where its first engine has fewer slots
+                                than that: after the hand-over to the Schur-form engine, with QMPC_ST_FALLBACK) and a
+                                larger one QMPC_ST_WS_FULL.  Either way it reads zero forces */
 #define QMPC_ST_WS_FULL 8    /* working-set capacity exceeded */
 #define QMPC_ST_FALLBACK 16  /* informational, NOT an error: the robot was solved by a slower engine than
                                 its class's first choice: the Schur-form engine (the fast engine's working-set
@@ -136,7 +145,9 @@ int qmpc_destroy(qmpc_handle h);
 
 /* Replaces setup_problem(dt, horizon, mu, f_max)
  * (src/MPC_Ctrl/convexMPC_interface.cpp:42-66).  dt, mu and f_max are
- * rounded to float exactly as struct problem_setup stores them. */
+ * rounded to float exactly as struct problem_setup stores them.
+ * QMPC_ERR_ARG (horizon out of range, dt or mu not positive, f_max NaN) leaves the handle as it was.  A negative f_max is
+ * taken as given: every robot with a stance foot-step is then reported (QMPC_ST_INFEASIBLE / QMPC_ST_WS_FULL below). */
 int qmpc_setup(qmpc_handle h, double dt, int horizon, double mu, double f_max);
 
 /* Robot constants the reference hard-codes: mass 9 (RobotState.h:23),

@@ -473,7 +473,8 @@ int qmpc_destroy(qmpc_handle h) {
 
 int qmpc_setup(qmpc_handle c, double dt, int horizon, double mu, double f_max) {
   if (!c) return QMPC_ERR_ARG;
-  if (horizon <= 0 || horizon > c->max_horizon || !(mu > 0) || !(dt > 0)) return QMPC_ERR_ARG;
+  // (a NaN f_max would switch every fz <= f_max row off without a status bit: no comparison with it is ever true)
+  if (horizon <= 0 || horizon > c->max_horizon || !(mu > 0) || !(dt > 0) || f_max != f_max) return QMPC_ERR_ARG;
   // struct problem_setup stores floats (convexMPC_interface.h:13-19)
   c->dt = (double)(float)dt;
   c->mu = (double)(float)mu;

@@ -1427,6 +1427,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     }
     // ---- H = 2 (tau (x) E_00 + sigma (x) E_11 + x_drag terms + alpha I) element by element (SolverMPC.cpp:395): a wave per
     // row, lanes along the columns
+    bool bad = false;  // a pivot of the sweep below that is not positive (JCQP alternate: or a diagonal entry of P itself)
     {
       const double w11 = Aa.W[11] * dm2, w5 = Aa.W[5] * dm2, w5x = Aa.W[5] * (x_drag * dm2);
       for (int r = wv; r < n; r += NWV) {
@@ -1446,6 +1447,8 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
           if (P.admm_mode != 0 && r == j) {
             // JCQP alternate on a large problem (use_jcqp = 1 / 2 at horizons above 16): the KKT matrix reduced to the x
             // block, M = P + sigma I + A^T R A with its DIAGONAL friction part -- as in stage 2 of the ADMM instantiations
+            // (and like there a diagonal entry of P that is not positive is reported: QMPC_ST_NOT_PD)
+            bad |= !(hv > 0.0);
             const double fk = S.fmaxk[r / 3];
             const double rho4 = (__builtin_fabs(fk) < 1e-10) ? P.admm_rho * 1e3 : (fk > 1e10 ? 1e-6 : P.admm_rho);
             hv += P.admm_sigma + ((ai < 2) ? 2.0 * 1e-6 * P.mu_inv * P.mu_inv : 4.0 * 1e-6 + rho4);
@@ -1477,7 +1480,6 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
         tl[(pq % NWV) * TLW + pq / NWV] = (unsigned short)((ti0 << 8) | (pq - ti0 * (ti0 + 1) / 2));
       }
     }
-    bool bad = false;
 #pragma unroll 1
     for (int k0 = 0; k0 < n; k0 += NB) {
       const int bsz = (n - k0 < NB) ? n - k0 : NB;
@@ -1801,6 +1803,10 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
 
   if (dbg_clk && tid == 0) dbg_clk[13] = clock64();
   double a[CW];
+  // JCQP alternate: the sweep below runs on M = P + sigma I + A^T R A, which sigma and rho can make definite where the
+  // condensed Hessian P itself is not (P = 0: weights and alpha all zero).  A diagonal entry of P that is not positive
+  // -- no positive definite matrix has one -- is looked at here, before the diagonal terms are added (QMPC_ST_NOT_PD)
+  bool hdiag = false;
   {
     const bool rowok = i < n;
     const int ki = rowok ? (int)S.sidx[(i / 3) & 63] : 0;  // (i/3 < 64 always; the load is unconditional)
@@ -1919,7 +1925,10 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
 #pragma unroll
       for (int jj = 0; jj < CW; ++jj) {
         double v = 2.0 * (a[jj] + ((dd == jj) ? dval : 0.0));
-        if constexpr (ADMM) v += (dd == jj) ? dadm : 0.0;  // the KKT matrix reduced to the x block
+        if constexpr (ADMM) {
+          hdiag |= rowok && dd == jj && !(v > 0.0);
+          v += (dd == jj) ? dadm : 0.0;  // the KKT matrix reduced to the x block
+        }
         a[jj] = v;
       }
     } else {
@@ -1927,7 +1936,10 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       for (int jj = 0; jj < CW; ++jj) {
         const int j = c * CW + jj;
         double v = 2.0 * (a[jj] + ((i == j) ? alpha : 0.0));
-        if constexpr (ADMM) v += (i == j) ? admm_diag : 0.0;  // the KKT matrix reduced to the x block
+        if constexpr (ADMM) {
+          hdiag |= rowok && i == j && !(v > 0.0);
+          v += (i == j) ? admm_diag : 0.0;  // the KKT matrix reduced to the x block
+        }
         a[jj] = (rowok && j < n) ? v : ((i == j) ? 1.0 : 0.0);  // identity padding
       }
     }
@@ -2256,7 +2268,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       });
     }
   }
-  if (notpd) S.status = QMPC_DEV_ST_NOT_PD;  // benign race: same value from every thread
+  if (notpd || hdiag) S.status = QMPC_DEV_ST_NOT_PD;  // benign race: same value from every thread
   QMPC_TICK(4);
   QMPC_STOP(3, a);
 

@@ -1615,9 +1615,14 @@ def test_empty_batch_and_argument_errors(mpc_factory):
     assert m.lib.qmpc_solve(m.h, 8, C.byref(bad2), C.byref(out), C.c_void_p(s)) == 1      # bad stride
     torch.cuda.synchronize()
     assert (o["grf"] == 7.0).all()
+    want = m.solve(b)
+    # a NaN f_max is refused (it would switch every fz <= f_max row off without a status bit) and leaves the handle as it was
+    assert m.lib.qmpc_setup(m.h, b["dt"], b["horizon"], b["mu"], float("nan")) == 1
     m.solve_async(8, inp, out)
     torch.cuda.synchronize()
     assert not (o["grf"] == 7.0).all()
+    assert np.array_equal(o["grf"].cpu().numpy(), want["grf"]) and np.array_equal(o["status"].cpu().numpy(), want["status"])
+    assert ((want["status"] & 47) == 0).all()
 
 
 def test_torch_custom_op(mpc_factory):
