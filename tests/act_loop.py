@@ -1,17 +1,13 @@
 """plant_loop.cpu_loop with the actuator stage of include/qmpc_act.h between the controller and the plant -- TEST SIDE
-ONLY.  tests/golden/make_act_closed_loop.py records its ladders; tests/test_act_cpu.py reads them and re-runs a prefix,
-tests/test_gpu_act.py holds the GPU fleet to the walking rungs by plant_loop.envelope().
+ONLY: plant_loop.closed_loop (the only copy of the tick) with `actuators`.  tests/golden/make_act_closed_loop.py records
+its ladders; tests/test_act_cpu.py reads them and re-runs a prefix, tests/test_gpu_act.py holds the GPU fleet to the
+walking rungs by plant_loop.envelope().
 """
 import numpy as np
 
-from oracle import oracle as O
-
 import act_model as AM
-import ctrl_model as M
-import ctrl_model_mode1 as M1
 import plant_loop as L
 import plant_model as PM
-from ctrl_model_state import estimate_state
 
 COUNTERS = AM.ACCUMULATORS
 # the rungs of the recorded ladders: (name, actuator arguments); `delay` is every robot's latency in ticks
@@ -36,46 +32,18 @@ def model_for(B, actuator):
 def cpu_loop_act(mode, ticks=L.TICKS, trace=False, **actuator):
     """plant_loop.cpu_loop(mode) with the motor, the latency and the accumulators in the loop
     -> (stats, info): info holds safe [B], the counters and, with trace, the state after every tick."""
-    gait, vel, xyyaw = L.commands(mode)
-    B = L.N_CMD
-    m = (M1.CtrlModelMode1 if mode == 1 else M.CtrlModel)(B, L.FREQ, L.PID)
-    m.set_gait(gait)
-    m.set_vel(vel)
-    plant = PM.PlantModel(B, L.FREQ, 0.4, 1, xyyaw)
-    act = model_for(B, actuator)
-    rec = L.Recorder(B, ticks)
-    rec.add(plant.state, initial=True)
-    nwsr_max, n_solves, rc_bad, states = 0, 0, 0, []
-    for t in range(ticks):
-        state, motor = plant.state, plant.motor
-        e = estimate_state(m, state, motor)
-        m.loco(e)
-        if mode == 0:
-            due = np.arange(B) if (t + 1) % 13 == 0 else np.zeros(0, int)
-        else:
-            due = np.flatnonzero(m.due)
-        if len(due):
-            if mode == 0:
-                r, wpd, xci = O.pack_commands(m.command(e), float(m.dt_mpc))
-            else:
-                cmd, tables = m.command_mode1(e, due)
-                r, wpd, xci = O.pack_commands(cmd, float(m.dt_mpc))
-                r["gait"] = tables
-            m.wpd[due], m.xci[due] = wpd, xci
-            r.update(dt=float(m.dt_mpc), mu=0.4, f_max=120.0)
-            soln, nwsr, rc = O.solve_batch(r)
-            rc_bad += int((rc != 0).sum())
-            nwsr_max = max(nwsr_max, int(nwsr.max()))
-            n_solves += len(due)
-            m.f_ff[due] = O.forces_to_body(e["r_body"][due], soln[:, :12].astype(np.float32))
-        eff = m.legcmd(e, m.f_ff)
-        eff = act.apply(eff, np.asarray(motor, np.float64)[:, 12:24])
-        plant.step(eff, m.contact_state, m.p_des, m.v_des)
-        rec.add(plant.state)
-        if trace:
+    m, xyyaw = L.controller_for(mode)
+    plant = PM.PlantModel(L.N_CMD, L.FREQ, 0.4, 1, xyyaw)
+    states = []
+
+    def record(t, plant):                              # (called before the step: the state after tick t - 1)
+        if t:
             states.append(np.asarray(plant.state, np.float64).copy())
-    info = dict(safe=m.safe.copy(), nwsr_max=nwsr_max, n_solves=n_solves, rc_bad=rc_bad,
-                counters={k: act.acc[k].copy() for k in COUNTERS})
+
+    stats, info = L.closed_loop(m, plant, ticks, actuators=model_for(L.N_CMD, actuator), each_tick=record if trace else None)
+    out = dict(L.scalars(info), counters={k: info["actuators"].acc[k].copy() for k in COUNTERS})
     if trace:
-        info["states"] = np.stack(states)
-    return rec.stats(), info
+        out["states"] = np.stack(states + [np.asarray(plant.state, np.float64).copy()])
+    return stats, out
+
+

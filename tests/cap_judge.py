@@ -64,6 +64,19 @@ def _records():
 
 RECORDS = _records()
 MIXED = ("mixed",)                # families whose robots differ widely in count: the middle cap must leave some alone
+# the families of tests/test_gpu_iteration_cap.py (tests/test_gpu_error_exits.py runs them too):
+# family -> (record of RECORDS, qmpc_set_split mode or None, engine events hook, fixed caps or None)
+FAMILIES = {
+    "trot": ("trot", None, 0, None),                                   # 64-row class, event-form engine
+    "mixed": ("mixed", None, 0, None),                                 # 64- and 96-row classes in one call
+    "standing_h10_one_kernel": ("standing_h10", False, 0, None),       # 128-row class, spills to the overflow pool
+    "standing_h10_decoupled": ("standing_h10", True, 0, None),         # qmpc_engine.hip
+    "decoupled_handed_back": ("standing_h10", True, 12, (20,)),        # handed back: capped by the one-kernel path, from 0
+    "standing_h14_one_kernel": ("standing_h14", False, 0, None),       # 192-row class
+    "standing_h14_decoupled": ("standing_h14", True, 0, None),
+    "many_active": ("many_active", None, 0, None),                     # Schur-form engine after the fallback; drops
+    "beyond_192_rows": ("trot_h36", None, 0, None),                    # large-problem path (model QP, not dumped)
+}
 
 
 def caps_of(counts):

@@ -193,7 +193,7 @@ def gi_until_infeasible(b, i, H, g, tol=1e-9, max_iter=5000):
 
 
 # ---- the families
-# The nine engine families are test_gpu_iteration_cap.FAMILIES as they are; ENGINE_FAMILIES names them so that a new one
+# The nine engine families are cap_judge.FAMILIES as they are; ENGINE_FAMILIES names them so that a new one
 # added there cannot be forgotten here (test_error_cases_cpu.py compares the two).  Which exit a family's method has:
 EXACT, ADMM = "exact", "admm"
 ENGINE_FAMILIES = ("trot", "mixed", "standing_h10_one_kernel", "standing_h10_decoupled", "decoupled_handed_back",

@@ -1,9 +1,13 @@
 """The closed loop controller <-> plant on the CPU, and the statistics both loops are compared by -- TEST SIDE ONLY.
 
-cpu_loop() runs tests/plant_model.py against the reference pipeline: the controller's restatements (tests/ctrl_model.py,
-ctrl_model_mode1.py, the cheater estimators of ctrl_model_state.py) with the reference's own qpOASES for every solve
-(oracle.solve_batch).  tests/golden/make_plant_closed_loop.py records its statistics; tests/test_gpu_plant.py holds the
-GPU loop (library controller + device plant) to the recorded envelope by the rule of envelope().
+closed_loop() is the ONLY copy of the reference tick: the controller's restatements (tests/ctrl_model.py,
+ctrl_model_mode1.py, the cheater estimators of ctrl_model_state.py or the filter behind a sensor model) with the
+reference's own qpOASES for every solve (reference_mpc: oracle.solve_batch), on whatever plant model, sensor model and
+actuator model the caller hands it.  cpu_loop() runs it on tests/plant_model.py; plant_loop_varied, plant_loop_terrain,
+plant_loop_contact, plant_loop_field, sense_loop and act_loop hold the other scenarios and call it too.
+tests/golden/make_plant_closed_loop.py records cpu_loop()'s statistics; tests/test_gpu_plant.py holds the GPU loop (library
+controller + device plant) to the recorded envelope by the rule of envelope().  The device side of that comparison --
+the walk and the statistics from the device accumulators -- is tests/fleet_gpu.py.
 """
 import numpy as np
 
@@ -87,40 +91,93 @@ def envelope(rec):
     return out
 
 
-def cpu_loop(mode, ticks=TICKS, substeps=1, mu=0.4):
-    """-> (stats, info): info holds safe [B], the largest reference nWSR, the number of solves."""
+def controller_for(mode):
+    """-> (the controller's restatement for robot mode `mode` with commands() set, the start poses xyyaw [16, 3])."""
     gait, vel, xyyaw = commands(mode)
-    B = N_CMD
-    m = (M1.CtrlModelMode1 if mode == 1 else M.CtrlModel)(B, FREQ, PID)
+    m = (M1.CtrlModelMode1 if mode == 1 else M.CtrlModel)(N_CMD, FREQ, PID)
     m.set_gait(gait)
     m.set_vel(vel)
-    plant = PM.PlantModel(B, FREQ, mu, substeps, xyyaw)
+    return m, xyyaw
+
+
+def reference_mpc(m, e, due):
+    """The reference's MPC for the robots `due` (not empty): command -> oracle.pack_commands (mode 1: with the gait
+    tables) -> wpd / xci written back -> the reference's own qpOASES -> the forces in the body frame into m.f_ff[due].
+    The MPC's model is the controller's: 9 kg, mu 0.4, flat ground, whatever the plant stands on.  -> (nwsr, rc) [due]."""
+    if isinstance(m, M1.CtrlModelMode1):
+        cmd, tables = m.command_mode1(e, due)
+        r, wpd, xci = O.pack_commands(cmd, float(m.dt_mpc))
+        r["gait"] = tables
+    else:
+        r, wpd, xci = O.pack_commands(m.command(e), float(m.dt_mpc))
+    m.wpd[due], m.xci[due] = wpd, xci
+    r.update(dt=float(m.dt_mpc), mu=0.4, f_max=120.0)
+    soln, nwsr, rc = O.solve_batch(r)
+    m.f_ff[due] = O.forces_to_body(e["r_body"][due], soln[:, :12].astype(f32))
+    return nwsr, rc
+
+
+def closed_loop(m, plant, ticks, sensors=None, settle=0, actuators=None, each_tick=None):
+    """THE reference closed loop -- every cpu_loop* of the loop modules is this on its own models.  Per tick: estimate ->
+    loco -> the robots that are due (mode 0: all, every 13th tick; mode 1: m.due) -> reference_mpc -> legcmd -> plant step
+    -> Recorder.  m: a controller's restatement with its commands set; plant: a plant model that the caller has built,
+    bound and reset.
+
+    sensors     a sense_model.SenseModel: the controller estimates from its readings (CtrlModel.estimate) in the order of
+                binding.rollout_sensed -- `settle` times sense -> estimate on the standing plant first (with settle = 0
+                one reading and no estimate), then one reading after every step.  None: the cheater estimators of
+                ctrl_model_state.estimate_state on the plant's own rows.
+    actuators   an act_model.ActModel, applied to the effort with the motor rates the plant showed before the step.
+    each_tick   each_tick(t, plant), called just before the step of tick t.
+
+    -> (stats, info): the Recorder's statistics; info holds safe [B], per robot nwsr_max [B] and rc_bad [B] (the number
+    of solves whose return code was not 0), n_solves, the last tick's estimate, and the objects the loop ran (ctrl, plant,
+    sensors, actuators)."""
+    B = plant.B
+    mode1 = isinstance(m, M1.CtrlModelMode1)
     rec = Recorder(B, ticks)
     rec.add(plant.state, initial=True)
-    nwsr_max, n_solves, rc_bad = 0, 0, 0
+    if sensors is not None:
+        for _ in range(max(settle, 1)):               # BatchedSensors.settle: sense -> pre_work on the standing plant
+            imu, motor = sensors.sense(plant.state, plant.motor)
+            if settle:
+                m.estimate(imu, motor)
+    nwsr_max, rc_bad, n_solves, e = np.zeros(B, int), np.zeros(B, int), 0, None
     for t in range(ticks):
-        state, motor = plant.state, plant.motor
-        e = estimate_state(m, state, motor)
+        e = estimate_state(m, plant.state, plant.motor) if sensors is None else m.estimate(imu, motor)
         m.loco(e)
-        if mode == 0:
-            due = np.arange(B) if (t + 1) % 13 == 0 else np.zeros(0, int)
-        else:
+        if mode1:
             due = np.flatnonzero(m.due)
+        else:
+            due = np.arange(B) if (t + 1) % 13 == 0 else np.zeros(0, int)
         if len(due):
-            if mode == 0:
-                r, wpd, xci = O.pack_commands(m.command(e), float(m.dt_mpc))
-            else:
-                cmd, tables = m.command_mode1(e, due)
-                r, wpd, xci = O.pack_commands(cmd, float(m.dt_mpc))
-                r["gait"] = tables
-            m.wpd[due], m.xci[due] = wpd, xci
-            r.update(dt=float(m.dt_mpc), mu=0.4, f_max=120.0)
-            soln, nwsr, rc = O.solve_batch(r)
-            rc_bad += int((rc != 0).sum())
-            nwsr_max = max(nwsr_max, int(nwsr.max()))
+            nwsr, rc = reference_mpc(m, e, due)
+            rc_bad[due] += (rc != 0)
+            nwsr_max[due] = np.maximum(nwsr_max[due], nwsr)
             n_solves += len(due)
-            m.f_ff[due] = O.forces_to_body(e["r_body"][due], soln[:, :12].astype(f32))
         eff = m.legcmd(e, m.f_ff)
+        if actuators is not None:
+            eff = actuators.apply(eff, np.asarray(plant.motor, np.float64)[:, 12:24])
+        if each_tick is not None:
+            each_tick(t, plant)
         plant.step(eff, m.contact_state, m.p_des, m.v_des)
         rec.add(plant.state)
-    return rec.stats(), dict(safe=m.safe.copy(), nwsr_max=nwsr_max, n_solves=n_solves, rc_bad=rc_bad)
+        if sensors is not None:
+            imu, motor = sensors.sense(plant.state, plant.motor)
+    return rec.stats(), dict(safe=m.safe.copy(), nwsr_max=nwsr_max, rc_bad=rc_bad, n_solves=n_solves, estimate=e, ctrl=m,
+                             plant=plant, sensors=sensors, actuators=actuators)
+
+
+def scalars(info):
+    """info of closed_loop -> the fields cpu_loop reports: safe, nwsr_max over everything, rc_bad as a count, n_solves."""
+    return dict(safe=info["safe"], nwsr_max=int(info["nwsr_max"].max()), n_solves=info["n_solves"],
+                rc_bad=int(info["rc_bad"].sum()))
+
+
+def cpu_loop(mode, ticks=TICKS, substeps=1, mu=0.4):
+    """-> (stats, info): info holds safe [B], the largest reference nWSR, the number of solves."""
+    m, xyyaw = controller_for(mode)
+    stats, info = closed_loop(m, PM.PlantModel(N_CMD, FREQ, mu, substeps, xyyaw), ticks)
+    return stats, scalars(info)
+
+

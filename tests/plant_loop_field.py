@@ -14,23 +14,20 @@ The ladder (tests/golden/make_plant_field_closed_loop.py climbs it) starts at th
 code 0 and nWSR < 100; each climb stops at its first fallen rung.  RUNGS is the MEASURED record: the top walked rung of each
 climb, None when even the first fell -- that combination's walk then runs at amplitude 0 (an all-zero map).  Nothing about
 the plant is tuned to move a rung.
+
+cpu_loop_field() is plant_loop_terrain.walk -- plant_loop.closed_loop, the only copy of the tick -- on FieldPlantModel.
 """
 import numpy as np
 
-from oracle import oracle as O
 from quadruped_ctrl_amd import workloads as W
 
-import ctrl_model as M
-import ctrl_model_mode1 as M1
 import plant_loop as L
+import plant_loop_contact as LC
 import plant_loop_terrain as LT
 import plant_model_contact as PCM
 import plant_model_field as PF
 import sense_loop as SL
-import sense_model as SM
-from ctrl_model_state import estimate_state
 
-f32 = np.float32
 PATHS = LT.PATHS
 KINDS = ("scheduled", "contact")
 LADDER = (0.02, 0.04, 0.06, 0.10, 0.15)
@@ -60,61 +57,17 @@ def cpu_loop_field(mode, path, kind, amp="rung", ticks=None, settle=SL.SETTLE, s
                    plant=None):
     """-> (stats, info): plant_loop_contact.cpu_loop_contact's fields on FieldPlantModel; amp "rung": RUNGS[kind].
     plant: walk THIS plant model (bound, set and reset by the caller) instead; info["plant"] is the plant walked."""
-    assert path in PATHS and kind in KINDS
+    assert kind in KINDS
     amp = RUNGS[kind] if isinstance(amp, str) else amp
-    ticks = TICKS if ticks is None else ticks
-    gait, vel, xyyaw = L.commands(mode)
-    B = L.N_CMD
-    z, place, cell = field_for(B, amp)
-    m = (M1.CtrlModelMode1 if mode == 1 else M.CtrlModel)(B, L.FREQ, L.PID)
-    m.set_gait(gait)
-    m.set_vel(vel)
+    m, xyyaw = L.controller_for(mode)
     if plant is None:
-        plant = PF.FieldPlantModel(B, L.FREQ, mu, substeps, xyyaw)             # init -> set_field -> set_contact -> reset
+        z, place, cell = field_for(L.N_CMD, amp)
+        plant = PF.FieldPlantModel(L.N_CMD, L.FREQ, mu, substeps, xyyaw)       # init -> set_field -> set_contact -> reset
         plant.set_field(z, place, cell, clamp_swing=True, rebase_z=path == "state")
-        fl = contact_flags(kind)
-        plant.set_contact(early=bool(fl & PCM.EARLY), late=bool(fl & PCM.LATE), slip=bool(fl & PCM.SLIP))
-        plant.reset(np.ones(B, bool), xyyaw)
-    rec = L.Recorder(B, ticks)
-    rec.add(plant.state, initial=True)
-    if path == "sensed":
-        sens = SM.SenseModel(B, seed)
-        sens.set_params(**SL.noise(B))
-        for _ in range(settle):
-            imu, motor = sens.sense(plant.state, plant.motor)
-            m.estimate(imu, motor)
-    nwsr_max, rc_bad, n_solves = np.zeros(B, int), np.zeros(B, int), 0
-    for t in range(ticks):
-        e = estimate_state(m, plant.state, plant.motor) if path == "state" else m.estimate(imu, motor)
-        m.loco(e)
-        if mode == 0:
-            due = np.arange(B) if (t + 1) % 13 == 0 else np.zeros(0, int)
-        else:
-            due = np.flatnonzero(m.due)
-        if len(due):
-            if mode == 0:
-                r, wpd, xci = O.pack_commands(m.command(e), float(m.dt_mpc))
-            else:
-                cmd, tables = m.command_mode1(e, due)
-                r, wpd, xci = O.pack_commands(cmd, float(m.dt_mpc))
-                r["gait"] = tables
-            m.wpd[due], m.xci[due] = wpd, xci
-            r.update(dt=float(m.dt_mpc), mu=0.4, f_max=120.0)        # the MPC's model: flat ground, mu 0.4
-            soln, nwsr, rc = O.solve_batch(r)
-            rc_bad[due] += (rc != 0)
-            nwsr_max[due] = np.maximum(nwsr_max[due], nwsr)
-            n_solves += len(due)
-            m.f_ff[due] = O.forces_to_body(e["r_body"][due], soln[:, :12].astype(f32))
-        eff = m.legcmd(e, m.f_ff)
-        plant.step(eff, m.contact_state, m.p_des, m.v_des)
-        rec.add(plant.state)
-        if path == "sensed":
-            imu, motor = sens.sense(plant.state, plant.motor)
-    stats = rec.stats()
-    assert (plant.stats["n"] == ticks).all()
-    psi = xyyaw[:, 2]
-    d = plant.p[:, :2] - xyyaw[:, :2]
-    travel = d[:, 0] * np.cos(psi) + d[:, 1] * np.sin(psi)
-    return stats, dict(safe=m.safe.copy(), nwsr_max=nwsr_max, n_solves=n_solves, rc_bad=rc_bad, travel=travel,
-                       support=plant.support.copy(), ground=plant.ground.copy(), early=plant.early.copy(),
+        LC.set_contact(plant, contact_flags(kind))
+        plant.reset(np.ones(L.N_CMD, bool), xyyaw)
+    stats, info = LT.walk(m, plant, xyyaw, path, TICKS if ticks is None else ticks, settle, seed)
+    return stats, dict(info, support=plant.support.copy(), ground=plant.ground.copy(), early=plant.early.copy(),
                        late=plant.late.copy(), slip=plant.slip.copy(), plant=plant)
+
+

@@ -13,22 +13,16 @@ paths, with every qpOASES return code 0 and nWSR < 100; tests/golden/make_plant_
 and records what it found, tests/test_terrain_cpu.py holds RUNGS and TICKS to the record.  The controller and the oracle
 are not told about the ground.
 
-cpu_loop_terrain(mode, path) is plant_loop.cpu_loop (path "state", with rebase_z) or sense_loop.cpu_loop_sensed with
-sense_loop.noise() (path "sensed"), on TerrainPlantModel with clamp_swing.
+cpu_loop_terrain(mode, path) is plant_loop.closed_loop (the only copy of the tick) on TerrainPlantModel with clamp_swing:
+through the cheater estimators with rebase_z (path "state"), or through sense_loop.noise() and the filter (path "sensed").
+walk() is the part the loops on contact and on the field share with it.
 """
 import numpy as np
 
-from oracle import oracle as O
-
-import ctrl_model as M
-import ctrl_model_mode1 as M1
 import plant_loop as L
 import plant_model_terrain as PT
 import sense_loop as SL
-import sense_model as SM
-from ctrl_model_state import estimate_state
 
-f32 = np.float32
 KINDS = ("stairs_up", "cross_slope", "stairs_down", "uphill")          # by k % 4
 START, TREADS = 0.10, 4
 # the ladders: (run, |rise|) from the reference's own boxes (scripts/walking_simulation.py: depth 0.2, heights 0.01 .. 0.04),
@@ -65,61 +59,34 @@ def terrain(B, rungs=None):
     return rows
 
 
+def travel(plant, xyyaw):
+    """The bodies' final abscissa along their start headings from their starts [B]."""
+    psi = xyyaw[:, 2]
+    d = plant.p[:, :2] - xyyaw[:, :2]
+    return d[:, 0] * np.cos(psi) + d[:, 1] * np.sin(psi)
+
+
+def walk(m, plant, xyyaw, path, ticks, settle, seed):
+    """plant_loop.closed_loop on a plant that stands on its ground, through the cheater estimators (path "state") or
+    through sense_loop.noise() and the filter (path "sensed") -> (stats, info): safe, nwsr_max and rc_bad PER ROBOT, n_solves
+    and travel [16].  The loops on terrain, contact and the field are this plus their plant's own arrays."""
+    assert path in PATHS
+    sens = SL.sensors_for(plant.B, seed) if path == "sensed" else None
+    stats, info = L.closed_loop(m, plant, ticks, sensors=sens, settle=settle)
+    assert (plant.stats["n"] == ticks).all()          # (the model's own accumulators counted every step)
+    return stats, dict(safe=info["safe"], nwsr_max=info["nwsr_max"], n_solves=info["n_solves"], rc_bad=info["rc_bad"],
+                       travel=travel(plant, xyyaw))
+
+
 def cpu_loop_terrain(mode, path, rungs=None, ticks=None, settle=SL.SETTLE, seed=SL.SEED, substeps=1, mu=0.4):
     """-> (stats, info): plant_loop.cpu_loop's fields; info's safe, nwsr_max and rc_bad are PER ROBOT here ([16] each),
     plus travel [16]: the body's final abscissa along its flight's heading from its start, and rows."""
-    assert path in PATHS
-    ticks = TICKS if ticks is None else ticks
-    gait, vel, xyyaw = L.commands(mode)
-    B = L.N_CMD
-    rows = terrain(B, rungs)
-    m = (M1.CtrlModelMode1 if mode == 1 else M.CtrlModel)(B, L.FREQ, L.PID)
-    m.set_gait(gait)
-    m.set_vel(vel)
-    plant = PT.TerrainPlantModel(B, L.FREQ, mu, substeps, xyyaw)                    # init -> set_terrain -> reset(all)
+    m, xyyaw = L.controller_for(mode)
+    rows = terrain(L.N_CMD, rungs)
+    plant = PT.TerrainPlantModel(L.N_CMD, L.FREQ, mu, substeps, xyyaw)              # init -> set_terrain -> reset(all)
     plant.set_terrain(rows, clamp_swing=True, rebase_z=path == "state")
-    plant.reset(np.ones(B, bool), xyyaw)
-    rec = L.Recorder(B, ticks)
-    rec.add(plant.state, initial=True)
-    if path == "sensed":
-        sens = SM.SenseModel(B, seed)
-        sens.set_params(**SL.noise(B))
-        for _ in range(settle):                       # BatchedSensors.settle: sense -> pre_work on the standing plant
-            imu, motor = sens.sense(plant.state, plant.motor)
-            m.estimate(imu, motor)
-    nwsr_max, rc_bad, n_solves = np.zeros(B, int), np.zeros(B, int), 0
-    for t in range(ticks):
-        e = estimate_state(m, plant.state, plant.motor) if path == "state" else m.estimate(imu, motor)
-        m.loco(e)
-        if mode == 0:
-            due = np.arange(B) if (t + 1) % 13 == 0 else np.zeros(0, int)
-        else:
-            due = np.flatnonzero(m.due)
-        if len(due):
-            if mode == 0:
-                r, wpd, xci = O.pack_commands(m.command(e), float(m.dt_mpc))
-            else:
-                cmd, tables = m.command_mode1(e, due)
-                r, wpd, xci = O.pack_commands(cmd, float(m.dt_mpc))
-                r["gait"] = tables
-            m.wpd[due], m.xci[due] = wpd, xci
-            r.update(dt=float(m.dt_mpc), mu=0.4, f_max=120.0)        # the MPC's model: flat ground
-            soln, nwsr, rc = O.solve_batch(r)
-            rc_bad[due] += (rc != 0)
-            nwsr_max[due] = np.maximum(nwsr_max[due], nwsr)
-            n_solves += len(due)
-            m.f_ff[due] = O.forces_to_body(e["r_body"][due], soln[:, :12].astype(f32))
-        eff = m.legcmd(e, m.f_ff)
-        plant.step(eff, m.contact_state, m.p_des, m.v_des)
-        rec.add(plant.state)
-        if path == "sensed":
-            imu, motor = sens.sense(plant.state, plant.motor)
-    stats = rec.stats()
-    # the model's own accumulators are the Recorder's extremes without the initial state
-    s = plant.stats
-    assert (s["n"] == ticks).all()
-    psi = xyyaw[:, 2]
-    d = plant.p[:, :2] - xyyaw[:, :2]
-    travel = d[:, 0] * np.cos(psi) + d[:, 1] * np.sin(psi)
-    return stats, dict(safe=m.safe.copy(), nwsr_max=nwsr_max, n_solves=n_solves, rc_bad=rc_bad, travel=travel, rows=rows,
-                       support=plant.support.copy(), ground=plant.ground.copy())
+    plant.reset(np.ones(L.N_CMD, bool), xyyaw)
+    stats, info = walk(m, plant, xyyaw, path, TICKS if ticks is None else ticks, settle, seed)
+    return stats, dict(info, rows=rows, support=plant.support.copy(), ground=plant.ground.copy())
+
+

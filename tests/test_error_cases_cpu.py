@@ -87,8 +87,7 @@ def _size_class(b, i):
 
 
 def test_placement():
-    import test_gpu_iteration_cap as CAP
-    sizes = {name: int(record(CAP.FAMILIES[name][0])["batch"]) for name in E.ENGINE_FAMILIES}
+    sizes = {name: int(record(J.FAMILIES[name][0])["batch"]) for name in E.ENGINE_FAMILIES}
     sizes.update({name: int(record(v[0])["batch"]) for name, v in E.MORE_FAMILIES.items()})
     sizes.update({name: E.FUSED_BATCH for name in E.FUSED_FAMILIES})
     assert min(sizes.values()) == 4 and max(sizes.values()) == 48
@@ -137,8 +136,7 @@ def test_command_kinds_reach_the_record(name):
 
 
 def test_family_table_names_every_engine_family():
-    import test_gpu_iteration_cap as CAP
-    assert set(E.ENGINE_FAMILIES) == set(CAP.FAMILIES) and len(E.ENGINE_FAMILIES) == len(CAP.FAMILIES)
+    assert set(E.ENGINE_FAMILIES) == set(J.FAMILIES) and len(E.ENGINE_FAMILIES) == len(J.FAMILIES)
     assert all(v[0] in RECORD_KEYS for v in E.MORE_FAMILIES.values())
     assert not (set(E.ENGINE_FAMILIES) & set(E.MORE_FAMILIES)) and not (set(E.MORE_FAMILIES) & set(E.FUSED_FAMILIES))
     assert E.ST_ERROR_MASK == 47 and E.iters_bound("trot", 10) == 1200 and E.iters_bound("jcqp1_trot", 10) == 10000

@@ -4,7 +4,8 @@ The kernel is compared with tests/act_model.py BIT FOR BIT: the path holds one f
 transcendental function, no contraction -- and the accumulators' sums run in the order the header fixes.  (A NaN is
 compared as a NaN: the device and numpy may sign a fresh one differently.)  The closed-loop fleets are held to the CPU
 loop's recorded walking rungs (tests/golden/act_closed_loop_cpu.json) by plant_loop.envelope(); everything else compares
-two runs of the library bit for bit.
+two runs of the library bit for bit.  The shared helpers and the walk are tests/fleet_gpu.py's, the episode fleets
+tests/episode_gpu.py's.
 """
 import ctypes as C
 import json
@@ -16,15 +17,16 @@ import pytest
 import act_cases as AC
 import act_loop as AL
 import act_model as AM
+import episode_gpu as EG
+import fleet_gpu as G
 import plant_loop as L
-import test_gpu_plant as TP
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = json.load(open(os.path.join(ROOT, "tests", "golden", "act_closed_loop_cpu.json")))
 DT = 1.0 / L.FREQ
-_pair, _dev, _snap = TP._pair, TP._dev, TP._snap
+_pair, _dev, _snap = G.pair, G.dev, G.snap
 STATE_KEYS = ("ring", "head", "age") + AM.ACCUMULATORS
 
 
@@ -303,35 +305,17 @@ def test_the_fleet_walks_on_the_recorded_rung(mode, ladder, rung, sensed):
         keep["delay"] = _dev(c, np.full(B, delay, np.int32))
     a.set_params(**keep)
     plant.enable_stats()
-    start = plant.state.cpu().numpy().copy()
-    if sensed:
+
+    def sensors():
+        nonlocal s
         s = BatchedSensors(plant)
         s.init(1)
         s.settle(50)
-    for t in range(L.TICKS):
-        if sensed:
-            rollout_sensed(c, plant, s, 1, actuators=a)
-        else:
-            rollout(c, plant, 1, actuators=a)
-        if (t + 1) % 13 == 0:
-            assert (c.read("status")[:, 0] & 47 == 0).all(), t
-        if t + 1 == L.TICKS - int(L.FREQ):
-            at150 = _plant_stats(plant)
-    end = _plant_stats(plant)
-    assert (c.read("safe") == 1).all()
-    assert (at150["n"] == 150).all() and (end["n"] == L.TICKS).all()
-    rpy0 = L.rpy_of(start[:, 0:4])
-    stats = dict(z_min=np.minimum(end["z_min"], start[:, 6]), z_max=np.maximum(end["z_max"], start[:, 6]),
-                 roll_max=np.maximum(end["roll_max"], np.abs(rpy0[:, 0])),
-                 pitch_max=np.maximum(end["pitch_max"], np.abs(rpy0[:, 1])),
-                 vx_mean=(end["vx_sum"] - at150["vx_sum"]) / (end["n"] - at150["n"]))
-    env = L.envelope(rec)
-    for k in L.STATS:
-        lo, hi = np.tile(env[k][0], reps), np.tile(env[k][1], reps)
-        want = np.tile(np.asarray(rec[k]), reps)
-        print(f"mode {mode} {rung} {k}: largest distance from the CPU run {np.abs(stats[k] - want).max():.3e}, "
-              f"allowed {float((hi - want).max()):.3e}")
-        assert (stats[k] >= lo).all() and (stats[k] <= hi).all(), (k, stats[k], lo, hi)
+
+    s = None
+    tick = (lambda t: rollout_sensed(c, plant, s, 1, actuators=a)) if sensed else (lambda t: rollout(c, plant, 1, actuators=a))
+    start, at150, end = G.walk(c, plant, tick, L.TICKS, lambda t: (t + 1) % 13 == 0, settle=sensors if sensed else None)
+    G.assert_inside_envelope(G.stats_from_accumulators(start, at150, end), rec, reps, f"mode {mode} {rung}")
     st = _state(a)
     print(f"mode {mode} {rung}: n_vsat {int(st['n_vsat'].sum()) // reps} (CPU {sum(rec['counters']['n_vsat'])}), "
           f"n_tsat {int(st['n_tsat'].sum()) // reps} (CPU {sum(rec['counters']['n_tsat'])}), "
@@ -339,13 +323,6 @@ def test_the_fleet_walks_on_the_recorded_rung(mode, ladder, rung, sensed):
     assert (st["n"] == L.TICKS).all() and (st["e_heat"] > 0).all() and (st["e_pos"] >= st["e_mech"]).all()
     del keep
     c.close()
-
-
-def _plant_stats(plant):
-    import torch
-    torch.cuda.synchronize()
-    st = plant.stats()
-    return {k: st[k].cpu().numpy().copy() for k in ("n", "z_min", "z_max", "roll_max", "pitch_max", "vx_sum", "vy_sum")}
 
 
 # ---- episodes -------------------------------------------------------------------------------------------------------------
@@ -356,10 +333,9 @@ def test_managed_fleet_with_actuators_equals_host_driven_resets():
     rollout_episodes(actuators=..., actuator_stats=True).  Fleet B: rollout(actuators=...) one tick at a time, the host
     decides with the episode model and resets through the same calls with its own mask.  90 ticks, compared every tenth:
     plant, controller, effort, statistics, and the actuators' ring, counters and accumulators -- every bit."""
-    import test_gpu_episode as TE
     from quadruped_ctrl_amd.binding import BatchedActuators, rollout, rollout_episodes
-    B, D = TE.B, 6
-    fa, fb = TE._Fleet("per_robot", "flat"), TE._Fleet("per_robot", "flat")
+    B, D = EG.B, 6
+    fa, fb = EG.Fleet("per_robot", "flat"), EG.Fleet("per_robot", "flat")
     acts = []
     for f in (fa, fb):
         a = BatchedActuators(f.p)
@@ -368,8 +344,8 @@ def test_managed_fleet_with_actuators_equals_host_driven_resets():
         a.set_params(delay=f.delay)
         acts.append(a)
     aa, ab = acts
-    ea = TE._episodes(fa, TE.RULE_ALL, 200)
-    m = TE._model(fb, TE.RULE_ALL, 200)
+    ea = EG.episodes(fa, EG.RULE_ALL, 200)
+    m = EG.model(fb, EG.RULE_ALL, 200)
     masks = []
     for chunk in range(9):
         if chunk == 4:
@@ -378,10 +354,10 @@ def test_managed_fleet_with_actuators_equals_host_driven_resets():
         rollout_episodes(fa.c, fa.p, ea, 10, actuators=aa, actuator_stats=True)
         for _ in range(10):
             rollout(fb.c, fb.p, 1, actuators=ab)
-            mask = TE._host_check(fb, m)
+            mask = EG.host_check(fb, m)
             ab.reset(_dev(fb.c, mask), stats=True)
             masks.append(mask)
-        TE._same(fa, fb, f"tick {10 * (chunk + 1)}", m.vel, m.gait)
+        EG.same(fa, fb, f"tick {10 * (chunk + 1)}", m.vel, m.gait)
         sa, sb = _state(aa), _state(ab)
         for k in STATE_KEYS:
             assert sa[k].tobytes() == sb[k].tobytes(), (chunk, k)
@@ -401,10 +377,9 @@ def test_sensor_path_episodes_reset_the_ring_under_mask_and_hold():
     with the actuators in rollout_sensed_episodes, one tick at a time: after every tick the stage's age and call count are
     what the manager's mask and hold flags of that tick say -- a robot reset or held has age 0 and n 0, every other robot
     one more, saturated at the ring's length -- so a robot leaves its warm-up with an empty ring."""
-    import test_gpu_episode_sense as TES
     from quadruped_ctrl_amd.binding import BatchedActuators, rollout_sensed_episodes
-    B, D = TES.B, 6
-    f = TES._Managed("per_robot", "flat", TES.W3, TES.RULE_ALL, 4000)
+    B, D = EG.B, 6
+    f = EG.Managed("per_robot", "flat", EG.W3, EG.RULE_ALL, 4000)
     a = BatchedActuators(f.p)
     a.init(max_delay=D)
     delay = _dev(f.c, (np.arange(B) % (D + 2)).astype(np.int32))

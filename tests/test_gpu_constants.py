@@ -14,10 +14,10 @@ from oracle import glue as G
 from quadruped_ctrl_amd import workloads as W
 
 import ctrl_model as M
+import fleet_gpu as FG
 import plant_cases as PC
 import test_gpu_controller as TC
 import test_gpu_ctrl_state as TS
-import test_gpu_plant as TP
 from test_gpu_parity import _dump_model_compare, _solver_parity_on_own_qp
 
 pytestmark = pytest.mark.gpu
@@ -182,11 +182,11 @@ def test_kalman_process_noise_does_not_follow_freq():
 def test_plant_single_step_at_the_second_constants(substeps):
     """test_gpu_plant.py::test_single_step_parity's case rebuilt for mass 12.5, inertia (0.11, 0.36, 0.41), the second
     geometry, 400 Hz and mu_plant 0.6."""
-    TP._single_step(substeps, PLANT2)
+    FG.single_step(substeps, PLANT2)
 
 
 def test_plant_closed_loop_at_the_second_constants():
-    TP._closed_loop(64, 20, PLANT2)
+    FG.teacher_forced_closed_loop(64, 20, PLANT2)
 
 
 def test_setters_between_two_plant_steps():
@@ -195,23 +195,23 @@ def test_setters_between_two_plant_steps():
     wdot, the geometry through the IK, J^-T and the joint read-out (robot 256, straight-legged under the default
     lengths, is an ordinary bent leg under the second)."""
     B, m, old, new, tau, cs, pd, vd = PC.parity_case(1)
-    c, plant = TP._pair(B)
-    TP._start(c, plant, m, cs, pd, vd)
-    plant.step(TP._dev(c, tau.reshape(B, 12)))
+    c, plant = FG.pair(B)
+    FG.start(c, plant, m, cs, pd, vd)
+    plant.step(FG.dev(c, tau.reshape(B, 12)))
     m.step(tau.reshape(B, 12), cs, pd, vd)
-    s = TP._snap(plant)
+    s = FG.snap(plant)
     s["foot"], s["grf"] = s["foot"].reshape(B, 4, 3), s["grf"].reshape(B, 4, 3)
-    TP._compare(s, m, "first step, default constants")
+    FG.compare(s, m, "first step, default constants")
     c.mpc.set_robot(MASS2, IBODY2, GRAVITY2)
     c.mpc.set_leg_geometry(*GEOM2)
     body = dict(PC.DEFAULTS, mass=MASS2, ibody=PLANT2["ibody"])
     stale, body_only, m2 = (PC.model(B, k).load(s) for k in (PC.DEFAULTS, body, dict(body, geom=PLANT2["geom"])))
-    plant.step(TP._dev(c, tau.reshape(B, 12)))
+    plant.step(FG.dev(c, tau.reshape(B, 12)))
     for x in (stale, body_only, m2):
         x.step(tau.reshape(B, 12), cs, pd, vd)
-    s = TP._snap(plant)
+    s = FG.snap(plant)
     s["foot"], s["grf"] = s["foot"].reshape(B, 4, 3), s["grf"].reshape(B, 4, 3)
-    TP._compare(s, m2, "second step, second body and geometry")
+    FG.compare(s, m2, "second step, second body and geometry")
     assert np.abs(body_only.v - stale.v).max() > 1e-4 and np.abs(body_only.w - stale.w).max() > 1e-4
     dq = np.abs(m2.motor[:, :12] - body_only.motor[:, :12]).reshape(B, 4, 3).max(2)
     assert dq.min() > 1e-3 and np.abs(m2.grf - body_only.grf).max() > 1.0            # every leg of every robot

@@ -5,7 +5,8 @@ tolerance, 1e-10 relative to max(1, |x|): the terrain step's arithmetic plus a f
 comparison the step branches on kept 1e-6 (relative) away from a tie by the case (about ten orders above its rounding);
 the flags and the counters are compared exactly.  The walk on plant_loop_contact.walk_config() is held to the CPU loops'
 recorded statistics (tests/golden/plant_contact_closed_loop_cpu.json) by plant_loop.envelope() and the same rule for the
-contact counters; everything else compares two runs of the library bit for bit.
+contact counters; everything else compares two runs of the library bit for bit.  The shared helpers (snap4,
+compare_contact, start_contact, masked_reset_is_the_models, ...) and the walk are tests/fleet_gpu.py's.
 """
 import ctypes as C
 import json
@@ -15,55 +16,22 @@ import numpy as np
 import pytest
 
 import contact_cases as CC
+import fleet_gpu as G
 import plant_loop as L
 import plant_loop_contact as LC
 import plant_loop_terrain as LT
 import plant_model_contact as PCM
 import plant_model_varied as PV
-import sense_loop as SL
-import test_gpu_plant as TP
-import test_gpu_terrain as TT
 from plant_cases import DEFAULTS
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
-_pair, _dev, _snap, _close = TP._pair, TP._dev, TP._snap, TP._close
-_snap3, _stats, _all, _walk_pair, _stand_on = TT._snap3, TT._stats, TT._all, TT._walk_pair, TT._stand_on
-CONTACT_KEYS = ("early", "late", "slip", "drop")
-ON = dict(early=True, late=True, slip=True)
-
-
-def _snap4(plant, B):
-    """The plant's views, the terrain's and the contact's, as numpy copies (synchronises)."""
-    s = _snap3(plant, B)
-    v = plant.contact()
-    s.update({k: v[k].cpu().numpy().copy() for k in CONTACT_KEYS})
-    return s
-
-
-def _compare_contact(s, m, what):
-    TT._compare_terrain(s, m, what)                       # every view array, state, motor, ground, support; stance exactly
-    _close(s["drop"], m.drop, f"{what} drop")
-    _close(s["slip"], m.slip, f"{what} slip")
-    assert np.array_equal(s["early"], m.early) and np.array_equal(s["late"], m.late), what
-
-
-def _start_contact(c, plant, m0, cs, pd, vd, rows, tflags, flags, params):
-    """The model's state on the device, the terrain and the contact as the model has them -> what must stay referenced."""
-    B = m0.B
-    TP._start(c, plant, m0, cs, pd, vd)
-    dev = None
-    if rows is not None:
-        dev = _dev(c, rows)
-        plant.set_terrain(dev, clamp_swing=tflags[0], rebase_z=tflags[1])
-    plant.terrain()["support"].copy_(_dev(c, m0.support))
-    plant.set_contact(*flags, **params)
-    v = plant.contact()
-    for k in CONTACT_KEYS:
-        v[k].copy_(_dev(c, getattr(m0, k)))
-    return dev
+_pair, _dev, _snap, _close, _same = G.pair, G.dev, G.snap, G.close, G.same
+_snap4, _stats, _all, _walk_pair, _stand_on = G.snap4, G.plant_stats, G.all_robots, G.walk_pair, G.stand_on
+_compare_contact, _start_contact = G.compare_contact, G.start_contact
+CONTACT_KEYS, ON = G.CONTACT_KEYS, G.ON
 
 
 # ---- 1. single-step parity ---------------------------------------------------------------------------------------------
@@ -161,11 +129,11 @@ def test_flags_zero_change_no_bit(schedule, terrain):
     assert pa.contact()["flags"] == 0
     rollout(ca, pa, 13)
     rollout(cb, pb, 13)
-    TT._same(pa, pb, "after set_contact(None)")
+    _same(pa, pb, "after set_contact(None)")
     pa.set_contact()
     rollout(ca, pa, 26)
     rollout(cb, pb, 26)
-    TT._same(pa, pb, "flags 0")
+    _same(pa, pb, "flags 0")
     sa, sb = _snap4(pa, B), _snap4(pb, B)
     for k in ("ground", "support") + CONTACT_KEYS:
         assert np.array_equal(sa[k], sb[k]), k
@@ -180,71 +148,13 @@ def test_flags_zero_change_no_bit(schedule, terrain):
     cb.close()
 
 
-def _masked_reset_is_the_models(ground):
-    """Contact on, on `ground` = "flat", "terrain" or "field": five robots (20 lanes, a third of one wave: every lane past
-    n is a padding lane) walk 13 closed-loop ticks, every counter, drop, support and ground is then made non-zero, and
-    reset(robots 1 and 3) leaves what tests/plant_model_field.py's reset leaves from the same state: the two robots
-    standing on their ground with their counters and drop at zero (without rows, support and ground too), at the parity's
-    tolerance and the integers exactly; the other three bit for bit as they were."""
-    from quadruped_ctrl_amd.binding import rollout
-    import plant_loop_field as LF
-    import plant_model_field as PF
-    B = 5
-    gait, vel, xyyaw = (a[:B] for a in L.commands(0))
-    c, plant = _pair(B, xyyaw=xyyaw)
-    c.set_gait(_dev(c, gait))
-    c.set_vel(_dev(c, vel))
-    m = PF.FieldPlantModel(B, DEFAULTS["freq"], DEFAULTS["mu"], 1, xyyaw)
-    keep = []
-    if ground == "terrain":
-        rows = LT.terrain(B)
-        keep.append(_dev(c, rows))
-        plant.set_terrain(keep[-1], clamp_swing=True, rebase_z=True)
-        m.set_terrain(rows, clamp_swing=True, rebase_z=True)
-    if ground == "field":
-        z, place, cell = LF.field_for(B, 0.06)
-        keep += [_dev(c, z), _dev(c, place)]
-        plant.set_field(keep[-2], keep[-1], cell, clamp_swing=True, rebase_z=True)
-        m.set_field(z, place, cell, clamp_swing=True, rebase_z=True)
-    plant.set_contact(**ON)
-    m.set_contact(**ON)
-    plant.reset(_all(c, B), _dev(c, xyyaw))
-    rollout(c, plant, 13)
-    v, t = plant.contact(), plant.terrain()
-    print(ground, "after 13 ticks:", {k: float(np.abs(a).max()) for k, a in _snap4(plant, B).items() if k in CONTACT_KEYS + ("support", "ground")})
-    for k in CONTACT_KEYS:
-        v[k].add_(1)
-    for k in ("support", "ground"):
-        t[k].add_(0.125)
-    before = _snap4(plant, B)
-    assert all(before[k].all() for k in CONTACT_KEYS + ("support", "ground"))
-    m.load(before)
-    for k in ("grf", "state", "motor", "ground", "support") + CONTACT_KEYS:
-        setattr(m, k, before[k].copy())
-    mask = np.zeros(B, bool)
-    mask[[1, 3]] = True
-    plant.reset(_dev(c, mask), _dev(c, xyyaw))
-    m.reset(mask, xyyaw)
-    after = _snap4(plant, B)
-    _compare_contact(after, m, f"masked reset on {ground}")
-    for k in CONTACT_KEYS + (("support", "ground") if ground == "flat" else ()):
-        assert not after[k][mask].any(), (ground, k)
-    if ground != "flat":
-        assert np.array_equal(after["p"][mask][:, 2], 0.29 + after["ground"][mask])
-    for k in before:
-        assert np.array_equal(after[k][~mask], before[k][~mask]), (ground, k)
-    assert (after["stance"][mask] == 1).all() and plant.contact()["flags"] == 7
-    del keep
-    c.close()
-
-
 def test_init_switches_contact_off_and_reset_keeps_it():
     """reset(mask) keeps contact on and zeroes the masked robots' counters and drop only; init() switches it off, zeroes
     the counters, and the plant is the plain plant again, bit for bit.  The masked reset is the model's on flat ground
-    and on terrain (_masked_reset_is_the_models; tests/test_gpu_field.py runs it on the field)."""
+    and on terrain (fleet_gpu.masked_reset_is_the_models; tests/test_gpu_field.py runs it on the field)."""
     from quadruped_ctrl_amd.binding import rollout
     for ground in ("flat", "terrain"):
-        _masked_reset_is_the_models(ground)
+        G.masked_reset_is_the_models(ground)
     B = 64
     ca, pa, (gait, vel, xyyaw) = _walk_pair(B)
     cb, pb, _ = _walk_pair(B)
@@ -277,7 +187,7 @@ def test_init_switches_contact_off_and_reset_keeps_it():
     assert pa.contact()["flags"] == 0 and not any(z[k].any() for k in CONTACT_KEYS)
     rollout(ca, pa, 14)
     rollout(cb, pb, 14)
-    TT._same(pa, pb, "after init")
+    _same(pa, pb, "after init")
     assert not any(_snap4(pa, B)[k].any() for k in CONTACT_KEYS)
     del rows
     ca.close()
@@ -362,7 +272,6 @@ def test_the_fleet_walks_with_contact_decided_by_the_ground(mode, path):
     under all three flags on the top walked floor.  Every robot stays safe, no solve reports an error bit, the five
     statistics lie inside plant_loop.envelope() of the CPU run, and so do the counters by the same rule -- a command's own
     recorded value widened by twice its spread across the 16 commands.  Feet were early, late and slid somewhere."""
-    from quadruped_ctrl_amd.binding import BatchedSensors, rollout, rollout_sensed
     reps = 4
     B = L.N_CMD * reps
     gold = json.load(open(os.path.join(ROOT, "tests", "golden", "plant_contact_closed_loop_cpu.json")))
@@ -379,37 +288,8 @@ def test_the_fleet_walks_with_contact_decided_by_the_ground(mode, path):
     plant.reset(_all(c, B), _dev(c, xyyaw))
     plant.enable_stats()
     plant.reset_stats()
-    start = plant.state.cpu().numpy().copy()
-    if path == "sensed":
-        s = BatchedSensors(plant)
-        s.init(gold["seed"])
-        keep = {k: _dev(c, v) for k, v in SL.noise(B).items()}
-        s.set_params(**keep)
-        s.settle(gold["settle"])
-    for t in range(ticks):
-        if path == "sensed":
-            rollout_sensed(c, plant, s, 1)
-        else:
-            rollout(c, plant, 1)
-        if mode == 1 or (t + 1) % 13 == 0:
-            assert (c.read("status")[:, 0] & 47 == 0).all(), t
-        if t + 1 == ticks - int(L.FREQ):
-            mid = _stats(plant)
-    end = _stats(plant)
-    assert (c.read("safe") == 1).all()
-    assert (mid["n"] == ticks - int(L.FREQ)).all() and (end["n"] == ticks).all()
-    rpy0 = L.rpy_of(start[:, 0:4])
-    stats = dict(z_min=np.minimum(end["z_min"], start[:, 6]), z_max=np.maximum(end["z_max"], start[:, 6]),
-                 roll_max=np.maximum(end["roll_max"], np.abs(rpy0[:, 0])),
-                 pitch_max=np.maximum(end["pitch_max"], np.abs(rpy0[:, 1])),
-                 vx_mean=(end["vx_sum"] - mid["vx_sum"]) / (end["n"] - mid["n"]))
-    env = L.envelope(rec)
-    for k in L.STATS:
-        lo, hi = np.tile(env[k][0], reps), np.tile(env[k][1], reps)
-        want = np.tile(np.asarray(rec[k]), reps)
-        print(f"mode {mode} {path} {k}: largest distance from the CPU run {np.abs(stats[k] - want).max():.3e}, "
-              f"allowed {float((hi - want).max()):.3e}")
-        assert (stats[k] >= lo).all() and (stats[k] <= hi).all(), (k, stats[k], lo, hi)
+    start, mid, end = G.ground_walk(c, plant, path, mode, ticks, gold["seed"], gold["settle"])
+    G.assert_inside_envelope(G.stats_from_accumulators(start, mid, end), rec, reps, f"mode {mode} {path}")
     got = _snap4(plant, B)
     for k in ("early", "late", "slip"):
         v = np.asarray(rec[k], np.float64)

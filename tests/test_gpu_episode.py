@@ -7,7 +7,10 @@ no tolerance: the decision is comparisons and single fp64 operations, the draw i
 
 B = 96: one full wave and one half wave, so the log's append crosses waves and meets a partial one.
 
-The workload (one definition, _Fleet.push): after a quiet first episode that every robot ends by timing out on the same
+The fleets, the manager's model and the host-driven counterpart are tests/episode_gpu.py's (tests/test_gpu_episode_sense.py
+and tests/test_gpu_act.py run them too).
+
+The workload (one definition, episode_gpu.Fleet.push): after a quiet first episode that every robot ends by timing out on the same
 tick, the plant -- not the controller -- is pushed per robot class k = b mod 16 mod 4:
   0  a roll torque of 0.15 Ixx / dt^2: the roll passes 0.45, 0.9 rad on consecutive ticks, TILT (cos 0.8) fires first
   1  1500 N downwards: the body sinks below z_min = 0.2 m in about twenty ticks (HEIGHT)
@@ -22,181 +25,18 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import episode_gpu as EG
 import episode_model as EM
+import fleet_gpu as G
 import plant_loop as L
-import plant_loop_field as LF
-import plant_loop_varied as LV
-import test_gpu_contact as TCN
-import test_gpu_plant as TP
-import test_gpu_terrain as TT
 
 pytestmark = pytest.mark.gpu
 
-B = 96
-SEED = 0x5EED0123456789AB
-DT = 1.0 / L.FREQ
-RULE_ALL = dict(causes=EM.ALL, max_ticks=40, cos_tilt_min=0.8, z_min=0.2, range=0.06)
+B, SEED, DT, RULE_ALL, COMMANDS = EG.B, EG.SEED, EG.DT, EG.RULE_ALL, EG.COMMANDS
 RULE_LATCH = dict(causes=EM.UNSAFE | EM.TIMEOUT, max_ticks=40, cos_tilt_min=0.8, z_min=0.2, range=0.06)
-COMMANDS = np.array([[0.3, 0.0, 0.05, 0], [0.0, 0.0, 0.0, 4], [0.5, 0.0, -0.1, 5], [0.2, 0.0, 0.0, 10], [0.02, 0.0, 0.0, 0]])
-_dev, _all = TP._dev, TT._all
-CTRL_KEYS = None  # (binding.CTRL_VIEW_WIDTH's keys, read on first use)
-
-
-def _np(t):
-    return t.cpu().numpy().copy()
-
-
-def _bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def _rows_equal(a, b):
-    """log rows: exact doubles, a NaN equal to a NaN (the device and numpy may sign a fresh NaN differently)."""
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return a.shape == b.shape and np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(a[~np.isnan(a)], b[~np.isnan(b)])
-
-
-def _key(rows):
-    return {(int(r[0]), int(r[1])): r for r in rows}
-
-
-class _Fleet:
-    """A controller and a plant for B robots on `ground` ("flat", or "field": plant_loop_field's map at the contact
-    rung with all three contact flags), per-robot payloads and floors, statistics on, the commands as device tensors."""
-
-    def __init__(self, schedule, ground):
-        import torch
-        self.torch = torch
-        self.c, self.p, (gait, vel, xyyaw) = TT._walk_pair(B, schedule)
-        self.xyyaw0 = xyyaw
-        self.ground = ground
-        self.keep = []
-        if ground == "field":
-            z, place, cell = LF.field_for(B, LF.RUNGS["contact"])
-            self.keep += [_dev(self.c, z), _dev(self.c, place)]
-            self.p.set_field(self.keep[0], self.keep[1], cell, clamp_swing=True, rebase_z=True)
-            self.p.set_contact(**TCN.ON)
-            self.p.reset(_all(self.c, B), _dev(self.c, xyyaw))
-        var = LV.variation(B)
-        self.ibody = var["ibody"]
-        self.prm = dict(mass=_dev(self.c, var["mass"]), ibody=_dev(self.c, var["ibody"]), mu=_dev(self.c, var["mu"]),
-                        force=_dev(self.c, np.zeros((B, 3))), torque=_dev(self.c, np.zeros((B, 3))))
-        self.p.set_params(**self.prm)
-        self.p.enable_stats()
-        self.p.reset_stats()
-        self.vel, self.gait = _dev(self.c, vel), _dev(self.c, gait)
-
-    def spawn(self):
-        """[B, 3, 3] per robot on the field (each robot stays on its own part of the map), [7, 3] shared on flat ground."""
-        if self.ground == "field":
-            off = np.array([[0.0, 0.0, 0.0], [0.3, 0.1, 0.2], [-0.2, 0.25, -0.3]])
-            return self.xyyaw0[:, None, :] + off[None, :, :]
-        k = np.arange(7.0)
-        return np.stack([0.4 * k - 1.0, 0.3 * (k % 3), 0.1 * (k - 3)], 1)
-
-    def push(self):
-        """The pushes of the module docstring, written in place into the bound tensors."""
-        k = np.arange(B) % 16 % 4
-        force, torque = np.zeros((B, 3)), np.zeros((B, 3))
-        torque[k == 0, 0] = 0.15 * self.ibody[k == 0, 0] / DT ** 2
-        force[k == 1, 2] = -1500.0
-        force[k == 2, 0] = 400.0
-        slow = np.arange(B) % 32 == 16
-        torque[slow, 0] = 0.006 * self.ibody[slow, 0] / DT ** 2
-        mass = _np(self.prm["mass"])
-        mass[5] = np.nan
-        for name, val in (("force", force), ("torque", torque), ("mass", mass)):
-            self.prm[name].copy_(_dev(self.c, val))
-
-    def ground_rows(self):
-        return _np(self.p.terrain()["ground"]) if self.ground == "field" else np.zeros(B)
-
-    def snapshot(self):
-        """Every array the issue names, as numpy copies (synchronises)."""
-        global CTRL_KEYS
-        from quadruped_ctrl_amd import binding
-        CTRL_KEYS = tuple(binding.CTRL_VIEW_WIDTH)
-        self.torch.cuda.synchronize()
-        s = {f"plant.{k}": _np(v) for k, v in self.p.view().items() if k in TP.PLANT_KEYS}
-        s.update({f"ctrl.{k}": _np(v) for k, v in self.c.view().items() if k in CTRL_KEYS})
-        s["effort"] = _np(self.p.effort)
-        s.update({f"contact.{k}": _np(self.p.contact()[k]) for k in TCN.CONTACT_KEYS})
-        t = self.p.terrain()
-        s["ground"], s["support"] = _np(t["ground"]), _np(t["support"])
-        st = self.p.stats()
-        s.update({f"stats.{k}": _np(st[k]) for k in ("n", "z_min", "z_max", "roll_max", "pitch_max", "vx_sum", "vy_sum")})
-        return s
-
-    def close(self):
-        self.c.close()
-
-
-def _same(fa, fb, what, vel_b=None, gait_b=None):
-    sa, sb = fa.snapshot(), fb.snapshot()
-    assert set(sa) == set(sb) and "ctrl.safe" in sa and "ctrl.counter" in sa and "plant.stance" in sa
-    for k in sa:
-        assert _bits(sa[k], sb[k]), (what, k, np.flatnonzero((sa[k] != sb[k]).reshape(B, -1).any(1))[:8])
-    if vel_b is not None:
-        assert _bits(_np(fa.vel), vel_b) and _bits(_np(fa.gait), gait_b), (what, "commands")
-    return sa
-
-
-def _episodes(f, rule, log_rows, commands=True):
-    from quadruped_ctrl_amd.binding import BatchedEpisodes
-    e = BatchedEpisodes(f.p)
-    e.init(SEED)
-    f.cmd = _dev(f.c, COMMANDS) if commands else None
-    f.spawn_t = _dev(f.c, f.spawn())
-    e.set(f.vel, f.gait, f.spawn_t, f.cmd, log_rows=log_rows, **rule)
-    return e
-
-
-def _model(f, rule, log_rows, commands=True):
-    f.torch.cuda.synchronize()
-    m = EM.EpisodeModel(B, SEED, _np(f.p.view()["p"]))
-    m.set(_np(f.vel), _np(f.gait), f.spawn(), COMMANDS if commands else None, log_rows=log_rows, **rule)
-    return m
-
-
-def _host_check(f, m, elapsed=1):
-    """What qmpc_episode_step does, by the host: the views to the host, the model decides and draws, and the calls
-    that existed before reset -> the mask."""
-    f.torch.cuda.synchronize()
-    v = f.p.view()
-    mask, xyyaw = m.step(_np(v["p"]), _np(v["q"]), _np(f.c.view()["safe"])[:, 0], f.ground_rows(), elapsed)
-    mt = _dev(f.c, mask)
-    f.gait.copy_(_dev(f.c, m.gait))
-    f.vel.copy_(_dev(f.c, m.vel))
-    f.c.reset(mt)
-    f.c.set_gait(f.gait)
-    f.c.set_vel(f.vel)
-    f.p.reset(mt, _dev(f.c, xyyaw))
-    f.p.reset_stats(mt)
-    return mask.copy()
-
-
-def _check_manager(e, m, what):
-    """The manager's state is the model's; the log holds every row that must be there, only rows that may, and the two
-    words add up."""
-    e.torch.cuda.synchronize()
-    v = e.view()
-    for k in ("age", "episode", "count", "ticks_sum", "last_cause", "last_ticks"):
-        assert np.array_equal(_np(v[k]).reshape(getattr(m, k).shape), getattr(m, k)), (what, k)
-    assert _bits(_np(v["start"]), m.start) and _bits(_np(v["xyyaw"]), m.xyyaw), what
-    assert np.array_equal(_np(v["mask"]) != 0, m.mask), what
-    lg = e.log()
-    n = int(_np(v["log_count"])[0])
-    assert n == len(lg["rows"]) == m.log_count and lg["dropped"] == m.dropped == int(_np(v["log_dropped"])[0]), \
-        (what, n, lg["dropped"], m.log_count, m.dropped)
-    assert n + lg["dropped"] == m.total
-    got, may, must = _key(lg["rows"]), _key(m.all_rows()), _key(m.certain_rows())
-    assert len(got) == n and set(must) <= set(got) <= set(may), what
-    for k, r in got.items():
-        assert _rows_equal(r, may[k]), (what, k, r, may[k])
-    if not m.dropped:
-        assert _rows_equal(lg["rows"], m.all_rows()), what
-    return lg
+_dev, _all, _np, _bits, _rows_equal = G.dev, G.all_robots, EG.to_np, EG.bits, EG.rows_equal
+_Fleet, _same, _episodes, _model, _host_check, _check_manager = (EG.Fleet, EG.same, EG.episodes, EG.model, EG.host_check,
+                                                                 EG.check_manager)
 
 
 # ---- 1. the device manager equals host-driven resets ---------------------------------------------------------------------

@@ -5,7 +5,9 @@ Everything but the last test compares two runs of the library BIT FOR BIT (np.ar
 holds against a robot that is settled by the calls that existed before (sensors.sense -> ctrl.prework on a fresh
 controller), a fleet the device manages against a fleet the host drives with tests/episode_sense_model.py deciding, a
 captured block against eager ticks.  There is no tolerance.  The last test is the envelope test of
-tests/test_gpu_sense.py for the SECOND episode of a fleet that the manager has reset and warmed up.
+tests/test_gpu_sense.py for the SECOND episode of a fleet that the manager has reset and warmed up; it keeps its own
+run() phases and takes the statistics and the envelope assertion from tests/fleet_gpu.py.  The managed fleet (Managed) and
+the manager's checks are tests/episode_gpu.py's.
 
 B = 96: one full wave and one half wave, so held, newly held and walking robots meet in one wave and the log's append
 crosses waves.
@@ -17,40 +19,26 @@ counterpart is therefore  W x (sense -> prework), sense, ticks.
 import ctypes as C
 import json
 import os
-import re
 
 import numpy as np
 import pytest
 
+import episode_gpu as EG
 import episode_model as EM
 import episode_sense_model as ESM
+import fleet_gpu as G
 import plant_loop as L
 import sense_loop as SL
-import test_gpu_episode as TE
-import test_gpu_plant as TP
-import test_gpu_sense as TS
-import test_gpu_terrain as TT
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-B = 96
-SEED_E = 0x5EED0123456789AB          # the draws'
-SEED_N = 0x9E3779B97F4A7C15          # the noise's
-_dev, _all, _np, _bits = TP._dev, TT._all, TE._np, TE._bits
+B, SEED_E, SEED_N, CTRL = EG.B, EG.SEED, EG.SEED_N, EG.CTRL     # (the draws' seed, the noise's, the controller's arrays)
+_dev, _all, _np, _bits, _snap, _stats = G.dev, G.all_robots, EG.to_np, EG.bits, G.snap, G.plant_stats
 KEPT = ("q", "qd", "leg_J", "leg_p", "leg_v", "kf_p", "kf_v", "orientation", "rpy", "r_body", "omega_body", "omega_world",
         "a_world", "ori_ini_inv", "xhat", "P", "position", "v_world", "v_body", "first_visit")
 SCRATCH = ("due_list", "due_count")   # a tick's dense list of due robots and its length: not a robot's own state
 LIST = ("due_list",)                  # ... and the list's order across waves is the atomics': two runs may differ in it
-
-
-def _ctrl_arrays():
-    src = open(os.path.join(ROOT, "quadruped_ctrl_amd", "csrc", "qmpc_glue.h")).read()
-    body = re.search(r"#define QMPC_CTRL_ARRAYS\(X\)((?:.*\\\n)*.*)", src).group(1)
-    return [n for _, n, _ in re.findall(r"X\((\w+), (\w+), (\d+)\)", body)]
-
-
-CTRL = _ctrl_arrays()
 assert set(KEPT) < set(CTRL) and set(SCRATCH) < set(CTRL)
 
 
@@ -60,10 +48,10 @@ class _Fleet:
     def __init__(self, schedule, mode=0, noisy=True, n=B, seed=SEED_N, noise=None):
         import torch
         self.torch, self.n = torch, n
-        self.c, self.p, self.s, (gait, vel, xyyaw) = TS._trio(n, schedule, 1 if mode == 1 else None, seed=seed)
+        self.c, self.p, self.s, (gait, vel, xyyaw) = G.trio(n, schedule, 1 if mode == 1 else None, seed=seed)
         self.gait_np, self.vel_np, self.xyyaw = gait, vel, xyyaw
         self.gait, self.vel = _dev(self.c, gait), _dev(self.c, vel)
-        self.keep = TS._bind(self.c, self.s, TS._values(n, 11) if noise is None else noise) if noisy else None
+        self.keep = G.sense_bind(self.c, self.s, G.sense_values(n, 11) if noise is None else noise) if noisy else None
         self.e = self.se = None
 
     def manage(self, W, spawn=None, commands=None, log_rows=0, **rule):
@@ -99,7 +87,7 @@ class _Fleet:
     def snapshot(self):
         self.torch.cuda.synchronize()
         d = {f"ctrl.{k}": self.c.read(k) for k in CTRL}
-        d.update({f"plant.{k}": v for k, v in TP._snap(self.p).items()})
+        d.update({f"plant.{k}": v for k, v in _snap(self.p).items()})
         d.update(effort=_np(self.p.effort), imu=_np(self.s.imu), motor=_np(self.s.motor))
         v = self.s.view()
         d["sense.n"], d["sense.epoch"] = _np(v["n"]), _np(v["epoch"])
@@ -276,12 +264,12 @@ def test_hold_keeps_a_placed_robot_on_its_pose_over_the_whole_circle_of_yaw():
             keep = [_dev(f.c, z), _dev(f.c, place)]
             f.p.set_field(keep[0], keep[1], cell, clamp_swing=True)
         f.p.reset(_all(f.c, n), _dev(f.c, rows))
-        before = TP._snap(f.p)
+        before = _snap(f.p)
         se = f.manage(2, causes=0)
         f.s.sense()
         se.hold()
         f.tick()
-        after = TP._snap(f.p)
+        after = _snap(f.p)
         got = _np(f.e.view()["xyyaw"])
         assert _bits(got[:, :2], rows[:, :2]) and np.abs(got[:, 2] - yaw).max() < 1e-15
         assert (_np(se.view()["hold"]) == 1).all()
@@ -292,40 +280,7 @@ def test_hold_keeps_a_placed_robot_on_its_pose_over_the_whole_circle_of_yaw():
 
 # ---- 3. the device manager equals host-driven resets and holds ----------------------------------------------------------
 
-RULE_ALL = TE.RULE_ALL              # all six causes: time-out at 40 ticks, tilt cosine 0.8, 0.2 m, 0.06 m from the start
-COMMANDS = np.array([[0.1, 0.0, 0.05, 0], [0.25, 0.0, 0.0, 5], [0.4, 0.0, -0.1, 0], [0.5, 0.0, 0.0, 10]])
-W3 = 5
-
-
-class _Managed:
-    """test_gpu_episode's fleet (flat, or the field with all three contact flags; per-robot payloads, statistics on)
-    with sensors and the sensor-path manager."""
-
-    def __init__(self, schedule, ground, W, rule, log_rows):
-        from quadruped_ctrl_amd.binding import BatchedSensors, SensedEpisodes
-        self.f = TE._Fleet(schedule, ground)
-        self.c, self.p, self.torch = self.f.c, self.f.p, self.f.torch
-        self.s = BatchedSensors(self.p)
-        self.s.init(SEED_N)
-        self.keep = TS._bind(self.c, self.s, TS._values(B, 11))
-        self.f.cmd = _dev(self.c, COMMANDS)
-        self.f.spawn_t = _dev(self.c, self.f.spawn())
-        from quadruped_ctrl_amd.binding import BatchedEpisodes
-        self.e = BatchedEpisodes(self.p)
-        self.e.init(SEED_E)
-        self.e.set(self.f.vel, self.f.gait, self.f.spawn_t, self.f.cmd, log_rows=log_rows, **rule)
-        self.se = SensedEpisodes(self.e, self.s)
-        self.se.init(W)
-
-    def snapshot(self):
-        s = self.f.snapshot()
-        s.update({f"read.{k}": self.c.read(k) for k in CTRL})
-        s.update(imu=_np(self.s.imu), motor=_np(self.s.motor))
-        v = self.s.view()
-        s["sense.n"], s["sense.epoch"] = _np(v["n"]), _np(v["epoch"])
-        w = self.se.view()
-        s["warm"], s["hold"] = _np(w["warm"]), _np(w["hold"])
-        return s
+RULE_ALL, COMMANDS, W3, _Managed = EG.RULE_ALL, EG.SENSE_COMMANDS, EG.W3, EG.Managed
 
 
 @pytest.mark.parametrize("ground", ["flat", "field"])
@@ -389,7 +344,7 @@ def test_device_manager_equals_host_driven_resets_and_holds(ground):
                 assert _bits(sa[k], sb[k]), (what, k, np.flatnonzero((sa[k] != sb[k]).reshape(B, -1).any(1))[:8])
         assert _bits(_np(a.f.vel), m.vel) and _bits(_np(a.f.gait), m.gait), what
         assert np.array_equal(sa["warm"], m.warm) and np.array_equal(sa["hold"] != 0, m.hold), what
-        TE._check_manager(a.e, m, what)
+        EG.check_manager(a.e, m, what)
     masks, holds = np.array(masks), np.array(holds)
     walking = ~masks & ~holds
     print("resets per tick", masks.sum(1).tolist(), "held per tick", holds.sum(1).tolist(), "per cause",
@@ -431,7 +386,7 @@ def test_w0_is_the_plain_manager_and_the_sensors_reset():
     va, vb = fa.e.view(), fb.e.view()
     for k in ("age", "episode", "start", "count", "ticks_sum", "last_cause", "last_ticks", "mask", "xyyaw", "log_count"):
         assert _bits(_np(va[k]), _np(vb[k])), k
-    assert TE._rows_equal(fa.e.log()["rows"], fb.e.log()["rows"]) and len(fa.e.log()["rows"]) > B
+    assert EG.rows_equal(fa.e.log()["rows"], fb.e.log()["rows"]) and len(fa.e.log()["rows"]) > B
     assert not _np(se.view()["warm"]).any() and not _np(se.view()["hold"]).any()
     assert (_np(fa.s.view()["epoch"]) == _np(va["episode"])).all() and _np(va["episode"]).max() > 1
     fa.close()
@@ -493,7 +448,7 @@ def test_graph_replays_equal_eager_ticks(schedule):
     _same(fa, fb, "130 ticks")
     assert _bits(_np(fa.vel), _np(fb.vel)) and _bits(_np(fa.gait), _np(fb.gait))
     la, lb = fa.e.log(), fb.e.log()
-    assert la["dropped"] == lb["dropped"] == 0 and len(la["rows"]) > B and TE._rows_equal(la["rows"], lb["rows"])
+    assert la["dropped"] == lb["dropped"] == 0 and len(la["rows"]) > B and EG.rows_equal(la["rows"], lb["rows"])
     va, vb = fa.e.view(), fb.e.view()
     for k in ("age", "episode", "start", "count", "ticks_sum", "last_cause", "last_ticks", "mask", "xyyaw", "log_count"):
         assert _bits(_np(va[k]), _np(vb[k])), k
@@ -628,31 +583,20 @@ def test_the_fleet_gets_up_and_walks_on_noisy_sensors(mode):
     f.torch.cuda.synchronize()
     assert not _np(se.view()["warm"]).any() and (_np(f.e.view()["age"]) == 0).all() and (_np(f.s.view()["n"]) == W + 1).all()
     run(99)
-    assert (f.c.read("safe") == 1).all() and (_np(f.e.view()["age"]) == 99).all() and (TS._stats(f.p)["n"] == 99).all()
+    assert (f.c.read("safe") == 1).all() and (_np(f.e.view()["age"]) == 99).all() and (_stats(f.p)["n"] == 99).all()
     run(1, judged=False)                                         # tick 100: everybody times out
     ev = f.e.view()
     f.torch.cuda.synchronize()
     assert (_np(ev["episode"]) == 1).all() and (_np(ev["last_cause"]) == EM.TIMEOUT).all() and (_np(se.view()["warm"]) == W).all()
-    assert (_np(f.s.view()["epoch"]) == 1).all() and (TS._stats(f.p)["n"] == 0).all()
+    assert (_np(f.s.view()["epoch"]) == 1).all() and (_stats(f.p)["n"] == 0).all()
     f.e.set(f.vel, f.gait, f.spawn_t, None, log_rows=2 * n, causes=EM.UNSAFE)     # the second episode has no time limit
     run(W, judged=False)
-    assert (TS._stats(f.p)["n"] == 0).all() and _bits(_np(f.p.state), start)
+    assert (_stats(f.p)["n"] == 0).all() and _bits(_np(f.p.state), start)
     run(L.TICKS - int(L.FREQ))
-    at150 = TS._stats(f.p)
+    at150 = _stats(f.p)
     run(int(L.FREQ))
-    end = TS._stats(f.p)
+    end = _stats(f.p)
     assert (f.c.read("safe") == 1).all() and (_np(ev["episode"]) == 1).all() and len(f.e.log()["rows"]) == n
     assert (at150["n"] == 150).all() and (end["n"] == L.TICKS).all() and (_np(f.s.view()["n"]) == W + 1 + L.TICKS).all()
-    rpy0 = L.rpy_of(start[:, 0:4])
-    stats = dict(z_min=np.minimum(end["z_min"], start[:, 6]), z_max=np.maximum(end["z_max"], start[:, 6]),
-                 roll_max=np.maximum(end["roll_max"], np.abs(rpy0[:, 0])),
-                 pitch_max=np.maximum(end["pitch_max"], np.abs(rpy0[:, 1])),
-                 vx_mean=(end["vx_sum"] - at150["vx_sum"]) / (end["n"] - at150["n"]))
-    env = L.envelope(rec)
-    for k in L.STATS:
-        lo, hi = np.tile(env[k][0], reps), np.tile(env[k][1], reps)
-        want = np.tile(np.asarray(rec[k]), reps)
-        print(f"mode {mode} {k}: largest distance from the CPU run {np.abs(stats[k] - want).max():.3e}, "
-              f"allowed {float((hi - want).max()):.3e}")
-        assert (stats[k] >= lo).all() and (stats[k] <= hi).all(), (k, stats[k], lo, hi)
+    G.assert_inside_envelope(G.stats_from_accumulators(start, at150, end), rec, reps, f"mode {mode}")
     f.close()

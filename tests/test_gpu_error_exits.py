@@ -38,7 +38,6 @@ import pytest
 
 import cap_judge as J
 import error_cases as E
-import test_gpu_iteration_cap as CAP
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -72,8 +71,8 @@ class Family:
             self.kind_names = list(E.COMMAND_KINDS)
             self.setup_of = {"batch": E.FUSED_BATCH, "horizon": E.FUSED_FAMILIES[name], "dt": 0.026, "mu": 0.4, "f_max": 120.0}
         else:
-            if name in CAP.FAMILIES:
-                rec, self.split, self.events, _ = CAP.FAMILIES[name]
+            if name in J.FAMILIES:
+                rec, self.split, self.events, _ = J.FAMILIES[name]
             else:
                 rec, opts = E.MORE_FAMILIES[name]
             self.b = b = E.record_of(rec)

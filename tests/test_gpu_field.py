@@ -5,7 +5,7 @@ The kernels of csrc/qmpc_field.hip are compared with tests/plant_model_field.py 
 floor() argument kept 1e-6 cells away from an integer and every comparison 1e-6 (relative) away from a tie by the case
 (tests/field_cases.py); flags and counters are compared exactly.  The walks at plant_loop_field.RUNGS are held to the CPU
 loops' recorded statistics (tests/golden/plant_field_closed_loop_cpu.json) by plant_loop.envelope(); everything else
-compares two runs of the library bit for bit.
+compares two runs of the library bit for bit.  The shared helpers and the walk are tests/fleet_gpu.py's.
 """
 import ctypes as C
 import json
@@ -15,31 +15,27 @@ import numpy as np
 import pytest
 
 import field_cases as FC
+import fleet_gpu as G
 import plant_loop as L
 import plant_loop_field as LF
 import plant_loop_terrain as LT
 import plant_model_varied as PV
-import sense_loop as SL
-import test_gpu_contact as TCN
-import test_gpu_plant as TP
-import test_gpu_terrain as TT
 from plant_cases import DEFAULTS
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
-_pair, _dev, _snap, _close = TP._pair, TP._dev, TP._snap, TP._close
-_stats, _all, _walk_pair = TT._stats, TT._all, TT._walk_pair
-_snap4, CONTACT_KEYS = TCN._snap4, TCN.CONTACT_KEYS
-ON = dict(early=True, late=True, slip=True)
+_pair, _dev, _snap, _close, _same = G.pair, G.dev, G.snap, G.close, G.same
+_stats, _all, _walk_pair = G.plant_stats, G.all_robots, G.walk_pair
+_snap4, CONTACT_KEYS, ON = G.snap4, G.CONTACT_KEYS, G.ON
 
 
 def _start_field(c, plant, case, contact):
     """The case's state on the device; terrain, field and contact bound as field_cases.model binds them -> what must
     stay referenced."""
     m0, rows, z, place, cell, old, new, tau, cs, pd, vd = case
-    TP._start(c, plant, m0, cs, pd, vd)
+    G.start(c, plant, m0, cs, pd, vd)
     keep = [_dev(c, z), _dev(c, place)]
     if rows is not None:
         keep.append(_dev(c, rows))
@@ -83,11 +79,7 @@ def _run_case(case, substeps, vary, stats, contact, dyadic=False, z=None):
 
 
 def _compare_field(s, m, what, contact):
-    TT._compare_terrain(s, m, what)                       # every view array, grf, foot, state, motor, ground, support; stance exactly
-    if contact:
-        _close(s["drop"], m.drop, f"{what} drop")
-        _close(s["slip"], m.slip, f"{what} slip")
-        assert np.array_equal(s["early"], m.early) and np.array_equal(s["late"], m.late), what
+    (G.compare_contact if contact else G.compare_terrain)(s, m, what)
 
 
 # ---- 1. single-step parity ---------------------------------------------------------------------------------------------
@@ -166,7 +158,7 @@ def test_zero_bank_changes_no_bit(schedule, ground):
     assert pa.field()["bound"] and not pb.field()["bound"]
 
     def same(what):
-        TT._same(pa, pb, what)
+        _same(pa, pb, what)
         sa, sb = _snap4(pa, B), _snap4(pb, B)
         for k in ("grf", "ground", "support") + CONTACT_KEYS:
             assert np.array_equal(sa[k], sb[k]), (what, k)
@@ -287,7 +279,6 @@ def test_the_fleet_walks_on_the_field(kind, mode, path):
     """The CPU yardstick's commands, two robots per command, spread over one random_blocks map at
     plant_loop_field.RUNGS[kind] (amplitude 0 where no rung was walked): every robot stays safe, no solve reports an error
     bit, and the five statistics lie inside plant_loop.envelope() of the CPU run."""
-    from quadruped_ctrl_amd.binding import BatchedSensors, rollout, rollout_sensed
     reps = 2
     B = L.N_CMD * reps
     gold = json.load(open(os.path.join(ROOT, "tests", "golden", "plant_field_closed_loop_cpu.json")))
@@ -300,37 +291,8 @@ def test_the_fleet_walks_on_the_field(kind, mode, path):
     assert np.array_equal(np.asarray(gold["place"]), keep[1].cpu().numpy()[:L.N_CMD])
     plant.enable_stats()
     plant.reset_stats()
-    start = plant.state.cpu().numpy().copy()
-    if path == "sensed":
-        s = BatchedSensors(plant)
-        s.init(gold["seed"])
-        noise = {k: _dev(c, v) for k, v in SL.noise(B).items()}
-        s.set_params(**noise)
-        s.settle(gold["settle"])
-    for t in range(ticks):
-        if path == "sensed":
-            rollout_sensed(c, plant, s, 1)
-        else:
-            rollout(c, plant, 1)
-        if mode == 1 or (t + 1) % 13 == 0:
-            assert (c.read("status")[:, 0] & 47 == 0).all(), t
-        if t + 1 == ticks - int(L.FREQ):
-            mid = _stats(plant)
-    end = _stats(plant)
-    assert (c.read("safe") == 1).all()
-    assert (mid["n"] == ticks - int(L.FREQ)).all() and (end["n"] == ticks).all()
-    rpy0 = L.rpy_of(start[:, 0:4])
-    stats = dict(z_min=np.minimum(end["z_min"], start[:, 6]), z_max=np.maximum(end["z_max"], start[:, 6]),
-                 roll_max=np.maximum(end["roll_max"], np.abs(rpy0[:, 0])),
-                 pitch_max=np.maximum(end["pitch_max"], np.abs(rpy0[:, 1])),
-                 vx_mean=(end["vx_sum"] - mid["vx_sum"]) / (end["n"] - mid["n"]))
-    env = L.envelope(rec)
-    for k in L.STATS:
-        lo, hi = np.tile(env[k][0], reps), np.tile(env[k][1], reps)
-        want = np.tile(np.asarray(rec[k]), reps)
-        print(f"{kind} mode {mode} {path} {k}: largest distance from the CPU run {np.abs(stats[k] - want).max():.3e}, "
-              f"allowed {float((hi - want).max()):.3e}")
-        assert (stats[k] >= lo).all() and (stats[k] <= hi).all(), (k, stats[k], lo, hi)
+    start, mid, end = G.ground_walk(c, plant, path, mode, ticks, gold["seed"], gold["settle"])
+    G.assert_inside_envelope(G.stats_from_accumulators(start, mid, end), rec, reps, f"{kind} mode {mode} {path}")
     got = _snap4(plant, B)
     if LF.RUNGS[kind]:
         assert np.abs(got["support"]).max() > 1e-3            # the ground is felt
@@ -344,10 +306,10 @@ def test_the_fleet_walks_on_the_field(kind, mode, path):
 def test_reset_keeps_the_binding_and_init_unbinds():
     """reset(mask) stands the masked robots on the summed surface -- the field over slope and stairs -- and leaves the
     others alone; init() unbinds, and the plant is the plain plant again, bit for bit.  With contact decided by the ground
-    the masked reset is the model's too, counters included (tests/test_gpu_contact.py: _masked_reset_is_the_models)."""
+    the masked reset is the model's too, counters included (fleet_gpu.masked_reset_is_the_models, which tests/test_gpu_contact.py runs on flat ground and on terrain)."""
     from quadruped_ctrl_amd.binding import rollout
     import plant_model_field as PF
-    TCN._masked_reset_is_the_models("field")
+    G.masked_reset_is_the_models("field")
     B = 32
     ca, pa, keep, (gait, vel, xyyaw) = _walk_on_field(B, "scheduled", amp=0.06)
     cb, pb, _ = _walk_pair(B)
@@ -381,14 +343,14 @@ def test_reset_keeps_the_binding_and_init_unbinds():
     assert not f["bound"] and f["z"] is None and f["flags"] == 0 and not pa.terrain()["bound"]
     rollout(ca, pa, 14)
     rollout(cb, pb, 14)
-    TT._same(pa, pb, "after init")
+    _same(pa, pb, "after init")
     pa.set_field(keep[0], keep[1], LF.CELL)
     assert pa.field()["bound"]
     pa.set_field(None)
     assert not pa.field()["bound"]
     rollout(ca, pa, 13)
     rollout(cb, pb, 13)
-    TT._same(pa, pb, "after set_field(None)")
+    _same(pa, pb, "after set_field(None)")
     del keep
     ca.close()
     cb.close()

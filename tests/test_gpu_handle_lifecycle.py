@@ -6,9 +6,9 @@ readings on a shared device include other tenants.
 import numpy as np
 import pytest
 
+import fleet_gpu as G
 import plant_loop as L
 import sense_loop as SL
-import test_gpu_plant as TP
 
 pytestmark = pytest.mark.gpu
 
@@ -21,14 +21,14 @@ def _init_and_run(c, plant, sensors):
     import torch
     from quadruped_ctrl_amd.binding import rollout_sensed
     gait, vel, xyyaw = (a[:B] for a in L.commands(0))
-    c.init(B, TP.DEFAULTS["freq"], L.PID)
-    c.set_gait(TP._dev(c, gait))
-    c.set_vel(TP._dev(c, vel))
-    plant.init(TP.DEFAULTS["mu"], 1, TP._dev(c, xyyaw))
+    c.init(B, G.DEFAULTS["freq"], L.PID)
+    c.set_gait(G.dev(c, gait))
+    c.set_vel(G.dev(c, vel))
+    plant.init(G.DEFAULTS["mu"], 1, G.dev(c, xyyaw))
     plant.enable_stats()
     plant.reset_stats()
     sensors.init(SEED)
-    keep = {k: TP._dev(c, v) for k, v in SL.noise(B).items()}
+    keep = {k: G.dev(c, v) for k, v in SL.noise(B).items()}
     sensors.set_params(**keep)
     sensors.settle(SETTLE)
     res = rollout_sensed(c, plant, sensors, TICKS)

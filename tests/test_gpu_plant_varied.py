@@ -2,10 +2,11 @@
 BatchedPlant.set_params / enable_stats / reset_stats / stats).
 
 The kernel is compared with tests/plant_model_varied.py at tests/test_gpu_plant.py's tolerance, 1e-10 relative to
-max(1, |x|): the same arithmetic with a handful more fp64 operations per substep.  The walk under the disturbance of
+max(1, |x|) (fleet_gpu.TOL): the same arithmetic with a handful more fp64 operations per substep.  The walk under the disturbance of
 plant_loop_varied.variation() is held to the CPU loop's recorded statistics
 (tests/golden/plant_varied_closed_loop_cpu.json) by plant_loop.envelope(); everything else compares two runs of the
-library bit for bit.
+library bit for bit.  The shared helpers and the walk (walk, stats_from_accumulators, assert_inside_envelope) are
+tests/fleet_gpu.py's.
 """
 import ctypes as C
 import json
@@ -14,11 +15,11 @@ import os
 import numpy as np
 import pytest
 
+import fleet_gpu as G
 import plant_loop as L
 import plant_loop_varied as LV
 import plant_model as PM
 import plant_model_varied as PV
-import test_gpu_plant as TP
 from plant_cases import DEFAULTS, parity_case
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +27,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 PARAMS = ("mass", "ibody", "mu", "force", "torque")
-_pair, _dev, _snap, _close, _compare, _walk_setup = TP._pair, TP._dev, TP._snap, TP._close, TP._compare, TP._walk_setup
+_pair, _dev, _snap, _close, _compare, _walk_pair = G.pair, G.dev, G.snap, G.close, G.compare, G.walk_pair
+_snap3, _stats = G.snap_legs, G.plant_stats
 
 
 def _values(B, seed):
@@ -55,19 +57,6 @@ def _model(B, substeps, vals, src=None, xyyaw=None):
     return mv
 
 
-def _snap3(plant, B):
-    s = _snap(plant)
-    s["foot"], s["grf"] = s["foot"].reshape(B, 4, 3), s["grf"].reshape(B, 4, 3)
-    return s
-
-
-def _stats(plant):
-    import torch
-    torch.cuda.synchronize()
-    s = plant.stats()
-    return {k: s[k].cpu().numpy().copy() for k in PV.STAT_KEYS}
-
-
 @pytest.mark.parametrize("substeps", [1, 4])
 def test_single_step_parity_with_all_five_bound(substeps):
     """tests/test_gpu_plant.py's single-step case (B = 257: a partial last block, a lane count that is no multiple of 64;
@@ -76,7 +65,7 @@ def test_single_step_parity_with_all_five_bound(substeps):
     vals = _values(B, 1000 + substeps)
     mv = _model(B, substeps, vals, m)
     c, plant = _pair(B, substeps=substeps)
-    TP._start(c, plant, m, cs, pd, vd)
+    G.start(c, plant, m, cs, pd, vd)
     keep = _bind(c, plant, vals)
     plant.enable_stats()
     plant.step(_dev(c, tau.reshape(B, 12)))
@@ -113,7 +102,7 @@ def test_each_pointer_alone_and_all_together(which):
     vals = full if which == "all" else {which: full[which]}
     mv = _model(B, 1, vals, m)
     c, plant = _pair(B)
-    TP._start(c, plant, m, cs, pd, vd)
+    G.start(c, plant, m, cs, pd, vd)
     keep = _bind(c, plant, vals)
     plant.step(_dev(c, tau.reshape(B, 12)))
     mv.step(tau.reshape(B, 12), cs, pd, vd)
@@ -123,14 +112,6 @@ def test_each_pointer_alone_and_all_together(which):
     assert np.abs(mv.state - m.state).max() > 1e-6, which
     del keep
     c.close()
-
-
-def _walk_pair(B, schedule="lockstep", mode=None):
-    gait, vel, xyyaw = _walk_setup(mode or 0, B // L.N_CMD)
-    c, plant = _pair(B, schedule, mode, xyyaw=xyyaw)
-    c.set_gait(_dev(c, gait))
-    c.set_vel(_dev(c, vel))
-    return c, plant, (gait, vel, xyyaw)
 
 
 def _neutral(B):
@@ -144,7 +125,7 @@ def test_neutral_values_change_no_bit_and_init_unbinds():
 
     def same(a, b, what):
         sa, sb = _snap(a), _snap(b)
-        for k in TP.PLANT_KEYS:
+        for k in G.PLANT_KEYS:
             assert np.array_equal(sa[k], sb[k]), (what, k)
         assert np.array_equal(a.effort.cpu().numpy(), b.effort.cpu().numpy()), what
 
@@ -338,31 +319,15 @@ def test_the_fleet_survives(mode):
     assert np.array_equal(rec["vel"], vel[:L.N_CMD]) and np.array_equal(rec["gait"], gait[:L.N_CMD])
     dev = _bind(c, plant, dict(mass=var["mass"], ibody=var["ibody"], mu=var["mu"], force=var["force"](0), torque=var["torque"]))
     plant.enable_stats()
-    start = plant.state.cpu().numpy().copy()
     t0, t1 = var["push_ticks"]
-    for t in range(L.TICKS):
+
+    def tick(t):
         if t in (t0, t1):
             dev["force"].copy_(_dev(c, var["force"](t)))
         rollout(c, plant, 1)
-        if mode == 1 or (t + 1) % 13 == 0:
-            assert (c.read("status")[:, 0] & 47 == 0).all(), t
-        if t + 1 == L.TICKS - int(L.FREQ):
-            at150 = _stats(plant)
-    end = _stats(plant)
-    assert (c.read("safe") == 1).all()
-    assert (at150["n"] == 150).all() and (end["n"] == L.TICKS).all()
-    rpy0 = L.rpy_of(start[:, 0:4])
-    stats = dict(z_min=np.minimum(end["z_min"], start[:, 6]), z_max=np.maximum(end["z_max"], start[:, 6]),
-                 roll_max=np.maximum(end["roll_max"], np.abs(rpy0[:, 0])),
-                 pitch_max=np.maximum(end["pitch_max"], np.abs(rpy0[:, 1])),
-                 vx_mean=(end["vx_sum"] - at150["vx_sum"]) / (end["n"] - at150["n"]))
-    env = L.envelope(rec)
-    for k in L.STATS:
-        lo, hi = np.tile(env[k][0], reps), np.tile(env[k][1], reps)
-        want = np.tile(np.asarray(rec[k]), reps)
-        print(f"mode {mode} {k}: largest distance from the CPU run {np.abs(stats[k] - want).max():.3e}, "
-              f"allowed {float((hi - want).max()):.3e}")
-        assert (stats[k] >= lo).all() and (stats[k] <= hi).all(), (k, stats[k], lo, hi)
+
+    start, at150, end = G.walk(c, plant, tick, L.TICKS, lambda t: mode == 1 or (t + 1) % 13 == 0)
+    G.assert_inside_envelope(G.stats_from_accumulators(start, at150, end), rec, reps, f"mode {mode}")
     del dev
     c.close()
 

@@ -3,7 +3,8 @@
 The kernel is compared with tests/sense_model.py BIT FOR BIT (np.array_equal): the path holds integer arithmetic, one
 conversion, and one fp64 operation at a time -- no transcendental function, no contraction.  The closed-loop walk through
 the controller's estimators is held to the CPU loop's recorded statistics (tests/golden/sense_closed_loop_cpu.json) by
-plant_loop.envelope(); everything else compares two runs of the library bit for bit.
+plant_loop.envelope(); everything else compares two runs of the library bit for bit.  The shared helpers (trio,
+sense_values, sense_bind, ...) and the walk are tests/fleet_gpu.py's.
 """
 import ctypes as C
 import json
@@ -12,43 +13,15 @@ import os
 import numpy as np
 import pytest
 
+import fleet_gpu as G
 import plant_loop as L
 import sense_loop as SL
 import sense_model as SM
-import test_gpu_plant as TP
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_pair, _dev, _snap = TP._pair, TP._dev, TP._snap
-
-
-def _trio(B, schedule="lockstep", mode=None, seed=SL.SEED):
-    """Controller + plant + sensors on plant_loop's commands, repeated over B robots (B need not be a multiple of 16)."""
-    from quadruped_ctrl_amd.binding import BatchedSensors
-    gait, vel, xyyaw = L.commands(mode or 0)
-    k = np.arange(B) % L.N_CMD
-    gait, vel, xyyaw = gait[k], vel[k], xyyaw[k]
-    c, plant = _pair(B, schedule, mode, xyyaw=xyyaw)
-    c.set_gait(_dev(c, gait))
-    c.set_vel(_dev(c, vel))
-    s = BatchedSensors(plant)
-    s.init(seed)
-    return c, plant, s, (gait, vel, xyyaw)
-
-
-def _values(B, seed):
-    """All six arrays, every robot its own values."""
-    rng = np.random.default_rng(seed)
-    return dict(acc_bias=rng.uniform(-0.5, 0.5, (B, 3)), gyro_bias=rng.uniform(-0.05, 0.05, (B, 3)),
-                acc_sigma=rng.uniform(0.05, 0.5, B), gyro_sigma=rng.uniform(0.005, 0.05, B),
-                q_sigma=rng.uniform(0.0005, 0.005, B), qd_sigma=rng.uniform(0.01, 0.1, B))
-
-
-def _bind(c, s, vals):
-    t = {k: _dev(c, v) for k, v in vals.items()}
-    s.set_params(**t)
-    return t
+_dev, _snap, _trio, _values, _bind = G.dev, G.snap, G.trio, G.sense_values, G.sense_bind
 
 
 def _out(s):
@@ -58,13 +31,6 @@ def _out(s):
     v = s.view()
     return dict(imu=s.imu.cpu().numpy().copy(), motor=s.motor.cpu().numpy().copy(), n=v["n"].cpu().numpy().copy(),
                 epoch=v["epoch"].cpu().numpy().copy())
-
-
-def _stats(plant):
-    import torch
-    torch.cuda.synchronize()
-    st = plant.stats()
-    return {k: st[k].cpu().numpy().copy() for k in ("n", "z_min", "z_max", "roll_max", "pitch_max", "vx_sum", "vy_sum")}
 
 
 @pytest.mark.parametrize("B", [5, 67])
@@ -275,29 +241,10 @@ def test_the_fleet_walks_on_noisy_sensors(mode):
     assert np.array_equal(gold[f"mode{mode}"]["vel"], vel[:L.N_CMD]) and np.array_equal(gold[f"mode{mode}"]["gait"], gait[:L.N_CMD])
     keep = _bind(c, s, nz)
     plant.enable_stats()
-    start = plant.state.cpu().numpy().copy()
-    s.settle(gold["settle"])
-    for t in range(L.TICKS):
-        rollout_sensed(c, plant, s, 1)
-        if mode == 1 or (t + 1) % 13 == 0:
-            assert (c.read("status")[:, 0] & 47 == 0).all(), t
-        if t + 1 == L.TICKS - int(L.FREQ):
-            at150 = _stats(plant)
-    end = _stats(plant)
-    assert (c.read("safe") == 1).all()
-    assert (at150["n"] == 150).all() and (end["n"] == L.TICKS).all() and (_out(s)["n"] == gold["settle"] + L.TICKS).all()
-    rpy0 = L.rpy_of(start[:, 0:4])
-    stats = dict(z_min=np.minimum(end["z_min"], start[:, 6]), z_max=np.maximum(end["z_max"], start[:, 6]),
-                 roll_max=np.maximum(end["roll_max"], np.abs(rpy0[:, 0])),
-                 pitch_max=np.maximum(end["pitch_max"], np.abs(rpy0[:, 1])),
-                 vx_mean=(end["vx_sum"] - at150["vx_sum"]) / (end["n"] - at150["n"]))
-    env = L.envelope(rec)
-    for k in L.STATS:
-        lo, hi = np.tile(env[k][0], reps), np.tile(env[k][1], reps)
-        want = np.tile(np.asarray(rec[k]), reps)
-        print(f"mode {mode} {k}: largest distance from the CPU run {np.abs(stats[k] - want).max():.3e}, "
-              f"allowed {float((hi - want).max()):.3e}")
-        assert (stats[k] >= lo).all() and (stats[k] <= hi).all(), (k, stats[k], lo, hi)
+    start, at150, end = G.walk(c, plant, lambda t: rollout_sensed(c, plant, s, 1), L.TICKS,
+                               lambda t: mode == 1 or (t + 1) % 13 == 0, settle=lambda: s.settle(gold["settle"]))
+    assert (_out(s)["n"] == gold["settle"] + L.TICKS).all()
+    G.assert_inside_envelope(G.stats_from_accumulators(start, at150, end), rec, reps, f"mode {mode}")
     del keep
     c.close()
 

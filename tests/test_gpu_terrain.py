@@ -5,7 +5,8 @@ tolerance, 1e-10 relative to max(1, |x|): the same arithmetic with a few dozen m
 whose argument the case keeps 1e-6 tread depths away from an integer (about ten orders above its rounding).  The walk on
 plant_loop_terrain.terrain() is held to the CPU loops' recorded statistics
 (tests/golden/plant_terrain_closed_loop_cpu.json) by plant_loop.envelope(); everything else compares two runs of the
-library bit for bit.
+library bit for bit.  The shared helpers (snap3, compare_terrain, walk_pair, stand_on, ...) and the walk are
+tests/fleet_gpu.py's.
 """
 import ctypes as C
 import json
@@ -14,64 +15,22 @@ import os
 import numpy as np
 import pytest
 
+import fleet_gpu as G
 import plant_loop as L
 import plant_loop_terrain as LT
 import plant_model as PM
 import plant_model_terrain as PT
 import plant_model_varied as PV
-import sense_loop as SL
 import terrain_cases as TC
-import test_gpu_plant as TP
 from plant_cases import DEFAULTS
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
-_pair, _dev, _snap, _close, _compare, _walk_setup = TP._pair, TP._dev, TP._snap, TP._close, TP._compare, TP._walk_setup
-
-
-def _snap3(plant, B):
-    """The plant's views and the terrain's, as numpy copies (synchronises)."""
-    s = _snap(plant)
-    s["foot"], s["grf"] = s["foot"].reshape(B, 4, 3), s["grf"].reshape(B, 4, 3)
-    t = plant.terrain()
-    s["ground"], s["support"] = t["ground"].cpu().numpy().copy(), t["support"].cpu().numpy().copy()
-    return s
-
-
-def _stats(plant):
-    import torch
-    torch.cuda.synchronize()
-    s = plant.stats()
-    return {k: s[k].cpu().numpy().copy() for k in PV.STAT_KEYS}
-
-
-def _compare_terrain(s, m, what):
-    _compare(s, m, what)
-    _close(s["ground"], m.ground, f"{what} ground")
-    _close(s["support"], m.support, f"{what} support")
-
-
-def _all(c, B):
-    import torch
-    return torch.ones(B, dtype=torch.bool, device=c.device)
-
-
-def _walk_pair(B, schedule="lockstep", mode=None):
-    gait, vel, xyyaw = _walk_setup(mode or 0, B // L.N_CMD)
-    c, plant = _pair(B, schedule, mode, xyyaw=xyyaw)
-    c.set_gait(_dev(c, gait))
-    c.set_vel(_dev(c, vel))
-    return c, plant, (gait, vel, xyyaw)
-
-
-def _stand_on(c, plant, rows, xyyaw, **flags):
-    """init -> set_terrain -> reset(all): -> the device rows (bound: keep them referenced)."""
-    dev = _dev(c, rows)
-    plant.set_terrain(dev, **flags)
-    plant.reset(_all(c, plant.batch), None if xyyaw is None else _dev(c, xyyaw))
-    return dev
+_pair, _dev, _snap, _close, _same = G.pair, G.dev, G.snap, G.close, G.same
+_snap3, _stats, _compare_terrain, _all, _walk_pair, _stand_on = (G.snap3, G.plant_stats, G.compare_terrain, G.all_robots,
+                                                                  G.walk_pair, G.stand_on)
 
 
 # ---- 1. single-step parity ---------------------------------------------------------------------------------------------
@@ -88,7 +47,7 @@ def test_single_step_parity(substeps, vary, stats):
     vals = TC.values(1000 + substeps) if vary else None
     m = TC.model(substeps, rows, vals, src=m0)
     c, plant = _pair(B, substeps=substeps)
-    TP._start(c, plant, m0, cs, pd, vd)
+    G.start(c, plant, m0, cs, pd, vd)
     dev = _dev(c, rows)
     plant.set_terrain(dev, clamp_swing=True, rebase_z=True)
     plant.terrain()["support"].copy_(_dev(c, m0.support))
@@ -150,13 +109,6 @@ def test_every_column_and_flag_moves_the_model():
 
 
 # ---- 3. neutrality -------------------------------------------------------------------------------------------------------
-
-def _same(a, b, what):
-    sa, sb = _snap(a), _snap(b)
-    for k in TP.PLANT_KEYS:
-        assert np.array_equal(sa[k], sb[k]), (what, k)
-    assert np.array_equal(a.effort.cpu().numpy(), b.effort.cpu().numpy()), what
-
 
 @pytest.mark.parametrize("schedule", ["lockstep", "per_robot"])
 @pytest.mark.parametrize("extras", [False, True])
@@ -347,7 +299,6 @@ def test_the_fleet_walks_on_terrain(mode, path):
     settle() (path "sensed").  The statistics are read from the device a second before the end and at the end.  Every
     robot stays safe, no solve reports an error bit, and the five statistics lie inside plant_loop.envelope() of the CPU
     run on the same ground."""
-    from quadruped_ctrl_amd.binding import BatchedSensors, rollout, rollout_sensed
     reps = 4
     B = L.N_CMD * reps
     gold = json.load(open(os.path.join(ROOT, "tests", "golden", "plant_terrain_closed_loop_cpu.json")))
@@ -360,37 +311,8 @@ def test_the_fleet_walks_on_terrain(mode, path):
     dev = _stand_on(c, plant, rows, xyyaw, clamp_swing=True, rebase_z=path == "state")
     plant.enable_stats()
     plant.reset_stats()
-    start = plant.state.cpu().numpy().copy()
-    if path == "sensed":
-        s = BatchedSensors(plant)
-        s.init(gold["seed"])
-        keep = {k: _dev(c, v) for k, v in SL.noise(B).items()}
-        s.set_params(**keep)
-        s.settle(gold["settle"])
-    for t in range(ticks):
-        if path == "sensed":
-            rollout_sensed(c, plant, s, 1)
-        else:
-            rollout(c, plant, 1)
-        if mode == 1 or (t + 1) % 13 == 0:
-            assert (c.read("status")[:, 0] & 47 == 0).all(), t
-        if t + 1 == ticks - int(L.FREQ):
-            mid = _stats(plant)
-    end = _stats(plant)
-    assert (c.read("safe") == 1).all()
-    assert (mid["n"] == ticks - int(L.FREQ)).all() and (end["n"] == ticks).all()
-    rpy0 = L.rpy_of(start[:, 0:4])
-    stats = dict(z_min=np.minimum(end["z_min"], start[:, 6]), z_max=np.maximum(end["z_max"], start[:, 6]),
-                 roll_max=np.maximum(end["roll_max"], np.abs(rpy0[:, 0])),
-                 pitch_max=np.maximum(end["pitch_max"], np.abs(rpy0[:, 1])),
-                 vx_mean=(end["vx_sum"] - mid["vx_sum"]) / (end["n"] - mid["n"]))
-    env = L.envelope(rec)
-    for k in L.STATS:
-        lo, hi = np.tile(env[k][0], reps), np.tile(env[k][1], reps)
-        want = np.tile(np.asarray(rec[k]), reps)
-        print(f"mode {mode} {path} {k}: largest distance from the CPU run {np.abs(stats[k] - want).max():.3e}, "
-              f"allowed {float((hi - want).max()):.3e}")
-        assert (stats[k] >= lo).all() and (stats[k] <= hi).all(), (k, stats[k], lo, hi)
+    start, mid, end = G.ground_walk(c, plant, path, mode, ticks, gold["seed"], gold["settle"])
+    G.assert_inside_envelope(G.stats_from_accumulators(start, mid, end), rec, reps, f"mode {mode} {path}")
     # they climbed: the stance feet of the robots that left an upward flight stand four treads up
     t = plant.terrain()
     sup = t["support"].cpu().numpy()

@@ -138,6 +138,32 @@ def test_cpu_closed_loop_on_the_varied_plant_is_safe_and_is_what_the_fixture_rec
         assert np.abs(stats["vx_mean"] - vel[:, 0]).max() < 0.05
 
 
+def test_statistics_from_the_accumulators_are_the_recorders():
+    """fleet_gpu.stats_from_accumulators -- the one formula every device walk rebuilds its five statistics with -- on the
+    CPU loop's own model, in both robot modes: the start state, the model's accumulators copied before the step of tick
+    150 and at the end give what plant_loop.Recorder returned for the same run.  The extremes are the same comparisons of
+    the same doubles: equal.  vx_mean: the two sides sum at most 650 speeds of a few m/s in a different order,
+    650^2 * 1.1e-16 * |v| / 500 is below 1e-12."""
+    import fleet_gpu as G
+    for mode in (0, 1):
+        seen = {}
+
+        def sample(t, plant):
+            if t == 0:
+                seen["start"], seen["plant"] = np.asarray(plant.state, np.float64).copy(), plant
+            if t == L.TICKS - int(L.FREQ):
+                seen["mid"] = {k: v.copy() for k, v in plant.stats.items()}
+
+        stats, info = LV.cpu_loop_varied(mode, each_tick=sample)
+        assert (seen["mid"]["n"] == 150).all() and (seen["plant"].stats["n"] == L.TICKS).all()
+        got = G.stats_from_accumulators(seen["start"], seen["mid"], seen["plant"].stats)
+        for k in ("z_min", "z_max", "roll_max", "pitch_max"):
+            assert np.array_equal(got[k], stats[k]), (mode, k, np.abs(got[k] - stats[k]).max())
+        err = np.abs(got["vx_mean"] - stats["vx_mean"]).max()
+        print(f"mode {mode} vx_mean: accumulators against Recorder {err:.3e}")
+        assert err <= 1e-12, (mode, err)
+
+
 @pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="no hipcc")
 def test_kernel_choice_for_every_binding(tmp_path):
     """tests/plant_pick_dump.cpp: csrc/qmpc_plant_pick.h alone, host only.  The step and the reset kernel for all eight
