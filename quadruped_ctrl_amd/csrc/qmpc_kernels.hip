@@ -29,7 +29,7 @@
 //     barrier in the loop in class 1 -- in the larger classes waves 1..3 take a
 //     share of the stored events once there are many).  A robot whose on-chip event
 //     pool fills up continues on a slice of an overflow pool in global memory; the
-//     Schur-form engine (second solve_one instantiation) is the last resort when the
+//     Schur-form engine (solve_one's QV_SCHUR variant) is the last resort when the
 //     working-set slots run out.  Swing feet are eliminated up front exactly like
 //     SolverMPC.cpp:441-525.
 //   * fp64 throughout the solve (the reference hands fp32-assembled data to a
@@ -37,9 +37,10 @@
 //     instead of adding a second, uncorrelated copy of it).
 //   * size classes chain 1 -> 4 -> 2 -> 3: the first is launched over the batch, a robot that does not fit appends
 //     itself to a work list that the next class (LISTED instantiation) consumes as a queue.
-//   * variants of the same template (own instantiations, the default kernel carries none of them):
-//     WARM  -- warm start across MPC cycles from the previous working set (qmpc_set_warm_start);
-//     ADMM  -- the reference's JCQP alternate, QpProblem::runFromDense (src/JCQP/QpProblem.cpp:178-269):
+//   * variants of the same template, solve_one<RB, QV> with QV a word of named flags (QV_EVENT | QV_CMD | ...: the enum in front
+//     of solve_one; own instantiations, the default kernel carries none of these):
+//     QV_WARM -- warm start across MPC cycles from the previous working set (qmpc_set_warm_start);
+//     QV_ADMM -- the reference's JCQP alternate, QpProblem::runFromDense (src/JCQP/QpProblem.cpp:178-269):
 //              same assembly and sweep with the KKT system reduced to the x block, ADMM engine;
 //     P.model = 1 -- SparseCMPC's discretisation (src/MPC_Ctrl/SparseCMPC_Math.cpp:6-28) through the same
 //              closed forms: one coefficient family and the height row of the free response change.
@@ -730,23 +731,50 @@ __device__ __forceinline__ void qmpc_census_dump(Smem<RB>& S, const QmpcParams& 
 #define QMPC_STOP(k, regs) do { } while (0)
 #endif
 
-// CMD selects where the input record comes from: false = loaded (qmpc_solve), true =
-// generated in stage 0 from the controller command (qmpc_solve_commands).
-// V5 selects the active-set engine: true = event form (projected inverse as a
-// sum of rank-1 events; fastest, capacity-limited by the LDS pool), false = the
-// Schur form that never overflows.  Both are run by wave 0 alone.  Returns true
-// when the robot must be re-run with the other engine.
-// PHA = true: the PRODUCER half of the decoupled path (qmpc_sweep_kernel): stages 0-3 and the unconstrained
-// minimiser as below, then the inverse goes to the robot's work item in global memory (L2 / Infinity-Cache
-// resident) instead of LDS and the workgroup moves on; the active set is run by qmpc_engine_kernel
-// (qmpc_engine.hip) -- a workgroup of the large classes no longer pins a whole CU while one of its waves iterates.
-// PRE = true: the caller fetched the kernel arguments of stage 0 in one batch (qmpc_kernarg_batch): *pre; otherwise they are read
-// from PK where they are used.
-template <int RB, bool V5, bool CMD, bool ADMM = false, bool WARM = false, bool PHA = false, bool BIG = false, bool PRIO = false,
-          bool PRE = false>
+// The variant of solve_one (and of solve_robot): a word of these flags, so that a call site says what it selects.
+// Exactly one engine; everything else is off unless named.
+enum : unsigned {
+  // the active-set engine, both run by wave 0 alone: event form (projected inverse as a sum of rank-1 events; fastest,
+  // capacity-limited by the LDS pool) or the Schur form that never overflows
+  QV_EVENT = 1u << 0,
+  QV_SCHUR = 0u,
+  // where the input record comes from: loaded (qmpc_solve), or with QV_CMD generated in stage 0 from the controller
+  // command (qmpc_solve_commands)
+  QV_CMD = 1u << 1,
+  QV_ADMM = 1u << 2,  // the JCQP alternate: ADMM in place of the active set
+  QV_WARM = 1u << 3,  // warm start from the robot's previous working set
+  // the PRODUCER half of the decoupled path (qmpc_sweep_kernel): stages 0-3 and the unconstrained minimiser as below, then
+  // the inverse goes to the robot's work item in global memory (L2 / Infinity-Cache resident) instead of LDS and the
+  // workgroup moves on; the active set is run by qmpc_engine_kernel (qmpc_engine.hip) -- a workgroup of the large classes
+  // no longer pins a whole CU while one of its waves iterates
+  QV_PRODUCER = 1u << 4,
+  QV_BIG = 1u << 5,       // ... of the LARGE problems (192 < n_r <= 432; qmpc_big_kernel)
+  QV_ONE_ROUND = 1u << 6,  // the first class of a chain, the only launch that can be one round: may stage by the proxy (STAGED below)
+  // the caller fetched the kernel arguments of stage 0 in one batch (qmpc_kernarg_batch): *pre; otherwise they are read
+  // from PK where they are used
+  QV_BATCHED_ARGS = 1u << 7,
+};
+
+// Returns true when the robot must be re-run with the other engine.
+template <int RB, unsigned QV>
 __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>& S, const QmpcParams& PK,
-                                          const bool ws_cold = false,  // (WARM: ignore the robot's previous working set)
+                                          const bool ws_cold = false,  // (QV_WARM: ignore the robot's previous working set)
                                           const QmpcStage0Args* pre = nullptr) {
+  constexpr bool V5 = (QV & QV_EVENT) != 0, CMD = (QV & QV_CMD) != 0, ADMM = (QV & QV_ADMM) != 0, WARM = (QV & QV_WARM) != 0;
+  constexpr bool PHA = (QV & QV_PRODUCER) != 0, BIG = (QV & QV_BIG) != 0, PRIO = (QV & QV_ONE_ROUND) != 0;
+  constexpr bool PRE = (QV & QV_BATCHED_ARGS) != 0;
+  static_assert(!BIG || PHA, "the large problems exist on the producer path only");
+  // STAGED: this instantiation does the one-round staging.
+  // ONE-ROUND launch without a usable hint (prio_cu != nullptr; DESIGN 13): the workgroups that share a CU compete for its issue
+  // slots, and the CU is done when the LAST of them is -- the one that iterates longest.  Which one that will be is guessed from
+  // the robot's keys (qmpc_robot_keys: correlation of the score with the iteration count 0.69 ... 0.76 -- configs[1]'s 13-iteration
+  // robot is third of 1024): wave 1 (which only copies tables in stage 0: the stance list and M_b / N_b are wave 0's, the
+  // transcendental-heavy error rows waves 2 - 3's) evaluates them in stage 0, behind the issue of its own loads of that stage (in
+  // front of them it put a second memory round trip into the stage: +2.8 k cycles for everybody), all its lanes together
+  // (qmpc_robot_keys_wave), and its last lane posts (call number, score level, robot) with ONE atomic maximum on its CU's word
+  // (four arrivals per word, served by the XCD's L2; a newer call's number beats whatever an older call left: nothing to reset);
+  // the end of stage 1 reads the word back, and the robots that are not their CU's hardest yield from the assembly on.
+  constexpr bool STAGED = PRIO && !CMD && !ADMM && !BIG && !PHA;
   using C = Cfg<RB>;
   constexpr int NP = C::NP, CW = C::CW, NT = C::NT, KMAX = C::KMAX, KW = C::KW, RE = C::RE;
   const QmpcParams& P = S.par;  // parked copy: everything after stage 0
@@ -948,15 +976,9 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     g_ct5 = QMPC_A(ctab)[5 * hh + tix];
     g_ct8 = QMPC_A(ctab)[8 * hh + tix];
   }
-  // ONE-ROUND launch without a usable hint (prio_cu != nullptr; DESIGN 13): the workgroups that share a CU compete for its issue
-  // slots, and the CU is done when the LAST of them is -- the one that iterates longest.  Which one that will be is guessed from
-  // the robot's keys (qmpc_robot_keys: correlation of the score with the iteration count 0.69 ... 0.76 -- configs[1]'s 13-iteration
-  // robot is third of 1024): wave 1 (which only copies tables in stage 0: the stance list and M_b / N_b are wave 0's, the
-  // transcendental-heavy error rows waves 2 - 3's) evaluates them HERE, behind the issue of its own loads of this stage (in front of them it put a second memory round trip
-  // into the stage: +2.8 k cycles for everybody), all its lanes together
-  // (qmpc_robot_keys_wave), and its last lane posts (call number, score level, robot) with ONE atomic maximum on its CU's word
-  // (four arrivals per word, served by the XCD's L2; a newer call's number beats whatever an older call left: nothing to reset) ...
-  if constexpr (PRIO && !CMD && !ADMM && !BIG && !PHA) {
+  // the one-round staging (STAGED above): wave 1 evaluates the robot's keys HERE, behind the issue of its own loads of this stage,
+  // and its last lane posts them on its CU's word ...
+  if constexpr (STAGED) {
     [[maybe_unused]] QmpcKeysRaw kraw = {};
     if constexpr (PRE) {
       // (the batched kernels: the keys' own loads go out with the stage's -- one round trip for wave 1 as well -- and the
@@ -988,7 +1010,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       }
     }
   }
-  if constexpr (PRE && !(PRIO && !CMD && !ADMM && !BIG && !PHA)) {
+  if constexpr (PRE && !STAGED) {
     asm volatile("; qmpc stage0 loads end");
     QMPC_ISSUED_TICK();
   }
@@ -1342,7 +1364,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       }
     }
   }
-  if constexpr (PRIO && !CMD && !ADMM && !BIG && !PHA) {
+  if constexpr (STAGED) {
     if (P.prio_cu && tid == NT - 1) {  // 0: this robot's entry stands; 1: another robot's of this call; 2: nobody on this CU posted
       unsigned hwid, xcc;  // (the same CU as the wave that posted: the same word)
       asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
@@ -1360,7 +1382,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
   // (the robots of a staged CU that are not its hardest step back one level from the assembly on, like the hint's robots after
   //  stage 0: configs[1] 2.73e7 -> 2.76e7, against stepping back only in the sweep; one level lower still throughout their
   //  sweep: no change)
-  if constexpr (PRIO && !CMD && !ADMM && !BIG && !PHA) {
+  if constexpr (STAGED) {
     if (PK.prio_cu && __builtin_amdgcn_readfirstlane(S.prio_rank) == 1) __builtin_amdgcn_s_setprio(2);
   }
   {
@@ -1970,7 +1992,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
   // F_k = I - P^-1, so the update has no row special-casing.
   bool notpd = false;
   bool staged = PK.hint_hard > 0;  // one-round staging of the sweep's issue priority: by the hint, or by the proxy's rank
-  if constexpr (PRIO && !CMD && !ADMM && !BIG && !PHA) {
+  if constexpr (STAGED) {
     if (PK.prio_cu) {  // (S.prio_rank: written before stage 1's barriers)
       const int rank = __builtin_amdgcn_readfirstlane(S.prio_rank);
       if (QMPC_DBG_ITER == 0 && dbg_clk && tid == 0) dbg_clk[14] = rank;  // (profiling hook)
@@ -3815,14 +3837,18 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
 // one robot with the engine pair of its class: event-form engine first (it continues in global memory when its
 // on-chip pool fills up); the (rare) robot that runs out of working-set SLOTS there is solved again from scratch
 // with the Schur-form engine, which has more of them
-// (PRE: the first solve takes the kernel arguments of its stage 0 from *pre, qmpc_kernarg_batch; a re-run reads them in place)
-template <int RB, bool CMD, bool WARM, bool PRIO = false, bool PRE = false>
+// QV: the variant without an engine -- QV_CMD, QV_WARM, and for the FIRST solve QV_ONE_ROUND and QV_BATCHED_ARGS (it takes the
+// kernel arguments of its stage 0 from *pre, qmpc_kernarg_batch; a re-run is never staged and reads them in place)
+template <int RB, unsigned QV>
 __device__ __forceinline__ void solve_robot(const int rid, const int tid, Smem<RB>& S, const QmpcParams& P,
                                             const QmpcStage0Args* pre = nullptr) {
+  static_assert((QV & ~(QV_CMD | QV_WARM | QV_ONE_ROUND | QV_BATCHED_ARGS)) == 0, "solve_robot picks the engine itself");
+  constexpr bool WARM = (QV & QV_WARM) != 0;
+  constexpr unsigned RERUN = QV & (QV_CMD | QV_WARM);
   if constexpr (Cfg<RB>::EVENT_ENGINE) {
     bool again;
     if (Cfg<RB>::GLOBAL_EVENTS && S.evslot < 0) again = true;  // no pool slice (pool_acquire timed out): Schur form only
-    else again = solve_one<RB, true, CMD, false, WARM, false, false, PRIO, PRE>(rid, tid, S, P, false, pre);
+    else again = solve_one<RB, QV_EVENT | QV>(rid, tid, S, P, false, pre);
     bool warm_again = false;
     if constexpr (WARM) {
       // a warm start that asked for the re-run (a guess the repair phase could not mend within the iteration limit, or one
@@ -3835,7 +3861,7 @@ __device__ __forceinline__ void solve_robot(const int rid, const int tid, Smem<R
         __syncthreads();
         int tid2 = tid;
         asm volatile("" : "+v"(tid2));
-        again = solve_one<RB, true, CMD, false, WARM>(rid, tid2, S, P, true);
+        again = solve_one<RB, QV_EVENT | RERUN>(rid, tid2, S, P, true);
         warm_again = true;
       }
     }
@@ -3845,7 +3871,7 @@ __device__ __forceinline__ void solve_robot(const int rid, const int tid, Smem<R
       // first run alive (spilled to scratch by EVERY workgroup) for this rare second run
       int tid2 = tid;
       asm volatile("" : "+v"(tid2));
-      solve_one<RB, false, CMD, false, WARM>(rid, tid2, S, P);
+      solve_one<RB, QV_SCHUR | RERUN>(rid, tid2, S, P);
       __syncthreads();
       if (tid2 == 0) P.status[rid] |= QMPC_DEV_ST_FALLBACK;  // informational
     } else if (WARM && warm_again) {
@@ -3853,7 +3879,7 @@ __device__ __forceinline__ void solve_robot(const int rid, const int tid, Smem<R
       if (tid == 0) P.status[rid] |= QMPC_DEV_ST_FALLBACK;  // informational: solved twice
     }
   } else {
-    solve_one<RB, false, CMD, false, WARM>(rid, tid, S, P);
+    solve_one<RB, QV_SCHUR | RERUN>(rid, tid, S, P);
   }
   // (thread 0 wrote the robot's status; the launch that re-solves what the decoupled engine handed back says so)
   if (P.status_or != 0 && tid == 0) P.status[rid] |= P.status_or;
@@ -4122,6 +4148,38 @@ __device__ __forceinline__ int size_order_take(const QmpcParams& P) {
   return (int)blockIdx.x;
 }
 
+// A work list consumed as a QUEUE (the LISTED kernels and qmpc_big_kernel, launched with at most one workgroup per resident
+// slot): entry blockIdx.x first, then whatever entry the head counter hands out, until the list (NLIST entries) is drained.
+// CHUNKED: the launch covers one chunk of the list, the entries from rid0 on -- the first entry and the refills are offset by it.
+// TID0: the thread's (logical) index in the workgroup of NT_ threads.  The statement given last solves one robot; it sees
+//   rid   the robot,
+//   tid1  the thread index, OPAQUE per robot: nothing derived from it is loop-invariant, so the compiler cannot hoist per-thread
+//         values out of the loop (and spill them across the whole solve),
+//   PK    the parameter block through an OPAQUE kernel-argument pointer: the ~30 scalar loads of stage 0 stay inside the loop
+//         instead of being hoisted into SGPRs that then spill (the parameter block is the only explicit kernel argument, so it
+//         sits at offset 0 of the kernarg segment).
+// The first barrier: every wave is done with this robot's LDS state; the exit test is uniform.
+// A macro, not a function: with the loop in a force-inlined function that is handed the solve as a callable, or with its steps
+// in force-inlined helpers, every kernel that drains a list compiled to other instructions -- and where the callable reached
+// the workgroup's LDS through a closure, the kernels that do not drain a list did too (profiles/solve_kernel_refactor_isa.md).
+#define QMPC_DRAIN_LIST(CHUNKED, NT_, TID0, NLIST, ...)                                                      \
+  for (int idx = (CHUNKED) ? P.rid0 + (int)blockIdx.x : (int)blockIdx.x;;) {                                 \
+    const int rid = P.list[idx];                                                                             \
+    int tid1 = (TID0);                                                                                       \
+    asm volatile("" : "+v"(tid1));                                                                           \
+    __builtin_assume(tid1 >= 0 && tid1 < (NT_));                                                             \
+    typedef const QMPC_AS4 QmpcParams* KernargPtr;                                                           \
+    KernargPtr pk = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();                                      \
+    asm volatile("" : "+s"(pk));                                                                             \
+    const QmpcParams& PK = *(const QmpcParams*)pk;                                                           \
+    __VA_ARGS__;                                                                                             \
+    __syncthreads();                                                                                         \
+    if ((TID0) == 0) S.qnext = ((CHUNKED) ? P.rid0 + (int)gridDim.x : (int)gridDim.x) + atomicAdd(P.qhead, 1); \
+    __syncthreads();                                                                                         \
+    idx = S.qnext;                                                                                           \
+    if (idx >= (NLIST)) break;                                                                               \
+  }
+
 // LISTED = false: the first class launched: robot = blockIdx.x; clears the NEXT call's list counters and queue
 // heads.  LISTED = true: every later class, launched with at most one workgroup per resident slot; it consumes
 // the list the previous classes filled as a queue: entry blockIdx.x first, then whatever entry the head counter
@@ -4134,6 +4192,7 @@ __global__ __launch_bounds__(Cfg<RB>::NT_LAUNCH, Cfg<RB>::MIN_WAVES) void qmpc_s
   // (the 96-row class: eight waves launched, six stay -- the logical thread index from here on)
   const int tid0 = balance_waves<RB>(S, P);
   if (tid0 < 0) return;
+  constexpr unsigned QV_RECORD = (CMD ? QV_CMD : 0u) | (WARM ? QV_WARM : 0u);  // where the record comes from, what the solve starts from
   if constexpr (!LISTED && Cfg<RB>::C1) {
     // The 64-row classes: every kernel argument that this head and stage 0 of the solve read comes in ONE batch of scalar loads
     // behind one wait (qmpc_kernarg_batch) -- the launch starts on a cold scalar cache, and fetched where they are used they
@@ -4166,7 +4225,7 @@ __global__ __launch_bounds__(Cfg<RB>::NT_LAUNCH, Cfg<RB>::MIN_WAVES) void qmpc_s
     __builtin_assume(tid0 >= 0 && tid0 < Cfg<RB>::NT);
     // (the first class of a chain: the only launch that can be one round.  Not the five-per-CU instantiation: it exists for launches
     //  of several rounds, and at 96 registers the staging's code in stage 0 costs it spills on the main path)
-    solve_robot<RB, CMD, WARM, RB != 6, true>(rid, tid0, S, P, &A);
+    solve_robot<RB, QV_RECORD | QV_BATCHED_ARGS | (RB != 6 ? QV_ONE_ROUND : 0u)>(rid, tid0, S, P, &A);
   } else if constexpr (!LISTED) {
     // (block index first: only block 0 waits for the kernel argument)
     if (blockIdx.x == 0 && P.clear_counts)
@@ -4182,7 +4241,7 @@ __global__ __launch_bounds__(Cfg<RB>::NT_LAUNCH, Cfg<RB>::MIN_WAVES) void qmpc_s
     }
     __builtin_assume(tid0 >= 0 && tid0 < Cfg<RB>::NT);
     // (the first class of a chain: the only launch that can be one round)
-    solve_robot<RB, CMD, WARM, true>(rid, tid0, S, P);
+    solve_robot<RB, QV_RECORD | QV_ONE_ROUND>(rid, tid0, S, P);
     pool_release<RB>(S, P);
     balance_release<RB>(tid0, S, P);
   } else {
@@ -4192,27 +4251,7 @@ __global__ __launch_bounds__(Cfg<RB>::NT_LAUNCH, Cfg<RB>::MIN_WAVES) void qmpc_s
       return;
     }
     pool_acquire<RB>(S, P);
-    for (int idx = (int)blockIdx.x;;) {
-      const int rid = P.list[idx];
-      // opaque thread id per robot: nothing derived from it is loop-invariant, so the compiler cannot hoist
-      // per-thread values out of the loop (and spill them across the whole solve)
-      int tid1 = tid0;
-      asm volatile("" : "+v"(tid1));
-      __builtin_assume(tid1 >= 0 && tid1 < Cfg<RB>::NT);
-      // ... and an opaque kernel-argument pointer: the ~30 scalar loads of stage 0 stay inside the loop instead
-      // of being hoisted into SGPRs that then spill (the parameter block is the only explicit kernel argument,
-      // so it sits at offset 0 of the kernarg segment)
-      typedef const __attribute__((address_space(4))) QmpcParams* KernargPtr;
-      KernargPtr pk = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
-      asm volatile("" : "+s"(pk));
-      const QmpcParams& PK = *(const QmpcParams*)pk;
-      solve_robot<RB, CMD, WARM>(rid, tid1, S, PK);
-      __syncthreads();  // every wave is done with this robot's LDS state
-      if (tid0 == 0) S.qnext = (int)gridDim.x + atomicAdd(P.qhead, 1);
-      __syncthreads();
-      idx = S.qnext;
-      if (idx >= nlist) break;  // uniform
-    }
+    QMPC_DRAIN_LIST(false, Cfg<RB>::NT, tid0, nlist, solve_robot<RB, QV_RECORD>(rid, tid1, S, PK))
     pool_release<RB>(S, P);
     balance_release<RB>(tid0, S, P);
   }
@@ -4232,7 +4271,7 @@ __global__ __launch_bounds__(Cfg<RB>::NT_LAUNCH, Cfg<RB>::MIN_WAVES) void qmpc_s
   const int rid = P.list[blockIdx.x];        // (< batch: the list holds robot indices of this call)
   const int tid0 = (int)threadIdx.x;
   __builtin_assume(tid0 >= 0 && tid0 < Cfg<RB>::NT);
-  solve_robot<RB, true, false>(rid, tid0, S, P);
+  solve_robot<RB, QV_CMD>(rid, tid0, S, P);
 }
 
 // JCQP alternate (update_solver_settings' use_jcqp = 1 / 2): same assembly and sweep, ADMM instead of the
@@ -4244,22 +4283,11 @@ __global__ __launch_bounds__(Cfg<RB>::NT, Cfg<RB>::MIN_WAVES) void qmpc_admm_ker
   if constexpr (!LISTED) {
     if (blockIdx.x == 0 && P.clear_counts)
       for (int k = threadIdx.x; k < QMPC_COUNTERS; k += blockDim.x) P.clear_counts[k] = 0;
-    solve_one<RB, false, false, true>((int)blockIdx.x, (int)threadIdx.x, S, P);
-  } else {  // list = queue, as in qmpc_solve_kernel
+    solve_one<RB, QV_SCHUR | QV_ADMM>((int)blockIdx.x, (int)threadIdx.x, S, P);
+  } else {
     const int nlist = *P.count;
     if ((int)blockIdx.x >= nlist) return;  // uniform
-    for (int idx = (int)blockIdx.x;;) {
-      const int rid = P.list[idx];
-      int tid1 = (int)threadIdx.x;
-      asm volatile("" : "+v"(tid1));
-      __builtin_assume(tid1 >= 0 && tid1 < Cfg<RB>::NT);
-      solve_one<RB, false, false, true>(rid, tid1, S, P);
-      __syncthreads();
-      if (threadIdx.x == 0) S.qnext = (int)gridDim.x + atomicAdd(P.qhead, 1);
-      __syncthreads();
-      idx = S.qnext;
-      if (idx >= nlist) break;  // uniform
-    }
+    QMPC_DRAIN_LIST(false, Cfg<RB>::NT, (int)threadIdx.x, nlist, solve_one<RB, QV_SCHUR | QV_ADMM>(rid, tid1, S, PK))
   }
 }
 
@@ -4271,34 +4299,20 @@ __global__ __launch_bounds__(Cfg<RB>::NT, Cfg<RB>::MIN_WAVES_A) void qmpc_sweep_
   Smem<RB>& S = *reinterpret_cast<Smem<RB>*>(qmpc_smem);
   // (a launch covers one CHUNK of the class: robots / list entries rid0 .. list_hi - 1, at most as many as the class has work items;
   //  the chunks of a call run one after the other on the caller's stream)
+  constexpr unsigned QV = QV_EVENT | QV_PRODUCER | (CMD ? QV_CMD : 0u);
   if constexpr (!LISTED) {
     if (blockIdx.x == 0 && P.clear_counts)
       for (int k = threadIdx.x; k < QMPC_COUNTERS; k += blockDim.x) P.clear_counts[k] = 0;
-    solve_one<RB, true, CMD, false, false, true>(P.rid0 + (int)blockIdx.x, (int)threadIdx.x, S, P);
+    solve_one<RB, QV>(P.rid0 + (int)blockIdx.x, (int)threadIdx.x, S, P);
   } else {
     int nlist = *P.count;
     nlist = nlist < P.list_hi ? nlist : P.list_hi;
     if (P.rid0 + (int)blockIdx.x >= nlist) return;  // uniform
-    for (int idx = P.rid0 + (int)blockIdx.x;;) {
-      const int rid = P.list[idx];
-      int tid1 = (int)threadIdx.x;
-      asm volatile("" : "+v"(tid1));
-      __builtin_assume(tid1 >= 0 && tid1 < Cfg<RB>::NT);
-      typedef const __attribute__((address_space(4))) QmpcParams* KernargPtr;
-      KernargPtr pk = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
-      asm volatile("" : "+s"(pk));
-      const QmpcParams& PK = *(const QmpcParams*)pk;
-      solve_one<RB, true, CMD, false, false, true>(rid, tid1, S, PK);
-      __syncthreads();
-      if (threadIdx.x == 0) S.qnext = P.rid0 + (int)gridDim.x + atomicAdd(P.qhead, 1);
-      __syncthreads();
-      idx = S.qnext;
-      if (idx >= nlist) break;  // uniform
-    }
+    QMPC_DRAIN_LIST(true, Cfg<RB>::NT, (int)threadIdx.x, nlist, solve_one<RB, QV>(rid, tid1, S, PK))
   }
 }
 
-// Producer of the LARGE problems (192 < n_r <= 432; solve_one<..., BIG>): list-consuming, one workgroup per CU (its block
+// Producer of the LARGE problems (192 < n_r <= 432; solve_one's QV_BIG variant): list-consuming, one workgroup per CU (its block
 // sweep uses the whole union as scratch).  Built with the 192-row class's translation unit.
 template <bool CMD>
 __global__ __launch_bounds__(Cfg<3>::NT, Cfg<3>::MIN_WAVES) void qmpc_big_kernel(const QmpcParams P) {
@@ -4308,22 +4322,7 @@ __global__ __launch_bounds__(Cfg<3>::NT, Cfg<3>::MIN_WAVES) void qmpc_big_kernel
   int nlist = *P.count;
   nlist = nlist < P.list_hi ? nlist : P.list_hi;
   if (P.rid0 + (int)blockIdx.x >= nlist) return;  // uniform
-  for (int idx = P.rid0 + (int)blockIdx.x;;) {
-    const int rid = P.list[idx];
-    int tid1 = (int)threadIdx.x;
-    asm volatile("" : "+v"(tid1));
-    __builtin_assume(tid1 >= 0 && tid1 < Cfg<3>::NT);
-    typedef const __attribute__((address_space(4))) QmpcParams* KernargPtr;
-    KernargPtr pk = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(pk));
-    const QmpcParams& PK = *(const QmpcParams*)pk;
-    solve_one<3, true, CMD, false, false, true, true>(rid, tid1, S, PK);
-    __syncthreads();
-    if (threadIdx.x == 0) S.qnext = P.rid0 + (int)gridDim.x + atomicAdd(P.qhead, 1);
-    __syncthreads();
-    idx = S.qnext;
-    if (idx >= nlist) break;  // uniform
-  }
+  QMPC_DRAIN_LIST(true, Cfg<3>::NT, (int)threadIdx.x, nlist, solve_one<3, QV_EVENT | QV_PRODUCER | QV_BIG | (CMD ? QV_CMD : 0u)>(rid, tid1, S, PK))
 }
 
 namespace {
