@@ -212,6 +212,16 @@ class EpisodeSenseView(C.Structure):
     _fields_ = [("warm", C.c_void_p), ("hold", C.c_void_p), ("warm_ticks", C.c_int), ("batch", C.c_int)]
 
 
+# qmpc_fleet_info's members (include/qmpc_fleet.h) in declaration order, and the bits of its `reason`
+FLEET_INFO_FIELDS = ("ticks", "fused_ticks", "fused_launches", "fallback_ticks", "reason")
+FLEET_REASONS = dict(terrain=1, contact=2, field=4)
+
+
+class FleetInfo(C.Structure):
+    """qmpc_fleet_info (include/qmpc_fleet.h)."""
+    _fields_ = [(n, C.c_int if n == "reason" else C.c_longlong) for n in FLEET_INFO_FIELDS]
+
+
 class LegCommand(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in LEG_F32] + [("kp_joint", C.c_float), ("kd_joint", C.c_float)]
 
@@ -372,7 +382,13 @@ ACT_SIGNATURES = {
     "qmpc_act": [_P, _I, _P, _P, _P],
     "qmpc_act_view_get": [_P, C.POINTER(ActView)],
 }
+# the closed loop of controller and plant, many ticks in one call (include/qmpc_fleet.h), same library and ABI version
+FLEET_SIGNATURES = {
+    "qmpc_fleet_run": [_P, _I, _I, _P, _P, _P, _P],
+    "qmpc_fleet_run_info": [_P, C.POINTER(FleetInfo)],
+}
 EXPORTS = list(SIGNATURES)
+FLEET_EXPORTS = list(FLEET_SIGNATURES)
 CTRL_EXPORTS = list(CTRL_SIGNATURES)
 PLANT_EXPORTS = list(PLANT_SIGNATURES)
 PLANT_VARY_EXPORTS = list(PLANT_VARY_SIGNATURES)
@@ -418,7 +434,7 @@ def load_library():
         lib = C.CDLL(LIB_PATH)
         for name, sig in {**SIGNATURES, **CTRL_SIGNATURES, **PLANT_SIGNATURES, **PLANT_VARY_SIGNATURES, **TERRAIN_SIGNATURES,
                           **CONTACT_SIGNATURES, **FIELD_SIGNATURES, **SENSE_SIGNATURES, **EPISODE_SIGNATURES,
-                          **EPISODE_SENSE_SIGNATURES, **ACT_SIGNATURES}.items():
+                          **EPISODE_SENSE_SIGNATURES, **ACT_SIGNATURES, **FLEET_SIGNATURES}.items():
             f = getattr(lib, name)
             f.argtypes, f.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
         _lib = lib
@@ -963,6 +979,14 @@ class BatchedController:
         fields = {k: (n, "<i4" if k in ("safe", "counter") else "<f4") for k, n in CTRL_VIEW_WIDTH.items()}
         return self._views("qmpc_ctrl_view_get", CtrlView, fields, ("batch", "ticks"))
 
+    def fleet_info(self):
+        """qmpc_fleet_run_info: how the ticks of rollout(..., fused=True) were served since init() -> dict(ticks,
+        fused_ticks, fused_launches, fallback_ticks, reason); reason is 0 when the last call ran fused, otherwise the OR
+        of the FLEET_REASONS bits that made it fall back to the per-tick launches.  Host-side counts: no synchronisation."""
+        info = FleetInfo()
+        self._call("qmpc_fleet_run_info", C.byref(info))
+        return {n: int(getattr(info, n)) for n in FLEET_INFO_FIELDS}
+
 
 class _DeviceArray:
     """__cuda_array_interface__ over a device pointer of the controller; keeps its owner alive while a tensor uses it."""
@@ -1468,17 +1492,19 @@ class SensedEpisodes:
                                 ("warm_ticks", "batch"))
 
 
-def _run_ticks(ctrl, who, ticks, graph, tick):
+def _run_ticks(ctrl, who, ticks, graph, tick, block=None):
     """The runner behind rollout() and rollout_sensed() (`who`: the caller's name, which starts its messages): tick()
-    `ticks` times on the current stream, or that block captured on a side stream and replayed once -> the graph, or None."""
+    `ticks` times on the current stream -- or block() once, where the caller has one call for all of them --, or that
+    block captured on a side stream and replayed once -> the graph, or None."""
     torch = ctrl.torch
     ticks = int(ticks)
     if ticks < 1:
         raise QmpcError(f"{who}: ticks must be at least 1")
 
-    def block():
-        for _ in range(ticks):
-            tick()
+    if block is None:
+        def block():
+            for _ in range(ticks):
+                tick()
 
     if not graph:
         block()
@@ -1496,7 +1522,7 @@ def _run_ticks(ctrl, who, ticks, graph, tick):
     return g
 
 
-def rollout(ctrl, plant, ticks, graph=False, actuators=None):
+def rollout(ctrl, plant, ticks, graph=False, actuators=None, fused=False):
     """`ticks` closed-loop ticks, ctrl.tick_state(plant.state, plant.motor) -> plant.step(effort), on the current
     stream, continuing from wherever the pair stands.  graph=True captures the block of `ticks` ticks into a
     torch.cuda.graph (on a side stream) and replays it once; the graph is returned for further replays, each of which
@@ -1504,6 +1530,10 @@ def rollout(ctrl, plant, ticks, graph=False, actuators=None):
     decides the MPC ticks from its own count, which replays do not advance: include/qmpc_ctrl.h) -- refused otherwise.
     actuators: a BatchedActuators of the plant, whose apply() then stands between the tick and the step (in place on
     plant.effort); None: nothing is added.
+    fused=True: the same ticks through ONE qmpc_fleet_run call (include/qmpc_fleet.h) -- everything between two MPC
+    solves in one launch, the same bits in every array; ctrl.fleet_info() tells whether the fused kernel served them or
+    the call fell back to the per-tick launches (terrain, ground-decided contact or a height field bound).  Not with
+    actuators, which stand between two stages of a tick: refused.
     -> dict(effort, state, motor, graph): the plant's own tensors, as the last tick left them."""
     def tick():
         ctrl.tick_state(plant.state, plant.motor, plant.effort)
@@ -1511,7 +1541,21 @@ def rollout(ctrl, plant, ticks, graph=False, actuators=None):
             actuators.apply()
         plant.step(plant.effort)
 
-    g = _run_ticks(ctrl, "rollout", ticks, graph, tick)
+    block = None
+    if fused:
+        if actuators is not None:
+            raise QmpcError("rollout: fused=True does not take actuators (they stand between the tick and the step)")
+        if plant.batch is None:
+            raise QmpcError("qmpc_fleet_run before init()")
+
+        def block():
+            chk = ctrl._chk
+            ctrl._call("qmpc_fleet_run", plant.batch, int(ticks),
+                       chk(plant.effort, (plant.batch, 12), ctrl.torch.float64, "effort"),
+                       chk(plant.state, (plant.batch, 16), ctrl.torch.float64, "state"),
+                       chk(plant.motor, (plant.batch, 24), ctrl.torch.float64, "motor"), ctrl._s(None))
+
+    g = _run_ticks(ctrl, "rollout", ticks, graph, tick, block)
     return dict(effort=plant.effort, state=plant.state, motor=plant.motor, graph=g)
 
 

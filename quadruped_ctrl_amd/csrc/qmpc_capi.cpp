@@ -29,6 +29,7 @@
 #include "../../include/qmpc_episode.h"  // episodes on the device: termination, respawn, result log
 #include "../../include/qmpc_episode_sense.h"  // ... on the sensor path: per-robot warm-up after a reset
 #include "../../include/qmpc_act.h"     // actuators between the controller's effort and the plant
+#include "../../include/qmpc_fleet.h"   // the closed loop of controller and plant, many ticks in one call
 #include "qmpc_device.h"
 #include "qmpc_glue.h"    // each launcher is declared once, in the header its defining file includes too:
 #include "qmpc_launch.h"  // qmpc_glue.h, qmpc_plant.h, qmpc_sense.h, qmpc_episode.h, qmpc_episode_sense.h, qmpc_act.h, and qmpc_launch.h for the rest
@@ -38,6 +39,7 @@
 #include "qmpc_episode.h"
 #include "qmpc_episode_sense.h"
 #include "qmpc_act.h"
+#include "qmpc_span.h"  // the fleet run's plan (host-only) and the span kernel's launcher
 static_assert(kLongHorizon == QMPC_LONG_HORIZON, "qmpc_plan.h and qmpc.h disagree");
 
 extern "C" size_t qmpc_smem_bytes(int rb) {
@@ -212,6 +214,7 @@ struct __attribute__((visibility("hidden"))) qmpc_ctx {
     int robot_mode = 0;                 // qmpc_ctrl_set_robot_mode (GaitCtrller::_robotMode)
     bool started = false;               // a tick or a reset has been enqueued since qmpc_ctrl_init: the schedule is fixed
     double freq = 0;                    // qmpc_ctrl_init's: the plant's dt is 1 / freq in double
+    qmpc_fleet_info fleet{};            // how qmpc_fleet_run's ticks were served since qmpc_ctrl_init (qmpc_fleet.h)
   };
   std::unique_ptr<Ctrl> ctrl;
   // reduced-order plant (qmpc_plant.h): device state for max_batch robots, made by qmpc_plant_init
@@ -1323,6 +1326,41 @@ int ctrl_reset_enqueue(qmpc_ctx* c, int batch, const uint8_t* mask_dev, hipStrea
   return QMPC_OK;
 }
 
+// The solve of an MPC tick, behind the locomotion stage that wrote the command rows (and, with the per-robot schedule, the
+// list of due robots): the per-tick path's and the fleet run's.  The caller holds the DeviceGuard and has ordered the stream.
+int ctrl_solve_enqueue(qmpc_ctx* c, int batch, hipStream_t stream) {
+  qmpc_ctx::Ctrl* k = c->ctrl.get();
+  const QmpcCtrlDev& d = k->d;
+  const bool per_robot = k->schedule == QMPC_CTRL_PER_ROBOT;
+  const bool aio = k->robot_mode == 1;  // (per_robot holds: qmpc_ctrl_set_robot_mode)
+  qmpc_command cmd{};
+  cmd.position = d.position;
+  cmd.v_world = d.v_world;
+  cmd.omega_world = d.omega_world;
+  cmd.orientation = d.orientation;
+  cmd.rpy = d.rpy;
+  cmd.r_body = d.r_cmd;
+  cmd.p_foot = d.p_foot;
+  cmd.vel_des = d.vel_des;
+  cmd.yaw_des_true = d.yaw_des_true;
+  cmd.rpy_comp = d.rpy_comp;
+  cmd.stand_traj = d.stand_traj;
+  cmd.rp_des = nullptr;  // _roll_des = _pitch_des = 0 (:112-113)
+  cmd.gait_type = d.current_gait;
+  // robot mode 1: the ten rows the horizon-10 solve reads of the robot's own table, as a 10-segment gait (qmpc_glue.hip:
+  // qmpc_ctrl_window_gait); gait_type is 9 for every due robot there
+  cmd.gait_offsets = aio ? d.mpc_offsets : d.offsets;
+  cmd.gait_durations = aio ? d.mpc_durations : d.durations;
+  cmd.gait_iteration = d.iteration;
+  cmd.world_position_desired = d.wpd;
+  cmd.x_comp_integral = d.xci;
+  cmd.body_height = 0.25f;  // _SetupCommand (:79)
+  cmd.omni_mode = 0;        // per robot through r_cmd
+  qmpc_outputs out{d.grf, nullptr, d.status, nullptr};
+  return solve_impl(c, batch, nullptr, &cmd, &out, nullptr, stream, per_robot ? d.due_list : nullptr,
+                    per_robot ? d.due_count : nullptr);
+}
+
 // A tick after its pre_work, whichever estimators that ran: the locomotion kernel, the solve by the handle's schedule, the
 // leg commands.  The caller holds the DeviceGuard and has ordered the stream.
 int ctrl_after_prework(qmpc_ctx* c, int batch, double* effort, hipStream_t stream) {
@@ -1338,35 +1376,8 @@ int ctrl_after_prework(qmpc_ctx* c, int batch, double* effort, hipStream_t strea
   // per-robot schedule: nothing depends on T -- every tick enqueues the solve over the list of due robots the locomotion
   // kernel has just built (d.due_list, d.due_count[0]); a tick on which nobody is due costs launches that find no entry
   const bool mpc_tick = (++k->ticks % 13 == 0) || per_robot;
-  if (mpc_tick) {
-    qmpc_command cmd{};
-    cmd.position = d.position;
-    cmd.v_world = d.v_world;
-    cmd.omega_world = d.omega_world;
-    cmd.orientation = d.orientation;
-    cmd.rpy = d.rpy;
-    cmd.r_body = d.r_cmd;
-    cmd.p_foot = d.p_foot;
-    cmd.vel_des = d.vel_des;
-    cmd.yaw_des_true = d.yaw_des_true;
-    cmd.rpy_comp = d.rpy_comp;
-    cmd.stand_traj = d.stand_traj;
-    cmd.rp_des = nullptr;  // _roll_des = _pitch_des = 0 (:112-113)
-    cmd.gait_type = d.current_gait;
-    // robot mode 1: the ten rows the horizon-10 solve reads of the robot's own table, as a 10-segment gait (qmpc_glue.hip:
-    // qmpc_ctrl_window_gait); gait_type is 9 for every due robot there
-    cmd.gait_offsets = aio ? d.mpc_offsets : d.offsets;
-    cmd.gait_durations = aio ? d.mpc_durations : d.durations;
-    cmd.gait_iteration = d.iteration;
-    cmd.world_position_desired = d.wpd;
-    cmd.x_comp_integral = d.xci;
-    cmd.body_height = 0.25f;  // _SetupCommand (:79)
-    cmd.omni_mode = 0;        // per robot through r_cmd
-    qmpc_outputs out{d.grf, nullptr, d.status, nullptr};
-    if (const int rc = solve_impl(c, batch, nullptr, &cmd, &out, nullptr, stream, per_robot ? d.due_list : nullptr,
-                                  per_robot ? d.due_count : nullptr))
-      return rc;
-  }
+  if (mpc_tick)
+    if (const int rc = ctrl_solve_enqueue(c, batch, stream)) return rc;
   HIP_TRY(c, qmpc_launch_ctrl_legcmd(&d, effort, batch, stream));
   return QMPC_OK;
 }
@@ -1422,6 +1433,7 @@ int qmpc_ctrl_init(qmpc_handle c, int batch, double freq, const double pid[4], v
   k->schedule = QMPC_CTRL_LOCKSTEP;
   k->robot_mode = 0;
   k->started = false;
+  k->fleet = qmpc_fleet_info{};
   return QMPC_OK;
 }
 
@@ -1889,6 +1901,72 @@ int qmpc_field_view_get(qmpc_handle c, qmpc_field_view* v) {
   v->place = k->field.place;
   v->flags = k->field_flags;
   v->batch = k->batch;
+  return QMPC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
+// Fleet run (include/qmpc_fleet.h): qmpc_ctrl_tick_state -> qmpc_plant_step, `ticks` times, with everything between two
+// solves in one launch.  The plan is qmpc_span.h's, the kernel qmpc_span.hip's.
+extern "C" {
+
+int qmpc_fleet_run(qmpc_handle c, int batch, int ticks, double* effort, double* state, double* motor, void* stream_) {
+  if (const int rc = plant_check(c, batch)) return rc;
+  if (ticks < 1 || !effort || !state || !motor) return QMPC_ERR_ARG;
+  qmpc_ctx::Ctrl* k = c->ctrl.get();
+  qmpc_ctx::Plant* pl = c->plant.get();
+  const int reason = (pl->terrain.rows ? QMPC_FLEET_TERRAIN : 0) | (pl->contact.flags ? QMPC_FLEET_CONTACT : 0) |
+                     (pl->field.z ? QMPC_FLEET_FIELD : 0);
+  // (the counts follow what has been enqueued: a call refused here, or one that stops half way, counts no tick it did not
+  //  enqueue)
+  if (reason) {
+    // what the span kernel does not cover: the per-tick calls themselves, so the launches are theirs exactly
+    for (int i = 0; i < ticks; ++i) {
+      if (const int rc = qmpc_ctrl_tick_state(c, batch, state, motor, effort, stream_)) return rc;
+      k->fleet.reason = reason;  // (the call has enqueued something: it is the last call now)
+      if (const int rc = qmpc_plant_step(c, batch, effort, state, motor, stream_)) return rc;
+      ++k->fleet.ticks;
+      ++k->fleet.fallback_ticks;
+    }
+    return QMPC_OK;
+  }
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  k->started = true;
+  k->fleet.reason = 0;
+  const bool per_robot = k->schedule == QMPC_CTRL_PER_ROBOT;
+  const QmpcPlantStepArgs P = plant_step_args(c, batch, effort, state, motor);
+  QmpcSpanArgs A{};
+  A.C = k->d;
+  A.g = QmpcLegGeom{c->leg_geom[0], c->leg_geom[1], c->leg_geom[2], c->leg_geom[3]};
+  A.S = P.S;
+  A.K = P.K;
+  A.effort = effort;
+  A.state = state;
+  A.motor = motor;
+  A.n = P.n;
+  A.V = P.V;
+  A.build_list = per_robot ? 1 : 0;
+  for (const SpanLaunch& l : plan_spans(k->ticks, ticks, per_robot)) {
+    // (a kernel, not a memset node: see fill_ints)
+    if (l.reset_due) HIP_TRY(c, fill_ints(k->d.due_count, 1, 0, q.stream));
+    HIP_TRY(c, qmpc_launch_span(&A, k->robot_mode, pl->bound, pl->stats_on, l.first_at_c, l.ticks, l.last_after_l, q.stream));
+    // T follows the locomotion stages as they are enqueued, in front of the solve that can still fail (ctrl_after_prework)
+    k->ticks += l.locos;
+    k->fleet.ticks += l.locos;
+    k->fleet.fused_ticks += l.locos;
+    ++k->fleet.fused_launches;
+    if (l.solve)
+      if (const int rc = ctrl_solve_enqueue(c, batch, q.stream)) return rc;
+  }
+  return QMPC_OK;
+}
+
+int qmpc_fleet_run_info(qmpc_handle c, qmpc_fleet_info* out) {
+  if (!c || !out) return QMPC_ERR_ARG;
+  if (!ctrl_ready(c)) return QMPC_ERR_STATE;
+  *out = c->ctrl->fleet;
   return QMPC_OK;
 }
 

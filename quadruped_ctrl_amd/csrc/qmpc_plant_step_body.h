@@ -21,7 +21,11 @@
 // robot's place row is loaded once beside the terrain row (T.rows may be null: the field alone), every height is the
 // summed surface, and the contact normal is this lane's own foot's, from the taps of its touch-down.  VARY = STATS =
 // TERRAIN = false reads nothing of V or T and is the plain step; FIELD = false reads nothing of Fd.
-  const int t = blockIdx.x * 256 + threadIdx.x;
+// QMPC_PLANT_STEP_LANE: the lane's index where the including file's workgroups are not 256 lanes (qmpc_span.hip).
+#ifndef QMPC_PLANT_STEP_LANE
+#define QMPC_PLANT_STEP_LANE (blockIdx.x * 256 + threadIdx.x)
+#endif
+  const int t = QMPC_PLANT_STEP_LANE;
   const bool live = t < n;
   const int tt = live ? t : n - 1;
   const int b = tt >> 2, leg = tt & 3;

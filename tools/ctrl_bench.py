@@ -67,9 +67,15 @@ stream supplies the joint rates the launch reads --; --delay D gives the ring D 
 period's last launch), us_added_per_period their difference, us_per_act_median the event pair around the launch itself.
 Without --actuators the stage is never initialised and the loop enqueues what it enqueued before.
 
+--fused (with --source plant) runs the loop through qmpc_fleet_run (include/qmpc_fleet.h: everything between two MPC
+solves in one launch); --graph adds a captured 13-tick block, replayed.  Either one switches to timing in blocks of ticks
+(run_blocks: the per-tick windows cut at the same places; --warmup a multiple of 13), so `--source plant --graph` is the
+per-tick path's figure to hold `--source plant --fused --graph` against.
+
     python tools/ctrl_bench.py [--batches 1024,4096,16384] [--cycles 8] [--warmup 26] [--schedule lockstep|per_robot]
                                [--stagger] [--robot-mode 0|1] [--source imu|state|plant|sensor] [--vary] [--terrain] [--contact] [--field]
-                               [--noise] [--episodes] [--every K] [--warm W] [--actuators] [--delay D] [--repeats R] [--out FILE]
+                               [--noise] [--episodes] [--every K] [--warm W] [--actuators] [--delay D] [--repeats R]
+                               [--fused] [--graph] [--out FILE]
 """
 import argparse
 import json
@@ -82,8 +88,69 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def run_blocks(ctrl, plant, B, cycles, warmup, schedule, stagger, robot_mode, fused, graph):
+    """--source plant with --fused and / or --graph: the closed loop timed in BLOCKS of ticks (HIP events around rollout()
+    calls), because a fused span has no event between its ticks.  The windows are the per-tick report's, cut at the same
+    places: in lockstep, per 13-tick period, the twelve ticks without a solve in one block (us_per_nonmpc_period: block /
+    12, tick + step) and the MPC tick in another (us_per_mpc_period: tick + step; the per-tick report's us_per_mpc_tick
+    plus its plant step); then whole 13-tick periods in one block each (us_per_13_tick_cycle, robot_ticks_per_s); with
+    --graph the same 13-tick block captured once and replayed (us_per_13_tick_cycle_graph, robot_ticks_per_s_graph).
+    With the per-robot schedule every tick solves and only the whole blocks are reported."""
+    import torch
+    from quadruped_ctrl_amd.binding import rollout
+    if warmup % 13:
+        raise SystemExit("--fused / --graph: --warmup must be a multiple of 13 (the blocks are cut at the MPC ticks)")
+    go = lambda n, g=False: rollout(ctrl, plant, n, graph=g, fused=fused)
+    pair = lambda: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    med = lambda evs: float(np.median([a.elapsed_time(b) * 1e3 for a, b in evs]))
+    go(warmup)
+    lockstep = schedule == "lockstep" and not stagger and robot_mode == 0
+    res = {"batch": B, "source": "plant", "schedule": schedule, "stagger": bool(stagger), "robot_mode": robot_mode,
+           "fused": bool(fused), "cycles_timed": cycles}
+    if lockstep:
+        non, mpc = [], []
+        for _ in range(cycles):
+            a, b = pair()
+            a.record(); go(12); b.record()
+            non.append((a, b))
+            a, b = pair()
+            a.record(); go(1); b.record()
+            mpc.append((a, b))
+        torch.cuda.synchronize()
+        res.update({"us_per_nonmpc_period": round(med(non) / 12, 2), "us_per_mpc_period": round(med(mpc), 2)})
+    whole = []
+    for _ in range(cycles):
+        a, b = pair()
+        a.record(); go(13); b.record()
+        whole.append((a, b))
+    torch.cuda.synchronize()
+    us13 = med(whole)
+    res.update({"us_per_13_tick_cycle": round(us13, 1), "robot_ticks_per_s": float(f"{13 * B / (us13 * 1e-6):.4g}")})
+    if graph:
+        g = go(13, True)["graph"]
+        torch.cuda.synchronize()
+        reps = []
+        for _ in range(cycles):
+            a, b = pair()
+            a.record(); g.replay(); b.record()
+            reps.append((a, b))
+        torch.cuda.synchronize()
+        us13g = med(reps)
+        res.update({"us_per_13_tick_cycle_graph": round(us13g, 1),
+                    "robot_ticks_per_s_graph": float(f"{13 * B / (us13g * 1e-6):.4g}")})
+    info, v = ctrl.fleet_info(), ctrl.view()
+    pz = plant.view()["p"][:, 2]
+    res.update({"fleet_info": info, "body_height_min": round(float(pz.min().item()), 4),
+                "body_height_max": round(float(pz.max().item()), 4),
+                "status_error_robots": int((torch.from_numpy(ctrl.read("status")[:, 0]) & 47 != 0).sum()),
+                "all_finite": bool(torch.isfinite(plant.effort).all().item()), "latched": int((v["safe"] == 0).sum())})
+    ctrl.close()
+    return res
+
+
 def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, source="imu", vary=False, noise=False, terrain=False,
-        contact=False, field=False, episodes=False, every=1, warm=50, actuators=False, delay=0, repeats=3):
+        contact=False, field=False, episodes=False, every=1, warm=50, actuators=False, delay=0, repeats=3, fused=False,
+        graph=False):
     import torch
     from quadruped_ctrl_amd import workloads as W
     from quadruped_ctrl_amd.binding import BatchedController
@@ -210,6 +277,8 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
                 plant.step(eff)
             if sensors is not None:
                 sensors.sense()
+    if fused or graph:
+        return run_blocks(ctrl, plant, B, cycles, warmup, schedule, stagger, robot_mode, fused, graph)
     held_seen = []
 
     hold_flags = sensed.view()["hold"] if sensed is not None else None
@@ -374,8 +443,12 @@ def main():
     ap.add_argument("--actuators", action="store_true")
     ap.add_argument("--delay", type=int, default=0)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--fused", action="store_true")
+    ap.add_argument("--graph", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if (a.fused or a.graph) and (a.source != "plant" or a.episodes or a.actuators):
+        ap.error("--fused and --graph go with --source plant, without --episodes and --actuators")
     if a.vary and a.source not in ("plant", "sensor"):
         ap.error("--vary needs --source plant or sensor")
     if a.terrain and a.source not in ("plant", "sensor"):
@@ -403,7 +476,7 @@ def main():
     out = []
     for B in [int(x) for x in a.batches.split(",")]:
         r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source, a.vary, a.noise, a.terrain, a.contact, a.field,
-                a.episodes, a.every, a.warm, a.actuators, a.delay, a.repeats)
+                a.episodes, a.every, a.warm, a.actuators, a.delay, a.repeats, a.fused, a.graph)
         print(json.dumps(r), flush=True)
         out.append(r)
     if a.out:
