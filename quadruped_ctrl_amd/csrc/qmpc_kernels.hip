@@ -18,7 +18,7 @@
 //     and every B_p^T W B_q has a closed form in the 3x3 blocks
 //     M_b = I_w^-1 [r_b]x, N_b = R_yaw^T M_b -- no 13h x 12h B_qp is ever formed
 //     (the reference multiplies it densely, SolverMPC.cpp:395).
-//   * inversion by symmetric Gauss-Jordan sweeps, two pivots per barrier; the
+//   * inversion by symmetric Gauss-Jordan sweeps, two pivots per barrier (four in class 1); the
 //     pivot columns are held one value per lane and broadcast INSIDE the fp64
 //     fmac (DP-ALU DPP, row_newbcast) instead of being re-read from LDS by every
 //     lane; in class 1 the wave that owns the next pivot pair inverts the 2x2
@@ -96,6 +96,28 @@ template <int J0>
 __device__ __forceinline__ void fmac4_rowbcast(double (&a)[16], double c, double u) {
   asm volatile(
       "s_nop 1\n\t"
+      "v_fmac_f64_dpp %0, %4, %5 row_newbcast:%6 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %1, %4, %5 row_newbcast:%7 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %2, %4, %5 row_newbcast:%8 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f64_dpp %3, %4, %5 row_newbcast:%9 row_mask:0xf bank_mask:0xf"
+      : "+v"(a[J0]), "+v"(a[J0 + 1]), "+v"(a[J0 + 2]), "+v"(a[J0 + 3])
+      : "v"(c), "v"(u), "n"(J0), "n"(J0 + 1), "n"(J0 + 2), "n"(J0 + 3));
+}
+
+// ... and for N = 4 or 2 accumulators from a[J0] on where c is the result of an LDS LOAD that no vector instruction has written
+// since: the hazard the s_nop covers (a vector write of the DPP operand in the two wait states before) cannot arise, and the
+// producing wave of the 64-row sweep, whose instruction stream paces the step, issues sixteen of these blocks per step
+template <int J0, int N>
+__device__ __forceinline__ void fmac_rowbcast_loaded(double (&a)[16], double c, double u) {
+  static_assert(N == 2 || N == 4, "block of 2 or 4 columns");
+  if constexpr (N == 2)
+    asm volatile(
+        "v_fmac_f64_dpp %0, %2, %3 row_newbcast:%4 row_mask:0xf bank_mask:0xf\n\t"
+        "v_fmac_f64_dpp %1, %2, %3 row_newbcast:%5 row_mask:0xf bank_mask:0xf"
+        : "+v"(a[J0]), "+v"(a[J0 + 1])
+        : "v"(c), "v"(u), "n"(J0), "n"(J0 + 1));
+  else
+  asm volatile(
       "v_fmac_f64_dpp %0, %4, %5 row_newbcast:%6 row_mask:0xf bank_mask:0xf\n\t"
       "v_fmac_f64_dpp %1, %4, %5 row_newbcast:%7 row_mask:0xf bank_mask:0xf\n\t"
       "v_fmac_f64_dpp %2, %4, %5 row_newbcast:%8 row_mask:0xf bank_mask:0xf\n\t"
@@ -564,6 +586,11 @@ struct Cfg {
   // waves 1..NHELP take a share of the stored events whenever there are enough of them to be worth two barriers
   // (the larger classes: long active-set runs, and seven or eleven waves with nothing else to do)
   static constexpr int NHELP = C1 ? 0 : 3;
+  // pivot pairs the sweep publishes per barrier.  Two in the four-per-CU 64-row class: its sweep storage (+4.1 KB) stays under
+  // the solve's.  The five-per-CU class keeps one: the second set would make the sweep storage its largest LDS phase and cost
+  // the fifth workgroup of a CU, and its producing wave would hold eight more loaded values through the step within 96 VGPRs
+  // (the two-pair cadence was not built for it)
+  static constexpr int SWP_PAIRS = (RB == 1) ? 2 : 1;
   // event records with the lane's entries stored adjacently (16-byte loads): the classes whose robots hold many
   // events; the record size is the same (NP and KS are multiples of 64 there)
   static constexpr bool PAIRED = (RB == 2 || RB == 3);
@@ -619,8 +646,10 @@ struct Smem {
         double s[3][C::HMAX * 12];
       } a;
       struct Swp {  // sweep + unconstrained minimiser (stages 2-4)
-        alignas(16) double colbuf[2][2][C::NP + 2];  // [parity][column of the pair][row]
-        double ubuf[2][2][C::NP];  // class 1: F columns (pivot-row correction folded in), same buffering
+        // [parity of the step][2 * pair of the step + column of the pair][row]: a step is one pivot pair, two in the class
+        // that publishes two pairs per barrier (C::SWP_PAIRS)
+        alignas(16) double colbuf[2][2 * C::SWP_PAIRS][C::NP + 2];
+        double ubuf[2][2 * C::SWP_PAIRS][C::NP];  // 64-row classes: F columns (pivot-row correction folded in), same buffering
         double g[C::NP];
         double part[4][C::NP];
       } w;
@@ -664,8 +693,21 @@ struct Smem {
       PK.dbg_clk[(size_t)(rid + PK.batch) * 16 + (k)] = clock64();                                    \
     }                                                                                                     \
   } while (0)
+// ... and of the 64-row classes' sweep, whose step is paced by the wave that PRODUCES the next step's pivot pairs: that wave's lane 0
+// stamps the step that starts at pivot k0 (a step inside a block of sixteen columns: the producing wave does not change), same
+// row, slots 0..3 -- 0 the barrier is passed, 1 the step's LDS loads are back, 2 its last store is issued, 3 the next barrier is
+// passed: tools/sweep_pair_phase.py
+#define QMPC_PROD_TICK(k, dep)                                                                            \
+  do {                                                                                                    \
+    if (PK.dbg_clk && lane == 0 && k0 == QMPC_SWEEP_STAMP) {                                              \
+      double dep__ = (dep);                                                                               \
+      asm volatile("" ::"v"(dep__));                                                                      \
+      PK.dbg_clk[(size_t)(rid + PK.batch) * 16 + (k)] = clock64();                                        \
+    }                                                                                                     \
+  } while (0)
 #else
 #define QMPC_STEP_TICK(k, dep) do { } while (0)
+#define QMPC_PROD_TICK(k, dep) do { } while (0)
 #endif
 
 // profiling build (-DQMPC_FIXED_STAMP): shader-clock stamps of EVERY wave of the (four-wave) workgroup in front of the sweep, taken by
@@ -1980,7 +2022,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
   QMPC_STOP(2, a);
 
   // ------------------------------------------------------------ stage 3
-  // Symmetric Gauss-Jordan sweeps, TWO pivots per barrier: a <- -H^-1.
+  // Symmetric Gauss-Jordan sweeps, TWO pivots per barrier (FOUR, two pairs, in the four-per-CU 64-row class): a <- -H^-1.
   // Pivot columns k0 = 2m, k1 = k0+1 live in column group k0 / CW, registers
   // k0 % CW and +1, and are broadcast through a double-buffered pair of LDS
   // vectors (row k == column k by symmetry).  Every thread applies pivot k0 to
@@ -2022,12 +2064,13 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
     // the pivot arithmetic in stages, so that the producing wave can slot the rest
     // of its update into the latencies of this dependent chain
     double pd0, pe, pd1, pdet, px, pc0, pc1, pm0, pm1;
-    auto prod_read = [&](double c0n, double c1n, int k0n) __attribute__((always_inline)) {
+    // (kd: the pair's rows for the diagonal's unit vectors -- k0n, or no row at all for a pair in the identity padding)
+    auto prod_read = [&](double c0n, double c1n, int k0n, int kd) __attribute__((always_inline)) {
       pd0 = readlane_f64(c0n, k0n);
       pe = readlane_f64(c0n, k0n + 1);   // A[k1][k0]   (k1 == n: identity padding column, a no-op pivot)
       pd1 = readlane_f64(c1n, k0n + 1);
-      pm0 = (i == k0n) ? 1.0 : 0.0;
-      pm1 = (i == k0n + 1) ? 1.0 : 0.0;
+      pm0 = (i == kd) ? 1.0 : 0.0;
+      pm1 = (i == kd + 1) ? 1.0 : 0.0;
       pc0 = c0n - pm0;  // C'
       pc1 = c1n - pm1;
     };
@@ -2054,14 +2097,33 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       pnf0 = pt0 * px;
       pnf1 = pt1 * px;
     };
-    auto prod_store = [&](int mn) __attribute__((always_inline)) {
-      Sw.colbuf[mn & 1][0][i] = pc0;
-      Sw.colbuf[mn & 1][1][i] = pc1;
-      Sw.ubuf[mn & 1][0][i] = pnf0;
-      Sw.ubuf[mn & 1][1][i] = pnf1;
+    auto prod_store = [&](int par, int pair) __attribute__((always_inline)) {
+      Sw.colbuf[par & 1][2 * pair][i] = pc0;
+      Sw.colbuf[par & 1][2 * pair + 1][i] = pc1;
+      Sw.ubuf[par & 1][2 * pair][i] = pnf0;
+      Sw.ubuf[par & 1][2 * pair + 1][i] = pnf1;
+    };
+    // TWO PAIRS PER BARRIER (C::SWP_PAIRS == 2).  A step is the pairs (k0, k0+1) and (k0+2, k0+3): one group of four registers of
+    // the wave that owns them.  That wave reads the SECOND pair's pivot block before anybody else has seen the first pair: it
+    // applies the first pair to those two columns itself, from registers -- the pivot-column entries of the two rows by readlane
+    // of C', times its own -F': the operands the DPP fmac of the bulk update takes, so the same bits -- and the bulk update of the
+    // next step leaves these two columns out for the first pair.  Everything else is the one-pair step twice: per element the
+    // same updates in the same order.
+    double ps00, ps01, ps10, ps11;  // C'[row of the group's third / fourth column][column 0 / 1 of its first pair]
+    auto prod_rows = [&](int k2) __attribute__((always_inline)) {
+      ps00 = readlane_f64(pc0, k2);
+      ps01 = readlane_f64(pc1, k2);
+      ps10 = readlane_f64(pc0, k2 + 1);
+      ps11 = readlane_f64(pc1, k2 + 1);
+    };
+    auto prod_own = [&](double& c2, double& c3) __attribute__((always_inline)) {
+      c2 = __builtin_fma(ps00, pnf0, c2);
+      c3 = __builtin_fma(ps10, pnf0, c3);
+      c2 = __builtin_fma(ps01, pnf1, c2);
+      c3 = __builtin_fma(ps11, pnf1, c3);
     };
     if (c == 0) {
-      prod_read(a[0], a[1], 0);
+      prod_read(a[0], a[1], 0, 0);
       a[0] = __builtin_fma(-2.0, pm0, a[0]);  // the pivot block's diagonal: 2 I - P^-1 -> -P^-1
       a[1] = __builtin_fma(-2.0, pm1, a[1]);
       prod_det();
@@ -2070,10 +2132,25 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       prod_newton();
       prod_newton();
       prod_fg();
-      prod_store(0);
+      prod_store(0, 0);
+      if constexpr (C::SWP_PAIRS == 2) {
+        prod_rows(2);
+        prod_own(a[2], a[3]);
+        prod_read(a[2], a[3], 2, 2 < n ? 2 : -2);
+        a[2] = __builtin_fma(-2.0, pm0, a[2]);
+        a[3] = __builtin_fma(-2.0, pm1, a[3]);
+        prod_det();
+        prod_rcp();
+        prod_adj();
+        prod_newton();
+        prod_newton();
+        prod_fg();
+        prod_store(0, 1);
+      }
     }
     __syncthreads();
 #define QMPC_PIN __builtin_amdgcn_sched_barrier(0)
+    asm volatile("; qmpc sweep begin");  // (comment-only markers around the loop: tools/sweep_shape.py)
 #pragma unroll 1
     for (int kb = 0; kb < 4; ++kb) {
       // Issue priority falls as the sweep advances.  Among equal priorities the SIMD
@@ -2085,25 +2162,146 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       else if (kb <= 1 || hfloor >= 2) __builtin_amdgcn_s_setprio(2);
       else if (kb == 2) __builtin_amdgcn_s_setprio(1);
       else __builtin_amdgcn_s_setprio(0);
-      StaticFor<0, CW / 2>::run([&](auto pc) __attribute__((always_inline)) {
+      if constexpr (C::SWP_PAIRS == 2) StaticFor<0, CW / 4>::run([&](auto sc) __attribute__((always_inline)) {
+        // the step's columns are registers r0 .. r0+3 of wave kb; the next step's, GN .. GN+3 of wave kbn
+        constexpr int r0 = 4 * decltype(sc)::value;
+        constexpr bool SAME = r0 + 4 < CW;  // the wave that produces the next step owns this one
+        constexpr int GN = SAME ? r0 + 4 : 0, G1 = (GN + 4) % 16, G2 = (GN + 8) % 16;  // (the fourth group is r0's)
+        const int k0 = kb * CW + r0;
+        if (k0 < n) {
+          const int par = (k0 >> 2) & 1;
+          const int kbn = SAME ? kb : kb + 1;
+          if (c == kbn) QMPC_PROD_TICK(0, 0.0);
+          // lane l holds pivot-column entry c*16 + l%16 (the 16 columns of this wave); u = -F'_i
+          const double* cb = &Sw.colbuf[par][0][c * CW + (lane & 15)];
+          const double* ub = &Sw.ubuf[par][0][i];
+          constexpr int CLD = C::NP + 2, ULD = C::NP;
+          if (k0 + 4 < n && c == kbn) {
+            // this wave owns the next step's two pairs (so this step has both of its own): every vector of the step behind ONE
+            // wait, the next group brought up to date with both pairs, then the two pivot-block inverses one after the other,
+            // interleaved with the wave's other twelve columns
+            asm volatile("; qmpc sweep producer begin");
+            const double cA0 = cb[0], cA1 = cb[CLD], cB0 = cb[2 * CLD], cB1 = cb[3 * CLD];
+            const double uA0 = ub[0], uA1 = ub[ULD], uB0 = ub[2 * ULD], uB1 = ub[3 * ULD];
+            asm volatile("" ::"v"(cA0), "v"(cA1), "v"(cB0), "v"(cB1), "v"(uA0), "v"(uA1), "v"(uB0), "v"(uB1));  // (one wait for all)
+            QMPC_PROD_TICK(1, cA0 + cA1 + cB0 + cB1 + uA0 + uA1 + uB0 + uB1);
+            fmac_rowbcast_loaded<GN, 4>(a, cA0, uA0);
+            fmac_rowbcast_loaded<GN, 4>(a, cA1, uA1);
+            fmac_rowbcast_loaded<GN, 4>(a, cB0, uB0);
+            fmac_rowbcast_loaded<GN, 4>(a, cB1, uB1);
+            QMPC_PIN;
+            prod_read(a[GN], a[GN + 1], k0 + 4, k0 + 4);
+            a[GN] = __builtin_fma(-2.0, pm0, a[GN]);
+            a[GN + 1] = __builtin_fma(-2.0, pm1, a[GN + 1]);
+            prod_rows(k0 + 6);
+            QMPC_PIN;
+            fmac_rowbcast_loaded<G1, 4>(a, cA0, uA0);
+            QMPC_PIN;
+            prod_det();
+            prod_rcp();
+            prod_adj();
+            QMPC_PIN;
+            fmac_rowbcast_loaded<G1, 4>(a, cA1, uA1);
+            QMPC_PIN;
+            prod_newton();
+            QMPC_PIN;
+            fmac_rowbcast_loaded<G1, 4>(a, cB0, uB0);
+            QMPC_PIN;
+            prod_newton();
+            QMPC_PIN;
+            fmac_rowbcast_loaded<G1, 4>(a, cB1, uB1);
+            QMPC_PIN;
+            prod_fg();
+            prod_own(a[GN + 2], a[GN + 3]);
+            QMPC_PIN;
+            fmac_rowbcast_loaded<G2, 4>(a, cA0, uA0);
+            QMPC_PIN;
+            prod_store(par + 1, 0);
+            // (k0 + 6 >= n: the second pair lies in the identity padding -- its block is I, its C' zero, nobody loads what is
+            //  stored for it -- and only the diagonal's correction must not happen: no row takes it)
+            prod_read(a[GN + 2], a[GN + 3], k0 + 6, k0 + 6 < n ? k0 + 6 : -2);
+            a[GN + 2] = __builtin_fma(-2.0, pm0, a[GN + 2]);
+            a[GN + 3] = __builtin_fma(-2.0, pm1, a[GN + 3]);
+            QMPC_PIN;
+            fmac_rowbcast_loaded<G2, 4>(a, cA1, uA1);
+            QMPC_PIN;
+            prod_det();
+            prod_rcp();
+            prod_adj();
+            QMPC_PIN;
+            fmac_rowbcast_loaded<G2, 4>(a, cB0, uB0);
+            QMPC_PIN;
+            prod_newton();
+            QMPC_PIN;
+            fmac_rowbcast_loaded<G2, 4>(a, cB1, uB1);
+            QMPC_PIN;
+            prod_newton();
+            QMPC_PIN;
+            // this step's own group: where the wave owns it too, its third and fourth column carry the first pair already
+            if constexpr (SAME) {
+              fmac_rowbcast_loaded<r0, 2>(a, cA0, uA0);
+              fmac_rowbcast_loaded<r0, 2>(a, cA1, uA1);
+            } else {
+              fmac_rowbcast_loaded<r0, 4>(a, cA0, uA0);
+              fmac_rowbcast_loaded<r0, 4>(a, cA1, uA1);
+            }
+            QMPC_PIN;
+            prod_fg();
+            QMPC_PIN;
+            fmac_rowbcast_loaded<r0, 4>(a, cB0, uB0);
+            QMPC_PIN;
+            prod_store(par + 1, 1);
+            QMPC_PROD_TICK(2, 0.0);
+            QMPC_PIN;
+            fmac_rowbcast_loaded<r0, 4>(a, cB1, uB1);
+            asm volatile("; qmpc sweep producer end");
+          } else if (c * CW < n) {
+            // (a column group that lies entirely in the identity padding never changes:
+            //  its pivot-column entries are zero)
+            const double cA0 = cb[0], cA1 = cb[CLD], uA0 = ub[0], uA1 = ub[ULD];
+            if (c == kb) {  // the step's owner applied the first pair to its third and fourth column when it read the second
+              fmac_range_rowbcast<0, r0>(a, cA0, uA0);
+              fmacn_rowbcast<r0, 2>(&a[r0], cA0, uA0);
+              fmac_range_rowbcast<r0 + 4, CW>(a, cA0, uA0);
+              fmac_range_rowbcast<0, r0>(a, cA1, uA1);
+              fmacn_rowbcast<r0, 2>(&a[r0], cA1, uA1);
+              fmac_range_rowbcast<r0 + 4, CW>(a, cA1, uA1);
+            } else {
+              fmac16_rowbcast(a, cA0, uA0);
+              fmac16_rowbcast(a, cA1, uA1);
+            }
+            if (k0 + 2 < n) {  // (an odd number of pairs: the last step is one pair)
+              const double cB0 = cb[2 * CLD], cB1 = cb[3 * CLD], uB0 = ub[2 * ULD], uB1 = ub[3 * ULD];
+              fmac16_rowbcast(a, cB0, uB0);
+              fmac16_rowbcast(a, cB1, uB1);
+            }
+          }
+          __syncthreads();
+          if (c == kbn) QMPC_PROD_TICK(3, 0.0);
+        }
+      });
+      else StaticFor<0, CW / 2>::run([&](auto pc) __attribute__((always_inline)) {
         constexpr int r0 = 2 * decltype(pc)::value;
         constexpr int rn0 = (r0 + 2 < CW) ? r0 + 2 : 0, rn1 = rn0 + 1;
         constexpr int G0 = 4 * (rn0 / 4), G1 = (G0 + 4) % 16, G2 = (G0 + 8) % 16, G3 = (G0 + 12) % 16;
         const int k0 = kb * CW + r0;
         if (k0 < n) {
           const int m = k0 >> 1;
+          const int kbn = (r0 + 2 < CW) ? kb : kb + 1;
+          if (c == kbn) QMPC_PROD_TICK(0, 0.0);
           // lane l holds pivot-column entry c*16 + l%16 (the 16 columns of this wave)
           const double cv0 = Sw.colbuf[m & 1][0][c * CW + (lane & 15)];
           const double cv1 = Sw.colbuf[m & 1][1][c * CW + (lane & 15)];
           const double nu0 = Sw.ubuf[m & 1][0][i], nu1 = Sw.ubuf[m & 1][1][i];  // -F'_i0, -F'_i1
-          const int kbn = (r0 + 2 < CW) ? kb : kb + 1;
+          if (c == kbn) QMPC_PROD_TICK(1, cv0 + cv1 + nu0 + nu1);
           if (k0 + 2 < n && c == kbn) {
             // this wave owns the next pivot pair: its two columns first, then the
             // pivot-block inverse interleaved with the other twelve columns
+            asm volatile("; qmpc sweep producer begin");
             fmac4_rowbcast<G0>(a, cv0, nu0);
             fmac4_rowbcast<G0>(a, cv1, nu1);
             QMPC_PIN;
-            prod_read(a[rn0], a[rn1], k0 + 2);
+            prod_read(a[rn0], a[rn1], k0 + 2, k0 + 2);
             a[rn0] = __builtin_fma(-2.0, pm0, a[rn0]);
             a[rn1] = __builtin_fma(-2.0, pm1, a[rn1]);
             QMPC_PIN;
@@ -2127,9 +2325,11 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
             QMPC_PIN;
             fmac4_rowbcast<G3>(a, cv0, nu0);
             QMPC_PIN;
-            prod_store(m + 1);
+            prod_store(m + 1, 0);
+            QMPC_PROD_TICK(2, 0.0);
             QMPC_PIN;
             fmac4_rowbcast<G3>(a, cv1, nu1);
+            asm volatile("; qmpc sweep producer end");
           } else if (c * CW < n) {
             // (a column group that lies entirely in the identity padding never changes:
             //  its pivot-column entries are zero)
@@ -2137,9 +2337,11 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
             fmac16_rowbcast(a, cv1, nu1);
           }
           __syncthreads();
+          if (c == kbn) QMPC_PROD_TICK(3, 0.0);
         }
       });
     }
+    asm volatile("; qmpc sweep end");
 #undef QMPC_PIN
   } else {
     // Larger classes: a column group spans several waves (and in the 96-row class waves straddle two

@@ -1,0 +1,169 @@
+"""GPU suite (-m gpu): the sweep of the 64-row classes (stage 3 of the solve kernels) at the smallest shapes at which its
+cadence changes path.  The four-per-CU class publishes TWO pivot pairs per barrier (a step is four columns, one register
+group of the wave that owns them), the five-per-CU class one; the chain, the producing wave of a block of sixteen columns, the
+order of the updates of every element and every floating-point expression are those of the one-pair sweep, so every figure
+below stays where the parent commit's build left it, bit for bit.
+
+Inputs.  Batches of 16 robots at h = 10: robots of configs[4] (random contact tables, tilted bodies, feet at different
+heights) thinned to exactly nst stance foot-steps, the first one kept (as test_gpu_engine_iteration.py's "stairs" thins).
+The reduced size is n = 3 nst:
+
+  nst  n   what it exercises
+   1   3   one step, its second pair half padding
+   2   6   an odd number of pairs: the last step is a single pair
+   3   9
+   4  12   n = 0 mod 4
+   5  15   the last step before the first change of producing wave
+   6  18   the first step behind it
+  11  33   the second change of producing wave, at column 32
+  17  51   the third change of producing wave, at column 48
+  20  60   the contract shape
+  21  63   full: the last pivot is the padded one
+
+Routes: c1 the four-per-CU class (set_dense(0)), c6 the five-per-CU class (set_dense(2)).
+
+Checks.
+  (a) no error status (status & 47 == 0);
+  (b) the solution against the reference's qpOASES on the GPU's own dumped QP, every robot: < 1e-8 relative, the bound of
+      test_gpu_engine_iteration.py (b);
+  (c) iters equal between c1 and c6 on the same robots;
+  (d) grf bits, status and iters equal to the fixture, which was recorded with the parent commit's build (one pair per barrier
+      in both classes) by running record() below on it (tests/golden/sweep_two_pairs/bits.npz: a directory of its own, as
+      test_gpu_parity.py and test_oracle_cpu.py take every tests/golden/*.npz for a batch of solver inputs);
+  (e) the not-positive-definite exit, one robot per parity of nst (2 and 3) with all weights and alpha zero
+      (error_cases' zero_hessian): the parent's status bits, QMPC_ST_NOT_PD among them, and the parent's forces, bit for
+      bit; its neighbours in the batch as in the clean case.  What the parent's build gives that robot (status 34 =
+      QMPC_ST_NOT_PD | QMPC_ST_NONFINITE in both cases, both routes): exactly zero for its three swing feet and NaN
+      (0xffc00000) in the three components of its one stance foot of the first segment -- the library's contract for a
+      matrix that is not positive definite (flagged; a non-finite value only under QMPC_ST_NONFINITE), not twelve zeros.
+      check_abandoned holds that form, the fixture the bits.
+"""
+import os
+
+import numpy as np
+import pytest
+
+import error_cases as E
+from quadruped_ctrl_amd import workloads as W
+from test_gpu_engine_iteration import qpoases_error
+from test_gpu_parity import _take
+
+pytestmark = pytest.mark.gpu
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sweep_two_pairs", "bits.npz")
+B = 16
+NST = (1, 2, 3, 4, 5, 6, 11, 17, 20, 21)
+NOT_PD = {2: 5, 3: 10}        # nst -> the robot of the batch whose Hessian is zeroed in the (e) case
+ROUTES = ("c1", "c6")
+_POOL = {}
+
+
+def batch_of(nst):
+    """16 robots of configs[4]'s first 256 with at least nst stance foot-steps, thinned to exactly nst."""
+    if "pool" not in _POOL:
+        _POOL["pool"] = W.make_config(4, batch=256)
+    if nst not in _POOL:
+        pool = _POOL["pool"]
+        rng = np.random.default_rng(20300 + nst)
+        g = pool["gait"].copy()
+        count = (g != 0).sum(1)
+        pick = np.flatnonzero(count >= nst)[:B]
+        assert pick.size == B
+        for i in pick:
+            on = np.flatnonzero(g[i])
+            if on.size > nst:
+                g[i, rng.choice(on[1:], on.size - nst, replace=False)] = 0
+        b = _take(dict(pool, gait=g), pick)
+        assert ((b["gait"] != 0).sum(1) == nst).all()
+        for v in b.values():
+            if isinstance(v, np.ndarray):
+                v.setflags(write=False)
+        _POOL[nst] = b
+    return _POOL[nst]
+
+
+def case_input(nst, notpd):
+    b = batch_of(nst)
+    return E.poisoned(b, {NOT_PD[nst]: "zero_hessian"}, E.NOT_PD_KINDS) if notpd else b
+
+
+def solve_case(nst, route, notpd, mpc_factory):
+    b = case_input(nst, notpd)
+    m = mpc_factory(b, max_batch=B)
+    m.set_order_hint(0)
+    m.set_max_stance(21)
+    m.set_dense(2 if route == "c6" else 0)
+    Hd, gd, ld = m.debug_dump(B)
+    res = m.solve(b, full=True)
+    m.debug_off()
+    res["H"], res["g"] = Hd.cpu().numpy(), gd.cpu().numpy()
+    return b, res
+
+
+def name_of(nst, route, notpd):
+    return f"{'notpd' if notpd else 'nst'}{nst}-{route}"
+
+
+CASES = [(nst, route, False) for nst in NST for route in ROUTES] + [(nst, route, True) for nst in NOT_PD for route in ROUTES]
+
+
+def record(mpc_factory, path=GOLD):
+    """Write the fixture (run once, on the parent commit's build)."""
+    out = {}
+    for nst, route, notpd in CASES:
+        b, res = solve_case(nst, route, notpd, mpc_factory)
+        print(name_of(nst, route, notpd), "iters", res["iters"].tolist(), "status", res["status"].tolist())
+        out[name_of(nst, route, notpd) + "/grf"] = res["grf"].view(np.uint32)
+        out[name_of(nst, route, notpd) + "/status"] = res["status"]
+        out[name_of(nst, route, notpd) + "/iters"] = res["iters"]
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    np.savez_compressed(path, **out)
+
+
+def check_abandoned(b, bad, grf_bits, status):
+    """The forces of the robot whose Hessian is zero: exactly +0 for every swing foot, and for a stance foot either +0 or a
+    non-finite value under QMPC_ST_NONFINITE (include/qmpc.h; test_gpu_error_exits.py's rule 1)."""
+    f = grf_bits[bad].view(np.float32).reshape(4, 3)
+    stance = b["gait"][bad].reshape(-1, 4)[0] != 0
+    assert not grf_bits[bad].reshape(4, 3)[~stance].any()
+    live = f[stance]
+    assert np.all((live == 0) | ~np.isfinite(live))
+    if not np.isfinite(live).all():
+        assert status[bad] & E.ST_NONFINITE
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return np.load(GOLD)
+
+
+def test_fixture_is_what_the_cases_need(gold):
+    for nst, route, notpd in CASES:
+        st = gold[name_of(nst, route, notpd) + "/status"]
+        bad = NOT_PD[nst] if notpd else -1
+        ok = np.arange(B) != bad
+        assert ((st[ok] & E.ST_ERROR_MASK) == 0).all()
+        if notpd:
+            assert st[bad] & E.ST_NOT_PD
+            check_abandoned(case_input(nst, True), bad, gold[name_of(nst, route, notpd) + "/grf"], st)
+    assert any(gold[name_of(nst, "c1", False) + "/iters"].max() > 0 for nst in NST)  # (robots that iterate are among them)
+
+
+@pytest.mark.parametrize("nst,route,notpd", CASES, ids=[name_of(*c) for c in CASES])
+def test_sweep_two_pairs(nst, route, notpd, gold, mpc_factory):
+    case = name_of(nst, route, notpd)
+    b, res = solve_case(nst, route, notpd, mpc_factory)
+    print(case, "iters", res["iters"].tolist(), "status", res["status"].tolist())
+    ok = np.arange(B) != (NOT_PD[nst] if notpd else -1)
+    assert ((res["status"][ok] & 47) == 0).all(), res["status"]                                         # (a)
+    idx = np.flatnonzero(ok)
+    err, _ = qpoases_error(_take(b, idx), {k: res[k][idx] for k in ("soln", "H", "g")})
+    print("   vs qpOASES on the dumped QP: worst", err.max())
+    assert err.max() < 1e-8                                                                             # (b)
+    if route == "c6":
+        assert np.array_equal(res["iters"], gold[name_of(nst, "c1", notpd) + "/iters"]), "iters differ between c1 and c6"  # (c)
+    assert np.array_equal(res["grf"].view(np.uint32), gold[case + "/grf"])                              # (d), (e)
+    assert np.array_equal(res["status"], gold[case + "/status"])
+    assert np.array_equal(res["iters"], gold[case + "/iters"])
+    if notpd:
+        assert res["status"][NOT_PD[nst]] & E.ST_NOT_PD                                                 # (e)
+        check_abandoned(b, NOT_PD[nst], res["grf"].view(np.uint32), res["status"])
