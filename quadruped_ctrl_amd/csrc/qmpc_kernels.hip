@@ -52,8 +52,13 @@
 #include "qmpc_device.h"
 #include "qmpc_cmd.h"
 #include "qmpc_wave.h"
+#include "qmpc_etab.h"
 
 namespace {
+
+// an entry of the interleaved E tables: .x = E_00[u][v], .y = E_11[u][v] (qmpc_etab.h), moved as one 16-byte LDS access
+typedef double qmpc_epair __attribute__((ext_vector_type(2)));
+static_assert(sizeof(qmpc_epair) == QMPC_E_PAIR_BYTES, "an E pair is one 16-byte access");
 
 // a[j] += c[lane j of this lane's row of 16] * u for j = 0..15: sixteen DP-ALU DPP
 // fmacs (row_newbcast), i.e. the 16 wave-uniform pivot-column values are held one
@@ -636,12 +641,14 @@ struct Smem {
         double Mb[4][9];  // M_b = I_world^-1 [r_b]x                 (B0 rows 6..8)
         double Nb[4][9];  // N_b = R_yaw^T M_b                       (B1 rows 0..2)
         double W[12];
+        // E_00 / E_11 as 16-byte pairs in rows of 13 (qmpc_etab.h: one ds_read_b128 per element of stage 2, no bank conflict
+        // between any rows).  Here, an even number of doubles into the (16-byte aligned) struct: the pairs stay aligned
+        alignas(QMPC_E_PAIR_BYTES) qmpc_epair EE[QMPC_E_PAIRS];
         // coefficient tables, (h + 1) x (h + 1) with a ZERO last row and column (built by qmpc_setup): a row of the identity
         // padding reads row h, a column beyond the stance list column h, and their entries of H vanish by themselves
         static constexpr int TAB = (C::HMAX + 1) * (C::HMAX + 1);
         double ct0[TAB], ct4[TAB];  // C_00 (tau), C_11 (sigma)
         double ct1[TAB], ct5[TAB], ct8[TAB];  // C_01, C_12, C_22 (x_drag != 0 only)
-        double E00[144], E11[144];
         double e[C::HMAX * 12];
         double s[3][C::HMAX * 12];
       } a;
@@ -665,6 +672,9 @@ struct Smem {
       double D[C::NP];  // event-form engine: diag(H^-1)
     } b;
   } u;
+  // (the solve's storage is the union's largest phase in every class: the padded E tables of the assembly cost no LDS, and the
+  //  workgroups per CU stay what POOL was sized for)
+  static_assert(sizeof(typename U::AW) <= sizeof(typename U::Slv), "assembly / sweep storage larger than the solve's");
 };
 
 // phase timestamps (profiling hook; dbg_clk == nullptr in production)
@@ -1341,8 +1351,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
       e11 += Aa.W[3 + au] * (inv_m * inv_m);
       if (drag && au == 0) e11 += Aa.W[11] * ((x_drag * inv_m) * (x_drag * inv_m));  // B1 row 11
     }
-    Aa.E00[tid] = e00;
-    Aa.E11[tid] = e11;
+    Aa.EE[qmpc_e_pair(u, v)] = qmpc_epair{e00, e11};
   }
   // s_p[st] = sum_{k>=st} coef_p(k-st) e_k for the three coefficient families
   //   coef_0(d) = dt,  coef_1(d) = (2d+1) dt^2/2,  coef_2(d) = (3d^2+3d+1) dt^3/6
@@ -1420,6 +1429,7 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
   }
   QMPC_WAVE_TICK(2);
   __syncthreads();  // ---- barrier 2
+  asm volatile("; qmpc assemble begin");  // (comment-only marker: from here to "; qmpc sweep begin" is stage 2, tools/etab_shape.py)
   QMPC_TICK(2);
   // (the robots of a staged CU that are not its hardest step back one level from the assembly on, like the hint's robots after
   //  stage 0: configs[1] 2.73e7 -> 2.76e7, against stepping back only in the sweep; one level lower still throughout their
@@ -1498,8 +1508,9 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
         const int ki = S.sidx[r / 3], ai = r % 3, si = ki >> 2, u = 3 * (ki & 3) + ai;
         for (int j = lane; j < n; j += 64) {
           const int kj = S.sidx[j / 3], cax = j % 3, sj = kj >> 2;
-          const int cidx = si * hs + sj, tidx = sj * hs + si, eidx = u * 12 + 3 * (kj & 3) + cax;
-          double v = Aa.ct0[cidx] * Aa.E00[eidx] + Aa.ct4[cidx] * Aa.E11[eidx];
+          const int cidx = si * hs + sj, tidx = sj * hs + si;
+          const qmpc_epair ee = Aa.EE[qmpc_e_pair(u, 3 * (kj & 3) + cax)];
+          double v = Aa.ct0[cidx] * ee.x + Aa.ct4[cidx] * ee.y;
           if (drag) {
             double add = 0.0;
             if (ai == 2 && cax == 0) add = Aa.ct1[cidx] * w11 + Aa.ct5[cidx] * w5;
@@ -1928,9 +1939,10 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
 #pragma unroll
         for (int jj = 0; jj < CW; ++jj) {
           const int kj = kj_at((CAX0 + jj) / 3), cax = (CAX0 + jj) % 3;
-          const int cidx = si * hs + (kj >> 2), eidx = u * 12 + 3 * (kj & 3) + cax;
+          const int cidx = si * hs + (kj >> 2);
+          const qmpc_epair ee = Aa.EE[qmpc_e_pair(u, 3 * (kj & 3) + cax)];
           // H = 2 (tau (x) E_00 + sigma (x) E_11 + x_drag terms + alpha I), SolverMPC.cpp:395
-          a[jj] = Aa.ct0[cidx] * Aa.E00[eidx] + Aa.ct4[cidx] * Aa.E11[eidx];
+          a[jj] = Aa.ct0[cidx] * ee.x + Aa.ct4[cidx] * ee.y;
           if ((jj & 1) == 1) __builtin_amdgcn_sched_barrier(0);  // bound the load hoisting (VGPR pressure)
         }
       } else {
@@ -1952,9 +1964,9 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
           constexpr int dummy = 0;
           (void)dummy;
           const int q = (CAX0 + jj) / 3, cax = (CAX0 + jj) % 3;
-          const int eidx = u * 12 + 3 * (kj_at(q) & 3) + cax;
+          const qmpc_epair ee = Aa.EE[qmpc_e_pair(u, 3 * (kj_at(q) & 3) + cax)];  // one 16-byte load
           // H = 2 (tau (x) E_00 + sigma (x) E_11 + x_drag terms + alpha I), SolverMPC.cpp:395
-          a[jj] = t0[q] * Aa.E00[eidx] + t4[q] * Aa.E11[eidx];
+          a[jj] = t0[q] * ee.x + t4[q] * ee.y;
           if ((jj & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // bound the load hoisting (VGPR pressure)
         }
       }
