@@ -8,7 +8,10 @@
 // The numbered comments are the steps of include/qmpc_contact.h.  FIELD (include/qmpc_field.h): the robot's place row is
 // loaded once beside the terrain row, every height is the summed surface, and G.n is this lane's own foot's normal,
 // evaluated after the edges and again after each slide move from the taps of the height it needs there anyway.
-// FIELD = false reads nothing of Fd.  No include guard: it is included once per kernel.
+// FIELD = false reads nothing of Fd.  The per-robot constants, J^-T tau, the cone about the normal, the quad sums with the
+// wrench, the body update, the quaternion step and the statistics fold are qmpc_plant_step_body.h's statements again, as
+// text, for the reasons its header gives: a change to one of them is made in both.  No include guard: it is included once
+// per kernel.
   const QmpcPlantConst& K = A.K;
   const QmpcContactArgs& C = A.C;
   const int n = A.n;

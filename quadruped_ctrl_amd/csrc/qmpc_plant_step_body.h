@@ -2,13 +2,21 @@
 // step kernel (qmpc_plant.hip: TERRAIN false; qmpc_terrain.hip: TERRAIN true) after qmpc_plant_dev.h, with in scope
 //   #pragma clang fp contract(off) at the head of the kernel's body (the pragma is only allowed there);
 //   the template parameters bool VARY, bool STATS, and constexpr bool TERRAIN, FIELD (qmpc_field.hip: both true);
-//   the kernel's parameters S, K, effort, contact_state, p_des, v_des, state_out, motor_out, n, V,
+//   the names S, K, effort, contact_state, p_des, v_des, state_out, motor_out, n, V of qmpc_plant.h's QmpcPlantStepArgs:
+//   the launchers spread the block's members, so in the step kernels these are separate kernel parameters (in
+//   qmpc_span.hip the span kernel's own parameters and locals, contact_state / p_des / v_des the controller's arrays);
 //   T (QmpcTerrainArgs: a parameter of the terrain kernels, an empty local of the flat ones) and
 //   Fd (QmpcFieldArgs: a parameter of the field kernels, an empty local of the others).
 // It is text and not a function on purpose.  As a force-inlined function template plant_step_body<VARY, STATS, TERRAIN>
 // the same statements cost the plain step 225 VGPRs and 17 scalar registers parked in scratch (arguments by value or by
 // reference, with or without __restrict__), against 221 and none when the kernel holds them itself -- the figures
-// tests/test_plant_varied_cpu.py keeps.  No include guard: it is included once per kernel.
+// tests/test_plant_varied_cpu.py keeps.  Piece by piece it is no different: the per-robot constants, J^-T tau, the cone
+// about the normal, the quad sums with the wrench, the body update, the quaternion step and the statistics fold are the
+// same statements here and in qmpc_contact_step_body.h, and each of them was tried as a function of qmpc_plant_dev.h.
+// Most cost registers, spills or scratch; the three that did not moved the --vary and --contact plant step by 0.02 to
+// 0.08 us on an MI355X, past the parent's own repeats (profiles/plant_kernel_resources.txt lists the forms and the
+// figures, profiles/plant_substep_shared_ab.json the runs).  So they stay text in both bodies: a change to one of them
+// is made in both.  No include guard: it is included once per kernel.
 //
 // One control period of lane t = blockIdx.x * 256 + threadIdx.x.  n = batch * 4 lanes; the lanes past n in the last wave
 // repeat lane n - 1 and store nothing, so that every shuffle has its partner.

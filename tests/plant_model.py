@@ -91,15 +91,21 @@ def leg(r, geom=GEOM):
     return ang, C, det
 
 
-def stance_force(R, rb, tau, mu, geom=GEOM):
-    """Ground reaction on the body (world) of pinned feet with body-frame lever rb [B,4,3] and torques tau [B,4,3]."""
+def leg_force(R, rb, tau, geom=GEOM):
+    """-(R J^-T tau) [B,4,3], the ground's reaction (world) to the torques tau [B,4,3] of feet with body-frame lever rb
+    [B,4,3], before any cone, and ok [B,4]: the leg is not singular."""
     r = rb - HIP
     _, C, det = leg(r, geom)
     ok = np.abs(det) >= DET_MIN
     sdet = np.where(ok, det, 1.0)
     Fb = np.stack([((C[..., 3 * k] * tau[..., 0] + C[..., 3 * k + 1] * tau[..., 1]) + C[..., 3 * k + 2] * tau[..., 2]) / sdet
                    for k in range(3)], -1)
-    f = -mul(R[:, None, :], Fb)
+    return -mul(R[:, None, :], Fb), ok
+
+
+def stance_force(R, rb, tau, mu, geom=GEOM):
+    """Ground reaction on the body (world) of pinned feet with body-frame lever rb [B,4,3] and torques tau [B,4,3]."""
+    f, ok = leg_force(R, rb, tau, geom)
     ok = ok & (f[..., 2] > 0.0)
     ft = np.sqrt(f[..., 0] * f[..., 0] + f[..., 1] * f[..., 1])
     cap = mu * f[..., 2]
@@ -108,6 +114,49 @@ def stance_force(R, rb, tau, mu, geom=GEOM):
     f = np.stack([np.where(ft > cap, f[..., 0] * sc, f[..., 0]), np.where(ft > cap, f[..., 1] * sc, f[..., 1]),
                   f[..., 2]], -1)
     return np.where(ok[..., None], f, 0.0)
+
+
+def quad_sum(x):
+    """The four legs' sum [B, 4, ...] -> [B, ...] in the device's order (csrc/qmpc_plant_dev.h: plant_quad_sum)."""
+    return (x[:, 0] + x[:, 1]) + (x[:, 2] + x[:, 3])
+
+
+def add_wrench(F, N, force, torque):
+    """The external force (world) and moment (body) on top of the quad sums, each only when bound."""
+    if force is not None:
+        F = F + force
+    if torque is not None:
+        N = N + torque
+    return F, N
+
+
+def body_update(p, v, w, F, N, mass, ibody, h):
+    """One substep of the rigid body under force F (world) and moment N (body) -> p, v, w, vdot.  mass, ibody: the
+    handle's scalar and (3,), or a robot's own [B] and [B, 3]."""
+    vdot = np.stack([F[:, 0] / mass, F[:, 1] / mass, F[:, 2] / mass - GRAVITY], 1)
+    Iw = ibody * w
+    wIw = cross(w, Iw)
+    v = v + h * vdot
+    w = w + h * ((N - wIw) / ibody)
+    p = p + h * v
+    return p, v, w, vdot
+
+
+def quat_step(q, w, h):
+    """q <- q (x) dq(w h), normalised (the caller holds np.errstate: wn == 0 divides by zero in the discarded branch)."""
+    wn = np.sqrt((w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1]) + w[:, 2] * w[:, 2])
+    a = wn * h
+    small = a < 1e-12
+    d0 = np.where(small, 1.0, np.cos(0.5 * a))
+    ds = np.where(small, 0.5 * h, np.sin(0.5 * a) / wn)
+    d1, d2, d3 = ds * w[:, 0], ds * w[:, 1], ds * w[:, 2]
+    q0, q1, q2, q3 = (q[:, k] for k in range(4))
+    n0 = ((q0 * d0 - q1 * d1) - q2 * d2) - q3 * d3
+    n1 = ((q0 * d1 + q1 * d0) + q2 * d3) - q3 * d2
+    n2 = ((q0 * d2 - q1 * d3) + q2 * d0) + q3 * d1
+    n3 = ((q0 * d3 + q1 * d2) - q2 * d1) + q3 * d0
+    nn = np.sqrt(((n0 * n0 + n1 * n1) + n2 * n2) + n3 * n3)
+    return np.stack([n0 / nn, n1 / nn, n2 / nn, n3 / nn], 1)
 
 
 class PlantModel:
@@ -166,28 +215,9 @@ class PlantModel:
             f = np.where(stance[..., None], stance_force(R, rb, tau, self.mu, self.geom), 0.0)
             fb = mulT(R[:, None, :], f)
             m = cross(rb, fb)
-            F = (f[:, 0] + f[:, 1]) + (f[:, 2] + f[:, 3])
-            N = (m[:, 0] + m[:, 1]) + (m[:, 2] + m[:, 3])
-            vdot = np.stack([F[:, 0] / self.mass, F[:, 1] / self.mass, F[:, 2] / self.mass - GRAVITY], 1)
-            Iw = self.ibody * w
-            wIw = cross(w, Iw)
-            v = v + h * vdot
-            w = w + h * ((N - wIw) / self.ibody)
-            p = p + h * v
-            wn = np.sqrt((w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1]) + w[:, 2] * w[:, 2])
-            a = wn * h
-            small = a < 1e-12
+            p, v, w, vdot = body_update(p, v, w, quad_sum(f), quad_sum(m), self.mass, self.ibody, h)
             with np.errstate(divide="ignore", invalid="ignore"):
-                d0 = np.where(small, 1.0, np.cos(0.5 * a))
-                ds = np.where(small, 0.5 * h, np.sin(0.5 * a) / wn)
-            d1, d2, d3 = ds * w[:, 0], ds * w[:, 1], ds * w[:, 2]
-            q0, q1, q2, q3 = (q[:, k] for k in range(4))
-            n0 = ((q0 * d0 - q1 * d1) - q2 * d2) - q3 * d3
-            n1 = ((q0 * d1 + q1 * d0) + q2 * d3) - q3 * d2
-            n2 = ((q0 * d2 - q1 * d3) + q2 * d0) + q3 * d1
-            n3 = ((q0 * d3 + q1 * d2) - q2 * d1) + q3 * d0
-            nn = np.sqrt(((n0 * n0 + n1 * n1) + n2 * n2) + n3 * n3)
-            q = np.stack([n0 / nn, n1 / nn, n2 / nn, n3 / nn], 1)
+                q = quat_step(q, w, h)
         state, motor, c = self._readout(p, v, q, w, c, stance, vdot, np.asarray(p_des).reshape(B, 4, 3),
                                         np.asarray(v_des).reshape(B, 4, 3))
         self.p, self.v, self.q, self.w, self.foot, self.grf, self.stance = p, v, q, w, c, f, stance
@@ -207,7 +237,6 @@ class PlantModel:
         return out
 
     def _readout(self, p, v, q, w, c, stance, vdot, p_des, v_des):
-        B = len(p)
         R = rot(q)
         vb = mulT(R, v)
         rb = mulT(R[:, None, :], c - p[:, None, :])
@@ -220,6 +249,12 @@ class PlantModel:
             r = np.where(sw, rs, r)
             rdot = np.where(sw, np.asarray(v_des, f64), rdot)
             c = np.where(sw, cs, c)
+        return self._rows(R, q, p, w, vb, r, rdot, vdot) + (c,)
+
+    def _rows(self, R, q, row_p, w, vb, r, rdot, vdot):
+        """-> the state row and the motor row: joint angles and rates from the feet's hip-frame position r and velocity
+        rdot [B,4,3]; row_p is what columns 4:7 show of the position."""
+        B = len(q)
         ang, C, det = leg(r, self.geom)
         ok = np.abs(det) >= DET_MIN
         sdet = np.where(ok, det, 1.0)
@@ -227,6 +262,6 @@ class PlantModel:
                        for k in range(3)], -1)
         qd = np.where(ok[..., None], qd, 0.0)
         sf = np.stack([vdot[:, 0], vdot[:, 1], vdot[:, 2] + GRAVITY], 1)
-        state = np.concatenate([q, p, w, vb, mulT(R, sf)], 1)
+        state = np.concatenate([q, row_p, w, vb, mulT(R, sf)], 1)
         motor = np.concatenate([ang.reshape(B, 12), qd.reshape(B, 12)], 1)
-        return state, motor, c
+        return state, motor

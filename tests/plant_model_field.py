@@ -120,9 +120,7 @@ class FieldPlantModel(PCM.ContactPlantModel):
     def _step_field(self, effort, contact_state, p_des, v_des):
         """TerrainPlantModel.step with the summed surface and the normal per foot."""
         B, h = self.B, self.h
-        mass = np.full(B, self.mass) if self.mass_b is None else self.mass_b
-        ibody = np.broadcast_to(self.ibody, (B, 3)) if self.ibody_b is None else self.ibody_b
-        mu = np.full(B, self.mu) if self.mu_b is None else self.mu_b
+        mass, ibody, mu = self.own()
         tau = np.asarray(effort, f64).reshape(B, 4, 3)
         stance = np.asarray(contact_state).reshape(B, 4) > 0
         p, v, q, w, c = self.p.copy(), self.v.copy(), self.q.copy(), self.w.copy(), self.foot.copy()
@@ -130,29 +128,16 @@ class FieldPlantModel(PCM.ContactPlantModel):
         with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
             hz, n = self.foot_surface(c[..., 0], c[..., 1])                                                  # 1 + normal
             c[..., 2] = np.where(stance & ~self.stance, hz, c[..., 2])
-            one, sz = np.where(stance, 1.0, 0.0), np.where(stance, c[..., 2], 0.0)
-            cnt = (one[:, 0] + one[:, 1]) + (one[:, 2] + one[:, 3])
-            ssum = (sz[:, 0] + sz[:, 1]) + (sz[:, 2] + sz[:, 3])
-            support = np.where(cnt > 0.0, ssum / np.where(cnt > 0.0, cnt, 1.0), self.support)
+            support = PT.support_height(stance, c[..., 2], self.support)
             for _ in range(self.substeps):
                 R = PM.rot(q)
                 rb = PM.mulT(R[:, None, :], c - p[:, None, :])
                 f = np.where(stance[..., None], PT.stance_force_terrain(R, rb, tau, mu[:, None], n, self.geom), 0.0)   # 2a
                 fb = PM.mulT(R[:, None, :], f)
                 m = PM.cross(rb, fb)
-                F = (f[:, 0] + f[:, 1]) + (f[:, 2] + f[:, 3])
-                N = (m[:, 0] + m[:, 1]) + (m[:, 2] + m[:, 3])
-                if self.force is not None:
-                    F = F + self.force
-                if self.torque is not None:
-                    N = N + self.torque
-                vdot = np.stack([F[:, 0] / mass, F[:, 1] / mass, F[:, 2] / mass - PM.GRAVITY], 1)
-                Iw = ibody * w
-                wIw = PM.cross(w, Iw)
-                v = v + h * vdot
-                w = w + h * ((N - wIw) / ibody)
-                p = p + h * v
-                q = self._quat_step(q, w, h)
+                F, N = PM.add_wrench(PM.quad_sum(f), PM.quad_sum(m), self.force, self.torque)
+                p, v, w, vdot = PM.body_update(p, v, w, F, N, mass, ibody, h)
+                q = PM.quat_step(q, w, h)
             state, motor, c = self._readout_terrain(p, v, q, w, c, stance, vdot, np.asarray(p_des).reshape(B, 4, 3),
                                                     np.asarray(v_des).reshape(B, 4, 3), support)
             self.ground = self.height(p[:, 0], p[:, 1])
@@ -163,29 +148,12 @@ class FieldPlantModel(PCM.ContactPlantModel):
             self._accumulate(state)
         return state, motor
 
-    @staticmethod
-    def _quat_step(q, w, h):
-        wn = np.sqrt((w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1]) + w[:, 2] * w[:, 2])
-        a = wn * h
-        small = a < 1e-12
-        d0 = np.where(small, 1.0, np.cos(0.5 * a))
-        ds = np.where(small, 0.5 * h, np.sin(0.5 * a) / wn)
-        d1, d2, d3 = ds * w[:, 0], ds * w[:, 1], ds * w[:, 2]
-        q0, q1, q2, q3 = (q[:, k] for k in range(4))
-        n0 = ((q0 * d0 - q1 * d1) - q2 * d2) - q3 * d3
-        n1 = ((q0 * d1 + q1 * d0) + q2 * d3) - q3 * d2
-        n2 = ((q0 * d2 - q1 * d3) + q2 * d0) + q3 * d1
-        n3 = ((q0 * d3 + q1 * d2) - q2 * d1) + q3 * d0
-        nn = np.sqrt(((n0 * n0 + n1 * n1) + n2 * n2) + n3 * n3)
-        return np.stack([n0 / nn, n1 / nn, n2 / nn, n3 / nn], 1)
-
     def _step_field_contact(self, effort, contact_state, p_des, v_des):
         """ContactPlantModel._step_contact with the summed surface and the normal per foot."""
         B, h, fl = self.B, self.h, self.cflags
         EARLY, LATE, SLIP = PCM.EARLY, PCM.LATE, PCM.SLIP
-        mass = np.full(B, self.mass) if self.mass_b is None else self.mass_b
-        ibody = np.broadcast_to(self.ibody, (B, 3)) if self.ibody_b is None else self.ibody_b
-        mu = (np.full(B, self.mu) if self.mu_b is None else self.mu_b)[:, None]
+        mass, ibody, mu = self.own()
+        mu = mu[:, None]
         tau = np.asarray(effort, f64).reshape(B, 4, 3)
         s = np.asarray(contact_state).reshape(B, 4) > 0
         pd, vd = np.asarray(p_des, f64).reshape(B, 4, 3), np.asarray(v_des, f64).reshape(B, 4, 3)
@@ -200,10 +168,7 @@ class FieldPlantModel(PCM.ContactPlantModel):
             self.ties.append(("edge", c[..., 2].copy(), hz, s & ~pin & bool(fl & LATE)))
             c[..., 2] = np.where(land, hz, c[..., 2])
             pin = (s & (pin | land)) | (~s & pin & bool(fl & EARLY))
-            one, sz = np.where(pin, 1.0, 0.0), np.where(pin, c[..., 2], 0.0)
-            cnt = (one[:, 0] + one[:, 1]) + (one[:, 2] + one[:, 3])
-            ssum = (sz[:, 0] + sz[:, 1]) + (sz[:, 2] + sz[:, 3])
-            support = np.where(cnt > 0.0, ssum / np.where(cnt > 0.0, cnt, 1.0), self.support)
+            support = PT.support_height(pin, c[..., 2], self.support)
             pin1 = pin.copy()
             # 2. substeps
             for _ in range(self.substeps):
@@ -214,18 +179,8 @@ class FieldPlantModel(PCM.ContactPlantModel):
                 cd = np.where(slid[..., None], -(sv[..., None] * (t / ft[..., None])), 0.0)
                 fb = PM.mulT(R[:, None, :], f)
                 m = PM.cross(rb, fb)
-                F = (f[:, 0] + f[:, 1]) + (f[:, 2] + f[:, 3])
-                N = (m[:, 0] + m[:, 1]) + (m[:, 2] + m[:, 3])
-                if self.force is not None:
-                    F = F + self.force
-                if self.torque is not None:
-                    N = N + self.torque
-                vdot = np.stack([F[:, 0] / mass, F[:, 1] / mass, F[:, 2] / mass - PM.GRAVITY], 1)
-                Iw = ibody * w
-                wIw = PM.cross(w, Iw)
-                v = v + h * vdot
-                w = w + h * ((N - wIw) / ibody)
-                p = p + h * v
+                F, N = PM.add_wrench(PM.quad_sum(f), PM.quad_sum(m), self.force, self.torque)
+                p, v, w, vdot = PM.body_update(p, v, w, F, N, mass, ibody, h)
                 if fl & SLIP:
                     cx = np.where(slid, c[..., 0] + h * cd[..., 0], c[..., 0])
                     cy = np.where(slid, c[..., 1] + h * cd[..., 1], c[..., 1])
@@ -233,54 +188,11 @@ class FieldPlantModel(PCM.ContactPlantModel):
                     cz = np.where(slid, hs_, c[..., 2])
                     n = np.where(slid[..., None], ns_, n)
                     c = np.stack([cx, cy, cz], -1)
-                    d = np.where(slid, h * sv, 0.0)
-                    slip = slip + ((d[:, 0] + d[:, 1]) + (d[:, 2] + d[:, 3]))
-                q = self._quat_step(q, w, h)
-            # 3. unpinned feet and release, at the new pose
-            R = PM.rot(q)
-            vb = PM.mulT(R, v)
-            cmd = ~(s & pin)
-            lateft = s & ~pin
-            drop = np.where(lateft, drop + self.drop_speed * self.dt, drop)
-            ez = R[:, None, 6:9]
-            rs = self.clamp(np.where(lateft[..., None], pd - drop[..., None] * ez, pd))
-            cs = p[:, None, :] + PM.mul(R[:, None, :], PM.HIP + rs)
-            hs = self.height(cs[..., 0], cs[..., 1])
-            touching = cs[..., 2] <= hs
-            test = s | bool(fl & EARLY)
-            hit = cmd & test & touching
-            self.ties.append(("touch", cs[..., 2], hs, cmd & test))
-            newpin = hit & ~pin
-            free = cmd & ~hit
-            on = np.stack([cs[..., 0], cs[..., 1], hs], -1)
-            c = np.where(newpin[..., None], on, np.where(free[..., None], cs, c))
-            pin = np.where(cmd, hit, pin)
-            low = np.zeros((B, 4), bool)
-            if self.flags & PT.CLAMP_SWING:
-                low = free & (c[..., 2] < hs)
-                c[..., 2] = np.where(low, hs, c[..., 2])
-            self.trace = dict(s=s, pin0=pin0, land=land, pin1=pin1, slid=slid_any, late=lateft, hit=hit, newpin=newpin,
-                              free=free, pin2=pin.copy(), foot1=c.copy())
-            self.early = self.early + (~s & pin).sum(1).astype(np.int32)
-            self.late = self.late + lateft.sum(1).astype(np.int32)
-            drop = np.where(pin | ~s, 0.0, drop)
-            # 4. read-out
-            rb = PM.mulT(R[:, None, :], c - p[:, None, :])
-            r = np.where((pin | low)[..., None], rb - PM.HIP, rs)
-            rdot = np.where(pin[..., None], (-vb[:, None, :] - PM.cross(w[:, None, :], rb)) + PM.mulT(R[:, None, :], cd), vd)
-            ang, C, det = PM.leg(r, self.geom)
-            ok = np.abs(det) >= PM.DET_MIN
-            sdet = np.where(ok, det, 1.0)
-            qd = np.stack([((C[..., k] * rdot[..., 0] + C[..., 3 + k] * rdot[..., 1]) + C[..., 6 + k] * rdot[..., 2]) / sdet
-                           for k in range(3)], -1)
-            qd = np.where(ok[..., None], qd, 0.0)
-            sf = np.stack([vdot[:, 0], vdot[:, 1], vdot[:, 2] + PM.GRAVITY], 1)
-            row_p = p.copy()
-            if self.flags & PT.REBASE_Z:
-                row_p[:, 2] = p[:, 2] - support
-            state = np.concatenate([q, row_p, w, vb, PM.mulT(R, sf)], 1)
-            motor = np.concatenate([ang.reshape(B, 12), qd.reshape(B, 12)], 1)
-            self.ground = self.height(p[:, 0], p[:, 1])
+                    slip = slip + PM.quad_sum(np.where(slid, h * sv, 0.0))
+                q = PM.quat_step(q, w, h)
+            # 3. unpinned feet and release, 4. read-out
+            self.trace = dict(s=s, pin0=pin0, land=land, pin1=pin1, slid=slid_any)
+            pin, c, drop, state, motor = self._release_and_readout(s, pin, p, v, q, w, c, cd, drop, vdot, pd, vd, support)
         self.support, self.drop, self.slip = support, drop, slip
         self.p, self.v, self.q, self.w, self.foot, self.grf, self.stance = p, v, q, w, c, f, pin
         self.state, self.motor = state, motor

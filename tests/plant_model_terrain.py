@@ -18,13 +18,7 @@ COLUMNS = ("z0", "gx", "gy", "rise", "run", "count", "s0", "psi")
 
 def stance_force_terrain(R, rb, tau, mu, n, geom=PM.GEOM):
     """plant_model.stance_force with the cone about the normal n [B,1,3]."""
-    r = rb - PM.HIP
-    _, C, det = PM.leg(r, geom)
-    ok = np.abs(det) >= PM.DET_MIN
-    sdet = np.where(ok, det, 1.0)
-    Fb = np.stack([((C[..., 3 * k] * tau[..., 0] + C[..., 3 * k + 1] * tau[..., 1]) + C[..., 3 * k + 2] * tau[..., 2]) / sdet
-                   for k in range(3)], -1)
-    g = -PM.mul(R[:, None, :], Fb)
+    g, ok = PM.leg_force(R, rb, tau, geom)
     fn = (g[..., 0] * n[..., 0] + g[..., 1] * n[..., 1]) + g[..., 2] * n[..., 2]
     ok = ok & (fn > 0.0)
     t = g - fn[..., None] * n
@@ -34,6 +28,13 @@ def stance_force_terrain(R, rb, tau, mu, n, geom=PM.GEOM):
         sc = cap / ft
         f = np.where((ft > cap)[..., None], fn[..., None] * n + t * sc[..., None], g)
     return np.where(ok[..., None], f, 0.0)
+
+
+def support_height(pinned, cz, previous):
+    """The pinned feet's mean height [B] (pinned, cz [B,4]); `previous` through a flight phase."""
+    cnt = PM.quad_sum(np.where(pinned, 1.0, 0.0))
+    ssum = PM.quad_sum(np.where(pinned, cz, 0.0))
+    return np.where(cnt > 0.0, ssum / np.where(cnt > 0.0, cnt, 1.0), previous)
 
 
 class TerrainPlantModel(PV.VariedPlantModel):
@@ -103,9 +104,7 @@ class TerrainPlantModel(PV.VariedPlantModel):
         if self.rows is None:
             return super().step(effort, contact_state, p_des, v_des)
         B, h = self.B, self.h
-        mass = np.full(B, self.mass) if self.mass_b is None else self.mass_b
-        ibody = np.broadcast_to(self.ibody, (B, 3)) if self.ibody_b is None else self.ibody_b
-        mu = np.full(B, self.mu) if self.mu_b is None else self.mu_b
+        mass, ibody, mu = self.own()
         tau = np.asarray(effort, f64).reshape(B, 4, 3)
         stance = np.asarray(contact_state).reshape(B, 4) > 0
         p, v, q, w, c = self.p.copy(), self.v.copy(), self.q.copy(), self.w.copy(), self.foot.copy()
@@ -113,41 +112,16 @@ class TerrainPlantModel(PV.VariedPlantModel):
         with np.errstate(divide="ignore", invalid="ignore", over="ignore"):   # (a robot's own bad values are its own)
             n = self.normal()[:, None, :]
             c[..., 2] = np.where(stance & ~self.stance, self.height(c[..., 0], c[..., 1]), c[..., 2])          # 1
-            one, sz = np.where(stance, 1.0, 0.0), np.where(stance, c[..., 2], 0.0)
-            cnt = (one[:, 0] + one[:, 1]) + (one[:, 2] + one[:, 3])
-            ssum = (sz[:, 0] + sz[:, 1]) + (sz[:, 2] + sz[:, 3])
-            support = np.where(cnt > 0.0, ssum / np.where(cnt > 0.0, cnt, 1.0), self.support)
+            support = support_height(stance, c[..., 2], self.support)
             for _ in range(self.substeps):
                 R = PM.rot(q)
                 rb = PM.mulT(R[:, None, :], c - p[:, None, :])
                 f = np.where(stance[..., None], stance_force_terrain(R, rb, tau, mu[:, None], n, self.geom), 0.0)   # 2a
                 fb = PM.mulT(R[:, None, :], f)
                 m = PM.cross(rb, fb)
-                F = (f[:, 0] + f[:, 1]) + (f[:, 2] + f[:, 3])
-                N = (m[:, 0] + m[:, 1]) + (m[:, 2] + m[:, 3])
-                if self.force is not None:
-                    F = F + self.force
-                if self.torque is not None:
-                    N = N + self.torque
-                vdot = np.stack([F[:, 0] / mass, F[:, 1] / mass, F[:, 2] / mass - PM.GRAVITY], 1)
-                Iw = ibody * w
-                wIw = PM.cross(w, Iw)
-                v = v + h * vdot
-                w = w + h * ((N - wIw) / ibody)
-                p = p + h * v
-                wn = np.sqrt((w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1]) + w[:, 2] * w[:, 2])
-                a = wn * h
-                small = a < 1e-12
-                d0 = np.where(small, 1.0, np.cos(0.5 * a))
-                ds = np.where(small, 0.5 * h, np.sin(0.5 * a) / wn)
-                d1, d2, d3 = ds * w[:, 0], ds * w[:, 1], ds * w[:, 2]
-                q0, q1, q2, q3 = (q[:, k] for k in range(4))
-                n0 = ((q0 * d0 - q1 * d1) - q2 * d2) - q3 * d3
-                n1 = ((q0 * d1 + q1 * d0) + q2 * d3) - q3 * d2
-                n2 = ((q0 * d2 - q1 * d3) + q2 * d0) + q3 * d1
-                n3 = ((q0 * d3 + q1 * d2) - q2 * d1) + q3 * d0
-                nn = np.sqrt(((n0 * n0 + n1 * n1) + n2 * n2) + n3 * n3)
-                q = np.stack([n0 / nn, n1 / nn, n2 / nn, n3 / nn], 1)
+                F, N = PM.add_wrench(PM.quad_sum(f), PM.quad_sum(m), self.force, self.torque)
+                p, v, w, vdot = PM.body_update(p, v, w, F, N, mass, ibody, h)
+                q = PM.quat_step(q, w, h)
             state, motor, c = self._readout_terrain(p, v, q, w, c, stance, vdot, np.asarray(p_des).reshape(B, 4, 3),
                                                     np.asarray(v_des).reshape(B, 4, 3), support)
             self.ground = self.height(p[:, 0], p[:, 1])
@@ -159,7 +133,6 @@ class TerrainPlantModel(PV.VariedPlantModel):
         return state, motor
 
     def _readout_terrain(self, p, v, q, w, c, stance, vdot, p_des, v_des, support):
-        B = len(p)
         R = PM.rot(q)
         vb = PM.mulT(R, v)
         rb = PM.mulT(R[:, None, :], c - p[:, None, :])
@@ -177,16 +150,11 @@ class TerrainPlantModel(PV.VariedPlantModel):
             r = np.where(sw, rs, r)
             rdot = np.where(sw, np.asarray(v_des, f64), rdot)
             c = np.where(sw, cs, c)
-        ang, C, det = PM.leg(r, self.geom)
-        ok = np.abs(det) >= PM.DET_MIN
-        sdet = np.where(ok, det, 1.0)
-        qd = np.stack([((C[..., k] * rdot[..., 0] + C[..., 3 + k] * rdot[..., 1]) + C[..., 6 + k] * rdot[..., 2]) / sdet
-                       for k in range(3)], -1)
-        qd = np.where(ok[..., None], qd, 0.0)
-        sf = np.stack([vdot[:, 0], vdot[:, 1], vdot[:, 2] + PM.GRAVITY], 1)
+        return self._rows(R, q, self._row_p(p, support), w, vb, r, rdot, vdot) + (c,)
+
+    def _row_p(self, p, support):
+        """Columns 4:7 of the state row: p, with REBASE_Z its height above the stance feet."""
         row_p = p.copy()
         if self.flags & REBASE_Z:                                                                            # 4
             row_p[:, 2] = p[:, 2] - support
-        state = np.concatenate([q, row_p, w, vb, PM.mulT(R, sf)], 1)
-        motor = np.concatenate([ang.reshape(B, 12), qd.reshape(B, 12)], 1)
-        return state, motor, c
+        return row_p

@@ -41,11 +41,16 @@ class VariedPlantModel(PM.PlantModel):
         for k, v in stats_initial(self.B).items():
             self.stats[k][mask] = v[mask]
 
+    def own(self):
+        """-> mass [B], ibody [B,3], mu [B]: the robot's own value where an array is bound, else the handle's."""
+        B = self.B
+        return (np.full(B, self.mass) if self.mass_b is None else self.mass_b,
+                np.broadcast_to(self.ibody, (B, 3)) if self.ibody_b is None else self.ibody_b,
+                np.full(B, self.mu) if self.mu_b is None else self.mu_b)
+
     def step(self, effort, contact_state, p_des, v_des):
         B, h = self.B, self.h
-        mass = np.full(B, self.mass) if self.mass_b is None else self.mass_b
-        ibody = np.broadcast_to(self.ibody, (B, 3)) if self.ibody_b is None else self.ibody_b
-        mu = np.full(B, self.mu) if self.mu_b is None else self.mu_b
+        mass, ibody, mu = self.own()
         tau = np.asarray(effort, f64).reshape(B, 4, 3)
         stance = np.asarray(contact_state).reshape(B, 4) > 0
         p, v, q, w, c = self.p.copy(), self.v.copy(), self.q.copy(), self.w.copy(), self.foot.copy()
@@ -58,31 +63,9 @@ class VariedPlantModel(PM.PlantModel):
                 f = np.where(stance[..., None], PM.stance_force(R, rb, tau, mu[:, None], self.geom), 0.0)      # 2a
                 fb = PM.mulT(R[:, None, :], f)
                 m = PM.cross(rb, fb)
-                F = (f[:, 0] + f[:, 1]) + (f[:, 2] + f[:, 3])
-                N = (m[:, 0] + m[:, 1]) + (m[:, 2] + m[:, 3])
-                if self.force is not None:                                                                     # 2b
-                    F = F + self.force
-                if self.torque is not None:
-                    N = N + self.torque
-                vdot = np.stack([F[:, 0] / mass, F[:, 1] / mass, F[:, 2] / mass - PM.GRAVITY], 1)              # 2c
-                Iw = ibody * w
-                wIw = PM.cross(w, Iw)
-                v = v + h * vdot
-                w = w + h * ((N - wIw) / ibody)
-                p = p + h * v
-                wn = np.sqrt((w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1]) + w[:, 2] * w[:, 2])
-                a = wn * h
-                small = a < 1e-12
-                d0 = np.where(small, 1.0, np.cos(0.5 * a))
-                ds = np.where(small, 0.5 * h, np.sin(0.5 * a) / wn)
-                d1, d2, d3 = ds * w[:, 0], ds * w[:, 1], ds * w[:, 2]
-                q0, q1, q2, q3 = (q[:, k] for k in range(4))
-                n0 = ((q0 * d0 - q1 * d1) - q2 * d2) - q3 * d3
-                n1 = ((q0 * d1 + q1 * d0) + q2 * d3) - q3 * d2
-                n2 = ((q0 * d2 - q1 * d3) + q2 * d0) + q3 * d1
-                n3 = ((q0 * d3 + q1 * d2) - q2 * d1) + q3 * d0
-                nn = np.sqrt(((n0 * n0 + n1 * n1) + n2 * n2) + n3 * n3)
-                q = np.stack([n0 / nn, n1 / nn, n2 / nn, n3 / nn], 1)
+                F, N = PM.add_wrench(PM.quad_sum(f), PM.quad_sum(m), self.force, self.torque)                  # 2b
+                p, v, w, vdot = PM.body_update(p, v, w, F, N, mass, ibody, h)                                  # 2c
+                q = PM.quat_step(q, w, h)
             state, motor, c = self._readout(p, v, q, w, c, stance, vdot, np.asarray(p_des).reshape(B, 4, 3),
                                             np.asarray(v_des).reshape(B, 4, 3))
         self.p, self.v, self.q, self.w, self.foot, self.grf, self.stance = p, v, q, w, c, f, stance

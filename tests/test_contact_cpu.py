@@ -6,13 +6,12 @@ import json
 import math
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import contact_cases as CC
+import kernel_resources as KR
 import plant_cases as PC
 import plant_loop as L
 import plant_loop_contact as LC
@@ -22,7 +21,6 @@ import plant_model_terrain as PT
 import terrain_cases as TC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 f32 = np.float32
 GOLD = os.path.join(ROOT, "tests", "golden", "plant_contact_closed_loop_cpu.json")
 
@@ -231,27 +229,17 @@ def test_cpu_closed_loop_with_contact_is_safe_and_is_what_the_fixture_records(mo
 
 # ---- the kernels --------------------------------------------------------------------------------------------------------
 
-@pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="no hipcc")
+# profiles/plant_kernel_resources.txt, qmpc_contact.hip:  VGPRs, AGPRs, SGPR spills, VGPR spills, waves per SIMD
+CONTACT_TABLE = {"qmpc_contact_reset_kernel": (10, 0, 0, 0, 8),
+                 "qmpc_contact_step_kernelILb0ELb0E": (249, 0, 30, 0, 1), "qmpc_contact_step_kernelILb0ELb1E": (249, 0, 30, 0, 1),
+                 "qmpc_contact_step_kernelILb1ELb0E": (256, 11, 59, 0, 1), "qmpc_contact_step_kernelILb1ELb1E": (256, 11, 59, 0, 1)}
+
+
+@KR.no_hipcc
 def test_contact_kernel_resources(tmp_path):
     """The four <VARY, STATS> instantiations of the contact step and the counters' reset compile for gfx950 without
-    scratch, without spills to memory and without LDS (profiles/plant_kernel_resources.txt)."""
-    src = os.path.join(ROOT, "quadruped_ctrl_amd", "csrc", "qmpc_contact.hip")
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-value", "-c", src,
-                          "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "contact.o")],
-                         capture_output=True, text=True, check=True).stderr
-    res, name = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-        for key, pat in (("vgpr", r" VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-                         ("vgpr_spill", r"VGPRs Spill: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and name:
-                res[name][key] = int(m.group(1))
-    step = {k: v for k, v in res.items() if "qmpc_contact_step_kernel" in k}
-    assert len(step) == 4 and len(res) == 5 and any("qmpc_contact_reset_kernel" in k for k in res), sorted(res)
-    for k, v in res.items():
-        print(k, v)
-        assert v["scratch"] == 0 and v["vgpr_spill"] == 0 and v["lds"] == 0, (k, v)
+    scratch, without spills to memory and without LDS, and within their rows of profiles/plant_kernel_resources.txt."""
+    res = KR.kernel_resources("qmpc_contact.hip", tmp_path)
+    assert len(res) == 5 and sum("qmpc_contact_step_kernel" in k for k in res) == 4, sorted(res)
+    assert all(v["vgpr_spill"] == 0 for v in res.values()), res
+    KR.hold(res, CONTACT_TABLE)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import field_cases as FC
+import kernel_resources as KR
 import plant_loop as L
 import plant_loop_field as LF
 import plant_loop_terrain as LT
@@ -315,28 +316,20 @@ def test_cpu_closed_loop_on_the_field_is_safe_and_is_what_the_fixture_records(ki
 
 # ---- the kernels --------------------------------------------------------------------------------------------------------
 
+# profiles/plant_kernel_resources.txt, qmpc_field.hip:  VGPRs, AGPRs, SGPR spills, VGPR spills (to AGPRs), waves per SIMD
+FIELD_TABLE = {"qmpc_field_init_kernel": (102, 0, 0, 0, 4),
+               "qmpc_field_step_kernelILb0ELb0E": (255, 2, 26, 0, 1), "qmpc_field_step_kernelILb0ELb1E": (255, 2, 26, 0, 1),
+               "qmpc_field_step_kernelILb1ELb0E": (256, 26, 40, 0, 1), "qmpc_field_step_kernelILb1ELb1E": (256, 26, 40, 0, 1),
+               "qmpc_field_contact_step_kernelILb0ELb0E": (255, 4, 31, 0, 1), "qmpc_field_contact_step_kernelILb0ELb1E": (255, 4, 31, 0, 1),
+               "qmpc_field_contact_step_kernelILb1ELb0E": (256, 30, 72, 4, 1), "qmpc_field_contact_step_kernelILb1ELb1E": (256, 30, 72, 4, 1)}
+
+
 @no_hipcc
 def test_field_kernel_resources(tmp_path):
     """The reset on the field and the four <VARY, STATS> instantiations of each step compile for gfx950 without scratch
-    and without LDS, and the kernels the plant launched before are where they were: no kernel of qmpc_field.hip's in the
-    other files."""
-    src = os.path.join(ROOT, "quadruped_ctrl_amd", "csrc", "qmpc_field.hip")
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-value", "-c", src,
-                          "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "field.o")],
-                         capture_output=True, text=True, check=True).stderr
-    res, name = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-        for key, pat in (("vgpr", r" VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-                         ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and name:
-                res[name][key] = int(m.group(1))
+    and without LDS, within their rows of profiles/plant_kernel_resources.txt, and the kernels the plant launched before
+    are where they were: no kernel of qmpc_field.hip's in the other files."""
+    res = KR.kernel_resources("qmpc_field.hip", tmp_path)
     assert len(res) == 9 and sum("qmpc_field_step_kernel" in k for k in res) == 4 \
-        and sum("qmpc_field_contact_step_kernel" in k for k in res) == 4 and any("qmpc_field_init_kernel" in k for k in res), sorted(res)
-    for k, v in res.items():
-        print(k, v)
-        assert v["scratch"] == 0 and v["lds"] == 0, (k, v)
+        and sum("qmpc_field_contact_step_kernel" in k for k in res) == 4, sorted(res)
+    KR.hold(res, FIELD_TABLE)

@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import kernel_resources as KR
 import plant_cases as PC
 import plant_loop as L
 import plant_loop_varied as LV
@@ -188,29 +189,18 @@ def test_kernel_choice_for_every_binding(tmp_path):
     assert [g["counters"] for g in got] == [w[1] for w in want]
 
 
-@pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="no hipcc")
+# profiles/plant_kernel_resources.txt, qmpc_plant.hip:  VGPRs, AGPRs, SGPR spills, VGPR spills, waves per SIMD
+PLANT_TABLE = {"qmpc_plant_init_kernel": (98, 0, 0, 0, 4), "qmpc_plant_stats_reset_kernel": (6, 0, 0, 0, 8),
+               "qmpc_plant_step_kernelILb0ELb0E": (221, 0, 15, 0, 2), "qmpc_plant_step_kernelILb0ELb1E": (221, 0, 15, 0, 2),
+               "qmpc_plant_step_kernelILb1ELb0E": (243, 0, 41, 0, 2), "qmpc_plant_step_kernelILb1ELb1E": (243, 0, 41, 0, 2)}
+
+
+@KR.no_hipcc
 def test_plant_kernel_resources(tmp_path):
     """Every plant kernel -- init, the statistics' reset and the four <VARY, STATS> instantiations of the step --
-    compiles for gfx950 without scratch, and the plain step keeps the 221 VGPRs INTEGRATION.md G records for it."""
-    src = os.path.join(ROOT, "quadruped_ctrl_amd", "csrc", "qmpc_plant.hip")
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-value", "-c", src,
-                          "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "plant.o")],
-                         capture_output=True, text=True, check=True).stderr
-    res, name = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-        for key, pat in (("vgpr", r" VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-                         ("vgpr_spill", r"VGPRs Spill: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and name:
-                res[name][key] = int(m.group(1))
-    step = {k: v for k, v in res.items() if "qmpc_plant_step_kernel" in k}
-    assert len(res) == 6 and len(step) == 4, sorted(res)
-    for k, v in res.items():
-        print(k, v)
-        assert v["scratch"] == 0 and v["vgpr_spill"] == 0 and v["lds"] == 0, (k, v)
-    plain = [v for k, v in step.items() if "ILb0ELb0E" in k]
-    assert len(plain) == 1 and plain[0]["vgpr"] <= 221, plain
+    compiles for gfx950 without scratch, spill to memory or LDS, and within its row of profiles/plant_kernel_resources.txt:
+    the plain step keeps the 221 VGPRs INTEGRATION.md G records for it."""
+    res = KR.kernel_resources("qmpc_plant.hip", tmp_path)
+    assert len(res) == 6 and sum("qmpc_plant_step_kernel" in k for k in res) == 4, sorted(res)
+    assert all(v["vgpr_spill"] == 0 for v in res.values()), res
+    KR.hold(res, PLANT_TABLE)

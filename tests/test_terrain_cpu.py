@@ -5,12 +5,11 @@ kernels' registers and scratch."""
 import json
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import kernel_resources as KR
 import plant_cases as PC
 import plant_loop as L
 import plant_loop_terrain as LT
@@ -21,7 +20,6 @@ import terrain_cases as TC
 from plant_cases import none as _none
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 f32 = np.float32
 MODEL_KEYS = ("p", "v", "q", "w", "foot", "grf", "stance", "state", "motor")
 
@@ -253,27 +251,18 @@ def test_cpu_closed_loop_on_terrain_is_safe_and_is_what_the_fixture_records(mode
     assert np.array_equal(np.asarray(rec[path]["left_flight"]), info["travel"] > np.where(stairs, LT.START + rows[:, 5] * rows[:, 4], np.inf))
 
 
-@pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="no hipcc")
+# profiles/plant_kernel_resources.txt, qmpc_terrain.hip:  VGPRs, AGPRs, SGPR spills, VGPR spills, waves per SIMD
+TERRAIN_TABLE = {"qmpc_terrain_init_kernel": (100, 0, 0, 0, 4),
+                 "qmpc_terrain_step_kernelILb0ELb0E": (247, 0, 17, 0, 2), "qmpc_terrain_step_kernelILb0ELb1E": (247, 0, 17, 0, 2),
+                 "qmpc_terrain_step_kernelILb1ELb0E": (255, 10, 31, 0, 1), "qmpc_terrain_step_kernelILb1ELb1E": (255, 10, 31, 0, 1)}
+
+
+@KR.no_hipcc
 def test_terrain_kernel_resources(tmp_path):
     """Every terrain kernel -- the reset on terrain and the four <VARY, STATS> instantiations of the step -- compiles
-    for gfx950 without scratch, without spills to memory and without LDS (profiles/plant_kernel_resources.txt)."""
-    src = os.path.join(ROOT, "quadruped_ctrl_amd", "csrc", "qmpc_terrain.hip")
-    out = subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-value", "-c", src,
-                          "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "terrain.o")],
-                         capture_output=True, text=True, check=True).stderr
-    res, name = {}, None
-    for line in out.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-        for key, pat in (("vgpr", r" VGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-                         ("vgpr_spill", r"VGPRs Spill: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and name:
-                res[name][key] = int(m.group(1))
-    step = {k: v for k, v in res.items() if "qmpc_terrain_step_kernel" in k}
-    assert len(res) == 5 and len(step) == 4 and any("qmpc_terrain_init_kernel" in k for k in res), sorted(res)
-    for k, v in res.items():
-        print(k, v)
-        assert v["scratch"] == 0 and v["vgpr_spill"] == 0 and v["lds"] == 0, (k, v)
+    for gfx950 without scratch, without spills to memory and without LDS, and within its row of
+    profiles/plant_kernel_resources.txt."""
+    res = KR.kernel_resources("qmpc_terrain.hip", tmp_path)
+    assert len(res) == 5 and sum("qmpc_terrain_step_kernel" in k for k in res) == 4, sorted(res)
+    assert all(v["vgpr_spill"] == 0 for v in res.values()), res
+    KR.hold(res, TERRAIN_TABLE)
