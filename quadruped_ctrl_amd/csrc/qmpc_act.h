@@ -1,5 +1,5 @@
 // qmpc_act.h -- device state, launch arguments and launchers of the actuator stage (include/qmpc_act.h), shared by
-// qmpc_act.hip (kernels) and qmpc_capi.cpp (entry points).  The per-robot arrays are views into one allocation made by
+// qmpc_act.hip (kernels) and qmpc_capi_stages.cpp (entry points).  The per-robot arrays are views into one allocation made by
 // qmpc_act_init for the handle's max_batch; the ring is an allocation of its own.
 #ifndef QMPC_ACT_DEV_H
 #define QMPC_ACT_DEV_H
@@ -42,7 +42,7 @@ struct QmpcActArgs {
   double dt;
 };
 
-// Launchers of qmpc_act.hip, declared once for the file that defines them and for qmpc_capi.cpp, which calls them: a
+// Launchers of qmpc_act.hip, declared once for the file that defines them and for qmpc_capi_stages.cpp, which calls them: a
 // signature that drifts fails to compile.
 // one control period; effort_out may be effort_in
 extern "C" hipError_t qmpc_launch_act(const QmpcActArgs* A, const double* effort_in, double* effort_out, int batch,

@@ -1,0 +1,344 @@
+// qmpc_capi_ctrl.cpp -- host side of include/qmpc_ctrl.h (the batched locomotion controller; the kernels are in
+// qmpc_glue.hip) and of include/qmpc_fleet.h (the closed loop of controller and plant; the kernel is in qmpc_span.hip).
+#include <cstring>
+
+#include "../../include/qmpc_debug.h"  // qmpc_debug_ctrl_read
+#include "../../include/qmpc_plant.h"  // qmpc_plant_step: the fleet run's fallback is the per-tick calls themselves
+#include "qmpc_host.h"
+#include "qmpc_span.h"  // the fleet run's plan (host-only) and the span kernel's launcher
+using namespace qmpc_host;
+
+size_t qmpc_host::carve(QmpcCtrlDev& d, char* base, int M) {
+  size_t off = 0;
+  QMPC_CTRL_ARRAYS(QMPC_CARVE)
+  return off;
+}
+
+// Where a reset robot's counter restarts (qmpc_ctrl_reset, and both episode managers'): in lockstep at T mod 13 (the
+// batch keeps solving on the same ticks), with the per-robot schedule at 0, as init_controller leaves it.  A reset
+// starts the controller (qmpc_ctrl_set_schedule's window closes).
+int qmpc_host::ctrl_reset_counter0(qmpc_ctx::Ctrl* k) {
+  k->started = true;
+  return k->schedule == QMPC_CTRL_PER_ROBOT ? 0 : (int)(k->ticks % 13);
+}
+
+// The controller's reset of the masked robots (qmpc_ctrl_reset, and the episode manager's).
+int qmpc_host::ctrl_reset_enqueue(qmpc_ctx* c, int batch, const uint8_t* mask_dev, hipStream_t stream) {
+  qmpc_ctx::Ctrl* k = c->ctrl.get();
+  const int counter0 = ctrl_reset_counter0(k);
+  HIP_TRY(c, qmpc_launch_ctrl_init(&k->d, mask_dev, counter0, batch, stream));
+  return QMPC_OK;
+}
+
+namespace {
+
+int ctrl_check(qmpc_ctx* c, int batch) {
+  if (!c) return QMPC_ERR_ARG;
+  if (!ctrl_ready(c)) return QMPC_ERR_STATE;
+  if (batch != c->ctrl->batch) return QMPC_ERR_ARG;
+  return QMPC_OK;
+}
+
+// The solve of an MPC tick, behind the locomotion stage that wrote the command rows (and, with the per-robot schedule, the
+// list of due robots): the per-tick path's and the fleet run's.  This and ctrl_after_prework are called as qmpc_host.h's
+// *_enqueue are: with the DeviceGuard held and the stream ordered.
+int ctrl_solve_enqueue(qmpc_ctx* c, int batch, hipStream_t stream) {
+  qmpc_ctx::Ctrl* k = c->ctrl.get();
+  const QmpcCtrlDev& d = k->d;
+  const bool per_robot = k->schedule == QMPC_CTRL_PER_ROBOT;
+  const bool aio = k->robot_mode == 1;  // (per_robot holds: qmpc_ctrl_set_robot_mode)
+  qmpc_command cmd{};
+  cmd.position = d.position;
+  cmd.v_world = d.v_world;
+  cmd.omega_world = d.omega_world;
+  cmd.orientation = d.orientation;
+  cmd.rpy = d.rpy;
+  cmd.r_body = d.r_cmd;
+  cmd.p_foot = d.p_foot;
+  cmd.vel_des = d.vel_des;
+  cmd.yaw_des_true = d.yaw_des_true;
+  cmd.rpy_comp = d.rpy_comp;
+  cmd.stand_traj = d.stand_traj;
+  cmd.rp_des = nullptr;  // _roll_des = _pitch_des = 0 (:112-113)
+  cmd.gait_type = d.current_gait;
+  // robot mode 1: the ten rows the horizon-10 solve reads of the robot's own table, as a 10-segment gait (qmpc_glue.hip:
+  // qmpc_ctrl_window_gait); gait_type is 9 for every due robot there
+  cmd.gait_offsets = aio ? d.mpc_offsets : d.offsets;
+  cmd.gait_durations = aio ? d.mpc_durations : d.durations;
+  cmd.gait_iteration = d.iteration;
+  cmd.world_position_desired = d.wpd;
+  cmd.x_comp_integral = d.xci;
+  cmd.body_height = 0.25f;  // _SetupCommand (:79)
+  cmd.omni_mode = 0;        // per robot through r_cmd
+  qmpc_outputs out{d.grf, nullptr, d.status, nullptr};
+  return solve_impl(c, batch, nullptr, &cmd, &out, nullptr, stream, per_robot ? d.due_list : nullptr,
+                    per_robot ? d.due_count : nullptr);
+}
+
+// A tick after its pre_work, whichever estimators that ran: the locomotion kernel, the solve by the handle's schedule, the
+// leg commands.
+int ctrl_after_prework(qmpc_ctx* c, int batch, double* effort, hipStream_t stream) {
+  qmpc_ctx::Ctrl* k = c->ctrl.get();
+  const QmpcCtrlDev& d = k->d;
+  const bool per_robot = k->schedule == QMPC_CTRL_PER_ROBOT;
+  const bool aio = k->robot_mode == 1;  // (per_robot holds: qmpc_ctrl_set_robot_mode)
+  if (aio) HIP_TRY(c, qmpc_launch_ctrl_loco_aio(&d, batch, stream));
+  else HIP_TRY(c, qmpc_launch_ctrl_loco(&d, batch, per_robot ? 1 : 0, stream));
+  // the locomotion kernel advances every robot's counter: T follows it here, before the launches that can still fail,
+  // so that the host's MPC schedule and the device's `counter % 13` test never disagree
+  // lockstep: every robot's incremented counter is a multiple of 13 on the same ticks, known from T alone.
+  // per-robot schedule: nothing depends on T -- every tick enqueues the solve over the list of due robots the locomotion
+  // kernel has just built (d.due_list, d.due_count[0]); a tick on which nobody is due costs launches that find no entry
+  const bool mpc_tick = (++k->ticks % 13 == 0) || per_robot;
+  if (mpc_tick)
+    if (const int rc = ctrl_solve_enqueue(c, batch, stream)) return rc;
+  HIP_TRY(c, qmpc_launch_ctrl_legcmd(&d, effort, batch, stream));
+  return QMPC_OK;
+}
+
+// The one body of qmpc_ctrl_prework / _tick and their _state pair: pre_work through the estimator launch `est`, then, when
+// `tick`, the rest of the tick.
+//   qmpc_launch_ctrl_est (in = imu): orientation estimator + leg data, then the Kalman filter (previous tick's leg data and
+//   contact phase);  qmpc_launch_ctrl_est_state (in = simulator ground truth): the cheater estimators + leg data in one
+//   launch, no filter
+using EstLaunch = hipError_t (*)(const QmpcCtrlDev*, const float*, const double*, const double*, int, hipStream_t);
+int ctrl_tick(qmpc_ctx* c, int batch, EstLaunch est, const double* in, const double* motor, double* effort, bool tick,
+              void* stream_) {
+  if (const int rc = ctrl_check(c, batch)) return rc;
+  if (!in || !motor || (tick && !effort)) return QMPC_ERR_ARG;
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  if (tick) c->ctrl->started = true;
+  const QmpcCtrlDev& d = c->ctrl->d;
+  HIP_TRY(c, est(&d, c->leg_geom, in, motor, batch, q.stream));
+  if (est == qmpc_launch_ctrl_est) {
+    qmpc_kf_state st{d.xhat, d.P, d.r_body, d.a_world, d.omega_body, d.contact_phase, d.kf_p, d.kf_v,
+                     d.position, d.v_world, d.v_body};
+    HIP_TRY(c, qmpc_launch_kf(&st, kAbadLocation, batch, q.stream));
+  }
+  return tick ? ctrl_after_prework(c, batch, effort, q.stream) : QMPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qmpc_ctrl_init(qmpc_handle c, int batch, double freq, const double pid[4], void* stream_) {
+  if (!c || !pid || batch <= 0 || batch > c->max_batch || !(freq > 0) || c->max_horizon < 14) return QMPC_ERR_ARG;
+  // ConvexMPCLocomotion(1.0 / freq, 13): float dt, dtMPC = dt * iterationsBetweenMPC (:23-42); setup_problem(dtMPC, 14,
+  // 0.4, 120) (:629-630)
+  const float dt = (float)(1.0 / freq);
+  const float dt_mpc = dt * 13;
+  if (const int rc = qmpc_setup(c, (double)dt_mpc, 14, 0.4, 120.0)) return rc;
+  DeviceGuard g(c->device);
+  hipStream_t stream = (hipStream_t)stream_;
+  qmpc_ctx::Ctrl* k = made(c->ctrl);
+  HIP_TRY(c, carve_block(k->buf, k->d, c->max_batch));
+  k->d.dt = dt;
+  k->d.dt_mpc = dt_mpc;
+  k->d.kp_joint = (float)pid[2];  // Vec4<float> ctrlParam (GaitCtrller.cpp:14-16)
+  k->d.kd_joint = (float)pid[3];
+  if (const int rc = order_after_previous(c, stream)) return rc;
+  HIP_TRY(c, qmpc_launch_ctrl_init(&k->d, nullptr, 0, batch, stream));
+  k->batch = batch;
+  k->freq = freq;
+  k->ticks = 0;
+  k->schedule = QMPC_CTRL_LOCKSTEP;
+  k->robot_mode = 0;
+  k->started = false;
+  k->fleet = qmpc_fleet_info{};
+  return QMPC_OK;
+}
+
+int qmpc_ctrl_reset(qmpc_handle c, int batch, const uint8_t* mask_dev, void* stream_) {
+  if (const int rc = ctrl_check(c, batch)) return rc;
+  if (!mask_dev) return QMPC_ERR_ARG;
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  return ctrl_reset_enqueue(c, batch, mask_dev, q.stream);
+}
+
+int qmpc_ctrl_set_schedule(qmpc_handle c, int mode) {
+  if (!c) return QMPC_ERR_ARG;
+  if (!ctrl_ready(c)) return QMPC_ERR_STATE;
+  if (mode != QMPC_CTRL_LOCKSTEP && mode != QMPC_CTRL_PER_ROBOT) return QMPC_ERR_ARG;
+  if (c->ctrl->started) return QMPC_ERR_STATE;
+  if (mode == QMPC_CTRL_LOCKSTEP && c->ctrl->robot_mode == 1) {
+    c->err = "robot mode 1 needs the per-robot schedule (select robot mode 0 first)";
+    return QMPC_ERR_STATE;
+  }
+  c->ctrl->schedule = mode;
+  return QMPC_OK;
+}
+
+int qmpc_ctrl_set_robot_mode(qmpc_handle c, int mode) {
+  if (!c) return QMPC_ERR_ARG;
+  if (!ctrl_ready(c)) return QMPC_ERR_STATE;
+  if (mode != 0 && mode != 1) return QMPC_ERR_ARG;
+  qmpc_ctx::Ctrl* k = c->ctrl.get();
+  if (k->started) return QMPC_ERR_STATE;
+  if (mode == 1 && k->schedule != QMPC_CTRL_PER_ROBOT) {
+    // a robot's counter restarts whenever its gait is re-timed (ConvexMPCLocomotion.cpp:182-224): no common MPC tick
+    c->err = "robot mode 1 needs the per-robot schedule: the handle is in lockstep (qmpc_ctrl_set_schedule first)";
+    return QMPC_ERR_STATE;
+  }
+  // every solve of mode 1 runs at horizonLength 10 (:174, :233), mode 0 at 14: setup_problem(dtMPC,
+  // horizonLength, 0.4, 120) (:629-630).  Host work and a table upload; nothing is enqueued
+  if (const int rc = qmpc_setup(c, (double)k->d.dt_mpc, mode == 1 ? 10 : 14, 0.4, 120.0)) return rc;
+  k->robot_mode = mode;
+  return QMPC_OK;
+}
+
+int qmpc_ctrl_set_gait(qmpc_handle c, int batch, const int32_t* gait_dev, void* stream_) {
+  if (const int rc = ctrl_check(c, batch)) return rc;
+  if (!gait_dev) return QMPC_ERR_ARG;
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  HIP_TRY(c, qmpc_launch_ctrl_set(&c->ctrl->d, gait_dev, nullptr, batch, q.stream));
+  return QMPC_OK;
+}
+
+int qmpc_ctrl_set_vel(qmpc_handle c, int batch, const double* vel_dev, void* stream_) {
+  if (const int rc = ctrl_check(c, batch)) return rc;
+  if (!vel_dev) return QMPC_ERR_ARG;
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  HIP_TRY(c, qmpc_launch_ctrl_set(&c->ctrl->d, nullptr, vel_dev, batch, q.stream));
+  return QMPC_OK;
+}
+
+int qmpc_ctrl_prework(qmpc_handle c, int batch, const double* imu, const double* motor, void* stream) {
+  return ctrl_tick(c, batch, qmpc_launch_ctrl_est, imu, motor, nullptr, false, stream);
+}
+
+int qmpc_ctrl_tick(qmpc_handle c, int batch, const double* imu, const double* motor, double* effort, void* stream) {
+  return ctrl_tick(c, batch, qmpc_launch_ctrl_est, imu, motor, effort, true, stream);
+}
+
+int qmpc_ctrl_prework_state(qmpc_handle c, int batch, const double* state, const double* motor, void* stream) {
+  return ctrl_tick(c, batch, qmpc_launch_ctrl_est_state, state, motor, nullptr, false, stream);
+}
+
+int qmpc_ctrl_tick_state(qmpc_handle c, int batch, const double* state, const double* motor, double* effort,
+                         void* stream) {
+  return ctrl_tick(c, batch, qmpc_launch_ctrl_est_state, state, motor, effort, true, stream);
+}
+
+int qmpc_debug_ctrl_read(qmpc_handle c, const char* name, void* dst, long long cap_bytes, int* per_robot) {
+  if (!c || !name || !dst) return QMPC_ERR_ARG;
+  if (!ctrl_ready(c)) return QMPC_ERR_STATE;
+  const QmpcCtrlDev& d = c->ctrl->d;
+  struct Arr {
+    const char* n;
+    const void* p;
+    int per;
+  };
+#define QMPC_CTRL_ENTRY(T, name, per_robot) {#name, d.name, per_robot},
+  const Arr tab[] = {QMPC_CTRL_ARRAYS(QMPC_CTRL_ENTRY)};
+#undef QMPC_CTRL_ENTRY
+  for (const Arr& a : tab) {
+    if (std::strcmp(a.n, name) != 0) continue;
+    const size_t bytes = (size_t)4 * a.per * (size_t)c->ctrl->batch;
+    if (per_robot) *per_robot = a.per;
+    if (cap_bytes < 0 || (size_t)cap_bytes < bytes) return QMPC_ERR_ARG;
+    DeviceGuard g(c->device);
+    if (c->has_last) HIP_TRY(c, hipStreamSynchronize(c->last_stream));
+    HIP_TRY(c, hipMemcpy(dst, a.p, bytes, hipMemcpyDefault));
+    return QMPC_OK;
+  }
+  return QMPC_ERR_ARG;
+}
+
+int qmpc_ctrl_view_get(qmpc_handle c, qmpc_ctrl_view* v) {
+  if (!c || !v) return QMPC_ERR_ARG;
+  if (!ctrl_ready(c)) return QMPC_ERR_STATE;
+  const QmpcCtrlDev& d = c->ctrl->d;
+  v->position = d.position;
+  v->v_world = d.v_world;
+  v->orientation = d.orientation;
+  v->rpy = d.rpy;
+  v->r_body = d.r_body;
+  v->omega_world = d.omega_world;
+  v->leg_q = d.q;
+  v->leg_p = d.leg_p;
+  v->leg_v = d.leg_v;
+  v->leg_J = d.leg_J;
+  v->contact_state = d.contact_state;
+  v->swing_state = d.swing_state;
+  v->p_des = d.p_des;
+  v->v_des = d.v_des;
+  v->f_ff = d.f_ff;
+  v->safe = d.safe;
+  v->counter = d.counter;
+  v->batch = c->ctrl->batch;
+  v->ticks = (int)c->ctrl->ticks;
+  return QMPC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
+// Fleet run (include/qmpc_fleet.h): qmpc_ctrl_tick_state -> qmpc_plant_step, `ticks` times, with everything between two
+// solves in one launch.  The plan is qmpc_span.h's, the kernel qmpc_span.hip's.
+extern "C" {
+
+int qmpc_fleet_run(qmpc_handle c, int batch, int ticks, double* effort, double* state, double* motor, void* stream_) {
+  if (const int rc = plant_check(c, batch)) return rc;
+  if (ticks < 1 || !effort || !state || !motor) return QMPC_ERR_ARG;
+  qmpc_ctx::Ctrl* k = c->ctrl.get();
+  qmpc_ctx::Plant* pl = c->plant.get();
+  const int reason = (pl->terrain.rows ? QMPC_FLEET_TERRAIN : 0) | (pl->contact.flags ? QMPC_FLEET_CONTACT : 0) |
+                     (pl->field.z ? QMPC_FLEET_FIELD : 0);
+  // (the counts follow what has been enqueued: a call refused here, or one that stops half way, counts no tick it did not
+  //  enqueue)
+  if (reason) {
+    // what the span kernel does not cover: the per-tick calls themselves, so the launches are theirs exactly
+    for (int i = 0; i < ticks; ++i) {
+      if (const int rc = qmpc_ctrl_tick_state(c, batch, state, motor, effort, stream_)) return rc;
+      k->fleet.reason = reason;  // (the call has enqueued something: it is the last call now)
+      if (const int rc = qmpc_plant_step(c, batch, effort, state, motor, stream_)) return rc;
+      ++k->fleet.ticks;
+      ++k->fleet.fallback_ticks;
+    }
+    return QMPC_OK;
+  }
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  k->started = true;
+  k->fleet.reason = 0;
+  const bool per_robot = k->schedule == QMPC_CTRL_PER_ROBOT;
+  const QmpcPlantStepArgs P = plant_step_args(c, batch, effort, state, motor);
+  QmpcSpanArgs A{};
+  A.C = k->d;
+  A.g = QmpcLegGeom{c->leg_geom[0], c->leg_geom[1], c->leg_geom[2], c->leg_geom[3]};
+  A.S = P.S;
+  A.K = P.K;
+  A.effort = effort;
+  A.state = state;
+  A.motor = motor;
+  A.n = P.n;
+  A.V = P.V;
+  A.build_list = per_robot ? 1 : 0;
+  for (const SpanLaunch& l : plan_spans(k->ticks, ticks, per_robot)) {
+    // (a kernel, not a memset node: see fill_ints)
+    if (l.reset_due) HIP_TRY(c, fill_ints(k->d.due_count, 1, 0, q.stream));
+    HIP_TRY(c, qmpc_launch_span(&A, k->robot_mode, pl->bound, pl->stats_on, l.first_at_c, l.ticks, l.last_after_l, q.stream));
+    // T follows the locomotion stages as they are enqueued, in front of the solve that can still fail (ctrl_after_prework)
+    k->ticks += l.locos;
+    k->fleet.ticks += l.locos;
+    k->fleet.fused_ticks += l.locos;
+    ++k->fleet.fused_launches;
+    if (l.solve)
+      if (const int rc = ctrl_solve_enqueue(c, batch, q.stream)) return rc;
+  }
+  return QMPC_OK;
+}
+
+int qmpc_fleet_run_info(qmpc_handle c, qmpc_fleet_info* out) {
+  if (!c || !out) return QMPC_ERR_ARG;
+  if (!ctrl_ready(c)) return QMPC_ERR_STATE;
+  *out = c->ctrl->fleet;
+  return QMPC_OK;
+}
+
+}  // extern "C"

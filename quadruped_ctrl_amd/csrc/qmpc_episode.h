@@ -1,5 +1,5 @@
 // qmpc_episode.h -- device state and launch arguments of the episode manager (include/qmpc_episode.h), shared by
-// qmpc_episode.hip (kernels) and qmpc_capi.cpp (entry points).  Views into one allocation made by qmpc_episode_init for the
+// qmpc_episode.hip (kernels) and qmpc_capi_stages.cpp (entry points).  Views into one allocation made by qmpc_episode_init for the
 // handle's max_batch.
 #ifndef QMPC_EPISODE_DEV_H
 #define QMPC_EPISODE_DEV_H
@@ -38,7 +38,7 @@ struct QmpcEpisodeIn {
   uint32_t key0, key1;   // the seed's low and high word
 };
 
-// Launchers of qmpc_episode.hip, declared once for the file that defines them and for qmpc_capi.cpp, which calls them: a
+// Launchers of qmpc_episode.hip, declared once for the file that defines them and for qmpc_capi_stages.cpp, which calls them: a
 // signature that drifts fails to compile.
 // every array of S zeroed for robots 0 .. max_batch-1 and both log words; start = p_x, p_y for robots 0 .. batch-1
 extern "C" hipError_t qmpc_launch_episode_init(const QmpcEpisodeDev* S, const double* p, int batch, int max_batch,

@@ -1,5 +1,5 @@
 // qmpc_episode_sense.h -- device state and launchers of episodes on the sensor path (include/qmpc_episode_sense.h), shared
-// by qmpc_episode_sense.hip (kernels) and qmpc_capi.cpp (entry points).  Views into one allocation made by
+// by qmpc_episode_sense.hip (kernels) and qmpc_capi_stages.cpp (entry points).  Views into one allocation made by
 // qmpc_episode_sense_init for the handle's max_batch.
 #ifndef QMPC_EPISODE_SENSE_DEV_H
 #define QMPC_EPISODE_SENSE_DEV_H
@@ -23,7 +23,7 @@ struct QmpcEpisodeSenseDev {
 #undef QMPC_EPISODE_SENSE_MEMBER
 };
 
-// Launchers of qmpc_episode_sense.hip, declared once for the file that defines them and for qmpc_capi.cpp, which calls
+// Launchers of qmpc_episode_sense.hip, declared once for the file that defines them and for qmpc_capi_stages.cpp, which calls
 // them: a signature that drifts fails to compile.
 // warm = hold = both = 0 for robots 0 .. max_batch-1
 extern "C" hipError_t qmpc_launch_episode_sense_init(const QmpcEpisodeSenseDev* W, int max_batch, hipStream_t stream);

@@ -114,7 +114,7 @@ __device__ __forceinline__ void qmpc_swing_axis(int axis, float p0, float pf, fl
 // every robot, one row per robot in every array.  Views into two allocations made by qmpc_ctrl_init.
 // The arrays are listed once, as X(element type, name, elements per robot): QmpcCtrlDev's members (in this order -- the
 // struct is passed to kernels by value, so its layout is that of the kernel arguments), their carving out of the
-// allocation (qmpc_capi.cpp: ctrl_carve) and the names of qmpc_debug_ctrl_read are generated from the list.
+// allocation (qmpc_capi_ctrl.cpp: carve) and the names of qmpc_debug_ctrl_read are generated from the list.
 #define QMPC_CTRL_ARRAYS(X)                                                                                            \
   /* inputs of the tick, rounded to float like VectorNavData / LegData (GaitCtrller.cpp:34-56) */                      \
   X(float, q, 12)                 /* datas[leg].q (clamped by checkJointLimit) */                                      \
@@ -367,7 +367,7 @@ __device__ __forceinline__ void qmpc_ctrl_init_robot(const QmpcCtrlDev& S, const
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Launchers of qmpc_glue.hip, declared once: qmpc_glue.hip (which defines them) and qmpc_capi.cpp (which calls them)
+// Launchers of qmpc_glue.hip, declared once: qmpc_glue.hip (which defines them) and the host units qmpc_capi*.cpp (which call them)
 // both read these lines, so a signature that drifts fails to compile.
 extern "C" hipError_t qmpc_launch_leg_kin(const float geom[4], const float* q, const float* qd, float* J, float* p,
                                           float* v, int batch, hipStream_t stream);

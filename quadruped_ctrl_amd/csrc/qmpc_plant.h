@@ -1,5 +1,5 @@
 // qmpc_plant.h -- device state of the reduced-order plant (include/qmpc_plant.h), shared by qmpc_plant.hip (kernels)
-// and qmpc_capi.cpp (entry points).  Views into one allocation made by qmpc_plant_init for the handle's max_batch.
+// and qmpc_capi_plant.cpp (entry points).  Views into one allocation made by qmpc_plant_init for the handle's max_batch.
 #ifndef QMPC_PLANT_DEV_H
 #define QMPC_PLANT_DEV_H
 
@@ -91,7 +91,7 @@ struct QmpcFieldArgs {
 #define QMPC_PLANT_KNEE_MIN 0.05    /* the swing clamp's shell, as knee angles */
 #define QMPC_PLANT_KNEE_MAX 2.6
 
-// The arguments of a step, filled in one place (qmpc_capi.cpp: plant_step_args) and given to every step launcher.  The
+// The arguments of a step, filled in one place (qmpc_capi_plant.cpp: plant_step_args) and given to every step launcher.  The
 // contact kernels take this struct itself, by value: it IS their kernarg segment, which they read a second time
 // (qmpc_contact_step_body.h), so a member a kernel does not read costs it kernarg bytes and no instruction.  The
 // scheduled-contact kernels keep separate parameters (profiles/plant_kernel_resources.txt); their launchers spread the
@@ -121,7 +121,7 @@ struct QmpcPlantResetArgs {
   QmpcFieldArgs Fd;   // qmpc_launch_terrain_init does not read Fd
 };
 
-// Launchers, declared once for the files that define them and for qmpc_capi.cpp, which calls them: a signature that
+// Launchers, declared once for the files that define them and for qmpc_capi_plant.cpp (the resets: qmpc_capi_stages.cpp too), which calls them: a signature that
 // drifts fails to compile.  One step and one reset launcher per entry of qmpc_plant_pick.h's lists, all of one signature;
 // vary (per-robot parameters bound) and stats (statistics on) pick the step's instantiation.
 #define QMPC_PLANT_DECLARE(NAME, name)                                                                             \

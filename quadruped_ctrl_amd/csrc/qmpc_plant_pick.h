@@ -2,7 +2,7 @@
 // HIP, no device: tests/plant_pick_dump.cpp includes this header alone and prints the choice for every combination.
 //
 // The two lists below are the only lists of the plant's step and reset kernels: qmpc_plant.h declares one launcher per
-// entry, qmpc_capi.cpp builds its launcher tables from them in the enums' order.  A new step kernel is one entry in
+// entry, qmpc_capi_plant.cpp builds its launcher tables from them in the enums' order.  A new step kernel is one entry in
 // QMPC_PLANT_STEP_KINDS, its launcher, and its line in qmpc_plant_pick.
 #ifndef QMPC_PLANT_PICK_H
 #define QMPC_PLANT_PICK_H

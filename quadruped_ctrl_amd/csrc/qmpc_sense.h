@@ -1,5 +1,5 @@
 // qmpc_sense.h -- launch arguments of the sensor model (include/qmpc_sense.h), shared by qmpc_sense.hip (kernels) and
-// qmpc_capi.cpp (entry points).
+// qmpc_capi_stages.cpp (entry points).
 #ifndef QMPC_SENSE_DEV_H
 #define QMPC_SENSE_DEV_H
 
@@ -24,7 +24,7 @@ struct QmpcSenseArgs {
 // channel numbers of a robot (the third counter word of the generator)
 enum { QMPC_SENSE_CH_ACC = 0, QMPC_SENSE_CH_GYRO = 3, QMPC_SENSE_CH_Q = 6, QMPC_SENSE_CH_QD = 18 };
 
-// Launchers of qmpc_sense.hip, declared once for the file that defines them and for qmpc_capi.cpp, which calls them: a
+// Launchers of qmpc_sense.hip, declared once for the file that defines them and for qmpc_capi_stages.cpp, which calls them: a
 // signature that drifts fails to compile.
 extern "C" hipError_t qmpc_launch_sense(const QmpcSenseArgs* A, double* imu_out, double* motor_out, int batch, int noisy,
                                         hipStream_t stream);

@@ -7,7 +7,7 @@
 // state and motor are as the last P left them), so the first span of a call starts at E and the last one stops behind P.
 //
 // The first part is host-only integer logic in the manner of qmpc_plan.h: no HIP, no handle, no device pointer;
-// tests/span_dump.cpp compiles it alone.  The second part (HIP only) is what qmpc_span.hip defines and qmpc_capi.cpp calls.
+// tests/span_dump.cpp compiles it alone.  The second part (HIP only) is what qmpc_span.hip defines and qmpc_capi_ctrl.cpp calls.
 #ifndef QMPC_SPAN_H
 #define QMPC_SPAN_H
 
@@ -57,7 +57,7 @@ inline std::vector<SpanLaunch> plan_spans(long long T, int ticks, bool per_robot
 #include "qmpc_glue.h"
 #include "qmpc_plant.h"
 
-// The arguments of a span launch, filled in one place (qmpc_capi.cpp: qmpc_fleet_run).  The plant's part is the flat
+// The arguments of a span launch, filled in one place (qmpc_capi_ctrl.cpp: qmpc_fleet_run).  The plant's part is the flat
 // step's (QmpcPlantStepArgs without terrain, contact and field); effort, state and motor are the caller's rows, read AND
 // written by the launch.  n = batch * 4 lanes.
 struct QmpcSpanArgs {

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(QMPC_SPAN_WG) void qmpc_span_kernel(const QmpcCtrlD
   const QmpcTerrainArgs T{};
   constexpr bool FIELD = false;
   const QmpcFieldArgs Fd{};
-  // what P reads of the controller (qmpc_capi.cpp: plant_step_args)
+  // what P reads of the controller (qmpc_capi_plant.cpp: plant_step_args)
   const float* contact_state = Cd.contact_state;
   const float* p_des = Cd.p_des;
   const float* v_des = Cd.v_des;

@@ -401,7 +401,7 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
                     "log_rows_written": int(len(lg["rows"])), "log_dropped": int(lg["dropped"])})
     if sensed is not None:
         # what one qmpc_episode_sense_step enqueues here, by include/qmpc_episode_sense.h's list (a count from the
-        # configuration, not a trace: it follows qmpc_capi.cpp's entry point by hand): decision, re-initialisation,
+        # configuration, not a trace: it follows qmpc_capi_stages.cpp's entry point by hand): decision, re-initialisation,
         # commands, plant reset (+ the contact counters'), statistics' reset (while on), sensors' reset
         held = np.array([int(x) for x in torch.stack(held_seen).cpu()])[keep]
         res.update({"warm": warm, "launches_per_episode_step": 5 + int(bool(contact)) + int(bool(vary)),
