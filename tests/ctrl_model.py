@@ -148,6 +148,29 @@ def yaw_inverse_quat(yaw):
     return q
 
 
+def fk64(q, leg, g=G.GEOM.astype(np.float64)):
+    """Independent fp64 forward kinematics from the leg geometry: abad rotation about x, hip and knee
+    about y (Mini Cheetah convention of computeLegJacobianAndPosition)."""
+    l1, l2, l3, l4 = g
+    side = -1.0 if leg % 2 == 0 else 1.0
+    s1, c1 = np.sin(q[0]), np.cos(q[0])
+    s2, c2 = np.sin(q[1]), np.cos(q[1])
+    s23, c23 = np.sin(q[1] + q[2]), np.cos(q[1] + q[2])
+    x = l3 * s23 + l2 * s2
+    zz = -(l3 * c23 + l2 * c2)          # leg-plane "down" before the abad rotation
+    yy = (l1 + l4) * side
+    return np.array([x, yy * c1 - zz * s1, yy * s1 + zz * c1])
+
+
+def calm_est(B, rng, roll=0.0):
+    """An estimator read-out of B robots standing calmly: what loco() takes where no estimator runs."""
+    return dict(position=np.stack([rng.normal(0, .1, B), rng.normal(0, .1, B), rng.uniform(.2, .3, B)], 1).astype(f32),
+                v_world=rng.normal(0, .5, (B, 3)).astype(f32),
+                rpy=np.stack([np.full(B, roll), rng.normal(0, .02, B), rng.normal(0, 1, B)], 1).astype(f32),
+                r_body=np.tile(np.eye(3, dtype=f32).reshape(1, 9), (B, 1)),
+                leg_p=np.tile(np.array([0, 0, -.28], f32), (B, 4)), leg_q=np.tile(np.array([0, -.8, 1.6], f32), (B, 4)))
+
+
 # the commands of the GPU suites' runs (tests/test_gpu_controller.py and the files that follow it)
 def command_gaits(B, t, switch_at):
     """Every gait number 0 .. 11 and its omni variant, switched part-way (into and out of standing)."""

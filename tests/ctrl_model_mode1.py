@@ -31,6 +31,24 @@ MPC_HORIZON = 10          # `int h = 10` (:174): horizonLength of every tick tha
 NSEG_AIO = 14             # the aio gait's constructor (:41)
 
 
+NSEGS = {10, 11, 12, 13, 14, 16}   # the segment counts the six cases reach
+
+# x commands of the six cases (:179-231): standing, turning on the spot (yaw 0.5), walking, walk-to-trot, trot, and
+# the fast trot's four segment counts 13 (42 - 28.4 = 13.6), 12 (42 - 29.6 = 12.4), 11 (42 - 30.4 = 11.6), 10 (42 - 35 < 10)
+SWEEP_X = (0.0, 0.0, 0.1, 0.32, 0.8, 1.42, 1.48, 1.52, 1.75)
+SWEEP_YAW = (0.0, 0.5, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+
+
+def sweep_vel(B, segment):
+    """Robot b's command in segment `segment`: case (b + 2 * segment) % 9; every fourth robot adds a y command."""
+    k = (np.arange(B) + 2 * segment) % len(SWEEP_X)
+    v = np.zeros((B, 3))
+    v[:, 0] = np.array(SWEEP_X)[k]
+    v[:, 2] = np.array(SWEEP_YAW)[k]
+    v[(np.arange(B) % 4 == 3) & (v[:, 0] > 0), 1] = 0.25       # vBody = |x| + y * y: + 0.0625
+    return v
+
+
 def aio_select(xv, yv, yr):
     """The phase-0 branch (:179-231) for scalars float32 -> (h, offsets, durations, gaitNumber)."""
     xv, yv, yr = f32(xv), f32(yv), f32(yr)

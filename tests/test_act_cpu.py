@@ -16,17 +16,12 @@ import pytest
 import act_cases as AC
 import act_model as AM
 import plant_loop as L
+from c_headers import members
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 no_hipcc = pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="no hipcc")
 GOLD = os.path.join(ROOT, "tests", "golden", "act_closed_loop_cpu.json")
-
-
-def _members(hdr, struct):
-    body = re.search(r"typedef struct \{([^}]*)\} %s;" % struct, hdr).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    return [n for decl in body.split(";") if decl.strip() for n in re.findall(r"\*?(\w+)(?:\[\d+\])?\s*(?:,|$)", decl.strip())]
 
 
 def test_act_symbols_exported_and_abi_version_kept():
@@ -47,7 +42,7 @@ def test_act_symbols_exported_and_abi_version_kept():
     # the structures of the binding follow the header's member order
     for struct, cls in (("qmpc_act_config", binding.ActConfig), ("qmpc_act_params", binding.ActParams),
                         ("qmpc_act_view", binding.ActView)):
-        assert _members(hdr, struct) == [n for n, _ in cls._fields_], struct
+        assert members(hdr, struct) == [n for n, _ in cls._fields_], struct
     assert list(AM.PARAMS) == list(binding.ACT_PARAM_FIELDS) and AM.ACCUMULATORS == binding.ACT_STATS
     assert int(re.search(r"#define QMPC_ACT_MAX_DELAY (\d+)", hdr).group(1)) == AM.MAX_DELAY == binding.ACT_MAX_DELAY == 64
     # none of the new symbols went into an older header or list

@@ -3,7 +3,7 @@ and the conditions its streams and poses have to meet there.
 
   * oracle/kron_model.assemble (mass, ibody, gravity, dt, the closed form the kernel shares) against a brute-force fp64
     condensation written from the reference's ct_ss_mats -> c2qp -> qH, qg (SolverMPC.cpp:64-125, 226-267, 296-399);
-  * oracle.glue's forward and inverse kinematics at the second geometry against tests/test_glue_cpu.py's fp64 FK;
+  * oracle.glue's forward and inverse kinematics at the second geometry against tests/ctrl_model.py's fp64 FK (fk64);
   * tests/plant_model.py's closed forms (tests/test_plant_cpu.py) with the second body, geometry, frequency and friction;
   * tests/ctrl_model.py at 400 Hz and 1000 Hz: no latch, stance / swing edges, the swing time.
 """
@@ -18,8 +18,9 @@ from quadruped_ctrl_amd import workloads as W
 import ctrl_model as M
 import plant_cases as PC
 import plant_model as PM
+from ctrl_model import fk64
 from second_robot import F_MAX2, GEOM2_F, GRAVITY2, IBODY2, MASS2, PLANT2, SOLVE2
-from test_glue_cpu import fk64
+
 
 PID = (0.0, 0.0, 3.0, 0.3)
 

@@ -19,14 +19,11 @@ import plant_model as PM
 import plant_model_contact as PCM
 import plant_model_terrain as PT
 import terrain_cases as TC
+from c_headers import declared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 GOLD = os.path.join(ROOT, "tests", "golden", "plant_contact_closed_loop_cpu.json")
-
-
-def _decl(name):
-    return set(re.findall(r"^int (qmpc_\w+)\(", open(os.path.join(ROOT, "include", name)).read(), re.M))
 
 
 def _fields(hdr, struct):
@@ -39,7 +36,7 @@ def test_contact_symbols_exported_and_abi_version_kept():
     lib = binding.load_library()
     hdr = open(os.path.join(ROOT, "include", "qmpc_contact.h")).read()
     want = {"qmpc_plant_set_contact", "qmpc_contact_view_get"}
-    assert _decl("qmpc_contact.h") == want == set(binding.CONTACT_EXPORTS)
+    assert declared("qmpc_contact.h") == want == set(binding.CONTACT_EXPORTS)
     for name in want:
         assert hasattr(lib, name), name
     assert lib.qmpc_abi_version() == binding.ABI_VERSION == 23
@@ -48,8 +45,8 @@ def test_contact_symbols_exported_and_abi_version_kept():
     assert re.search(r"QMPC_CONTACT_EARLY = 1, QMPC_CONTACT_LATE = 2, QMPC_CONTACT_SLIP = 4", hdr)
     assert (binding.CONTACT_EARLY, binding.CONTACT_LATE, binding.CONTACT_SLIP) == (PCM.EARLY, PCM.LATE, PCM.SLIP) == (1, 2, 4)
     # the older headers still declare exactly what they declared
-    assert _decl("qmpc_terrain.h") == {"qmpc_plant_set_terrain", "qmpc_terrain_view_get"} == set(binding.TERRAIN_EXPORTS)
-    assert _decl("qmpc_plant.h") == set(binding.PLANT_EXPORTS) and not want & (_decl("qmpc_plant.h") | _decl("qmpc_terrain.h"))
+    assert declared("qmpc_terrain.h") == {"qmpc_plant_set_terrain", "qmpc_terrain_view_get"} == set(binding.TERRAIN_EXPORTS)
+    assert declared("qmpc_plant.h") == set(binding.PLANT_EXPORTS) and not want & (declared("qmpc_plant.h") | declared("qmpc_terrain.h"))
     # the binding's defaults are the header's
     import inspect
     d = {k: v.default for k, v in inspect.signature(binding.BatchedPlant.set_contact).parameters.items() if k != "self"}

@@ -11,6 +11,8 @@ from oracle import oracle as O
 from quadruped_ctrl_amd import binding
 
 import ctrl_model as M
+from c_headers import binding_agrees_with_ctrl_arrays
+from ctrl_model import calm_est
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
@@ -77,14 +79,6 @@ def test_swing_and_contact_states_match_gait_cpp():
             assert (s > 0).any() and (c > 0).any()
 
 
-def _calm_est(B, rng, roll=0.0):
-    return dict(position=np.stack([rng.normal(0, .1, B), rng.normal(0, .1, B), rng.uniform(.2, .3, B)], 1).astype(f32),
-                v_world=rng.normal(0, .5, (B, 3)).astype(f32),
-                rpy=np.stack([np.full(B, roll), rng.normal(0, .02, B), rng.normal(0, 1, B)], 1).astype(f32),
-                r_body=np.tile(np.eye(3, dtype=f32).reshape(1, 9), (B, 1)),
-                leg_p=np.tile(np.array([0, 0, -.28], f32), (B, 4)), leg_q=np.tile(np.array([0, -.8, 1.6], f32), (B, 4)))
-
-
 def test_counter_and_table_timing():
     """setIterations sees the counter before the increment (:239), updateMPCIfNeeded the incremented one (:375, :387):
     the restatement's MPC ticks are 12, 25, 38 (0-based) on table iterations 0, 1, 2, and the gait phase of tick t is
@@ -92,7 +86,7 @@ def test_counter_and_table_timing():
     rng = np.random.default_rng(3)
     m = M.CtrlModel(2)
     m.set_gait([9, 10])
-    est = _calm_est(2, rng)
+    est = calm_est(2, rng)
     solves = []
     for t in range(40):
         m.loco(est)
@@ -110,7 +104,7 @@ def test_abs_and_sqrt_decisions_are_observable():
     float overload would on a realistic tick (so the GPU test's bit-exact comparison pins the choice)."""
     B = 256
     rng = np.random.default_rng(1)
-    est = _calm_est(B, rng, roll=0.45)
+    est = calm_est(B, rng, roll=0.45)
     out = {}
     for fs in (False, True):
         m = M.CtrlModel(B, float_sqrt=fs)
@@ -147,13 +141,4 @@ def test_controller_symbols_exported():
 
 
 def test_binding_agrees_with_the_controller_array_list():
-    """QMPC_CTRL_ARRAYS (csrc/qmpc_glue.h) is the one list of the controller's device arrays; what the binding still has
-    to know about it (read()'s int32 arrays, view()'s widths and element types) matches it."""
-    src = open(os.path.join(ROOT, "quadruped_ctrl_amd", "csrc", "qmpc_glue.h")).read()
-    body = re.search(r"#define QMPC_CTRL_ARRAYS\(X\)((?:.*\\\n)*.*)", src).group(1)
-    arrays = {n: (t, int(w)) for t, n, w in re.findall(r"X\((\w+), (\w+), (\d+)\)", body)}
-    assert arrays and {t for t, _ in arrays.values()} <= {"float", "int"}   # (read() moves 4-byte elements)
-    assert {n for n, (t, _) in arrays.items() if t == "int"} == set(binding.CTRL_INT_ARRAYS)
-    for k, n in binding.CTRL_VIEW_WIDTH.items():
-        t, w = arrays[dict(leg_q="q").get(k, k)]
-        assert w == n and t == ("int" if k in ("safe", "counter") else "float"), k
+    binding_agrees_with_ctrl_arrays()

@@ -8,8 +8,6 @@ of ConvexMPCLocomotion.cpp:173-233, so this file also pins facts derived from th
     solve rests on -- those ten rows are themselves the table of a 10-segment offset / duration gait.
 """
 import ctypes as C
-import os
-import re
 
 import numpy as np
 
@@ -17,11 +15,11 @@ from quadruped_ctrl_amd import binding
 
 import ctrl_model as M
 import ctrl_model_mode1 as M1
-from test_ctrl_cpu import _calm_est, test_binding_agrees_with_the_controller_array_list as _array_list_agrees
+from c_headers import binding_agrees_with_ctrl_arrays, ctrl_arrays
+from ctrl_model import calm_est
+from ctrl_model_mode1 import NSEGS, sweep_vel
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32, f64 = np.float32, np.float64
-NSEGS = {10, 11, 12, 13, 14, 16}
 
 
 def test_set_robot_mode_exported_and_declared():
@@ -37,10 +35,8 @@ def test_set_robot_mode_exported_and_declared():
 
 
 def test_new_rows_are_in_the_array_list_and_the_binding():
-    _array_list_agrees()                                        # int rows == CTRL_INT_ARRAYS, by test_ctrl_cpu's parser
-    src = open(os.path.join(ROOT, "quadruped_ctrl_amd", "csrc", "qmpc_glue.h")).read()
-    body = re.search(r"#define QMPC_CTRL_ARRAYS\(X\)((?:.*\\\n)*.*)", src).group(1)
-    arrays = {n: (t, int(w)) for t, n, w in re.findall(r"X\((\w+), (\w+), (\d+)\)", body)}
+    binding_agrees_with_ctrl_arrays()                           # int rows == CTRL_INT_ARRAYS
+    arrays = ctrl_arrays()
     assert arrays["nseg"] == ("int", 1) and arrays["gait_phase"] == ("float", 1)
     assert arrays["mpc_offsets"] == ("int", 4) and arrays["mpc_durations"] == ("int", 4)
     assert {"nseg", "mpc_offsets", "mpc_durations"} <= set(binding.CTRL_INT_ARRAYS)
@@ -48,27 +44,11 @@ def test_new_rows_are_in_the_array_list_and_the_binding():
 
 
 # ---- the horizon claim, on the model alone
-# x commands of the six cases (:179-231): standing, turning on the spot (yaw 0.5), walking, walk-to-trot, trot, and
-# the fast trot's four segment counts 13 (42 - 28.4 = 13.6), 12 (42 - 29.6 = 12.4), 11 (42 - 30.4 = 11.6), 10 (42 - 35 < 10)
-SWEEP_X = (0.0, 0.0, 0.1, 0.32, 0.8, 1.42, 1.48, 1.52, 1.75)
-SWEEP_YAW = (0.0, 0.5, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
-
-
-def sweep_vel(B, segment):
-    """Robot b's command in segment `segment`: case (b + 2 * segment) % 9; every fourth robot adds a y command."""
-    k = (np.arange(B) + 2 * segment) % len(SWEEP_X)
-    v = np.zeros((B, 3))
-    v[:, 0] = np.array(SWEEP_X)[k]
-    v[:, 2] = np.array(SWEEP_YAW)[k]
-    v[(np.arange(B) % 4 == 3) & (v[:, 0] > 0), 1] = 0.25       # vBody = |x| + y * y: + 0.0625
-    return v
-
-
 def test_every_solving_tick_has_horizon_ten():
     B, ticks, seg = 72, 3200, 800
     m = M1.CtrlModelMode1(B)
     m.set_gait(np.where(np.arange(B) % 5 == 0, 29, 9))          # (omni robots among them; the gait number selects nothing else)
-    est = _calm_est(B, np.random.default_rng(7))
+    est = calm_est(B, np.random.default_rng(7))
     seen = [set() for _ in range(B)]
     restarts = np.zeros(B, int)
     solves = np.zeros(B, int)
@@ -121,7 +101,7 @@ def _settle(x, yaw=0.0):
         B = len(SETTLE_X)
         m = M1.CtrlModelMode1(B)
         m.set_vel(np.stack([SETTLE_X, np.zeros(B), SETTLE_YAW], 1))
-        est = _calm_est(B, np.random.default_rng(1))
+        est = calm_est(B, np.random.default_rng(1))
         for _ in range(1600):
             m.loco(est)
         _settled["m"] = m

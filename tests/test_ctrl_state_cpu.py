@@ -96,7 +96,7 @@ def test_make_state_stream():
     pos, vb = state[..., POS], state[..., VBODY]
     assert np.abs(pos - np.array([0, 0, 0.29])).max() < 0.05 and np.ptp(pos[..., 0], axis=0).max() > 1e-3
     assert np.abs(np.diff(pos, axis=0)).max() < 1e-3
-    assert (vb[..., 0] > -0.8).all() and (vb[..., 0] < 1.5).all() and np.abs(vb[..., 1]).max() < 0.4   # test_gpu_controller._vel
+    assert (vb[..., 0] > -0.8).all() and (vb[..., 0] < 1.5).all() and np.abs(vb[..., 1]).max() < 0.4   # ctrl_model.command_vel
     assert np.abs(vb).max() > 0.05
     # roll / joint as in make_tick_stream
     sr, mr = W.make_state_stream(B, T, 5, roll=(2, 0.7, 10), joint=(3, 4, 0.5, 7))

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import episode_model as EM
+from c_headers import declared, members
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -18,34 +19,24 @@ no_hipcc = pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists
 INT_MAX = 2 ** 31 - 1
 
 
-def _decl(name):
-    return set(re.findall(r"^int (qmpc_\w+)\(", open(os.path.join(ROOT, "include", name)).read(), re.M))
-
-
-def _members(hdr, struct):
-    body = re.search(r"typedef struct \{([^}]*)\} %s;" % struct, hdr).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    return [n for decl in body.split(";") if decl.strip() for n in re.findall(r"(\w+)\s*(?:,|$)", decl.strip())]
-
-
 def test_episode_symbols_exported_and_abi_version_kept():
     from quadruped_ctrl_amd import binding
     lib = binding.load_library()
     hdr = open(os.path.join(ROOT, "include", "qmpc_episode.h")).read()
     want = {"qmpc_episode_init", "qmpc_episode_set", "qmpc_episode_step", "qmpc_episode_log_clear", "qmpc_episode_view_get"}
-    assert _decl("qmpc_episode.h") == want == set(binding.EPISODE_EXPORTS)
+    assert declared("qmpc_episode.h") == want == set(binding.EPISODE_EXPORTS)
     for name in want:
         assert hasattr(lib, name), name
     assert lib.qmpc_abi_version() == binding.ABI_VERSION == 23
-    assert _members(hdr, "qmpc_episode_rule") == [n for n, _ in binding.EpisodeRule._fields_]
-    assert _members(hdr, "qmpc_episode_bind") == [n for n, _ in binding.EpisodeBind._fields_]
-    assert _members(hdr, "qmpc_episode_view") == [n for n, _ in binding.EpisodeView._fields_]
+    assert members(hdr, "qmpc_episode_rule") == [n for n, _ in binding.EpisodeRule._fields_]
+    assert members(hdr, "qmpc_episode_bind") == [n for n, _ in binding.EpisodeBind._fields_]
+    assert members(hdr, "qmpc_episode_view") == [n for n, _ in binding.EpisodeView._fields_]
     for k, name in enumerate(EM.NAMES):
         bit = int(re.search(r"#define QMPC_EP_%s (\d+)" % name.upper(), hdr).group(1))
         assert bit == 1 << k == binding.EP_CAUSES[name] == getattr(EM, name.upper())
     assert list(binding.EP_CAUSES) == list(EM.NAMES)
     # the older headers still declare exactly what they declared
-    assert _decl("qmpc_sense.h") == set(binding.SENSE_EXPORTS) and _decl("qmpc_plant.h") == set(binding.PLANT_EXPORTS)
+    assert declared("qmpc_sense.h") == set(binding.SENSE_EXPORTS) and declared("qmpc_plant.h") == set(binding.PLANT_EXPORTS)
     # without a device every entry point refuses a null handle
     assert lib.qmpc_episode_init(None, 4, 0, None) == 1 and lib.qmpc_episode_step(None, 4, 1, None) == 1
     assert lib.qmpc_episode_log_clear(None, None) == 1 and lib.qmpc_episode_view_get(None, None) == 1

@@ -12,6 +12,7 @@ import pytest
 
 import episode_model as EM
 import episode_sense_model as ESM
+from c_headers import declared, members
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "quadruped_ctrl_amd", "csrc")
@@ -23,28 +24,18 @@ KEPT = {"q", "qd", "leg_J", "leg_p", "leg_v", "kf_p", "kf_v", "orientation", "rp
         "a_world", "ori_ini_inv", "xhat", "P", "position", "v_world", "v_body", "first_visit"}
 
 
-def _decl(name):
-    return set(re.findall(r"^int (qmpc_\w+)\(", open(os.path.join(ROOT, "include", name)).read(), re.M))
-
-
-def _members(hdr, struct):
-    body = re.search(r"typedef struct \{([^}]*)\} %s;" % struct, hdr).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    return [n for decl in body.split(";") if decl.strip() for n in re.findall(r"(\w+)\s*(?:,|$)", decl.strip())]
-
-
 def test_symbols_exported_and_abi_version_kept():
     from quadruped_ctrl_amd import binding
     lib = binding.load_library()
     hdr = open(os.path.join(ROOT, "include", "qmpc_episode_sense.h")).read()
     want = {"qmpc_episode_sense_init", "qmpc_episode_sense_hold", "qmpc_episode_sense_step", "qmpc_episode_sense_view_get"}
-    assert _decl("qmpc_episode_sense.h") == want == set(binding.EPISODE_SENSE_EXPORTS)
+    assert declared("qmpc_episode_sense.h") == want == set(binding.EPISODE_SENSE_EXPORTS)
     for name in want:
         assert hasattr(lib, name), name
     assert lib.qmpc_abi_version() == binding.ABI_VERSION == 23
-    assert _members(hdr, "qmpc_episode_sense_view") == [n for n, _ in binding.EpisodeSenseView._fields_]
+    assert members(hdr, "qmpc_episode_sense_view") == [n for n, _ in binding.EpisodeSenseView._fields_]
     # the two headers this one stands on still declare exactly what they declared
-    assert _decl("qmpc_episode.h") == set(binding.EPISODE_EXPORTS) and _decl("qmpc_sense.h") == set(binding.SENSE_EXPORTS)
+    assert declared("qmpc_episode.h") == set(binding.EPISODE_EXPORTS) and declared("qmpc_sense.h") == set(binding.SENSE_EXPORTS)
     # without a device every entry point refuses a null handle
     assert lib.qmpc_episode_sense_init(None, 4, 5, None) == 1 and lib.qmpc_episode_sense_hold(None, 4, None, 5, None) == 1
     assert lib.qmpc_episode_sense_step(None, 4, None, None) == 1 and lib.qmpc_episode_sense_view_get(None, None) == 1

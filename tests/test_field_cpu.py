@@ -20,6 +20,7 @@ import plant_loop_terrain as LT
 import plant_model_contact as PCM
 import plant_model_field as PF
 import plant_model_terrain as PT
+from c_headers import declared, members
 from quadruped_ctrl_amd import workloads as W
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,29 +32,19 @@ OUT_KEYS = ("p", "v", "q", "w", "foot", "grf", "stance", "state", "motor", "supp
             "drop")
 
 
-def _decl(name):
-    return set(re.findall(r"^int (qmpc_\w+)\(", open(os.path.join(ROOT, "include", name)).read(), re.M))
-
-
-def _members(hdr, struct):
-    body = re.search(r"typedef struct \{([^}]*)\} %s;" % struct, hdr).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    return [n for decl in body.split(";") if decl.strip() for n in re.findall(r"(\w+)\s*(?:,|$)", decl.strip())]
-
-
 def test_field_symbols_exported_and_abi_version_kept():
     from quadruped_ctrl_amd import binding
     lib = binding.load_library()
     hdr = open(os.path.join(ROOT, "include", "qmpc_field.h")).read()
     want = {"qmpc_plant_set_field", "qmpc_field_view_get"}
-    assert _decl("qmpc_field.h") == want == set(binding.FIELD_EXPORTS)
+    assert declared("qmpc_field.h") == want == set(binding.FIELD_EXPORTS)
     for name in want:
         assert hasattr(lib, name), name
     assert lib.qmpc_abi_version() == binding.ABI_VERSION == 23
-    assert _members(hdr, "qmpc_field_bank") == [n for n, _ in binding.FieldBank._fields_] == ["z", "nx", "ny", "count", "cell"]
-    assert _members(hdr, "qmpc_field_view") == [n for n, _ in binding.FieldView._fields_] == ["bank", "place", "flags", "batch"]
+    assert members(hdr, "qmpc_field_bank") == [n for n, _ in binding.FieldBank._fields_] == ["z", "nx", "ny", "count", "cell"]
+    assert members(hdr, "qmpc_field_view") == [n for n, _ in binding.FieldView._fields_] == ["bank", "place", "flags", "batch"]
     # the older headers still declare exactly what they declared, and no longer call the feature out of scope
-    assert _decl("qmpc_terrain.h") == set(binding.TERRAIN_EXPORTS) and _decl("qmpc_contact.h") == set(binding.CONTACT_EXPORTS)
+    assert declared("qmpc_terrain.h") == set(binding.TERRAIN_EXPORTS) and declared("qmpc_contact.h") == set(binding.CONTACT_EXPORTS)
     for name in ("include/qmpc_terrain.h", "include/qmpc_contact.h", "INTEGRATION.md"):
         text = re.sub(r"[\s*]+", " ", open(os.path.join(ROOT, name)).read())
         assert "Still out of scope" in text and not re.search(r"Still out of scope:[^.]*height maps", text), name

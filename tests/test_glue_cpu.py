@@ -6,19 +6,7 @@ import numpy as np
 from oracle import glue as G
 from quadruped_ctrl_amd import workloads as W
 
-
-def fk64(q, leg, g=G.GEOM.astype(np.float64)):
-    """Independent fp64 forward kinematics from the leg geometry: abad rotation about x, hip and knee
-    about y (Mini Cheetah convention of computeLegJacobianAndPosition)."""
-    l1, l2, l3, l4 = g
-    side = -1.0 if leg % 2 == 0 else 1.0
-    s1, c1 = np.sin(q[0]), np.cos(q[0])
-    s2, c2 = np.sin(q[1]), np.cos(q[1])
-    s23, c23 = np.sin(q[1] + q[2]), np.cos(q[1] + q[2])
-    x = l3 * s23 + l2 * s2
-    zz = -(l3 * c23 + l2 * c2)          # leg-plane "down" before the abad rotation
-    yy = (l1 + l4) * side
-    return np.array([x, yy * c1 - zz * s1, yy * s1 + zz * c1])
+from ctrl_model import fk64
 
 
 def test_fk_position_and_jacobian():

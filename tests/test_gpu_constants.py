@@ -2,7 +2,7 @@
 
 The rest of the suite runs the Mini Cheetah at 500 Hz: qmpc_set_leg_geometry, qmpc_set_robot, qmpc_ctrl_init's freq and
 qmpc_plant_init's mu_plant each at one value.  Here one other robot goes through the same comparisons -- the helpers of
-tests/test_gpu_glue.py, test_gpu_controller.py, test_gpu_ctrl_state.py, test_gpu_plant.py and test_gpu_parity.py with
+tests/test_gpu_glue.py, test_gpu_plant.py, tests/ctrl_gpu.py (the controller's) and tests/solve_gpu.py (the solve's) with
 their own tolerances (bit-exact glue and discrete controller state, 1e-10 assembly and plant, 1e-8 solver, bound_for for
 the MPC forces); no bound of its own.  The references' parameters are pinned without the GPU in
 tests/test_constants_cpu.py, which also checks the conditions the streams below have to meet.
@@ -16,9 +16,8 @@ from quadruped_ctrl_amd import workloads as W
 import ctrl_model as M
 import fleet_gpu as FG
 import plant_cases as PC
-import test_gpu_controller as TC
-import test_gpu_ctrl_state as TS
-from test_gpu_parity import _dump_model_compare, _solver_parity_on_own_qp
+import ctrl_gpu as CG
+from solve_gpu import dump_model_compare, solver_parity_on_own_qp
 
 pytestmark = pytest.mark.gpu
 
@@ -102,7 +101,7 @@ def test_teacher_forced_tick_parity_imu_path(freq, geom):
     at tick 20) at another frequency and geometry: dt_mpc = 13 float(1 / freq) enters swing_time, swing_rem, the landing
     point and the solve's coefficient tables; the Kalman filter keeps the reference's 0.002."""
     B, ticks = 257, 40
-    c, m, eff = TC._teacher_forced(B, ticks, seed=B, freq=freq, geom=geom)
+    c, m, eff = CG.teacher_forced(B, ticks, seed=B, freq=freq, geom=geom)
     assert m.dt == np.float32(1.0 / freq) and m.dt_mpc == np.float32(1.0 / freq) * np.float32(13)
     assert np.isfinite(eff).all() and (c.read("safe") == 1).all()
     _, motor = W.make_tick_stream(B, ticks, B, dt=1.0 / freq)
@@ -117,14 +116,14 @@ def test_teacher_forced_tick_parity_imu_path(freq, geom):
 
 @pytest.mark.parametrize("freq,geom", CASES, ids=["400Hz-geom2", "1000Hz"])
 def test_teacher_forced_tick_parity_state_path(freq, geom):
-    TS._teacher_forced_state(257, 40, 257, 20, freq=freq, geom=geom)
+    CG.teacher_forced_state(257, 40, 257, 20, freq=freq, geom=geom)
 
 
 def test_mode1_per_robot_at_400hz_second_geometry():
     """Robot mode 1, per-robot schedule, 257 robots, 40 ticks at 400 Hz with the second geometry: the model parity of
     test_gpu_ctrl_state.py::test_mode1_per_robot_schedule_state and the forces of every solve against the oracle
     pipeline with dt = dt_mpc."""
-    seen, n_solves = TS._mode1_state(257, 40, 131, freq=400.0, geom=GEOM2, check_mpc=True)
+    seen, n_solves = CG.mode1_state(257, 40, 131, freq=400.0, geom=GEOM2, check_mpc=True)
     assert n_solves == 257 * 3
 
 
@@ -141,7 +140,7 @@ def test_geometry_before_or_after_ctrl_init():
         c = BatchedController(0, max_batch=B)
         if order == "before":
             c.mpc.set_leg_geometry(*GEOM2)
-        c.init(B, 400.0, TC.PID)
+        c.init(B, 400.0, CG.PID)
         if order == "after":
             c.mpc.set_leg_geometry(*GEOM2)
         c.set_gait(torch.from_numpy(g).to(c.device))
@@ -163,7 +162,7 @@ def test_kalman_process_noise_does_not_follow_freq():
     imu, motor = W.make_tick_stream(B, 1, 55)
     out = []
     for freq in (400.0, 500.0):
-        c = TC._ctrl(B, freq)
+        c = CG.make_ctrl(B, freq)
         c.tick(torch.from_numpy(imu[0]).to(c.device), torch.from_numpy(motor[0]).to(c.device))
         out.append({k: c.read(k) for k in ("P", "xhat", "position", "v_world", "r_body", "a_world", "omega_body", "kf_p", "kf_v")})
         c.close()
@@ -247,10 +246,10 @@ def test_assembly_and_solver_at_the_second_body(dt, mu, mpc_factory):
         b = _second(b, dt, mu)
         m = mpc_factory(b)
         m.set_robot(MASS2, IBODY2, GRAVITY2)
-        wh, wg = _dump_model_compare(m, b, range(0, B, max(1, B // 12)))
+        wh, wg = dump_model_compare(m, b, range(0, B, max(1, B // 12)))
         print("h", b["horizon"], "dt", dt, "mu", mu, "H rel", wh, "g rel", wg)
         assert wh < 1e-10 and wg < 1e-10
-        res, idx, worst, nact = _solver_parity_on_own_qp(m, b, lambda r: list(range(0, B, max(1, B // 12))))
+        res, idx, worst, nact = solver_parity_on_own_qp(m, b, lambda r: list(range(0, B, max(1, B // 12))))
         print("   solver worst", worst, "rows at a bound", nact)
         assert max(nact) > 0
         rel = np.abs(res["grf"] - plain["grf"]).max(1) / np.maximum(np.abs(plain["grf"]).max(1), 1.0)
@@ -265,9 +264,9 @@ def test_decoupled_path_at_the_second_body(mpc_factory):
     m = mpc_factory(b)
     m.set_robot(MASS2, IBODY2, GRAVITY2)
     m.set_split(2)
-    wh, wg = _dump_model_compare(m, b, range(0, 48, 4))
+    wh, wg = dump_model_compare(m, b, range(0, 48, 4))
     assert wh < 1e-10 and wg < 1e-10
-    res, idx, worst, nact = _solver_parity_on_own_qp(m, b, lambda r: list(range(0, 48, 4)))
+    res, idx, worst, nact = solver_parity_on_own_qp(m, b, lambda r: list(range(0, 48, 4)))
     print("decoupled: H rel", wh, "g rel", wg, "solver worst", worst)
     rel = np.abs(res["grf"] - plain["grf"]).max(1) / np.maximum(np.abs(plain["grf"]).max(1), 1.0)
     assert np.median(rel) > 0.01, np.median(rel)

@@ -23,130 +23,19 @@ explains the gain), so position / velocity are bounded by 1e-3 m / 1e-2 m/s and 
 import numpy as np
 import pytest
 
-from oracle import noise_floor as NF
 from oracle import oracle as O
 from quadruped_ctrl_amd import workloads as W
 
 import ctrl_model as M
-from ctrl_model import command_gaits as _gaits, command_vel as _vel
+from ctrl_gpu import PID, gpu_est, make_ctrl, teacher_forced
+from ctrl_model import command_gaits, command_vel
 
 pytestmark = pytest.mark.gpu
-
-LAND_ULPS = 8
-EXACT_F32 = ("q", "vel_des", "yaw_des_true", "rpy_int", "rpy_comp", "stand_traj", "p_foot", "pf_rel", "swing_time",
-             "swing_rem", "contact_state", "swing_state", "sw_p0", "sw_p", "sw_v", "p_des", "v_des", "contact_phase")
-EXACT_I32 = ("counter", "first_run", "first_swing", "current_gait", "offsets", "durations", "iteration", "safe")
-PID = (0.0, 0.0, 3.0, 0.3)
-
-
-def _ctrl(B, freq=500.0, geom=None):
-    from quadruped_ctrl_amd.binding import BatchedController
-    c = BatchedController(0, max_batch=B)
-    c.init(B, freq, PID)
-    if geom is not None:
-        c.mpc.set_leg_geometry(*geom)
-    return c
-
-
-def _gpu_est(c):
-    return {k: c.read(k) for k in ("orientation", "rpy", "r_body", "omega_world", "omega_body", "a_world", "position",
-                                "v_world", "leg_p", "leg_v", "leg_J", "qd")}
-
-
-def _bound(rec, err):
-    """Per-robot bound of the suite: max(1e-4, 1.5 spread_i), the spread evaluated for robots over 1e-4 only."""
-    bnd = np.full(len(err), 1e-4)
-    for i in np.flatnonzero(err >= 1e-4):
-        bnd[i] = max(1e-4, 1.5 * NF.robot_floor(rec, int(i))["spread12"])
-    return bnd
-
-
-def _teacher_forced(B, ticks, seed, switch_at=20, roll=None, joint=None, check_mpc=True, freq=500.0, geom=None,
-                    gaits_at=None, vel_at=None, capped=None, stream=None, each_tick=None):
-    """freq: qmpc_ctrl_init's (the stream is sampled at 1 / freq); geom: qmpc_set_leg_geometry's four lengths, None for
-    the handle's default.
-    gaits_at / vel_at: {tick: command}, given before that tick (default: the suite's gaits at 0 and switch_at, its
-    velocities at 0).  capped: None compares with whatever the reference returned; "converged" compares a robot on which
-    the reference stopped at its nWSR cap with the same pipeline run to convergence (test_gpu_ctrl_mode1._converged).
-    stream: (imu, motor) instead of make_tick_stream(seed).  each_tick(t, c, m, e): called at the end of every tick with
-    the controller, the model and the estimator read-out."""
-    import torch
-    assert capped in (None, "converged")
-    c = _ctrl(B, freq, geom)
-    m = M.CtrlModel(B, freq, PID) if geom is None else M.CtrlModel(B, freq, PID, geom=geom)
-    dev = c.device
-    imu, motor = W.make_tick_stream(B, ticks, seed, dt=1.0 / freq, roll=roll, joint=joint) if stream is None else stream
-    if gaits_at is None:
-        gaits_at = {0: _gaits(B, 0, switch_at)}
-        gaits_at[switch_at] = _gaits(B, switch_at, switch_at)
-    if vel_at is None:
-        vel_at = {0: _vel(B, seed + 1)}
-    vel = vel_at[0]
-    c.set_vel(torch.from_numpy(vel).to(dev))
-    m.set_vel(vel)
-    n_mpc = 0
-    eff_hist = []
-    for t in range(ticks):
-        if t in gaits_at:
-            g = gaits_at[t]
-            c.set_gait(torch.from_numpy(g).to(dev))
-            m.set_gait(g)
-        if t in vel_at and t > 0:
-            c.set_vel(torch.from_numpy(vel_at[t]).to(dev))
-            m.set_vel(vel_at[t])
-        eff = c.tick(torch.from_numpy(imu[t]).to(dev), torch.from_numpy(motor[t]).to(dev)).cpu().numpy()
-        e = _gpu_est(c)
-        e["leg_q"] = motor[t][:, :12].astype(np.float32)
-        gpu_pf = c.read("sw_pf")
-        out = m.loco(e, pf_override=gpu_pf)
-        # the landing points: through sin / cos
-        scale = np.maximum(1.0, np.abs(out["pf"]))
-        land = np.abs(gpu_pf - out["pf"]) / (np.finfo(np.float32).eps * scale)
-        assert land.max() <= LAND_ULPS, (t, land.max())
-        zero_yr = m.vel_des[:, 2] == 0
-        assert np.array_equal(gpu_pf[zero_yr], out["pf"][zero_yr]), t   # yaw rate 0: sin / cos exact
-        for k in EXACT_I32:
-            assert np.array_equal(c.read(k).reshape(getattr(m, k).shape), getattr(m, k)), (t, k)
-        for k in EXACT_F32:
-            g_ = c.read(k).reshape(getattr(m, k).shape)
-            assert np.array_equal(g_, getattr(m, k)), (t, k, np.abs(g_ - getattr(m, k)).max())
-        mpc_tick = (t + 1) % 13 == 0
-        if mpc_tick:
-            n_mpc += 1
-            rec, wpd, xci = O.pack_commands(m.command(e), float(m.dt_mpc))
-            m.wpd[:], m.xci[:] = wpd, xci
-            rec.update(dt=float(m.dt_mpc), mu=0.4, f_max=120.0)
-            f_gpu = c.read("f_ff")
-            if check_mpc:
-                soln, nwsr, rc = O.solve_batch(rec)
-                assert (rc == 0).all()
-                if capped == "converged":
-                    from test_gpu_ctrl_mode1 import _converged
-                    over_cap = np.flatnonzero(nwsr >= 100)
-                    for i in over_cap:                            # (the reference stopped at its cap: see there)
-                        soln[i] = _converged(rec, int(i))
-                    print(f"tick {t}: {len(over_cap)} robots compared with the pipeline run to convergence {over_cap.tolist()}")
-                f_ref = O.forces_to_body(e["r_body"], soln[:, :12].astype(np.float32))
-                err = np.abs(f_gpu.astype(np.float64) - f_ref).max(1) / np.maximum(np.abs(f_ref).max(1), 1.0)
-                over = err >= 1e-4
-                if over.any():
-                    assert (err <= _bound(rec, err)).all(), (t, err.max())
-            m.f_ff[:] = f_gpu      # teacher forcing of the solver's answer
-        for k in ("wpd", "xci"):
-            assert np.array_equal(c.read(k).reshape(getattr(m, k).shape), getattr(m, k)), (t, k)
-        # stance legs carry exactly f_ff, swing legs nothing: the effort is leg_command of those commands
-        eff_m = m.legcmd(e, m.f_ff)
-        assert np.array_equal(eff, eff_m), (t, np.abs(eff - eff_m).max())
-        eff_hist.append(eff)
-        if each_tick is not None:
-            each_tick(t, c, m, e)
-    assert n_mpc == ticks // 13
-    return c, m, np.array(eff_hist)
 
 
 @pytest.mark.parametrize("B", [1, 257, 4096])
 def test_teacher_forced_tick_parity(B):
-    c, m, eff = _teacher_forced(B, 40, seed=B, check_mpc=B <= 257)
+    c, m, eff = teacher_forced(B, 40, seed=B, check_mpc=B <= 257)
     assert np.isfinite(eff).all()
     assert (c.read("safe") == 1).all()
     c.close()
@@ -154,7 +43,7 @@ def test_teacher_forced_tick_parity(B):
 
 def test_mpc_coupling_large_batch():
     """The oracle check of f_ff on every MPC tick at 1024 robots, all gait numbers and omni variants."""
-    c, m, eff = _teacher_forced(1024, 27, seed=5)
+    c, m, eff = teacher_forced(1024, 27, seed=5)
     c.close()
 
 
@@ -164,11 +53,11 @@ def test_free_running_parity(prework):
     torque_calculator..., i.e. qmpc_ctrl_prework once before the ticks (estimators and leg data, no control step)."""
     import torch
     B, ticks = 64, 130
-    c = _ctrl(B)
+    c = make_ctrl(B)
     m = M.CtrlModel(B, 500.0, PID)
     imu, motor = W.make_tick_stream(B, ticks + 1, 11)
-    vel = _vel(B, 12)
-    g = _gaits(B, 0, 10 ** 9)
+    vel = command_vel(B, 12)
+    g = command_gaits(B, 0, 10 ** 9)
     c.set_vel(torch.from_numpy(vel).to(c.device))
     c.set_gait(torch.from_numpy(g).to(c.device))
     m.set_vel(vel)
@@ -211,7 +100,7 @@ def test_safety_latch_and_abs_binding():
     what the joint PD reads.  A latched robot's effort is zero from that tick on."""
     import torch
     B, ticks = 6, 30
-    c = _ctrl(B)
+    c = make_ctrl(B)
     dev = c.device
     imu, motor = W.make_tick_stream(B, ticks, 3, roll=(1, 0.45, 0))
     for rb, val, t0 in ((2, 0.7, 5), (4, 1.2, 9)):
@@ -221,7 +110,7 @@ def test_safety_latch_and_abs_binding():
     m = M.CtrlModel(B, 500.0, PID)
     for t in range(ticks):
         eff = c.tick(torch.from_numpy(imu[t]).to(dev), torch.from_numpy(motor[t]).to(dev)).cpu().numpy()
-        e = _gpu_est(c)
+        e = gpu_est(c)
         e["leg_q"] = motor[t][:, :12].astype(np.float32)
         m.loco(e, pf_override=c.read("sw_pf"))
         if (t + 1) % 13 == 0:
@@ -255,10 +144,10 @@ def test_view_tensors_alias_the_state():
     import torch
     from quadruped_ctrl_amd.binding import CTRL_VIEW_WIDTH, CtrlView
     B = 33
-    c = _ctrl(B)
+    c = make_ctrl(B)
     imu, motor = W.make_tick_stream(B, 20, 41)
-    c.set_gait(torch.from_numpy(_gaits(B, 0, 10 ** 9)).to(c.device))
-    c.set_vel(torch.from_numpy(_vel(B, 42)).to(c.device))
+    c.set_gait(torch.from_numpy(command_gaits(B, 0, 10 ** 9)).to(c.device))
+    c.set_vel(torch.from_numpy(command_vel(B, 42)).to(c.device))
     for t in range(14):
         c.tick(torch.from_numpy(imu[t]).to(c.device), torch.from_numpy(motor[t]).to(c.device))
     v = c.view()
@@ -282,10 +171,10 @@ def test_view_tensors_alias_the_state():
 def test_reset_leaves_other_robots_bit_identical():
     import torch
     B, ticks, at = 40, 33, 17
-    a, b = _ctrl(B), _ctrl(B)
+    a, b = make_ctrl(B), make_ctrl(B)
     imu, motor = W.make_tick_stream(B, ticks, 21)
-    g = torch.from_numpy(_gaits(B, 0, 10 ** 9)).to(a.device)
-    v = torch.from_numpy(_vel(B, 22)).to(a.device)
+    g = torch.from_numpy(command_gaits(B, 0, 10 ** 9)).to(a.device)
+    v = torch.from_numpy(command_vel(B, 22)).to(a.device)
     for c in (a, b):
         c.set_gait(g)
         c.set_vel(v)
@@ -314,12 +203,12 @@ def test_graph_capture_replay_matches_eager():
     """One captured 13-tick block replayed 3 times equals 39 eager ticks, bit for bit (single stream)."""
     import torch
     B = 300
-    eager, cap = _ctrl(B), _ctrl(B)
+    eager, cap = make_ctrl(B), make_ctrl(B)
     dev = eager.device
     n = 13 * 4
     imu, motor = W.make_tick_stream(B, n, 31)
-    g = torch.from_numpy(_gaits(B, 0, 10 ** 9)).to(dev)
-    v = torch.from_numpy(_vel(B, 32)).to(dev)
+    g = torch.from_numpy(command_gaits(B, 0, 10 ** 9)).to(dev)
+    v = torch.from_numpy(command_vel(B, 32)).to(dev)
     for c in (eager, cap):
         c.set_gait(g)
         c.set_vel(v)
@@ -402,8 +291,8 @@ def test_calm_stream_1024_robots_1300_ticks():
     B = 1024
     ctrl = BatchedController(0, max_batch=B)
     ctrl.init(B, freq=500.0, pid=PID)
-    ctrl.set_gait(torch.from_numpy(_gaits(B, 0, 10 ** 9)).cuda())
-    ctrl.set_vel(torch.from_numpy(_vel(B, 7)).cuda())
+    ctrl.set_gait(torch.from_numpy(command_gaits(B, 0, 10 ** 9)).cuda())
+    ctrl.set_vel(torch.from_numpy(command_vel(B, 7)).cuda())
     imu, motor = W.make_tick_stream(B, 1300, 7)
     imu, motor = torch.from_numpy(imu).cuda(), torch.from_numpy(motor).cuda()
     for t in range(1300):

@@ -7,8 +7,8 @@ every reachable gait -- and, in the hard case, drive rpy_int, vel_des and pf_rel
 its re-anchor and the gait commands through two changes mid-swing.  tests/test_ctrl_cycle_cpu.py shows on the CPU that
 the restatement reaches all of that on these inputs, and that the 40-tick case reaches none of it.
 
-The comparison is the one of tests/test_gpu_controller.py and tests/test_gpu_ctrl_state.py, by their own helpers
-(_teacher_forced, _teacher_forced_state): every robot on every tick, EXACT_I32 and EXACT_F32 bit for bit, sw_pf within
+The comparison is the one of tests/test_gpu_controller.py and tests/test_gpu_ctrl_state.py, by the helpers they share
+(teacher_forced, teacher_forced_state): every robot on every tick, EXACT_I32 and EXACT_F32 bit for bit, sw_pf within
 LAND_ULPS = 8 ulps of max(1, |Pf|) and equal where the yaw rate is 0, wpd / xci bit for bit, effort == legcmd(f_ff) bit for
 bit.  In the two calm tests f_ff is held on each of the 29 MPC ticks to oracle.pack_commands -> solve_batch ->
 forces_to_body within the suite's per-robot bound max(1e-4, 1.5 x the reference's float-order spread), a robot on which
@@ -24,8 +24,7 @@ import numpy as np
 import pytest
 
 import ctrl_cycle_cases as CC
-from test_gpu_controller import _teacher_forced
-from test_gpu_ctrl_state import _teacher_forced_state
+from ctrl_gpu import teacher_forced, teacher_forced_state
 
 pytestmark = pytest.mark.gpu
 
@@ -53,7 +52,7 @@ class _Watch:
 def test_two_cycles_state_path(calm):
     """The calm case through tick_state: 24 robots, 380 ticks, 29 MPC ticks against the oracle."""
     w = _Watch(status=True)
-    _teacher_forced_state(calm["B"], calm["ticks"], calm["seed"], 10 ** 9, gaits_at=calm["gaits_at"], vel_at=calm["vel_at"],
+    teacher_forced_state(calm["B"], calm["ticks"], calm["seed"], 10 ** 9, gaits_at=calm["gaits_at"], vel_at=calm["vel_at"],
                           capped="converged", stream=(calm["state"], calm["motor"]), each_tick=w)
     assert w.n_mpc == 29
     CC.assert_calm_coverage(CC.coverage(w.trace))
@@ -63,7 +62,7 @@ def test_two_cycles_imu_path(calm):
     """The same robots through tick on make_tick_stream: the Kalman filter sees contact_phase over whole cycles, and the
     restatement is fed the device's own estimator read-out."""
     w = _Watch(status=True)
-    c, m, eff = _teacher_forced(calm["B"], calm["ticks"], calm["seed"], 10 ** 9, gaits_at=calm["gaits_at"],
+    c, m, eff = teacher_forced(calm["B"], calm["ticks"], calm["seed"], 10 ** 9, gaits_at=calm["gaits_at"],
                                 vel_at=calm["vel_at"], capped="converged", stream=(calm["imu"], calm["motor"]), each_tick=w)
     assert w.n_mpc == 29 and c.view()["ticks"] == calm["ticks"]
     assert np.isfinite(eff).all() and (c.read("safe") == 1).all()
@@ -83,7 +82,7 @@ def test_hard_branches_state_path():
     landing-point distance of the run is 1.00 ulp (0.25 in the calm case)."""
     case = CC.hard_case()
     w = _Watch(status=False)
-    _teacher_forced_state(case["B"], case["ticks"], case["seed"], 10 ** 9, gaits_at=case["gaits_at"], vel_at=case["vel_at"],
+    teacher_forced_state(case["B"], case["ticks"], case["seed"], 10 ** 9, gaits_at=case["gaits_at"], vel_at=case["vel_at"],
                           mpc="forced", stream=(case["state"], case["motor"]), each_tick=w)
     cov = CC.coverage(w.trace)
     print({k: cov[k] for k in CC.COUNTERS}, "complete swings", cov["complete_swings"])

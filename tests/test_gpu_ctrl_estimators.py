@@ -21,24 +21,12 @@ from oracle import glue as G
 
 import ctrl_model as M
 import est_cases as E
-from test_gpu_controller import EXACT_F32, EXACT_I32, LAND_ULPS, PID
+from ctrl_gpu import EXACT_F32, EXACT_I32, LAND_ULPS, PID, make_ctrl, to_dev
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 ORI_EXACT = ("orientation", "r_body", "omega_body", "omega_world", "a_world")
-
-
-def _ctrl(B):
-    from quadruped_ctrl_amd.binding import BatchedController
-    c = BatchedController(0, max_batch=B)
-    c.init(B, 500.0, PID)
-    return c
-
-
-def _dev(c, a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(c.device)
 
 
 def _first_visit(c, m, imu_row, rows=None):
@@ -78,11 +66,11 @@ def test_orientation_stage_on_hard_attitudes():
     float arguments within 1.12 ulps on the GPU and 1.36 ulps in the restatement."""
     imu, motor = E.hard_attitudes()
     V, B = imu.shape[:2]
-    c = _ctrl(B)
+    c = make_ctrl(B)
     m = M.CtrlModel(B, 500.0, PID)
     worst = {"gpu": 0.0, "restatement": 0.0}
     for v in range(V):
-        c.prework(_dev(c, imu[v]), _dev(c, motor[v]))
+        c.prework(to_dev(c, imu[v]), to_dev(c, motor[v]))
         if v == 0:
             d = _first_visit(c, m, imu[0])
             print(f"ori_ini_inv: worst distance to the restatement {d:.3e}")
@@ -115,10 +103,10 @@ def test_kalman_filter_inside_the_tick():
     bit for bit.  Swing legs (contact phase 0: trust 0, factor 101) and a late covariance reset are met on the way."""
     B, ticks = E.TICK_B, E.TICK_COUNT
     imu, motor, gait, vel = E.tick_inputs(ticks)
-    c = _ctrl(B)
-    c.set_gait(_dev(c, gait))
-    c.set_vel(_dev(c, vel))
-    imu_d, motor_d = _dev(c, imu), _dev(c, motor)
+    c = make_ctrl(B)
+    c.set_gait(to_dev(c, gait))
+    c.set_vel(to_dev(c, vel))
+    imu_d, motor_d = to_dev(c, imu), to_dev(c, motor)
     swing_fed, late_reset = False, np.zeros(B, bool)
     for t in range(ticks):
         x, P, phase = c.read("xhat"), c.read("P"), c.read("contact_phase")
@@ -148,17 +136,17 @@ def test_non_finite_imu_row_is_contained():
     imu, bad, motor = E.non_finite_rows()
     two = np.array([E.BAD_QUAT, E.BAD_ACC])
     rest = np.setdiff1d(np.arange(B), two)
-    a, b = _ctrl(B), _ctrl(B)
+    a, b = make_ctrl(B), make_ctrl(B)
     m = M.CtrlModel(B, 500.0, PID)
     gait, vel = M.command_gaits(B, 0, 10 ** 9), M.command_vel(B, 62)
     for c in (a, b):
-        c.set_gait(_dev(c, gait))
-        c.set_vel(_dev(c, vel))
+        c.set_gait(to_dev(c, gait))
+        c.set_vel(to_dev(c, vel))
     m.set_gait(gait)
     m.set_vel(vel)
     for t in range(ticks):
-        ea = a.tick(_dev(a, bad[t]), _dev(a, motor[t])).cpu().numpy()
-        eb = b.tick(_dev(b, imu[t]), _dev(b, motor[t])).cpu().numpy()
+        ea = a.tick(to_dev(a, bad[t]), to_dev(a, motor[t])).cpu().numpy()
+        eb = b.tick(to_dev(b, imu[t]), to_dev(b, motor[t])).cpu().numpy()
         if t == 0:
             _first_visit(a, m, bad[0])
         with np.errstate(all="ignore"):

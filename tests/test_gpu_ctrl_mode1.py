@@ -2,12 +2,12 @@
 of ConvexMPCLocomotion.cpp:173-233 against the restatement in tests/ctrl_model_mode1.py and the oracle pipeline.
 
 Model parity is teacher-forced exactly as tests/test_gpu_controller.py does it for mode 0, with the same rule per
-quantity (its EXACT_I32 / EXACT_F32 lists bit for bit, the landing point within its LAND_ULPS, the effort bit for bit),
+quantity (ctrl_gpu's EXACT_I32 / EXACT_F32 lists bit for bit, the landing point within its LAND_ULPS, the effort bit for bit),
 plus the mode's own state: nseg, the phase, due.  Every robot is compared on every tick, latched ones included.
 Forces: on every tick the due robots' records are rebuilt from the restatement -- horizon 10, rows 0 .. 9 of the robot's
-n-row table -- solved with the oracle pipeline and compared under tests/test_gpu_parity.py's per-robot bound
+n-row table -- solved with the oracle pipeline and compared under the suite's per-robot bound (solve_gpu.bound_for)
 max(1e-4, 1.5 x the reference's float-order spread of that robot).  No allow-list.
-The other tests compare two runs of the library bit for bit (tests/test_gpu_ctrl_schedule.py's helpers).
+The other tests compare two runs of the library bit for bit (ctrl_gpu's run_ticks / same_ticks).
 """
 import numpy as np
 import pytest
@@ -17,25 +17,14 @@ from quadruped_ctrl_amd import workloads as W
 
 import ctrl_model as M
 import ctrl_model_mode1 as M1
-from test_ctrl_mode1_cpu import NSEGS, sweep_vel
-from test_gpu_controller import EXACT_F32, EXACT_I32, LAND_ULPS, PID, _gpu_est
-from test_gpu_ctrl_schedule import STATE, _run, _same
-from test_gpu_parity import bound_for
+from ctrl_gpu import EXACT_F32, EXACT_I32, LAND_ULPS, PID, STATE, converged, gpu_est, make_ctrl, run_ticks, same_ticks
+from ctrl_model import command_vel
+from ctrl_model_mode1 import NSEGS, sweep_vel
+from solve_gpu import bound_for
 
 pytestmark = pytest.mark.gpu
 
 MODE1_STATE = ("nseg", "gait_phase", "due", "grf", "status")
-
-
-def _ctrl(B, mode=1, schedule="per_robot"):
-    from quadruped_ctrl_amd.binding import BatchedController
-    c = BatchedController(0, max_batch=B)
-    c.init(B, 500.0, PID)
-    if schedule != "lockstep":
-        c.set_schedule(schedule)
-    if mode is not None:
-        c.set_robot_mode(mode)
-    return c
 
 
 def _gaits1(B):
@@ -43,33 +32,20 @@ def _gaits1(B):
     return np.array([9, 29, 4, 24, 0, 30], np.int32)[np.arange(B) % 6]
 
 
-def _converged(rec, i):
-    """The oracle pipeline's answer for robot i of a packed record with qpOASES run to convergence: the same float
-    assembly (oracle.assemble) and swing elimination (oracle.reduce) as oracle.solve_batch, nWSR 5000 instead of the
-    reference's 100 -> the full 12 h solution, eliminated (swing) variables zero."""
-    H, g, A, lb, ub, _ = O.assemble(rec, i)
-    ve, Hr, gr, Ar, lr, ur = O.reduce(H, g, A, lb, ub)
-    x, _, used, rc, irc = O.qpoases(Hr, gr, Ar, lr, ur, nwsr=5000)
-    assert rc == 0 and irc == 0 and used < 5000 and (~ve).sum() == x.size
-    full = np.zeros(g.size)
-    full[~ve] = x
-    return full
-
-
 def test_model_parity_and_forces():
-    """256 robots, 1500 ticks: velocity commands over all six cases (test_ctrl_mode1_cpu.sweep_vel), changed at ticks
+    """256 robots, 1500 ticks: velocity commands over all six cases (ctrl_model_mode1.sweep_vel), changed at ticks
     500 and 1000; omni robots; robot 5 rolls over at tick 700 and latches (compared like the others: zero effort).
 
     The reference's qpOASES call stops after 100 working-set recalculations (SolverMPC.cpp:527-541) and then returns an
     iterate that is not the minimiser; tests/test_gpu_parity.py drops such robots from its comparison (`capped`).  Here
     nobody is dropped: a solve on which the oracle pipeline reports nWSR >= 100 is compared, under the same bound, with
-    the same pipeline run to convergence (_converged: the oracle's float assembly and swing elimination, qpOASES
+    the same pipeline run to convergence (ctrl_gpu.converged: the oracle's float assembly and swing elimination, qpOASES
     with nWSR 5000).  Measured on an MI355X: 2 of the run's 29433 solves are such -- the rolled-over robot 5 in the
     16-segment walk at ticks 1356 and 1369, which need 105 and 111 recalculations; the capped iterate is 1.4e-2 away from
     the minimiser there, the library 1e-6."""
     import torch
     B, ticks, seg = 256, 1500, 500
-    c = _ctrl(B)
+    c = make_ctrl(B, schedule="per_robot", mode=1)
     m = M1.CtrlModelMode1(B, 500.0, PID)
     dev = c.device
     imu, motor = W.make_tick_stream(B, ticks, 91, roll=(5, 0.7, 700))
@@ -86,7 +62,7 @@ def test_model_parity_and_forces():
             m.set_vel(vel)
         before = m.counter.copy()
         eff = c.tick(torch.from_numpy(imu[t]).to(dev), torch.from_numpy(motor[t]).to(dev)).cpu().numpy()
-        e = _gpu_est(c)
+        e = gpu_est(c)
         e["leg_q"] = motor[t][:, :12].astype(np.float32)
         gpu_pf = c.read("sw_pf")
         out = m.loco(e, pf_override=gpu_pf)
@@ -119,7 +95,7 @@ def test_model_parity_and_forces():
             soln, nwsr, rc = O.solve_batch(rec)
             assert (rc == 0).all(), t
             for k in np.flatnonzero(nwsr >= 100):
-                soln[k] = _converged(rec, int(k))
+                soln[k] = converged(rec, int(k))
                 n_capped += 1
                 print(f"tick {t} robot {due[k]}: the reference stopped at its nWSR cap; compared with the converged solve")
             f_ref = O.forces_to_body(e["r_body"][due], soln[:, :12].astype(np.float32))
@@ -179,7 +155,7 @@ def _run1(c, B, imu, motor, t0, ticks, resets=None, vel_at=None):
 
 
 def _same1(a, b, rows, what, a_off=0, b_off=0, ticks=None):
-    _same(a[0], a[1], b[0], b[1], rows, what, a_off=a_off, b_off=b_off, ticks=ticks)
+    same_ticks(a[0], a[1], b[0], b[1], rows, what, a_off=a_off, b_off=b_off, ticks=ticks)
     n = ticks if ticks is not None else min(len(a[0]) - a_off, len(b[0]) - b_off)
     for i in range(n):
         for k in MODE1_STATE + ("counter",):
@@ -188,18 +164,17 @@ def _same1(a, b, rows, what, a_off=0, b_off=0, ticks=None):
 
 def test_mode0_untouched():
     """set_robot_mode(0) called explicitly: a per-robot-schedule run is bit-identical to the same run without the call
-    (test_gpu_ctrl_schedule's mixed gaits and velocities)."""
-    from test_gpu_controller import _vel
+    (test_gpu_ctrl_schedule.py's mixed gaits and velocities)."""
     B, ticks = 257, 40
     imu, motor = W.make_tick_stream(B, ticks, 51)
-    vel = _vel(B, 52)
+    vel = command_vel(B, 52)
     out = []
     for mode in (None, 0):
-        c = _ctrl(B, mode=mode)
-        out.append(_run(c, B, imu, motor, vel, 0, ticks, extra=("due", "grf", "status", "nseg")))
+        c = make_ctrl(B, schedule="per_robot", mode=mode)
+        out.append(run_ticks(c, B, imu, motor, vel, 0, ticks, extra=("due", "grf", "status", "nseg")))
         assert c.mpc.horizon == 14
         c.close()
-    _same(*out[0], *out[1], np.ones(B, bool), "explicit mode 0 vs default")
+    same_ticks(*out[0], *out[1], np.ones(B, bool), "explicit mode 0 vs default")
     for a, b in zip(out[0][1], out[1][1]):
         for k in ("counter", "due", "grf", "status", "nseg"):
             assert np.array_equal(a[k], b[k]), k
@@ -214,13 +189,13 @@ def test_reset_mid_run():
     imu, motor = W.make_tick_stream(B, n, 93)
     vel_at = {0: sweep_vel(B, 0), 120: sweep_vel(B, 1)}
     mask = np.arange(B) % 3 == 0
-    c = _ctrl(B)
+    c = make_ctrl(B, schedule="per_robot", mode=1)
     r = _run1(c, B, imu, motor, 0, n, resets={at: mask}, vel_at=vel_at)
     c.close()
-    c = _ctrl(B)
+    c = make_ctrl(B, schedule="per_robot", mode=1)
     p = _run1(c, B, imu, motor, 0, n, vel_at=vel_at)
     c.close()
-    c = _ctrl(B)
+    c = make_ctrl(B, schedule="per_robot", mode=1)
     f = _run1(c, B, imu, motor, at, ticks, vel_at={at: vel_at[120]})
     c.close()
     _same1(r, f, mask, "reset robots vs fresh mode-1 controller", a_off=at, ticks=ticks)
@@ -237,7 +212,7 @@ def test_graph_of_five_ticks_across_a_restart():
     B, K, R, pre = 150, 5, 12, 215
     n = pre + K * R
     imu, motor = W.make_tick_stream(B, n, 95)
-    eager, cap = _ctrl(B), _ctrl(B)
+    eager, cap = make_ctrl(B, schedule="per_robot", mode=1), make_ctrl(B, schedule="per_robot", mode=1)
     dev = eager.device
     for t in range(pre):
         x, y = torch.from_numpy(imu[t]).to(dev), torch.from_numpy(motor[t]).to(dev)

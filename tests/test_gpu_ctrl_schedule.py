@@ -5,7 +5,7 @@ LOCKSTEP controller freshly initialised at the moment of its reset: a fresh lock
 reference's init_controller exactly, and lockstep is what tests/test_gpu_controller.py pins against the restatement and
 the oracle.  Everything here is therefore compared bit for bit between two runs of the library:
   * the effort of every tick,
-  * the arrays of test_gpu_controller's EXACT_F32 / EXACT_I32 lists, f_ff, wpd and xci after every tick.
+  * the arrays of ctrl_gpu's EXACT_F32 / EXACT_I32 lists, f_ff, wpd and xci after every tick (its STATE).
 Streams are workloads.make_tick_stream, gaits and velocities the mixed ones of test_gpu_controller.py (every gait number
 and omni variant, switched into and out of standing at tick 20 of the stream), PID (0, 0, 3.0, 0.3).  A reset zeroes the
 robot's gait and velocity command, so both are applied again after every reset, in both runs.
@@ -22,74 +22,24 @@ import pytest
 
 from quadruped_ctrl_amd import workloads as W
 
-from test_gpu_controller import EXACT_F32, EXACT_I32, PID, _gaits, _vel
+from ctrl_gpu import PID, STATE, apply_commands, make_ctrl, run_ticks, same_ticks
+from ctrl_model import command_vel
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-STATE = EXACT_F32 + EXACT_I32 + ("f_ff", "wpd", "xci")
-SWITCH_AT = 20   # tick of the stream at which the gaits switch
-
-
-def _ctrl(B, mode):
-    from quadruped_ctrl_amd.binding import BatchedController
-    c = BatchedController(0, max_batch=B)
-    c.init(B, 500.0, PID)
-    if mode != "lockstep":
-        c.set_schedule(mode)
-    return c
-
-
-def _apply(c, B, t_abs, vel):
-    import torch
-    c.set_gait(torch.from_numpy(_gaits(B, t_abs, SWITCH_AT)).to(c.device))
-    c.set_vel(torch.from_numpy(vel).to(c.device))
-
-
-def _run(c, B, imu, motor, vel, t0, ticks, resets=None, extra=(), before=None):
-    """Ticks t0 .. t0 + ticks - 1 of the stream (absolute indices) on controller c.  resets: {tick: mask}, applied before
-    that tick.  -> (effort [ticks, B, 12], per-tick dicts of STATE + extra).  before(t): called ahead of tick t."""
-    import torch
-    dev = c.device
-    eff, snaps = [], []
-    for t in range(t0, t0 + ticks):
-        if resets and t in resets:
-            c.reset(torch.from_numpy(resets[t]).to(dev))
-        if t in (t0, SWITCH_AT) or (resets and t in resets):
-            _apply(c, B, t, vel)
-        if before:
-            before(t)
-        e = c.tick(torch.from_numpy(imu[t]).to(dev), torch.from_numpy(motor[t]).to(dev)).cpu().numpy()
-        eff.append(e)
-        snaps.append({k: c.read(k) for k in STATE + tuple(extra)})
-    return np.array(eff), snaps
-
-
-def _same(a_eff, a_snaps, b_eff, b_snaps, rows, what, a_off=0, b_off=0, ticks=None):
-    """Rows `rows` of run a from tick a_off equal those of run b from tick b_off, bit for bit, on `ticks` ticks."""
-    n = ticks if ticks is not None else min(len(a_eff) - a_off, len(b_eff) - b_off)
-    for i in range(n):
-        ea, eb = a_eff[a_off + i][rows], b_eff[b_off + i][rows]
-        assert np.array_equal(ea, eb), (what, i, "effort", np.abs(ea - eb).max())
-        for k in STATE:
-            if k == "counter":
-                continue   # compared by the caller (runs that start at different ticks count differently)
-            xa, xb = a_snaps[a_off + i][k][rows], b_snaps[b_off + i][k][rows]
-            assert np.array_equal(xa, xb), (what, i, k)
-
-
 def test_per_robot_without_resets_equals_lockstep():
     B, ticks = 257, 40
     imu, motor = W.make_tick_stream(B, ticks, 51)
-    vel = _vel(B, 52)
+    vel = command_vel(B, 52)
     out = {}
     for mode in ("lockstep", "per_robot"):
-        c = _ctrl(B, mode)
-        out[mode] = _run(c, B, imu, motor, vel, 0, ticks, extra=("due", "grf", "status"))
+        c = make_ctrl(B, schedule=mode)
+        out[mode] = run_ticks(c, B, imu, motor, vel, 0, ticks, extra=("due", "grf", "status"))
         assert c.view()["ticks"] == ticks
         c.close()
     rows = np.ones(B, bool)
-    _same(*out["lockstep"], *out["per_robot"], rows, "per_robot vs lockstep")
+    same_ticks(*out["lockstep"], *out["per_robot"], rows, "per_robot vs lockstep")
     for mode in out:
         for t, s in enumerate(out[mode][1]):
             assert (s["counter"] == t + 1).all(), (mode, t)
@@ -106,19 +56,19 @@ def test_exact_reset():
     B, at, ticks = 257, 17, 40
     n = at + ticks
     imu, motor = W.make_tick_stream(B, n, 61)
-    vel = _vel(B, 62)
+    vel = command_vel(B, 62)
     mask = np.arange(B) % 3 == 0
-    c = _ctrl(B, "per_robot")
-    r_eff, r_snaps = _run(c, B, imu, motor, vel, 0, n, resets={at: mask}, extra=("due",))
+    c = make_ctrl(B, schedule="per_robot")
+    r_eff, r_snaps = run_ticks(c, B, imu, motor, vel, 0, n, resets={at: mask}, extra=("due",))
     c.close()
-    c = _ctrl(B, "per_robot")
-    p_eff, p_snaps = _run(c, B, imu, motor, vel, 0, n)
+    c = make_ctrl(B, schedule="per_robot")
+    p_eff, p_snaps = run_ticks(c, B, imu, motor, vel, 0, n)
     c.close()
-    c = _ctrl(B, "lockstep")
-    f_eff, f_snaps = _run(c, B, imu, motor, vel, at, ticks)
+    c = make_ctrl(B, schedule="lockstep")
+    f_eff, f_snaps = run_ticks(c, B, imu, motor, vel, at, ticks)
     c.close()
-    _same(r_eff, r_snaps, f_eff, f_snaps, mask, "reset robots vs fresh lockstep", a_off=at, ticks=ticks)
-    _same(r_eff, r_snaps, p_eff, p_snaps, ~mask, "other robots vs no reset")
+    same_ticks(r_eff, r_snaps, f_eff, f_snaps, mask, "reset robots vs fresh lockstep", a_off=at, ticks=ticks)
+    same_ticks(r_eff, r_snaps, p_eff, p_snaps, ~mask, "other robots vs no reset")
     for i in range(ticks):
         s = r_snaps[at + i]
         assert (s["counter"][mask, 0] == i + 1).all(), i                 # ticks since the reset
@@ -157,10 +107,10 @@ def test_stagger():
     B, ticks = 1024, 40
     n = 13 + ticks
     imu, motor = W.make_tick_stream(B, n, 71)
-    vel = _vel(B, 72)
+    vel = command_vel(B, 72)
     group = np.arange(B) % 13
     resets = {g: group == g for g in range(13)}
-    c = _ctrl(B, "per_robot")
+    c = make_ctrl(B, schedule="per_robot")
     prev = {}
     keys = ("f_ff", "grf", "status", "wpd", "xci", "first_run", "current_gait")
 
@@ -170,7 +120,7 @@ def test_stagger():
 
     eff, snaps = [], []
     for t in range(n):
-        e, s = _run(c, B, imu, motor, vel, t, 1, resets=resets, before=before,
+        e, s = run_ticks(c, B, imu, motor, vel, t, 1, resets=resets, before=before,
                     extra=("due", "grf", "status", "position", "r_body", "gait_num"))
         eff.append(e[0])
         s = s[0]
@@ -191,11 +141,11 @@ def test_stagger():
     assert c.view()["ticks"] == n
     c.close()
     for g in (0, 5):
-        f = _ctrl(B, "lockstep")
-        f_eff, f_snaps = _run(f, B, imu, motor, vel, g, ticks)
+        f = make_ctrl(B, schedule="lockstep")
+        f_eff, f_snaps = run_ticks(f, B, imu, motor, vel, g, ticks)
         f.close()
         rows = group == g
-        _same(eff, snaps, f_eff, f_snaps, rows, f"group {g} vs fresh lockstep", a_off=g, ticks=ticks)
+        same_ticks(eff, snaps, f_eff, f_snaps, rows, f"group {g} vs fresh lockstep", a_off=g, ticks=ticks)
         for i in range(ticks):
             assert np.array_equal(snaps[g + i]["counter"][rows], f_snaps[i]["counter"][rows]), (g, i)
     assert np.abs(snaps[-1]["f_ff"]).max() > 1.0
@@ -208,8 +158,8 @@ def test_graph_of_five_ticks_replayed():
     B, K, R = 300, 5, 8
     n = 13 + K * R
     imu, motor = W.make_tick_stream(B, n, 81)
-    vel = _vel(B, 82)
-    eager, cap = _ctrl(B, "per_robot"), _ctrl(B, "per_robot")
+    vel = command_vel(B, 82)
+    eager, cap = make_ctrl(B, schedule="per_robot"), make_ctrl(B, schedule="per_robot")
     dev = eager.device
     group = np.arange(B) % 13
     # thirteen eager ticks on both: the stagger (group g reset before tick g), first visit, first run, first solves
@@ -217,7 +167,7 @@ def test_graph_of_five_ticks_replayed():
         x, y = torch.from_numpy(imu[t]).to(dev), torch.from_numpy(motor[t]).to(dev)
         for c in (eager, cap):
             c.reset(torch.from_numpy(group == t).to(dev))
-            _apply(c, B, 0, vel)
+            apply_commands(c, B, 0, vel)
             c.tick(x, y)
     torch.cuda.synchronize()
     bi = torch.zeros((K, B, 10), dtype=torch.float64, device=dev)

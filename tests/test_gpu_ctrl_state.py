@@ -5,43 +5,24 @@ The estimator stage is compared with tests/ctrl_model_state.py (the cheater esti
 for bit where no transcendental is involved -- the quaternion, rBody, the three rBody^T products, position and the
 velocities -- and within the suite's 1e-5 rad for rpy (the device's atan2f / asinf).  Everything after the estimators is
 the existing tick, so it is checked with the existing restatements (tests/ctrl_model.py, tests/ctrl_model_mode1.py)
-teacher-forced on the GPU's own estimator read-out, under the rules of tests/test_gpu_controller.py and
-tests/test_gpu_ctrl_mode1.py; the remaining tests compare two runs of the library bit for bit.
+teacher-forced on the GPU's own estimator read-out (tests/ctrl_gpu.py: teacher_forced_state, mode1_state), under the rules
+of tests/test_gpu_controller.py and tests/test_gpu_ctrl_mode1.py; the remaining tests compare two runs of the library bit for bit.
 """
 import numpy as np
 import pytest
 
-from oracle import oracle as O
 from quadruped_ctrl_amd import workloads as W
 
 import ctrl_model as M
-import ctrl_model_mode1 as M1
-from ctrl_model_state import ACC, OMEGA, ORI, POS, VBODY, estimate_state, rebase_yaw
-from test_gpu_controller import EXACT_F32, EXACT_I32, LAND_ULPS, PID, _bound, _gaits, _gpu_est, _vel
+from ctrl_gpu import EXACT_F32, EXACT_I32, PID, make_ctrl, mode1_state, teacher_forced_state, to_dev
+from ctrl_model import command_gaits, command_vel
+from ctrl_model_state import ACC, OMEGA, ORI, POS, VBODY, estimate_state
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 EST_EXACT = ("orientation", "r_body", "omega_body", "omega_world", "a_world", "position", "v_world", "v_body")
 LEG = ("q", "qd", "leg_J", "leg_p", "leg_v")
-
-
-def _ctrl(B, schedule="lockstep", mode=None, freq=500.0, geom=None):
-    from quadruped_ctrl_amd.binding import BatchedController
-    c = BatchedController(0, max_batch=B)
-    c.init(B, freq, PID)
-    if geom is not None:
-        c.mpc.set_leg_geometry(*geom)
-    if schedule != "lockstep":
-        c.set_schedule(schedule)
-    if mode is not None:
-        c.set_robot_mode(mode)
-    return c
-
-
-def _dev(c, a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(c.device)
 
 
 def test_estimator_stage_bit_for_bit():
@@ -54,10 +35,10 @@ def test_estimator_stage_bit_for_bit():
     rpy = np.stack([0.45 * np.cos(np.arange(B) * 0.37), rng.uniform(-0.3, 0.3, B), np.linspace(-3.14, 3.14, B)], 1)
     rpy[1:3] = [[0.45, 0.3, 1.0], [0, 0, 0]]              # (robots 0 and 256 sit at the two ends of the circle)
     state[:, ORI] = W._quat_from_rpy(rpy)
-    c, ref = _ctrl(B), _ctrl(B)
-    c.prework_state(_dev(c, state), _dev(c, motor))
+    c, ref = make_ctrl(B), make_ctrl(B)
+    c.prework_state(to_dev(c, state), to_dev(c, motor))
     imu, _ = W.make_tick_stream(B, 1, 101)
-    ref.prework(_dev(ref, imu[0]), _dev(ref, motor))
+    ref.prework(to_dev(ref, imu[0]), to_dev(ref, motor))
     m = M.CtrlModel(B, 500.0, PID)
     e = estimate_state(m, state, motor)
     assert np.abs(e["rpy"][:, 0]).max() > 0.44 and np.ptp(e["rpy"][:, 2]) > 6.2
@@ -79,14 +60,14 @@ def test_one_code_path_for_the_orientation():
     bit: both estimators call the same quaternionToRotationMatrix / quatToRPY / rBody^T code."""
     B = 64
     imu, motor = W.make_tick_stream(B, 1, 111)
-    a, b = _ctrl(B), _ctrl(B)
-    a.prework(_dev(a, imu[0]), _dev(a, motor[0]))
+    a, b = make_ctrl(B), make_ctrl(B)
+    a.prework(to_dev(a, imu[0]), to_dev(a, motor[0]))
     state = np.zeros((B, 16))
     state[:, ORI] = a.read("orientation").astype(np.float64)
     state[:, OMEGA] = imu[0][:, 7:10]
     state[:, ACC] = imu[0][:, 0:3]
     state[:, POS] = [0, 0, 0.29]
-    b.prework_state(_dev(b, state), _dev(b, motor[0]))
+    b.prework_state(to_dev(b, state), to_dev(b, motor[0]))
     for k in ("orientation", "rpy", "r_body", "omega_world", "a_world"):
         assert np.array_equal(a.read(k), b.read(k)), k
     assert np.abs(a.read("rpy")[:, 2]).max() < 1e-6      # (the IMU path re-based yaw on this first visit)
@@ -96,14 +77,14 @@ def test_one_code_path_for_the_orientation():
 
 def test_filter_is_left_alone():
     B = 32
-    c = _ctrl(B)
+    c = make_ctrl(B)
     keys = ("xhat", "P", "first_visit", "ori_ini_inv", "kf_p", "kf_v")
     before = {k: c.read(k) for k in keys}
     assert (before["first_visit"] == 1).all() and (before["P"][:, 0] == 100).all()
     state, motor = W.make_state_stream(B, 20, 121)
-    c.set_vel(_dev(c, _vel(B, 122)))
+    c.set_vel(to_dev(c, command_vel(B, 122)))
     for t in range(20):
-        eff = c.tick_state(_dev(c, state[t]), _dev(c, motor[t]))
+        eff = c.tick_state(to_dev(c, state[t]), to_dev(c, motor[t]))
     assert np.isfinite(eff.cpu().numpy()).all() and c.view()["ticks"] == 20
     for k in keys:
         assert np.array_equal(c.read(k), before[k]), k
@@ -111,7 +92,7 @@ def test_filter_is_left_alone():
 
 
 def test_teacher_forced_tick_parity_state():
-    """tests/test_gpu_controller.py::_teacher_forced with tick_state: robot mode 0, lockstep, 257 robots, 40 ticks (three
+    """tests/ctrl_gpu.py: teacher_forced with tick_state: robot mode 0, lockstep, 257 robots, 40 ticks (three
     MPC ticks), every gait number and omni variant, switched at tick 20.
 
     The stream is make_state_stream's with every robot's yaw re-based on its tick-0 yaw (ctrl_model_state.rebase_yaw).
@@ -125,204 +106,27 @@ def test_teacher_forced_tick_parity_state():
     set full -- and zero forces).  The whole circle of yaw is covered where no solver is involved:
     test_estimator_stage_bit_for_bit, and the raw stream in every other test of this file.  Nobody is dropped here, and
     the test asserts that the reference converged on every robot it compares with."""
-    _teacher_forced_state(257, 40, 257, 20)
-
-
-def _model(cls, B, freq, geom):
-    return cls(B, freq, PID) if geom is None else cls(B, freq, PID, geom=geom)
-
-
-def _teacher_forced_state(B, ticks, seed, switch_at, freq=500.0, geom=None, gaits_at=None, vel_at=None, mpc="oracle",
-                          capped="assert", stream=None, each_tick=None):
-    """The body of test_teacher_forced_tick_parity_state.  freq: qmpc_ctrl_init's (the stream is sampled at 1 / freq);
-    geom: qmpc_set_leg_geometry's four lengths, None for the handle's default.
-    gaits_at / vel_at: {tick: command}, given before that tick (default: the suite's gaits at 0 and switch_at, its
-    velocities at 0).  mpc: "oracle" compares f_ff with the oracle pipeline on every MPC tick; "forced" only takes the
-    device's f_ff over, as test_safety_latch_and_abs_binding does.  capped: what to do where the reference stopped at its
-    nWSR cap -- "assert" that it nowhere did, or compare with the same pipeline run to "converged"
-    (test_gpu_ctrl_mode1._converged).  stream: (state, motor) instead of the re-based make_state_stream(seed).
-    each_tick(t, c, m, e): called at the end of every tick with the controller, the model and the estimator read-out."""
-    assert mpc in ("oracle", "forced") and capped in ("assert", "converged")
-    c = _ctrl(B, freq=freq, geom=geom)
-    m = _model(M.CtrlModel, B, freq, geom)
-    if stream is None:
-        state, motor = W.make_state_stream(B, ticks, seed, dt=1.0 / freq)
-        state = rebase_yaw(state)
-    else:
-        state, motor = stream
-    assert np.abs(np.linalg.norm(state[..., ORI], axis=-1) - 1).max() < 1e-12
-    if gaits_at is None:
-        gaits_at = {0: _gaits(B, 0, switch_at)}
-        gaits_at[switch_at] = _gaits(B, switch_at, switch_at)
-    if vel_at is None:
-        vel_at = {0: _vel(B, seed + 1)}
-    vel = vel_at[0]
-    c.set_vel(_dev(c, vel))
-    m.set_vel(vel)
-    # what the model receives is what `state` gives, through estimate_state: a path that ran the filter cannot pass
-    c.prework_state(_dev(c, state[0]), _dev(c, motor[0]))
-    e0 = estimate_state(_model(M.CtrlModel, B, freq, geom), state[0], motor[0])
-    g0 = _gpu_est(c)
-    for k in ("position", "v_world"):
-        assert np.array_equal(g0[k], e0[k]), k
-    assert np.array_equal(g0["position"], state[0][:, POS].astype(f32))
-    assert np.abs(g0["v_world"]).max() > 0.1 and c.view()["ticks"] == 0
-    n_mpc, worst_land = 0, 0.0
-    for t in range(ticks):
-        if t in gaits_at:
-            g = gaits_at[t]
-            c.set_gait(_dev(c, g))
-            m.set_gait(g)
-        if t in vel_at and t > 0:
-            c.set_vel(_dev(c, vel_at[t]))
-            m.set_vel(vel_at[t])
-        eff = c.tick_state(_dev(c, state[t]), _dev(c, motor[t])).cpu().numpy()
-        e = _gpu_est(c)
-        assert np.array_equal(e["position"], state[t][:, POS].astype(f32)), t
-        e["leg_q"] = motor[t][:, :12].astype(f32)
-        gpu_pf = c.read("sw_pf")
-        out = m.loco(e, pf_override=gpu_pf)
-        scale = np.maximum(1.0, np.abs(out["pf"]))
-        land = np.abs(gpu_pf - out["pf"]) / (np.finfo(f32).eps * scale)
-        assert land.max() <= LAND_ULPS, (t, land.max())
-        worst_land = max(worst_land, float(land.max()))
-        zero_yr = m.vel_des[:, 2] == 0
-        assert np.array_equal(gpu_pf[zero_yr], out["pf"][zero_yr]), t
-        for k in EXACT_I32:
-            assert np.array_equal(c.read(k).reshape(getattr(m, k).shape), getattr(m, k)), (t, k)
-        for k in EXACT_F32:
-            g_ = c.read(k).reshape(getattr(m, k).shape)
-            assert np.array_equal(g_, getattr(m, k)), (t, k, np.abs(g_ - getattr(m, k)).max())
-        if (t + 1) % 13 == 0:
-            n_mpc += 1
-            rec, wpd, xci = O.pack_commands(m.command(e), float(m.dt_mpc))
-            m.wpd[:], m.xci[:] = wpd, xci
-            rec.update(dt=float(m.dt_mpc), mu=0.4, f_max=120.0)
-            f_gpu = c.read("f_ff")
-            if mpc == "oracle":
-                soln, nwsr, rc = O.solve_batch(rec)
-                assert (rc == 0).all()
-                if capped == "converged":
-                    from test_gpu_ctrl_mode1 import _converged
-                    over_cap = np.flatnonzero(nwsr >= 100)
-                    for i in over_cap:                            # (the reference stopped at its cap: see there)
-                        soln[i] = _converged(rec, int(i))
-                    print(f"tick {t}: {len(over_cap)} robots compared with the pipeline run to convergence {over_cap.tolist()}")
-                f_ref = O.forces_to_body(e["r_body"], soln[:, :12].astype(f32))
-                err = np.abs(f_gpu.astype(np.float64) - f_ref).max(1) / np.maximum(np.abs(f_ref).max(1), 1.0)
-                print(f"tick {t}: worst relative f_ff error {err.max():.3e}, {(err >= 1e-4).sum()} robots over 1e-4, "
-                      f"largest reference nWSR {nwsr.max()}, |yaw - yaw_des_true| up to {np.abs(e['rpy'][:, 2] - m.yaw_des_true).max():.3f}")
-                if (err >= 1e-4).any():
-                    bnd, st = _bound(rec, err), c.read("status")[:, 0]
-                    for i in np.flatnonzero(err >= 1e-4):
-                        print(f"  robot {i}: error {err[i]:.3e}, bound {bnd[i]:.3e}, reference nWSR {nwsr[i]}, status {st[i]}, "
-                              f"gait {m.gait_num[i]}, v_world {e['v_world'][i]}, command {m.vel_des[i]}")
-                    assert (err <= bnd).all(), (t, err.max())
-                if capped == "assert":
-                    assert (nwsr < 100).all(), (t, np.flatnonzero(nwsr >= 100))     # the reference converged on every robot
-                assert (c.read("status")[:, 0] & 47 == 0).all(), t               # and the library reports no error bit
-            m.f_ff[:] = f_gpu
-        for k in ("wpd", "xci"):
-            assert np.array_equal(c.read(k).reshape(getattr(m, k).shape), getattr(m, k)), (t, k)
-        eff_m = m.legcmd(e, m.f_ff)
-        assert np.array_equal(eff, eff_m), (t, np.abs(eff - eff_m).max())
-        if each_tick is not None:
-            each_tick(t, c, m, e)
-    print(f"largest landing-point distance {worst_land:.2f} of {LAND_ULPS} ulps")
-    assert n_mpc == ticks // 13 and c.view()["ticks"] == ticks
-    assert np.isfinite(eff).all() and (c.read("safe") == 1).all()
-    c.close()
+    teacher_forced_state(257, 40, 257, 20)
 
 
 def test_mode1_per_robot_schedule_state():
     """Robot mode 1 on state ticks, 64 robots, 400 ticks, teacher-forced against CtrlModelMode1 as
     tests/test_gpu_ctrl_mode1.py does it (without the oracle solves): x commands over [0, 2] m/s."""
-    seen, n_solves = _mode1_state(64, 400, 131)
+    seen, n_solves = mode1_state(64, 400, 131)
     assert len(seen) >= 3, seen
     assert n_solves > 64 * (400 // 13 - 6)
-
-
-def _mode1_state(B, ticks, seed, freq=500.0, geom=None, check_mpc=False):
-    """The body of test_mode1_per_robot_schedule_state -> (segment counts seen, solves).  freq, geom: as in
-    _teacher_forced_state.  check_mpc: the stream's yaw re-based as in test_teacher_forced_tick_parity_state, and the due
-    robots' forces against the oracle pipeline under tests/test_gpu_parity.py's bound_for, as
-    tests/test_gpu_ctrl_mode1.py::test_model_parity_and_forces does it."""
-    c = _ctrl(B, "per_robot", 1, freq=freq, geom=geom)
-    m = _model(M1.CtrlModelMode1, B, freq, geom)
-    state, motor = W.make_state_stream(B, ticks, seed, dt=1.0 / freq)
-    if check_mpc:
-        state = rebase_yaw(state)
-    g = np.array([9, 29, 4, 24, 0, 30], np.int32)[np.arange(B) % 6]
-    vel = np.zeros((B, 3))
-    vel[:, 0] = np.linspace(0.0, 2.0, B)
-    vel[1::4, 1] = 0.25
-    vel[2::8, 2] = 0.3
-    c.set_gait(_dev(c, g))
-    c.set_vel(_dev(c, vel))
-    m.set_gait(g)
-    m.set_vel(vel)
-    seen, n_solves = set(), 0
-    for t in range(ticks):
-        eff = c.tick_state(_dev(c, state[t]), _dev(c, motor[t])).cpu().numpy()
-        e = _gpu_est(c)
-        e["leg_q"] = motor[t][:, :12].astype(f32)
-        gpu_pf = c.read("sw_pf")
-        out = m.loco(e, pf_override=gpu_pf)
-        scale = np.maximum(1.0, np.abs(out["pf"]))
-        land = np.abs(gpu_pf - out["pf"]) / (np.finfo(f32).eps * scale)
-        assert land.max() <= LAND_ULPS, (t, land.max())
-        for k in EXACT_I32 + ("nseg",):          # (offsets, durations among them)
-            assert np.array_equal(c.read(k).reshape(getattr(m, k).shape), getattr(m, k)), (t, k)
-        assert np.array_equal(c.read("due")[:, 0] != 0, m.due), t
-        for k in EXACT_F32 + ("gait_phase",):
-            g_ = c.read(k).reshape(getattr(m, k).shape)
-            assert np.array_equal(g_, getattr(m, k)), (t, k, np.abs(g_ - getattr(m, k)).max())
-        due = np.flatnonzero(m.due)
-        f_gpu = c.read("f_ff")
-        if len(due):
-            n_solves += len(due)
-            cmd, tables = m.command_mode1(e, due)
-            mo, md, it = c.read("mpc_offsets"), c.read("mpc_durations"), c.read("iteration")[:, 0]
-            for k, b in enumerate(due):
-                assert np.array_equal(M.mpc_table(mo[b], md[b], int(it[b]), n=10), tables[k]), (t, b)
-            rec, wpd, xci = O.pack_commands(cmd, float(m.dt_mpc))
-            m.wpd[due], m.xci[due] = wpd, xci
-            if check_mpc:
-                from test_gpu_ctrl_mode1 import _converged
-                from test_gpu_parity import bound_for
-                rec["gait"] = tables
-                rec.update(dt=float(m.dt_mpc), mu=0.4, f_max=120.0)
-                soln, nwsr, rc = O.solve_batch(rec)
-                assert (rc == 0).all(), t
-                for k in np.flatnonzero(nwsr >= 100):                     # (the reference stopped at its cap: see there)
-                    soln[k] = _converged(rec, int(k))
-                f_ref = O.forces_to_body(e["r_body"][due], soln[:, :12].astype(f32))
-                err = np.abs(f_gpu[due].astype(np.float64) - f_ref).max(1) / np.maximum(np.abs(f_ref).max(1), 1.0)
-                print(f"tick {t}: {len(due)} solves, worst relative f_ff error {err.max():.3e}")
-                if (err >= 1e-4).any():
-                    assert (err <= bound_for(rec, err=err)).all(), (t, err.max())
-                assert (c.read("status")[due, 0] & 47 == 0).all(), t
-            m.f_ff[due] = f_gpu[due]
-        assert np.array_equal(f_gpu[~m.due], m.f_ff[~m.due]), t
-        for k in ("wpd", "xci"):
-            assert np.array_equal(c.read(k).reshape(getattr(m, k).shape), getattr(m, k)), (t, k)
-        assert np.array_equal(eff, m.legcmd(e, m.f_ff)), t
-        seen |= set(int(x) for x in m.nseg)
-    assert np.isfinite(eff).all()
-    c.close()
-    return seen, n_solves
 
 
 def test_safety_latch_state():
     """Robot 2's state quaternion has roll 0.7 rad from tick 5: it latches on that tick and outputs zeros from then on;
     robot 1 at roll 0.45 rad keeps running."""
     B, ticks = 6, 30
-    c = _ctrl(B)
+    c = make_ctrl(B)
     state, motor = W.make_state_stream(B, ticks, 3, roll=(1, 0.45, 0))
     s2, _ = W.make_state_stream(B, ticks, 3, roll=(2, 0.7, 5))
     state[:, 2] = s2[:, 2]
     for t in range(ticks):
-        eff = c.tick_state(_dev(c, state[t]), _dev(c, motor[t])).cpu().numpy()
+        eff = c.tick_state(to_dev(c, state[t]), to_dev(c, motor[t])).cpu().numpy()
         safe, rpy = c.read("safe")[:, 0], c.read("rpy")
         assert safe[1] == 1 and 0.4 < abs(rpy[1, 0]) < 0.5, (t, rpy[1])
         assert safe[2] == (1 if t < 5 else 0), t
@@ -338,19 +142,19 @@ def test_reset_state_per_robot():
     reset; the reset ones restart at counter 0 and first solve 13 ticks later."""
     B, at, ticks = 32, 17, 32
     state, motor = W.make_state_stream(B, ticks, 141)
-    a, b = _ctrl(B, "per_robot"), _ctrl(B, "per_robot")
-    g, v = _gaits(B, 0, 10 ** 9), _vel(B, 142)
+    a, b = make_ctrl(B, schedule="per_robot"), make_ctrl(B, schedule="per_robot")
+    g, v = command_gaits(B, 0, 10 ** 9), command_vel(B, 142)
     mask = np.arange(B) % 2 == 0
     for c in (a, b):
-        c.set_gait(_dev(c, g))
-        c.set_vel(_dev(c, v))
+        c.set_gait(to_dev(c, g))
+        c.set_vel(to_dev(c, v))
     for t in range(ticks):
         if t == at:
-            a.reset(_dev(a, mask))
+            a.reset(to_dev(a, mask))
             assert (a.read("counter")[mask, 0] == 0).all() and (a.read("counter")[~mask, 0] == at).all()
-            a.set_gait(_dev(a, g))
-            a.set_vel(_dev(a, v))
-        x, y = _dev(a, state[t]), _dev(a, motor[t])
+            a.set_gait(to_dev(a, g))
+            a.set_vel(to_dev(a, v))
+        x, y = to_dev(a, state[t]), to_dev(a, motor[t])
         ea, eb = a.tick_state(x, y).cpu().numpy(), b.tick_state(x, y).cpu().numpy()
         assert np.array_equal(ea[~mask], eb[~mask]), t
         due = a.read("due")[:, 0]
@@ -369,14 +173,14 @@ def test_graph_capture_replay_matches_eager_state():
     """13 captured tick_state calls replayed twice equal 39 eager ticks of a second controller, bit for bit."""
     import torch
     B = 64
-    eager, cap = _ctrl(B), _ctrl(B)
+    eager, cap = make_ctrl(B), make_ctrl(B)
     dev = eager.device
     state, motor = W.make_state_stream(B, 39, 151)
     for c in (eager, cap):
-        c.set_gait(_dev(c, _gaits(B, 0, 10 ** 9)))
-        c.set_vel(_dev(c, _vel(B, 152)))
+        c.set_gait(to_dev(c, command_gaits(B, 0, 10 ** 9)))
+        c.set_vel(to_dev(c, command_vel(B, 152)))
     for t in range(13):          # first run and one MPC, eager on both
-        x, y = _dev(eager, state[t]), _dev(eager, motor[t])
+        x, y = to_dev(eager, state[t]), to_dev(eager, motor[t])
         eager.tick_state(x, y)
         cap.tick_state(x, y)
     torch.cuda.synchronize()
@@ -398,7 +202,7 @@ def test_graph_capture_replay_matches_eager_state():
         graph.replay()
         torch.cuda.synchronize()
         for k in range(13):
-            ee = eager.tick_state(_dev(eager, state[lo + k]), _dev(eager, motor[lo + k]))
+            ee = eager.tick_state(to_dev(eager, state[lo + k]), to_dev(eager, motor[lo + k]))
             torch.cuda.synchronize()
             assert torch.equal(ee, be[k]), (r, k)
     for k in ("f_ff", "p_des", "counter", "xhat", "wpd", "xci", "safe"):

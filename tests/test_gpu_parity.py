@@ -28,6 +28,8 @@ Tolerances (floating point, stated per north_star):
         assembled H_red, g_red vs the fp64 model (same float transcendentals) <= 1e-10 rel
         assembled H_red, g_red vs the float restatement                      <= 5e-6 rel
         GPU solution vs the reference qpOASES on the SAME H,g                 <= 1e-8 rel
+The helpers that evaluate these bounds (bound_for, report, dump_model_compare, solver_parity_on_own_qp, ...) are in
+tests/solve_gpu.py, with what the other solve tests share.
 """
 import ctypes as C
 import glob
@@ -38,73 +40,15 @@ import numpy as np
 import pytest
 
 from oracle import kron_model as K
-from oracle import noise_floor as NF
 from oracle import oracle as O
 from quadruped_ctrl_amd import workloads as W
+from solve_gpu import (REC_KEYS, SPREAD_FACTOR, bound_for, dump_model_compare, gpu_pack, load_gold, pack_setup, rel_f0, report,
+                       solver_parity_on_own_qp, take)
 
 pytestmark = pytest.mark.gpu
 GOLD = sorted(p for p in glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz"))
               if not os.path.basename(p).startswith("pack_"))
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def rel_f0(f, ref):
-    ref12 = ref[:, :12]
-    return np.abs(f.astype(np.float64) - ref12).max(1) / np.maximum(np.abs(ref12).max(1), 1.0)
-
-
-def load_gold(path):
-    z = np.load(path)
-    b = {k: z[k] for k in z.files}
-    for k in ("batch", "horizon"):
-        b[k] = int(b[k])
-    for k in ("dt", "mu", "f_max"):
-        b[k] = float(b[k])
-    return b
-
-
-NOISE = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "noise_floor.json")))["families"]
-
-
-def bound_for(b, idx=None, family=None, full=False, err=None):
-    """Per-robot end-to-end bound max(1e-4, 1.5 spread_i) at every horizon, with spread_i = the
-    pairwise spread of the reference's six float evaluation orders on that robot
-    (oracle/noise_floor.py: spread12 / spread_full -- reference pipeline only, no fp64 term, so the
-    bound does not know what the GPU computes).  family = golden file name -> committed per-robot
-    spreads; otherwise computed live with the oracle.  err (the measured errors of the same robots):
-    the spread is then evaluated only for the robots over the flat 1e-4 -- a robot at or under it
-    passes whatever its spread is, so the others keep the bound 1e-4."""
-    idx = list(range(b["batch"])) if idx is None else list(idx)
-    if family is not None:
-        fl = np.array(NOISE[family]["per_robot_spread_full" if full else "per_robot_spread_first_step"])[idx]
-    else:
-        key = "spread_full" if full else "spread12"
-        need = np.ones(len(idx), bool) if err is None else ~(np.asarray(err) < 1e-4)
-        if err is None and b["horizon"] <= 10:
-            need[:] = False     # (callers that give no errors assert against the flat 1e-4 at h <= 10, as before)
-        fl = np.zeros(len(idx))
-        for k in np.flatnonzero(need):
-            fl[k] = NF.robot_floor(b, idx[k])[key]
-    # six evaluation orders are six SAMPLES of the reference's rounding noise; the exactly-assembled answer the GPU
-    # reproduces need not lie inside their hull (measured: up to 1.6x the pairwise spread on the committed
-    # families below 1e-4, 1.25x on a robot of configs[3] over it), hence the factor -- still a function of the
-    # reference alone
-    return np.maximum(1e-4, SPREAD_FACTOR * fl)
-
-
-SPREAD_FACTOR = 1.5
-
-
-def report(name, err, bound):
-    over = err > 1e-4
-    print(f"{name}: rel err median {np.median(err):.2e} p99 {np.percentile(err, 99):.2e} max {err.max():.2e}; "
-          f"bound (reference float-order spread) min {bound.min():.2e} max {bound.max():.2e}; "
-          f"robots over 1e-4: {over.sum()}/{err.size} = {over.mean():.4f}")
-    # robots outside the reference's own pairwise spread (1.0 x), whether or not they pass the 1.5 x bound, are named
-    raw = np.where(bound > 1e-4, bound / SPREAD_FACTOR, bound)
-    for i in np.nonzero(~(err < raw))[0][:20]:
-        print(f"   robot {i}: err {err[i]:.3e} vs float-order spread {raw[i]:.3e} (bound {bound[i]:.3e})"
-              + ("  FAIL" if not err[i] < bound[i] else ""))
 
 
 @pytest.mark.parametrize("path", GOLD, ids=[os.path.basename(p)[:-4] for p in GOLD])
@@ -231,43 +175,13 @@ def test_closed_loop_cycles_vs_oracle(cfg, B, mpc_factory):
         ro.advance(res["grf"])
 
 
-def _dump_model_compare(m, b, idx):
-    """GPU H_red, g_red (fp64) of robots idx vs the fp64 model fed the kernel's own float
-    transcendentals -> worst relative differences (H, g)."""
-    B = b["batch"]
-    Hd, gd, ld = m.debug_dump(B)
-    aux = m.debug_aux(B)
-    res = m.solve(b, full=True)
-    m.debug_off()
-    assert ((res["status"] & 47) == 0).all()
-    sel = np.asarray(list(idx))
-    import torch
-    ti = torch.as_tensor(sel, device=Hd.device)
-    Hc, gc, ac = Hd[ti].cpu().numpy(), gd[ti].cpu().numpy(), aux[ti].cpu().numpy()
-    worst_h = worst_g = 0.0
-    for k, i in enumerate(sel):
-        a = ac[k]
-        # the transcendentals themselves: float evaluations of the same angles (<= 2 ulp of float)
-        assert abs(a[0] - np.cos(np.float64(b["yaw"][i]))) < 3e-7 and abs(a[1] - np.sin(np.float64(b["yaw"][i]))) < 3e-7
-        r64 = K.quat_to_rpy(b["q"][i])
-        assert np.abs(a[2:5] - np.array(r64)).max() < 1e-6
-        H, g = K.assemble(b, i, trig=(a[0], a[1]), rpy=(a[2], a[3], a[4]))
-        st = np.flatnonzero(b["gait"][i])
-        vi = (3 * st[:, None] + np.arange(3)[None]).reshape(-1)
-        n = vi.size
-        Hr, gr = H[np.ix_(vi, vi)], g[vi]
-        worst_h = max(worst_h, np.abs(Hc[k][:n, :n] - Hr).max() / np.abs(Hr).max())
-        worst_g = max(worst_g, np.abs(gc[k][:n] - gr).max() / np.abs(gr).max())
-    return worst_h, worst_g
-
-
 @pytest.mark.parametrize("path", GOLD, ids=[os.path.basename(p)[:-4] for p in GOLD])
 def test_assembly_vs_fp64_model_golden(path, mpc_factory):
     """The kernel's closed-form assembly IS the fp64 condensation: on every golden family the
     dumped H_red, g_red agree with oracle/kron_model.assemble (dense Kronecker sum in numpy
     fp64, fed the kernel's own float sin/cos/atan2/asin values) to 1e-10."""
     b = load_gold(path)
-    wh, wg = _dump_model_compare(mpc_factory(b), b, range(0, b["batch"], max(1, b["batch"] // 16)))
+    wh, wg = dump_model_compare(mpc_factory(b), b, range(0, b["batch"], max(1, b["batch"] // 16)))
     print(os.path.basename(path), "H rel", wh, "g rel", wg)
     assert wh < 1e-10 and wg < 1e-10
 
@@ -281,7 +195,7 @@ def test_assembly_vs_fp64_model_x_drag_and_parameters(mpc_factory):
         b["x_drag"] = rng.normal(0, 0.7, B).astype(np.float32)
         b["alpha"] = (4e-5 * rng.uniform(0.25, 2.0, B)).astype(np.float32)
         b["weights"] = (b["weights"] * rng.uniform(0.5, 2.0, (B, 12))).astype(np.float32)
-        wh, wg = _dump_model_compare(mpc_factory(b), b, range(0, B, max(1, B // 12)))
+        wh, wg = dump_model_compare(mpc_factory(b), b, range(0, B, max(1, B // 12)))
         print("h", b["horizon"], "H rel", wh, "g rel", wg)
         assert wh < 1e-10 and wg < 1e-10
 
@@ -550,7 +464,7 @@ def test_long_horizons_vs_oracle(h, gait, B, mpc_factory):
     assert 3 * nst.max() <= 192
     m = mpc_factory(b)
     m.set_split(True)
-    res, idx, worst, nact = _solver_parity_on_own_qp(m, b, lambda r: np.argsort(r["iters"])[-4:], nwsr=5000)
+    res, idx, worst, nact = solver_parity_on_own_qp(m, b, lambda r: np.argsort(r["iters"])[-4:], nwsr=5000)
     assert ((res["status"] & 47) == 0).all()
     ref, nwsr, rc = O.solve_batch(b)
     # The reference caps qpOASES at nWSR = 100 working-set recalculations and ignores init()'s return value
@@ -953,23 +867,6 @@ def test_many_active_constraints_engine_fallback(mpc_factory):
 
 
 # ---------------------------------------------------------------- caller side on the GPU
-REC_KEYS = ("p", "v", "q", "w", "r", "yaw", "traj", "gait", "weights", "alpha", "x_drag")
-
-
-def _gpu_pack(m, cmd):
-    import torch
-    dcmd = m.upload_command(cmd)
-    rec = m.alloc_record(cmd["batch"])
-    m.pack_async(dcmd, rec)
-    torch.cuda.synchronize()
-    got = {k: rec[k].cpu().numpy() for k in REC_KEYS}
-    return got, dcmd["world_position_desired"].cpu().numpy(), dcmd["x_comp_integral"].cpu().numpy(), rec
-
-
-def _pack_setup(cmd, dt=0.026):
-    return {"batch": cmd["batch"], "horizon": cmd["horizon"], "dt": dt, "mu": 0.4, "f_max": 120.0}
-
-
 @pytest.mark.parametrize("name", ["pack_h10", "pack_h16_omni"])
 def test_pack_golden_bit_exact(name, mpc_factory):
     """qmpc_pack / qmpc_forces_to_body against the committed fixtures: float and
@@ -980,8 +877,8 @@ def test_pack_golden_bit_exact(name, mpc_factory):
     for k in ("batch", "horizon", "omni_mode"):
         cmd[k] = int(cmd[k])
     cmd["body_height"] = float(cmd["body_height"])
-    m = mpc_factory(_pack_setup(cmd, float(z["dt"])))
-    got, wpd, xci, _ = _gpu_pack(m, cmd)
+    m = mpc_factory(pack_setup(cmd, float(z["dt"])))
+    got, wpd, xci, _ = gpu_pack(m, cmd)
     for k in REC_KEYS:
         assert np.array_equal(got[k], z["rec_" + k]), k
     assert np.array_equal(wpd, z["wpd_out"]) and np.array_equal(xci, z["xci_out"])
@@ -996,8 +893,8 @@ def test_pack_golden_bit_exact(name, mpc_factory):
 @pytest.mark.parametrize("B,h,omni", [(1, 10, 0), (3, 12, 1), (1025, 10, 0), (260, 16, 0)])
 def test_pack_vs_live_oracle_ragged_batches(B, h, omni, mpc_factory):
     cmd = W.make_commands(B, horizon=h, seed=100 + B, omni_mode=omni, stand_fraction=0.2)
-    m = mpc_factory(_pack_setup(cmd))
-    got, wpd, xci, _ = _gpu_pack(m, cmd)
+    m = mpc_factory(pack_setup(cmd))
+    got, wpd, xci, _ = gpu_pack(m, cmd)
     ref, wpd_r, xci_r = O.pack_commands(cmd, np.float32(0.026))
     for k in REC_KEYS:
         assert np.array_equal(got[k], ref[k]), k
@@ -1009,7 +906,7 @@ def test_pack_then_solve_end_to_end(mpc_factory):
     the reference pipeline (oracle packing + oracle assembly + reference qpOASES)."""
     import torch
     cmd = W.make_commands(192, horizon=10, seed=77, stand_fraction=0.15)
-    m = mpc_factory(_pack_setup(cmd))
+    m = mpc_factory(pack_setup(cmd))
     dcmd = m.upload_command(cmd)
     rec = m.alloc_record(cmd["batch"])
     o = m.alloc_outputs(cmd["batch"], full=True)
@@ -1040,47 +937,9 @@ def test_class3_working_set_beyond_48_slots(mpc_factory):
     cmd = W.make_commands(150, horizon=14, seed=6, stand_fraction=0.1)
     b, _, _ = O.pack_commands(cmd, np.float32(0.026))
     b.update(dt=0.026, mu=0.4, f_max=120.0)
-    m = mpc_factory(b)
-    Hd, gd, ld = m.debug_dump(b["batch"])
-    res = m.solve(b, full=True)
-    m.debug_off()
-    Hd, gd = Hd.cpu().numpy(), gd.cpu().numpy()
-    assert ((res["status"] & 47) == 0).all()
     nst = (b["gait"] != 0).sum(1)
-    big = np.nonzero((3 * nst > 128) & (res["iters"] > 48))[0]
+    res, big, worst, nact = solver_parity_on_own_qp(mpc_factory(b), b, lambda r: np.nonzero((3 * nst > 128) & (r["iters"] > 48))[0])
     assert len(big) >= 2
-    for i in big:
-        H, g, A, lb, ub, x0 = O.assemble(b, i)
-        ve, Hr, gr, Ar, lr, ur = O.reduce(H, g, A, lb, ub)
-        n = gr.size
-        xq, y, used, rc, irc = O.qpoases(Hd[i][:n, :n], gd[i][:n], Ar, lr, ur, nwsr=20000)
-        assert rc == 0 and irc == 0
-        xs = res["soln"][i][~ve]
-        assert np.abs(xs - xq).max() / max(np.abs(xq).max(), 1.0) < 1e-8
-
-
-def _solver_parity_on_own_qp(m, b, pick, tol=1e-8, nwsr=20000):
-    """Solve b with the QP dump on and compare the robots `pick(res)` selects with the reference's qpOASES
-    (iteration cap lifted) on the GPU's own assembled QP."""
-    Hd, gd, ld = m.debug_dump(b["batch"])
-    res = m.solve(b, full=True)
-    m.debug_off()
-    Hd, gd = Hd.cpu().numpy(), gd.cpu().numpy()
-    assert ((res["status"] & 47) == 0).all()
-    idx = pick(res)
-    worst, nact = 0.0, []
-    for i in idx:
-        H, g, A, lb, ub, x0 = O.assemble(b, i)
-        ve, Hr, gr, Ar, lr, ur = O.reduce(H, g, A, lb, ub)
-        n = gr.size
-        xq, y, used, rc, irc = O.qpoases(Hd[i][:n, :n], gd[i][:n], Ar, lr, ur, nwsr=nwsr)
-        assert rc == 0 and irc == 0
-        xs = res["soln"][i][~ve]
-        worst = max(worst, np.abs(xs - xq).max() / max(np.abs(xq).max(), 1.0))
-        ax = Ar @ xq
-        nact.append(int(((ax - lr < 1e-7) | (ur - ax < 1e-7)).sum()))   # rows at a bound at the solution
-    assert worst < tol, worst
-    return res, idx, worst, nact
 
 
 @pytest.mark.parametrize("mk,name", [(lambda: W.make_standing(384, 10), "standing h10 (128-row class)"),
@@ -1092,7 +951,7 @@ def test_event_pool_overflow_continues_in_global_memory(mk, name, mpc_factory):
     b = mk()
     m = mpc_factory(b)
     m.set_split(False)   # the one-kernel path owns the overflow pool (the decoupled engine keeps its events in registers)
-    res, idx, worst, _ = _solver_parity_on_own_qp(m, b, lambda r: np.nonzero(r["status"] & 128)[0][:6])
+    res, idx, worst, _ = solver_parity_on_own_qp(m, b, lambda r: np.nonzero(r["status"] & 128)[0][:6])
     print(name, "spilled robots", int(((res["status"] & 128) != 0).sum()), "checked", len(idx), "worst err", worst,
           "fallback", int(((res["status"] & 16) != 0).sum()))
     assert len(idx) >= 1
@@ -1187,7 +1046,7 @@ def test_decoupled_path_matches_one_kernel_path_and_qpoases(mk, name, mpc_factor
     m.set_split(False)
     one = m.solve(b, full=True)
     m.set_split(True)
-    res, idx, worst, nact = _solver_parity_on_own_qp(m, b, lambda r: np.argsort(r["iters"])[-4:])
+    res, idx, worst, nact = solver_parity_on_own_qp(m, b, lambda r: np.argsort(r["iters"])[-4:])
     assert ((one["status"] & 47) == 0).all() and ((res["status"] & 47) == 0).all()
     scale = np.abs(one["soln"]).max(1).clip(1.0)
     d = (np.abs(res["soln"] - one["soln"]).max(1) / scale).max()
@@ -1274,7 +1133,7 @@ def test_decoupled_engine_overflow_events_continue_in_global_memory(mpc_factory)
     m.set_min_stance(64)
     m.set_split(True)
     pick = lambda r: np.argsort(r["iters"])[-4:]
-    res, idx, worst, nact = _solver_parity_on_own_qp(m, b, pick)
+    res, idx, worst, nact = solver_parity_on_own_qp(m, b, pick)
     spilled = (res["status"] & 128) != 0
     print("iters of the hardest", res["iters"][idx].tolist(), "spilled", int(spilled.sum()), "handed back",
           int(((res["status"] & 16) != 0).sum()), "worst err vs qpOASES", worst)
@@ -1297,16 +1156,10 @@ def test_class3_working_sets_beyond_ninety_constraints_and_compaction(mpc_factor
     b.update(dt=0.026, mu=0.4, f_max=40.0)
     m = mpc_factory(b)
     pick = lambda r: np.unique(np.concatenate([np.argsort(r["iters"])[-3:], np.nonzero(r["status"] & 64)[0][:2]]))
-    res, idx, worst, nact = _solver_parity_on_own_qp(m, b, pick, tol=1e-7)
+    res, idx, worst, nact = solver_parity_on_own_qp(m, b, pick, tol=1e-7)
     print("iters", res["iters"][idx].tolist(), "rows at a bound", nact, "compacted", int(((res["status"] & 64) != 0).sum()),
           "fallback", int(((res["status"] & 16) != 0).sum()), "worst err", worst)
     assert ((res["status"] & 47) == 0).all() and max(nact) > 90
-
-
-def _take(b, idx):
-    out = {k: (v[idx] if isinstance(v, np.ndarray) and v.shape[:1] == (b["batch"],) else v) for k, v in b.items()}
-    out["batch"] = len(idx)
-    return out
 
 
 @pytest.mark.parametrize("case", ["configs4", "configs4-admm", "standing-h14"])
@@ -1338,7 +1191,7 @@ def test_result_does_not_depend_on_the_batch_around_a_robot(case, mpc_factory):
         assert len(big) > 600                              # > 512 resident workgroups of the 96-row class
         extra += [big[:6], big[-12:]]
     pick = np.unique(np.concatenate([rng.choice(B, 24, replace=False)] + extra))
-    sub = _take(b, pick)
+    sub = take(b, pick)
     # (a handle of the same size: which path the large classes take is a property of the handle -- its max_batch --
     #  never of the size of a call, include/qmpc.h qmpc_set_split)
     m2 = mpc_factory(sub, max_batch=B)
@@ -1357,7 +1210,7 @@ def test_class3_more_than_64_working_constraints(mpc_factory):
     b = W.make_standing(1024, 16)
     m = mpc_factory(b)
     m.set_min_stance(64)
-    res, idx, worst, nact = _solver_parity_on_own_qp(m, b, lambda r: np.argsort(r["iters"])[-3:])
+    res, idx, worst, nact = solver_parity_on_own_qp(m, b, lambda r: np.argsort(r["iters"])[-3:])
     print("three hardest robots: iters", res["iters"][idx].tolist(), "rows at a bound", nact, "worst err", worst,
           "fallback", int(((res["status"] & 16) != 0).sum()))
     assert max(nact) > 64
@@ -1396,7 +1249,7 @@ def test_fused_command_solve_is_bit_identical_to_the_three_calls(B, h, omni, sta
     large-problem producer and its seven-block engine)."""
     import torch
     cmd = W.make_commands(B, horizon=h, seed=300 + B, omni_mode=omni, stand_fraction=stand, calm=calm)
-    m = mpc_factory(_pack_setup(cmd))
+    m = mpc_factory(pack_setup(cmd))
     m.set_split(split)
     # three calls
     d1 = m.upload_command(cmd)
@@ -1891,7 +1744,7 @@ def test_sparse_contact_tables_at_long_horizons_vs_oracle(h, duty, mpc_factory):
     assert over15.size <= (1 if (h, duty) == (16, 0.30) else 0), (over15, err[over15], bd[over15])
     assert (err < np.maximum(1e-4, 2.0 * raw)).all()
     # assembly parity: the dumped H_red, g_red against the fp64 Kronecker model fed the kernel's own float transcendentals
-    wh, wg = _dump_model_compare(mpc_factory(b), b, range(0, B, 4))
+    wh, wg = dump_model_compare(mpc_factory(b), b, range(0, B, 4))
     print(f"   H vs fp64 model {wh:.2e}, g {wg:.2e}")
     assert wh < 1e-10 and wg < 1e-10
     # solver parity on the GPU's own assembled QP (the padding must be the exact identity: qpOASES sees only the n_r x n_r block)

@@ -12,7 +12,7 @@ Checks.
   (a) every robot's grf, status and iters are byte-identical solved in the full batch, alone in a batch of one, and in the batch
       reversed (a result never depends on the batch around the robot); the first and the last three as batches of three;
   (b) the forces agree with the oracle pipeline, per robot, within max(1e-4, 1.5 x the reference's float-order spread)
-      (test_gpu_parity.bound_for, the bound the parity suite uses for these families);
+      (solve_gpu.bound_for, the bound the parity suite uses for these families);
   (c) the order hint: the same inputs twice with set_order_hint(1) give the bytes of the run with the hint off;
   (d) qmpc_solve_commands (which shares the prologue) against qmpc_pack -> qmpc_solve -> qmpc_forces_to_body, byte-identical.
 """
@@ -21,7 +21,7 @@ import pytest
 
 from oracle import oracle as O
 from quadruped_ctrl_amd import workloads as W
-from test_gpu_parity import _pack_setup, _take, bound_for, rel_f0, report
+from solve_gpu import bound_for, pack_setup, rel_f0, report, take
 
 pytestmark = pytest.mark.gpu
 HORIZONS = (1, 10, 15, 16)
@@ -82,7 +82,7 @@ def _per_robot(b):
 
 def sub_batch(b, idx):
     """Robots idx of the batch; a shared row stays the shared row (stride 0)."""
-    out = _take(b, np.asarray(idx))
+    out = take(b, np.asarray(idx))
     for k, n in (("weights", 12), ("alpha", 1), ("x_drag", 1)):
         if b[k].size == n:
             out[k] = b[k]
@@ -131,7 +131,7 @@ def test_commands_share_the_prologue(mpc_factory):
     import torch
     B = 65
     cmd = W.make_commands(B, horizon=10, seed=77, omni_mode=0, stand_fraction=0.0, calm=True)
-    m = mpc_factory(_pack_setup(cmd))
+    m = mpc_factory(pack_setup(cmd))
     d1 = m.upload_command(cmd)
     rec = m.alloc_record(B)
     o1 = m.alloc_outputs(B, full=True)

@@ -8,7 +8,7 @@ run inside the driver's suite (~1900 robots, about a minute o
 (b) END-TO-END parity against the ORACLE PIPELINE (float restatement of SolverMPC.cpp:296-525 + the reference's
     qpOASES at its own nWSR = 100) for every robot the reference solves under its cap: first-step GRF within
     max(1e-4, 1.5 x spread_i), spread_i = the pairwise spread of the reference's six float evaluation orders on that robot
-    (tests/test_gpu_parity.py::bound_for), at every horizon; the spread is evaluated only for robots over the flat 1e-4.
+    (tests/solve_gpu.py: bound_for), at every horizon; the spread is evaluated only for robots over the flat 1e-4.
     Printed for every family: frac_over_1e-4.
 """
 import time
@@ -19,7 +19,7 @@ import pytest
 from oracle import kron_model as K
 from oracle import oracle as O
 from quadruped_ctrl_amd import workloads as W
-from test_gpu_parity import bound_for, rel_f0, report
+from solve_gpu import bound_for, rel_f0, report
 
 pytestmark = pytest.mark.gpu
 

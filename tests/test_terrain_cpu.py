@@ -17,6 +17,7 @@ import plant_model as PM
 import plant_model_terrain as PT
 import plant_model_varied as PV
 import terrain_cases as TC
+from c_headers import declared
 from plant_cases import none as _none
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,16 +25,12 @@ f32 = np.float32
 MODEL_KEYS = ("p", "v", "q", "w", "foot", "grf", "stance", "state", "motor")
 
 
-def _decl(name):
-    return set(re.findall(r"^int (qmpc_\w+)\(", open(os.path.join(ROOT, "include", name)).read(), re.M))
-
-
 def test_terrain_symbols_exported_and_abi_version_kept():
     from quadruped_ctrl_amd import binding
     lib = binding.load_library()
     hdr = open(os.path.join(ROOT, "include", "qmpc_terrain.h")).read()
     want = {"qmpc_plant_set_terrain", "qmpc_terrain_view_get"}
-    assert _decl("qmpc_terrain.h") == want == set(binding.TERRAIN_EXPORTS)
+    assert declared("qmpc_terrain.h") == want == set(binding.TERRAIN_EXPORTS)
     for name in want:
         assert hasattr(lib, name), name
     assert lib.qmpc_abi_version() == binding.ABI_VERSION == 23
@@ -43,11 +40,11 @@ def test_terrain_symbols_exported_and_abi_version_kept():
     assert re.search(r"QMPC_TERRAIN_CLAMP_SWING = 1, QMPC_TERRAIN_REBASE_Z = 2", hdr)
     assert (binding.TERRAIN_CLAMP_SWING, binding.TERRAIN_REBASE_Z) == (PT.CLAMP_SWING, PT.REBASE_Z) == (1, 2)
     # the two older headers still declare exactly what they declared
-    assert _decl("qmpc_plant.h") == {"qmpc_plant_init", "qmpc_plant_reset", "qmpc_plant_step", "qmpc_plant_view_get"} \
+    assert declared("qmpc_plant.h") == {"qmpc_plant_init", "qmpc_plant_reset", "qmpc_plant_step", "qmpc_plant_view_get"} \
         == set(binding.PLANT_EXPORTS)
-    assert _decl("qmpc_plant_vary.h") == {"qmpc_plant_set_params", "qmpc_plant_stats_enable", "qmpc_plant_stats_reset",
+    assert declared("qmpc_plant_vary.h") == {"qmpc_plant_set_params", "qmpc_plant_stats_enable", "qmpc_plant_stats_reset",
                                           "qmpc_plant_stats_get"} == set(binding.PLANT_VARY_EXPORTS)
-    assert not want & (_decl("qmpc_plant.h") | _decl("qmpc_plant_vary.h"))
+    assert not want & (declared("qmpc_plant.h") | declared("qmpc_plant_vary.h"))
 
 
 @pytest.mark.parametrize("substeps", [1, 4])
