@@ -222,6 +222,22 @@ class FleetInfo(C.Structure):
     _fields_ = [(n, C.c_int if n == "reason" else C.c_longlong) for n in FLEET_INFO_FIELDS]
 
 
+# qmpc_loop_opts' and qmpc_loop_info's members (include/qmpc_loop.h) in declaration order; the reason bits are the fleet run's
+LOOP_OPTS_FIELDS = ("actuators", "episodes_every", "actuator_stats")
+LOOP_INFO_FIELDS = ("ticks", "fused_ticks", "fused_launches", "fallback_ticks", "reason")
+LOOP_REASONS = dict(terrain=1, contact=2, field=4)
+
+
+class LoopOpts(C.Structure):
+    """qmpc_loop_opts (include/qmpc_loop.h)."""
+    _fields_ = [(n, C.c_int) for n in LOOP_OPTS_FIELDS]
+
+
+class LoopInfo(C.Structure):
+    """qmpc_loop_info (include/qmpc_loop.h)."""
+    _fields_ = [(n, C.c_int if n == "reason" else C.c_longlong) for n in LOOP_INFO_FIELDS]
+
+
 class LegCommand(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in LEG_F32] + [("kp_joint", C.c_float), ("kd_joint", C.c_float)]
 
@@ -387,6 +403,13 @@ FLEET_SIGNATURES = {
     "qmpc_fleet_run": [_P, _I, _I, _P, _P, _P, _P],
     "qmpc_fleet_run_info": [_P, C.POINTER(FleetInfo)],
 }
+# the fleet's long-running loop -- actuators and episode resets inside the fused launch (include/qmpc_loop.h), same library
+# and ABI version
+LOOP_SIGNATURES = {
+    "qmpc_loop_run": [_P, _I, _I, C.POINTER(LoopOpts), _P, _P, _P, _P],
+    "qmpc_loop_run_info": [_P, C.POINTER(LoopInfo)],
+}
+LOOP_ENTRY_POINTS = list(LOOP_SIGNATURES)
 EXPORTS = list(SIGNATURES)
 FLEET_EXPORTS = list(FLEET_SIGNATURES)
 CTRL_EXPORTS = list(CTRL_SIGNATURES)
@@ -434,7 +457,7 @@ def load_library():
         lib = C.CDLL(LIB_PATH)
         for name, sig in {**SIGNATURES, **CTRL_SIGNATURES, **PLANT_SIGNATURES, **PLANT_VARY_SIGNATURES, **TERRAIN_SIGNATURES,
                           **CONTACT_SIGNATURES, **FIELD_SIGNATURES, **SENSE_SIGNATURES, **EPISODE_SIGNATURES,
-                          **EPISODE_SENSE_SIGNATURES, **ACT_SIGNATURES, **FLEET_SIGNATURES}.items():
+                          **EPISODE_SENSE_SIGNATURES, **ACT_SIGNATURES, **FLEET_SIGNATURES, **LOOP_SIGNATURES}.items():
             f = getattr(lib, name)
             f.argtypes, f.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
         _lib = lib
@@ -986,6 +1009,14 @@ class BatchedController:
         info = FleetInfo()
         self._call("qmpc_fleet_run_info", C.byref(info))
         return {n: int(getattr(info, n)) for n in FLEET_INFO_FIELDS}
+
+    def loop_info(self):
+        """qmpc_loop_run_info (include/qmpc_loop.h) as a dict: how rollout_loop()'s ticks were served since init() -- ticks,
+        fused_ticks, fused_launches, fallback_ticks -- and the last call's reason: 0 when it ran fused, else the sum of the
+        LOOP_REASONS bits that made it fall back to the per-tick launches.  Host-side counts: no synchronisation."""
+        info = LoopInfo()
+        self._call("qmpc_loop_run_info", C.byref(info))
+        return {n: int(getattr(info, n)) for n in LOOP_INFO_FIELDS}
 
 
 class _DeviceArray:
@@ -1631,3 +1662,34 @@ def rollout_sensed_episodes(ctrl, plant, sensors, sensed, ticks, graph=False, ac
 
     g = _run_ticks(ctrl, "rollout_sensed_episodes", ticks, graph, tick)
     return dict(effort=plant.effort, state=plant.state, motor=plant.motor, imu=sensors.imu, graph=g)
+
+
+def rollout_loop(ctrl, plant, ticks, graph=False, actuators=None, episodes=None, every=1, actuator_stats=False):
+    """rollout_episodes() through ONE qmpc_loop_run call (include/qmpc_loop.h): `ticks` closed-loop ticks
+    ctrl.tick_state -> [actuators.apply] -> plant.step, after every `every`-th tick of the call [episodes.step(every) ->
+    actuators.reset(the manager's mask, stats=actuator_stats)], with everything between two MPC solves in one launch and
+    the same bits in every array; ctrl.loop_info() tells whether the fused kernel served them or the call fell back to the
+    per-tick launches (terrain, ground-decided contact or a height field bound).  actuators: a BatchedActuators of the
+    plant or None; episodes: a BatchedEpisodes of the plant, set(), or None (`every` is then ignored); with neither the
+    call is rollout(fused=True).  `ticks` must be a multiple of `every`.  graph=True as in rollout(): the call is captured
+    and replayed once, the graph returned for further replays; in lockstep a captured block holds a multiple of 13 ticks.
+    -> dict(effort, state, motor, graph): the plant's own tensors, as the last tick left them."""
+    if plant.batch is None:
+        raise QmpcError("qmpc_loop_run before init()")
+    every = int(every) if episodes is not None else 0
+    if episodes is not None and (every < 1 or int(ticks) % every != 0):
+        raise QmpcError(f"rollout_loop: ticks ({ticks}) must be a multiple of every ({every}) >= 1")
+    for who, stage in (("actuators", actuators), ("episodes", episodes)):
+        if stage is not None and stage.plant is not plant:
+            raise QmpcError(f"rollout_loop: the {who} of another plant")
+    opts = LoopOpts(1 if actuators is not None else 0, every, 1 if actuator_stats else 0)
+
+    def block():
+        chk = ctrl._chk
+        ctrl._call("qmpc_loop_run", plant.batch, int(ticks), C.byref(opts),
+                   chk(plant.effort, (plant.batch, 12), ctrl.torch.float64, "effort"),
+                   chk(plant.state, (plant.batch, 16), ctrl.torch.float64, "state"),
+                   chk(plant.motor, (plant.batch, 24), ctrl.torch.float64, "motor"), ctrl._s(None))
+
+    g = _run_ticks(ctrl, "rollout_loop", ticks, graph, None, block)
+    return dict(effort=plant.effort, state=plant.state, motor=plant.motor, graph=g)

@@ -27,6 +27,22 @@ struct QmpcActDev {
 #undef QMPC_ACT_MEMBER
 };
 
+#if defined(__HIPCC__)
+// qmpc_act_reset of robot b: the ring fills again; with stats the accumulators start at zero.  One text behind the reset
+// kernel of qmpc_act.hip and the reset stage of qmpc_loop.hip.
+__device__ __forceinline__ void qmpc_act_reset_robot(const QmpcActDev& S, const int b, const int stats) {
+  S.age[b] = 0;
+  if (!stats) return;
+  S.n[b] = 0;
+  S.n_vsat[b] = 0;
+  S.n_tsat[b] = 0;
+  S.tau_peak[b] = 0.0;
+  S.e_heat[b] = 0.0;
+  S.e_mech[b] = 0.0;
+  S.e_pos[b] = 0.0;
+}
+#endif
+
 // by value; the six parameter pointers are the caller's arrays as bound (null: the config's value / absent / 0)
 struct QmpcActArgs {
   QmpcActDev d;

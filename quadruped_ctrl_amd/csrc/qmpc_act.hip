@@ -77,15 +77,7 @@ __global__ __launch_bounds__(256) void qmpc_act_reset_kernel(const QmpcActDev S,
   if (b >= batch) return;
   const bool all = !mask_a && !mask_b;
   if (!all && !((mask_a && mask_a[b]) || (mask_b && mask_b[b]))) return;
-  S.age[b] = 0;
-  if (!stats) return;
-  S.n[b] = 0;
-  S.n_vsat[b] = 0;
-  S.n_tsat[b] = 0;
-  S.tau_peak[b] = 0.0;
-  S.e_heat[b] = 0.0;
-  S.e_mech[b] = 0.0;
-  S.e_pos[b] = 0.0;
+  qmpc_act_reset_robot(S, b, stats);
 }
 
 }  // namespace

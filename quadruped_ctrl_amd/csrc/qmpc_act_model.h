@@ -77,6 +77,21 @@ QMPC_ACT_HD void qmpc_act_sums_add(QmpcActSums& S, double tau, double heat, doub
   S.mech = S.mech + power;
   S.pos = S.pos + (power > 0.0 ? power : 0.0);
 }
+// The same subtotals where a lane holds THREE joints of its robot (the loop kernel of qmpc_loop.hip: lane = leg, four lanes
+// a robot): every lane of the quad takes the twelve terms in joint order, term k from lane k / 3, component k % 3.
+// shfl(own value, source lane, slot) returns the source lane's value of that slot (3 * component + 0 / 1 / 2 for tau,
+// heat, power): a width-4 shuffle in the kernel, a table lookup in the CPU program (tests/loop_dump.cpp), which compares
+// the result with the sixteen-lane order above bit for bit.
+template <class Shfl>
+QMPC_ACT_HD void qmpc_act_sums_quad(QmpcActSums& S, const QmpcActJoint* J, Shfl shfl) {
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#pragma unroll
+#endif
+  for (int k = 0; k < 12; ++k) {
+    const int c = k % 3, src = k / 3;
+    qmpc_act_sums_add(S, shfl(J[c].tau, src, 3 * c), shfl(J[c].heat, src, 3 * c + 1), shfl(J[c].power, src, 3 * c + 2));
+  }
+}
 // an energy after the period: e + dt * subtotal
 QMPC_ACT_HD double qmpc_act_energy(double e, double dt, double subtotal) {
 #pragma clang fp contract(off)

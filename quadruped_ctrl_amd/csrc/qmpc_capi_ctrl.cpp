@@ -1,11 +1,14 @@
 // qmpc_capi_ctrl.cpp -- host side of include/qmpc_ctrl.h (the batched locomotion controller; the kernels are in
-// qmpc_glue.hip) and of include/qmpc_fleet.h (the closed loop of controller and plant; the kernel is in qmpc_span.hip).
+// qmpc_glue.hip), of include/qmpc_fleet.h (the closed loop of controller and plant; the kernel is in qmpc_span.hip) and of
+// include/qmpc_loop.h (that loop with the actuators and the episode manager inside the launch; qmpc_loop.hip).
 #include <cstring>
 
 #include "../../include/qmpc_debug.h"  // qmpc_debug_ctrl_read
 #include "../../include/qmpc_plant.h"  // qmpc_plant_step: the fleet run's fallback is the per-tick calls themselves
+#include "../../include/qmpc_act.h"    // ... and the loop run's: qmpc_act, qmpc_act_reset
 #include "qmpc_host.h"
 #include "qmpc_span.h"  // the fleet run's plan (host-only) and the span kernel's launcher
+#include "qmpc_loop.h"  // the loop kernel's argument block and launcher
 using namespace qmpc_host;
 
 size_t qmpc_host::carve(QmpcCtrlDev& d, char* base, int M) {
@@ -147,6 +150,7 @@ int qmpc_ctrl_init(qmpc_handle c, int batch, double freq, const double pid[4], v
   k->robot_mode = 0;
   k->started = false;
   k->fleet = qmpc_fleet_info{};
+  k->loop = qmpc_loop_info{};
   return QMPC_OK;
 }
 
@@ -338,6 +342,118 @@ int qmpc_fleet_run_info(qmpc_handle c, qmpc_fleet_info* out) {
   if (!c || !out) return QMPC_ERR_ARG;
   if (!ctrl_ready(c)) return QMPC_ERR_STATE;
   *out = c->ctrl->fleet;
+  return QMPC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
+// Loop run (include/qmpc_loop.h): the fleet run's loop with the actuator stage and the episode step inside the launch.
+// The plan is the span's, unchanged; the kernel is qmpc_loop.hip's, or the span's own where no option is set.
+extern "C" {
+
+int qmpc_loop_run(qmpc_handle c, int batch, int ticks, const qmpc_loop_opts* o, double* effort, double* state,
+                  double* motor, void* stream_) {
+  if (const int rc = plant_check(c, batch)) return rc;
+  if (!o || ticks < 1 || !effort || !state || !motor) return QMPC_ERR_ARG;
+  const bool act = o->actuators != 0;
+  const int every = o->episodes_every;
+  if (every < 0 || (every && ticks % every != 0)) return QMPC_ERR_ARG;
+  qmpc_ctx::Ctrl* k = c->ctrl.get();
+  qmpc_ctx::Plant* pl = c->plant.get();
+  if (act) {
+    if (!ready(c->act)) return QMPC_ERR_STATE;
+    if (batch != c->act->batch) return QMPC_ERR_ARG;
+    // the actuator stage reads the rates in the plant's motor rows while it writes the effort (qmpc_act's own check)
+    const double* m = pl->d.motor;
+    if (effort < m + (size_t)batch * 24 && m < effort + (size_t)batch * 12) return QMPC_ERR_ARG;
+  }
+  if (every) {
+    if (!ready(c->episode) || !c->episode->is_set) return QMPC_ERR_STATE;
+    if (batch != c->episode->batch) return QMPC_ERR_ARG;
+    // the plant's reset writes its own read-out rows only: the loop would carry on from stale caller rows
+    if (state != pl->d.state || motor != pl->d.motor) return QMPC_ERR_ARG;
+  }
+  const int reason = (pl->terrain.rows ? QMPC_LOOP_TERRAIN : 0) | (pl->contact.flags ? QMPC_LOOP_CONTACT : 0) |
+                     (pl->field.z ? QMPC_LOOP_FIELD : 0);
+  if (reason) {
+    // what the loop kernel does not cover: the per-tick calls themselves, so the launches are theirs exactly
+    for (int i = 0; i < ticks; ++i) {
+      if (const int rc = qmpc_ctrl_tick_state(c, batch, state, motor, effort, stream_)) return rc;
+      k->loop.reason = reason;  // (the call has enqueued something: it is the last call now)
+      if (act)
+        if (const int rc = qmpc_act(c, batch, effort, effort, stream_)) return rc;
+      if (const int rc = qmpc_plant_step(c, batch, effort, state, motor, stream_)) return rc;
+      ++k->loop.ticks;
+      ++k->loop.fallback_ticks;
+      if (every && (i + 1) % every == 0) {
+        if (const int rc = qmpc_episode_step(c, batch, every, stream_)) return rc;
+        if (act)
+          if (const int rc = qmpc_act_reset(c, batch, c->episode->d.mask, nullptr, o->actuator_stats, stream_)) return rc;
+      }
+    }
+    return QMPC_OK;
+  }
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  k->started = true;
+  k->loop.reason = 0;
+  const bool per_robot = k->schedule == QMPC_CTRL_PER_ROBOT;
+  const QmpcPlantStepArgs P = plant_step_args(c, batch, effort, state, motor);
+  QmpcLoopArgs A{};
+  A.X.C = k->d;
+  A.X.g = QmpcLegGeom{c->leg_geom[0], c->leg_geom[1], c->leg_geom[2], c->leg_geom[3]};
+  A.X.S = P.S;
+  A.X.K = P.K;
+  A.X.effort = effort;
+  A.X.state = state;
+  A.X.motor = motor;
+  A.X.n = P.n;
+  A.X.V = P.V;
+  A.X.build_list = per_robot ? 1 : 0;
+  if (act) {
+    A.A = c->act->a;
+    A.A.motor = pl->d.motor;
+    A.A.dt = 1.0 / k->freq;
+    A.act = 1;
+    A.act_stats = o->actuator_stats;
+  }
+  if (every) {
+    const qmpc_ctx::Episode* e = c->episode.get();
+    A.decide = e->rule.causes ? 1 : 0;  // (causes 0: qmpc_episode_step enqueues nothing)
+    A.every = A.decide || act ? every : 0;
+    A.E = e->d;
+    A.In = episode_inputs(c);
+    A.R = e->rule;
+    A.Bd = e->bind;
+  }
+  const bool plain = !A.act && !A.every;  // nothing of this header's in the launch: the span kernel itself
+  int cur = 0;                            // the call's index of the launch's first tick
+  for (const SpanLaunch& l : plan_spans(k->ticks, ticks, per_robot)) {
+    // (a kernel, not a memset node: see fill_ints)
+    if (l.reset_due) HIP_TRY(c, fill_ints(k->d.due_count, 1, 0, q.stream));
+    if (plain)
+      HIP_TRY(c, qmpc_launch_span(&A.X, k->robot_mode, pl->bound, pl->stats_on, l.first_at_c, l.ticks, l.last_after_l, q.stream));
+    else
+      HIP_TRY(c, qmpc_launch_loop(&A, k->robot_mode, pl->bound, pl->stats_on, l.first_at_c, l.ticks, l.last_after_l, cur,
+                                  (int)(k->ticks % 13), q.stream));
+    // T follows the locomotion stages as they are enqueued, in front of the solve that can still fail (ctrl_after_prework)
+    k->ticks += l.locos;
+    k->loop.ticks += l.locos;
+    k->loop.fused_ticks += l.locos;
+    ++k->loop.fused_launches;
+    if (l.solve) {
+      if (const int rc = ctrl_solve_enqueue(c, batch, q.stream)) return rc;
+      cur += l.ticks - 1;
+    }
+  }
+  return QMPC_OK;
+}
+
+int qmpc_loop_run_info(qmpc_handle c, qmpc_loop_info* out) {
+  if (!c || !out) return QMPC_ERR_ARG;
+  if (!ctrl_ready(c)) return QMPC_ERR_STATE;
+  *out = c->ctrl->loop;
   return QMPC_OK;
 }
 

@@ -238,18 +238,18 @@ int qmpc_act_view_get(qmpc_handle c, qmpc_act_view* v) {
 
 // ---------------------------------------------------------------------------------------------------
 // Episode manager (include/qmpc_episode.h).  The kernels are in qmpc_episode.hip.
-namespace {
-
-int episode_check(qmpc_ctx* c, int batch) { return stage_check(c, batch, &qmpc_ctx::episode); }
-
 // what a decision kernel reads of the handle's other state
-QmpcEpisodeIn episode_inputs(const qmpc_ctx* c) {
+QmpcEpisodeIn qmpc_host::episode_inputs(const qmpc_ctx* c) {
   const qmpc_ctx::Plant* pl = c->plant.get();
   // the plant writes ground[b] on terrain, on a field and with contact on (there 0 without rows); the flat plant never does
   const bool ground = pl->terrain.rows || pl->field.z || pl->contact.flags;
   return QmpcEpisodeIn{pl->d.p, pl->d.q, c->ctrl->d.safe, ground ? pl->terrain.ground : nullptr,
                        (uint32_t)(c->episode->seed & 0xFFFFFFFFu), (uint32_t)(c->episode->seed >> 32)};
 }
+
+namespace {
+
+int episode_check(qmpc_ctx* c, int batch) { return stage_check(c, batch, &qmpc_ctx::episode); }
 
 const int kEpisodeCauses = QMPC_EP_UNSAFE | QMPC_EP_NONFINITE | QMPC_EP_TILT | QMPC_EP_HEIGHT | QMPC_EP_RANGE | QMPC_EP_TIMEOUT;
 

@@ -243,6 +243,17 @@ __device__ __forceinline__ void qmpc_ctrl_due_append(const QmpcCtrlDev& S, const
   }
 }
 
+// qmpc_ctrl_set_gait / qmpc_ctrl_set_vel for robot b (null: that command is left alone).  One text behind the set kernel of
+// qmpc_glue.hip and the reset stage of qmpc_loop.hip.
+__device__ __forceinline__ void qmpc_ctrl_set_robot(const QmpcCtrlDev& S, const int32_t* gait, const double* vel, const int b) {
+  if (gait) S.gait_num[b] = gait[b];
+  if (vel)  // SetRobotVel (GaitCtrller.cpp:75-93): abs(double) there is the double overload (<math.h>)
+    for (int k = 0; k < 3; ++k) {
+      const double v = vel[(size_t)b * 3 + k];
+      S.vel_cmd[(size_t)b * 3 + k] = (float)(fabs(v) < 0.03 ? 0.0 : v * 1.0);
+    }
+}
+
 // Stage C for lane t = robot * 4 + leg: f_ff (on MPC ticks), the gains of :378-382, LegController::updateCommand and the
 // latch
 __device__ __forceinline__ void qmpc_ctrl_legcmd_body(const QmpcCtrlDev& S, double* effort, const int t) {

@@ -441,12 +441,7 @@ __global__ __launch_bounds__(256) void qmpc_ctrl_set_kernel(const QmpcCtrlDev S,
                                                             const double* __restrict__ vel, const int batch) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= batch) return;
-  if (gait) S.gait_num[b] = gait[b];
-  if (vel)  // SetRobotVel (GaitCtrller.cpp:75-93): abs(double) there is the double overload (<math.h>)
-    for (int k = 0; k < 3; ++k) {
-      const double v = vel[(size_t)b * 3 + k];
-      S.vel_cmd[(size_t)b * 3 + k] = (float)(fabs(v) < 0.03 ? 0.0 : v * 1.0);
-    }
+  qmpc_ctrl_set_robot(S, gait, vel, b);
 }
 
 }  // namespace

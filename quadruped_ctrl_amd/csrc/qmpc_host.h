@@ -1,6 +1,6 @@
 // qmpc_host.h -- what the host-side translation units of the C ABI share (host only, not installed):
 //   qmpc_capi.cpp         the handle and the solve (qmpc.h, qmpc_expert.h, qmpc_debug.h)
-//   qmpc_capi_ctrl.cpp    the batched controller and the fleet run (qmpc_ctrl.h, qmpc_fleet.h)
+//   qmpc_capi_ctrl.cpp    the batched controller, the fleet run and the loop run (qmpc_ctrl.h, qmpc_fleet.h, qmpc_loop.h)
 //   qmpc_capi_plant.cpp   the plant and its extensions (qmpc_plant.h, qmpc_plant_vary.h, qmpc_terrain.h, qmpc_contact.h,
 //                         qmpc_field.h)
 //   qmpc_capi_stages.cpp  sensors, actuators, episodes (qmpc_sense.h, qmpc_act.h, qmpc_episode.h, qmpc_episode_sense.h)
@@ -18,6 +18,7 @@
 #include "../../include/qmpc.h"
 #include "../../include/qmpc_ctrl.h"
 #include "../../include/qmpc_fleet.h"
+#include "../../include/qmpc_loop.h"
 #include "qmpc_device.h"
 #include "qmpc_plan.h"  // the solve's launch plan (host-only)
 // the device-side argument blocks the handle keeps.  Each launcher is declared once, in the header its defining file
@@ -150,6 +151,7 @@ struct __attribute__((visibility("hidden"))) qmpc_ctx {
     bool started = false;               // a tick or a reset has been enqueued since qmpc_ctrl_init: the schedule is fixed
     double freq = 0;                    // qmpc_ctrl_init's: the plant's dt is 1 / freq in double
     qmpc_fleet_info fleet{};            // how qmpc_fleet_run's ticks were served since qmpc_ctrl_init (qmpc_fleet.h)
+    qmpc_loop_info loop{};              // ... and qmpc_loop_run's (qmpc_loop.h)
   };
   std::unique_ptr<Ctrl> ctrl;
   // reduced-order plant (qmpc_plant.h): device state for max_batch robots, made by qmpc_plant_init
@@ -350,6 +352,10 @@ int ctrl_reset_counter0(qmpc_ctx::Ctrl* k);                                     
 int ctrl_reset_enqueue(qmpc_ctx* c, int batch, const uint8_t* mask_dev, hipStream_t stream);  // ...
 int plant_reset_enqueue(qmpc_ctx* c, int batch, const uint8_t* mask_dev, const double* init_xyyaw,
                         hipStream_t stream);                                                // qmpc_capi_plant.cpp
+
+// qmpc_capi_stages.cpp.  What an episode decision reads of the handle's other state (the manager is initialised): the
+// decision kernels' and the loop kernel's (qmpc_capi_ctrl.cpp: qmpc_loop_run)
+QmpcEpisodeIn episode_inputs(const qmpc_ctx* c);
 
 }  // namespace qmpc_host
 

@@ -29,24 +29,12 @@ __global__ __launch_bounds__(256) void qmpc_plant_init_kernel(const QmpcPlantDev
 #pragma clang fp contract(off)
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= n) return;
-  const int b = t >> 2, leg = t & 3;
+  const int b = t >> 2;
   if (mask && !mask[b]) return;
   const double x0 = xyyaw ? xyyaw[(size_t)b * 3] : 0.0, y0 = xyyaw ? xyyaw[(size_t)b * 3 + 1] : 0.0;
   const double yaw = xyyaw ? xyyaw[(size_t)b * 3 + 2] : 0.0;
-  const double p[3] = {x0, y0, QMPC_PLANT_HEIGHT}, v[3] = {0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
   const double q[4] = {cos(yaw / 2), 0.0, 0.0, sin(yaw / 2)};
-  const double side = (leg & 1) ? 1.0 : -1.0;
-  double hip[3], R[9], fw[3];
-  plant_hip(leg, hip);
-  plant_rot(q, R);
-  const double fb[3] = {hip[0], hip[1] + side * QMPC_PLANT_SIDE_OFFSET, -QMPC_PLANT_HEIGHT};
-  plant_mul(R, fb, fw);
-  double c[3] = {p[0] + fw[0], p[1] + fw[1], 0.0};
-  for (int k = 0; k < 3; ++k) S.grf[(size_t)t * 3 + k] = 0.0;
-  S.stance[t] = 1;
-  const PlantGround flat{};
-  plant_readout<false>(S, K, t, true, p, v, q, w, c, true, v /* vdot = 0 */, nullptr, nullptr, nullptr, nullptr,
-                       flat);
+  plant_init_lane(S, K, x0, y0, q, t);
 }
 
 // One control period on flat ground: qmpc_plant_step_body.h with TERRAIN = false.  <false, false> reads nothing of V
@@ -72,15 +60,7 @@ __global__ __launch_bounds__(256) void qmpc_plant_stats_reset_kernel(const QmpcP
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= batch) return;
   if (mask && !mask[b]) return;
-  double* a = V.acc + b;
-  const size_t M = (size_t)V.acc_stride;
-  V.n[b] = 0;
-  a[QMPC_PLANT_STAT_Z_MIN * M] = __builtin_inf();
-  a[QMPC_PLANT_STAT_Z_MAX * M] = -__builtin_inf();
-  a[QMPC_PLANT_STAT_ROLL_MAX * M] = 0.0;
-  a[QMPC_PLANT_STAT_PITCH_MAX * M] = 0.0;
-  a[QMPC_PLANT_STAT_VX_SUM * M] = 0.0;
-  a[QMPC_PLANT_STAT_VY_SUM * M] = 0.0;
+  plant_stats_reset_robot(V, b);
 }
 
 }  // namespace

@@ -355,6 +355,42 @@ __device__ __forceinline__ void plant_readout(const QmpcPlantDev& S, const QmpcP
   for (int k = 0; k < 4; ++k) S.q[(size_t)b * 4 + k] = q[k];
 }
 
+// qmpc_plant_init / qmpc_plant_reset of lane t = robot * 4 + leg on flat ground: the robot stands at (x0, y0) with the
+// attitude q (a yaw: the caller builds it from its xyyaw row) at QMPC_PLANT_HEIGHT, its feet under the hips, every foot in
+// stance, and the read-out goes to the plant's own rows.  One text behind the init kernel of qmpc_plant.hip and the reset
+// stage of qmpc_loop.hip; the caller decides which lanes run it.
+__device__ __forceinline__ void plant_init_lane(const QmpcPlantDev& S, const QmpcPlantConst& K, const double x0,
+                                                const double y0, const double* q, const int t) {
+#pragma clang fp contract(off)
+  const int leg = t & 3;
+  const double p[3] = {x0, y0, QMPC_PLANT_HEIGHT}, v[3] = {0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
+  const double side = (leg & 1) ? 1.0 : -1.0;
+  double hip[3], R[9], fw[3];
+  plant_hip(leg, hip);
+  plant_rot(q, R);
+  const double fb[3] = {hip[0], hip[1] + side * QMPC_PLANT_SIDE_OFFSET, -QMPC_PLANT_HEIGHT};
+  plant_mul(R, fb, fw);
+  double c[3] = {p[0] + fw[0], p[1] + fw[1], 0.0};
+  for (int k = 0; k < 3; ++k) S.grf[(size_t)t * 3 + k] = 0.0;
+  S.stance[t] = 1;
+  const PlantGround flat{};
+  plant_readout<false>(S, K, t, true, p, v, q, w, c, true, v /* vdot = 0 */, nullptr, nullptr, nullptr, nullptr,
+                       flat);
+}
+
+// qmpc_plant_stats_reset of robot b: the accumulators as qmpc_plant_stats_enable leaves them
+__device__ __forceinline__ void plant_stats_reset_robot(const QmpcPlantVary& V, const int b) {
+  double* a = V.acc + b;
+  const size_t M = (size_t)V.acc_stride;
+  V.n[b] = 0;
+  a[QMPC_PLANT_STAT_Z_MIN * M] = __builtin_inf();
+  a[QMPC_PLANT_STAT_Z_MAX * M] = -__builtin_inf();
+  a[QMPC_PLANT_STAT_ROLL_MAX * M] = 0.0;
+  a[QMPC_PLANT_STAT_PITCH_MAX * M] = 0.0;
+  a[QMPC_PLANT_STAT_VX_SUM * M] = 0.0;
+  a[QMPC_PLANT_STAT_VY_SUM * M] = 0.0;
+}
+
 // Host side of every launcher here: 256 lanes per block over n = batch * 4 lanes ...
 inline dim3 plant_grid(int n) { return dim3((n + 255) / 256); }
 

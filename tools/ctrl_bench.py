@@ -71,6 +71,10 @@ Without --actuators the stage is never initialised and the loop enqueues what it
 solves in one launch); --graph adds a captured 13-tick block, replayed.  Either one switches to timing in blocks of ticks
 (run_blocks: the per-tick windows cut at the same places; --warmup a multiple of 13), so `--source plant --graph` is the
 per-tick path's figure to hold `--source plant --fused --graph` against.
+With --actuators [--delay D] and / or --episodes [--every K], --fused routes the loop through qmpc_loop_run
+(include/qmpc_loop.h: the actuator stage and the episode step inside the same launch) and --graph alone through
+rollout_episodes() / rollout() with the actuators, in the same block windows; with --every K > 1 only the whole 13-tick
+blocks are timed (K must divide 13: a block ends on a check tick).
 
     python tools/ctrl_bench.py [--batches 1024,4096,16384] [--cycles 8] [--warmup 26] [--schedule lockstep|per_robot]
                                [--stagger] [--robot-mode 0|1] [--source imu|state|plant|sensor] [--vary] [--terrain] [--contact] [--field]
@@ -88,26 +92,38 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def run_blocks(ctrl, plant, B, cycles, warmup, schedule, stagger, robot_mode, fused, graph):
+def run_blocks(ctrl, plant, B, cycles, warmup, schedule, stagger, robot_mode, fused, graph, acts=None, manager=None, every=1):
     """--source plant with --fused and / or --graph: the closed loop timed in BLOCKS of ticks (HIP events around rollout()
     calls), because a fused span has no event between its ticks.  The windows are the per-tick report's, cut at the same
     places: in lockstep, per 13-tick period, the twelve ticks without a solve in one block (us_per_nonmpc_period: block /
     12, tick + step) and the MPC tick in another (us_per_mpc_period: tick + step; the per-tick report's us_per_mpc_tick
     plus its plant step); then whole 13-tick periods in one block each (us_per_13_tick_cycle, robot_ticks_per_s); with
     --graph the same 13-tick block captured once and replayed (us_per_13_tick_cycle_graph, robot_ticks_per_s_graph).
-    With the per-robot schedule every tick solves and only the whole blocks are reported."""
+    With the per-robot schedule every tick solves and only the whole blocks are reported.
+    acts / manager (--actuators / --episodes): the longer loop -- fused through rollout_loop() (qmpc_loop_run), else
+    through rollout_episodes() / rollout(actuators=...), the per-tick launches; the blocks are cut at the same places."""
     import torch
-    from quadruped_ctrl_amd.binding import rollout
+    from quadruped_ctrl_amd.binding import rollout, rollout_episodes, rollout_loop
     if warmup % 13:
         raise SystemExit("--fused / --graph: --warmup must be a multiple of 13 (the blocks are cut at the MPC ticks)")
-    go = lambda n, g=False: rollout(ctrl, plant, n, graph=g, fused=fused)
+    longer = acts is not None or manager is not None
+    if not longer:
+        go = lambda n, g=False: rollout(ctrl, plant, n, graph=g, fused=fused)
+    elif fused:
+        go = lambda n, g=False: rollout_loop(ctrl, plant, n, graph=g, actuators=acts, episodes=manager, every=every)
+    elif manager is not None:
+        go = lambda n, g=False: rollout_episodes(ctrl, plant, manager, n, graph=g, every=every, actuators=acts)
+    else:
+        go = lambda n, g=False: rollout(ctrl, plant, n, graph=g, actuators=acts)
     pair = lambda: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
     med = lambda evs: float(np.median([a.elapsed_time(b) * 1e3 for a, b in evs]))
     go(warmup)
     lockstep = schedule == "lockstep" and not stagger and robot_mode == 0
     res = {"batch": B, "source": "plant", "schedule": schedule, "stagger": bool(stagger), "robot_mode": robot_mode,
            "fused": bool(fused), "cycles_timed": cycles}
-    if lockstep:
+    if longer:
+        res.update({"actuators": acts is not None, "episodes": manager is not None, "every": every})
+    if lockstep and every == 1:
         non, mpc = [], []
         for _ in range(cycles):
             a, b = pair()
@@ -138,9 +154,15 @@ def run_blocks(ctrl, plant, B, cycles, warmup, schedule, stagger, robot_mode, fu
         us13g = med(reps)
         res.update({"us_per_13_tick_cycle_graph": round(us13g, 1),
                     "robot_ticks_per_s_graph": float(f"{13 * B / (us13g * 1e-6):.4g}")})
-    info, v = ctrl.fleet_info(), ctrl.view()
+    info, v = (ctrl.loop_info() if longer else ctrl.fleet_info()), ctrl.view()
     pz = plant.view()["p"][:, 2]
-    res.update({"fleet_info": info, "body_height_min": round(float(pz.min().item()), 4),
+    if manager is not None:
+        ev_ = manager.view()
+        res.update({"episodes_finished": int(ev_["episode"].sum().item()),
+                    "episodes_per_cause": [int(x) for x in ev_["count"].sum(0).tolist()]})
+    if acts is not None:
+        res["act_calls"] = int(acts.stats()["n"].min().item())
+    res.update({"loop_info" if longer else "fleet_info": info, "body_height_min": round(float(pz.min().item()), 4),
                 "body_height_max": round(float(pz.max().item()), 4),
                 "status_error_robots": int((torch.from_numpy(ctrl.read("status")[:, 0]) & 47 != 0).sum()),
                 "all_finite": bool(torch.isfinite(plant.effort).all().item()), "latched": int((v["safe"] == 0).sum())})
@@ -278,7 +300,7 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
             if sensors is not None:
                 sensors.sense()
     if fused or graph:
-        return run_blocks(ctrl, plant, B, cycles, warmup, schedule, stagger, robot_mode, fused, graph)
+        return run_blocks(ctrl, plant, B, cycles, warmup, schedule, stagger, robot_mode, fused, graph, acts, manager, every)
     held_seen = []
 
     hold_flags = sensed.view()["hold"] if sensed is not None else None
@@ -447,8 +469,10 @@ def main():
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if (a.fused or a.graph) and (a.source != "plant" or a.episodes or a.actuators):
-        ap.error("--fused and --graph go with --source plant, without --episodes and --actuators")
+    if (a.fused or a.graph) and a.source != "plant":
+        ap.error("--fused and --graph go with --source plant")
+    if (a.fused or a.graph) and a.episodes and 13 % a.every:
+        ap.error("--fused / --graph with --episodes: --every K must divide 13 (the blocks are 13 ticks)")
     if a.vary and a.source not in ("plant", "sensor"):
         ap.error("--vary needs --source plant or sensor")
     if a.terrain and a.source not in ("plant", "sensor"):
