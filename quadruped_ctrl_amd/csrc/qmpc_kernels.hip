@@ -3411,10 +3411,23 @@ __device__ __forceinline__ bool solve_one(const int rid, const int tid, Smem<RB>
           }
           double t1 = __builtin_inf();
           int l = -1;
-          if (khw > 0 && !(WARM && forced)) {
-            // (the ratio is +inf from slot lane khw on: a class of 32 slots stops at lane 31, a working set that has
-            //  never reached past slot 16 at lane 15; same values compared, same minimum)
-            if constexpr (KS <= 32) t1 = (khw <= 16) ? wave_min_pos_f64<16>(rmin) : wave_min_pos_f64<32>(rmin);
+          // t1 = min ratio has three uses: t = min(t1, t2), the full / partial decision t2 <= t1 and the dropped slot l
+          // (partial steps only).  The reduction and the search for l run only when some slot BLOCKS the full step, i.e.
+          // its ratio is below t2; on a full step no bit of t1 reaches a result.  Same values as with the reduction
+          // on every iteration:
+          //   not blocked: rmin >= t2 on every lane, so the true minimum is >= t2 and the step was t = t2, full; with
+          //     t1 left at +inf it is t = t2, full, and l is not read;
+          //   t2 = +inf (dependent constraint): any finite ratio blocks and the reduction runs as before; with no
+          //     finite ratio t1 = +inf either way and the exit below is INFEASIBLE;
+          //   t2 NaN: !(rmin >= NaN) holds on every lane, the reduction runs as before (hence the negated >=, not
+          //     rmin < t2: non-finite records must leave by the same exit with the same status);
+          //   rmin is never NaN: max(qv, 0) or +inf.
+          // An empty working set (khw == 0) has every ratio at +inf and blocks nothing.
+          const bool blocked = uni(!(rmin >= t2));
+          if (blocked && !(WARM && forced)) {
+            // (the ratio is +inf from slot lane khw on: a class of 32 slots stops at lane 31; same values compared,
+            //  same minimum)
+            if constexpr (KS <= 32) t1 = wave_min_pos_f64<32>(rmin);
             else t1 = wave_min_pos_f64(rmin);
             if (uni(t1 < __builtin_inf())) {
 #pragma unroll
