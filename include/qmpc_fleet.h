@@ -19,8 +19,10 @@
  * The fused kernel covers the state-driven tick in both robot modes and both schedules, on the flat plant with
  * scheduled contact, with or without qmpc_plant_set_params and the statistics, at any `substeps` and any constants of the
  * handle (the kernel takes them at run time).  With terrain rows, contact decided by the ground or a height field
- * bound, the call FALLS BACK: it enqueues the per-tick calls above, exactly, and says so in
- * qmpc_fleet_info.reason.  The answer is the per-tick answer either way.  Sensors, actuators and the episode managers
+ * bound, the call FALLS BACK unless the handle's ground-run switch is on and contact is scheduled: it enqueues the
+ * per-tick calls above, exactly, and says so in qmpc_fleet_info.reason.  qmpc_ground_run.h has the switch, which lets
+ * terrain rows and height fields run fused too, and says what `reason` holds then.  The answer is the per-tick answer
+ * either way.  Sensors, actuators and the episode managers
  * stand between the stages of a tick and keep their own loops (rollout_sensed, ... in the Python binding).
  *
  * The call only enqueues, on `stream`, and allocates nothing: it can be captured into a graph.  As with the per-tick

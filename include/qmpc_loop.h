@@ -28,8 +28,11 @@
  *
  * The fused kernel covers what the plain fused loop covers: the state-driven tick in both robot modes and both
  * schedules, on the flat plant with scheduled contact, with or without per-robot plant parameters and statistics.  With
- * terrain rows, contact decided by the ground or a height field bound the call FALLS BACK: it enqueues the sequence
- * above, exactly, and says so in qmpc_loop_info.reason.  With all three options 0 the call is the plain fused loop.
+ * terrain rows, contact decided by the ground or a height field bound the call FALLS BACK unless the handle's ground-run
+ * switch is on and contact is scheduled: it enqueues the sequence above, exactly, and says so in qmpc_loop_info.reason.
+ * qmpc_ground_run.h has the switch, which lets terrain rows and height fields run fused too -- the reset stage then
+ * stands a robot on its ground -- and says what `reason` holds then.  With all three options 0 the call is the plain
+ * fused loop.
  * Where the episode rule's `causes` are 0, qmpc_episode_step enqueues nothing and the fused call runs no reset stage.
  *
  * The call only enqueues, on `stream`, and allocates nothing: it can be captured into a graph.  The host decides the

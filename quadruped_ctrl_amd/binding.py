@@ -410,6 +410,13 @@ LOOP_SIGNATURES = {
     "qmpc_loop_run_info": [_P, C.POINTER(LoopInfo)],
 }
 LOOP_ENTRY_POINTS = list(LOOP_SIGNATURES)
+# the switch that lets both run calls serve terrain rows and height fields fused (include/qmpc_ground_run.h), same
+# library and ABI version
+GROUND_RUN_SIGNATURES = {
+    "qmpc_ground_run_enable": [_P, _I],
+    "qmpc_ground_run_enabled": [_P, C.POINTER(C.c_int)],
+}
+GROUND_RUN_ENTRY_POINTS = list(GROUND_RUN_SIGNATURES)
 EXPORTS = list(SIGNATURES)
 FLEET_EXPORTS = list(FLEET_SIGNATURES)
 CTRL_EXPORTS = list(CTRL_SIGNATURES)
@@ -457,7 +464,8 @@ def load_library():
         lib = C.CDLL(LIB_PATH)
         for name, sig in {**SIGNATURES, **CTRL_SIGNATURES, **PLANT_SIGNATURES, **PLANT_VARY_SIGNATURES, **TERRAIN_SIGNATURES,
                           **CONTACT_SIGNATURES, **FIELD_SIGNATURES, **SENSE_SIGNATURES, **EPISODE_SIGNATURES,
-                          **EPISODE_SENSE_SIGNATURES, **ACT_SIGNATURES, **FLEET_SIGNATURES, **LOOP_SIGNATURES}.items():
+                          **EPISODE_SENSE_SIGNATURES, **ACT_SIGNATURES, **FLEET_SIGNATURES, **LOOP_SIGNATURES,
+                          **GROUND_RUN_SIGNATURES}.items():
             f = getattr(lib, name)
             f.argtypes, f.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
         _lib = lib
@@ -1017,6 +1025,20 @@ class BatchedController:
         info = LoopInfo()
         self._call("qmpc_loop_run_info", C.byref(info))
         return {n: int(getattr(info, n)) for n in LOOP_INFO_FIELDS}
+
+    def set_ground_run(self, on=True):
+        """qmpc_ground_run_enable (include/qmpc_ground_run.h): with the switch on, rollout(..., fused=True) and
+        rollout_loop() serve a plant on terrain rows and / or a height field (scheduled contact) through the fused launch
+        too, with the per-tick bits; off (the default after init()) they fall back there.  Read by the next call; a
+        captured graph keeps what it captured.  fleet_info() / loop_info() tell how the ticks were served."""
+        self._call("qmpc_ground_run_enable", 1 if on else 0)
+
+    @property
+    def ground_run(self):
+        """qmpc_ground_run_enabled: whether the next run call serves terrain rows and height fields fused."""
+        on = C.c_int(0)
+        self._call("qmpc_ground_run_enabled", C.byref(on))
+        return bool(on.value)
 
 
 class _DeviceArray:

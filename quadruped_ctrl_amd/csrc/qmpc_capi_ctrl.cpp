@@ -1,14 +1,17 @@
 // qmpc_capi_ctrl.cpp -- host side of include/qmpc_ctrl.h (the batched locomotion controller; the kernels are in
 // qmpc_glue.hip), of include/qmpc_fleet.h (the closed loop of controller and plant; the kernel is in qmpc_span.hip) and of
-// include/qmpc_loop.h (that loop with the actuators and the episode manager inside the launch; qmpc_loop.hip).
+// include/qmpc_loop.h (that loop with the actuators and the episode manager inside the launch; qmpc_loop.hip), with the
+// switch of include/qmpc_ground_run.h (both on terrain rows and height fields: qmpc_loop.hip's ground compiles).
 #include <cstring>
 
 #include "../../include/qmpc_debug.h"  // qmpc_debug_ctrl_read
 #include "../../include/qmpc_plant.h"  // qmpc_plant_step: the fleet run's fallback is the per-tick calls themselves
 #include "../../include/qmpc_act.h"    // ... and the loop run's: qmpc_act, qmpc_act_reset
+#include "../../include/qmpc_ground_run.h"  // the switch that lets both run calls serve rows and a field fused
 #include "qmpc_host.h"
-#include "qmpc_span.h"  // the fleet run's plan (host-only) and the span kernel's launcher
-#include "qmpc_loop.h"  // the loop kernel's argument block and launcher
+#include "qmpc_span.h"      // the fleet run's plan (host-only) and the span kernel's launcher
+#include "qmpc_loop.h"      // the loop kernel's argument blocks and launchers
+#include "qmpc_run_pick.h"  // which of them serves a call (host-only)
 using namespace qmpc_host;
 
 size_t qmpc_host::carve(QmpcCtrlDev& d, char* base, int M) {
@@ -151,6 +154,7 @@ int qmpc_ctrl_init(qmpc_handle c, int batch, double freq, const double pid[4], v
   k->started = false;
   k->fleet = qmpc_fleet_info{};
   k->loop = qmpc_loop_info{};
+  k->ground_run = false;
   return QMPC_OK;
 }
 
@@ -282,60 +286,111 @@ int qmpc_ctrl_view_get(qmpc_handle c, qmpc_ctrl_view* v) {
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------
+// The fused launches behind both run calls.  Which kernel serves a call, and what its `reason` says, is qmpc_run_pick.h's
+// pure function of the handle's switch (include/qmpc_ground_run.h), what is bound and the call's options.
+namespace {
+
+static_assert(QMPC_RUN_REASON_TERRAIN == QMPC_FLEET_TERRAIN && QMPC_RUN_REASON_CONTACT == QMPC_FLEET_CONTACT &&
+                  QMPC_RUN_REASON_FIELD == QMPC_FLEET_FIELD && QMPC_RUN_REASON_TERRAIN == QMPC_LOOP_TERRAIN &&
+                  QMPC_RUN_REASON_CONTACT == QMPC_LOOP_CONTACT && QMPC_RUN_REASON_FIELD == QMPC_LOOP_FIELD,
+              "qmpc_run_pick.h's reason bits are both headers'");
+
+QmpcRunPick run_pick(const qmpc_ctx* c, bool actuators, bool episodes) {
+  const qmpc_ctx::Plant* pl = c->plant.get();
+  return qmpc_run_pick(c->ctrl->ground_run, pl->terrain.rows != nullptr, pl->contact.flags != 0, pl->field.z != nullptr,
+                       actuators, episodes);
+}
+
+// `ticks` ticks under the span's plan through `kernel` (not QMPC_RUN_PER_TICK).  A: the stages' part as the caller
+// filled it (the fleet run: none); the span's block and the ground are filled here.  info: the call's own counts.
+template <class Info>
+int run_fused(qmpc_ctx* c, int batch, int ticks, QmpcRunKernel kernel, QmpcLoopGroundArgs& A, double* effort,
+              double* state, double* motor, Info& info, void* stream_) {
+  const Enqueue q(c, stream_);
+  if (q.rc) return q.rc;
+  qmpc_ctx::Ctrl* k = c->ctrl.get();
+  const qmpc_ctx::Plant* pl = c->plant.get();
+  k->started = true;
+  info.reason = 0;
+  const bool per_robot = k->schedule == QMPC_CTRL_PER_ROBOT;
+  const QmpcPlantStepArgs P = plant_step_args(c, batch, effort, state, motor);
+  A.X.C = k->d;
+  A.X.g = QmpcLegGeom{c->leg_geom[0], c->leg_geom[1], c->leg_geom[2], c->leg_geom[3]};
+  A.X.S = P.S;
+  A.X.K = P.K;
+  A.X.effort = effort;
+  A.X.state = state;
+  A.X.motor = motor;
+  A.X.n = P.n;
+  A.X.V = P.V;
+  A.X.build_list = per_robot ? 1 : 0;
+  A.T = P.T;  // (the flat kernels are given neither)
+  A.Fd = P.Fd;
+  int cur = 0;  // the call's index of the launch's first tick
+  for (const SpanLaunch& l : plan_spans(k->ticks, ticks, per_robot)) {
+    // (a kernel, not a memset node: see fill_ints)
+    if (l.reset_due) HIP_TRY(c, fill_ints(k->d.due_count, 1, 0, q.stream));
+    const int t_mod13 = (int)(k->ticks % 13);
+    switch (kernel) {
+      case QMPC_RUN_SPAN:
+        HIP_TRY(c, qmpc_launch_span(&A.X, k->robot_mode, pl->bound, pl->stats_on, l.first_at_c, l.ticks, l.last_after_l, q.stream));
+        break;
+      case QMPC_RUN_LOOP:
+        HIP_TRY(c, qmpc_launch_loop(&A, k->robot_mode, pl->bound, pl->stats_on, l.first_at_c, l.ticks, l.last_after_l, cur,
+                                    t_mod13, q.stream));
+        break;
+      case QMPC_RUN_LOOP_TERRAIN:
+        HIP_TRY(c, qmpc_launch_loop_terrain(&A, k->robot_mode, pl->bound, pl->stats_on, l.first_at_c, l.ticks,
+                                            l.last_after_l, cur, t_mod13, q.stream));
+        break;
+      case QMPC_RUN_LOOP_FIELD:
+        HIP_TRY(c, qmpc_launch_loop_field(&A, k->robot_mode, pl->bound, pl->stats_on, l.first_at_c, l.ticks,
+                                          l.last_after_l, cur, t_mod13, q.stream));
+        break;
+      default:
+        return QMPC_ERR_STATE;  // (not reached: the caller serves QMPC_RUN_PER_TICK itself)
+    }
+    // T follows the locomotion stages as they are enqueued, in front of the solve that can still fail (ctrl_after_prework)
+    k->ticks += l.locos;
+    info.ticks += l.locos;
+    info.fused_ticks += l.locos;
+    ++info.fused_launches;
+    if (l.solve) {
+      if (const int rc = ctrl_solve_enqueue(c, batch, q.stream)) return rc;
+      cur += l.ticks - 1;
+    }
+  }
+  return QMPC_OK;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------
 // Fleet run (include/qmpc_fleet.h): qmpc_ctrl_tick_state -> qmpc_plant_step, `ticks` times, with everything between two
-// solves in one launch.  The plan is qmpc_span.h's, the kernel qmpc_span.hip's.
+// solves in one launch.  The plan is qmpc_span.h's, the kernel qmpc_span.hip's; on ground (include/qmpc_ground_run.h)
+// qmpc_loop.hip's ground compile with its two stages off.
 extern "C" {
 
 int qmpc_fleet_run(qmpc_handle c, int batch, int ticks, double* effort, double* state, double* motor, void* stream_) {
   if (const int rc = plant_check(c, batch)) return rc;
   if (ticks < 1 || !effort || !state || !motor) return QMPC_ERR_ARG;
   qmpc_ctx::Ctrl* k = c->ctrl.get();
-  qmpc_ctx::Plant* pl = c->plant.get();
-  const int reason = (pl->terrain.rows ? QMPC_FLEET_TERRAIN : 0) | (pl->contact.flags ? QMPC_FLEET_CONTACT : 0) |
-                     (pl->field.z ? QMPC_FLEET_FIELD : 0);
+  const QmpcRunPick pick = run_pick(c, false, false);
   // (the counts follow what has been enqueued: a call refused here, or one that stops half way, counts no tick it did not
   //  enqueue)
-  if (reason) {
-    // what the span kernel does not cover: the per-tick calls themselves, so the launches are theirs exactly
+  if (pick.kernel == QMPC_RUN_PER_TICK) {
+    // what the fused kernels do not cover: the per-tick calls themselves, so the launches are theirs exactly
     for (int i = 0; i < ticks; ++i) {
       if (const int rc = qmpc_ctrl_tick_state(c, batch, state, motor, effort, stream_)) return rc;
-      k->fleet.reason = reason;  // (the call has enqueued something: it is the last call now)
+      k->fleet.reason = pick.reason;  // (the call has enqueued something: it is the last call now)
       if (const int rc = qmpc_plant_step(c, batch, effort, state, motor, stream_)) return rc;
       ++k->fleet.ticks;
       ++k->fleet.fallback_ticks;
     }
     return QMPC_OK;
   }
-  const Enqueue q(c, stream_);
-  if (q.rc) return q.rc;
-  k->started = true;
-  k->fleet.reason = 0;
-  const bool per_robot = k->schedule == QMPC_CTRL_PER_ROBOT;
-  const QmpcPlantStepArgs P = plant_step_args(c, batch, effort, state, motor);
-  QmpcSpanArgs A{};
-  A.C = k->d;
-  A.g = QmpcLegGeom{c->leg_geom[0], c->leg_geom[1], c->leg_geom[2], c->leg_geom[3]};
-  A.S = P.S;
-  A.K = P.K;
-  A.effort = effort;
-  A.state = state;
-  A.motor = motor;
-  A.n = P.n;
-  A.V = P.V;
-  A.build_list = per_robot ? 1 : 0;
-  for (const SpanLaunch& l : plan_spans(k->ticks, ticks, per_robot)) {
-    // (a kernel, not a memset node: see fill_ints)
-    if (l.reset_due) HIP_TRY(c, fill_ints(k->d.due_count, 1, 0, q.stream));
-    HIP_TRY(c, qmpc_launch_span(&A, k->robot_mode, pl->bound, pl->stats_on, l.first_at_c, l.ticks, l.last_after_l, q.stream));
-    // T follows the locomotion stages as they are enqueued, in front of the solve that can still fail (ctrl_after_prework)
-    k->ticks += l.locos;
-    k->fleet.ticks += l.locos;
-    k->fleet.fused_ticks += l.locos;
-    ++k->fleet.fused_launches;
-    if (l.solve)
-      if (const int rc = ctrl_solve_enqueue(c, batch, q.stream)) return rc;
-  }
-  return QMPC_OK;
+  QmpcLoopGroundArgs A{};
+  return run_fused(c, batch, ticks, pick.kernel, A, effort, state, motor, k->fleet, stream_);
 }
 
 int qmpc_fleet_run_info(qmpc_handle c, qmpc_fleet_info* out) {
@@ -374,43 +429,7 @@ int qmpc_loop_run(qmpc_handle c, int batch, int ticks, const qmpc_loop_opts* o, 
     // the plant's reset writes its own read-out rows only: the loop would carry on from stale caller rows
     if (state != pl->d.state || motor != pl->d.motor) return QMPC_ERR_ARG;
   }
-  const int reason = (pl->terrain.rows ? QMPC_LOOP_TERRAIN : 0) | (pl->contact.flags ? QMPC_LOOP_CONTACT : 0) |
-                     (pl->field.z ? QMPC_LOOP_FIELD : 0);
-  if (reason) {
-    // what the loop kernel does not cover: the per-tick calls themselves, so the launches are theirs exactly
-    for (int i = 0; i < ticks; ++i) {
-      if (const int rc = qmpc_ctrl_tick_state(c, batch, state, motor, effort, stream_)) return rc;
-      k->loop.reason = reason;  // (the call has enqueued something: it is the last call now)
-      if (act)
-        if (const int rc = qmpc_act(c, batch, effort, effort, stream_)) return rc;
-      if (const int rc = qmpc_plant_step(c, batch, effort, state, motor, stream_)) return rc;
-      ++k->loop.ticks;
-      ++k->loop.fallback_ticks;
-      if (every && (i + 1) % every == 0) {
-        if (const int rc = qmpc_episode_step(c, batch, every, stream_)) return rc;
-        if (act)
-          if (const int rc = qmpc_act_reset(c, batch, c->episode->d.mask, nullptr, o->actuator_stats, stream_)) return rc;
-      }
-    }
-    return QMPC_OK;
-  }
-  const Enqueue q(c, stream_);
-  if (q.rc) return q.rc;
-  k->started = true;
-  k->loop.reason = 0;
-  const bool per_robot = k->schedule == QMPC_CTRL_PER_ROBOT;
-  const QmpcPlantStepArgs P = plant_step_args(c, batch, effort, state, motor);
-  QmpcLoopArgs A{};
-  A.X.C = k->d;
-  A.X.g = QmpcLegGeom{c->leg_geom[0], c->leg_geom[1], c->leg_geom[2], c->leg_geom[3]};
-  A.X.S = P.S;
-  A.X.K = P.K;
-  A.X.effort = effort;
-  A.X.state = state;
-  A.X.motor = motor;
-  A.X.n = P.n;
-  A.X.V = P.V;
-  A.X.build_list = per_robot ? 1 : 0;
+  QmpcLoopGroundArgs A{};
   if (act) {
     A.A = c->act->a;
     A.A.motor = pl->d.motor;
@@ -427,33 +446,53 @@ int qmpc_loop_run(qmpc_handle c, int batch, int ticks, const qmpc_loop_opts* o, 
     A.R = e->rule;
     A.Bd = e->bind;
   }
-  const bool plain = !A.act && !A.every;  // nothing of this header's in the launch: the span kernel itself
-  int cur = 0;                            // the call's index of the launch's first tick
-  for (const SpanLaunch& l : plan_spans(k->ticks, ticks, per_robot)) {
-    // (a kernel, not a memset node: see fill_ints)
-    if (l.reset_due) HIP_TRY(c, fill_ints(k->d.due_count, 1, 0, q.stream));
-    if (plain)
-      HIP_TRY(c, qmpc_launch_span(&A.X, k->robot_mode, pl->bound, pl->stats_on, l.first_at_c, l.ticks, l.last_after_l, q.stream));
-    else
-      HIP_TRY(c, qmpc_launch_loop(&A, k->robot_mode, pl->bound, pl->stats_on, l.first_at_c, l.ticks, l.last_after_l, cur,
-                                  (int)(k->ticks % 13), q.stream));
-    // T follows the locomotion stages as they are enqueued, in front of the solve that can still fail (ctrl_after_prework)
-    k->ticks += l.locos;
-    k->loop.ticks += l.locos;
-    k->loop.fused_ticks += l.locos;
-    ++k->loop.fused_launches;
-    if (l.solve) {
-      if (const int rc = ctrl_solve_enqueue(c, batch, q.stream)) return rc;
-      cur += l.ticks - 1;
+  // (neither stage in the launch: nothing of this header's, the span kernel itself on the flat plant)
+  const QmpcRunPick pick = run_pick(c, A.act != 0, A.every != 0);
+  if (pick.kernel == QMPC_RUN_PER_TICK) {
+    // what the fused kernels do not cover: the per-tick calls themselves, so the launches are theirs exactly
+    for (int i = 0; i < ticks; ++i) {
+      if (const int rc = qmpc_ctrl_tick_state(c, batch, state, motor, effort, stream_)) return rc;
+      k->loop.reason = pick.reason;  // (the call has enqueued something: it is the last call now)
+      if (act)
+        if (const int rc = qmpc_act(c, batch, effort, effort, stream_)) return rc;
+      if (const int rc = qmpc_plant_step(c, batch, effort, state, motor, stream_)) return rc;
+      ++k->loop.ticks;
+      ++k->loop.fallback_ticks;
+      if (every && (i + 1) % every == 0) {
+        if (const int rc = qmpc_episode_step(c, batch, every, stream_)) return rc;
+        if (act)
+          if (const int rc = qmpc_act_reset(c, batch, c->episode->d.mask, nullptr, o->actuator_stats, stream_)) return rc;
+      }
     }
+    return QMPC_OK;
   }
-  return QMPC_OK;
+  return run_fused(c, batch, ticks, pick.kernel, A, effort, state, motor, k->loop, stream_);
 }
 
 int qmpc_loop_run_info(qmpc_handle c, qmpc_loop_info* out) {
   if (!c || !out) return QMPC_ERR_ARG;
   if (!ctrl_ready(c)) return QMPC_ERR_STATE;
   *out = c->ctrl->loop;
+  return QMPC_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
+// The switch of include/qmpc_ground_run.h: host state only, read by the next run call.
+extern "C" {
+
+int qmpc_ground_run_enable(qmpc_handle c, int on) {
+  if (!c) return QMPC_ERR_ARG;
+  if (!ctrl_ready(c)) return QMPC_ERR_STATE;
+  c->ctrl->ground_run = on != 0;
+  return QMPC_OK;
+}
+
+int qmpc_ground_run_enabled(qmpc_handle c, int* on) {
+  if (!c || !on) return QMPC_ERR_ARG;
+  if (!ctrl_ready(c)) return QMPC_ERR_STATE;
+  *on = c->ctrl->ground_run ? 1 : 0;
   return QMPC_OK;
 }
 

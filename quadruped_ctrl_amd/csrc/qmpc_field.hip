@@ -15,8 +15,9 @@
 
 namespace {
 
-// qmpc_plant_reset while a field is bound (mask == NULL: every robot): qmpc_terrain_init_kernel on the summed surface.
-// T.rows may be null (the field alone).  Every lane computes (the shuffles need their partners); masked ones store.
+// qmpc_plant_reset while a field is bound (mask == NULL: every robot): qmpc_terrain_init_kernel on the summed surface,
+// qmpc_plant_dev.h's plant_ground_init_lane with FIELD.  T.rows may be null (the field alone).  Every lane computes (the
+// shuffles need their partners); masked ones store.
 __global__ __launch_bounds__(256) void qmpc_field_init_kernel(const QmpcPlantDev S, const QmpcPlantConst K,
                                                               const uint8_t* __restrict__ mask,
                                                               const double* __restrict__ xyyaw, const int n,
@@ -25,40 +26,12 @@ __global__ __launch_bounds__(256) void qmpc_field_init_kernel(const QmpcPlantDev
   const int t = blockIdx.x * 256 + threadIdx.x;
   const bool in = t < n;
   const int tt = in ? t : n - 1;
-  const int b = tt >> 2, leg = tt & 3;
+  const int b = tt >> 2;
   const bool live = in && (!mask || mask[b]);
   const double x0 = xyyaw ? xyyaw[(size_t)b * 3] : 0.0, y0 = xyyaw ? xyyaw[(size_t)b * 3 + 1] : 0.0;
   const double yaw = xyyaw ? xyyaw[(size_t)b * 3 + 2] : 0.0;
-  PlantGround G;
-  PlantField Fl;
-  if (T.rows)
-    plant_ground_load(T.rows + (size_t)b * 8, T.flags, G);
-  else
-    plant_ground_flat(G);
-  G.flags = T.flags;
-  plant_field_load(Fd, b, Fl);
-  const double ground = plant_field_height(G, Fl, x0, y0);
-  const double p[3] = {x0, y0, QMPC_PLANT_HEIGHT + ground}, v[3] = {0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
   const double q[4] = {cos(yaw / 2), 0.0, 0.0, sin(yaw / 2)};
-  const double side = (leg & 1) ? 1.0 : -1.0;
-  double hip[3], R[9], fw[3];
-  plant_hip(leg, hip);
-  plant_rot(q, R);
-  const double fb[3] = {hip[0], hip[1] + side * QMPC_PLANT_SIDE_OFFSET, -QMPC_PLANT_HEIGHT};
-  plant_mul(R, fb, fw);
-  double c[3] = {p[0] + fw[0], p[1] + fw[1], 0.0};
-  c[2] = plant_field_height(G, Fl, c[0], c[1]);
-  G.support = plant_quad_sum(c[2]) / 4.0;
-  if (live) {
-    for (int k = 0; k < 3; ++k) S.grf[(size_t)tt * 3 + k] = 0.0;
-    S.stance[tt] = 1;
-    if (leg == 0) {
-      T.support[b] = G.support;
-      T.ground[b] = ground;
-    }
-  }
-  plant_readout<true, true>(S, K, tt, live, p, v, q, w, c, true, v /* vdot = 0 */, nullptr, nullptr, nullptr, nullptr, G,
-                            Fl);
+  plant_ground_init_lane<true>(S, K, T, Fd, x0, y0, q, tt, live);
 }
 
 // One control period with scheduled contact on the summed surface: qmpc_plant_step_body.h with TERRAIN = FIELD = true

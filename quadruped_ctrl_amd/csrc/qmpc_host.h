@@ -1,6 +1,7 @@
 // qmpc_host.h -- what the host-side translation units of the C ABI share (host only, not installed):
 //   qmpc_capi.cpp         the handle and the solve (qmpc.h, qmpc_expert.h, qmpc_debug.h)
-//   qmpc_capi_ctrl.cpp    the batched controller, the fleet run and the loop run (qmpc_ctrl.h, qmpc_fleet.h, qmpc_loop.h)
+//   qmpc_capi_ctrl.cpp    the batched controller, the fleet run and the loop run (qmpc_ctrl.h, qmpc_fleet.h, qmpc_loop.h,
+//                         qmpc_ground_run.h)
 //   qmpc_capi_plant.cpp   the plant and its extensions (qmpc_plant.h, qmpc_plant_vary.h, qmpc_terrain.h, qmpc_contact.h,
 //                         qmpc_field.h)
 //   qmpc_capi_stages.cpp  sensors, actuators, episodes (qmpc_sense.h, qmpc_act.h, qmpc_episode.h, qmpc_episode_sense.h)
@@ -152,6 +153,7 @@ struct __attribute__((visibility("hidden"))) qmpc_ctx {
     double freq = 0;                    // qmpc_ctrl_init's: the plant's dt is 1 / freq in double
     qmpc_fleet_info fleet{};            // how qmpc_fleet_run's ticks were served since qmpc_ctrl_init (qmpc_fleet.h)
     qmpc_loop_info loop{};              // ... and qmpc_loop_run's (qmpc_loop.h)
+    bool ground_run = false;            // qmpc_ground_run_enable: both run calls serve rows and a field fused
   };
   std::unique_ptr<Ctrl> ctrl;
   // reduced-order plant (qmpc_plant.h): device state for max_batch robots, made by qmpc_plant_init

@@ -28,10 +28,26 @@ struct QmpcLoopArgs {
   qmpc_episode_bind Bd;
 };
 
+// The block of the kernel's ground compiles (qmpc_loop.hip with -DQMPC_LOOP_GROUND=1: terrain rows, =2: a height-field
+// bank; include/qmpc_ground_run.h): the ground travels BEHIND the flat block, so the default compile's kernarg segment
+// is the flat block alone, as it always was.  T.rows may be null under a bank (qmpc_field.hip).
+struct QmpcLoopGroundArgs : QmpcLoopArgs {
+  QmpcTerrainArgs T;  // the plant's ground(): rows as bound, ground[], support[], both bindings' flags
+  QmpcFieldArgs Fd;   // the bank and the placement rows (QMPC_LOOP_GROUND == 1 reads none of it)
+};
+
 // robot_mode, vary, stats, first_at_c, ticks, last_after_l: as qmpc_launch_span.  tick0: the call's index of the launch's
 // first tick (which ticks are check ticks); t_mod13: the controller's T modulo 13 when the launch is enqueued (lockstep:
 // a reset robot's counter restarts at T mod 13 of ITS tick; the kernel counts its L stages on top).
 extern "C" hipError_t qmpc_launch_loop(const QmpcLoopArgs* A, int robot_mode, int vary, int stats, int first_at_c,
                                        int ticks, int last_after_l, int tick0, int t_mod13, hipStream_t stream);
+// ... and of the two ground compiles: the same file, the launcher's name by its define.  With act = every = 0 these serve
+// the fleet run on ground: there is no ground compile of the span kernel.
+extern "C" hipError_t qmpc_launch_loop_terrain(const QmpcLoopGroundArgs* A, int robot_mode, int vary, int stats,
+                                               int first_at_c, int ticks, int last_after_l, int tick0, int t_mod13,
+                                               hipStream_t stream);
+extern "C" hipError_t qmpc_launch_loop_field(const QmpcLoopGroundArgs* A, int robot_mode, int vary, int stats,
+                                             int first_at_c, int ticks, int last_after_l, int tick0, int t_mod13,
+                                             hipStream_t stream);
 
 #endif

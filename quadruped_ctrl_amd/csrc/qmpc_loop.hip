@@ -33,11 +33,34 @@
 //
 // A and R are run-time switches, uniform over the grid: as template arguments they would make 24 more instantiations of
 // a kernel that takes 10 s to compile, for stages that are short beside L and P.
+//
+// The ground is a compile-time switch of the FILE (include/qmpc_ground_run.h): the build compiles it three times, as
+// qmpc_kernels.hip is compiled once per size class.  QMPC_LOOP_GROUND undefined or 0 is the flat plant, P with TERRAIN =
+// FIELD = false and empty T / Fd; 1 is terrain rows (TERRAIN); 2 a height-field bank on any rows (TERRAIN and FIELD,
+// T.rows may be null).  The ground compiles take the ground behind the flat block (qmpc_loop.h: QmpcLoopGroundArgs), their
+// launcher has its own name, and their stage R stands a reset robot on its ground with the init kernels' own text
+// (qmpc_plant_dev.h).  With A and R off they are the fleet run's kernels on ground.
 #include "qmpc_plant_dev.h"
 #include "qmpc_ctrl_stages.h"
 #include "qmpc_act_model.h"
 #include "qmpc_episode_rule.h"
 #include "qmpc_loop.h"
+
+#ifndef QMPC_LOOP_GROUND
+#define QMPC_LOOP_GROUND 0
+#endif
+#if QMPC_LOOP_GROUND == 0
+#define QMPC_LOOP_LAUNCHER qmpc_launch_loop
+typedef QmpcLoopArgs LoopArgs;
+#elif QMPC_LOOP_GROUND == 1
+#define QMPC_LOOP_LAUNCHER qmpc_launch_loop_terrain
+typedef QmpcLoopGroundArgs LoopArgs;
+#elif QMPC_LOOP_GROUND == 2
+#define QMPC_LOOP_LAUNCHER qmpc_launch_loop_field
+typedef QmpcLoopGroundArgs LoopArgs;
+#else
+#error "QMPC_LOOP_GROUND: 0 (flat), 1 (terrain rows) or 2 (height field)"
+#endif
 
 // Lanes per workgroup: the span's choice
 #ifndef QMPC_LOOP_WG
@@ -123,20 +146,22 @@ __device__ __forceinline__ void qmpc_loop_act_body(const QmpcActArgs& A, double*
 // R, which writes some seventy arrays, reads it through a pointer in a VECTOR register: the array pointers then come by
 // vector loads, into the registers the stores address with, and take no scalar register at all.
 #define QMPC_LOOP_ARGS_AGAIN(name, reg)                                             \
-  typedef const __attribute__((address_space(4))) QmpcLoopArgs* KernargPtr_##name;  \
+  typedef const __attribute__((address_space(4))) LoopArgs* KernargPtr_##name;      \
   KernargPtr_##name again_##name = (KernargPtr_##name)__builtin_amdgcn_kernarg_segment_ptr(); \
   asm volatile("" : reg(again_##name));                                             \
-  const QmpcLoopArgs& name = *(const QmpcLoopArgs*)again_##name
+  const LoopArgs& name = *(const LoopArgs*)again_##name
 
 template <int MODE, bool VARY, bool STATS>
-__global__ __launch_bounds__(QMPC_LOOP_WG) void qmpc_loop_kernel(const QmpcLoopArgs W, const int first_at_c,
-                                                                 const int ticks, const int last_after_l,
-                                                                 const int tick0, const int t_mod13) {
+__global__ __launch_bounds__(QMPC_LOOP_WG) void qmpc_loop_kernel(const LoopArgs W, const int first_at_c, const int ticks,
+                                                                 const int last_after_l, const int tick0,
+                                                                 const int t_mod13) {
 #pragma clang fp contract(off)
-  constexpr bool TERRAIN = false;
+  constexpr bool TERRAIN = QMPC_LOOP_GROUND >= 1;
+  constexpr bool FIELD = QMPC_LOOP_GROUND == 2;
+#if !QMPC_LOOP_GROUND
   const QmpcTerrainArgs T{};
-  constexpr bool FIELD = false;
   const QmpcFieldArgs Fd{};
+#endif
   // the span's names (qmpc_span.hip)
   const QmpcCtrlDev& Cd = W.X.C;
   const QmpcLegGeom& g = W.X.g;
@@ -183,6 +208,12 @@ __global__ __launch_bounds__(QMPC_LOOP_WG) void qmpc_loop_kernel(const QmpcLoopA
     }
     __syncthreads();
     {
+#if QMPC_LOOP_GROUND
+      // (the ground's pointers are read again too: nothing of T or Fd is carried around the tick loop)
+      QMPC_LOOP_ARGS_AGAIN(Wp, "+s");
+      const QmpcTerrainArgs& T = Wp.T;
+      const QmpcFieldArgs& Fd = Wp.Fd;
+#endif
 #include "qmpc_plant_step_body.h"
     }
     __syncthreads();
@@ -216,11 +247,16 @@ __global__ __launch_bounds__(QMPC_LOOP_WG) void qmpc_loop_kernel(const QmpcLoopA
           }
           qmpc_ctrl_set_robot(Wr.X.C, Wr.Bd.gait, Wr.Bd.vel, robot_r);
         }
-        if (hit) {  // (the flat plant's reset kernel: the robot's row of the manager's xyyaw)
+        if (hit) {  // (the plant's reset kernel on this ground: the robot's row of the manager's xyyaw)
           const double* row = Wr.E.xyyaw + (size_t)robot_r * 3;
           const double yaw = row[2];
           const double q[4] = {cos(yaw / 2), 0.0, 0.0, sin(yaw / 2)};
+#if QMPC_LOOP_GROUND
+          // (hit is the robot's: a quad is in here whole, so the reset's shuffles have their partners)
+          plant_ground_init_lane<FIELD>(Wr.X.S, Wr.X.K, Wr.T, Wr.Fd, row[0], row[1], q, lane_r, true);
+#else
           plant_init_lane(Wr.X.S, Wr.X.K, row[0], row[1], q, lane_r);
+#endif
         }
         if constexpr (STATS) {
           if (hit && leg0) plant_stats_reset_robot(Wr.X.V, robot_r);
@@ -234,7 +270,7 @@ __global__ __launch_bounds__(QMPC_LOOP_WG) void qmpc_loop_kernel(const QmpcLoopA
 #undef QMPC_LOOP_ARGS_AGAIN
 
 template <int MODE>
-hipError_t launch_mode(const QmpcLoopArgs* A, int vary, int stats, int first_at_c, int ticks, int last_after_l, int tick0,
+hipError_t launch_mode(const LoopArgs* A, int vary, int stats, int first_at_c, int ticks, int last_after_l, int tick0,
                        int t_mod13, hipStream_t stream) {
   plant_vary_stats(vary, stats, [&](auto VARY, auto STATS) {
     hipLaunchKernelGGL((qmpc_loop_kernel<MODE, VARY.value, STATS.value>), dim3((A->X.n + QMPC_LOOP_WG - 1) / QMPC_LOOP_WG),
@@ -245,8 +281,8 @@ hipError_t launch_mode(const QmpcLoopArgs* A, int vary, int stats, int first_at_
 
 }  // namespace
 
-extern "C" hipError_t qmpc_launch_loop(const QmpcLoopArgs* A, int robot_mode, int vary, int stats, int first_at_c,
-                                       int ticks, int last_after_l, int tick0, int t_mod13, hipStream_t stream) {
+extern "C" hipError_t QMPC_LOOP_LAUNCHER(const LoopArgs* A, int robot_mode, int vary, int stats, int first_at_c,
+                                         int ticks, int last_after_l, int tick0, int t_mod13, hipStream_t stream) {
   return robot_mode == 1 ? launch_mode<1>(A, vary, stats, first_at_c, ticks, last_after_l, tick0, t_mod13, stream)
                          : launch_mode<0>(A, vary, stats, first_at_c, ticks, last_after_l, tick0, t_mod13, stream);
 }

@@ -378,6 +378,54 @@ __device__ __forceinline__ void plant_init_lane(const QmpcPlantDev& S, const Qmp
                        flat);
 }
 
+// qmpc_plant_reset of lane tt = robot * 4 + leg while terrain rows (FIELD false) or a height-field bank (FIELD true;
+// T.rows may be null: the field alone) are bound.  The body stands level at (x0, y0, 0.29 + height(x0, y0)) under the
+// yaw, every foot at its usual body-frame xy on the surface; support is the mean of the four feet, (c_0 + c_1) +
+// (c_2 + c_3) over 4, so EVERY lane of a quad calls this (the shuffles need their partners) and `live` says whether the
+// lane stores; the leg-0 lane writes support[b] and ground[b].  q: the yaw as a quaternion, built by the caller from its
+// xyyaw row, as for plant_init_lane.  One text behind the init kernels of qmpc_terrain.hip and
+// qmpc_field.hip and the reset stage of qmpc_loop.hip on ground.
+template <bool FIELD>
+__device__ __forceinline__ void plant_ground_init_lane(const QmpcPlantDev& S, const QmpcPlantConst& K,
+                                                       const QmpcTerrainArgs& T, const QmpcFieldArgs& Fd, const double x0,
+                                                       const double y0, const double* q, const int tt, const bool live) {
+#pragma clang fp contract(off)
+  const int b = tt >> 2, leg = tt & 3;
+  PlantGround G;
+  PlantField Fl{};
+  if constexpr (FIELD) {
+    if (T.rows)
+      plant_ground_load(T.rows + (size_t)b * 8, T.flags, G);
+    else
+      plant_ground_flat(G);
+    G.flags = T.flags;
+    plant_field_load(Fd, b, Fl);
+  } else {
+    plant_ground_load(T.rows + (size_t)b * 8, T.flags, G);
+  }
+  const double ground = plant_surface<FIELD>(G, Fl, x0, y0);
+  const double p[3] = {x0, y0, QMPC_PLANT_HEIGHT + ground}, v[3] = {0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
+  const double side = (leg & 1) ? 1.0 : -1.0;
+  double hip[3], R[9], fw[3];
+  plant_hip(leg, hip);
+  plant_rot(q, R);
+  const double fb[3] = {hip[0], hip[1] + side * QMPC_PLANT_SIDE_OFFSET, -QMPC_PLANT_HEIGHT};
+  plant_mul(R, fb, fw);
+  double c[3] = {p[0] + fw[0], p[1] + fw[1], 0.0};
+  c[2] = plant_surface<FIELD>(G, Fl, c[0], c[1]);
+  G.support = plant_quad_sum(c[2]) / 4.0;
+  if (live) {
+    for (int k = 0; k < 3; ++k) S.grf[(size_t)tt * 3 + k] = 0.0;
+    S.stance[tt] = 1;
+    if (leg == 0) {
+      T.support[b] = G.support;
+      T.ground[b] = ground;
+    }
+  }
+  plant_readout<true, FIELD>(S, K, tt, live, p, v, q, w, c, true, v /* vdot = 0 */, nullptr, nullptr, nullptr, nullptr, G,
+                             Fl);
+}
+
 // qmpc_plant_stats_reset of robot b: the accumulators as qmpc_plant_stats_enable leaves them
 __device__ __forceinline__ void plant_stats_reset_robot(const QmpcPlantVary& V, const int b) {
   double* a = V.acc + b;

@@ -75,11 +75,15 @@ With --actuators [--delay D] and / or --episodes [--every K], --fused routes the
 (include/qmpc_loop.h: the actuator stage and the episode step inside the same launch) and --graph alone through
 rollout_episodes() / rollout() with the actuators, in the same block windows; with --every K > 1 only the whole 13-tick
 blocks are timed (K must divide 13: a block ends on a check tick).
+--ground-run (with --fused, and --terrain and / or --field) turns the handle's switch of include/qmpc_ground_run.h on: both
+run calls then serve the bound ground through the fused launch instead of falling back to the per-tick launches.  The
+result carries the info struct's counts (fleet_info / loop_info: fused_ticks, fallback_ticks, reason) and the flags, so a
+fallback cannot pass for a fused run: without the switch `--fused --terrain` times the fallback.
 
     python tools/ctrl_bench.py [--batches 1024,4096,16384] [--cycles 8] [--warmup 26] [--schedule lockstep|per_robot]
                                [--stagger] [--robot-mode 0|1] [--source imu|state|plant|sensor] [--vary] [--terrain] [--contact] [--field]
                                [--noise] [--episodes] [--every K] [--warm W] [--actuators] [--delay D] [--repeats R]
-                               [--fused] [--graph] [--out FILE]
+                               [--fused] [--ground-run] [--graph] [--out FILE]
 """
 import argparse
 import json
@@ -92,7 +96,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def run_blocks(ctrl, plant, B, cycles, warmup, schedule, stagger, robot_mode, fused, graph, acts=None, manager=None, every=1):
+def run_blocks(ctrl, plant, B, cycles, warmup, schedule, stagger, robot_mode, fused, graph, acts=None, manager=None, every=1,
+               tags=None):
     """--source plant with --fused and / or --graph: the closed loop timed in BLOCKS of ticks (HIP events around rollout()
     calls), because a fused span has no event between its ticks.  The windows are the per-tick report's, cut at the same
     places: in lockstep, per 13-tick period, the twelve ticks without a solve in one block (us_per_nonmpc_period: block /
@@ -121,6 +126,7 @@ def run_blocks(ctrl, plant, B, cycles, warmup, schedule, stagger, robot_mode, fu
     lockstep = schedule == "lockstep" and not stagger and robot_mode == 0
     res = {"batch": B, "source": "plant", "schedule": schedule, "stagger": bool(stagger), "robot_mode": robot_mode,
            "fused": bool(fused), "cycles_timed": cycles}
+    res.update(tags or {})   # (what is bound under the plant and the ground-run switch, as the caller set them)
     if longer:
         res.update({"actuators": acts is not None, "episodes": manager is not None, "every": every})
     if lockstep and every == 1:
@@ -172,7 +178,7 @@ def run_blocks(ctrl, plant, B, cycles, warmup, schedule, stagger, robot_mode, fu
 
 def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, source="imu", vary=False, noise=False, terrain=False,
         contact=False, field=False, episodes=False, every=1, warm=50, actuators=False, delay=0, repeats=3, fused=False,
-        graph=False):
+        graph=False, ground_run=False):
     import torch
     from quadruped_ctrl_amd import workloads as W
     from quadruped_ctrl_amd.binding import BatchedController
@@ -299,8 +305,12 @@ def run(B, cycles, warmup, schedule="lockstep", stagger=False, robot_mode=0, sou
                 plant.step(eff)
             if sensors is not None:
                 sensors.sense()
+    if ground_run:
+        ctrl.set_ground_run()
     if fused or graph:
-        return run_blocks(ctrl, plant, B, cycles, warmup, schedule, stagger, robot_mode, fused, graph, acts, manager, every)
+        tags = {"vary": bool(vary), "terrain": bool(terrain), "contact": bool(contact), "field": bool(field),
+                "ground_run": ctrl.ground_run}
+        return run_blocks(ctrl, plant, B, cycles, warmup, schedule, stagger, robot_mode, fused, graph, acts, manager, every, tags)
     held_seen = []
 
     hold_flags = sensed.view()["hold"] if sensed is not None else None
@@ -466,11 +476,14 @@ def main():
     ap.add_argument("--delay", type=int, default=0)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--fused", action="store_true")
+    ap.add_argument("--ground-run", action="store_true")
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if (a.fused or a.graph) and a.source != "plant":
         ap.error("--fused and --graph go with --source plant")
+    if a.ground_run and not (a.fused and (a.terrain or a.field)):
+        ap.error("--ground-run goes with --fused and --terrain and / or --field")
     if (a.fused or a.graph) and a.episodes and 13 % a.every:
         ap.error("--fused / --graph with --episodes: --every K must divide 13 (the blocks are 13 ticks)")
     if a.vary and a.source not in ("plant", "sensor"):
@@ -500,7 +513,7 @@ def main():
     out = []
     for B in [int(x) for x in a.batches.split(",")]:
         r = run(B, a.cycles, a.warmup, a.schedule, a.stagger, a.robot_mode, a.source, a.vary, a.noise, a.terrain, a.contact, a.field,
-                a.episodes, a.every, a.warm, a.actuators, a.delay, a.repeats, a.fused, a.graph)
+                a.episodes, a.every, a.warm, a.actuators, a.delay, a.repeats, a.fused, a.graph, a.ground_run)
         print(json.dumps(r), flush=True)
         out.append(r)
     if a.out:
